@@ -68,7 +68,7 @@ static int dmalloc_bytes(void **p, size_t bytes)
     return PRE3_OK;
 }
 
-static int check_ctx(pre3_ctx *c)
+static int complete_deferred_hi(pre3_ctx *c)
 {
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
     PRE3_HIP(hipSetDevice(c->device));
@@ -77,9 +77,27 @@ static int check_ctx(pre3_ctx *c)
         PRE3_TRY(pre3_update_hi(c));
         c->last_n_hi = c->hi_from_host >= 0 ? c->hi_from_host : (c->hi_kernel ? c->mail_host[5] : 0);
     }
-    // PRE3_OPT_PEND_HI: only pre3_step carries a pending HI down-date into its launches (pend_keep); for everybody else P is P before the call goes on
+    return PRE3_OK;
+}
+// PRE3_OPT_PEND_HI: only pre3_step carries a pending HI down-date into its launches (pend_keep); for everybody else P is P before the call goes on.
+// The marginal readers (pre3_get_landmarks / pre3_get_marginal) complete a deferred HI update as pre3_step would and leave its rows/cols 3..6 pass
+// pending for the next prediction's launch, as pre3_step would: whoever else comes next runs that pass first (k_jnorm_P, behind the flush it makes).
+int flush_unless_kept(pre3_ctx *c)
+{
+    if (c->jn_pending && !c->leave_jn_to_predict) { c->jn_pending = false; PRE3_TRY(launch_jnorm(c, 0)); }
     if (c->pend_rows > 0 && !c->pend_keep) PRE3_TRY(pend_flush(c));
     return PRE3_OK;
+}
+static int check_ctx(pre3_ctx *c)
+{
+    PRE3_TRY(complete_deferred_hi(c));
+    return flush_unless_kept(c);
+}
+// PRE3_FUSE_JN (default 1): the rows/cols 3..6 pass of a HI update completed at the start of a step rides in that step's prediction launch
+static bool fuse_jn_env()
+{
+    static const int v = getenv("PRE3_FUSE_JN") ? atoi(getenv("PRE3_FUSE_JN")) : 1;
+    return v != 0;
 }
 
 // Poll the pinned mailbox until the kernel that was launched with sequence number `seq` has published.
@@ -141,13 +159,18 @@ static int wait_mail(pre3_ctx *c, int slot, int32_t seq)
     return PRE3_OK;
 }
 
+// the device's error words, once a copy of them into pinned_stats has completed
+static int stats_words(pre3_ctx *c)
+{
+    PRE3_CHECK(c->pinned_stats[7] == 0, PRE3_E_HIP, "a device-side wait on another workgroup gave up (counter never arrived): results are invalid");
+    PRE3_CHECK(c->pinned_stats[6] == 0, PRE3_E_NUMERIC, "innovation covariance S is not positive definite");
+    return PRE3_OK;
+}
 static int fetch_stats(pre3_ctx *c)
 {
     PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
     PRE3_TRY(stream_drain(c, __func__));
-    PRE3_CHECK(c->pinned_stats[7] == 0, PRE3_E_HIP, "a device-side wait on another workgroup gave up (counter never arrived): results are invalid");
-    PRE3_CHECK(c->pinned_stats[6] == 0, PRE3_E_NUMERIC, "innovation covariance S is not positive definite");
-    return PRE3_OK;
+    return stats_words(c);
 }
 
 // the staged scan [descriptors | positions] out of pinned host memory into the two device arrays (n16_pos == 0: one array)
@@ -465,6 +488,7 @@ int pre3_destroy(pre3_ctx *c)
                      c->inbox_dev, c->row_col, c->row_val, c->row_nu, c->HP, c->W, c->G, c->Smat, c->Rdense,
                      c->sel_rows, c->support, c->stats, c->pred_params, c->tiles, c->tile_ctr, c->tile_cnt, c->tiles_flat, c->P_alt, c->x_alt, c->map_col, c->map_val, c->map_desc, c->map_src0, c->map_conv, c->map_feat, c->map_flags, c->bank, c->bank_alt, c->scan_desc, c->scan_pos, c->ic_pred, c->ic_counts, c->ic_arg, c->ic_newk2, c->ic_best, c->ic_second, c->bank_src, c->chol_arrive, c->ic_pb, c->ic_ps, c->ic_pa, c->Wp, c->Sp, c->tiles128, c->need, c->cholp_flags, c->cholp_tp, c->dd_groups, c->dd_tiles, c->tail_yp, c->tail_hb, c->tail_hib, c->tail_wt, c->jn_q, c->W_pend, c->Wp_pend, c->hf_xy, c->hf_sx };
     for (void *b : bufs) if (b) (void)hipFree(b);
+    free_readers(c);
     for (int k2 = 0; k2 < 2; ++k2) { if (c->map_stage[k2]) (void)hipHostFree(c->map_stage[k2]); if (c->map_stage_ev[k2]) (void)hipEventDestroy(c->map_stage_ev[k2]); }
     for (int k2 = 0; k2 < 2; ++k2) { if (c->up_stage[k2]) (void)hipHostFree(c->up_stage[k2]); if (c->up_stage_ev[k2]) (void)hipEventDestroy(c->up_stage_ev[k2]); }
     if (c->pinned_stats) (void)hipHostFree(c->pinned_stats);
@@ -620,6 +644,58 @@ int pre3_get_state(pre3_ctx *c, int which, int n, double *x, double *P)
         }
     }
     return PRE3_OK;
+}
+
+// The checks every marginal reader makes on the host before anything is launched
+static int reader_precheck(pre3_ctx *c, int which, const char *who)
+{
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_CHECK(which == PRE3_X_K_K || which == PRE3_X_K_KM1, PRE3_E_ARG, "%s: bad selector", who);
+    PRE3_CHECK(c->x_valid[which], PRE3_E_STATE, "%s: that estimate has not been computed", who);
+    PRE3_CHECK(c->p_which == which, PRE3_E_STATE, "%s: the covariance buffer currently holds the other estimate (it is updated in place)", who);
+    return PRE3_OK;
+}
+// A deferred HI update is completed as pre3_step would complete it (its rows/cols 3..6 pass left to the next prediction's launch), and nothing
+// pending is flushed: the filter's next step runs exactly as it would have without the read.  Returns the pending pass's Jn on the device, or null.
+static int reader_settle(pre3_ctx *c, const double **jn)
+{
+    c->leave_jn_to_predict = fuse_jn_env() && c->hi_pending;
+    const int rc = complete_deferred_hi(c);
+    c->leave_jn_to_predict = false;
+    if (rc != PRE3_OK) { if (c->jn_pending) { c->jn_pending = false; (void)launch_jnorm(c, 0); } return rc; }
+    // fetch_stats with the reader's own synchronisation: the error words leave in front of the gather, and are checked once the stream has drained
+    PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
+    *jn = c->jn_pending ? c->pred_params + 16 : nullptr;           // (k_jnorm_P's Jn: params[16..31])
+    return PRE3_OK;
+}
+static int reader_finish(pre3_ctx *c, int rc)
+{
+    PRE3_TRY(rc);
+    PRE3_TRY(stream_drain(c, __func__));
+    return stats_words(c);
+}
+
+int pre3_get_landmarks(pre3_ctx *c, int which, int first, int count, double *xyz, double *cov_xyz, double *cov_native, double *linearity)
+{
+    PRE3_TRY(reader_precheck(c, which, "pre3_get_landmarks"));
+    PRE3_CHECK(first >= 0 && count >= 0 && (long long)first + count <= c->N, PRE3_E_ARG, "pre3_get_landmarks: landmarks %d .. %d outside the map (N=%d)", first, first + count - 1, c->N);
+    PRE3_HIP(hipSetDevice(c->device));
+    const double *jn = nullptr;
+    PRE3_TRY(reader_settle(c, &jn));
+    return reader_finish(c, c->N == 0 ? PRE3_OK : read_landmarks(c, which, first, count, xyz, cov_xyz, cov_native, linearity));
+}
+
+int pre3_get_marginal(pre3_ctx *c, int which, int k, const int32_t *idx, double *x_out, double *P_out)
+{
+    PRE3_TRY(reader_precheck(c, which, "pre3_get_marginal"));
+    PRE3_CHECK(k >= 0 && (k == 0 || idx != nullptr), PRE3_E_ARG, "pre3_get_marginal: bad index set");
+    PRE3_CHECK(ceil_div(k, 16) <= 65535, PRE3_E_ARG, "pre3_get_marginal: k=%d indices exceed the launch grid", k);
+    for (int t = 0; t < k; ++t)
+        PRE3_CHECK(idx[t] >= 0 && idx[t] < c->n, PRE3_E_ARG, "pre3_get_marginal: index %d outside the state (n=%d)", idx[t], c->n);
+    PRE3_HIP(hipSetDevice(c->device));
+    const double *jn = nullptr;
+    PRE3_TRY(reader_settle(c, &jn));
+    return reader_finish(c, read_marginal(c, which, k, idx, jn, x_out, P_out));
 }
 
 int pre3_predict(pre3_ctx *c, const double u[7])
@@ -1453,8 +1529,8 @@ int pre3_step(pre3_ctx *c, const double u[7], int m, const int32_t *meas_idx, co
 {
     // the previous step's deferred HI update is completed here; its rows/cols 3..6 <- Jn pass (update.m:42-46) is left to the prediction's
     // launch below (one launch less per step; PRE3_FUSE_JN=0: as its own launch).  Any return before that launch flushes it.
-    static const int fuse_jn_env = getenv("PRE3_FUSE_JN") ? atoi(getenv("PRE3_FUSE_JN")) : 1;
-    if (c) c->leave_jn_to_predict = fuse_jn_env && c->hi_pending;
+    // (a pass a marginal reader has left pending since -- it completed the update -- rides the same way)
+    if (c) c->leave_jn_to_predict = fuse_jn_env() && (c->hi_pending || c->jn_pending);
     // PRE3_OPT_PEND_HI: this call's own launches take a pending HI down-date along (prediction, H*P + S_i, the LI update's consumers); whatever of it
     // cannot -- and every call made from in here that reads P some other way -- flushes it first (pend_flush in the launchers)
     struct PendKeep { pre3_ctx *c; ~PendKeep() { if (c) c->pend_keep = false; } } pend_keep{ c };

@@ -44,12 +44,7 @@ __device__ inline void d_process_noise(double *Pn)
 
 // pred_params layout: [0..15] A4 = Qq1, [16..31] Jn, [32..80] Q7 = G Pn G' (7x7), [96..111] Jn of the last update (a copy the prediction's
 // launch does not overwrite: k_predict reads it when it carries that update's update.m:42-46 pass, fuse_jn)
-// One row of the 4x4 normalisation Jacobian applied to a 4-vector, with the contraction spelled out: k_jnorm_P and the prediction launch
-// that carries the same pass (fuse_jn) must round identically (tests/test_gpu_synth.py: deferred == immediate HI update, bit for bit).
-__device__ __forceinline__ double jn_row(const double *J, int i, const double v[4])
-{
-    return fma(J[i * 4 + 3], v[3], fma(J[i * 4 + 2], v[2], fma(J[i * 4 + 1], v[1], J[i * 4] * v[0])));
-}
+// (jn_row: pre3_geomdev.h)
 // k_predict_x and k_predict_P in ONE launch (a kernel boundary costs ~5 us on this platform, more than either kernel):
 // lane 0 of every block recomputes the quaternion product and its normalisation Jacobian (a few dozen flops) instead of
 // reading them from a previous kernel; block 0 additionally owns x_out[0:13], the process noise and the 7x7 pose block.

@@ -32,6 +32,37 @@ __device__ inline void d_q2R_sola(const double *q, double *R)
     R[6] = bd - ac;           R[7] = cd + ab;           R[8] = aa - bb - cc + dd;
 }
 
+// One row of the 4x4 normalisation Jacobian applied to a 4-vector, with the contraction spelled out: k_jnorm_P and the prediction launch
+// that carries the same pass (fuse_jn) must round identically (tests/test_gpu_synth.py: deferred == immediate HI update, bit for bit);
+// so must the marginal reader that applies a pass still pending (k_read_marginal, pre3_map.hip)
+__device__ __forceinline__ double jn_row(const double *J, int i, const double v[4])
+{
+    return fma(J[i * 4 + 3], v[3], fma(J[i * 4 + 2], v[2], fma(J[i * 4 + 1], v[1], J[i * 4] * v[0])));
+}
+
+// inversedepth_2_cartesian.m:41-65 for the inverse-depth landmark at offset o of x, with P(rho, rho) = p_rho_rho: the point p
+// (inversedepth2cartesian.m), the linearity index 4 std_d cos(alpha) / d_c2p (camera position x(1:3)) and the 3 x 6 Jacobian
+// J = [I3, dm_dtheta / rho, dm_dphi / rho, -m / rho^2] (row-major).  One arithmetic for k_map_convert_flags and the landmark reader
+// k_read_landmarks (pre3_map.hip): the reader's index is the very number the conversion compares with its threshold.
+__device__ __forceinline__ void id_to_cartesian(const double *x, int o, double p_rho_rho, double p[3], double *lin, double J[18])
+{
+    const double std_rho = sqrt(p_rho_rho);
+    const double rho = x[o + 5], std_d = std_rho / (rho * rho), theta = x[o + 3], phi = x[o + 4];
+    const double cphi = cos(phi);
+    const double mi[3] = { cphi * sin(theta), -sin(phi), cphi * cos(theta) };
+    p[0] = x[o] + (1 / rho) * mi[0]; p[1] = x[o + 1] + (1 / rho) * mi[1]; p[2] = x[o + 2] + (1 / rho) * mi[2];
+    const double a[3] = { p[0] - x[o], p[1] - x[o + 1], p[2] - x[o + 2] }, c2[3] = { p[0] - x[0], p[1] - x[1], p[2] - x[2] };
+    const double d_c2p = sqrt(c2[0] * c2[0] + c2[1] * c2[1] + c2[2] * c2[2]);
+    const double cos_alpha = (a[0] * c2[0] + a[1] * c2[1] + a[2] * c2[2]) / (sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) * d_c2p);
+    *lin = 4 * std_d * cos_alpha / d_c2p;
+    const double dmt[3] = { cos(phi) * cos(theta), 0, -cos(phi) * sin(theta) };
+    const double dmp[3] = { -sin(phi) * sin(theta), -cos(phi), -sin(phi) * cos(theta) };
+    for (int r_ = 0; r_ < 3; ++r_) {
+        for (int c = 0; c < 3; ++c) J[r_ * 6 + c] = r_ == c ? 1.0 : 0.0;
+        J[r_ * 6 + 3] = (1 / rho) * dmt[r_]; J[r_ * 6 + 4] = (1 / rho) * dmp[r_]; J[r_ * 6 + 5] = -mi[r_] / (rho * rho);
+    }
+}
+
 // hu_my_version.m:41-42 + distort_fm_my_version.m:52-61
 __device__ inline void d_pinhole_distort(const double *hrl, const CamD &cam, double *uvd)
 {

@@ -203,6 +203,10 @@ struct pre3_ctx {
     bool tail_want = false; double tail_chi2 = 0;  // pre3_step asks the LI update's launch to carry the tail
     bool tail_launched = false;                   // the last launch_cholp carried it
     bool tail_done = false;                       // ... and it ran (the LI update had rows): P holds P - W'W - W~'W~ with ONE pending rows/cols 3..6 pass (params[96..])
+    // marginal readers (pre3_get_landmarks / pre3_get_marginal, pre3_map.hip), allocated on first use: device results and their pinned host image;
+    // the landmark block is sized by the map capacity, the index-set block grows with k
+    double *lmr_dev = nullptr, *lmr_host = nullptr;
+    void *mset_dev = nullptr, *mset_host = nullptr; size_t mset_bytes = 0;
 };
 
 namespace pre3 {
@@ -257,6 +261,13 @@ struct IcMatchRide;
 int launch_project_innovation(pre3_ctx *c, int which, int clear_first, int mode, double chi2, bool collect = true, bool clear_ic = false, const IcMatchRide *ride = nullptr);
 int launch_update_x(pre3_ctx *c, int which_prior, int r);
 int launch_jnorm(pre3_ctx *c, int which);
+
+// ---- marginal readers (pre3_map.hip): gathers of x and P at `which`, a pending HI down-date (PendW) and a pending rows/cols 3..6 pass (jn: Jn on the
+// device, null: none) applied by the reading launch itself; results into the caller's host arrays (any may be null).  Arguments checked by the caller.
+int read_landmarks(pre3_ctx *c, int which, int first, int count, double *xyz, double *cov_xyz, double *cov_native, double *linearity);
+int read_marginal(pre3_ctx *c, int which, int k, const int32_t *idx, const double *jn, double *x_out, double *P_out);
+void free_readers(pre3_ctx *c);
+int flush_unless_kept(pre3_ctx *c);     /* a pending rows/cols 3..6 pass, then a pending HI down-date, out unless this call keeps them (pre3_api.hip) */
 
 int run_hypothesis_support(int n, const double *xi, const pre3_cam &cam, int n_id, const int32_t *i1, const int32_t *i2, const int32_t *i3,
                            const double *z_id, int n_euc, const int32_t *i4, const double *z_euc, double threshold, int32_t *out_host /* [1 + n_id + n_euc] */);

@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "pre3_internal.h"
+#include "pre3_geomdev.h"
 
 namespace pre3 {
 
@@ -107,22 +108,13 @@ __global__ void k_map_convert_flags(int N, const int32_t *__restrict__ lm_type, 
     int flag = 0;
     if (lm_type[i] == PRE3_INVDEPTH) {
         const int o = lm_off[i];
-        const double std_rho = sqrt((double)P[(size_t)(o + 5) * ld + o + 5]);
-        const double rho = x[o + 5], std_d = std_rho / (rho * rho), theta = x[o + 3], phi = x[o + 4];
-        const double cphi = cos(phi);
-        const double mi[3] = { cphi * sin(theta), -sin(phi), cphi * cos(theta) };
-        const double p[3] = { x[o] + (1 / rho) * mi[0], x[o + 1] + (1 / rho) * mi[1], x[o + 2] + (1 / rho) * mi[2] };
-        const double a[3] = { p[0] - x[o], p[1] - x[o + 1], p[2] - x[o + 2] }, c2[3] = { p[0] - x[0], p[1] - x[1], p[2] - x[2] };
-        const double d_c2p = sqrt(c2[0] * c2[0] + c2[1] * c2[1] + c2[2] * c2[2]);
-        const double cos_alpha = (a[0] * c2[0] + a[1] * c2[1] + a[2] * c2[2]) / (sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) * d_c2p);
-        flag = (4 * std_d * cos_alpha / d_c2p) < threshold ? 1 : 0;
+        double p[3], lin, J[18];
+        id_to_cartesian(x, o, (double)P[(size_t)(o + 5) * ld + o + 5], p, &lin, J);      // (pre3_geomdev.h: shared with the landmark reader)
+        flag = lin < threshold ? 1 : 0;
         double *cv = conv + (size_t)i * CONVW;
-        const double dmt[3] = { cos(phi) * cos(theta), 0, -cos(phi) * sin(theta) };
-        const double dmp[3] = { -sin(phi) * sin(theta), -cos(phi), -sin(phi) * cos(theta) };
         for (int r_ = 0; r_ < 3; ++r_) {
             cv[r_] = p[r_];
-            for (int c = 0; c < 3; ++c) cv[3 + r_ * 6 + c] = r_ == c ? 1.0 : 0.0;
-            cv[3 + r_ * 6 + 3] = (1 / rho) * dmt[r_]; cv[3 + r_ * 6 + 4] = (1 / rho) * dmp[r_]; cv[3 + r_ * 6 + 5] = -mi[r_] / (rho * rho);
+            for (int c = 0; c < 6; ++c) cv[3 + r_ * 6 + c] = J[r_ * 6 + c];
         }
     }
     flags[i] = flag;
@@ -452,7 +444,208 @@ static int map_precheck(pre3_ctx *c, const char *who)
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
     PRE3_HIP(hipSetDevice(c->device));
     PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "%s: needs (x_k_k, p_k_k) on the device (map management runs between steps)", who);
+    // (a rows/cols 3..6 pass -- and the HI down-date behind it -- that a marginal reader left pending for the next step goes out first: the map is re-laid out)
+    if (c->jn_pending) PRE3_TRY(flush_unless_kept(c));
     return ensure_map_buffers(c);
+}
+
+// ---- marginal readers (pre3_get_landmarks / pre3_get_marginal): plots_complete.m:161-237 and inversedepth_2_cartesian.m:36-62 read a few blocks of
+// P, not all of it.  Plain gathers plus a small reduction, no waits between workgroups; the results go to a device block and leave in ONE copy.
+// PRE3_OPT_PEND_HI: while a HI down-date is pending P stands for P - W~'W~ (PendW); the reading launch subtracts the landmark's / the tile's share of
+// W~'W~ itself (in double, as the S_i riders do), and leaves the pending rows pending.
+constexpr int LMR_W = 49;        // doubles per landmark: xyz 3 | cov_xyz 9 | cov_native 36 | linearity 1
+constexpr int LMR_PER_WG = 4;    // landmarks per 256-thread workgroup: one wave64 each
+constexpr int PEND_CHUNK = 128;  // pending rows staged in LDS at a time (k_hi_fused leaves at most 2 x 64)
+constexpr int MS_T = 16;         // output tile edge of the index-set reader
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_read_landmarks(int first, int count, const int32_t *__restrict__ lm_type, const int32_t *__restrict__ lm_off,
+                                                        const double *__restrict__ x, const T *__restrict__ P, int ld,
+                                                        const float *__restrict__ pend_W, int pend_ldw, int pend_rows, double *__restrict__ out)
+{
+    __shared__ float sW[LMR_PER_WG][PEND_CHUNK][6];
+    __shared__ double sB[LMR_PER_WG][36];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int q = blockIdx.x * LMR_PER_WG + wv;
+    const bool valid = q < count;
+    const int i = first + (valid ? q : 0);
+    const int d = lm_type[i] == PRE3_INVDEPTH ? 6 : 3, o = lm_off[i];
+    // lanes 0..35: entry (a, b) of the landmark's own block -- six rows of six contiguous entries (3 x 3 for a Cartesian landmark)
+    const int a = lane / 6, b = lane % 6;
+    const bool mine = valid && lane < 36 && a < d && b < d;
+    const double pv = mine ? (double)P[(size_t)(o + a) * ld + o + b] : 0.0;
+    double s = 0.0;
+    for (int r0 = 0; r0 < pend_rows; r0 += PEND_CHUNK) {          // (pend_rows is the same for the whole workgroup)
+        const int nr = min(PEND_CHUNK, pend_rows - r0);
+        __syncthreads();
+        for (int t = lane; t < nr * 6; t += 64) {
+            const int r = t / 6, cc = t % 6;
+            sW[wv][r][cc] = valid && cc < d ? pend_W[(size_t)(r0 + r) * pend_ldw + o + cc] : 0.f;
+        }
+        __syncthreads();
+        if (mine)
+            for (int r = 0; r < nr; ++r) s += (double)sW[wv][r][a] * (double)sW[wv][r][b];
+    }
+    const double v = mine ? pv - s : 0.0;
+    if (lane < 36) sB[wv][lane] = v;
+    __syncthreads();
+    if (!valid) return;
+    double *res = out + (size_t)q * LMR_W;
+    if (lane < 36) res[12 + lane] = v;
+    if (lane != 0) return;
+    const double *B = sB[wv];
+    if (d == 6) {
+        double p[3], lin, J[18], Tm[18];
+        id_to_cartesian(x, o, B[35], p, &lin, J);
+        for (int r = 0; r < 3; ++r)                                // J * P_ii * J' (inversedepth_2_cartesian.m:58-69 on the landmark's block)
+            for (int c = 0; c < 6; ++c) {
+                double t = 0.0;
+                for (int e = 0; e < 6; ++e) t += J[r * 6 + e] * B[e * 6 + c];
+                Tm[r * 6 + c] = t;
+            }
+        for (int r = 0; r < 3; ++r)
+            for (int c = r; c < 3; ++c) {
+                double t = 0.0;
+                for (int e = 0; e < 6; ++e) t += Tm[r * 6 + e] * J[c * 6 + e];
+                res[3 + r * 3 + c] = t; res[3 + c * 3 + r] = t;
+            }
+        for (int r = 0; r < 3; ++r) res[r] = p[r];
+        res[48] = lin;
+    } else {
+        for (int r = 0; r < 3; ++r) {
+            res[r] = x[o + r];
+            for (int c = 0; c < 3; ++c) res[3 + r * 3 + c] = B[r * 6 + c];
+        }
+        res[48] = -1.0;
+    }
+}
+
+// entry (s, t) of P - W~'W~ straight from global memory (the few entries a pending rows/cols 3..6 pass needs)
+template <typename T>
+__device__ double pend_entry(const T *__restrict__ P, int ld, const float *__restrict__ W, int ldw, int rows, int s, int t)
+{
+    double acc = 0.0;
+    for (int r = 0; r < rows; ++r) acc += (double)W[(size_t)r * ldw + s] * (double)W[(size_t)r * ldw + t];
+    return (double)P[(size_t)s * ld + t] - acc;
+}
+
+// entry (a, b) of P after a pending rows/cols 3..6 <- Jn pass (update.m:42-46), value for value as k_jnorm_P stores it (pre3_geom.hip: jn_row,
+// the 4 x 4 corner through its double-precision intermediate, the result rounded to T)
+template <typename T>
+__device__ double jn_entry(const T *__restrict__ P, int ld, const float *__restrict__ W, int ldw, int rows, const double *__restrict__ jn, int a, int b)
+{
+    const bool ja = a >= 3 && a < 7, jb = b >= 3 && b < 7;
+    if (ja && jb) {
+        double T1[4];
+        for (int t = 0; t < 4; ++t) {
+            const double w[4] = { pend_entry(P, ld, W, ldw, rows, 3, 3 + t), pend_entry(P, ld, W, ldw, rows, 4, 3 + t),
+                                  pend_entry(P, ld, W, ldw, rows, 5, 3 + t), pend_entry(P, ld, W, ldw, rows, 6, 3 + t) };
+            T1[t] = jn_row(jn, a - 3, w);
+        }
+        return (double)(T)jn_row(jn, b - 3, T1);
+    }
+    const int r = ja ? a - 3 : b - 3, col = ja ? b : a;
+    const double v[4] = { pend_entry(P, ld, W, ldw, rows, 3, col), pend_entry(P, ld, W, ldw, rows, 4, col),
+                          pend_entry(P, ld, W, ldw, rows, 5, col), pend_entry(P, ld, W, ldw, rows, 6, col) };
+    return (double)(T)jn_row(jn, r, v);
+}
+
+// P[idx, idx] (k x k, row-major) and x[idx]: one 16 x 16 output tile per workgroup; the tile's rows and columns of W~ are staged in LDS
+template <typename T>
+__global__ __launch_bounds__(256) void k_read_marginal(int k, const int32_t *__restrict__ idx, const double *__restrict__ x, const T *__restrict__ P, int ld,
+                                                       const float *__restrict__ pend_W, int pend_ldw, int pend_rows, const double *__restrict__ jn,
+                                                       double *__restrict__ x_out, double *__restrict__ P_out)
+{
+    __shared__ float sR[PEND_CHUNK][MS_T], sC[PEND_CHUNK][MS_T + 1];
+    const int ty = threadIdx.x / MS_T, tx = threadIdx.x % MS_T;
+    const int i0 = blockIdx.y * MS_T, j0 = blockIdx.x * MS_T, i = i0 + ty, j = j0 + tx;
+    const int a = idx[i < k ? i : k - 1], b = idx[j < k ? j : k - 1];
+    double s = 0.0;
+    for (int r0 = 0; r0 < pend_rows; r0 += PEND_CHUNK) {
+        const int nr = min(PEND_CHUNK, pend_rows - r0);
+        __syncthreads();
+        for (int t = threadIdx.x; t < nr * MS_T; t += blockDim.x) {
+            const int r = t / MS_T, cc = t % MS_T;
+            const float *wr = pend_W + (size_t)(r0 + r) * pend_ldw;
+            sR[r][cc] = i0 + cc < k ? wr[idx[i0 + cc]] : 0.f;
+            sC[r][cc] = j0 + cc < k ? wr[idx[j0 + cc]] : 0.f;
+        }
+        __syncthreads();
+        for (int r = 0; r < nr; ++r) s += (double)sR[r][ty] * (double)sC[r][tx];
+    }
+    if (i >= k || j >= k) return;
+    if (blockIdx.y == 0 && ty == 0) x_out[j] = x[b];
+    const bool jn_ab = jn != nullptr && ((a >= 3 && a < 7) || (b >= 3 && b < 7));
+    P_out[(size_t)i * k + j] = jn_ab ? jn_entry(P, ld, pend_W, pend_ldw, pend_rows, jn, a, b) : (double)P[(size_t)a * ld + b] - s;
+}
+
+int read_landmarks(pre3_ctx *c, int which, int first, int count, double *xyz, double *cov_xyz, double *cov_native, double *linearity)
+{
+    if (count <= 0 || (!xyz && !cov_xyz && !cov_native && !linearity)) return PRE3_OK;
+    if (c->lmr_dev == nullptr) {
+        const size_t bytes = sizeof(double) * LMR_W * (size_t)std::max(c->capN, 1);
+        if (hipMalloc((void **)&c->lmr_dev, bytes) != hipSuccess) { c->lmr_dev = nullptr; set_error("pre3_get_landmarks: device allocation failed"); return PRE3_E_NOMEM; }
+        if (hipHostMalloc((void **)&c->lmr_host, bytes, 0) != hipSuccess) { c->lmr_host = nullptr; (void)hipFree(c->lmr_dev); c->lmr_dev = nullptr; set_error("pre3_get_landmarks: pinned allocation failed"); return PRE3_E_NOMEM; }
+    }
+    const PendW pw = pend_args(c);
+    const double *x = which == PRE3_X_K_K ? c->x_kk : c->x_km1;
+    const dim3 g(ceil_div(count, LMR_PER_WG)), blk(256);
+    DISPATCH_T(c,
+        hipLaunchKernelGGL(k_read_landmarks<double>, g, blk, 0, c->stream, first, count, c->lm.type, c->lm.off, x, (const double *)c->P, c->ld, pw.W, pw.ldw, pw.rows, c->lmr_dev),
+        hipLaunchKernelGGL(k_read_landmarks<float>, g, blk, 0, c->stream, first, count, c->lm.type, c->lm.off, x, (const float *)c->P, c->ld, pw.W, pw.ldw, pw.rows, c->lmr_dev));
+    PRE3_HIP(hipGetLastError());
+    PRE3_HIP(hipMemcpyAsync(c->lmr_host, c->lmr_dev, sizeof(double) * LMR_W * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+    PRE3_TRY(stream_drain(c, __func__));
+    for (int q = 0; q < count; ++q) {
+        const double *r = c->lmr_host + (size_t)q * LMR_W;
+        if (xyz) memcpy(xyz + 3 * (size_t)q, r, sizeof(double) * 3);
+        if (cov_xyz) memcpy(cov_xyz + 9 * (size_t)q, r + 3, sizeof(double) * 9);
+        if (cov_native) memcpy(cov_native + 36 * (size_t)q, r + 12, sizeof(double) * 36);
+        if (linearity) linearity[q] = r[48];
+    }
+    return PRE3_OK;
+}
+
+int read_marginal(pre3_ctx *c, int which, int k, const int32_t *idx, const double *jn, double *x_out, double *P_out)
+{
+    if (k <= 0 || (!x_out && !P_out)) return PRE3_OK;
+    const size_t o_x = ((size_t)k * sizeof(int32_t) + 15) & ~(size_t)15, o_P = o_x + sizeof(double) * (size_t)k;
+    const size_t bytes = o_P + sizeof(double) * (size_t)k * (size_t)k;
+    if (bytes > c->mset_bytes) {                     // (grows with k; the call before this one has drained the stream)
+        if (c->mset_dev) (void)hipFree(c->mset_dev);
+        if (c->mset_host) (void)hipHostFree(c->mset_host);
+        c->mset_dev = c->mset_host = nullptr; c->mset_bytes = 0;
+        if (hipMalloc(&c->mset_dev, bytes) != hipSuccess) { c->mset_dev = nullptr; set_error("pre3_get_marginal: device allocation of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
+        if (hipHostMalloc(&c->mset_host, bytes, 0) != hipSuccess) { c->mset_host = nullptr; (void)hipFree(c->mset_dev); c->mset_dev = nullptr; set_error("pre3_get_marginal: pinned allocation of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
+        c->mset_bytes = bytes;
+    }
+    unsigned char *hb = static_cast<unsigned char *>(c->mset_host), *db = static_cast<unsigned char *>(c->mset_dev);
+    memcpy(hb, idx, sizeof(int32_t) * (size_t)k);
+    PRE3_HIP(hipMemcpyAsync(db, hb, sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, c->stream));
+    const PendW pw = pend_args(c);
+    const double *x = which == PRE3_X_K_K ? c->x_kk : c->x_km1;
+    const dim3 g(ceil_div(k, MS_T), ceil_div(k, MS_T)), blk(MS_T * MS_T);
+    const int32_t *d_idx = reinterpret_cast<const int32_t *>(db);
+    double *d_x = reinterpret_cast<double *>(db + o_x), *d_P = reinterpret_cast<double *>(db + o_P);
+    DISPATCH_T(c,
+        hipLaunchKernelGGL(k_read_marginal<double>, g, blk, 0, c->stream, k, d_idx, x, (const double *)c->P, c->ld, pw.W, pw.ldw, pw.rows, jn, d_x, d_P),
+        hipLaunchKernelGGL(k_read_marginal<float>, g, blk, 0, c->stream, k, d_idx, x, (const float *)c->P, c->ld, pw.W, pw.ldw, pw.rows, jn, d_x, d_P));
+    PRE3_HIP(hipGetLastError());
+    const size_t back = P_out ? bytes - o_x : o_P - o_x;          // x and P are contiguous: one copy
+    PRE3_HIP(hipMemcpyAsync(hb + o_x, db + o_x, back, hipMemcpyDeviceToHost, c->stream));
+    PRE3_TRY(stream_drain(c, __func__));
+    if (x_out) memcpy(x_out, hb + o_x, sizeof(double) * (size_t)k);
+    if (P_out) memcpy(P_out, hb + o_P, sizeof(double) * (size_t)k * (size_t)k);
+    return PRE3_OK;
+}
+
+void free_readers(pre3_ctx *c)
+{
+    if (c->lmr_dev) (void)hipFree(c->lmr_dev);
+    if (c->lmr_host) (void)hipHostFree(c->lmr_host);
+    if (c->mset_dev) (void)hipFree(c->mset_dev);
+    if (c->mset_host) (void)hipHostFree(c->mset_host);
+    c->lmr_dev = c->lmr_host = nullptr; c->mset_dev = c->mset_host = nullptr; c->mset_bytes = 0;
 }
 
 }  // namespace pre3

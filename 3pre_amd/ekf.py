@@ -12,6 +12,7 @@ matlab_code/ of the reference):
       .rescue_hi_inliers()        <-> @ekf_filter/rescue_hi_inliers.m:29-47
       .ekf_update_hi_inliers()    <-> @ekf_filter/ekf_update_hi_inliers.m:45-58
       .ekf_update_all()           <-> @ekf_filter/ekf_update_all.m:46-62
+      .landmarks() / .marginal()  <-> plots_complete.m:161-237, inversedepth_2_cartesian.m:36-62 (what they read of x and P, without fetching P)
     update(x, P, H, R, z, h)      <-> update.m:27   (stateless drop-in: host arrays in, host arrays out)
     predict_state_and_covariance  <-> predict_state_and_covariance.m:27 (u passed explicitly instead of fv.m's disk read)
 
@@ -85,6 +86,36 @@ class EkfFilter:
 
     def get_p_k_km1(self):
         return self._get(_lib.X_K_KM1)[1]
+
+    # ---- marginals without fetching P (pre3_get_landmarks / pre3_get_marginal)
+    def landmarks(self, which=_lib.X_K_K, first=0, count=None):
+        """The map as 3-D points with their uncertainty, as plots_complete.m:208-237 draws it (inversedepth2cartesian.m for the point,
+        inversedepth_2_cartesian.m:58-62's J for its 3x3 covariance J P_ii J', inversedepth_2_cartesian.m:36-49's linearity index), for
+        landmarks first .. first+count-1 (count None: to the end of the map).  Returns a dict of xyz (count, 3), cov_xyz (count, 3, 3),
+        cov_native (count, 6, 6: the landmark's own block of P; a Cartesian landmark's 3x3 in the top-left corner, the rest 0) and linearity
+        (count,: -1 for a Cartesian landmark).  A deferred HI update is completed first; a pending HI down-date is applied by the reading launch
+        and stays pending (the filter's next step is not changed by the read)."""
+        first = int(first)
+        count = self.N - first if count is None else int(count)
+        k = max(count, 0)
+        xyz, cxyz = np.zeros((max(k, 1), 3)), np.zeros((max(k, 1), 3, 3))
+        cnat, lin = np.zeros((max(k, 1), 6, 6)), np.zeros(max(k, 1))
+        check(lib.pre3_get_landmarks(self._ctx, int(which), first, count, dptr(xyz), dptr(cxyz), dptr(cnat), dptr(lin)))
+        return {"xyz": xyz[:k].copy(), "cov_xyz": cxyz[:k].copy(), "cov_native": cnat[:k].copy(), "linearity": lin[:k].copy()}
+
+    def marginal(self, idx, which=_lib.X_K_K):
+        """(x[idx], P[idx][:, idx]) for any index set (unsorted, repeats allowed): the pose plots_complete.m:161-164, 185 reads (idx 0..6),
+        a landmark's block (plots_complete.m:208-237), P(rho, rho) of inversedepth_2_cartesian.m:41, or any pose-landmark cross term --
+        without copying P to the host.  Same pending rule as landmarks()."""
+        ix = i32(np.asarray(idx, dtype=np.int64).reshape(-1))
+        k = int(ix.shape[0])
+        x, P = np.zeros(max(k, 1)), np.zeros((max(k, 1), max(k, 1)))
+        check(lib.pre3_get_marginal(self._ctx, int(which), k, dptr(ix), dptr(x), dptr(P)))
+        return x[:k].copy(), P[:k, :k].copy()
+
+    def pose(self, which=_lib.X_K_K):
+        """marginal(range(7)): the camera position and quaternion x(1:7) and their 7x7 covariance (plots_complete.m:161-164, 185)."""
+        return self.marginal(np.arange(7), which)
 
     def sync(self):
         check(lib.pre3_sync(self._ctx))

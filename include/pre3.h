@@ -75,6 +75,33 @@ PRE3_API int pre3_state_size(pre3_ctx *ctx);                 /* n = 13 + 6*N_id 
 PRE3_API int pre3_set_state(pre3_ctx *ctx, int which, int n, const double *x, const double *P);
 PRE3_API int pre3_get_state(pre3_ctx *ctx, int which, int n, double *x, double *P);   /* P may be NULL */
 
+/* ---- marginals without fetching P -------------------------------------------
+ * Both readers follow pre3_get_state's rules: which = PRE3_X_K_K or PRE3_X_K_KM1; the other estimate in the covariance buffer is PRE3_E_STATE;
+ * the device's error words are read (as pre3_get_state does); a deferred HI update (PRE3_OPT_DEFER_HI) is completed first -- the landmarks
+ * include it, and x_k_k is final only after it.  A range or index outside the map is PRE3_E_ARG, checked on the host before anything is
+ * launched.  N = 0: pre3_get_landmarks returns PRE3_OK and writes nothing; pre3_get_marginal still reads the pose (n = 13), as
+ * pre3_get_state does.  Synchronous; one gather launch and one device-to-host copy.
+ * Unlike every other entry point they do NOT complete a pending HI down-date (PRE3_OPT_PEND_HI) or its pending rows / columns 3..6 pass:
+ * the values returned are those of P - W~'W~ (and of that pass), computed by the reading launch itself, and the filter's next step runs
+ * exactly as it would have without the read. */
+
+/* plots_complete.m:208-237, inversedepth2cartesian.m, inversedepth_2_cartesian.m:36-62: the map as a set of 3-D points with
+ * their uncertainty, for landmarks first .. first+count-1 at the chosen estimate.  Any output may be NULL.
+ *   xyz[3*count]         inverse depth: y(1:3) + m(theta,phi)/rho; Cartesian: the state's 3 entries
+ *   cov_xyz[9*count]     3x3, J * P_ii * J' with J = [I3, dm_dtheta/rho, dm_dphi/rho, -m/rho^2] (inversedepth_2_cartesian.m:58-62); Cartesian: P_ii
+ *   cov_native[36*count] the landmark's own block of P, 6x6; Cartesian: 3x3 in the top-left corner, the rest 0
+ *   linearity[count]     inversedepth_2_cartesian.m:36-49's index (camera position x(1:3) of the same estimate); -1 for Cartesian
+ * Matrices row-major (all are symmetric).  Synchronous.  Does NOT apply a pending HI down-date to P: the blocks are those of
+ * P - W~'W~, computed by the reading launch itself. */
+PRE3_API int pre3_get_landmarks(pre3_ctx *ctx, int which, int first, int count,
+                                double *xyz, double *cov_xyz, double *cov_native, double *linearity);
+
+/* The state entries x[idx] and the marginal covariance P[idx, idx] (k x k, row-major) for any index set: the pose is
+ * idx = 0..6, a landmark's block is its offset .. offset+5, and pose-landmark cross terms are any mix of the two.
+ * Indices need not be sorted and may repeat.  x_out / P_out may be NULL.  Same pending rule as above.  Meant for small sets
+ * (16 x 16 output tiles); any k works, the staging buffer grows with it (8 k^2 bytes). */
+PRE3_API int pre3_get_marginal(pre3_ctx *ctx, int which, int k, const int32_t *idx, double *x_out, double *P_out);
+
 /* ---- a2: predict_state_and_covariance.m:27-143 (called by @ekf_filter/ekf_prediction.m:29) ------ */
 /* u = [dX(3); dq(4)], the visual-odometry increment the reference reads through fv.m:47.
  * (x_k_k, p_k_k) -> (x_k_km1, p_k_km1); the covariance is transformed IN PLACE (only rows/cols 4:7

@@ -11,6 +11,7 @@
  *   rescue_hi_inliers.m:32-47       hi = pre3_mex('rescue', 5.9915)
  *   ekf_update_hi_inliers.m:57      pre3_mex('update_hi')
  *   get_x_k_k.m / get_p_k_k.m       [x, P] = pre3_mex('get_state', 0)
+ *   plots_complete.m:161-237        [xv, Pv] = pre3_mex('marginal', 0:6); s = pre3_mex('landmarks')     % without fetching P
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
  * corrcoef_partitioned_mex.c:25-57).  NOT compiled in the build container (no MATLAB / mex.h there).
@@ -115,6 +116,36 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         out[0] = mxCreateDoubleMatrix(1, m, mxREAL);
         for (i = 0; i < m; ++i) mxGetPr(out[0])[i] = hi[i];
         mxFree(hi); check(rc);
+    }
+    else if (!strcmp(cmd, "landmarks")) {         /* s = pre3_mex('landmarks' [, which, first, count]): struct with xyz (3xN), P_xyz (3x3xN), P_native (6x6xN), linearity (1xN)
+                                                     plots_complete.m:208-237 / inversedepth_2_cartesian.m:36-62 without get_p_k_k (pre3_get_landmarks) */
+        const char *fn[4] = { "xyz", "P_xyz", "P_native", "linearity" };
+        int which = nin > 1 ? (int)mxGetScalar(in[1]) : PRE3_X_K_K, first = nin > 2 ? (int)mxGetScalar(in[2]) : 0, count;
+        mwSize d3[3];
+        mxArray *xyz, *Pxyz, *Pnat, *lin;
+        count = nin > 3 ? (int)mxGetScalar(in[3]) : pre3_get_map(g_ctx, NULL) - first;
+        if (count < 0) count = 0;
+        xyz = mxCreateDoubleMatrix(3, count, mxREAL); lin = mxCreateDoubleMatrix(1, count, mxREAL);
+        d3[0] = 3; d3[1] = 3; d3[2] = count; Pxyz = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);      /* symmetric: row-major == column-major */
+        d3[0] = 6; d3[1] = 6; Pnat = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        check(pre3_get_landmarks(g_ctx, which, first, count, mxGetPr(xyz), mxGetPr(Pxyz), mxGetPr(Pnat), mxGetPr(lin)));
+        out[0] = mxCreateStructMatrix(1, 1, 4, fn);
+        mxSetField(out[0], 0, "xyz", xyz); mxSetField(out[0], 0, "P_xyz", Pxyz); mxSetField(out[0], 0, "P_native", Pnat); mxSetField(out[0], 0, "linearity", lin);
+    }
+    else if (!strcmp(cmd, "marginal")) {          /* [x, P] = pre3_mex('marginal', idx (0-based, any order, repeats allowed) [, which]): x(idx+1), P(idx+1, idx+1) (pre3_get_marginal) */
+        int k = (int)mxGetNumberOfElements(in[1]), i, j, rc, which = nin > 2 ? (int)mxGetScalar(in[2]) : PRE3_X_K_K;
+        int32_t *d = (int32_t *)mxMalloc(sizeof(int32_t) * (k ? k : 1));
+        double *Prm = (double *)mxMalloc(sizeof(double) * (k ? (size_t)k * k : 1));
+        for (i = 0; i < k; ++i) d[i] = (int32_t)mxGetPr(in[1])[i];
+        out[0] = mxCreateDoubleMatrix(k, 1, mxREAL);
+        rc = pre3_get_marginal(g_ctx, which, k, d, mxGetPr(out[0]), Prm);
+        mxFree(d);
+        if (rc != PRE3_OK) { mxFree(Prm); check(rc); }
+        if (nout > 1) {
+            out[1] = mxCreateDoubleMatrix(k, k, mxREAL);
+            for (i = 0; i < k; ++i) for (j = 0; j < k; ++j) mxGetPr(out[1])[(size_t)j * k + i] = Prm[(size_t)i * k + j];      /* row-major -> column-major */
+        }
+        mxFree(Prm);
     }
     else if (!strcmp(cmd, "map_delete")) {        /* pre3_mex('map_delete', idx (0-based, ascending))   delete_features.m:54-74 */
         int k = (int)mxGetNumberOfElements(in[1]), i, rc; int32_t *d = (int32_t *)mxMalloc(sizeof(int32_t) * (k ? k : 1));
