@@ -11,16 +11,18 @@ pytestmark = pytest.mark.gpu
 synth = importlib.import_module("3pre_amd.synth")
 
 
-def _with_n_rescued(tw, types, off, seq, s, n_hi):
+def _with_n_rescued(tw, types, off, seq, s, n_hi, x0=None, P0=None):
     """the step's measurements with all but n_hi of the twin's rescued landmarks turned into gross outliers (a rescue candidate is not a row of the
-    LI update, and each gate is per landmark: the others' outcome does not change)"""
+    LI update, and each gate is per landmark: the others' outcome does not change); from the sequence's prior unless x0 / P0 are given"""
     z = np.array(s["z"], float)
-    ref = tw.step(types, off, seq["cam"], seq["x0"], seq["P0"], s["u"], s["meas_idx"], z, s["hyp"], 1.0, early_exit=False)
+    x0 = seq["x0"] if x0 is None else x0
+    P0 = seq["P0"] if P0 is None else P0
+    ref = tw.step(types, off, seq["cam"], x0, P0, s["u"], s["meas_idx"], z, s["hyp"], 1.0, early_exit=False)
     hi_pos = np.nonzero(ref["hi"])[0]
     if len(hi_pos) < n_hi:
         pytest.skip("the sequence rescues only %d landmarks" % len(hi_pos))
     z[hi_pos[n_hi:]] += 300.0
-    ref2 = tw.step(types, off, seq["cam"], seq["x0"], seq["P0"], s["u"], s["meas_idx"], z, s["hyp"], 1.0, early_exit=False)
+    ref2 = tw.step(types, off, seq["cam"], x0, P0, s["u"], s["meas_idx"], z, s["hyp"], 1.0, early_exit=False)
     assert np.array_equal(ref2["li"], ref["li"]) and int(ref2["hi"].sum()) == n_hi, (int(ref2["hi"].sum()), n_hi)
     return z, ref2
 
