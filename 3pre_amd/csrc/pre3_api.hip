@@ -489,6 +489,7 @@ int pre3_destroy(pre3_ctx *c)
                      c->sel_rows, c->support, c->stats, c->pred_params, c->tiles, c->tile_ctr, c->tile_cnt, c->tiles_flat, c->P_alt, c->x_alt, c->map_col, c->map_val, c->map_desc, c->map_src0, c->map_conv, c->map_feat, c->map_flags, c->bank, c->bank_alt, c->scan_desc, c->scan_pos, c->ic_pred, c->ic_counts, c->ic_arg, c->ic_newk2, c->ic_best, c->ic_second, c->bank_src, c->chol_arrive, c->ic_pb, c->ic_ps, c->ic_pa, c->Wp, c->Sp, c->tiles128, c->need, c->cholp_flags, c->cholp_tp, c->dd_groups, c->dd_tiles, c->tail_yp, c->tail_hb, c->tail_hib, c->tail_wt, c->jn_q, c->W_pend, c->Wp_pend, c->hf_xy, c->hf_sx };
     for (void *b : bufs) if (b) (void)hipFree(b);
     free_readers(c);
+    free_rows(c);
     for (int k2 = 0; k2 < 2; ++k2) { if (c->map_stage[k2]) (void)hipHostFree(c->map_stage[k2]); if (c->map_stage_ev[k2]) (void)hipEventDestroy(c->map_stage_ev[k2]); }
     for (int k2 = 0; k2 < 2; ++k2) { if (c->up_stage[k2]) (void)hipHostFree(c->up_stage[k2]); if (c->up_stage_ev[k2]) (void)hipEventDestroy(c->up_stage_ev[k2]); }
     if (c->pinned_stats) (void)hipHostFree(c->pinned_stats);
@@ -538,6 +539,7 @@ int pre3_get_option(pre3_ctx *c, int option, int *value_out)
     case PRE3_OPT_K9_OVERLAP: *value_out = c->k9_overlap ? 1 : 0; return PRE3_OK;
     case PRE3_OPT_STEP_TAIL: *value_out = (c->step_tail && c->tail_yp != nullptr) ? 1 : 0; return PRE3_OK;
     case PRE3_OPT_PEND_HI: *value_out = c->pend_opt ? 1 : 0; return PRE3_OK;
+    case PRE3_OPT_ROWS_FORM: *value_out = c->rows_form; return PRE3_OK;
     default: set_error("pre3_get_option: unknown option %d", option); return PRE3_E_ARG;
     }
 }
@@ -1435,6 +1437,148 @@ int pre3_update_all(pre3_ctx *c)
     PRE3_TRY(check_ctx(c));
     PRE3_CHECK(c->measurements_set && c->projected, PRE3_E_STATE, "pre3_update_all: needs projection and measurements");
     return update_selected(c, PRE3_X_K_KM1, c->m, nullptr);
+}
+
+// ---- update.m on the resident current estimate (pre3_rows.hip) -------------------------------------------------------------
+// The host checks of both calls, before anything is launched
+static int rows_precheck(pre3_ctx *c, const char *who)
+{
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE,
+               "%s: acts on (x_k_k, p_k_k); the covariance buffer holds the prediction (update first)", who);
+    return PRE3_OK;
+}
+
+int pre3_update_rows(pre3_ctx *c, int r, int width, const int32_t *nnz, const int32_t *col, const double *val, const double *R, const double *z,
+                     const double *h)
+{
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_CHECK(r >= 0, PRE3_E_ARG, "pre3_update_rows: r=%d", r);
+    PRE3_CHECK(round_up(r, NB) <= c->rcap, PRE3_E_ARG, "pre3_update_rows: %d rows exceed the context's capacity %d", r, c->rcap);
+    PRE3_CHECK(r == 0 || (nnz && col && val && z && h && width >= 1), PRE3_E_ARG, "pre3_update_rows: null row data");
+    for (int a = 0; a < r; ++a) {
+        PRE3_CHECK(nnz[a] >= 0 && nnz[a] <= width && nnz[a] <= ELLW, PRE3_E_ARG, "pre3_update_rows: row %d has %d non-zeros (max %d)", a, nnz[a], ELLW);
+        for (int t = 0; t < nnz[a]; ++t)
+            PRE3_CHECK(col[(size_t)a * width + t] >= 0 && col[(size_t)a * width + t] < c->n, PRE3_E_ARG,
+                       "pre3_update_rows: column index %d out of range (n=%d) in row %d", col[(size_t)a * width + t], c->n, a);
+    }
+    PRE3_TRY(rows_precheck(c, "pre3_update_rows"));
+    PRE3_TRY(check_ctx(c));
+    if (r == 0) return PRE3_OK;                 // update.m:50-55
+    if (r <= RMAX) {
+        // the single-sweep form (pre3_rows.hip)
+        RowsBlock b{};
+        b.r = r; b.applied = 1;
+        for (int a = 0; a < r; ++a) {
+            for (int t = 0; t < nnz[a]; ++t) { b.col[a * RMAX + t] = col[(size_t)a * width + t]; b.val[a * RMAX + t] = val[(size_t)a * width + t]; }
+            b.nu[a] = z[a] - h[a];
+            for (int e = 0; e < r; ++e) b.R[a * r + e] = R ? R[(size_t)a * r + e] : (a == e ? 1.0 : 0.0);
+        }
+        c->rows_form = 1;
+        PRE3_TRY(launch_rows_update(c, &b, nullptr));
+        c->hp_all_valid = false;
+        return PRE3_OK;
+    }
+    // above RMAX rows: the rows as pre3_update_ell installs them, then the existing route (run_update) in place on x_k_k / p_k_k
+    const int r_pad = round_up(r, NB);
+    std::vector<int32_t> hc((size_t)r_pad * ELLW, 0);
+    std::vector<double> hv((size_t)r_pad * ELLW, 0.0), nu(r_pad, 0.0);
+    for (int a = 0; a < r; ++a) {
+        for (int t = 0; t < nnz[a]; ++t) { hc[(size_t)a * ELLW + t] = col[(size_t)a * width + t]; hv[(size_t)a * ELLW + t] = val[(size_t)a * width + t]; }
+        nu[a] = z[a] - h[a];
+    }
+    PRE3_HIP(hipMemcpyAsync(c->row_col, hc.data(), sizeof(int32_t) * hc.size(), hipMemcpyHostToDevice, c->stream));
+    std::vector<float> hf, rf;
+    if (c->dtype == PRE3_F64) PRE3_HIP(hipMemcpyAsync(c->row_val, hv.data(), sizeof(double) * hv.size(), hipMemcpyHostToDevice, c->stream));
+    else { hf.assign(hv.begin(), hv.end()); PRE3_HIP(hipMemcpyAsync(c->row_val, hf.data(), sizeof(float) * hf.size(), hipMemcpyHostToDevice, c->stream)); }
+    PRE3_HIP(hipMemcpyAsync(c->row_nu, nu.data(), sizeof(double) * r_pad, hipMemcpyHostToDevice, c->stream));
+    if (R) {
+        if (c->Rdense == nullptr) PRE3_TRY(dmalloc_bytes(&c->Rdense, (size_t)c->rcap * c->rcap * c->esz));
+        if (c->dtype == PRE3_F64) PRE3_HIP(hipMemcpyAsync(c->Rdense, R, sizeof(double) * r * r, hipMemcpyHostToDevice, c->stream));
+        else { rf.assign(R, R + (size_t)r * r); PRE3_HIP(hipMemcpyAsync(c->Rdense, rf.data(), sizeof(float) * rf.size(), hipMemcpyHostToDevice, c->stream)); }
+    }
+    c->rows_form = 0;
+    PRE3_TRY(run_update(c, PRE3_X_K_K, r, R != nullptr, nullptr));
+    c->hp_all_valid = false;
+    c->x_valid[PRE3_X_K_K] = true; c->p_which = PRE3_X_K_K;
+    // (the host vectors may go: a copy from pageable memory has consumed its source when hipMemcpyAsync returns)
+    return PRE3_OK;
+}
+
+// ekf_heading_update.m:36-40 on the host: RR = J_z J_e2q diag((pi/180)^2 [1 1 1]) J_e2q' J_z' with [~, J_e2q] = e2q(q2e(R2q(R_plane))) and
+// J_z = observe_heading_jac(R2q(R_plane)).  R_plane 3 x 3 column-major; RR row-major.
+static void heading_RR(const double *Rp, double RR[9])
+{
+    auto Rm = [&](int i, int j) { return Rp[(j - 1) * 3 + (i - 1)]; };       // R(i, j), MATLAB indices
+    // slamToolbox_11_02_18/FrameTransforms/Rotations/R2q.m:11-55
+    double a, b, cc, d;
+    const double T = Rm(1, 1) + Rm(2, 2) + Rm(3, 3) + 1.0;
+    if (T > 0.00000001) {
+        const double S = 2.0 * sqrt(T);
+        a = 0.25 * S; b = (Rm(2, 3) - Rm(3, 2)) / S; cc = (Rm(3, 1) - Rm(1, 3)) / S; d = (Rm(1, 2) - Rm(2, 1)) / S;
+    } else if (Rm(1, 1) > Rm(2, 2) && Rm(1, 1) > Rm(3, 3)) {
+        const double S = 2.0 * sqrt(1.0 + Rm(1, 1) - Rm(2, 2) - Rm(3, 3));
+        a = (Rm(2, 3) - Rm(3, 2)) / S; b = 0.25 * S; cc = (Rm(1, 2) + Rm(2, 1)) / S; d = (Rm(3, 1) + Rm(1, 3)) / S;
+    } else if (Rm(2, 2) > Rm(3, 3)) {
+        const double S = 2.0 * sqrt(1.0 + Rm(2, 2) - Rm(1, 1) - Rm(3, 3));
+        a = (Rm(3, 1) - Rm(1, 3)) / S; b = (Rm(1, 2) + Rm(2, 1)) / S; cc = 0.25 * S; d = (Rm(2, 3) + Rm(3, 2)) / S;
+    } else {
+        const double S = 2.0 * sqrt(1.0 + Rm(3, 3) - Rm(1, 1) - Rm(2, 2));
+        a = (Rm(1, 2) - Rm(2, 1)) / S; b = (Rm(3, 1) + Rm(1, 3)) / S; cc = (Rm(2, 3) + Rm(3, 2)) / S; d = 0.25 * S;
+    }
+    const double q[4] = { a, -b, -cc, -d };
+    // q2e.m:15-38
+    const double y1 = 2 * q[2] * q[3] + 2 * q[0] * q[1], x1 = q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3];
+    const double z2 = -2 * q[1] * q[3] + 2 * q[0] * q[2];
+    const double y3 = 2 * q[1] * q[2] + 2 * q[0] * q[3], x3 = q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3];
+    const double e[3] = { atan2(y1, x1), asin(z2), atan2(y3, x3) };
+    // e2q.m:22-35
+    const double sr = sin(e[0] / 2), sp = sin(e[1] / 2), sy = sin(e[2] / 2), cr = cos(e[0] / 2), cp = cos(e[1] / 2), cy = cos(e[2] / 2);
+    const double Qe[4][3] = {
+        { 0.5 * (-cy * cp * sr + sy * sp * cr), 0.5 * (-cy * sp * cr + sy * cp * sr), 0.5 * (-sy * cp * cr + cy * sp * sr) },
+        { 0.5 * (cy * cp * cr + sy * sp * sr), 0.5 * (-cy * sp * sr - sy * cp * cr), 0.5 * (-sy * cp * sr - cy * sp * cr) },
+        { 0.5 * (-cy * sp * sr + sy * cp * cr), 0.5 * (cy * cp * cr - sy * sp * sr), 0.5 * (-sy * sp * cr + cy * cp * sr) },
+        { 0.5 * (-sy * cp * sr - cy * sp * cr), 0.5 * (-cy * cp * sr - sy * sp * cr), 0.5 * (cy * cp * cr + sy * sp * sr) } };
+    // aux_code/observe_heading_jac.m:31-38 at R2q(R_plane)
+    const double q1 = q[0], q2 = q[1], q3 = q[2], q4 = q[3];
+    const double Jz[3][4] = { { -2 * q4, 2 * q3, 2 * q2, -2 * q1 }, { 2 * q1, -2 * q2, 2 * q3, -2 * q4 }, { 2 * q2, 2 * q1, 2 * q4, 2 * q3 } };
+    const double var = (M_PI / 180.0) * (M_PI / 180.0);
+    double A[3][3];                                              // J_z J_e2q
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 4; ++k) s += Jz[i][k] * Qe[k][j]; A[i][j] = s; }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 3; ++k) s += A[i][k] * var * A[j][k]; RR[i * 3 + j] = s; }
+}
+
+int pre3_heading_update(pre3_ctx *c, const double R_plane[9], int strict_reference, int32_t *applied_out)
+{
+    PRE3_CHECK(c != nullptr && R_plane != nullptr, PRE3_E_ARG, "pre3_heading_update: null argument");
+    for (int k = 0; k < 9; ++k) PRE3_CHECK(std::isfinite(R_plane[k]), PRE3_E_ARG, "pre3_heading_update: R_plane is not finite");
+    PRE3_TRY(rows_precheck(c, "pre3_heading_update"));
+    PRE3_TRY(check_ctx(c));
+    RowsHeading hd{};
+    hd.on = 1; hd.strict = strict_reference ? 1 : 0;
+    for (int k = 0; k < 3; ++k) hd.z[k] = R_plane[3 + k];          // ekf_heading_update.m:29, z = R_plane(:, 2)
+    heading_RR(R_plane, hd.RR);
+    c->rows_form = 1;
+    PRE3_TRY(launch_rows_update(c, nullptr, &hd));
+    c->hp_all_valid = false;
+    if (applied_out) {
+        int32_t applied = 0;
+        PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
+        PRE3_TRY(rows_applied(c, &applied));
+        PRE3_TRY(stream_drain(c, __func__));
+        const int rc = stats_words(c);
+        *applied_out = rc == PRE3_OK ? applied : 0;
+        if (rc != PRE3_OK) {
+            // reported once, as the step's collection reports them: the words are cleared with the report
+            (void)hipMemsetAsync(c->stats + 6, 0, sizeof(int32_t) * 2, c->stream);
+            c->mail_host[6] = 0; c->mail_host[7] = 0;
+            PRE3_TRY(stream_drain(c, __func__));
+        }
+        return rc;
+    }
+    return PRE3_OK;
 }
 
 int pre3_get_flags(pre3_ctx *c, int32_t *li, int32_t *hi)

@@ -57,6 +57,18 @@ struct LmBuffers {
     int32_t *ic = nullptr, *li = nullptr, *hi = nullptr;   // [N]
 };
 
+// the small-rank update of pre3_update_rows / pre3_heading_update (pre3_rows.hip): r <= RMAX rows in ELL form (RMAX entries per row), all fp64
+constexpr int RMAX = 16;
+struct RowsBlock {
+    int32_t r, applied, pad_[2];    // applied: 0 = the heading gate returned (ekf_heading_update.m:42-44); written by the rows launch
+    int32_t col[RMAX * RMAX];
+    double val[RMAX * RMAX];
+    double nu[RMAX];                // z - h
+    double R[RMAX * RMAX];          // r x r, leading dimension r
+    double q[4];                    // x_k_k(4:7) before the update (the sweep writes x)
+};
+struct RowsHeading { int on, strict; double z[3]; double RR[9]; };    // ekf_heading_update.m:29, :37-40 (RR row-major)
+
 struct KernelTiming {
     bool enabled = false;
     int every = 1, seen = 0;        // bracket one K9 launch out of `every` (an event pair costs ~11 us of stream time)
@@ -207,6 +219,9 @@ struct pre3_ctx {
     // the landmark block is sized by the map capacity, the index-set block grows with k
     double *lmr_dev = nullptr, *lmr_host = nullptr;
     void *mset_dev = nullptr, *mset_host = nullptr; size_t mset_bytes = 0;
+    // pre3_update_rows / pre3_heading_update (pre3_rows.hip), allocated on first use: the rows block and H*P (RMAX x ld, fp64)
+    pre3::RowsBlock *rows_blk = nullptr; double *rows_hp = nullptr;
+    int rows_form = 0;                            // PRE3_OPT_ROWS_FORM: 1 the single-sweep form, 0 run_update
 };
 
 namespace pre3 {
@@ -267,7 +282,13 @@ int launch_jnorm(pre3_ctx *c, int which);
 int read_landmarks(pre3_ctx *c, int which, int first, int count, double *xyz, double *cov_xyz, double *cov_native, double *linearity);
 int read_marginal(pre3_ctx *c, int which, int k, const int32_t *idx, const double *jn, double *x_out, double *P_out);
 void free_readers(pre3_ctx *c);
-int flush_unless_kept(pre3_ctx *c);     /* a pending rows/cols 3..6 pass, then a pending HI down-date, out unless this call keeps them (pre3_api.hip) */
+int flush_unless_kept(pre3_ctx *c);
+
+// ---- small-rank update on the resident x_k_k / p_k_k (pre3_rows.hip): rows from the host block, or (rows == null) the heading rows built on the device
+// from x_k_k(4:7) behind the gate of hd.  Two launches, P swept once.  rows_applied: the gate word into host memory, on the stream (caller drains).
+int launch_rows_update(pre3_ctx *c, const RowsBlock *rows, const RowsHeading *hd);
+int rows_applied(pre3_ctx *c, int32_t *applied_host);
+void free_rows(pre3_ctx *c);     /* a pending rows/cols 3..6 pass, then a pending HI down-date, out unless this call keeps them (pre3_api.hip) */
 
 int run_hypothesis_support(int n, const double *xi, const pre3_cam &cam, int n_id, const int32_t *i1, const int32_t *i2, const int32_t *i3,
                            const double *z_id, int n_euc, const int32_t *i4, const double *z_euc, double threshold, int32_t *out_host /* [1 + n_id + n_euc] */);

@@ -117,6 +117,47 @@ class EkfFilter:
         """marginal(range(7)): the camera position and quaternion x(1:7) and their 7x7 covariance (plots_complete.m:161-164, 185)."""
         return self.marginal(np.arange(7), which)
 
+    # ---- other measurements on the resident current estimate (pre3_update_rows / pre3_heading_update, DESIGN.md section 15)
+    def update(self, H, R, z, h):
+        """[x_k_k, p_k_k] = update(x_k_k, p_k_k, H, R, z, h) (update.m:27-56) in place on the device: H r x n (dense or scipy sparse, at most 16
+        non-zeros per row), R r x r or None for eye(r).  Up to 16 rows: one sweep of P (rows_form() == 1); more: the general route."""
+        z, h = f64(z).ravel(), f64(h).ravel()
+        r = int(z.shape[0])
+        if h.shape[0] != r:
+            raise Pre3Error(-1, "update: z and h differ in length")
+        if r == 0:
+            check(lib.pre3_update_rows(self._ctx, 0, 1, None, None, None, None, None, None))
+            return
+        if H.shape != (r, self.n):
+            raise Pre3Error(-1, "update: H must be %d x %d" % (r, self.n))
+        width, nnz, col, val = _to_ell(H, self.n)
+        if width > 16:
+            raise Pre3Error(-1, "update: H has a row with %d non-zeros; the measurement rows of this filter have 13 (max 16)" % width)
+        col, val = i32(col), f64(val)
+        Rm = None if R is None else f64(R)
+        if Rm is not None and Rm.shape != (r, r):
+            raise Pre3Error(-1, "update: R must be %d x %d" % (r, r))
+        check(lib.pre3_update_rows(self._ctx, r, width, dptr(nnz), dptr(col), dptr(val), dptr(Rm), dptr(z), dptr(h)))
+
+    def ekf_heading_update(self, R_plane, strict_reference=True):
+        """@ekf_filter/ekf_heading_update.m:27-52: corrects the camera's orientation from the rotation of a fitted plane, R_plane (3 x 3); the
+        observation is its second column.  strict_reference=True keeps the reference's gate (it skips only when all seven angles of
+        find_angle_bw_2_vecs exceed 4 degrees, quirk Q12); False skips when the angle between z and h exceeds 4 degrees.  Returns whether the
+        update was applied (synchronises)."""
+        Rp = np.asfortranarray(np.asarray(R_plane, dtype=np.float64))
+        if Rp.shape != (3, 3):
+            raise Pre3Error(-1, "ekf_heading_update: R_plane must be 3 x 3")
+        Rc = f64(Rp.ravel(order="F"))
+        applied = C.c_int32(0)
+        check(lib.pre3_heading_update(self._ctx, dptr(Rc), int(bool(strict_reference)), C.byref(applied)))
+        return bool(applied.value)
+
+    def rows_form(self):
+        """PRE3_OPT_ROWS_FORM: 1 if the last update() / ekf_heading_update() took the single-sweep form, 0 the general route"""
+        v = C.c_int(0)
+        check(lib.pre3_get_option(self._ctx, 9, C.byref(v)))
+        return int(v.value)
+
     def sync(self):
         check(lib.pre3_sync(self._ctx))
 

@@ -211,6 +211,27 @@ PRE3_API int pre3_step_all(pre3_ctx *ctx, const double u[7], int m, const int32_
 PRE3_API int pre3_step_predicted(pre3_ctx *ctx, int n_draw, int k, const int32_t *hyp, double threshold, int early_exit, double chi2,
                                  int32_t stats[8]);
 
+/* ---- update.m:27-56 on the resident current estimate ----------------------------------------------------------------------
+ * Both calls act IN PLACE on (x_k_k, p_k_k), which the covariance buffer must hold (after pre3_predict and before an update it holds the prediction:
+ * PRE3_E_STATE).  Arguments are checked on the host before anything is launched (PRE3_E_ARG); the deferred HI update and a pending HI down-date
+ * (PRE3_OPT_DEFER_HI / PRE3_OPT_PEND_HI) are completed first, as every entry point but the marginal readers does.  Nothing else of the context changes
+ * (flags, per-landmark fields, map, descriptors, options); the next pre3_step predicts from the updated estimate.  S not positive definite: x and P are
+ * left untouched and the device's error word is set -- the next call that reads the error words (pre3_get_state, the marginal readers, the next step's
+ * collection) returns PRE3_E_NUMERIC.  Asynchronous unless stated.  Up to 16 rows: two launches, P swept once (PRE3_OPT_ROWS_FORM = 1). */
+/* update.m:27-56 on the resident current estimate (x_k_k, p_k_k), in place: r rows in pre3_update_ell's ELL form
+ * (row a: nnz[a] <= width <= 16 entries col[a*width+t], val[...]), R r x r dense (row-major) or NULL for eye(r), z[r], h[r].
+ * r == 0 changes nothing (update.m:50-55).  r above the context's row capacity, a row with more than 16 non-zeros, a column outside [0, n): PRE3_E_ARG.
+ * More than 16 rows take the general update route (PRE3_OPT_ROWS_FORM = 0). */
+PRE3_API int pre3_update_rows(pre3_ctx *ctx, int r, int width, const int32_t *nnz, const int32_t *col, const double *val,
+                              const double *R, const double *z, const double *h);
+/* @ekf_filter/ekf_heading_update.m:27-52: z = R_plane(:,2); h, H from the resident quaternion x_k_k(4:7); RR from R_plane; the angle gate.
+ * R_plane 3 x 3 column-major (as MATLAB passes it).  applied_out (may be NULL; non-NULL synchronises): 1 = updated, 0 = the gate returned.
+ * The gate is evaluated on the device.  strict_reference = 1 reproduces the reference's gate (quirk Q12: `if a > 4` on find_angle_bw_2_vecs' seven
+ * angles returns only when ALL of them exceed 4 degrees); 0 returns when the angle between z and h exceeds 4 degrees.  With applied_out the call
+ * reads the device's error words itself: an S that was not positive definite (this call's or an earlier one's) is reported here (PRE3_E_NUMERIC,
+ * *applied_out = 0) -- once: the words are cleared with the report, as the step's HI collection clears them. */
+PRE3_API int pre3_heading_update(pre3_ctx *ctx, const double R_plane[9], int strict_reference, int32_t *applied_out);
+
 /* Stateless drop-in for `[x,P,K] = update(x,P,H,R,z,h)` (update.m:27): host in, host out.
  * H is r x n given by rows in ELL form: row a has nnz[a] <= width entries (col[a*width+t], val[...]);
  * R is r x r dense or NULL for eye(r) (every caller in the reference passes eye).  K_out (n x r,
@@ -264,6 +285,10 @@ PRE3_API int pre3_update_ell(int device, int dtype, int n, int r, const double *
  * context (and every path of pre3_step that cannot take the pending rows) first runs the down-date as the launch it would have been.  The same
  * arithmetic except that P between the two updates is never rounded to fp32: results agree with the default form to fp32 rounding, not to the bit. */
 #define PRE3_OPT_PEND_HI 8
+/* PRE3_OPT_ROWS_FORM (read only): the form the last pre3_update_rows / pre3_heading_update took -- 1: the single-sweep small-rank form (r <= 16 rows,
+ * two launches, P read and written once); 0: the general update route (H*P, S, panel factorisation, down-date, Jnorm pass).
+ * Chosen from r alone. */
+#define PRE3_OPT_ROWS_FORM 9
 PRE3_API int pre3_set_option(pre3_ctx *ctx, int option, int value);
 PRE3_API int pre3_get_option(pre3_ctx *ctx, int option, int *value_out);
 

@@ -12,6 +12,8 @@
  *   ekf_update_hi_inliers.m:57      pre3_mex('update_hi')
  *   get_x_k_k.m / get_p_k_k.m       [x, P] = pre3_mex('get_state', 0)
  *   plots_complete.m:161-237        [xv, Pv] = pre3_mex('marginal', 0:6); s = pre3_mex('landmarks')     % without fetching P
+ *   update(x_k_k, p_k_k, H, R, z, h) pre3_mex('update', H, R, z, h)             % in place on the resident estimate; R = [] for eye
+ *   ekf_heading_update.m:27-52      applied = pre3_mex('heading', R_plane, 1)
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
  * corrcoef_partitioned_mex.c:25-57).  NOT compiled in the build container (no MATLAB / mex.h there).
@@ -146,6 +148,55 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
             for (i = 0; i < k; ++i) for (j = 0; j < k; ++j) mxGetPr(out[1])[(size_t)j * k + i] = Prm[(size_t)i * k + j];      /* row-major -> column-major */
         }
         mxFree(Prm);
+    }
+    else if (!strcmp(cmd, "update")) {            /* pre3_mex('update', H (full or sparse, r x n, <= 16 non-zeros per row), R (r x r, [] = eye), z, h): update.m:27-56 IN PLACE
+                                                     on (x_k_k, p_k_k) (pre3_update_rows) */
+        int r = (int)mxGetNumberOfElements(in[3]), n = pre3_state_size(g_ctx), a, i, j, rc;
+        int32_t *nnz, *col;
+        double *val, *Rrow = NULL;
+        if (nin != 5) mexErrMsgTxt("pre3_mex('update', H, R, z, h): four arguments");
+        if ((int)mxGetNumberOfElements(in[4]) != r) mexErrMsgTxt("pre3_mex('update'): z and h differ in length");
+        if (r > 0 && ((int)mxGetM(in[1]) != r || (int)mxGetN(in[1]) != n)) mexErrMsgTxt("pre3_mex('update'): H must be length(z) x n");
+        nnz = (int32_t *)mxCalloc(r ? r : 1, sizeof(int32_t));
+        col = (int32_t *)mxCalloc((size_t)(r ? r : 1) * 16, sizeof(int32_t));
+        val = (double *)mxCalloc((size_t)(r ? r : 1) * 16, sizeof(double));
+        if (r > 0 && mxIsSparse(in[1])) {             /* CSC -> rows */
+            const mwIndex *ir = mxGetIr(in[1]), *jc = mxGetJc(in[1]);
+            const double *pr = mxGetPr(in[1]);
+            mwIndex k;
+            for (j = 0; j < n; ++j)
+                for (k = jc[j]; k < jc[j + 1]; ++k) {
+                    a = (int)ir[k];
+                    if (pr[k] == 0.0) continue;
+                    if (nnz[a] >= 16) mexErrMsgTxt("pre3_mex('update'): a row of H has more than 16 non-zeros");
+                    col[a * 16 + nnz[a]] = j; val[a * 16 + nnz[a]] = pr[k]; ++nnz[a];
+                }
+        } else if (r > 0) {
+            const double *H = mxGetPr(in[1]);
+            for (j = 0; j < n; ++j)
+                for (a = 0; a < r; ++a) {
+                    double v = H[(size_t)j * r + a];
+                    if (v == 0.0) continue;
+                    if (nnz[a] >= 16) mexErrMsgTxt("pre3_mex('update'): a row of H has more than 16 non-zeros");
+                    col[a * 16 + nnz[a]] = j; val[a * 16 + nnz[a]] = v; ++nnz[a];
+                }
+        }
+        if (!mxIsEmpty(in[2])) {                      /* column-major -> row-major */
+            const double *Rm = mxGetPr(in[2]);
+            if ((int)mxGetM(in[2]) != r || (int)mxGetN(in[2]) != r) mexErrMsgTxt("pre3_mex('update'): R must be length(z) x length(z)");
+            Rrow = (double *)mxMalloc(sizeof(double) * (size_t)(r ? r * r : 1));
+            for (i = 0; i < r; ++i) for (j = 0; j < r; ++j) Rrow[(size_t)i * r + j] = Rm[(size_t)j * r + i];
+        }
+        rc = pre3_update_rows(g_ctx, r, 16, nnz, col, val, Rrow, mxGetPr(in[3]), mxGetPr(in[4]));
+        mxFree(nnz); mxFree(col); mxFree(val); if (Rrow) mxFree(Rrow);
+        check(rc);
+    }
+    else if (!strcmp(cmd, "heading")) {           /* applied = pre3_mex('heading', R_plane (3x3), strict): ekf_heading_update.m:27-52 on the resident estimate
+                                                     (pre3_heading_update; strict = 1: the reference's gate, quirk Q12) */
+        int32_t applied = 0;
+        if (mxGetNumberOfElements(in[1]) != 9) mexErrMsgTxt("pre3_mex('heading'): R_plane must be 3 x 3");
+        check(pre3_heading_update(g_ctx, mxGetPr(in[1]), nin > 2 ? (int)mxGetScalar(in[2]) : 1, &applied));
+        out[0] = mxCreateDoubleScalar((double)applied);
     }
     else if (!strcmp(cmd, "map_delete")) {        /* pre3_mex('map_delete', idx (0-based, ascending))   delete_features.m:54-74 */
         int k = (int)mxGetNumberOfElements(in[1]), i, rc; int32_t *d = (int32_t *)mxMalloc(sizeof(int32_t) * (k ? k : 1));
