@@ -93,6 +93,7 @@ static int check_ctx(pre3_ctx *c)
     PRE3_TRY(complete_deferred_hi(c));
     return flush_unless_kept(c);
 }
+int settle_ctx(pre3_ctx *c) { return check_ctx(c); }
 // PRE3_FUSE_JN (default 1): the rows/cols 3..6 pass of a HI update completed at the start of a step rides in that step's prediction launch
 static bool fuse_jn_env()
 {
@@ -490,6 +491,7 @@ int pre3_destroy(pre3_ctx *c)
     for (void *b : bufs) if (b) (void)hipFree(b);
     free_readers(c);
     free_rows(c);
+    free_policy(c);
     for (int k2 = 0; k2 < 2; ++k2) { if (c->map_stage[k2]) (void)hipHostFree(c->map_stage[k2]); if (c->map_stage_ev[k2]) (void)hipEventDestroy(c->map_stage_ev[k2]); }
     for (int k2 = 0; k2 < 2; ++k2) { if (c->up_stage[k2]) (void)hipHostFree(c->up_stage[k2]); if (c->up_stage_ev[k2]) (void)hipEventDestroy(c->up_stage_ev[k2]); }
     if (c->pinned_stats) (void)hipHostFree(c->pinned_stats);
@@ -587,6 +589,7 @@ int pre3_set_map(pre3_ctx *c, int N, const int32_t *lm_type)
     PRE3_HIP(hipMemset(c->lm.hi, 0, sizeof(int32_t) * c->capN));
     c->m = 0; c->meas_host.clear(); c->measurements_set = false; c->projected = false; c->innovated = false;
     c->x_valid[0] = c->x_valid[1] = false; c->p_which = -1;
+    c->booked = false; c->book_s = 0;             // a new map has no book until pre3_set_book (or an empty map's first pre3_map_policy)
     return PRE3_OK;
 }
 
@@ -1357,10 +1360,8 @@ int pre3_update_li(pre3_ctx *c)
     return update_selected(c, PRE3_X_K_KM1, n_li, c->sel_rows, gathered, first_done);
 }
 
-int pre3_rescue(pre3_ctx *c, double chi2, int32_t *hi_mask)
+static int rescue_impl(pre3_ctx *c, double chi2, int32_t *hi_mask)
 {
-    PRE3_TRY(check_ctx(c));
-    PRE3_CHECK(c->p_which == PRE3_X_K_K && c->x_valid[PRE3_X_K_K], PRE3_E_STATE, "pre3_rescue: needs (x_k_k, p_k_k), i.e. after the LI update");
     if (c->N) {
         if (c->rescue_projected) PRE3_TRY(launch_innovation(c, 1, chi2));          // h / H at x_k_k came with the K9 launch
         else PRE3_TRY(launch_project_innovation(c, PRE3_X_K_K, 0, 1, chi2));
@@ -1373,6 +1374,17 @@ int pre3_rescue(pre3_ctx *c, double chi2, int32_t *hi_mask)
     }
     return PRE3_OK;
 }
+
+// record: a booked context records what rescue_hi_inliers.m:32 projects (pre3_map_policy's times_predicted), at the x_k_k this projection uses
+// (pre3_step records it itself, in front of whichever rescue form it takes)
+static int rescue_checked(pre3_ctx *c, double chi2, int32_t *hi_mask, bool record)
+{
+    PRE3_TRY(check_ctx(c));
+    PRE3_CHECK(c->p_which == PRE3_X_K_K && c->x_valid[PRE3_X_K_K], PRE3_E_STATE, "pre3_rescue: needs (x_k_k, p_k_k), i.e. after the LI update");
+    if (record && c->booked && c->m > 0 && c->N > 0) PRE3_TRY(launch_book_vis(c));
+    return rescue_impl(c, chi2, hi_mask);
+}
+int pre3_rescue(pre3_ctx *c, double chi2, int32_t *hi_mask) { return rescue_checked(c, chi2, hi_mask, true); }
 
 int pre3_update_hi(pre3_ctx *c)
 {
@@ -1633,7 +1645,9 @@ static int step_back(pre3_ctx *c, int m, int n_draw, int k, const int32_t *hyp, 
     static const int ride_rescue = getenv("PRE3_RIDE_RESCUE") ? atoi(getenv("PRE3_RIDE_RESCUE")) : 1;      // 0: projection + gate as one launch of their own (A/B)
     c->ride_rescue_projection = ride_rescue != 0;                   // the rescue's projection rides in the LI update's K9 launch
     {
-        c->tail_want = c->step_tail && hi_fused_usable(c); c->tail_chi2 = chi2;      // ... or, with the whole rescue stage and the HI update, in the persistent launch itself
+        // ... or, with the whole rescue stage and the HI update, in the persistent launch itself (not on a booked context: the rescue's visibility
+        // record needs the point between the LI update and the rescue, which that form does not have -- the step takes the default form)
+        c->tail_want = c->step_tail && !c->booked && hi_fused_usable(c); c->tail_chi2 = chi2;
         // ... or projection AND chi2 gate in the Jnorm pass's launch, when the persistent launch's consumers leave rows 3..6 of P behind (GateRide)
         c->want_gate_ride = ride_rescue != 0 && !c->tail_want && hi_fused_usable(c); c->rescue_chi2 = chi2; c->rescue_gated = false;
         const int rc_li = pre3_update_li(c);                        // mono_slam.m:181
@@ -1642,6 +1656,10 @@ static int step_back(pre3_ctx *c, int m, int n_draw, int k, const int32_t *hyp, 
         if (rc_li != PRE3_OK) { c->rescue_projected = false; c->rescue_gated = false; c->tail_done = false; return rc_li; }
     }
     if (ran) for (int i = 0; i < 4; ++i) st[i] = c->mail_host[i];
+    // a booked context: visibility at the post-LI x_k_k, where rescue_hi_inliers.m:32 projects -- one small launch in stream order between the LI
+    // update and the rescue / HI update (also under PRE3_OPT_DEFER_HI / PEND_HI, which only move the HI update later); only when the reference's
+    // rescue runs ('1PRE' with at least one IC measurement, mono_slam.m:165)
+    if (c->booked && m > 0 && c->N > 0 && !c->tail_done) PRE3_TRY(launch_book_vis(c));
     if (c->tail_done) {
         // mono_slam.m:184 + :187 went out with the LI update's launch: the count arrives with mailbox word 9 (pre3_update_hi)
         c->rescue_projected = false; c->proj_with_jnorm = false;
@@ -1658,7 +1676,7 @@ static int step_back(pre3_ctx *c, int m, int n_draw, int k, const int32_t *hyp, 
         PRE3_TRY(launch_hi_fused(c, ++c->seq_collect));
         c->hi_fused = true;
     } else
-    PRE3_TRY(pre3_rescue(c, chi2, nullptr));                        // mono_slam.m:184
+    PRE3_TRY(rescue_checked(c, chi2, nullptr, false));             // mono_slam.m:184
     if (c->defer_hi) c->hi_pending = true;                          // mono_slam.m:187, completed at the next call on this context
     else PRE3_TRY(pre3_update_hi(c));                               // mono_slam.m:187
     st[4] = c->li_from_host >= 0 ? c->li_from_host : (c->li_kernel ? c->mail_host[4] : 0);

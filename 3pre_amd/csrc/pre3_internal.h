@@ -222,6 +222,14 @@ struct pre3_ctx {
     // pre3_update_rows / pre3_heading_update (pre3_rows.hip), allocated on first use: the rows block and H*P (RMAX x ld, fp64)
     pre3::RowsBlock *rows_blk = nullptr; double *rows_hp = nullptr;
     int rows_form = 0;                            // PRE3_OPT_ROWS_FORM: 1 the single-sweep form, 0 run_update
+    // features_info bookkeeping and the map policy (pre3_set_book / pre3_map_policy, pre3_map.hip).  A booked context carries
+    // [capN][4] int32 (times_predicted, times_measured, init_frame, last_visible) through every map call; book_vis[i] = has_h || visible at x_k_k
+    // after the LI update, recorded where the reference's rescue projects (pre3_step / pre3_step_predicted / pre3_rescue), cleared by every map call
+    bool booked = false; int book_s = 0;          // book_s: init_frame / last_visible of landmarks a map call adds (the last policy call's step - 1)
+    int32_t *book = nullptr, *book_alt = nullptr, *book_vis = nullptr;
+    const int32_t *book_from = nullptr;           // pre3_map_policy: the updated counters (policy scratch) the next apply_map re-lays out instead of book
+    void *pol_dev = nullptr; size_t pol_dev_bytes = 0;                     // policy scratch: candidates, per-landmark flags and projections, blocked[K]
+    int32_t *pol_host = nullptr, *pol_host_dev = nullptr; size_t pol_host_bytes = 0;   // the result block in mapped pinned memory
 };
 
 namespace pre3 {
@@ -289,6 +297,11 @@ int flush_unless_kept(pre3_ctx *c);
 int launch_rows_update(pre3_ctx *c, const RowsBlock *rows, const RowsHeading *hd);
 int rows_applied(pre3_ctx *c, int32_t *applied_host);
 void free_rows(pre3_ctx *c);     /* a pending rows/cols 3..6 pass, then a pending HI down-date, out unless this call keeps them (pre3_api.hip) */
+
+// ---- map policy (pre3_map.hip): the rescue-visibility rider of a booked context (one small launch at the post-LI x_k_k), buffers
+int launch_book_vis(pre3_ctx *c);
+void free_policy(pre3_ctx *c);
+int settle_ctx(pre3_ctx *c);     /* pre3_api.hip: complete a deferred HI update and flush pending work, as every ordinary call does first */
 
 int run_hypothesis_support(int n, const double *xi, const pre3_cam &cam, int n_id, const int32_t *i1, const int32_t *i2, const int32_t *i3,
                            const double *z_id, int n_euc, const int32_t *i4, const double *z_euc, double threshold, int32_t *out_host /* [1 + n_id + n_euc] */);

@@ -10,6 +10,7 @@
 // P[src(a)][src(b)] -- 36 MB read + 36 MB written at N = 500 instead of the two gather passes T = A P, P = T A' of rounds 1-3, which moved
 // twice that at half the rate: 53 -> ~17 us per call).  Rows that are plain copies (coefficient 1) reproduce their source bit for bit.
 #include <algorithm>
+#include <cmath>
 
 #include "pre3_internal.h"
 #include "pre3_geomdev.h"
@@ -190,9 +191,11 @@ __global__ __launch_bounds__(256) void k_map_cols(int n_new, const int32_t *__re
 // Everything that follows the congruence as riders of the congruence's launch (k_map_one; round 4: it was one copy, two uploads, three fills and the bank gather with two
 // stream synchronisations): the new state, the new landmark table, the per-landmark fields cleared (update_features_info.m:30-44), the
 // inbox cleared, and the descriptor bank re-laid-out (src[i] = old index of new landmark i, -1: a new landmark, zero descriptor).
+// A booked context (pre3_set_book) also re-lays out its book the same way (a new landmark: {0, 0, s, s}) and clears the rescue's visibility record.
 struct MapFinish {
     int n_new; const double *x_alt; double *x_kk; int N; const int32_t *types_src, *off_src; int32_t *lm_type, *lm_off; int capN;
     int32_t *has_h, *has_S, *inbox; int inbox_words; const int32_t *src; const double *bank; double *bank_out;
+    const int32_t *book; int32_t *book_out; int32_t *book_vis; int book_s;
 };
 __device__ __forceinline__ void map_finish_block(const MapFinish &f, int t, int nt)
 {
@@ -202,6 +205,10 @@ __device__ __forceinline__ void map_finish_block(const MapFinish &f, int t, int 
     for (int i = t; i < f.inbox_words; i += nt) f.inbox[i] = 0;
     if (f.bank != nullptr)
         for (int i = t; i < f.N * 128; i += nt) { const int sidx = f.src[i >> 7]; f.bank_out[i] = sidx >= 0 ? f.bank[(size_t)sidx * 128 + (i & 127)] : 0.0; }
+    if (f.book_out != nullptr) {
+        for (int i = t; i < f.N * 4; i += nt) { const int sidx = f.src[i >> 2]; f.book_out[i] = sidx >= 0 ? f.book[sidx * 4 + (i & 3)] : ((i & 3) < 2 ? 0 : f.book_s); }
+        for (int i = t; i < f.capN; i += nt) f.book_vis[i] = 0;
+    }
 }
 __global__ __launch_bounds__(256) void k_map_finish(MapFinish f) { map_finish_block(f, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x); }
 
@@ -402,9 +409,11 @@ static int apply_map(pre3_ctx *c, const std::vector<int32_t> &desc, int n_new, c
         hipLaunchKernelGGL(k_map_fill<float>, dim3(ceil_div(n_new, 256)), dim3(256), 0, c->stream, n_new, c->map_desc, c->x_kk, feat, conv, c->lm.off, c->map_col, (float *)c->map_val, c->x_alt, c->map_src0));
     // new state, landmark table, cleared per-landmark fields and inbox, re-laid-out descriptor bank: riders of the congruence's launch (or one launch behind the two-pass form); no synchronisation
     const bool with_bank = c->bank != nullptr && c->bank_alt != nullptr && N > 0;
-    const int fin_work = std::max(std::max(n_new, (int)(c->inbox_bytes / 4)), with_bank ? N * 128 : 0);
+    const bool with_book = c->booked;
+    const int fin_work = std::max(std::max(std::max(n_new, (int)(c->inbox_bytes / 4)), with_bank ? N * 128 : 0), with_book ? std::max(4 * N, c->capN) : 0);
     const MapFinish fin{ n_new, c->x_alt, c->x_kk, N, d_types, d_off, c->lm.type, c->lm.off, c->capN, c->lm.has_h, c->lm.has_S, (int32_t *)c->inbox_dev, (int)(c->inbox_bytes / 4),
-                         d_src, with_bank ? c->bank : nullptr, c->bank_alt };
+                         d_src, with_bank ? c->bank : nullptr, c->bank_alt,
+                         c->book_from ? c->book_from : c->book, with_book ? c->book_alt : nullptr, c->book_vis, c->book_s };
     static const int one_pass = getenv("PRE3_MAP_ONE_PASS") ? atoi(getenv("PRE3_MAP_ONE_PASS")) : 1;
     if (one_pass) {
         // one pass into the second buffer, which becomes P
@@ -432,6 +441,7 @@ static int apply_map(pre3_ctx *c, const std::vector<int32_t> &desc, int n_new, c
     }
     PRE3_HIP(hipGetLastError());
     if (with_bank) std::swap(c->bank, c->bank_alt);
+    if (with_book) std::swap(c->book, c->book_alt);
     c->N = N; c->n = n; c->lm_type_host = new_types;
     c->m = 0; c->meas_host.clear(); c->measurements_set = false; c->projected = false; c->innovated = false; c->hp_all_valid = false;
     c->li_from_host = c->hi_from_host = -1; c->li_kernel = c->hi_kernel = false;
@@ -648,9 +658,244 @@ void free_readers(pre3_ctx *c)
     c->lmr_dev = c->lmr_host = nullptr; c->mset_dev = c->mset_host = nullptr; c->mset_bytes = 0;
 }
 
+
+// ---- map policy (pre3_map_policy): delete_features.m:31-49, update_features_info.m:30-44 and the walk of
+// initialize_features.m:110-142 -> initialize_a_feature_sift_3.m:72-138 on the device.  Three launches, none waits on another workgroup:
+//   k_policy_lm        one lane per landmark: IC stamp, deletion rule, counters, projection of every survivor at x_k_k (a converted landmark as the
+//                      Cartesian point the conversion writes)
+//   k_policy_prefilter one workgroup per candidate: the box test against every visible survivor (exact: an addition does not move the map)
+//   k_policy_walk      ONE wave: compaction, measured, the target, then the candidates in the caller's order, each unblocked one tested only
+//                      against the features accepted before it (ballot), the accepted ones projected at x_k_k; results into mapped host memory
+constexpr int POL_HDR = 8;           // result block: measured, T, examined, N after, n_del, n_acc, n_surv, pad | del[capN] | acc[K] | conv[capN]
+constexpr double POL_SEMI_U = 15.0, POL_SEMI_V = 10.0;     // initialize_a_feature_sift_3.m:58-60: [60,40]/2/2
+
+struct PolicyArgs {
+    int N, K, step, min_features, strict, capN;
+    const int32_t *type, *off, *ic, *li, *hi, *has_h, *vis, *conv_flags;
+    const double *conv, *x; CamD cam;
+    const int32_t *book;                // [N][4] as it stands
+    int32_t *book_new;                  // [N][4] the survivors' updated counters (scratch: apply_map re-lays them out; the book itself is untouched until then)
+    int32_t *del, *mh, *pvis; double *puv;          // per landmark
+    const double *cand;                 // [K][2] distorted pixels, then rho[K]
+    int32_t *blocked;                   // [K]
+    int32_t *res;                       // the result block (device address of mapped pinned memory)
+};
+
+__device__ __forceinline__ bool pol_in_box(double pu, double pv, double cu, double cv, int strict)
+{
+    // initialize_a_feature_sift_3.m:80-98: search_region_center = (UV(c,2), UV(c,1)) is compared with uv_pred(1,:) +- 15 and uv_pred(2,:) +- 10
+    // (quirk Q14: u against the candidate's v); strict = 0 compares u with u and v with v
+    const double bu = strict ? cv : cu, bv = strict ? cu : cv;
+    return pu > bu - POL_SEMI_U && pu < bu + POL_SEMI_U && pv > bv - POL_SEMI_V && pv < bv + POL_SEMI_V;
+}
+
+__global__ __launch_bounds__(64) void k_policy_lm(PolicyArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.N) return;
+    const int32_t *b = a.book + 4 * i;
+    int32_t *nb = a.book_new + 4 * i;
+    const int tp = b[0], tm = b[1], init = b[2];
+    const int lv = a.ic[i] ? a.step - 1 : b[3];                      // matching_sift_based.m:133: last frame's IC matches were visible at step - 1
+    // delete_features.m:31-49, on the counters as they stand; the N > 20 gate on the map before deletion
+    const bool del = ((double)tm < 0.5 * (double)tp && tp > 5) || (a.step - init > 20) || (a.N > 20 && a.step - lv > 20);
+    a.del[i] = del ? 1 : 0;
+    if (del) { a.mh[i] = 0; a.pvis[i] = 0; return; }
+    // update_features_info.m:30-44: times_predicted += ~isempty(h) (the IC search's projection, or the rescue's: has_h || the recorded visibility)
+    const int pred = (a.has_h[i] || (a.vis != nullptr && a.vis[i])) ? 1 : 0, meas = (a.li[i] || a.hi[i]) ? 1 : 0;
+    nb[0] = tp + pred; nb[1] = tm + meas; nb[2] = init; nb[3] = lv;
+    a.mh[i] = meas;
+    // predict_camera_measurements at x_k_k (initialize_a_feature_sift_3.m:72-76), on the map as inversedepth_2_cartesian leaves it
+    const bool cv = a.conv_flags[i] != 0;
+    const double *y = cv ? a.conv + (size_t)i * CONVW : a.x + a.off[i];
+    double zi[2] = { 0, 0 }, hc[14], hl[12];
+    bool fresh = false;
+    (void)project_core(cv ? PRE3_CARTESIAN : a.type[i], a.x, y, a.cam, 0, nullptr, zi, fresh, hc, hl);
+    a.pvis[i] = fresh ? 1 : 0;
+    a.puv[2 * i] = zi[0]; a.puv[2 * i + 1] = zi[1];
+}
+
+__global__ __launch_bounds__(256) void k_policy_prefilter(PolicyArgs a)
+{
+    const int c = blockIdx.x;
+    const double cu = a.cand[2 * c], cv = a.cand[2 * c + 1];
+    int hit = 0;
+    for (int j = threadIdx.x; j < a.N; j += blockDim.x)
+        hit |= (a.pvis[j] && pol_in_box(a.puv[2 * j], a.puv[2 * j + 1], cu, cv, a.strict)) ? 1 : 0;
+    hit = __syncthreads_or(hit);
+    if (threadIdx.x == 0) a.blocked[c] = hit;
+}
+
+// hinv_my_version.m:26-53 (the geometry of k_map_new_features) and its projection at x_k_k: the h the reference's next attempt sees for it
+__device__ __noinline__ bool pol_new_feature_h(double ud, double vd, double rho, const double *x, const CamD &cam, double zi[2])
+{
+    double xd = (ud - cam.Cx) / cam.f, yd = (vd - cam.Cy) / cam.f;
+    double rd = sqrt(xd * xd + yd * yd);
+    double ru = rd / (1 + cam.k1 * rd * rd + cam.k2 * rd * rd * rd * rd);
+    for (int k = 0; k < 10; ++k) {
+        double f1 = ru + cam.k1 * ru * ru * ru + cam.k2 * ru * ru * ru * ru * ru - rd;
+        double f1p = 1 + 3 * cam.k1 * ru * ru + 5 * cam.k2 * ru * ru * ru * ru;
+        ru = ru - f1 / f1p;
+    }
+    const double Dd = 1 + cam.k1 * ru * ru + cam.k2 * ru * ru * ru * ru;
+    const double uu = cam.f * xd / Dd + cam.Cx, vu = cam.f * yd / Dd + cam.Cy;
+    double R[9];
+    m_q2r(x + 3, R);
+    const double hcv[3] = { -(cam.Cx - uu) / cam.f, -(cam.Cy - vu) / cam.f, 1.0 };
+    double nw[3];
+    for (int i = 0; i < 3; ++i) nw[i] = R[i * 3] * hcv[0] + R[i * 3 + 1] * hcv[1] + R[i * 3 + 2] * hcv[2];
+    const double y[6] = { x[0], x[1], x[2], atan2(nw[0], nw[2]), atan2(-nw[1], sqrt(nw[0] * nw[0] + nw[2] * nw[2])), rho };
+    double hc[14], hl[12];
+    bool fresh = false;
+    (void)project_core(PRE3_INVDEPTH, x, y, cam, 0, nullptr, zi, fresh, hc, hl);
+    return fresh;
+}
+
+constexpr int POL_MAX_FEATURES = 1024;     // min_features cap: the accepted features' h live in LDS
+__global__ __launch_bounds__(64) void k_policy_walk(PolicyArgs a)
+{
+    __shared__ double s_hu[POL_MAX_FEATURES], s_hv[POL_MAX_FEATURES];
+    __shared__ int s_newvis;
+    const int lane = threadIdx.x;
+    int32_t *r_del = a.res + POL_HDR, *r_acc = r_del + a.capN, *r_conv = r_acc + a.K;
+    // survivors in order, measured (map_management.m:37-40: LI || HI of last frame, survivors only), conversion flags of the survivors
+    int n_del = 0, measured = 0;
+    for (int base = 0; base < a.N; base += 64) {
+        const int i = base + lane;
+        const int d = i < a.N ? a.del[i] : 0;
+        const unsigned long long bm = __ballot(d);
+        if (d) r_del[n_del + __popcll(bm & ((1ull << lane) - 1ull))] = i;
+        n_del += __popcll(bm);
+        measured += __popcll(__ballot(i < a.N && !d && a.mh[i]));
+        if (i < a.N) r_conv[i] = d ? 0 : a.conv_flags[i];
+    }
+    const int n_surv = a.N - n_del;
+    // map_management.m:58-66; quirk Q13 (initialize_features.m:127-129 + :138-140 count one SIFT feature twice): ceil(T / 2) additions
+    const int T = measured == 0 ? a.min_features : max(0, a.min_features - measured);
+    const int goal = min(a.strict ? (T + 1) / 2 : T, a.capN - n_surv);      // (additions stop at the capacity: stats[3] shows it)
+    int n_acc = 0, nh = 0, examined = 0;
+    for (int c0 = 0; c0 < a.K && n_acc < goal; c0 += 64) {
+        const int cl = c0 + lane;
+        const int blk = cl < a.K ? a.blocked[cl] : 1;
+        const double u = cl < a.K ? a.cand[2 * cl] : 0.0, v = cl < a.K ? a.cand[2 * cl + 1] : 0.0;
+        for (int k = 0; k < 64 && c0 + k < a.K && n_acc < goal; ++k) {
+            examined = c0 + k + 1;
+            if (__shfl(blk, k)) continue;                                   // a survivor of the map is in its box
+            const double cu = __shfl(u, k), cv = __shfl(v, k);
+            int hit = 0;
+            for (int j = lane; j < nh; j += 64) hit |= pol_in_box(s_hu[j], s_hv[j], cu, cv, a.strict) ? 1 : 0;
+            if (__any(hit)) continue;                                       // ... or a feature this walk has added
+            if (lane == 0) {
+                r_acc[n_acc] = c0 + k;
+                double zi[2];
+                const bool vis = pol_new_feature_h(cu, cv, a.cand[2 * a.K + c0 + k], a.x, a.cam, zi);
+                if (vis) { s_hu[nh] = zi[0]; s_hv[nh] = zi[1]; }
+                s_newvis = vis ? 1 : 0;
+            }
+            __syncthreads();
+            nh += s_newvis; ++n_acc;
+            __syncthreads();
+        }
+    }
+    if (lane == 0) {
+        a.res[0] = measured; a.res[1] = T; a.res[2] = examined; a.res[3] = n_surv + n_acc;
+        a.res[4] = n_del; a.res[5] = n_acc; a.res[6] = n_surv; a.res[7] = 0;
+    }
+}
+
+// the rescue's visibility record: has_h (the IC search's projection at x_k_km1) || visible at the post-LI x_k_k (rescue_hi_inliers.m:32 projects
+// every landmark there and keeps stale h for the ones it cannot see, quirk Q7)
+__global__ __launch_bounds__(64) void k_book_vis(int N, const int32_t *__restrict__ type, const int32_t *__restrict__ off, const double *__restrict__ x,
+                                                 CamD cam, const int32_t *__restrict__ has_h, int32_t *__restrict__ vis)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    double zi[2] = { 0, 0 }, hc[14], hl[12];
+    bool fresh = false;
+    (void)project_core(type[i], x, x + off[i], cam, 0, nullptr, zi, fresh, hc, hl);
+    vis[i] = (has_h[i] || fresh) ? 1 : 0;
+}
+
+static CamD cam_d(const pre3_ctx *c) { return CamD{ c->cam.f, c->cam.Cx, c->cam.Cy, c->cam.k1, c->cam.k2, c->cam.nRows, c->cam.nCols }; }
+
+int launch_book_vis(pre3_ctx *c)
+{
+    hipLaunchKernelGGL(k_book_vis, dim3(ceil_div(c->N, 64)), dim3(64), 0, c->stream, c->N, c->lm.type, c->lm.off, c->x_kk, cam_d(c), c->lm.has_h, c->book_vis);
+    PRE3_HIP(hipGetLastError());
+    return PRE3_OK;
+}
+
+static int ensure_book(pre3_ctx *c)
+{
+    if (c->book) return PRE3_OK;
+    const size_t b4 = sizeof(int32_t) * 4 * (size_t)c->capN, b1 = sizeof(int32_t) * (size_t)c->capN;
+    if (hipMalloc((void **)&c->book, b4) != hipSuccess || hipMalloc((void **)&c->book_alt, b4) != hipSuccess || hipMalloc((void **)&c->book_vis, b1) != hipSuccess) {
+        free_policy(c); set_error("features_info book: device allocation failed"); return PRE3_E_NOMEM;
+    }
+    return PRE3_OK;
+}
+
+// a context's first booking starts from zero counters and an empty visibility record
+static int start_book(pre3_ctx *c)
+{
+    PRE3_TRY(ensure_book(c));
+    if (!c->booked) {
+        PRE3_HIP(hipMemsetAsync(c->book, 0, sizeof(int32_t) * 4 * (size_t)c->capN, c->stream));
+        PRE3_HIP(hipMemsetAsync(c->book_vis, 0, sizeof(int32_t) * (size_t)c->capN, c->stream));
+        c->booked = true;
+    }
+    return PRE3_OK;
+}
+
+void free_policy(pre3_ctx *c)
+{
+    void *d[] = { c->book, c->book_alt, c->book_vis, c->pol_dev };
+    for (void *p : d) if (p) (void)hipFree(p);
+    if (c->pol_host) (void)hipHostFree(c->pol_host);
+    c->book = c->book_alt = c->book_vis = nullptr; c->pol_dev = nullptr; c->pol_host = c->pol_host_dev = nullptr;
+    c->pol_dev_bytes = c->pol_host_bytes = 0; c->booked = false;
+}
+
 }  // namespace pre3
 
 using namespace pre3;
+
+// The composition of pre3_map_management with the conversion flags already known (flags[i]: the conversion of old landmark i, its points and
+// Jacobians in c->map_conv): pre3_map_management after k_map_convert_flags, pre3_map_policy with the flags its own launches produced.
+// always: apply the (identity) map even when nothing changes -- the policy's book and cleared fields go through it.
+static int map_compose(pre3_ctx *c, int n_del, const int32_t *del_idx, std::vector<int32_t> &flags, int32_t *converted_out,
+                       int n_new, const double *uvd, double std_pxl, const double *initial_rho, bool always)
+{
+    const int N = c->N;
+    std::vector<int32_t> desc, types, src;
+    desc.reserve(3 * (size_t)(c->n + 6 * n_new)); types.reserve(N + n_new); src.reserve(N + n_new);
+    for (int i = 0; i < 13; ++i) { desc.push_back(0); desc.push_back(i); desc.push_back(0); }
+    int d = 0, off = 13, n_out = 13;
+    bool any = always || n_del > 0 || n_new > 0;
+    for (int i = 0; i < N; ++i) {
+        const int dim = c->lm_type_host[i] == PRE3_INVDEPTH ? 6 : 3;
+        if (d < n_del && del_idx[d] == i) { ++d; off += dim; flags[i] = 0; continue; }
+        if (flags[i]) {
+            for (int q = 0; q < 3; ++q) { desc.push_back(2); desc.push_back(i); desc.push_back(q); }
+            types.push_back(PRE3_CARTESIAN); n_out += 3; any = true;
+        } else {
+            for (int q = 0; q < dim; ++q) { desc.push_back(0); desc.push_back(off + q); desc.push_back(0); }
+            types.push_back(c->lm_type_host[i]); n_out += dim;
+        }
+        src.push_back(i);
+        off += dim;
+    }
+    if (converted_out) for (int i = 0; i < N; ++i) converted_out[i] = flags[i];
+    if (!any) return PRE3_OK;
+    const int first_new_off = n_out;
+    for (int f = 0; f < n_new; ++f) {
+        for (int q = 0; q < 6; ++q) { desc.push_back(1); desc.push_back(f); desc.push_back(q); }
+        types.push_back(PRE3_INVDEPTH); src.push_back(-1); n_out += 6;
+    }
+    return apply_map(c, desc, n_out, types, n_new, first_new_off, src, uvd, initial_rho, std_pxl);
+}
+
+
 
 extern "C" {
 
@@ -757,32 +1002,122 @@ int pre3_map_management(pre3_ctx *c, int n_del, const int32_t *del_idx, double c
         PRE3_TRY(stream_drain(c, __func__));
         PRE3_HIP(hipMemcpy(flags.data(), c->map_flags, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
     }
-    std::vector<int32_t> desc, types, src;
-    desc.reserve(3 * (size_t)(c->n + 6 * n_new)); types.reserve(N + n_new); src.reserve(N + n_new);
-    for (int i = 0; i < 13; ++i) { desc.push_back(0); desc.push_back(i); desc.push_back(0); }
-    int d = 0, off = 13, n_out = 13;
-    bool any = n_del > 0 || n_new > 0;
-    for (int i = 0; i < N; ++i) {
-        const int dim = c->lm_type_host[i] == PRE3_INVDEPTH ? 6 : 3;
-        if (d < n_del && del_idx[d] == i) { ++d; off += dim; flags[i] = 0; continue; }
-        if (flags[i]) {
-            for (int q = 0; q < 3; ++q) { desc.push_back(2); desc.push_back(i); desc.push_back(q); }
-            types.push_back(PRE3_CARTESIAN); n_out += 3; any = true;
-        } else {
-            for (int q = 0; q < dim; ++q) { desc.push_back(0); desc.push_back(off + q); desc.push_back(0); }
-            types.push_back(c->lm_type_host[i]); n_out += dim;
-        }
-        src.push_back(i);
-        off += dim;
+    return map_compose(c, n_del, del_idx, flags, converted_out, n_new, uvd, std_pxl, initial_rho, false);
+}
+int pre3_set_book(pre3_ctx *c, int first, int count, const int32_t *book)
+{
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_CHECK(first >= 0 && count >= 0 && (long long)first + count <= c->N && (count == 0 || book != nullptr), PRE3_E_ARG,
+               "pre3_set_book: landmarks %d .. %d outside the map (N=%d)", first, first + count - 1, c->N);
+    PRE3_TRY(settle_ctx(c));
+    PRE3_TRY(start_book(c));
+    if (count > 0) PRE3_HIP(hipMemcpyAsync(c->book + 4 * (size_t)first, book, sizeof(int32_t) * 4 * (size_t)count, hipMemcpyHostToDevice, c->stream));
+    return stream_drain(c, __func__);
+}
+
+int pre3_get_book(pre3_ctx *c, int first, int count, int32_t *book_out)
+{
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_CHECK(c->booked, PRE3_E_STATE, "pre3_get_book: the context has no book (pre3_set_book)");
+    PRE3_CHECK(first >= 0 && count >= 0 && (long long)first + count <= c->N && (count == 0 || book_out != nullptr), PRE3_E_ARG,
+               "pre3_get_book: landmarks %d .. %d outside the map (N=%d)", first, first + count - 1, c->N);
+    PRE3_TRY(settle_ctx(c));
+    if (count > 0) PRE3_HIP(hipMemcpyAsync(book_out, c->book + 4 * (size_t)first, sizeof(int32_t) * 4 * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+    return stream_drain(c, __func__);
+}
+
+// map_management.m:27-79 with its policy: the decisions on the device (k_policy_lm, k_policy_prefilter, k_policy_walk), ONE host wait for the
+// result block, then the composition of pre3_map_management with those lists (one pass over P), the candidates' descriptors and the book rows
+int pre3_map_policy(pre3_ctx *c, int step, int min_features, double convert_threshold, double std_pxl, int strict_reference, int K,
+                    const double *cand_uv, const double *cand_xyz, const double *cand_desc, int32_t *del_out, int32_t *n_del_out,
+                    int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out, int32_t stats[4])
+{
+    // ---- every argument and state check before anything is launched: an error leaves the context as it was
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_CHECK(K >= 0 && K <= PRE3_POLICY_MAX_CANDIDATES && (K == 0 || (cand_uv && cand_xyz)), PRE3_E_ARG,
+               "pre3_map_policy: K=%d candidates (at most %d, uv and xyz required)", K, PRE3_POLICY_MAX_CANDIDATES);
+    PRE3_CHECK(min_features >= 0 && min_features <= POL_MAX_FEATURES, PRE3_E_ARG, "pre3_map_policy: min_features=%d outside 0 .. %d", min_features, POL_MAX_FEATURES);
+    PRE3_CHECK(std::isfinite(std_pxl) && std::isfinite(convert_threshold), PRE3_E_ARG, "pre3_map_policy: std_pxl and the threshold must be finite");
+    std::vector<double> rho(K);
+    for (int k = 0; k < K; ++k) {
+        const double x = cand_xyz[3 * k], y = cand_xyz[3 * k + 1], z = cand_xyz[3 * k + 2];
+        rho[k] = 1.0 / sqrt(x * x + y * y + z * z);                 // initialize_a_feature_sift_3.m:116-117
+        PRE3_CHECK(std::isfinite(cand_uv[2 * k]) && std::isfinite(cand_uv[2 * k + 1]), PRE3_E_ARG, "pre3_map_policy: candidate %d has a non-finite pixel", k);
+        PRE3_CHECK(std::isfinite(rho[k]) && rho[k] > 0, PRE3_E_ARG, "pre3_map_policy: candidate %d has a zero or non-finite XYZ", k);
     }
-    if (converted_out) for (int i = 0; i < N; ++i) converted_out[i] = flags[i];
-    if (!any) return PRE3_OK;
-    const int first_new_off = n_out;
-    for (int f = 0; f < n_new; ++f) {
-        for (int q = 0; q < 6; ++q) { desc.push_back(1); desc.push_back(f); desc.push_back(q); }
-        types.push_back(PRE3_INVDEPTH); src.push_back(-1); n_out += 6;
+    PRE3_CHECK(c->have_cam, PRE3_E_STATE, "pre3_map_policy: camera not set");
+    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "pre3_map_policy: needs (x_k_k, p_k_k) on the device (map management runs between steps)");
+    PRE3_CHECK(c->booked || c->N == 0, PRE3_E_STATE, "pre3_map_policy: the context has no book (pre3_set_book)");
+    // ---- a deferred HI update completed, pending work flushed (map_precheck); the book
+    PRE3_TRY(settle_ctx(c));
+    PRE3_TRY(map_precheck(c, "pre3_map_policy"));
+    PRE3_TRY(start_book(c));
+    const int N = c->N;
+    // ---- buffers: device scratch [cand 3K | puv 2capN | del, mh, pvis capN | blocked K], the mapped result block [hdr | del capN | acc K | conv capN | cand 3K]
+    const size_t cap = (size_t)std::max(c->capN, 1), Kc = (size_t)std::max(K, 1);
+    const size_t dev_bytes = sizeof(double) * (3 * Kc + 2 * cap) + sizeof(int32_t) * (7 * cap + Kc);
+    const size_t res_words = ((POL_HDR + 2 * cap + Kc) + 1) & ~(size_t)1, host_bytes = sizeof(int32_t) * res_words + sizeof(double) * 3 * Kc;
+    if (dev_bytes > c->pol_dev_bytes) {
+        if (c->pol_dev) (void)hipFree(c->pol_dev);
+        c->pol_dev = nullptr; c->pol_dev_bytes = 0;
+        PRE3_CHECK(hipMalloc(&c->pol_dev, dev_bytes) == hipSuccess, PRE3_E_NOMEM, "pre3_map_policy: device allocation of %zu bytes failed", dev_bytes);
+        c->pol_dev_bytes = dev_bytes;
     }
-    return apply_map(c, desc, n_out, types, n_new, first_new_off, src, uvd, initial_rho, std_pxl);
+    if (host_bytes > c->pol_host_bytes) {
+        if (c->pol_host) (void)hipHostFree(c->pol_host);
+        c->pol_host = c->pol_host_dev = nullptr; c->pol_host_bytes = 0;
+        PRE3_CHECK(hipHostMalloc((void **)&c->pol_host, host_bytes, hipHostMallocMapped) == hipSuccess, PRE3_E_NOMEM, "pre3_map_policy: pinned allocation failed");
+        PRE3_HIP(hipHostGetDevicePointer((void **)&c->pol_host_dev, c->pol_host, 0));
+        c->pol_host_bytes = host_bytes;
+    }
+    double *h_cand = reinterpret_cast<double *>(c->pol_host + res_words);
+    for (int k = 0; k < K; ++k) { h_cand[2 * k] = cand_uv[2 * k]; h_cand[2 * k + 1] = cand_uv[2 * k + 1]; h_cand[2 * K + k] = rho[k]; }
+    double *d_cand = static_cast<double *>(c->pol_dev), *d_puv = d_cand + 3 * Kc;
+    int32_t *d_del = reinterpret_cast<int32_t *>(d_puv + 2 * cap), *d_mh = d_del + cap, *d_pvis = d_mh + cap, *d_nbook = d_pvis + cap, *d_blocked = d_nbook + 4 * cap;
+    if (K > 0) PRE3_HIP(hipMemcpyAsync(d_cand, h_cand, sizeof(double) * 3 * K, hipMemcpyHostToDevice, c->stream));
+    // ---- inversedepth_2_cartesian's flags and points (the same launch pre3_map_management makes: the same linearity numbers)
+    if (convert_threshold >= 0 && N > 0) {
+        DISPATCH_T(c,
+            hipLaunchKernelGGL(k_map_convert_flags<double>, dim3(ceil_div(N, 64)), dim3(64), 0, c->stream, N, c->lm.type, c->lm.off, c->x_kk, (const double *)c->P, c->ld, convert_threshold, c->map_flags, c->map_conv),
+            hipLaunchKernelGGL(k_map_convert_flags<float>, dim3(ceil_div(N, 64)), dim3(64), 0, c->stream, N, c->lm.type, c->lm.off, c->x_kk, (const float *)c->P, c->ld, convert_threshold, c->map_flags, c->map_conv));
+    } else if (N > 0) PRE3_HIP(hipMemsetAsync(c->map_flags, 0, sizeof(int32_t) * N, c->stream));
+    const PolicyArgs pa{ N, K, step, min_features, strict_reference ? 1 : 0, c->capN, c->lm.type, c->lm.off, c->lm.ic, c->lm.li, c->lm.hi, c->lm.has_h, c->book_vis,
+                         c->map_flags, c->map_conv, c->x_kk, cam_d(c), c->book, d_nbook, d_del, d_mh, d_pvis, d_puv, d_cand, d_blocked, c->pol_host_dev };
+    if (N > 0) hipLaunchKernelGGL(k_policy_lm, dim3(ceil_div(N, 64)), dim3(64), 0, c->stream, pa);
+    if (K > 0) {
+        if (N > 0) hipLaunchKernelGGL(k_policy_prefilter, dim3(K), dim3(256), 0, c->stream, pa);
+        else PRE3_HIP(hipMemsetAsync(d_blocked, 0, sizeof(int32_t) * K, c->stream));
+    }
+    hipLaunchKernelGGL(k_policy_walk, dim3(1), dim3(64), 0, c->stream, pa);
+    PRE3_HIP(hipGetLastError());
+    PRE3_TRY(stream_drain(c, __func__));                            // the one host wait
+    const int32_t *res = c->pol_host, *r_del = res + POL_HDR, *r_acc = r_del + c->capN, *r_conv = r_acc + K;
+    const int n_del = res[4], n_acc = res[5], n_surv = res[6];
+    PRE3_CHECK(n_del >= 0 && n_del <= N && n_acc >= 0 && n_acc <= K && n_surv == N - n_del && n_surv + n_acc <= c->capN, PRE3_E_HIP, "pre3_map_policy: inconsistent result block");
+    std::vector<int32_t> dl(r_del, r_del + n_del), acc(r_acc, r_acc + n_acc), flags(N ? N : 1, 0);
+    for (int i = 0; i < N; ++i) flags[i] = r_conv[i];
+    int32_t st[4] = { res[0], res[1], res[2], res[3] };
+    std::vector<double> uvd(2 * (size_t)n_acc), rho_acc(n_acc);
+    for (int a = 0; a < n_acc; ++a) { uvd[2 * a] = cand_uv[2 * acc[a]]; uvd[2 * a + 1] = cand_uv[2 * acc[a] + 1]; rho_acc[a] = rho[acc[a]]; }
+    // ---- the state: pre3_map_management's composition with these lists; the book rides along (new landmarks: {0, 0, step - 1, step - 1},
+    // initialize_features.m:120 passes step - 1 to add_feature_to_info_vector_my_version_sift.m:42-60)
+    // (the counters reach the book only through this re-layout: a failure before it leaves the book as it was)
+    const int book_s_before = c->book_s;
+    c->book_s = step - 1; c->book_from = d_nbook;
+    const int rc_map = map_compose(c, n_del, dl.data(), flags, converted_out, n_acc, uvd.data(), std_pxl, rho_acc.data(), true);
+    c->book_from = nullptr;
+    if (rc_map != PRE3_OK) { c->book_s = book_s_before; return rc_map; }
+    if (cand_desc != nullptr && n_acc > 0) {                        // initialize_a_feature_sift_3.m:132: the candidate's own descriptor
+        std::vector<double> dsc(128 * (size_t)n_acc);
+        for (int a = 0; a < n_acc; ++a) memcpy(dsc.data() + 128 * (size_t)a, cand_desc + 128 * (size_t)acc[a], sizeof(double) * 128);
+        PRE3_TRY(pre3_set_descriptors(c, n_surv, n_acc, dsc.data()));
+    }
+    if (del_out) for (int d = 0; d < n_del; ++d) del_out[d] = dl[d];
+    if (n_del_out) *n_del_out = n_del;
+    if (accepted_out) for (int a = 0; a < n_acc; ++a) accepted_out[a] = acc[a];
+    if (n_acc_out) *n_acc_out = n_acc;
+    if (stats) for (int q = 0; q < 4; ++q) stats[q] = st[q];
+    return PRE3_OK;
 }
 
 }  // extern "C"

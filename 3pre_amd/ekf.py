@@ -13,6 +13,7 @@ matlab_code/ of the reference):
       .ekf_update_hi_inliers()    <-> @ekf_filter/ekf_update_hi_inliers.m:45-58
       .ekf_update_all()           <-> @ekf_filter/ekf_update_all.m:46-62
       .landmarks() / .marginal()  <-> plots_complete.m:161-237, inversedepth_2_cartesian.m:36-62 (what they read of x and P, without fetching P)
+      .map_management_policy()    <-> map_management.m:27-79 with delete_features.m / update_features_info.m / initialize_features.m's policy
     update(x, P, H, R, z, h)      <-> update.m:27   (stateless drop-in: host arrays in, host arrays out)
     predict_state_and_covariance  <-> predict_state_and_covariance.m:27 (u passed explicitly instead of fv.m's disk read)
 
@@ -50,6 +51,7 @@ class EkfFilter:
         self.n = int(lib.pre3_state_size(self._ctx))
         self.lm_type = lm_type
         self.m = 0
+        self.meas_idx = np.zeros(0, np.int32)            # the installed measurements' landmarks (the flags of get_flags are in this order)
         self._st = np.zeros(8, np.int32)                 # pre3_step's statistics block (kept: the wrapper's time is GPU idle time)
         self._st_addr = self._st.ctypes.data
 
@@ -226,7 +228,7 @@ class EkfFilter:
         check(lib.pre3_get_option(self._ctx, 6, C.byref(v)))
         return bool(v.value)
 
-    # ---- map management between steps (map_management.m:27-79); the policy stays with the caller
+    # ---- map management between steps (map_management.m:27-79); the policy is the caller's (map_management_policy: the device's)
     def _refresh_map(self):
         self.N = int(lib.pre3_get_map(self._ctx, None))
         t = np.zeros(max(self.N, 1), np.int32)
@@ -234,6 +236,7 @@ class EkfFilter:
         self.lm_type = t[:self.N].copy()
         self.n = int(lib.pre3_state_size(self._ctx))
         self.m = 0
+        self.meas_idx = np.zeros(0, np.int32)
 
     def delete_features(self, del_idx):
         """delete_features.m:54-74 -> delete_a_feature.m:47-51 (0-based landmark indices)."""
@@ -269,6 +272,43 @@ class EkfFilter:
         self._refresh_map()
         return conv[:n_before].copy()
 
+    # ---- the policy half of map_management.m:27-79 on the device
+    def set_book(self, book, first=0):
+        """features_info bookkeeping: (count, 4) int rows {times_predicted, times_measured, init_frame, last_visible} for landmarks first..."""
+        b = i32(np.asarray(book).reshape(-1, 4))
+        check(lib.pre3_set_book(self._ctx, int(first), int(b.shape[0]), dptr(b)))
+
+    def book(self):
+        out = np.zeros((max(self.N, 1), 4), np.int32)
+        check(lib.pre3_get_book(self._ctx, 0, self.N, dptr(out)))
+        return out[:self.N].copy()
+
+    def map_management_policy(self, step, cand_uv, cand_xyz, cand_desc=None, min_features=50, linearity_index_threshold=0.1, std_pxl=None,
+                              strict_reference=True):
+        """map_management.m:27-79 with its policy decided on the device: deletion (delete_features.m:31-49), counters (update_features_info.m),
+        inversedepth_2_cartesian (threshold None: skipped) and the initialisation walk over the candidates in the given order
+        (initialize_features.m:110-142).  cand_uv (K, 2) distorted pixels, cand_xyz (K, 3) camera-frame points, cand_desc (128, K) or None.
+        Returns dict(deleted, accepted, converted, measured, target, examined, N)."""
+        uv = f64(np.asarray(cand_uv, float).reshape(-1, 2))
+        xyz = f64(np.asarray(cand_xyz, float).reshape(-1, 3))
+        K = int(uv.shape[0])
+        if xyz.shape[0] != K:
+            raise ValueError("cand_uv and cand_xyz disagree on K")
+        desc = None
+        if cand_desc is not None:
+            d = np.asarray(cand_desc, dtype=np.float64)
+            desc = np.ascontiguousarray(d.T) if d.ndim == 2 and d.shape[0] == 128 and d.shape[1] == K else f64(d).reshape(K, 128)
+        N0 = self.N
+        dl, acc, conv = np.zeros(max(N0, 1), np.int32), np.zeros(max(K, 1), np.int32), np.zeros(max(N0, 1), np.int32)
+        nd, na, st = C.c_int32(0), C.c_int32(0), np.zeros(4, np.int32)
+        thr = -1.0 if linearity_index_threshold is None else float(linearity_index_threshold)
+        check(lib.pre3_map_policy(self._ctx, int(step), int(min_features), C.c_double(thr), C.c_double(self.std_z if std_pxl is None else std_pxl),
+                                  int(bool(strict_reference)), K, dptr(uv), dptr(xyz), dptr(desc), dptr(dl), C.byref(nd), dptr(acc), C.byref(na),
+                                  dptr(conv), dptr(st)))
+        self._refresh_map()
+        return dict(deleted=dl[:nd.value].copy(), accepted=acc[:na.value].copy(), converted=conv[:N0].copy(), measured=int(st[0]),
+                    target=int(st[1]), examined=int(st[2]), N=int(st[3]))
+
     # ---- IC search on the device (search_IC_matches.m:31-44 + matching_sift_based.m:104-149)
     def set_descriptors(self, desc, first=0):
         """features_info(first+i).Descriptor; desc is (128, count) as MATLAB stores it (or (count, 128) C-order rows)."""
@@ -296,6 +336,7 @@ class EkfFilter:
         meas, z, pairs = np.zeros(N, np.int32), np.zeros((N, 2)), np.zeros((N, 3), np.int32)
         check(lib.pre3_ic_search(self._ctx, C.c_double(thresh), int(bool(strict_reference)), C.byref(nm), C.byref(m), dptr(meas), dptr(z), dptr(pairs)))
         self.m = int(m.value)
+        self.meas_idx = meas[:self.m].copy()
         return dict(meas_idx=meas[:self.m].copy(), z=z[:self.m].copy(), match_idx=pairs[:nm.value, :2].T.copy(),
                     accepted=pairs[:nm.value, 2].copy())
 
@@ -332,6 +373,7 @@ class EkfFilter:
     def set_measurements(self, meas_idx, z):
         meas_idx, z = i32(meas_idx), f64(z)
         self.m = int(meas_idx.shape[0])
+        self.meas_idx = meas_idx
         check(lib.pre3_set_measurements(self._ctx, self.m, dptr(meas_idx), dptr(z)))
 
     def ransac_hypotheses(self, hyp, threshold=None, early_exit=True):
@@ -422,6 +464,7 @@ class EkfFilter:
         """One '1PRE' filter step (mono_slam.m:153-187)."""
         u, meas_idx, z, hyp = f64(u), i32(meas_idx), f64(z), i32(hyp)
         self.m = int(meas_idx.shape[0])
+        self.meas_idx = meas_idx
         n_draw, k = hyp.shape
         st = self._st
         rc = lib.pre3_step(self._ctx, addr(u), self.m, addr(meas_idx), addr(z), n_draw, k, addr(hyp),
@@ -436,6 +479,7 @@ class EkfFilter:
         measurements, ekf_update_all, as one call (the same arithmetic as the four calls, fewer launches)"""
         u, meas_idx, z = f64(u), i32(meas_idx), f64(z)
         self.m = int(meas_idx.shape[0])
+        self.meas_idx = meas_idx
         check(lib.pre3_step_all(self._ctx, dptr(u), self.m, dptr(meas_idx), dptr(z)))
 
     def step_predicted(self, hyp, threshold=None, early_exit=True, chi2=CHI2INV_2_95):

@@ -114,11 +114,63 @@ def filter_from_snapshot(snap, cam, which="k_k", dtype="f32", device=0, max_hyp=
     desc = [np.asarray(a.get("Descriptor", []), float).reshape(-1) for a in snap["features_info"]]
     if desc and all(d.size == 128 for d in desc):
         f.set_descriptors(np.stack(desc, 1))
+    f.set_book(features_info_book(snap["features_info"]))
     return f
 
 
+BOOK_FIELDS = ("times_predicted", "times_measured", "init_frame", "last_visible")
+FLAG_FIELDS = ("individually_compatible", "low_innovation_inlier", "high_innovation_inlier")
+
+
+def _int(v):
+    return int(np.asarray(v).reshape(-1)[0]) if np.size(v) else 0
+
+
+def features_info_book(features_info):
+    """The device book (pre3_set_book): [times_predicted, times_measured, init_frame, last_visible] per entry."""
+    return np.array([[_int(a.get(k, 0)) for k in BOOK_FIELDS] for a in features_info], np.int32).reshape(-1, 4)
+
+
+def apply_policy_result(features_info, result, step, cand_uv, cand_xyz, cand_desc=None, book=None):
+    """features_info after EkfFilter.map_management_policy: the deleted entries dropped (delete_features.m:63-74, without the reference's
+    extra drop of a 2-entry list), one entry per accepted candidate appended with the fields of
+    add_feature_to_info_vector_my_version_sift.m:37-60 (init_frame = last_visible = step - 1), per-frame fields emptied
+    (update_features_info.m:30-44).  book (N, 4) -- EkfFilter.book() after the call -- overwrites the four counters of every entry."""
+    gone = set(int(i) for i in result["deleted"])
+    out = [dict(a) for i, a in enumerate(features_info) if i not in gone]
+    cand_uv, cand_xyz = np.asarray(cand_uv, float).reshape(-1, 2), np.asarray(cand_xyz, float).reshape(-1, 3)
+    conv = [c for i, c in enumerate(result.get("converted", np.zeros(len(features_info), int))) if i not in gone]
+    for a, cv in zip(out, conv):
+        if cv:
+            a["type"] = "cartesian"
+    for c in result["accepted"]:
+        c = int(c)
+        e = {k: np.zeros((0, 0)) for k in FEATURE_FIELDS}
+        e.update(uv_when_initialized=cand_uv[c].copy(), half_patch_size_when_initialized=20, half_patch_size_when_matching=6,
+                 times_predicted=0, times_measured=0, init_frame=step - 1, type="inversedepth", state_size=6, measurement_size=2,
+                 individually_compatible=0, low_innovation_inlier=0, high_innovation_inlier=0, last_visible=step - 1,
+                 Feature3d_in_code_coordinate=cand_xyz[c].copy())
+        if cand_desc is not None:
+            e["Descriptor"] = np.asarray(cand_desc, float).reshape(128, -1)[:, c].copy()
+        out.append(e)
+    for a in out:
+        for k in FLAG_FIELDS:
+            a[k] = 0
+        for k in ("z", "h", "H", "S"):
+            a[k] = np.zeros((0, 0))
+    if book is not None:
+        book = np.asarray(book).reshape(-1, 4)
+        if len(book) != len(out):
+            raise ValueError("book has %d rows, features_info %d entries" % (len(book), len(out)))
+        for a, b in zip(out, book):
+            for k, v in zip(BOOK_FIELDS, b):
+                a[k] = int(v)
+    return out
+
+
 def update_snapshot_from_filter(snap, f, step=None):
-    """The writer side of mono_slam.m:251-254: x_k_k / p_k_k (and the landmark types) from the device."""
+    """The writer side of mono_slam.m:251-254: x_k_k / p_k_k, the landmark types, the last frame's IC / LI / HI flags and, on a booked filter,
+    the book (times_predicted, times_measured, init_frame, last_visible) from the device."""
     out = dict(step=int(snap["step"] if step is None else step), features_info=[dict(a) for a in snap["features_info"]],
                filter=dict(snap["filter"]))
     if len(out["features_info"]) != f.N:
@@ -126,4 +178,20 @@ def update_snapshot_from_filter(snap, f, step=None):
     out["filter"]["x_k_k"], out["filter"]["p_k_k"] = f.get_x_k_k(), f.get_p_k_k()
     for a, t in zip(out["features_info"], f.lm_type):
         a["type"] = "inversedepth" if t == _lib.INVDEPTH else "cartesian"
+    try:
+        book = f.book()
+    except _lib.Pre3Error:                            # a filter without a book (pre3_set_book) keeps the snapshot's counters
+        book = None
+    if book is not None:
+        for a, b in zip(out["features_info"], book):
+            for k, v in zip(BOOK_FIELDS, b):
+                a[k] = int(v)
+    # the last frame's flags: IC = the installed measurements (matching_sift_based.m:131-134), LI / HI as the updates left them
+    ic, lm_li, lm_hi = np.zeros(f.N, np.int32), np.zeros(f.N, np.int32), np.zeros(f.N, np.int32)
+    meas = np.asarray(f.meas_idx, np.int64)
+    if meas.size:
+        li, hi = f.get_flags()
+        ic[meas], lm_li[meas], lm_hi[meas] = 1, li, hi
+    for a, i1, l1, h1 in zip(out["features_info"], ic, lm_li, lm_hi):
+        a["individually_compatible"], a["low_innovation_inlier"], a["high_innovation_inlier"] = int(i1), int(l1), int(h1)
     return out

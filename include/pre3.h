@@ -296,8 +296,8 @@ PRE3_API int pre3_get_option(pre3_ctx *ctx, int option, int *value_out);
 /* These act on (x_k_k, p_k_k) between steps, as map_management.m:140 does, and keep P resident: P <- A P A' (+D) with
  * a sparse A (selection rows / the 6x13 and 3x6 Jacobians of the reference), evaluated by two gather passes through a
  * second ld x ld buffer (allocated on first use).  Per-landmark fields (h, H, S, z, flags) are cleared afterwards,
- * as update_features_info.m:30-44 does.  The POLICY (which landmarks to delete, which pixels to initialise) stays on
- * the host, as in delete_features.m:31-52 / initialize_features.m. */
+ * as update_features_info.m:30-44 does.  These calls take the POLICY (which landmarks to delete, which pixels to initialise)
+ * from the caller, as delete_features.m:31-52 / initialize_features.m decide it; pre3_map_policy below decides it on the device. */
 /* delete_features.m:54-74 -> delete_a_feature.m:47-51: remove landmarks del_idx[n_del] (ascending, 0-based). */
 PRE3_API int pre3_map_delete(pre3_ctx *ctx, int n_del, const int32_t *del_idx);
 /* add_features_inverse_depth.m:27-47 (hinv_my_version.m:26-53 + add_a_feature_covariance_inverse_depth.m:27-90):
@@ -316,6 +316,40 @@ PRE3_API int pre3_map_management(pre3_ctx *ctx, int n_del, const int32_t *del_id
                                  int n_new, const double *uvd, double std_pxl, const double *initial_rho);
 /* current landmark table: returns N, writes lm_type_out[N] if not NULL */
 PRE3_API int pre3_get_map(pre3_ctx *ctx, int32_t *lm_type_out);
+
+/* ---- the policy half of map_management.m:27-79 on the device ----------------------------------------- */
+/* The features_info bookkeeping: 4 int32 per landmark, {times_predicted, times_measured, init_frame, last_visible}, for landmarks
+ * first .. first+count-1.  A context has a book once pre3_set_book has been called (rows never set read 0), or when its map is empty at
+ * the first pre3_map_policy; pre3_set_map drops it.  On a booked context every map call (pre3_map_delete, _add_inverse_depth,
+ * _inversedepth_2_cartesian, pre3_map_management, pre3_map_policy) carries the book with the landmarks; landmarks they add get
+ * {0, 0, s, s}, s = the last pre3_map_policy's step - 1 (0 before any).  A booked context's pre3_step / pre3_step_predicted / pre3_rescue
+ * also record, per landmark, visibility at the x_k_k the rescue projects at (after the LI update, before the HI update) -- only in frames
+ * where rescue_hi_inliers.m runs (at least one measurement; pre3_step_all records nothing) -- as one small launch between the two
+ * updates; PRE3_OPT_STEP_TAIL has no such point, so a booked context's step takes the default form.  Every map call clears the record. */
+PRE3_API int pre3_set_book(pre3_ctx *ctx, int first, int count, const int32_t *book);
+PRE3_API int pre3_get_book(pre3_ctx *ctx, int first, int count, int32_t *book_out);     /* PRE3_E_STATE without a book */
+#define PRE3_POLICY_MAX_CANDIDATES 8192
+/* map_management.m:27-79 as ONE call, policy included (frame `step`, the loop variable of mono_slam.m:113):
+ *  1. last_visible = step - 1 for last frame's IC landmarks (matching_sift_based.m:133); delete_features.m:31-49 on the counters as they
+ *     stand (tm < 0.5 tp && tp > 5; step - init_frame > 20; N > 20 && step - last_visible > 20, N before deletion);
+ *  2. measured = surviving landmarks with LI || HI (:37-40); 3. survivors: tp += (h predicted), tm += (LI || HI) (update_features_info.m);
+ *  4. inversedepth_2_cartesian (convert_threshold < 0: skipped);
+ *  5. T = measured == 0 ? min_features : max(0, min_features - measured); the K candidates (distorted pixels cand_uv[2K], camera-frame
+ *     points cand_xyz[3K], descriptors cand_desc[128K] or NULL) are walked in the given order (the caller's Weighted_Smpl_wo_replacement
+ *     draw): a candidate is rejected when any landmark visible at x_k_k -- the map after step 4 and the features accepted before it --
+ *     lies strictly inside its box (semisizes 15 x 10 px), otherwise added with initial_rho = 1 / norm(xyz) and std_pxl; the walk ends when
+ *     T is met or the candidates run out.  strict_reference = 1 reproduces quirk Q13 (ceil(T/2) additions) and Q14 (the box centre is
+ *     (v, u)).  Additions also stop at the capacity.
+ * Outputs (any may be NULL): del_out[N] ascending 0-based (*n_del_out of them), accepted_out[K] candidate indices in order (*n_acc_out;
+ * they become landmarks N - n_del .. in that order), converted_out[N] per landmark before the call (a deleted one reads 0),
+ * stats = {measured, T, candidates examined, N after}.  No book: PRE3_E_STATE.  Non-finite uv, a zero or non-finite xyz norm, K above
+ * PRE3_POLICY_MAX_CANDIDATES or min_features above 1024: PRE3_E_ARG, before anything is launched (the context is unchanged).  The counters
+ * reach the book only with the map's re-layout: a call that fails before it leaves the book as it was.
+ * A deferred HI update is completed first and pending work flushed; x and P are what pre3_map_management gives with the same lists. */
+PRE3_API int pre3_map_policy(pre3_ctx *ctx, int step, int min_features, double convert_threshold, double std_pxl, int strict_reference,
+                             int K, const double *cand_uv, const double *cand_xyz, const double *cand_desc,
+                             int32_t *del_out, int32_t *n_del_out, int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out,
+                             int32_t stats[4]);
 
 /* ---- the IC-search stage on the device (search_IC_matches.m:31-44 + matching_sift_based.m:104-149) ---- */
 /* features_info(i).Descriptor (128 x 1 double each, add_feature_to_info_vector_my_version_sift.m): desc is 128 x count

@@ -14,6 +14,7 @@
  *   plots_complete.m:161-237        [xv, Pv] = pre3_mex('marginal', 0:6); s = pre3_mex('landmarks')     % without fetching P
  *   update(x_k_k, p_k_k, H, R, z, h) pre3_mex('update', H, R, z, h)             % in place on the resident estimate; R = [] for eye
  *   ekf_heading_update.m:27-52      applied = pre3_mex('heading', R_plane, 1)
+ *   map_management.m:27-79          [del, acc] = pre3_mex('map_policy', step, UV, XYZ, DESC, 50, 0.1, std_z, 1)   % policy on the device; pre3_mex('set_book', B) first
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
  * corrcoef_partitioned_mex.c:25-57).  NOT compiled in the build container (no MATLAB / mex.h there).
@@ -222,6 +223,39 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         out[0] = mxCreateDoubleMatrix(1, N, mxREAL);
         for (i = 0; i < N; ++i) mxGetPr(out[0])[i] = f[i];
         mxFree(d); mxFree(f); check(rc);
+    }
+    else if (!strcmp(cmd, "set_book")) {          /* pre3_mex('set_book', [tp; tm; init_frame; last_visible] (4xN) [, first (0-based)])   features_info's counters */
+        int k, i, rc; int32_t *b;
+        if (nin < 2) mexErrMsgTxt("pre3_mex('set_book', B [, first]): the book is missing");
+        k = (int)mxGetN(in[1]); b = (int32_t *)mxMalloc(sizeof(int32_t) * 4 * (k ? k : 1));
+        if (k > 0 && mxGetM(in[1]) != 4) mexErrMsgTxt("pre3_mex('set_book'): the book is 4 x N");
+        for (i = 0; i < 4 * k; ++i) b[i] = (int32_t)mxGetPr(in[1])[i];
+        rc = pre3_set_book(g_ctx, nin > 2 ? (int)mxGetScalar(in[2]) : 0, k, b); mxFree(b); check(rc);
+    }
+    else if (!strcmp(cmd, "book")) {              /* b = pre3_mex('book'): 4 x N [times_predicted; times_measured; init_frame; last_visible] */
+        int N = pre3_get_map(g_ctx, NULL), i, rc; int32_t *b = (int32_t *)mxCalloc(4 * (N ? N : 1), sizeof(int32_t));
+        rc = pre3_get_book(g_ctx, 0, N, b);
+        if (rc == PRE3_OK) { out[0] = mxCreateDoubleMatrix(4, N, mxREAL); for (i = 0; i < 4 * N; ++i) mxGetPr(out[0])[i] = b[i]; }
+        mxFree(b); check(rc);
+    }
+    else if (!strcmp(cmd, "map_policy")) {        /* [deleted, accepted, converted, stats] = pre3_mex('map_policy', step, UV (2xK), XYZ (3xK), DESC (128xK or []),
+                                                     min_features, linearity_thr (< 0: none), std_pxl, strict): map_management.m:27-79 with its policy; UV is
+                                                     UV_GoodFeaturesToInitialize(idx, 1:2)' (2xK, in Weighted_Smpl_wo_replacement's order); 1-based outputs */
+        int K, N, i, rc; int32_t nd = 0, na = 0, st[4] = { 0, 0, 0, 0 }, *dl, *acc, *cv;
+        if (nin != 9) mexErrMsgTxt("pre3_mex('map_policy', step, UV, XYZ, DESC, min_features, thr, std_pxl, strict): eight arguments");
+        K = (int)mxGetN(in[2]); N = pre3_get_map(g_ctx, NULL);
+        if ((K > 0 && mxGetM(in[2]) != 2) || (int)mxGetN(in[3]) != K || (K > 0 && mxGetM(in[3]) != 3)) mexErrMsgTxt("pre3_mex('map_policy'): UV is 2xK, XYZ 3xK");
+        if (!mxIsEmpty(in[4]) && ((int)mxGetN(in[4]) != K || mxGetM(in[4]) != 128)) mexErrMsgTxt("pre3_mex('map_policy'): DESC is 128xK or []");
+        dl = (int32_t *)mxCalloc(N ? N : 1, sizeof(int32_t)); acc = (int32_t *)mxCalloc(K ? K : 1, sizeof(int32_t)); cv = (int32_t *)mxCalloc(N ? N : 1, sizeof(int32_t));
+        rc = pre3_map_policy(g_ctx, (int)mxGetScalar(in[1]), (int)mxGetScalar(in[5]), mxGetScalar(in[6]), mxGetScalar(in[7]), (int)mxGetScalar(in[8]), K,
+                             mxGetPr(in[2]), mxGetPr(in[3]), mxIsEmpty(in[4]) ? NULL : mxGetPr(in[4]), dl, &nd, acc, &na, cv, st);
+        if (rc == PRE3_OK) {
+            out[0] = mxCreateDoubleMatrix(1, nd, mxREAL); for (i = 0; i < nd; ++i) mxGetPr(out[0])[i] = dl[i] + 1;
+            if (nout > 1) { out[1] = mxCreateDoubleMatrix(1, na, mxREAL); for (i = 0; i < na; ++i) mxGetPr(out[1])[i] = acc[i] + 1; }
+            if (nout > 2) { out[2] = mxCreateDoubleMatrix(1, N, mxREAL); for (i = 0; i < N; ++i) mxGetPr(out[2])[i] = cv[i]; }
+            if (nout > 3) { out[3] = mxCreateDoubleMatrix(1, 4, mxREAL); for (i = 0; i < 4; ++i) mxGetPr(out[3])[i] = st[i]; }
+        }
+        mxFree(dl); mxFree(acc); mxFree(cv); check(rc);
     }
     else if (!strcmp(cmd, "set_descriptors")) {   /* pre3_mex('set_descriptors', [features_info.Descriptor] (128xN), first (0-based)) */
         check(pre3_set_descriptors(g_ctx, nin > 2 ? (int)mxGetScalar(in[2]) : 0, (int)mxGetN(in[1]), mxGetPr(in[1])));
