@@ -1,5 +1,5 @@
-// pre3_api.hip -- the C ABI of include/pre3.h: context management, host<->device marshalling, and the
-// stage order of one filter step (mono_slam.m:153-187).  No compute happens on the host.
+// pre3_api.hip -- the C ABI of include/pre3.h: context management, the way into and out of every stateful call (EntryScope), host<->device
+// marshalling, the stateless drop-ins, matcher forwards and timers.  The stage order of a filter step is in pre3_step.hip.
 #include <time.h>
 #include <algorithm>
 #include <immintrin.h>
@@ -24,33 +24,6 @@ void set_error(const char *fmt, ...)
     va_end(ap);
 }
 
-// launchers defined in the kernel files
-int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection = false, size_t inbox_n16 = 0, int32_t inbox_seq = 0);
-IcMatchRide ic_match_ride(const pre3_ctx *c);
-int launch_inbox_pull(pre3_ctx *c, const void *src_host_mapped, void *dst_dev, size_t n16, int32_t seq, int slot = 10, int32_t *clear = nullptr, int n_clear = 0);
-int launch_slice_prepare(pre3_ctx *c, const void *src_host_mapped, size_t n16, int32_t seq, int n_zero, int k, int lo, int hi, int tag);   // (either direction: 16-byte words between device memory and a mapped pinned block, then `seq` into mailbox word `slot`)
-int launch_window_gate(pre3_ctx *c, int M, const int32_t *pred_idx_dev, const int32_t *k1_dev, const double *zc_dev, int strict, int32_t *accept_dev);
-int launch_build_rows_impl(pre3_ctx *c, int nsel, const int32_t *sel_dev, int r_pad);
-int launch_ransac_score_impl(pre3_ctx *c, int k, double threshold, int hyp_begin, int hyp_end, int ldg, int32_t *support_dev, uint32_t *mask_dev, int mask_words,
-                             int select_n_draw = 0, int early_exit = 0);
-int launch_ransac_select_impl(pre3_ctx *c, int n_draw, int k, int early_exit, int32_t *support_dev, const uint32_t *mask_dev, int mask_words, int err_idx = -1);
-int launch_fill_w(pre3_ctx *c, int r_pad);
-void release_scratch();
-int match_partial(int device, int cls, int ND, int K1, const void *L1, int K2, const void *L2, int k2_offset, double *best, double *second, int32_t *arg);
-int knn_run(int device, int D, int N, const double *data, int M, const double *query, int k, double *ids, double *dist);
-void *match_bench_create(int cls, int ND, int K1, const void *L1, int K2, const void *L2);
-int match_bench_info(void *h, int32_t info[3]);
-int match_bench_run(void *h, int reps, double *ms_per);
-int match_bench_fetch(void *h, double *best, double *second, int32_t *arg);
-void match_bench_destroy(void *h);
-void *match_shard_create(int device, int cls, int ND, int K1, const void *L1, int K2, const void *L2, int k2_offset);
-int match_shard_run(void *h, void **partial_dev, int *n_doubles);
-int match_shard_merge(void *h, int G, const void *gathered_dev, double thresh, double *pairs_out, double *score_out, int *M_out);
-void match_shard_destroy(void *h);
-int match_shard_set_comm(void *h, void *comm);
-int match_shard_match(void *h, double thresh, double *pairs_out, double *score_out, int *M_out);
-int match_shard_test_stall(void *h, int release);
-
 template <typename T> static int dmalloc(T **p, size_t count)
 {
     void *q = nullptr;
@@ -61,7 +34,7 @@ template <typename T> static int dmalloc(T **p, size_t count)
     *p = (T *)q;
     return PRE3_OK;
 }
-static int dmalloc_bytes(void **p, size_t bytes)
+int dmalloc_bytes(void **p, size_t bytes)
 {
     if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) { set_error("hipMalloc of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
     if (hipMemset(*p, 0, bytes ? bytes : 16) != hipSuccess) { (void)hipFree(*p); *p = nullptr; set_error("hipMemset failed"); return PRE3_E_HIP; }
@@ -70,35 +43,47 @@ static int dmalloc_bytes(void **p, size_t bytes)
 
 static int complete_deferred_hi(pre3_ctx *c)
 {
-    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
-    PRE3_HIP(hipSetDevice(c->device));
-    if (c->hi_pending) {                 // PRE3_OPT_DEFER_HI: the previous step's HI update is completed by whatever call comes next
-        c->hi_pending = false;
-        PRE3_TRY(pre3_update_hi(c));
-        c->last_n_hi = c->hi_from_host >= 0 ? c->hi_from_host : (c->hi_kernel ? c->mail_host[5] : 0);
+    if (c->carry.hi_pending) {           // PRE3_OPT_DEFER_HI: the previous step's HI update is completed by whatever call comes next
+        c->carry.hi_pending = false;
+        PRE3_TRY(update_hi_impl(c));
+        c->carry.last_n_hi = c->hi_from_host >= 0 ? c->hi_from_host : (c->hi_kernel ? c->mail_host[5] : 0);
     }
     return PRE3_OK;
 }
-// PRE3_OPT_PEND_HI: only pre3_step carries a pending HI down-date into its launches (pend_keep); for everybody else P is P before the call goes on.
+// PRE3_OPT_PEND_HI: only pre3_step carries a pending HI down-date into its launches (req.pend_keep); for everybody else P is P before the call goes on.
 // The marginal readers (pre3_get_landmarks / pre3_get_marginal) complete a deferred HI update as pre3_step would and leave its rows/cols 3..6 pass
 // pending for the next prediction's launch, as pre3_step would: whoever else comes next runs that pass first (k_jnorm_P, behind the flush it makes).
 int flush_unless_kept(pre3_ctx *c)
 {
-    if (c->jn_pending && !c->leave_jn_to_predict) { c->jn_pending = false; PRE3_TRY(launch_jnorm(c, 0)); }
-    if (c->pend_rows > 0 && !c->pend_keep) PRE3_TRY(pend_flush(c));
+    if (c->carry.jn_pending && !c->req.leave_jn_to_predict) { c->carry.jn_pending = false; PRE3_TRY(launch_jnorm(c, 0)); }
+    if (c->carry.pend_rows > 0 && !c->req.pend_keep) PRE3_TRY(pend_flush(c));
     return PRE3_OK;
 }
-static int check_ctx(pre3_ctx *c)
-{
-    PRE3_TRY(complete_deferred_hi(c));
-    return flush_unless_kept(c);
-}
-int settle_ctx(pre3_ctx *c) { return check_ctx(c); }
+void drop_carried(pre3_ctx *c) { c->carry = {}; }
 // PRE3_FUSE_JN (default 1): the rows/cols 3..6 pass of a HI update completed at the start of a step rides in that step's prediction launch
 static bool fuse_jn_env()
 {
     static const int v = getenv("PRE3_FUSE_JN") ? atoi(getenv("PRE3_FUSE_JN")) : 1;
     return v != 0;
+}
+static int enter_ctx(pre3_ctx *c, Entry kind, bool pend_keep)
+{
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_HIP(hipSetDevice(c->device));
+    // step: the completed update's rows/cols 3..6 pass (or one a reader has left pending since) is left to the prediction's launch (PRE3_FUSE_JN=0: its own launch)
+    c->req.leave_jn_to_predict = kind != Entry::ordinary && fuse_jn_env() && (c->carry.hi_pending || (kind == Entry::step && c->carry.jn_pending));
+    c->req.pend_keep = pend_keep;
+    int rc = complete_deferred_hi(c);
+    if (rc == PRE3_OK && kind != Entry::reader) rc = flush_unless_kept(c);
+    c->req.leave_jn_to_predict = false;
+    return rc;
+}
+EntryScope::EntryScope(pre3_ctx *c_, Entry kind_, bool pend_keep) : c(c_), kind(kind_), rc(enter_ctx(c_, kind_, pend_keep)) {}
+EntryScope::~EntryScope()
+{
+    if (c == nullptr) return;
+    if (c->carry.jn_pending && !(kind == Entry::reader && rc == PRE3_OK)) { c->carry.jn_pending = false; (void)launch_jnorm(c, 0); }
+    c->req = {}; c->out = {};
 }
 
 // Poll the pinned mailbox until the kernel that was launched with sequence number `seq` has published.
@@ -127,7 +112,7 @@ int stream_drain_on(hipStream_t st, void *comm, const char *what)
     }
 }
 int stream_drain(pre3_ctx *c, const char *what) { return stream_drain_on(c->stream, c->comm, what); }
-static int wait_mail(pre3_ctx *c, int slot, int32_t seq)
+int wait_mail(pre3_ctx *c, int slot, int32_t seq)
 {
     volatile int32_t *w = c->mail_host + slot;
     // With a communicator on the context the awaited kernel may sit behind a collective: a peer that stalls (or never entered) must not hang this
@@ -160,14 +145,13 @@ static int wait_mail(pre3_ctx *c, int slot, int32_t seq)
     return PRE3_OK;
 }
 
-// the device's error words, once a copy of them into pinned_stats has completed
-static int stats_words(pre3_ctx *c)
+int stats_words(pre3_ctx *c)
 {
     PRE3_CHECK(c->pinned_stats[7] == 0, PRE3_E_HIP, "a device-side wait on another workgroup gave up (counter never arrived): results are invalid");
     PRE3_CHECK(c->pinned_stats[6] == 0, PRE3_E_NUMERIC, "innovation covariance S is not positive definite");
     return PRE3_OK;
 }
-static int fetch_stats(pre3_ctx *c)
+int fetch_stats(pre3_ctx *c)
 {
     PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
     PRE3_TRY(stream_drain(c, __func__));
@@ -230,6 +214,43 @@ int launch_pull(pre3_ctx *c, const void *pinned_host, void *dst_dev, size_t byte
     hipLaunchKernelGGL(k_scan_pull, dim3(ceil_div(n16, 256)), dim3(256), 0, c->stream, (const int4 *)src_dev, n16, (int4 *)dst_dev, 0, (int4 *)nullptr,
                        done_slot >= 0 ? stage_done(c, done_slot) : StageDone{ nullptr, nullptr, 0 });
     PRE3_HIP(hipGetLastError());
+    return PRE3_OK;
+}
+
+// see pre3_internal.h: ONE pull of [meas | ic | (hyp) | z]; hyp (n_hyp_ints ints) optional
+int install_measurements(pre3_ctx *c, int m, const int32_t *meas_idx, const double *z, const int32_t *hyp, int n_hyp_ints, bool flags_clear, bool pull, size_t *nbytes_out)
+{
+    PRE3_CHECK(m >= 0 && m <= c->capm, PRE3_E_ARG, "measurements: m=%d exceeds capacity %d", m, c->capm);
+    for (int j = 0; j < m; ++j) {
+        PRE3_CHECK(meas_idx[j] >= 0 && meas_idx[j] < c->N, PRE3_E_ARG, "measurements: landmark index %d out of range", meas_idx[j]);
+        PRE3_CHECK(j == 0 || meas_idx[j] > meas_idx[j - 1], PRE3_E_ARG, "measurements: landmark indices must be strictly ascending");
+    }
+    // the previous pull out of the pinned inbox must have completed before the host overwrites it (it has, a whole step ago: the pull
+    // kernel publishes its sequence number in mailbox word 10, so this is one read of host memory -- no event, whose record would put
+    // a barrier packet into the stream -- and, unlike a stream sync, it does not wait for the kernels queued since)
+    if (c->inbox_pending) { PRE3_TRY(wait_mail(c, 10, c->seq_inbox)); c->inbox_pending = false; }
+    c->m = m; c->meas_host.assign(meas_idx, meas_idx + m);
+    c->carry.select_pending = false;
+    int32_t *hm = (int32_t *)(c->inbox_host + c->off_meas), *hic = (int32_t *)(c->inbox_host + c->off_ic);
+    double *hz = (double *)(c->inbox_host + c->off_z);
+    memset(hic, 0, sizeof(int32_t) * c->N);
+    for (int j = 0; j < m; ++j) { hm[j] = meas_idx[j]; hic[meas_idx[j]] = 1; }
+    if (z) {
+        memset(hz, 0, sizeof(double) * 2 * c->N);
+        for (int j = 0; j < m; ++j) { hz[2 * meas_idx[j]] = z[2 * j]; hz[2 * meas_idx[j] + 1] = z[2 * j + 1]; }
+    }
+    if (hyp) memcpy(c->inbox_host + c->off_hyp, hyp, sizeof(int32_t) * n_hyp_ints);
+    // The inbox crosses PCIe by a KERNEL that reads the pinned, device-mapped host buffer (14 KB at N=500): a hipMemcpyAsync between
+    // kernels is a blit with barrier packets on both sides and opened two ~10 us holes in the stream around a 3 us copy.
+    const size_t nbytes = z ? c->off_z + sizeof(double) * 2 * c->N : c->off_hyp + (hyp ? sizeof(int32_t) * n_hyp_ints : 0);
+    // (the inlier flags behind the inbox are cleared by the pull's own workgroup: a hipMemsetAsync is a fill kernel between barrier packets)
+    int32_t *const flags = (int32_t *)((unsigned char *)c->inbox_dev + c->off_flags);
+    if (pull) { PRE3_TRY(launch_inbox_pull(c, c->inbox_host_dev, c->inbox_dev, (nbytes + 15) / 16, ++c->seq_inbox, 10, flags_clear ? nullptr : flags, flags_clear ? 0 : (int)(c->flags_bytes / 4))); c->inbox_pending = true; }
+    if (nbytes_out) *nbytes_out = nbytes;
+    if (!flags_clear && !pull) PRE3_HIP(hipMemsetAsync(flags, 0, c->flags_bytes, c->stream));
+    c->li_from_host = c->hi_from_host = -1; c->li_kernel = c->hi_kernel = false;
+    c->hp_all_valid = false;
+    c->measurements_set = true;
     return PRE3_OK;
 }
 
@@ -508,7 +529,7 @@ int pre3_destroy(pre3_ctx *c)
 
 int pre3_set_option(pre3_ctx *c, int option, int value)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     switch (option) {
     case PRE3_OPT_DEFER_HI: c->defer_hi = value != 0; return PRE3_OK;
     case PRE3_OPT_K9_BF16X3: c->k9_b3 = value != 0 && c->dtype == PRE3_F32 && c->Wp != nullptr; return PRE3_OK;
@@ -548,14 +569,14 @@ int pre3_get_option(pre3_ctx *c, int option, int *value_out)
 
 int pre3_sync(pre3_ctx *c)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_TRY(stream_drain(c, __func__));
     return PRE3_OK;
 }
 
 int pre3_set_cam(pre3_ctx *c, const pre3_cam *cam)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(cam != nullptr && cam->f > 0, PRE3_E_ARG, "pre3_set_cam: invalid camera");
     c->cam = *cam; c->have_cam = true;
     return PRE3_OK;
@@ -563,7 +584,7 @@ int pre3_set_cam(pre3_ctx *c, const pre3_cam *cam)
 
 int pre3_set_map(pre3_ctx *c, int N, const int32_t *lm_type)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(N >= 0 && N <= c->capN, PRE3_E_ARG, "pre3_set_map: N=%d exceeds capacity %d", N, c->capN);
     PRE3_CHECK(N == 0 || lm_type != nullptr, PRE3_E_ARG, "pre3_set_map: null type list");
     std::vector<int32_t> off(N ? N : 1);
@@ -597,20 +618,15 @@ int pre3_state_size(pre3_ctx *c) { return c ? c->n : PRE3_E_ARG; }
 
 int pre3_set_state(pre3_ctx *c, int which, int n, const double *x, const double *P)
 {
-    {
-        // a fresh state also clears what an earlier state left in the device's error words (a factorisation that was not positive definite, a
-        // wait that gave up): the deferred work of the old state is dropped with them
-        const int rc0 = check_ctx(c);
-        if (c && rc0 != PRE3_OK && rc0 != PRE3_E_NUMERIC && rc0 != PRE3_E_HIP) return rc0;
-        if (c) {
-            PRE3_HIP(hipSetDevice(c->device));
-            (void)stream_drain(c, __func__);
-            (void)hipMemsetAsync(c->stats + 6, 0, sizeof(int32_t) * 2, c->stream);
-            if (c->mail_host) { c->mail_host[6] = 0; c->mail_host[7] = 0; }
-            c->jn_pending = false; c->hi_pending = false; c->tail_done = false; c->hi_fused = false; c->pend_rows = 0; c->hi_pend_launched = false;
-        }
-    }
-    PRE3_TRY(check_ctx(c));
+    // a fresh state also clears what an earlier state left in the device's error words (a factorisation that was not positive definite, a
+    // wait that gave up): the deferred work of the old state is dropped with them
+    EntryScope scope(c);
+    if (c == nullptr || (scope.rc != PRE3_OK && scope.rc != PRE3_E_NUMERIC && scope.rc != PRE3_E_HIP)) return scope.rc;
+    PRE3_HIP(hipSetDevice(c->device));
+    (void)stream_drain(c, __func__);
+    (void)hipMemsetAsync(c->stats + 6, 0, sizeof(int32_t) * 2, c->stream);
+    if (c->mail_host) { c->mail_host[6] = 0; c->mail_host[7] = 0; }
+    drop_carried(c);
     PRE3_CHECK(which == PRE3_X_K_K || which == PRE3_X_K_KM1, PRE3_E_ARG, "pre3_set_state: bad selector");
     PRE3_CHECK(n == c->n, PRE3_E_ARG, "pre3_set_state: n=%d but the map defines n=%d", n, c->n);
     PRE3_CHECK(x && P, PRE3_E_ARG, "pre3_set_state: null pointer");
@@ -631,7 +647,7 @@ int pre3_set_state(pre3_ctx *c, int which, int n, const double *x, const double 
 
 int pre3_get_state(pre3_ctx *c, int which, int n, double *x, double *P)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(which == PRE3_X_K_K || which == PRE3_X_K_KM1, PRE3_E_ARG, "pre3_get_state: bad selector");
     PRE3_CHECK(n == c->n, PRE3_E_ARG, "pre3_get_state: n=%d but the map defines n=%d", n, c->n);
     PRE3_CHECK(c->x_valid[which], PRE3_E_STATE, "pre3_get_state: that estimate has not been computed");
@@ -660,17 +676,13 @@ static int reader_precheck(pre3_ctx *c, int which, const char *who)
     PRE3_CHECK(c->p_which == which, PRE3_E_STATE, "%s: the covariance buffer currently holds the other estimate (it is updated in place)", who);
     return PRE3_OK;
 }
-// A deferred HI update is completed as pre3_step would complete it (its rows/cols 3..6 pass left to the next prediction's launch), and nothing
-// pending is flushed: the filter's next step runs exactly as it would have without the read.  Returns the pending pass's Jn on the device, or null.
+// Entry::reader has completed a deferred HI update as pre3_step would complete it (its rows/cols 3..6 pass left to the next prediction's launch) and
+// flushed nothing that is pending: the filter's next step runs exactly as it would have without the read.  Returns the pending pass's Jn on the device, or null.
 static int reader_settle(pre3_ctx *c, const double **jn)
 {
-    c->leave_jn_to_predict = fuse_jn_env() && c->hi_pending;
-    const int rc = complete_deferred_hi(c);
-    c->leave_jn_to_predict = false;
-    if (rc != PRE3_OK) { if (c->jn_pending) { c->jn_pending = false; (void)launch_jnorm(c, 0); } return rc; }
     // fetch_stats with the reader's own synchronisation: the error words leave in front of the gather, and are checked once the stream has drained
     PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
-    *jn = c->jn_pending ? c->pred_params + 16 : nullptr;           // (k_jnorm_P's Jn: params[16..31])
+    *jn = c->carry.jn_pending ? c->pred_params + 16 : nullptr;     // (k_jnorm_P's Jn: params[16..31])
     return PRE3_OK;
 }
 static int reader_finish(pre3_ctx *c, int rc)
@@ -684,7 +696,7 @@ int pre3_get_landmarks(pre3_ctx *c, int which, int first, int count, double *xyz
 {
     PRE3_TRY(reader_precheck(c, which, "pre3_get_landmarks"));
     PRE3_CHECK(first >= 0 && count >= 0 && (long long)first + count <= c->N, PRE3_E_ARG, "pre3_get_landmarks: landmarks %d .. %d outside the map (N=%d)", first, first + count - 1, c->N);
-    PRE3_HIP(hipSetDevice(c->device));
+    EntryScope scope(c, Entry::reader); PRE3_TRY(scope.rc);
     const double *jn = nullptr;
     PRE3_TRY(reader_settle(c, &jn));
     return reader_finish(c, c->N == 0 ? PRE3_OK : read_landmarks(c, which, first, count, xyz, cov_xyz, cov_native, linearity));
@@ -697,7 +709,7 @@ int pre3_get_marginal(pre3_ctx *c, int which, int k, const int32_t *idx, double 
     PRE3_CHECK(ceil_div(k, 16) <= 65535, PRE3_E_ARG, "pre3_get_marginal: k=%d indices exceed the launch grid", k);
     for (int t = 0; t < k; ++t)
         PRE3_CHECK(idx[t] >= 0 && idx[t] < c->n, PRE3_E_ARG, "pre3_get_marginal: index %d outside the state (n=%d)", idx[t], c->n);
-    PRE3_HIP(hipSetDevice(c->device));
+    EntryScope scope(c, Entry::reader); PRE3_TRY(scope.rc);
     const double *jn = nullptr;
     PRE3_TRY(reader_settle(c, &jn));
     return reader_finish(c, read_marginal(c, which, k, idx, jn, x_out, P_out));
@@ -705,7 +717,7 @@ int pre3_get_marginal(pre3_ctx *c, int which, int k, const int32_t *idx, double 
 
 int pre3_predict(pre3_ctx *c, const double u[7])
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(u != nullptr, PRE3_E_ARG, "pre3_predict: null u");
     PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "pre3_predict: needs (x_k_k, p_k_k) on the device");
     PRE3_TRY(launch_predict_impl(c, u));
@@ -715,7 +727,7 @@ int pre3_predict(pre3_ctx *c, const double u[7])
 
 int pre3_project(pre3_ctx *c, int which, int clear_first)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(which == PRE3_X_K_K || which == PRE3_X_K_KM1, PRE3_E_ARG, "pre3_project: bad selector");
     PRE3_CHECK(c->have_cam, PRE3_E_STATE, "pre3_project: camera not set");
     PRE3_CHECK(c->x_valid[which], PRE3_E_STATE, "pre3_project: that estimate is not on the device");
@@ -727,7 +739,7 @@ int pre3_project(pre3_ctx *c, int which, int clear_first)
 
 int pre3_innovation(pre3_ctx *c)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(c->projected, PRE3_E_STATE, "pre3_innovation: call pre3_project first");
     if (c->N == 0) return PRE3_OK;
     PRE3_TRY(launch_innovation(c, 0, 0.0));
@@ -737,7 +749,7 @@ int pre3_innovation(pre3_ctx *c)
 
 int pre3_get_landmark_fields(pre3_ctx *c, double *h, int32_t *has_h, double *Hc, double *Hl, double *S)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_TRY(stream_drain(c, __func__));
     int N = c->N;
     if (N == 0) return PRE3_OK;
@@ -749,56 +761,16 @@ int pre3_get_landmark_fields(pre3_ctx *c, double *h, int32_t *has_h, double *Hc,
     return PRE3_OK;
 }
 
-// Fill the pinned inbox and ship it with ONE async copy: [meas | ic | (hyp) | z].  hyp (n_hyp_ints ints) optional.
-// pull == false: the inbox is filled and the context updated, but no pull is launched: the caller's next launch carries it (pre3_step: k_predict);
-// *nbytes_out = what that pull must copy
-static int install_measurements(pre3_ctx *c, int m, const int32_t *meas_idx, const double *z /* 2m, null: z already on device */,
-                                const int32_t *hyp, int n_hyp_ints, bool flags_clear = false, bool pull = true, size_t *nbytes_out = nullptr)
-{
-    PRE3_CHECK(m >= 0 && m <= c->capm, PRE3_E_ARG, "measurements: m=%d exceeds capacity %d", m, c->capm);
-    for (int j = 0; j < m; ++j) {
-        PRE3_CHECK(meas_idx[j] >= 0 && meas_idx[j] < c->N, PRE3_E_ARG, "measurements: landmark index %d out of range", meas_idx[j]);
-        PRE3_CHECK(j == 0 || meas_idx[j] > meas_idx[j - 1], PRE3_E_ARG, "measurements: landmark indices must be strictly ascending");
-    }
-    // the previous pull out of the pinned inbox must have completed before the host overwrites it (it has, a whole step ago: the pull
-    // kernel publishes its sequence number in mailbox word 10, so this is one read of host memory -- no event, whose record would put
-    // a barrier packet into the stream -- and, unlike a stream sync, it does not wait for the kernels queued since)
-    if (c->inbox_pending) { PRE3_TRY(wait_mail(c, 10, c->seq_inbox)); c->inbox_pending = false; }
-    c->m = m; c->meas_host.assign(meas_idx, meas_idx + m);
-    c->select_pending = false;
-    int32_t *hm = (int32_t *)(c->inbox_host + c->off_meas), *hic = (int32_t *)(c->inbox_host + c->off_ic);
-    double *hz = (double *)(c->inbox_host + c->off_z);
-    memset(hic, 0, sizeof(int32_t) * c->N);
-    for (int j = 0; j < m; ++j) { hm[j] = meas_idx[j]; hic[meas_idx[j]] = 1; }
-    if (z) {
-        memset(hz, 0, sizeof(double) * 2 * c->N);
-        for (int j = 0; j < m; ++j) { hz[2 * meas_idx[j]] = z[2 * j]; hz[2 * meas_idx[j] + 1] = z[2 * j + 1]; }
-    }
-    if (hyp) memcpy(c->inbox_host + c->off_hyp, hyp, sizeof(int32_t) * n_hyp_ints);
-    // The inbox crosses PCIe by a KERNEL that reads the pinned, device-mapped host buffer (14 KB at N=500): a hipMemcpyAsync between
-    // kernels is a blit with barrier packets on both sides and opened two ~10 us holes in the stream around a 3 us copy.
-    const size_t nbytes = z ? c->off_z + sizeof(double) * 2 * c->N : c->off_hyp + (hyp ? sizeof(int32_t) * n_hyp_ints : 0);
-    // (the inlier flags behind the inbox are cleared by the pull's own workgroup: a hipMemsetAsync is a fill kernel between barrier packets)
-    int32_t *const flags = (int32_t *)((unsigned char *)c->inbox_dev + c->off_flags);
-    if (pull) { PRE3_TRY(launch_inbox_pull(c, c->inbox_host_dev, c->inbox_dev, (nbytes + 15) / 16, ++c->seq_inbox, 10, flags_clear ? nullptr : flags, flags_clear ? 0 : (int)(c->flags_bytes / 4))); c->inbox_pending = true; }
-    if (nbytes_out) *nbytes_out = nbytes;
-    if (!flags_clear && !pull) PRE3_HIP(hipMemsetAsync(flags, 0, c->flags_bytes, c->stream));
-    c->li_from_host = c->hi_from_host = -1; c->li_kernel = c->hi_kernel = false;
-    c->hp_all_valid = false;
-    c->measurements_set = true;
-    return PRE3_OK;
-}
-
 int pre3_set_measurements(pre3_ctx *c, int m, const int32_t *meas_idx, const double *z)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(m == 0 || (meas_idx && z), PRE3_E_ARG, "pre3_set_measurements: null pointer");
     return install_measurements(c, m, meas_idx, z, nullptr, 0);
 }
 
 int pre3_window_gate(pre3_ctx *c, int M, const int32_t *k1, const double *zc, int strict_reference, int32_t *accept_out)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(c->projected, PRE3_E_STATE, "pre3_window_gate: call pre3_project / pre3_innovation first");
     PRE3_CHECK(M >= 0 && (M == 0 || (k1 && zc)), PRE3_E_ARG, "pre3_window_gate: bad arguments");
     int N = c->N;
@@ -923,9 +895,9 @@ static int stage_release(pre3_ctx *c, int slot)        // (the pull launched wit
     return PRE3_OK;
 }
 
-int pre3_set_descriptors(pre3_ctx *c, int first, int count, const double *desc)
+}  // extern "C"
+int pre3::set_descriptors_impl(pre3_ctx *c, int first, int count, const double *desc)
 {
-    PRE3_TRY(check_ctx(c));
     PRE3_CHECK(first >= 0 && count >= 0 && first + count <= c->N && (count == 0 || desc), PRE3_E_ARG, "pre3_set_descriptors: range [%d, %d) outside the map (N=%d)", first, first + count, c->N);
     PRE3_TRY(ensure_ic_buffers(c));
     bool ok = true;
@@ -946,10 +918,17 @@ int pre3_set_descriptors(pre3_ctx *c, int first, int count, const double *desc)
     else if (first == 0 && count >= c->N) c->bank_ok = true;
     return PRE3_OK;
 }
+extern "C" {
+
+int pre3_set_descriptors(pre3_ctx *c, int first, int count, const double *desc)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return set_descriptors_impl(c, first, count, desc);
+}
 
 int pre3_get_descriptors(pre3_ctx *c, int first, int count, double *desc)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(first >= 0 && count >= 0 && first + count <= c->N && (count == 0 || desc), PRE3_E_ARG, "pre3_get_descriptors: range outside the map");
     PRE3_CHECK(c->bank_set, PRE3_E_STATE, "pre3_get_descriptors: no descriptors have been set");
     PRE3_TRY(stream_drain(c, __func__));
@@ -959,7 +938,7 @@ int pre3_get_descriptors(pre3_ctx *c, int first, int count, double *desc)
 
 int pre3_set_scan(pre3_ctx *c, int K2, const double *descriptor_raw, const double *scale_orient_pos_raw)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(K2 >= 0 && (K2 == 0 || (descriptor_raw && scale_orient_pos_raw)), PRE3_E_ARG, "pre3_set_scan: bad arguments");
     if (K2 > c->scan_cap) {
         PRE3_TRY(stream_drain(c, __func__));             // (the buffers being replaced may still be read by queued kernels)
@@ -1008,7 +987,7 @@ int pre3_set_scan(pre3_ctx *c, int K2, const double *descriptor_raw, const doubl
 int pre3_ic_search(pre3_ctx *c, double thresh, int strict_reference, int32_t *n_matches_out, int32_t *m_out, int32_t *meas_idx_out,
                    double *z_out, int32_t *pairs_out)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(c->bank_set, PRE3_E_STATE, "pre3_ic_search: call pre3_set_descriptors first");
     PRE3_CHECK(c->scan_K2 >= 0 && (c->scan_K2 == 0 || c->scan_desc), PRE3_E_STATE, "pre3_ic_search: call pre3_set_scan first");
     PRE3_CHECK(c->x_valid[PRE3_X_K_KM1] && c->p_which == PRE3_X_K_KM1, PRE3_E_STATE, "pre3_ic_search: needs the predicted estimate (call pre3_predict first)");
@@ -1053,143 +1032,9 @@ int pre3_ic_search(pre3_ctx *c, double thresh, int strict_reference, int32_t *n_
     return install_measurements(c, (int)meas.size(), meas.data(), nullptr, nullptr, 0);
 }
 
-// ---- RANSAC ---------------------------------------------------------------------------------------
-// zero_words > 0 (the sliced forms): that many words of c->support (supports, masks [, the missing-slice word]) are cleared on the way
-static int ransac_prepare(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, int lo = 0, int hi = -1, bool slice_form = false, size_t zero_words = 0)
-{
-    PRE3_CHECK(c->measurements_set && c->projected, PRE3_E_STATE, "ransac: needs pre3_project and measurements");
-    PRE3_CHECK(c->p_which == PRE3_X_K_KM1, PRE3_E_STATE, "ransac: needs the predicted estimate (call pre3_predict or set x_k_km1)");
-    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph, PRE3_E_ARG, "ransac: n_draw=%d exceeds capacity %d", n_draw, c->caph);
-    PRE3_CHECK(k >= 1 && k <= MAXK, PRE3_E_ARG, "ransac: k=%d unsupported (1..%d)", k, MAXK);
-    PRE3_CHECK(hyp != nullptr, PRE3_E_ARG, "ransac: null hypothesis table");
-    PRE3_CHECK(c->m >= k, PRE3_E_ARG, "ransac: %d measurements but k=%d", c->m, k);
-    for (int i = 0; i < n_draw * k; ++i) PRE3_CHECK(hyp[i] >= 0 && hyp[i] < c->m, PRE3_E_ARG, "ransac: hyp[%d]=%d not a position in the IC list (m=%d)", i, hyp[i], c->m);
-    if (hi < 0) hi = n_draw;
-    const bool sliced = lo > 0 || hi < n_draw || slice_form;
-    const bool need_pull = hyp != (const int32_t *)(c->inbox_host + c->off_hyp);       // not already shipped with the measurements
-    if (need_pull) {
-        if (c->inbox_pending) { PRE3_TRY(wait_mail(c, 10, c->seq_inbox)); c->inbox_pending = false; }
-        memcpy(c->inbox_host + c->off_hyp, hyp, sizeof(int32_t) * n_draw * k);
-    }
-    if (sliced) {
-        // one launch: the clear, the pull and the marks of the measurements this slice's hypotheses draw (k_slice_prepare)
-        ++c->need_tag;
-        PRE3_TRY(launch_slice_prepare(c, (const unsigned char *)c->inbox_host_dev + c->off_hyp, need_pull ? (sizeof(int32_t) * n_draw * k + 15) / 16 : 0,
-                                      need_pull ? ++c->seq_inbox : c->seq_inbox, (int)zero_words, k, lo, hi, c->need_tag));
-        if (need_pull) c->inbox_pending = true;
-    } else {
-        if (zero_words) PRE3_HIP(hipMemsetAsync(c->support, 0, sizeof(int32_t) * zero_words, c->stream));
-        // (need_pull: the caller's table crosses PCIe as a rider of the H*P launch below -- its first reader is the scorer behind that launch)
-    }
-    c->masks = reinterpret_cast<uint32_t *>(c->support + round_up(n_draw, 4));
-    c->scored_n_draw = n_draw; c->scored_k = k;         // the mask offset depends on n_draw: select / export / import must use the same
-    int r = 2 * c->m, r_pad = round_up(r, NB);
-    static const int inline_g_env = getenv("PRE3_INLINE_G") ? atoi(getenv("PRE3_INLINE_G")) : 1;
-    const bool inline_g = inline_g_env != 0;
-    if (sliced) {
-        // a rank's slice of a sharded round: H*P and H*P*H' only for the measurements its hypotheses draw (the scorer of hypothesis h
-        // reads the 2k rows of its own landmarks and the entries of G among them, nothing else) -- the part of the round that
-        // shrinks with the number of ranks.  The LI update must not gather from these partial products: hp_all_valid stays false.
-        PRE3_TRY(launch_ell_HP_build(c, c->HP, c->need, c->need_tag));
-        if (!inline_g) PRE3_TRY(launch_ell_G_hyp(c, k, lo, hi, r_pad));
-        c->g_valid = !inline_g;
-        c->hp_all_valid = false;
-        return PRE3_OK;
-    }
-    if (need_pull) {
-        static const int ride_env = getenv("PRE3_HYP_RIDE") ? atoi(getenv("PRE3_HYP_RIDE")) : 1;      // 0: the pull as a launch of its own (rounds 2-4)
-        const size_t n16 = (sizeof(int32_t) * n_draw * k + 15) / 16;
-        if (ride_env) {
-            const InboxRide ib{ (const int4 *)((const unsigned char *)c->inbox_host_dev + c->off_hyp), (int4 *)c->hyp, (int)n16, c->mail_dev, ++c->seq_inbox, 10, nullptr, 0 };
-            c->inbox_pending = true;
-            PRE3_TRY(launch_ell_HP_build(c, c->HP, nullptr, 0, &ib));
-        } else {
-            PRE3_TRY(launch_inbox_pull(c, (const unsigned char *)c->inbox_host_dev + c->off_hyp, c->hyp, n16, ++c->seq_inbox)); c->inbox_pending = true;
-            PRE3_TRY(launch_ell_HP_build(c, c->HP));
-        }
-    } else
-    PRE3_TRY(launch_ell_HP_build(c, c->HP));
-    // H*P*H' of all measured rows is no longer built (6.6 us of launch in front of the scoring, PRE3_INLINE_G=0 brings it back): the scorer
-    // computes the (2k)^2 entries among its hypothesis' rows and the LI gather the entries of S it needs, both with k_ell_G's sum
-    if (!inline_g) PRE3_TRY(launch_ell_G(c, r, c->HP, c->G, r_pad, 0, nullptr, true));      // lower triangle: the scorer and the LI gather read (max, min)
-    c->g_valid = !inline_g;
-    c->hp_all_valid = true;
-    return PRE3_OK;
-}
-
-int pre3_ransac_score(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, double threshold, int hyp_begin, int hyp_end,
-                      void **support_dev, void **mask_dev, int *mask_words)
-{
-    PRE3_TRY(check_ctx(c));
-    PRE3_CHECK(hyp_begin >= 0 && hyp_begin <= hyp_end && hyp_end <= n_draw, PRE3_E_ARG, "ransac: bad hypothesis range [%d,%d) of %d", hyp_begin, hyp_end, n_draw);
-    int words = ceil_div(c->m, 32);
-    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph, PRE3_E_ARG, "ransac: n_draw=%d exceeds capacity %d", n_draw, c->caph);
-    PRE3_TRY(ransac_prepare(c, n_draw, k, hyp, hyp_begin, hyp_end, false, (size_t)round_up(n_draw, 4) + (size_t)n_draw * words));   // (supports + masks cleared on the way)
-    PRE3_TRY(launch_ransac_score_impl(c, k, threshold, hyp_begin, hyp_end, round_up(2 * c->m, NB), c->support, c->masks, words));
-    if (support_dev) *support_dev = c->support;
-    if (mask_dev) *mask_dev = c->masks;
-    if (mask_words) *mask_words = words;
-    PRE3_TRY(stream_drain(c, __func__));     // the caller's collective runs on another stream
-    return PRE3_OK;
-}
-
-// after the selection stage has been enqueued (its own kernel, or the tail of the scoring launch)
-static int ransac_results(pre3_ctx *c, int n_draw, int32_t *support, int32_t *li_mask, int32_t stats[4])
-{
-    c->li_from_host = -1; c->li_kernel = true;
-    if (support || li_mask) {
-        // (behind a collective the synchronisation comes second: the selection's mailbox word first, under the communicator's deadline)
-        if (c->shard_round) PRE3_TRY(wait_mail(c, 8, c->seq_select));
-        PRE3_TRY(stream_drain(c, __func__));
-        if (support) PRE3_HIP(hipMemcpy(support, c->support, sizeof(int32_t) * n_draw, hipMemcpyDeviceToHost));
-        if (li_mask && c->m) PRE3_HIP(hipMemcpy(li_mask, c->li_meas, sizeof(int32_t) * c->m, hipMemcpyDeviceToHost));
-    }
-    if (stats) {
-        PRE3_TRY(wait_mail(c, 8, c->seq_select));
-        PRE3_CHECK(!c->shard_round || c->mail_host[11] == 0, PRE3_E_COMM, "sharded RANSAC: a rank failed before the collective of this round (its slice is missing from the sums)");
-        for (int i = 0; i < 4; ++i) stats[i] = c->mail_host[i];
-    }
-    return PRE3_OK;
-}
-
-int pre3_ransac_select(pre3_ctx *c, int n_draw, int k, int early_exit, int32_t *support, int32_t *li_mask, int32_t stats[4])
-{
-    PRE3_TRY(check_ctx(c));
-    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph, PRE3_E_ARG, "ransac: n_draw out of range");
-    PRE3_CHECK(n_draw == c->scored_n_draw && k == c->scored_k, PRE3_E_STATE, "pre3_ransac_select: n_draw=%d, k=%d differs from the scored round (n_draw=%d, k=%d): the mask buffer is laid out for that round", n_draw, k, c->scored_n_draw, c->scored_k);
-    int words = ceil_div(c->m, 32);
-    PRE3_TRY(launch_ransac_select_impl(c, n_draw, k, early_exit, c->support, c->masks, words));
-    return ransac_results(c, n_draw, support, li_mask, stats);
-}
-
-int pre3_ransac_export(pre3_ctx *c, int n_draw, void *support_dst_dev, void *mask_dst_dev)
-{
-    PRE3_TRY(check_ctx(c));
-    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph, PRE3_E_ARG, "ransac: n_draw out of range");
-    PRE3_CHECK(n_draw == c->scored_n_draw, PRE3_E_STATE, "pre3_ransac_export: n_draw=%d differs from the scored round (n_draw=%d): the mask buffer is laid out for that round", n_draw, c->scored_n_draw);
-    int words = ceil_div(c->m, 32);
-    if (support_dst_dev) PRE3_HIP(hipMemcpyAsync(support_dst_dev, c->support, sizeof(int32_t) * n_draw, hipMemcpyDeviceToDevice, c->stream));
-    if (mask_dst_dev) PRE3_HIP(hipMemcpyAsync(mask_dst_dev, c->masks, sizeof(uint32_t) * (size_t)n_draw * words, hipMemcpyDeviceToDevice, c->stream));
-    PRE3_TRY(stream_drain(c, __func__));
-    return PRE3_OK;
-}
-
-int pre3_ransac_import(pre3_ctx *c, int n_draw, const void *support_src_dev, const void *mask_src_dev)
-{
-    PRE3_TRY(check_ctx(c));
-    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph, PRE3_E_ARG, "ransac: n_draw out of range");
-    PRE3_CHECK(n_draw == c->scored_n_draw, PRE3_E_STATE, "pre3_ransac_import: n_draw=%d differs from the scored round (n_draw=%d): the mask buffer is laid out for that round", n_draw, c->scored_n_draw);
-    int words = ceil_div(c->m, 32);
-    if (support_src_dev) PRE3_HIP(hipMemcpyAsync(c->support, support_src_dev, sizeof(int32_t) * n_draw, hipMemcpyDeviceToDevice, c->stream));
-    if (mask_src_dev) PRE3_HIP(hipMemcpyAsync(c->masks, mask_src_dev, sizeof(uint32_t) * (size_t)n_draw * words, hipMemcpyDeviceToDevice, c->stream));
-    PRE3_TRY(stream_drain(c, __func__));
-    return PRE3_OK;
-}
-
 // ---- RCCL communicator on the context (pre3_comm.hip) ------------------------------------------------
-int pre3_set_comm(pre3_ctx *c, pre3_comm *comm)
+static int set_comm_impl(pre3_ctx *c, pre3_comm *comm)
 {
-    PRE3_TRY(check_ctx(c));
     PRE3_CHECK(comm == nullptr || comm_device(comm) == c->device, PRE3_E_ARG, "pre3_set_comm: the communicator lives on device %d, the context on %d", comm ? comm_device(comm) : -1, c->device);
     if (c->comm && c->comm != (void *)comm) {
         // nothing queued on the stream may still use the handle being replaced (the caller may destroy it next); after a deadline: its abort has come back
@@ -1200,21 +1045,23 @@ int pre3_set_comm(pre3_ctx *c, pre3_comm *comm)
     c->comm = comm; c->comm_owned = false;
     return PRE3_OK;
 }
+int pre3_set_comm(pre3_ctx *c, pre3_comm *comm)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return set_comm_impl(c, comm);
+}
 
 int pre3_comm_init(pre3_ctx *c, const void *id, int rank, int world)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     pre3_comm *cm = nullptr;
     PRE3_TRY(pre3_comm_create(&cm, c->device, id, rank, world));
-    const int rc = pre3_set_comm(c, cm);
+    const int rc = set_comm_impl(c, cm);
     if (rc != PRE3_OK) { (void)pre3_comm_destroy(cm); return rc; }
     c->comm_owned = true;
     return PRE3_OK;
 }
 
-// One sharded RANSAC round with everything on the context's stream: [H*P | H*P*H' of this rank's measurements] -> scoring of hypotheses
-// [lo, hi) -> ncclAllReduce(sum) of [supports | masks], in place (the slices are disjoint and the buffer is cleared first: the integer sum
-// is the union) -> selection.  The host waits once, on the selection's mailbox word.
 // ---- test hook (pre3_test_hooks.h; inert without PRE3_TEST_HOOKS=1): a kernel that keeps the stream busy until the host releases it (or ~20 s have passed)
 static bool test_hooks_on() { const char *e = getenv("PRE3_TEST_HOOKS"); return e && atoi(e) == 1; }
 __global__ void k_test_stall(volatile int32_t *flag)
@@ -1236,366 +1083,9 @@ int pre3_test_stall(pre3_ctx *c, int release)
     return PRE3_OK;
 }
 
-int pre3_ransac_sharded(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, double threshold, int early_exit, int32_t *support, int32_t *li_mask,
-                        int32_t stats[4])
-{
-    // What may differ between the ranks must not decide whether a rank enters the collective: only the arguments every rank passes alike (the
-    // communicator, n_draw) return early.  Everything rank-local -- the deferred work of the previous step (check_ctx), the measurements, the
-    // table, a failed launch -- is folded into rc_local: the rank then still enters ncclAllReduce, with its slice zero and the missing-slice
-    // word set, and every rank fails the round with PRE3_E_COMM instead of waiting for a partner that has returned.
-    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
-    PRE3_HIP(hipSetDevice(c->device));
-    PRE3_CHECK(c->comm != nullptr, PRE3_E_STATE, "pre3_ransac_sharded: no communicator (pre3_comm_init / pre3_set_comm)");
-    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph, PRE3_E_ARG, "ransac: n_draw=%d exceeds capacity %d", n_draw, c->caph);
-    int rc_local = check_ctx(c);
-    int rank = 0, world = 1;
-    comm_rank_world(c->comm, &rank, &world);
-    const int base = n_draw / world, rem = n_draw % world;
-    const int lo = rank * base + std::min(rank, rem), hi = lo + base + (rank < rem ? 1 : 0);
-    const int words = ceil_div(c->m, 32);
-    // the element count of the all-reduce comes from the contexts' capacities, which the ranks share (replicas), not from this rank's
-    // measurement count: supports | masks laid out for the capacity's mask words | the missing-slice word
-    const size_t count = (size_t)round_up(n_draw, 4) + (size_t)n_draw * c->mask_words_cap;
-    if (rc_local == PRE3_OK) rc_local = ransac_prepare(c, n_draw, k, hyp, lo, hi, true, count + 1);
-    if (rc_local != PRE3_OK) (void)hipMemsetAsync(c->support, 0, sizeof(int32_t) * (count + 1), c->stream);      // (a failure in front of the prepare launch: the buffer must still be clear)
-    if (rc_local == PRE3_OK && hi > lo) rc_local = launch_ransac_score_impl(c, k, threshold, lo, hi, round_up(2 * c->m, NB), c->support, c->masks, words);
-    if (rc_local != PRE3_OK) {
-        (void)hipMemsetAsync(c->support, 0, sizeof(int32_t) * count, c->stream);                      // whatever part of the slice got written does not count
-        (void)hipMemsetAsync(c->support + count, 1, sizeof(int32_t), c->stream);                       // (0x01010101: non-zero is all that matters)
-    }
-    const int rc_coll = comm_all_reduce_i32(c->comm, c->support, count + 1, c->stream);
-    if (rc_local != PRE3_OK) return rc_local;
-    PRE3_TRY(rc_coll);
-    PRE3_TRY(launch_ransac_select_impl(c, n_draw, k, early_exit, c->support, c->masks, words, (int)count));
-    c->shard_round = true;
-    return ransac_results(c, n_draw, support, li_mask, stats);
-}
-
-int pre3_ransac(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, double threshold, int early_exit, int32_t *support, int32_t *li_mask,
-                int32_t stats[4])
-{
-    PRE3_TRY(check_ctx(c));
-    c->shard_round = false; c->select_pending = false;
-    PRE3_TRY(ransac_prepare(c, n_draw, k, hyp));
-    int words = ceil_div(c->m, 32);
-    // Scoring, then the selection stage (the reference's loop replayed on the supports) as a launch of its own.  The selection can also ride
-    // in the scoring launch's last workgroup (PRE3_SELECT_FUSE=1, round 1's form), but measured at N=500 / 200 hypotheses that launch then
-    // takes 21.2 us against 10.0 + 6.7 us for the two (tools/score_split.py): every workgroup pays a device-scope release (an L2 write-back)
-    // and a ticket before it may finish, and the last one starts the selection behind an L2 invalidate.
-    static const int fuse_env = getenv("PRE3_SELECT_FUSE") ? atoi(getenv("PRE3_SELECT_FUSE")) : 0;
-    if (fuse_env) PRE3_TRY(launch_ransac_score_impl(c, k, threshold, 0, n_draw, round_up(2 * c->m, NB), c->support, c->masks, words, n_draw, early_exit));
-    else {
-        PRE3_TRY(launch_ransac_score_impl(c, k, threshold, 0, n_draw, round_up(2 * c->m, NB), c->support, c->masks, words, 0, 0));
-        // pre3_step: the selection rides in the LI gather's launch (k_select_gather), which pre3_update_li sends next
-        if (c->defer_select && !support && !li_mask && !stats && select_gather_usable(c)) {
-            c->select_pending = true; c->sel_n_draw = n_draw; c->sel_k = k; c->sel_early_exit = early_exit;
-            c->li_from_host = -1; c->li_kernel = true;
-            return PRE3_OK;
-        }
-        PRE3_TRY(launch_ransac_select_impl(c, n_draw, k, early_exit, c->support, c->masks, words));
-    }
-    return ransac_results(c, n_draw, support, li_mask, stats);
-}
-
-// ---- updates --------------------------------------------------------------------------------------
-static int update_selected(pre3_ctx *c, int which_prior, int nsel, const int32_t *sel_dev, bool gathered = false, bool first_done = false)
-{
-    PRE3_CHECK(c->p_which == which_prior, PRE3_E_STATE, "update: the covariance buffer does not hold the required prior");
-    int r = 2 * nsel;
-    // rows of the predicted-state update that RANSAC already multiplied out: gather instead of recomputing
-    const bool reuse = r > 0 && which_prior == PRE3_X_K_KM1 && c->hp_all_valid && sel_dev != nullptr;
-    bool hp_built = false;
-    if (reuse) { if (!gathered) PRE3_TRY(launch_gather_li(c, nsel, nsel, sel_dev, round_up(2 * c->m, NB))); }
-    else if (r > 0) {
-        // rows built on the fly inside the H*P launch (one launch instead of k_build_rows + k_ell_HP; PRE3_FUSE_ROWS=0: the two)
-        static const int fuse_rows = getenv("PRE3_FUSE_ROWS") ? atoi(getenv("PRE3_FUSE_ROWS")) : 1;
-        if (fuse_rows && round_up(r, NB) <= c->rcap) { PRE3_TRY(launch_ell_HP_build_sel(c, nsel, sel_dev, c->W)); hp_built = true; }
-        else PRE3_TRY(launch_build_rows_impl(c, nsel, sel_dev, round_up(r, NB)));
-    }
-    PRE3_TRY(run_update(c, which_prior, r, false, nullptr, reuse, first_done && reuse, hp_built));
-    c->hp_all_valid = false;                 // P changed
-    c->x_valid[PRE3_X_K_K] = true; c->p_which = PRE3_X_K_K;
-    return PRE3_OK;
-}
-
-int pre3_update_li(pre3_ctx *c)
-{
-    PRE3_TRY(check_ctx(c));
-    PRE3_CHECK(c->measurements_set && c->projected, PRE3_E_STATE, "pre3_update_li: needs projection and measurements");
-    int n_li = 0;       // no RANSAC / flags for this measurement set: no low-innovation inliers, update is the identity
-    bool gathered = false, first_done = false;
-    if (c->li_from_host >= 0) n_li = c->li_from_host;
-    else if (c->li_kernel) {
-        const bool fused_sel = c->select_pending && c->p_which == PRE3_X_K_KM1 && c->hp_all_valid && c->m > 0;
-        if (c->select_pending && !fused_sel) PRE3_TRY(launch_ransac_select_impl(c, c->sel_n_draw, c->sel_k, c->sel_early_exit, c->support, c->masks, ceil_div(c->m, 32)));
-        c->select_pending = false;
-        // the gather of the LI rows does not need the count on the host: issue it first, with the grid sized for all
-        // measurements, so that the GPU has work while the host polls the mailbox and launches the factorisation
-        if (c->p_which == PRE3_X_K_KM1 && c->hp_all_valid && c->m > 0) {
-            if (fused_sel) PRE3_TRY(launch_select_gather(c, c->sel_n_draw, c->sel_k, c->sel_early_exit, ceil_div(c->m, 32)));
-            else PRE3_TRY(launch_gather_li(c, -1, c->m, c->sel_rows, round_up(2 * c->m, NB)));
-            gathered = true;
-            // ... and so does the first panel of the factorisation (row count read on the device, grid sized for all measurements)
-            static const int spec_env = getenv("PRE3_CHOL_SPEC0") ? atoi(getenv("PRE3_CHOL_SPEC0")) : 1;
-            if (spec_env && round_up(2 * c->m, NB) <= c->rcap) {
-                // fp32: the whole factorisation + solve is ONE launch that reads the row count on the device (pre3_cholp.hip)
-                if (cholp_usable(c, round_up(2 * c->m, NB) / NB)) {
-                    // pre3_step: the rescue stage and the HI update ride in the same launch (mono_slam.m:184-187 as panel nrb of this factorisation)
-                    CholpTailReq req{ c->tail_chi2, c->seq_collect + 1 };
-                    c->tail_launched = false;
-                    PRE3_TRY(launch_cholp(c, -1, round_up(2 * c->m, NB) / NB, -1, PRE3_X_K_KM1, c->tail_want ? &req : nullptr));
-                    if (c->tail_launched) ++c->seq_collect;
-                    c->cholp_done = true;
-                }
-                else PRE3_TRY(launch_chol_first_spec(c, c->m));
-                first_done = true;
-            }
-        }
-        PRE3_TRY(wait_mail(c, 8, c->seq_select)); n_li = c->mail_host[4];
-        PRE3_CHECK(!c->shard_round || c->mail_host[11] == 0, PRE3_E_COMM, "sharded RANSAC: a rank failed before the collective of the round this update follows");
-    }
-    // (a launch that found no rows on the device returned at once: the tail has not run either)
-    c->tail_done = first_done && c->cholp_done && c->tail_launched && n_li > 0;
-    c->tail_launched = false;
-    return update_selected(c, PRE3_X_K_KM1, n_li, c->sel_rows, gathered, first_done);
-}
-
-static int rescue_impl(pre3_ctx *c, double chi2, int32_t *hi_mask)
-{
-    if (c->N) {
-        if (c->rescue_projected) PRE3_TRY(launch_innovation(c, 1, chi2));          // h / H at x_k_k came with the K9 launch
-        else PRE3_TRY(launch_project_innovation(c, PRE3_X_K_K, 0, 1, chi2));
-    }
-    c->rescue_projected = false;
-    c->hi_from_host = -1; c->hi_kernel = true;
-    if (hi_mask) {
-        PRE3_TRY(stream_drain(c, __func__));
-        if (c->m) PRE3_HIP(hipMemcpy(hi_mask, c->hi_meas, sizeof(int32_t) * c->m, hipMemcpyDeviceToHost));
-    }
-    return PRE3_OK;
-}
-
-// record: a booked context records what rescue_hi_inliers.m:32 projects (pre3_map_policy's times_predicted), at the x_k_k this projection uses
-// (pre3_step records it itself, in front of whichever rescue form it takes)
-static int rescue_checked(pre3_ctx *c, double chi2, int32_t *hi_mask, bool record)
-{
-    PRE3_TRY(check_ctx(c));
-    PRE3_CHECK(c->p_which == PRE3_X_K_K && c->x_valid[PRE3_X_K_K], PRE3_E_STATE, "pre3_rescue: needs (x_k_k, p_k_k), i.e. after the LI update");
-    if (record && c->booked && c->m > 0 && c->N > 0) PRE3_TRY(launch_book_vis(c));
-    return rescue_impl(c, chi2, hi_mask);
-}
-int pre3_rescue(pre3_ctx *c, double chi2, int32_t *hi_mask) { return rescue_checked(c, chi2, hi_mask, true); }
-
-int pre3_update_hi(pre3_ctx *c)
-{
-    PRE3_TRY(check_ctx(c));
-    int n_hi = 0;
-    const bool tail_done = c->tail_done, was_fused = c->hi_fused;
-    c->tail_done = false; c->hi_fused = false;                      // (before anything can return)
-    if (c->hi_from_host >= 0) n_hi = c->hi_from_host;
-    else if (c->hi_kernel) {
-        PRE3_TRY(wait_mail(c, 9, c->seq_collect)); n_hi = c->mail_host[5];
-        // the collection stage also brings the device's error words: what went wrong in this step's launches fails THIS call -- once: the words
-        // are cleared with the report, so that a context that installs a fresh state (pre3_set_state) works again
-        const int e_wait = c->mail_host[7], e_npd = c->mail_host[6];
-        if (e_wait != 0 || e_npd != 0) {
-            c->mail_host[6] = 0; c->mail_host[7] = 0;
-            (void)hipMemsetAsync(c->stats + 6, 0, sizeof(int32_t) * 2, c->stream);
-        }
-        PRE3_CHECK(e_wait == 0, PRE3_E_HIP, "a device-side wait on another workgroup gave up (counter never arrived): results are invalid");
-        PRE3_CHECK(e_npd == 0, PRE3_E_NUMERIC, "innovation covariance S is not positive definite");
-    }
-    if (tail_done) {
-        // The persistent launch of the LI update has run the rescue stage and (up to 32 landmarks) the HI update as well (pre3_cholp.hip, CpTail):
-        // P holds P - W'W - W~'W~ and update.m:42-46 of BOTH updates is one pending rows / columns 3..6 pass (params[16..] = params[96..] = J2 J1,
-        // or J1 alone when nothing was updated).  More than 32: that pass now (J1), then the general path.
-        c->hp_all_valid = false;
-        if (c->hi_from_host < 0 && n_hi <= 32) {
-            if (c->leave_jn_to_predict) c->jn_pending = true;
-            else PRE3_TRY(launch_jnorm(c, 0));
-            return PRE3_OK;
-        }
-        PRE3_TRY(launch_jnorm(c, 0));
-        return update_selected(c, PRE3_X_K_K, n_hi, c->sel_rows);
-    }
-    if (was_fused) {
-        // pre3_step sent the collection and the update out as one device-driven pair of launches (k_hi_fused + its down-date): up to 64
-        // landmarks (two panels) are done, only the Jnorm pass of update.m:42-46 is left; more than that take the general path now
-        const bool pend_launched = c->hi_pend_launched;
-        c->hi_pend_launched = false;
-        if (c->hi_from_host < 0 && n_hi <= hi_fused_max(c)) {
-            if (n_hi > 0) {
-                c->hp_all_valid = false;
-                // PRE3_OPT_PEND_HI: k_hi_fused's down-date was not launched -- from here on P stands for P - W~'W~ (2 n_hi rows) until somebody takes it
-                if (pend_launched) {
-                    c->pend_rows = 2 * n_hi;
-                    // (two panels of pending rows cost the next H*P launch ~19 us more, one panel ~5: sending the two-panel ones out at once -- PRE3_PEND_MAX_ROWS=64 --
-                    //  measured 5922 against 5954 steps/s: the launch they then need costs as much)
-                    static const int pend_max = getenv("PRE3_PEND_MAX_ROWS") ? atoi(getenv("PRE3_PEND_MAX_ROWS")) : 2 * NB;
-                    if (c->pend_rows > pend_max) PRE3_TRY(pend_flush(c));
-                }
-                if (c->leave_jn_to_predict) c->jn_pending = true;
-                else PRE3_TRY(launch_jnorm(c, 0));              // (flushes the pending rows first: the pass reads P)
-            }
-            return PRE3_OK;
-        }
-        // (more than k_hi_fused takes: it has written nothing -- no W~, no x-update --, the general path follows)
-    }
-    return update_selected(c, PRE3_X_K_K, n_hi, c->sel_rows);
-}
-
-int pre3_update_all(pre3_ctx *c)
-{
-    PRE3_TRY(check_ctx(c));
-    PRE3_CHECK(c->measurements_set && c->projected, PRE3_E_STATE, "pre3_update_all: needs projection and measurements");
-    return update_selected(c, PRE3_X_K_KM1, c->m, nullptr);
-}
-
-// ---- update.m on the resident current estimate (pre3_rows.hip) -------------------------------------------------------------
-// The host checks of both calls, before anything is launched
-static int rows_precheck(pre3_ctx *c, const char *who)
-{
-    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
-    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE,
-               "%s: acts on (x_k_k, p_k_k); the covariance buffer holds the prediction (update first)", who);
-    return PRE3_OK;
-}
-
-int pre3_update_rows(pre3_ctx *c, int r, int width, const int32_t *nnz, const int32_t *col, const double *val, const double *R, const double *z,
-                     const double *h)
-{
-    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
-    PRE3_CHECK(r >= 0, PRE3_E_ARG, "pre3_update_rows: r=%d", r);
-    PRE3_CHECK(round_up(r, NB) <= c->rcap, PRE3_E_ARG, "pre3_update_rows: %d rows exceed the context's capacity %d", r, c->rcap);
-    PRE3_CHECK(r == 0 || (nnz && col && val && z && h && width >= 1), PRE3_E_ARG, "pre3_update_rows: null row data");
-    for (int a = 0; a < r; ++a) {
-        PRE3_CHECK(nnz[a] >= 0 && nnz[a] <= width && nnz[a] <= ELLW, PRE3_E_ARG, "pre3_update_rows: row %d has %d non-zeros (max %d)", a, nnz[a], ELLW);
-        for (int t = 0; t < nnz[a]; ++t)
-            PRE3_CHECK(col[(size_t)a * width + t] >= 0 && col[(size_t)a * width + t] < c->n, PRE3_E_ARG,
-                       "pre3_update_rows: column index %d out of range (n=%d) in row %d", col[(size_t)a * width + t], c->n, a);
-    }
-    PRE3_TRY(rows_precheck(c, "pre3_update_rows"));
-    PRE3_TRY(check_ctx(c));
-    if (r == 0) return PRE3_OK;                 // update.m:50-55
-    if (r <= RMAX) {
-        // the single-sweep form (pre3_rows.hip)
-        RowsBlock b{};
-        b.r = r; b.applied = 1;
-        for (int a = 0; a < r; ++a) {
-            for (int t = 0; t < nnz[a]; ++t) { b.col[a * RMAX + t] = col[(size_t)a * width + t]; b.val[a * RMAX + t] = val[(size_t)a * width + t]; }
-            b.nu[a] = z[a] - h[a];
-            for (int e = 0; e < r; ++e) b.R[a * r + e] = R ? R[(size_t)a * r + e] : (a == e ? 1.0 : 0.0);
-        }
-        c->rows_form = 1;
-        PRE3_TRY(launch_rows_update(c, &b, nullptr));
-        c->hp_all_valid = false;
-        return PRE3_OK;
-    }
-    // above RMAX rows: the rows as pre3_update_ell installs them, then the existing route (run_update) in place on x_k_k / p_k_k
-    const int r_pad = round_up(r, NB);
-    std::vector<int32_t> hc((size_t)r_pad * ELLW, 0);
-    std::vector<double> hv((size_t)r_pad * ELLW, 0.0), nu(r_pad, 0.0);
-    for (int a = 0; a < r; ++a) {
-        for (int t = 0; t < nnz[a]; ++t) { hc[(size_t)a * ELLW + t] = col[(size_t)a * width + t]; hv[(size_t)a * ELLW + t] = val[(size_t)a * width + t]; }
-        nu[a] = z[a] - h[a];
-    }
-    PRE3_HIP(hipMemcpyAsync(c->row_col, hc.data(), sizeof(int32_t) * hc.size(), hipMemcpyHostToDevice, c->stream));
-    std::vector<float> hf, rf;
-    if (c->dtype == PRE3_F64) PRE3_HIP(hipMemcpyAsync(c->row_val, hv.data(), sizeof(double) * hv.size(), hipMemcpyHostToDevice, c->stream));
-    else { hf.assign(hv.begin(), hv.end()); PRE3_HIP(hipMemcpyAsync(c->row_val, hf.data(), sizeof(float) * hf.size(), hipMemcpyHostToDevice, c->stream)); }
-    PRE3_HIP(hipMemcpyAsync(c->row_nu, nu.data(), sizeof(double) * r_pad, hipMemcpyHostToDevice, c->stream));
-    if (R) {
-        if (c->Rdense == nullptr) PRE3_TRY(dmalloc_bytes(&c->Rdense, (size_t)c->rcap * c->rcap * c->esz));
-        if (c->dtype == PRE3_F64) PRE3_HIP(hipMemcpyAsync(c->Rdense, R, sizeof(double) * r * r, hipMemcpyHostToDevice, c->stream));
-        else { rf.assign(R, R + (size_t)r * r); PRE3_HIP(hipMemcpyAsync(c->Rdense, rf.data(), sizeof(float) * rf.size(), hipMemcpyHostToDevice, c->stream)); }
-    }
-    c->rows_form = 0;
-    PRE3_TRY(run_update(c, PRE3_X_K_K, r, R != nullptr, nullptr));
-    c->hp_all_valid = false;
-    c->x_valid[PRE3_X_K_K] = true; c->p_which = PRE3_X_K_K;
-    // (the host vectors may go: a copy from pageable memory has consumed its source when hipMemcpyAsync returns)
-    return PRE3_OK;
-}
-
-// ekf_heading_update.m:36-40 on the host: RR = J_z J_e2q diag((pi/180)^2 [1 1 1]) J_e2q' J_z' with [~, J_e2q] = e2q(q2e(R2q(R_plane))) and
-// J_z = observe_heading_jac(R2q(R_plane)).  R_plane 3 x 3 column-major; RR row-major.
-static void heading_RR(const double *Rp, double RR[9])
-{
-    auto Rm = [&](int i, int j) { return Rp[(j - 1) * 3 + (i - 1)]; };       // R(i, j), MATLAB indices
-    // slamToolbox_11_02_18/FrameTransforms/Rotations/R2q.m:11-55
-    double a, b, cc, d;
-    const double T = Rm(1, 1) + Rm(2, 2) + Rm(3, 3) + 1.0;
-    if (T > 0.00000001) {
-        const double S = 2.0 * sqrt(T);
-        a = 0.25 * S; b = (Rm(2, 3) - Rm(3, 2)) / S; cc = (Rm(3, 1) - Rm(1, 3)) / S; d = (Rm(1, 2) - Rm(2, 1)) / S;
-    } else if (Rm(1, 1) > Rm(2, 2) && Rm(1, 1) > Rm(3, 3)) {
-        const double S = 2.0 * sqrt(1.0 + Rm(1, 1) - Rm(2, 2) - Rm(3, 3));
-        a = (Rm(2, 3) - Rm(3, 2)) / S; b = 0.25 * S; cc = (Rm(1, 2) + Rm(2, 1)) / S; d = (Rm(3, 1) + Rm(1, 3)) / S;
-    } else if (Rm(2, 2) > Rm(3, 3)) {
-        const double S = 2.0 * sqrt(1.0 + Rm(2, 2) - Rm(1, 1) - Rm(3, 3));
-        a = (Rm(3, 1) - Rm(1, 3)) / S; b = (Rm(1, 2) + Rm(2, 1)) / S; cc = 0.25 * S; d = (Rm(2, 3) + Rm(3, 2)) / S;
-    } else {
-        const double S = 2.0 * sqrt(1.0 + Rm(3, 3) - Rm(1, 1) - Rm(2, 2));
-        a = (Rm(1, 2) - Rm(2, 1)) / S; b = (Rm(3, 1) + Rm(1, 3)) / S; cc = (Rm(2, 3) + Rm(3, 2)) / S; d = 0.25 * S;
-    }
-    const double q[4] = { a, -b, -cc, -d };
-    // q2e.m:15-38
-    const double y1 = 2 * q[2] * q[3] + 2 * q[0] * q[1], x1 = q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3];
-    const double z2 = -2 * q[1] * q[3] + 2 * q[0] * q[2];
-    const double y3 = 2 * q[1] * q[2] + 2 * q[0] * q[3], x3 = q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3];
-    const double e[3] = { atan2(y1, x1), asin(z2), atan2(y3, x3) };
-    // e2q.m:22-35
-    const double sr = sin(e[0] / 2), sp = sin(e[1] / 2), sy = sin(e[2] / 2), cr = cos(e[0] / 2), cp = cos(e[1] / 2), cy = cos(e[2] / 2);
-    const double Qe[4][3] = {
-        { 0.5 * (-cy * cp * sr + sy * sp * cr), 0.5 * (-cy * sp * cr + sy * cp * sr), 0.5 * (-sy * cp * cr + cy * sp * sr) },
-        { 0.5 * (cy * cp * cr + sy * sp * sr), 0.5 * (-cy * sp * sr - sy * cp * cr), 0.5 * (-sy * cp * sr - cy * sp * cr) },
-        { 0.5 * (-cy * sp * sr + sy * cp * cr), 0.5 * (cy * cp * cr - sy * sp * sr), 0.5 * (-sy * sp * cr + cy * cp * sr) },
-        { 0.5 * (-sy * cp * sr - cy * sp * cr), 0.5 * (-cy * cp * sr - sy * sp * cr), 0.5 * (cy * cp * cr + sy * sp * sr) } };
-    // aux_code/observe_heading_jac.m:31-38 at R2q(R_plane)
-    const double q1 = q[0], q2 = q[1], q3 = q[2], q4 = q[3];
-    const double Jz[3][4] = { { -2 * q4, 2 * q3, 2 * q2, -2 * q1 }, { 2 * q1, -2 * q2, 2 * q3, -2 * q4 }, { 2 * q2, 2 * q1, 2 * q4, 2 * q3 } };
-    const double var = (M_PI / 180.0) * (M_PI / 180.0);
-    double A[3][3];                                              // J_z J_e2q
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 4; ++k) s += Jz[i][k] * Qe[k][j]; A[i][j] = s; }
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 3; ++k) s += A[i][k] * var * A[j][k]; RR[i * 3 + j] = s; }
-}
-
-int pre3_heading_update(pre3_ctx *c, const double R_plane[9], int strict_reference, int32_t *applied_out)
-{
-    PRE3_CHECK(c != nullptr && R_plane != nullptr, PRE3_E_ARG, "pre3_heading_update: null argument");
-    for (int k = 0; k < 9; ++k) PRE3_CHECK(std::isfinite(R_plane[k]), PRE3_E_ARG, "pre3_heading_update: R_plane is not finite");
-    PRE3_TRY(rows_precheck(c, "pre3_heading_update"));
-    PRE3_TRY(check_ctx(c));
-    RowsHeading hd{};
-    hd.on = 1; hd.strict = strict_reference ? 1 : 0;
-    for (int k = 0; k < 3; ++k) hd.z[k] = R_plane[3 + k];          // ekf_heading_update.m:29, z = R_plane(:, 2)
-    heading_RR(R_plane, hd.RR);
-    c->rows_form = 1;
-    PRE3_TRY(launch_rows_update(c, nullptr, &hd));
-    c->hp_all_valid = false;
-    if (applied_out) {
-        int32_t applied = 0;
-        PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
-        PRE3_TRY(rows_applied(c, &applied));
-        PRE3_TRY(stream_drain(c, __func__));
-        const int rc = stats_words(c);
-        *applied_out = rc == PRE3_OK ? applied : 0;
-        if (rc != PRE3_OK) {
-            // reported once, as the step's collection reports them: the words are cleared with the report
-            (void)hipMemsetAsync(c->stats + 6, 0, sizeof(int32_t) * 2, c->stream);
-            c->mail_host[6] = 0; c->mail_host[7] = 0;
-            PRE3_TRY(stream_drain(c, __func__));
-        }
-        return rc;
-    }
-    return PRE3_OK;
-}
-
 int pre3_get_flags(pre3_ctx *c, int32_t *li, int32_t *hi)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_TRY(stream_drain(c, __func__));
     if (c->m == 0) return PRE3_OK;
     if (li) PRE3_HIP(hipMemcpy(li, c->li_meas, sizeof(int32_t) * c->m, hipMemcpyDeviceToHost));
@@ -1605,7 +1095,7 @@ int pre3_get_flags(pre3_ctx *c, int32_t *li, int32_t *hi)
 
 int pre3_set_flags(pre3_ctx *c, const int32_t *li, const int32_t *hi)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(c->measurements_set, PRE3_E_STATE, "pre3_set_flags: no measurements");
     PRE3_TRY(stream_drain(c, __func__));
     int m = c->m, N = c->N;
@@ -1622,173 +1112,6 @@ int pre3_set_flags(pre3_ctx *c, const int32_t *li, const int32_t *hi)
         if (pass == 0) c->li_from_host = cnt; else c->hi_from_host = cnt;
     }
     return PRE3_OK;
-}
-
-// mono_slam.m:178-187 behind the prediction and the IC search: RANSAC, LI update, rescue, HI update, every launch sized on the device.
-// hyp: the draw table -- the inbox's own copy when it was shipped with the measurements (pre3_step), the caller's otherwise.
-static int step_back(pre3_ctx *c, int m, int n_draw, int k, const int32_t *hyp, double threshold, int early_exit, double chi2, int32_t stats[8])
-{
-    int32_t st[8] = { -1, 0, 0, 0, 0, 0, 0, 0 };
-    bool ran = false;
-    if (m >= k && m > 0) {
-        // mono_slam.m:178; the statistics are read after pre3_update_li's poll of the same mailbox
-        c->defer_select = true;                                     // the selection stage rides in the LI gather's launch (pre3_update_li below)
-        const int rc_r = pre3_ransac(c, n_draw, k, hyp, threshold, early_exit, nullptr, nullptr, nullptr);
-        c->defer_select = false;
-        if (c->ride_innovation) {                                   // the H*P launch did not go out (error before it): S_i on its own, flags cleared
-            c->ride_innovation = false;
-            PRE3_TRY(launch_innovation(c, 0, 0.0, true));
-        }
-        PRE3_TRY(rc_r);
-        ran = true;
-    }
-    static const int ride_rescue = getenv("PRE3_RIDE_RESCUE") ? atoi(getenv("PRE3_RIDE_RESCUE")) : 1;      // 0: projection + gate as one launch of their own (A/B)
-    c->ride_rescue_projection = ride_rescue != 0;                   // the rescue's projection rides in the LI update's K9 launch
-    {
-        // ... or, with the whole rescue stage and the HI update, in the persistent launch itself (not on a booked context: the rescue's visibility
-        // record needs the point between the LI update and the rescue, which that form does not have -- the step takes the default form)
-        c->tail_want = c->step_tail && !c->booked && hi_fused_usable(c); c->tail_chi2 = chi2;
-        // ... or projection AND chi2 gate in the Jnorm pass's launch, when the persistent launch's consumers leave rows 3..6 of P behind (GateRide)
-        c->want_gate_ride = ride_rescue != 0 && !c->tail_want && hi_fused_usable(c); c->rescue_chi2 = chi2; c->rescue_gated = false;
-        const int rc_li = pre3_update_li(c);                        // mono_slam.m:181
-        c->tail_want = false; c->want_gate_ride = false;
-        c->ride_rescue_projection = false;                          // (also on failure: a later K9 launch must not carry the riders)
-        if (rc_li != PRE3_OK) { c->rescue_projected = false; c->rescue_gated = false; c->tail_done = false; return rc_li; }
-    }
-    if (ran) for (int i = 0; i < 4; ++i) st[i] = c->mail_host[i];
-    // a booked context: visibility at the post-LI x_k_k, where rescue_hi_inliers.m:32 projects -- one small launch in stream order between the LI
-    // update and the rescue / HI update (also under PRE3_OPT_DEFER_HI / PEND_HI, which only move the HI update later); only when the reference's
-    // rescue runs ('1PRE' with at least one IC measurement, mono_slam.m:165)
-    if (c->booked && m > 0 && c->N > 0 && !c->tail_done) PRE3_TRY(launch_book_vis(c));
-    if (c->tail_done) {
-        // mono_slam.m:184 + :187 went out with the LI update's launch: the count arrives with mailbox word 9 (pre3_update_hi)
-        c->rescue_projected = false; c->proj_with_jnorm = false;
-        c->hi_from_host = -1; c->hi_kernel = true; c->hi_fused = false;
-    } else if (hi_fused_usable(c)) {
-        // mono_slam.m:184 + :187 without the host in between: the chi2 gate, then the collection and the HI update of up to 32 landmarks as ONE
-        // launch that reads the count on the device, and its down-date behind it (pre3_update.hip, k_hi_fused)
-        PRE3_CHECK(c->p_which == PRE3_X_K_K && c->x_valid[PRE3_X_K_K], PRE3_E_STATE, "pre3_step: the LI update did not leave (x_k_k, p_k_k)");
-        if (c->rescue_gated) { /* the gate rode with the Jnorm pass */ }
-        else if (c->rescue_projected) PRE3_TRY(launch_innovation(c, 1, chi2, false, false));
-        else PRE3_TRY(launch_project_innovation(c, PRE3_X_K_K, 0, 1, chi2, false));
-        c->rescue_projected = false; c->rescue_gated = false;
-        c->hi_from_host = -1; c->hi_kernel = true;
-        PRE3_TRY(launch_hi_fused(c, ++c->seq_collect));
-        c->hi_fused = true;
-    } else
-    PRE3_TRY(rescue_checked(c, chi2, nullptr, false));             // mono_slam.m:184
-    if (c->defer_hi) c->hi_pending = true;                          // mono_slam.m:187, completed at the next call on this context
-    else PRE3_TRY(pre3_update_hi(c));                               // mono_slam.m:187
-    st[4] = c->li_from_host >= 0 ? c->li_from_host : (c->li_kernel ? c->mail_host[4] : 0);
-    st[5] = c->defer_hi ? c->last_n_hi : (c->hi_from_host >= 0 ? c->hi_from_host : (c->hi_kernel ? c->mail_host[5] : 0));
-    st[7] = c->defer_hi ? 1 : 0;          // 1: st[5] is the HI count of the PREVIOUS step (this step's is still on the device)
-    if (stats) for (int i = 0; i < 8; ++i) stats[i] = st[i];
-    return PRE3_OK;
-}
-
-int pre3_step(pre3_ctx *c, const double u[7], int m, const int32_t *meas_idx, const double *z, int n_draw, int k, const int32_t *hyp,
-              double threshold, int early_exit, double chi2, int32_t stats[8])
-{
-    // the previous step's deferred HI update is completed here; its rows/cols 3..6 <- Jn pass (update.m:42-46) is left to the prediction's
-    // launch below (one launch less per step; PRE3_FUSE_JN=0: as its own launch).  Any return before that launch flushes it.
-    // (a pass a marginal reader has left pending since -- it completed the update -- rides the same way)
-    if (c) c->leave_jn_to_predict = fuse_jn_env() && (c->hi_pending || c->jn_pending);
-    // PRE3_OPT_PEND_HI: this call's own launches take a pending HI down-date along (prediction, H*P + S_i, the LI update's consumers); whatever of it
-    // cannot -- and every call made from in here that reads P some other way -- flushes it first (pend_flush in the launchers)
-    struct PendKeep { pre3_ctx *c; ~PendKeep() { if (c) c->pend_keep = false; } } pend_keep{ c };
-    if (c) c->pend_keep = c->pend_opt && c->dtype == PRE3_F32 && m >= k && m > 0 && c->N > 0;
-    {
-        const int rc0 = check_ctx(c);
-        if (c) c->leave_jn_to_predict = false;
-        if (rc0 != PRE3_OK) { if (c && c->jn_pending) { c->jn_pending = false; (void)launch_jnorm(c, 0); } return rc0; }
-    }
-    struct JnFlush { pre3_ctx *c; ~JnFlush() { if (c->jn_pending) { c->jn_pending = false; (void)launch_jnorm(c, 0); } } } jn_flush{ c };
-    static const bool trace = getenv("PRE3_STEP_TRACE") != nullptr;     // host-side stage clock (debug): where the host spends a step
-    static double acc[8], t_prev_end = 0; static int nacc = 0;
-    auto now = [] { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e6 + t.tv_nsec * 1e-3; };
-    double t0 = trace ? now() : 0, t1 = 0, t5 = 0;
-    PRE3_CHECK(u != nullptr, PRE3_E_ARG, "pre3_step: null u");
-    PRE3_CHECK(c->have_cam, PRE3_E_STATE, "pre3_step: camera not set");
-    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "pre3_step: needs (x_k_k, p_k_k) on the device");
-    PRE3_CHECK(m == 0 || (meas_idx && z), PRE3_E_ARG, "pre3_step: null measurement pointers");
-    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph && k >= 1 && k <= MAXK && hyp, PRE3_E_ARG, "pre3_step: bad hypothesis table");
-    // matching_sift_based.m:131-134 outcome (+ the draws) into the pinned inbox; it crosses PCIe in one extra block of the prediction's
-    // launch (nothing in that launch reads it), so the copy costs neither a launch nor stream time.  Flags cleared by k_innovation.
-    size_t inbox_bytes = 0;
-    PRE3_TRY(install_measurements(c, m, meas_idx, z, hyp, n_draw * k, c->N > 0, false, &inbox_bytes));
-    // mono_slam.m:153 + search_IC_matches.m:31-32: prediction, with the projection of every landmark at x_k_km1 riding in the
-    // same launch; then search_IC_matches.m:33-44 (S_i), which also clears the previous frame's inlier flags
-    {
-        static const int ride_proj = getenv("PRE3_RIDE_PROJ") ? atoi(getenv("PRE3_RIDE_PROJ")) : 1;      // 0: the projection as its own launch (A/B)
-        const int rc_p = launch_predict_impl(c, u, ride_proj != 0, (inbox_bytes + 15) / 16, ++c->seq_inbox);
-        c->inbox_pending = rc_p == PRE3_OK;
-        if (rc_p != PRE3_OK) { c->measurements_set = false; return rc_p; }
-        if (!ride_proj && c->N) PRE3_TRY(launch_project(c, PRE3_X_K_KM1, 1));
-    }
-    c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
-    c->projected = true;
-    // S_i (which also clears last frame's inlier flags) rides in the H*P launch of the RANSAC stage when there is one
-    static const int ride_env = getenv("PRE3_RIDE_INNOV") ? atoi(getenv("PRE3_RIDE_INNOV")) : 1;
-    c->ride_innovation = ride_env && c->N > 0 && m >= k && m > 0;
-    if (c->N && !c->ride_innovation) PRE3_TRY(launch_innovation(c, 0, 0.0, true));
-    c->innovated = true;
-    if (trace) t1 = now();
-    const int rc_back = step_back(c, m, n_draw, k, (const int32_t *)(c->inbox_host + c->off_hyp), threshold, early_exit, chi2, stats);
-    if (trace) {
-        t5 = now();
-        acc[0] += t1 - t0; acc[1] += t5 - t1;
-        if (t_prev_end > 0) acc[5] += t0 - t_prev_end;
-        t_prev_end = t5;
-        if (++nacc == 100) {
-            fprintf(stderr, "[pre3 step trace, us] predict+project+innov launches %.1f | ransac .. HI update (polls + launches) %.1f | caller between steps %.1f\n",
-                    acc[0] / nacc, acc[1] / nacc, acc[5] / nacc);
-            nacc = 0; for (double &a2 : acc) a2 = 0;
-        }
-    }
-    return rc_back;
-}
-
-/* mono_slam.m:153-162 + :199 -- the 'PURE_EKF' branch (config_file.m:21): prediction, projection + Jacobians + S_i of every landmark, then ONE
- * update with every individually compatible measurement (ekf_update_all.m:46-62), as one call: the projection and the inbox ride in the
- * prediction's launch, S_i and the flag clearing in the H*P launch -- four launches fewer than the call-by-call sequence
- * (pre3_predict, pre3_project, pre3_innovation, pre3_set_measurements, pre3_update_all), the same arithmetic. */
-int pre3_step_all(pre3_ctx *c, const double u[7], int m, const int32_t *meas_idx, const double *z)
-{
-    PRE3_TRY(check_ctx(c));
-    PRE3_CHECK(u != nullptr, PRE3_E_ARG, "pre3_step_all: null u");
-    PRE3_CHECK(c->have_cam, PRE3_E_STATE, "pre3_step_all: camera not set");
-    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "pre3_step_all: needs (x_k_k, p_k_k) on the device");
-    PRE3_CHECK(m == 0 || (meas_idx && z), PRE3_E_ARG, "pre3_step_all: null measurement pointers");
-    size_t inbox_bytes = 0;
-    PRE3_TRY(install_measurements(c, m, meas_idx, z, nullptr, 0, c->N > 0 && m > 0, false, &inbox_bytes));
-    {
-        const int rc_p = launch_predict_impl(c, u, true, (inbox_bytes + 15) / 16, ++c->seq_inbox);
-        c->inbox_pending = rc_p == PRE3_OK;
-        if (rc_p != PRE3_OK) { c->measurements_set = false; return rc_p; }
-    }
-    c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
-    c->projected = true;
-    c->ride_innovation = c->N > 0 && m > 0;          // S_i (and the clearing of last frame's flags) in the update's H*P launch
-    if (c->N && !c->ride_innovation) PRE3_TRY(launch_innovation(c, 0, 0.0, true));
-    c->innovated = true;
-    const int rc_u = update_selected(c, PRE3_X_K_KM1, c->m, nullptr);
-    if (c->ride_innovation) {                        // (the H*P launch did not go out: S_i on its own)
-        c->ride_innovation = false;
-        if (rc_u == PRE3_OK) PRE3_TRY(launch_innovation(c, 0, 0.0, true));
-    }
-    return rc_u;
-}
-
-/* The same behind a prediction and an IC search the caller has already run (mono_slam.m:153 ekf_prediction, :159 search_IC_matches +
- * matching_sift_based, e.g. pre3_predict + pre3_ic_search): the installed measurements are used. */
-int pre3_step_predicted(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, double threshold, int early_exit, double chi2, int32_t stats[8])
-{
-    PRE3_TRY(check_ctx(c));
-    PRE3_CHECK(c->x_valid[PRE3_X_K_KM1] && c->p_which == PRE3_X_K_KM1, PRE3_E_STATE, "pre3_step_predicted: needs the predicted estimate (pre3_predict)");
-    PRE3_CHECK(c->measurements_set && c->projected && c->innovated, PRE3_E_STATE, "pre3_step_predicted: needs projection, S_i and measurements (pre3_ic_search, or pre3_project + pre3_innovation + pre3_set_measurements)");
-    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph && k >= 1 && k <= MAXK && hyp, PRE3_E_ARG, "pre3_step_predicted: bad hypothesis table");
-    c->ride_innovation = false;
-    return step_back(c, c->m, n_draw, k, hyp, threshold, early_exit, chi2, stats);
 }
 
 // ---- stateless update.m drop-in ---------------------------------------------------------------------
@@ -2005,14 +1328,14 @@ int pre3_knn_f64(int device, int D, int N, const double *data, int M, const doub
 // ---- measurement hooks ---------------------------------------------------------------------------------
 int pre3_timer_start(pre3_ctx *c)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_HIP(hipEventRecord(c->t0, c->stream));
     return PRE3_OK;
 }
 
 int pre3_timer_stop(pre3_ctx *c, double *ms_out)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_HIP(hipEventRecord(c->t1, c->stream));
     PRE3_HIP(hipEventSynchronize(c->t1));
     float ms = 0;
@@ -2023,7 +1346,7 @@ int pre3_timer_stop(pre3_ctx *c, double *ms_out)
 
 int pre3_kernel_timing(pre3_ctx *c, int enable)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     c->kt.enabled = enable != 0; c->kt.every = enable > 1 ? enable : 1; c->kt.seen = 0; c->kt.used = 0; c->kt.flops = 0; c->kt.bytes = 0;
     c->kt.fused = 0; c->kt.fact_flops = 0; c->kt.pending = false;
     return PRE3_OK;
@@ -2031,7 +1354,7 @@ int pre3_kernel_timing(pre3_ctx *c, int enable)
 
 int pre3_kernel_timing_read(pre3_ctx *c, int *launches_out, double *total_ms_out, double *flops_out, double *bytes_out)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_TRY(stream_drain(c, __func__));
     double tot = 0;
     for (int i = 0; i + 1 < c->kt.used; i += 2) { float ms = 0; PRE3_HIP(hipEventElapsedTime(&ms, c->kt.ev[i], c->kt.ev[i + 1])); tot += ms; }
@@ -2045,7 +1368,7 @@ int pre3_kernel_timing_read(pre3_ctx *c, int *launches_out, double *total_ms_out
 
 int pre3_kernel_timing_info(pre3_ctx *c, int *fused_launches_out, double *fact_flops_out)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     if (fused_launches_out) *fused_launches_out = c->kt.fused;
     if (fact_flops_out) *fact_flops_out = c->kt.fact_flops;
     c->kt.fused = 0; c->kt.fact_flops = 0;
@@ -2054,19 +1377,15 @@ int pre3_kernel_timing_info(pre3_ctx *c, int *fused_launches_out, double *fact_f
 
 int pre3_bench_downdate(pre3_ctx *c, int r, int reps, double *ms_per_launch_out)
 {
-    PRE3_TRY(check_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(r >= 1 && round_up(r, NB) <= c->rcap && reps >= 1, PRE3_E_ARG, "pre3_bench_downdate: bad r/reps");
     PRE3_CHECK(c->n > 0, PRE3_E_STATE, "pre3_bench_downdate: no map/state set");
     int r_pad = round_up(r, NB);
     PRE3_TRY(launch_fill_w(c, r_pad));
     bool was = c->kt.enabled; c->kt.enabled = false;
-    c->dd_done = 0; c->x_done = false;
     PRE3_TRY(launch_downdate(c, r, c->W));                         // (splits W into its bf16 planes on the way)
     PRE3_HIP(hipEventRecord(c->t0, c->stream));
-    for (int i = 0; i < reps; ++i) {
-        if (c->k9_b3 && c->dtype == PRE3_F32 && c->Wp != nullptr) c->split_rows = r_pad;      // the planes are there: time the down-date alone, as it runs behind a factorisation
-        PRE3_TRY(launch_downdate(c, r, c->W));
-    }
+    for (int i = 0; i < reps; ++i) PRE3_TRY(launch_downdate(c, r, c->W, -1, r_pad));      // the planes are there: time the down-date alone, as it runs behind a factorisation
     PRE3_HIP(hipEventRecord(c->t1, c->stream));
     PRE3_HIP(hipEventSynchronize(c->t1));
     float ms = 0; PRE3_HIP(hipEventElapsedTime(&ms, c->t0, c->t1));

@@ -2834,7 +2834,7 @@ int launch_cholp(pre3_ctx *c, int nrb, int nrb_max, int rows, int which_prior, c
     a.strip_rl = strip_rl;
     // every group of P's tiles is in this launch and the strips finish x: the consumers also leave rows 3..6 behind for the gate (GateRide, pre3_geom.hip)
     a.jn_q = (!tail && n_dd > 0 && n_dd == c->dd_n_groups && c->jn_q != nullptr) ? c->jn_q : nullptr;
-    c->jn_q_valid = a.jn_q != nullptr;
+    c->out.jn_q_valid = a.jn_q != nullptr;
     // with the consumers in the launch the strips also finish the state: x_k_k = x_prior + W'(L^-1 nu) (the K9 launch that used to carry the
     // x-update as riders has nothing left to do at N = 500)
     static const int xu_env = getenv("PRE3_CHOLP_XU") ? atoi(getenv("PRE3_CHOLP_XU")) : 1;
@@ -2845,13 +2845,13 @@ int launch_cholp(pre3_ctx *c, int nrb, int nrb_max, int rows, int which_prior, c
     a.tail = tail ? 1 : 0;
     // without the tail: the strips still end with the rescue stage's projection when the step wants the gate to ride with the Jnorm pass (GateRide)
     static const int proj_env = getenv("PRE3_CHOLP_PROJ") ? atoi(getenv("PRE3_CHOLP_PROJ")) : 1;
-    a.proj = (proj_env && !tail && c->want_gate_ride && a.jn_q != nullptr && a.xu && c->N > 0 && lds_strip <= CP_T_OFF) ? 1 : 0;
+    a.proj = (proj_env && !tail && c->req.want_gate_ride && a.jn_q != nullptr && a.xu && c->N > 0 && lds_strip <= CP_T_OFF) ? 1 : 0;
     if (a.proj) {
         t.N = c->N; t.lm_type = c->lm.type; t.lm_off = c->lm.off; t.has_h = c->lm.has_h; t.h = c->lm.h; t.Hc = c->lm.Hc; t.Hl = c->lm.Hl;
         t.cam = CamD{ c->cam.f, c->cam.Cx, c->cam.Cy, c->cam.k1, c->cam.k2, (double)c->cam.nRows, (double)c->cam.nCols };
         lds = 160 * 1024;
     }
-    c->proj_in_cholp = a.proj != 0;
+    c->out.proj_in_cholp = a.proj != 0;
     if (tail) {
         t.on = 1; t.N = c->N; t.m = c->m; t.seq = tail_req->seq; t.ykcap = c->rcap; t.chi2 = tail_req->chi2;
         t.lm_type = c->lm.type; t.lm_off = c->lm.off; t.lm_ic = c->lm.ic; t.lm_li = c->lm.li; t.meas = c->meas;
@@ -2864,11 +2864,11 @@ int launch_cholp(pre3_ctx *c, int nrb, int nrb_max, int rows, int which_prior, c
         t.dbgS = c->lm.S;
 #endif
     }
-    c->tail_launched = tail;
+    c->out.tail_launched = tail;
     // PRE3_OPT_PEND_HI: with every group of P's tiles in the launch the consumers take the pending HI down-date as the panels in front of panel 0
     // (and run even when the device finds no LI rows); otherwise it goes out as its own launch now
-    if (c->pend_rows > 0) {
-        if (!tail && n_dd > 0 && n_dd == c->dd_n_groups && c->Wp_pend != nullptr) { a.Wp_pend = c->Wp_pend; a.pend_ns = (c->pend_rows + B3_BK - 1) / B3_BK; c->pend_rows = 0; }
+    if (c->carry.pend_rows > 0) {
+        if (!tail && n_dd > 0 && n_dd == c->dd_n_groups && c->Wp_pend != nullptr) { a.Wp_pend = c->Wp_pend; a.pend_ns = (c->carry.pend_rows + B3_BK - 1) / B3_BK; c->carry.pend_rows = 0; }
         else PRE3_TRY(pend_flush(c));
     }
     // roofline bracket (pre3_kernel_timing): the launches that carry a matrix-bound down-date -- updates of the predicted state
@@ -2890,9 +2890,10 @@ int launch_cholp(pre3_ctx *c, int nrb, int nrb_max, int rows, int which_prior, c
         else cholp_timing_rows(c, a.rows);
     }
     PRE3_HIP(hipGetLastError());
-    c->split_rows = (nrb < 0 ? nrb_max : nrb) * NB;             // the strips' epilogues have written every plane k_downdate_b3 reads
-    c->x_done = a.xu != 0;
-    c->dd_done = n_dd;                                          // the next launch_downdate only covers the groups behind these
+    c->out.split_rows = (nrb < 0 ? nrb_max : nrb) * NB;         // the strips' epilogues have written every plane k_downdate_b3 reads
+    c->out.x_done = a.xu != 0;
+    c->out.dd_done = n_dd;                                      // the next launch_downdate only covers the groups behind these
+    c->out.cholp_done = nrb < 0;                                // the speculative launch of an LI update: launch_chol_solve has nothing left to do
     return PRE3_OK;
 }
 

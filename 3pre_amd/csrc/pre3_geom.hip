@@ -1097,12 +1097,12 @@ int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection, si
     }
     InboxRide ib{ (const int4 *)c->inbox_host_dev, (int4 *)c->inbox_dev, (int)inbox_n16, c->mail_dev, inbox_seq };     // one more block when inbox_n16 > 0
     const int nb = blocks + pr.n_blocks + (inbox_n16 ? 1 : 0);
-    const int fuse_jn = c->jn_pending ? 1 : 0;          // the pending update.m:42-46 pass of the update in front (run_update left it to this launch)
+    const int fuse_jn = c->carry.jn_pending ? 1 : 0;          // the pending update.m:42-46 pass of the update in front (run_update left it to this launch)
     DISPATCH_T(c,
         hipLaunchKernelGGL(k_predict<double>, dim3(nb), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (double *)c->P, c->n, c->ld, uu, c->pred_params, blocks, pr, ib, fuse_jn, PendW{}),
         hipLaunchKernelGGL(k_predict<float>, dim3(nb), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (float *)c->P, c->n, c->ld, uu, c->pred_params, blocks, pr, ib, fuse_jn, pend_args(c)));
     PRE3_HIP(hipGetLastError());
-    c->jn_pending = false;
+    c->carry.jn_pending = false;
     return PRE3_OK;
 }
 
@@ -1113,20 +1113,20 @@ int launch_jnorm(pre3_ctx *c, int)
     ProjRide pr{};
     GateRide<float> gr{};
     static const int gate_env = getenv("PRE3_GATE_RIDE") ? atoi(getenv("PRE3_GATE_RIDE")) : 1;      // 0: the gate as a launch of its own behind this one (rounds 3-4)
-    if (c->proj_with_jnorm && c->N > 0) {        // (no producer to wait for: x_k_k is complete)
-        if (gate_env && c->want_gate_ride && c->jn_q_valid && c->dtype == PRE3_F32) {
+    if (c->out.proj_with_jnorm && c->N > 0) {        // (no producer to wait for: x_k_k is complete)
+        if (gate_env && c->req.want_gate_ride && c->out.jn_q_valid && c->dtype == PRE3_F32) {
             // pre3_step behind a persistent launch whose consumers wrote all of P: projection AND chi2 gate ride here (GateRide)
-            gr.n_blocks = ceil_div(c->N, 16); gr.N = c->N; gr.Q = c->jn_q; gr.chi2 = c->rescue_chi2; gr.project = c->proj_in_cholp ? 0 : 1;
+            gr.n_blocks = ceil_div(c->N, 16); gr.N = c->N; gr.Q = c->jn_q; gr.chi2 = c->req.rescue_chi2; gr.project = c->out.proj_in_cholp ? 0 : 1;
             gr.lm_type = c->lm.type; gr.lm_off = c->lm.off; gr.x = c->x_kk; gr.cam = to_camd(c->cam);
             gr.h = c->lm.h; gr.has_h = c->lm.has_h; gr.Hc = c->lm.Hc; gr.Hl = c->lm.Hl; gr.z = c->lm.z; gr.ic = c->lm.ic; gr.li = c->lm.li; gr.hi = c->lm.hi;
-            c->rescue_gated = true;
+            c->out.rescue_gated = true;
         } else {
             pr = make_proj_ride(c, PRE3_X_K_K, 0, 1, 0);
         }
-        c->rescue_projected = true;
+        c->out.rescue_projected = true;
     }
-    c->proj_with_jnorm = false; c->proj_in_cholp = false;
-    c->jn_q_valid = false;                        // (Q belongs to the update that has just been normalised)
+    c->out.proj_with_jnorm = false; c->out.proj_in_cholp = false;
+    c->out.jn_q_valid = false;                     // (Q belongs to the update that has just been normalised)
     DISPATCH_T(c,
         hipLaunchKernelGGL(k_jnorm_P<double>, dim3(blocks + pr.n_blocks), dim3(256), 0, c->stream, (double *)c->P, c->n, c->ld, c->pred_params, blocks, pr, GateRide<double>{}),
         hipLaunchKernelGGL(k_jnorm_P<float>, dim3(blocks + pr.n_blocks + gr.n_blocks), dim3(256), 0, c->stream, (float *)c->P, c->n, c->ld, c->pred_params, blocks, pr, gr));

@@ -393,6 +393,7 @@ __device__ __forceinline__ void innov_ride_block(const InnovRide &ir, int blk)
 }
 
 ProjRide make_proj_ride(pre3_ctx *c, int which, int clear_first, int slot, int n_producers);   // pre3_geom.hip
+IcMatchRide ic_match_ride(const pre3_ctx *c);                                                  // pre3_match.hip
 
 
 // ---- (best, second, first arg) of siftmatch.c:110-116's scan, and the IC search's small-problem matcher tile (pre3_match.hip, k_ic_match_small; it

@@ -82,6 +82,44 @@ struct KernelTiming {
 
 }  // namespace pre3
 
+// ---- hand-offs between the host stages of one API call.  W: who writes, R: who reads.
+// What the current entry point asks the launchers below it to carry.  Written by extern "C" entry points, step_back and EntryScope; read-only for launchers.
+struct StepRequest {
+    bool leave_jn_to_predict = false;      // W EntryScope (step, readers) while it completes a deferred HI update | R update_hi_impl, run_update, flush_unless_kept
+    bool pend_keep = false;                // W EntryScope (step): this call's launches take a pending HI down-date along | R flush_unless_kept
+    bool defer_select = false;             // W step_back: the selection stage rides in the LI gather's launch | R ransac_impl
+    bool ride_innovation = false;          // W pre3_step, pre3_step_all: S_i goes out with the next H*P build launch | R launch_ell_HP_build(_sel)
+    bool ride_rescue_projection = false;   // W step_back: the LI update's K9 launch also projects at x_k_k | R launch_downdate
+    bool want_gate_ride = false; double rescue_chi2 = 0.0;   // W step_back: projection AND chi2 gate in the Jnorm pass's launch (GateRide) | R launch_cholp, launch_jnorm
+    bool tail_want = false; double tail_chi2 = 0.0;          // W step_back: the LI update's persistent launch carries the tail (CpTail) | R update_li_impl
+    const int32_t *book_from = nullptr;    // W pre3_map_policy: the updated counters the map re-layout reads instead of book | R apply_map
+};
+// What the launchers of the current call report back.  Written by launchers only; everybody else reads it or resets it whole.
+struct LaunchOutcome {
+    bool innovation_rode = false;          // W launch_ell_HP_build(_sel): S_i went out with this launch | R the same (once per call), step_back, pre3_step_all
+    bool rescue_projected = false;         // W launch_downdate, launch_jnorm: h / H at the current x_k_k are on the device | R the same (once per call), rescue_impl, step_back
+    bool proj_with_jnorm = false;          // W launch_downdate: no K9 launch was left, the projection rides in the next k_jnorm_P | R launch_jnorm (clears), run_update
+    bool rescue_gated = false;             // W launch_jnorm: the chi2 gate rode with the Jnorm pass | R step_back
+    bool cholp_done = false;               // W launch_cholp: the speculative launch has factored and solved | R update_li_impl, launch_chol_solve (clears)
+    bool tail_launched = false;            // W launch_cholp: that launch carried the tail | R update_li_impl
+    bool x_done = false;                   // W launch_cholp: its strips have computed x_k_k | R launch_downdate (clears)
+    bool jn_q_valid = false;               // W launch_cholp: its consumers left the un-normalised rows 3..6 of P in jn_q | R launch_jnorm (clears)
+    bool proj_in_cholp = false;            // W launch_cholp: its strips projected every landmark at x_k_k | R launch_jnorm (clears)
+    int dd_done = 0;                       // W launch_cholp: groups its consumers have down-dated | R launch_downdate (clears)
+    int split_rows = 0;                    // W launch_cholp, launch_chol_solve: rows of W whose bf16 planes exist | R launch_downdate (clears)
+};
+// Work one API call leaves for the next.  drop_carried() is the only reset (pre3_set_state).
+struct Carried {
+    bool hi_pending = false;               // W step_back (PRE3_OPT_DEFER_HI) | R EntryScope: completed by whatever call comes next
+    int last_n_hi = 0;                     // W EntryScope: the HI count of the deferred update it completed | R step_back (stats[5] under PRE3_OPT_DEFER_HI)
+    bool jn_pending = false;               // W update_hi_impl, run_update: a rows/cols 3..6 <- Jn pass waits for the next k_predict | R launch_predict_impl (takes it), EntryScope, readers
+    int pend_rows = 0;                     // W update_hi_impl (PRE3_OPT_PEND_HI): P stands for P - W~'W~ | R pend_args, pend_flush, launch_cholp (take them)
+    bool hi_pend_launched = false;         // W launch_hi_fused: W~ went to the pending buffers, no down-date launched | R update_hi_impl
+    bool hi_fused = false;                 // W step_back: collection + HI update went out as k_hi_fused | R update_hi_impl
+    bool tail_done = false;                // W update_li_impl: the tail ran inside the LI update's launch | R run_update, step_back, update_hi_impl
+    bool select_pending = false; int sel_n_draw = 0, sel_k = 0, sel_early_exit = 0;   // W ransac_impl: the selection is still to be launched | R update_li_impl; install_measurements drops it
+};
+
 struct pre3_ctx {
     int device = 0, dtype = PRE3_F32;
     size_t esz = 4;
@@ -105,17 +143,13 @@ struct pre3_ctx {
     int num_cus = 256;
     void *Wp = nullptr;                           // fp32 path: bf16 planes of W in stage-image order (k_split_w), ld x rcap x 6 B
     bool k9_b3 = false;                           // fp32: K9 as three-way bf16 split on the bf16 matrix cores (PRE3_K9_B3=0 turns it off)
-    int split_rows = 0;                           // rows of W whose bf16 planes the factorisation launches have already produced
     void *Sp = nullptr;                           // fp32 path: bf16 planes of the factorisation's S blocks (pending updates), rcap/64 x rcap/64 x 24 KB
     void *tiles128 = nullptr; int n_tiles128 = 0; // int2[n_tiles128]: 128x128 upper-triangle tiles of k_downdate_b3, XCD-interleaved
     unsigned int *chol_arrive = nullptr; unsigned int chol_target = 0;   // [0] panel arrivals, [1] scoring done, [2] rescue done, [3],[4] rider producers
     unsigned int ride_target[2] = { 0, 0 };
     void *comm = nullptr; bool comm_owned = false;                 // RCCL communicator (pre3_comm.hip): pre3_comm_init / pre3_set_comm
-    bool leave_jn_to_predict = false, jn_pending = false;          // the deferred HI update's rows/cols 3..6 <- Jn pass rides in the next k_predict
-    bool defer_hi = false, hi_pending = false; int last_n_hi = 0;   // PRE3_OPT_DEFER_HI (pre3_set_option)
-    bool ride_rescue_projection = false;          // request: the next K9 launch also projects at x_k_k (pre3_step sets it before the LI update)
-    bool rescue_projected = false;                // h / H at the current x_k_k are on the device (set by that launch, consumed by pre3_rescue)
-    //   // panel kernels: arrivals of the workgroups that read the raw diagonal block
+    StepRequest req; LaunchOutcome out; Carried carry;             // the hand-offs of a call: see the three structs above
+    bool defer_hi = false;                                         // PRE3_OPT_DEFER_HI (pre3_set_option)
     int p_which = -1;                             // which estimate P currently holds (-1: none)
     bool x_valid[2] = {false, false};
     pre3::LmBuffers lm;
@@ -148,17 +182,13 @@ struct pre3_ctx {
     int32_t *mail_host = nullptr, *mail_dev = nullptr;
     int32_t seq_select = 0, seq_collect = 0;
     bool g_valid = false;                         // c->G holds H*P*H' of all measured rows (PRE3_INLINE_G=0); otherwise the scorer and the LI gather compute their entries
-    // pre3_step: the selection stage of the RANSAC round is not launched by pre3_ransac but rides in the LI gather's launch (k_select_gather)
-    bool defer_select = false, select_pending = false;
-    int sel_n_draw = 0, sel_k = 0, sel_early_exit = 0;
     int li_from_host = -1, hi_from_host = -1;     // row counts forced through pre3_set_flags (-1: use the kernels' counts)
     bool li_kernel = false, hi_kernel = false;    // a select / collect kernel has run for the current measurement set
     // per-step inbox: [meas | ic | hyp | z] contiguous on the device, mirrored in pinned host memory -> ONE H2D copy
     void *inbox_dev = nullptr; unsigned char *inbox_host = nullptr; void *inbox_host_dev = nullptr;   // pinned + device-mapped: the device address of inbox_host
     size_t inbox_bytes = 0, off_meas = 0, off_ic = 0, off_hyp = 0, off_z = 0, off_flags = 0, flags_bytes = 0;
-    bool ride_innovation = false;                 // pre3_step: the S_i pass goes out with the next k_ell_HP_build launch instead of its own
     int32_t seq_inbox = 0;                        // sequence number of the last inbox pull (published by the kernel in mailbox word 10)
-    bool inbox_pending = false;
+    bool inbox_pending = false;                   // a pull out of the pinned inbox may still be in flight (install_measurements waits before it overwrites)
     // map management (allocated on first use)
     void *P_alt = nullptr; double *x_alt = nullptr; int32_t *map_col = nullptr; void *map_val = nullptr; int32_t *map_desc = nullptr; int32_t *map_src0 = nullptr; double *map_conv = nullptr;
     double *map_feat = nullptr; int32_t *map_flags = nullptr;
@@ -190,31 +220,21 @@ struct pre3_ctx {
     // persistent factorisation (pre3_cholp.hip)
     unsigned int *cholp_flags = nullptr; void *cholp_tp = nullptr; unsigned int cholp_epoch = 0; bool chol_persist = true;
     bool cholp_counted = false;                   // this context is in pre3_cholp.hip's per-device count
-    bool cholp_done = false;                      // the speculative launch of an LI update has already factored and solved
     // down-date consumers inside the persistent factorisation (pre3_cholp.hip): group records, all tiles in group order, first tile per group
     int32_t *dd_groups = nullptr; int dd_n_groups = 0; void *dd_tiles = nullptr; std::vector<int> dd_tile_off;
     bool k9_overlap = true;                       // PRE3_OPT_K9_OVERLAP
     bool shard_round = false;                     // the last RANSAC round was pre3_ransac_sharded (its selection publishes the missing-slice word in mail[11])
-    bool hi_fused = false;                        // the rescue stage's collection + HI update went out as k_hi_fused (pre3_step): pre3_update_hi only has the count to read
-    bool x_done = false;                          // ... and its strips have computed x_k_k = x_prior + W'(L^-1 nu) as well (update.m:36,42,48)
-    float *jn_q = nullptr; bool jn_q_valid = false;   // un-normalised rows 3..6 of P, left by the persistent launch's consumers for the gate that rides with the Jnorm pass (GateRide)
-    bool want_gate_ride = false, rescue_gated = false; double rescue_chi2 = 0.0;
-    bool proj_in_cholp = false;                   // the persistent launch's strips have projected every landmark at x_k_k (strip_proj_body): the gate needs no projection
-    bool proj_with_jnorm = false;                 // the rescue's projection rides in the next k_jnorm_P launch (no K9 launch to carry it)
-    int dd_done = 0;                              // groups the last k_cholp launch has down-dated (consumed by the next launch_downdate)
+    float *jn_q = nullptr;                        // un-normalised rows 3..6 of P, left by the persistent launch's consumers for the gate that rides with the Jnorm pass (GateRide)
     bool hp_all_valid = false;                    // HP / G hold H*P, H*P*H' of ALL measured rows at the current prior (ransac_prepare)
     // the rescue stage + HI update inside the persistent launch (pre3_cholp.hip, CpTail): per landmark the planes of y = H J W' and the row H J;
     // crit's published list
     void *tail_yp = nullptr; float *tail_hb = nullptr; int32_t *tail_hib = nullptr; float *tail_wt = nullptr;
-    // PRE3_OPT_PEND_HI (PendW, pre3_geomdev.h): k_hi_fused's W~ goes to its own buffers and the down-date is not launched; pend_rows > 0 from the moment the host
+    // PRE3_OPT_PEND_HI (PendW, pre3_geomdev.h): k_hi_fused's W~ goes to its own buffers and the down-date is not launched; carry.pend_rows > 0 from the moment the host
     // has the HI count (pre3_update_hi) until k_cholp's consumers have taken the panels (launch_cholp) or pend_flush() has run k_downdate_b3 on them
-    bool pend_opt = false; bool hi_pend_launched = false; bool pend_keep = false; int pend_rows = 0;
+    bool pend_opt = false;
     unsigned long long *hf_sx = nullptr;          // k_hi_fused, two panels: S as [128][128] (sequence number, value) pairs, dealt over the workgroups (hf_S_dealt)
     float *W_pend = nullptr; void *Wp_pend = nullptr; unsigned *hf_xy = nullptr;      // hf_xy: [0] k_hi_fused's "L^-1 nu is out" word, [64 .. 191] L^-1 nu (hf_x_update)
     bool step_tail = false;                       // PRE3_OPT_STEP_TAIL (default: the environment's PRE3_TAIL, else off)
-    bool tail_want = false; double tail_chi2 = 0;  // pre3_step asks the LI update's launch to carry the tail
-    bool tail_launched = false;                   // the last launch_cholp carried it
-    bool tail_done = false;                       // ... and it ran (the LI update had rows): P holds P - W'W - W~'W~ with ONE pending rows/cols 3..6 pass (params[96..])
     // marginal readers (pre3_get_landmarks / pre3_get_marginal, pre3_map.hip), allocated on first use: device results and their pinned host image;
     // the landmark block is sized by the map capacity, the index-set block grows with k
     double *lmr_dev = nullptr, *lmr_host = nullptr;
@@ -227,7 +247,6 @@ struct pre3_ctx {
     // after the LI update, recorded where the reference's rescue projects (pre3_step / pre3_step_predicted / pre3_rescue), cleared by every map call
     bool booked = false; int book_s = 0;          // book_s: init_frame / last_visible of landmarks a map call adds (the last policy call's step - 1)
     int32_t *book = nullptr, *book_alt = nullptr, *book_vis = nullptr;
-    const int32_t *book_from = nullptr;           // pre3_map_policy: the updated counters (policy scratch) the next apply_map re-lays out instead of book
     void *pol_dev = nullptr; size_t pol_dev_bytes = 0;                     // policy scratch: candidates, per-landmark flags and projections, blocked[K]
     int32_t *pol_host = nullptr, *pol_host_dev = nullptr; size_t pol_host_bytes = 0;   // the result block in mapped pinned memory
 };
@@ -245,9 +264,48 @@ __device__ inline void d_normjac(const double *q, double *J)
     J[12] = s * (-z * r); J[13] = s * (-z * x); J[14] = s * (-z * y); J[15] = s * (r * r + x * x + y * y);
 }
 
+// ---- the way into and out of every stateful entry point (pre3_api.hip).  In: the context is checked, a deferred HI update completed and pending work
+// flushed -- `ordinary`: all of it; `step`: the rows/cols 3..6 pass is left to the prediction's launch and (pend_keep) a pending HI down-date to this call's
+// own launches; `reader`: nothing is flushed.  Out: a rows/cols 3..6 pass nobody took goes out as its own launch (a reader that settled leaves it to the next
+// step), then req and out are reset.  Nested calls go through the *_impl functions, never through an exported wrapper.
+enum class Entry { ordinary, step, reader };
+struct EntryScope {
+    pre3_ctx *c; Entry kind; int rc;
+    explicit EntryScope(pre3_ctx *c, Entry kind = Entry::ordinary, bool pend_keep = false);
+    ~EntryScope();
+    EntryScope(const EntryScope &) = delete;
+};
+int flush_unless_kept(pre3_ctx *c);      /* a pending rows/cols 3..6 pass, then a pending HI down-date, out unless this call keeps them */
+void drop_carried(pre3_ctx *c);          /* the deferred work of a state that is being replaced is dropped, not run */
+int dmalloc_bytes(void **p, size_t bytes);
+int wait_mail(pre3_ctx *c, int slot, int32_t seq);      /* poll the pinned mailbox until the kernel launched with `seq` has published in word `slot` */
+int stats_words(pre3_ctx *c);            /* the device's error words, once a copy of them into pinned_stats has completed */
+int fetch_stats(pre3_ctx *c);
+// Fill the pinned inbox and ship it: [meas | ic | (hyp) | z].  pull == false: the caller's next launch carries the pull of *nbytes_out bytes (pre3_step: k_predict)
+int install_measurements(pre3_ctx *c, int m, const int32_t *meas_idx, const double *z /* 2m, null: z already on device */, const int32_t *hyp, int n_hyp_ints,
+                         bool flags_clear = false, bool pull = true, size_t *nbytes_out = nullptr);
+int set_descriptors_impl(pre3_ctx *c, int first, int count, const double *desc);
+int update_hi_impl(pre3_ctx *c);         /* pre3_step.hip: pre3_update_hi without the way in (EntryScope completes a deferred HI update with it) */
+
 // ---- pooled device scratch of the stateless entry points (pre3_match.hip)
 int scratch_acquire(size_t bytes, void **p_out, int *slot_out);
 void scratch_release(int slot, void *p);
+void release_scratch();
+// ---- matchers (pre3_match.hip)
+int match_partial(int device, int cls, int ND, int K1, const void *L1, int K2, const void *L2, int k2_offset, double *best, double *second, int32_t *arg);
+int knn_run(int device, int D, int N, const double *data, int M, const double *query, int k, double *ids, double *dist);
+void *match_bench_create(int cls, int ND, int K1, const void *L1, int K2, const void *L2);
+int match_bench_info(void *h, int32_t info[3]);
+int match_bench_run(void *h, int reps, double *ms_per);
+int match_bench_fetch(void *h, double *best, double *second, int32_t *arg);
+void match_bench_destroy(void *h);
+void *match_shard_create(int device, int cls, int ND, int K1, const void *L1, int K2, const void *L2, int k2_offset);
+int match_shard_run(void *h, void **partial_dev, int *n_doubles);
+int match_shard_merge(void *h, int G, const void *gathered_dev, double thresh, double *pairs_out, double *score_out, int *M_out);
+void match_shard_destroy(void *h);
+int match_shard_set_comm(void *h, void *comm);
+int match_shard_match(void *h, double thresh, double *pairs_out, double *score_out, int *M_out);
+int match_shard_test_stall(void *h, int release);
 
 // ---- RCCL communicator (pre3_comm.hip): collectives on the caller's stream
 int comm_all_reduce_i32(void *comm, void *buf, size_t count, hipStream_t st);                       /* in place, sum */
@@ -284,24 +342,31 @@ struct IcMatchRide;
 int launch_project_innovation(pre3_ctx *c, int which, int clear_first, int mode, double chi2, bool collect = true, bool clear_ic = false, const IcMatchRide *ride = nullptr);
 int launch_update_x(pre3_ctx *c, int which_prior, int r);
 int launch_jnorm(pre3_ctx *c, int which);
+int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection = false, size_t inbox_n16 = 0, int32_t inbox_seq = 0);
+// (either direction: 16-byte words between device memory and a mapped pinned block, then `seq` into mailbox word `slot`)
+int launch_inbox_pull(pre3_ctx *c, const void *src_host_mapped, void *dst_dev, size_t n16, int32_t seq, int slot = 10, int32_t *clear = nullptr, int n_clear = 0);
+int launch_slice_prepare(pre3_ctx *c, const void *src_host_mapped, size_t n16, int32_t seq, int n_zero, int k, int lo, int hi, int tag);
+int launch_window_gate(pre3_ctx *c, int M, const int32_t *pred_idx_dev, const int32_t *k1_dev, const double *zc_dev, int strict, int32_t *accept_dev);
+int launch_build_rows_impl(pre3_ctx *c, int nsel, const int32_t *sel_dev, int r_pad);
+int launch_ransac_score_impl(pre3_ctx *c, int k, double threshold, int hyp_begin, int hyp_end, int ldg, int32_t *support_dev, uint32_t *mask_dev, int mask_words,
+                             int select_n_draw = 0, int early_exit = 0);
+int launch_ransac_select_impl(pre3_ctx *c, int n_draw, int k, int early_exit, int32_t *support_dev, const uint32_t *mask_dev, int mask_words, int err_idx = -1);
 
 // ---- marginal readers (pre3_map.hip): gathers of x and P at `which`, a pending HI down-date (PendW) and a pending rows/cols 3..6 pass (jn: Jn on the
 // device, null: none) applied by the reading launch itself; results into the caller's host arrays (any may be null).  Arguments checked by the caller.
 int read_landmarks(pre3_ctx *c, int which, int first, int count, double *xyz, double *cov_xyz, double *cov_native, double *linearity);
 int read_marginal(pre3_ctx *c, int which, int k, const int32_t *idx, const double *jn, double *x_out, double *P_out);
 void free_readers(pre3_ctx *c);
-int flush_unless_kept(pre3_ctx *c);
 
 // ---- small-rank update on the resident x_k_k / p_k_k (pre3_rows.hip): rows from the host block, or (rows == null) the heading rows built on the device
 // from x_k_k(4:7) behind the gate of hd.  Two launches, P swept once.  rows_applied: the gate word into host memory, on the stream (caller drains).
 int launch_rows_update(pre3_ctx *c, const RowsBlock *rows, const RowsHeading *hd);
 int rows_applied(pre3_ctx *c, int32_t *applied_host);
-void free_rows(pre3_ctx *c);     /* a pending rows/cols 3..6 pass, then a pending HI down-date, out unless this call keeps them (pre3_api.hip) */
+void free_rows(pre3_ctx *c);
 
 // ---- map policy (pre3_map.hip): the rescue-visibility rider of a booked context (one small launch at the post-LI x_k_k), buffers
 int launch_book_vis(pre3_ctx *c);
 void free_policy(pre3_ctx *c);
-int settle_ctx(pre3_ctx *c);     /* pre3_api.hip: complete a deferred HI update and flush pending work, as every ordinary call does first */
 
 int run_hypothesis_support(int n, const double *xi, const pre3_cam &cam, int n_id, const int32_t *i1, const int32_t *i2, const int32_t *i3,
                            const double *z_id, int n_euc, const int32_t *i4, const double *z_euc, double threshold, int32_t *out_host /* [1 + n_id + n_euc] */);
@@ -322,7 +387,9 @@ int launch_select_gather(pre3_ctx *c, int n_draw, int k, int early_exit, int mas
 bool select_gather_usable(const pre3_ctx *c);
 int launch_ell_HP(pre3_ctx *c, int r, void *dst /*r_pad x ldw*/, bool with_nu);
 int launch_ell_G(pre3_ctx *c, int r, const void *HPsrc, void *dst, int ldg, int add_identity, const void *Rdense, bool lower_only = false);
-int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior = -1 /* >= 0: also x <- x_prior + W'y (update.m:36) */);
+int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior = -1 /* >= 0: also x <- x_prior + W'y (update.m:36) */,
+                    int planes_rows = 0 /* pre3_bench_downdate: rows of W whose bf16 planes an earlier launch of the same W has produced */);
+int launch_fill_w(pre3_ctx *c, int r_pad);
 bool hi_fused_usable(const pre3_ctx *c);
 int hi_fused_max(const pre3_ctx *c);                  /* landmarks k_hi_fused updates with on its own (64: two panels; 32) */
 int launch_hi_fused(pre3_ctx *c, int32_t seq);        /* the HI collection + update of up to 32 landmarks without the host (k_hi_fused + its down-date) */

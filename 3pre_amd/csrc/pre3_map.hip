@@ -413,7 +413,7 @@ static int apply_map(pre3_ctx *c, const std::vector<int32_t> &desc, int n_new, c
     const int fin_work = std::max(std::max(std::max(n_new, (int)(c->inbox_bytes / 4)), with_bank ? N * 128 : 0), with_book ? std::max(4 * N, c->capN) : 0);
     const MapFinish fin{ n_new, c->x_alt, c->x_kk, N, d_types, d_off, c->lm.type, c->lm.off, c->capN, c->lm.has_h, c->lm.has_S, (int32_t *)c->inbox_dev, (int)(c->inbox_bytes / 4),
                          d_src, with_bank ? c->bank : nullptr, c->bank_alt,
-                         c->book_from ? c->book_from : c->book, with_book ? c->book_alt : nullptr, c->book_vis, c->book_s };
+                         c->req.book_from ? c->req.book_from : c->book, with_book ? c->book_alt : nullptr, c->book_vis, c->book_s };
     static const int one_pass = getenv("PRE3_MAP_ONE_PASS") ? atoi(getenv("PRE3_MAP_ONE_PASS")) : 1;
     if (one_pass) {
         // one pass into the second buffer, which becomes P
@@ -455,7 +455,7 @@ static int map_precheck(pre3_ctx *c, const char *who)
     PRE3_HIP(hipSetDevice(c->device));
     PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "%s: needs (x_k_k, p_k_k) on the device (map management runs between steps)", who);
     // (a rows/cols 3..6 pass -- and the HI down-date behind it -- that a marginal reader left pending for the next step goes out first: the map is re-laid out)
-    if (c->jn_pending) PRE3_TRY(flush_unless_kept(c));
+    if (c->carry.jn_pending) PRE3_TRY(flush_unless_kept(c));
     return ensure_map_buffers(c);
 }
 
@@ -1009,7 +1009,7 @@ int pre3_set_book(pre3_ctx *c, int first, int count, const int32_t *book)
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
     PRE3_CHECK(first >= 0 && count >= 0 && (long long)first + count <= c->N && (count == 0 || book != nullptr), PRE3_E_ARG,
                "pre3_set_book: landmarks %d .. %d outside the map (N=%d)", first, first + count - 1, c->N);
-    PRE3_TRY(settle_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_TRY(start_book(c));
     if (count > 0) PRE3_HIP(hipMemcpyAsync(c->book + 4 * (size_t)first, book, sizeof(int32_t) * 4 * (size_t)count, hipMemcpyHostToDevice, c->stream));
     return stream_drain(c, __func__);
@@ -1021,7 +1021,7 @@ int pre3_get_book(pre3_ctx *c, int first, int count, int32_t *book_out)
     PRE3_CHECK(c->booked, PRE3_E_STATE, "pre3_get_book: the context has no book (pre3_set_book)");
     PRE3_CHECK(first >= 0 && count >= 0 && (long long)first + count <= c->N && (count == 0 || book_out != nullptr), PRE3_E_ARG,
                "pre3_get_book: landmarks %d .. %d outside the map (N=%d)", first, first + count - 1, c->N);
-    PRE3_TRY(settle_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     if (count > 0) PRE3_HIP(hipMemcpyAsync(book_out, c->book + 4 * (size_t)first, sizeof(int32_t) * 4 * (size_t)count, hipMemcpyDeviceToHost, c->stream));
     return stream_drain(c, __func__);
 }
@@ -1049,7 +1049,7 @@ int pre3_map_policy(pre3_ctx *c, int step, int min_features, double convert_thre
     PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "pre3_map_policy: needs (x_k_k, p_k_k) on the device (map management runs between steps)");
     PRE3_CHECK(c->booked || c->N == 0, PRE3_E_STATE, "pre3_map_policy: the context has no book (pre3_set_book)");
     // ---- a deferred HI update completed, pending work flushed (map_precheck); the book
-    PRE3_TRY(settle_ctx(c));
+    EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_TRY(map_precheck(c, "pre3_map_policy"));
     PRE3_TRY(start_book(c));
     const int N = c->N;
@@ -1103,14 +1103,13 @@ int pre3_map_policy(pre3_ctx *c, int step, int min_features, double convert_thre
     // initialize_features.m:120 passes step - 1 to add_feature_to_info_vector_my_version_sift.m:42-60)
     // (the counters reach the book only through this re-layout: a failure before it leaves the book as it was)
     const int book_s_before = c->book_s;
-    c->book_s = step - 1; c->book_from = d_nbook;
+    c->book_s = step - 1; c->req.book_from = d_nbook;
     const int rc_map = map_compose(c, n_del, dl.data(), flags, converted_out, n_acc, uvd.data(), std_pxl, rho_acc.data(), true);
-    c->book_from = nullptr;
     if (rc_map != PRE3_OK) { c->book_s = book_s_before; return rc_map; }
     if (cand_desc != nullptr && n_acc > 0) {                        // initialize_a_feature_sift_3.m:132: the candidate's own descriptor
         std::vector<double> dsc(128 * (size_t)n_acc);
         for (int a = 0; a < n_acc; ++a) memcpy(dsc.data() + 128 * (size_t)a, cand_desc + 128 * (size_t)acc[a], sizeof(double) * 128);
-        PRE3_TRY(pre3_set_descriptors(c, n_surv, n_acc, dsc.data()));
+        PRE3_TRY(set_descriptors_impl(c, n_surv, n_acc, dsc.data()));
     }
     if (del_out) for (int d = 0; d < n_del; ++d) del_out[d] = dl[d];
     if (n_del_out) *n_del_out = n_del;

@@ -2322,7 +2322,7 @@ int launch_ell_HP_build_sel(pre3_ctx *c, int nsel, const int32_t *sel_dev, void 
     if (r_pad == 0) return PRE3_OK;
     const int gx = ceil_div(c->ldw / 4, 256), ny = r_pad / 2;
     InnovRide ir{};
-    if (c->ride_innovation && c->N > 0) {            // pre3_step_all: S_i of every predicted landmark (+ the clearing of last frame's inlier flags) in this launch
+    if (c->req.ride_innovation && !c->out.innovation_rode && c->N > 0) {            // pre3_step_all: S_i of every predicted landmark (+ the clearing of last frame's inlier flags) in this launch
         const int nb = ceil_div(c->N * 16, 256), rows = ceil_div(nb, gx);
         ir = InnovRide{ rows * gx, c->N, c->ld, (int)(c->flags_bytes / sizeof(int32_t)), c->lm.type, c->lm.off, c->lm.has_h, c->P, c->lm.Hc, c->lm.Hl,
                         c->lm.S, c->lm.has_S, (int32_t *)((unsigned char *)c->inbox_dev + c->off_flags) };
@@ -2338,7 +2338,7 @@ int launch_ell_HP_build_sel(pre3_ctx *c, int nsel, const int32_t *sel_dev, void 
             hipLaunchKernelGGL(kf, g, b, 0, c->stream, nsel, r_pad, c->meas, c->lm.type, c->lm.off, c->lm.Hc, c->lm.Hl, c->lm.z, c->lm.h,
                                c->row_col, (float *)c->row_val, c->row_nu, (const float *)c->P, c->ld, (float *)dst, c->ldw, (const int32_t *)nullptr, 0, nyg, ir, sel_dev, InboxRide{}, PendW{}));
         PRE3_HIP(hipGetLastError());
-        if (ir.n_blocks) { c->ride_innovation = false; c->innovated = true; }
+        if (ir.n_blocks) { c->out.innovation_rode = true; c->innovated = true; }
         return PRE3_OK;
     }
     dim3 g(gx, ny + (ir.n_blocks ? ir.n_blocks / gx : 0)), b(256);
@@ -2348,7 +2348,7 @@ int launch_ell_HP_build_sel(pre3_ctx *c, int nsel, const int32_t *sel_dev, void 
         hipLaunchKernelGGL(k_ell_HP_build<float>, g, b, 0, c->stream, nsel, r_pad, c->meas, c->lm.type, c->lm.off, c->lm.Hc, c->lm.Hl, c->lm.z, c->lm.h,
                            c->row_col, (float *)c->row_val, c->row_nu, (const float *)c->P, c->ld, (float *)dst, c->ldw, (const int32_t *)nullptr, 0, ny, ir, sel_dev));
     PRE3_HIP(hipGetLastError());
-    if (ir.n_blocks) { c->ride_innovation = false; c->innovated = true; }
+    if (ir.n_blocks) { c->out.innovation_rode = true; c->innovated = true; }
     return PRE3_OK;
 }
 
@@ -2360,7 +2360,7 @@ int launch_ell_HP_build(pre3_ctx *c, void *dst, const int32_t *need, int need_ta
     const int r_pad = round_up(2 * c->m, NB);
     const int gx = ceil_div(c->ldw / 4, 256), ny = r_pad / 2;
     InnovRide ir{};
-    if (c->ride_innovation && c->N > 0) {            // pre3_step: S_i of every predicted landmark (+ the clearing of last frame's inlier flags) in this launch
+    if (c->req.ride_innovation && !c->out.innovation_rode && c->N > 0) {            // pre3_step: S_i of every predicted landmark (+ the clearing of last frame's inlier flags) in this launch
         const int nb = ceil_div(c->N * 16, 256), rows = ceil_div(nb, gx);
         ir = InnovRide{ rows * gx, c->N, c->ld, (int)(c->flags_bytes / sizeof(int32_t)), c->lm.type, c->lm.off, c->lm.has_h, c->P, c->lm.Hc, c->lm.Hl,
                         c->lm.S, c->lm.has_S, (int32_t *)((unsigned char *)c->inbox_dev + c->off_flags) };
@@ -2382,7 +2382,7 @@ int launch_ell_HP_build(pre3_ctx *c, void *dst, const int32_t *need, int need_ta
             hipLaunchKernelGGL(kf, g, b, 0, c->stream, c->m, r_pad, c->meas, c->lm.type, c->lm.off, c->lm.Hc, c->lm.Hl, c->lm.z, c->lm.h,
                                c->row_col, (float *)c->row_val, c->row_nu, (const float *)c->P, c->ld, (float *)dst, c->ldw, need, need_tag, nyg, ir, (const int32_t *)nullptr, ib, pw));
         PRE3_HIP(hipGetLastError());
-        if (ir.n_blocks) { c->ride_innovation = false; c->innovated = true; }
+        if (ir.n_blocks) { c->out.innovation_rode = true; c->innovated = true; }
         return PRE3_OK;
     }
     dim3 g(gx, ny + (ir.n_blocks ? ir.n_blocks / gx : 0) + ib_rows), b(256);
@@ -2392,7 +2392,7 @@ int launch_ell_HP_build(pre3_ctx *c, void *dst, const int32_t *need, int need_ta
         hipLaunchKernelGGL(k_ell_HP_build<float>, g, b, 0, c->stream, c->m, r_pad, c->meas, c->lm.type, c->lm.off, c->lm.Hc, c->lm.Hl, c->lm.z, c->lm.h,
                            c->row_col, (float *)c->row_val, c->row_nu, (const float *)c->P, c->ld, (float *)dst, c->ldw, need, need_tag, ny, ir, (const int32_t *)nullptr, ib));
     PRE3_HIP(hipGetLastError());
-    if (ir.n_blocks) { c->ride_innovation = false; c->innovated = true; }
+    if (ir.n_blocks) { c->out.innovation_rode = true; c->innovated = true; }
     return PRE3_OK;
 }
 
@@ -2423,14 +2423,14 @@ int launch_ell_G_hyp(pre3_ctx *c, int k, int lo, int hi, int ldg)
 static int launch_chol_solve(pre3_ctx *c, int r_pad, bool first_done = false, bool predicted_prior = false, int r = -1 /* real rows, if known */, int which_prior = -1)
 {
     int nrb = r_pad / NB, nW = c->ldw / NB;
-    c->split_rows = 0;
-    if (first_done && c->cholp_done) {             // pre3_update_li's speculative launch was the persistent form: everything is done
-        c->cholp_done = false;
-        c->split_rows = nrb * NB;                  // (c->dd_done: the groups its consumers have down-dated already)
+    c->out.split_rows = 0;
+    if (first_done && c->out.cholp_done) {         // pre3_update_li's speculative launch was the persistent form: everything is done
+        c->out.cholp_done = false;
+        c->out.split_rows = nrb * NB;              // (out.dd_done: the groups its consumers have down-dated already)
         if (c->kt.pending) cholp_timing_rows(c, r > 0 ? r : r_pad);
         return PRE3_OK;
     }
-    c->cholp_done = false; c->dd_done = 0; c->x_done = false;
+    c->out.cholp_done = false; c->out.dd_done = 0; c->out.x_done = false;
     // (one panel is one launch in either form, and the lock-step form has no hand-off in it: 12.5 us against 17 -- taken for the rescue
     // stage's small updates; an update of the PREDICTED state keeps the persistent form at any size, because pre3_update_li's speculative
     // launch -- row count still on the device -- cannot choose, and the two ways into that update must compute the same thing)
@@ -2499,13 +2499,16 @@ static int launch_chol_solve(pre3_ctx *c, int r_pad, bool first_done = false, bo
                                    c->Wp, c->rcap / B3_BK, c->Sp, c->rcap / NB, J);
             }
         }
-        if (split) c->split_rows = nrb * NB;
+        if (split) c->out.split_rows = nrb * NB;
         PRE3_HIP(hipGetLastError());
         return PRE3_OK;
     }
 }
 
-int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior)
+// the step asks for the rescue's projection as a rider (req) and no launch of this call has taken it yet (out)
+static bool rescue_ride_open(const pre3_ctx *c) { return c->req.ride_rescue_projection && !c->out.rescue_projected && !c->out.proj_with_jnorm && c->N > 0; }
+
+int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior, int planes_rows)
 {
     int r_pad = round_up(r, NB);
     // persistent grid: 2 workgroups per CU (or one per tile when there are fewer tiles); the tile counter is
@@ -2527,7 +2530,7 @@ int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior)
     // only launches in the matrix-bound regime are bracketed: the updates of the PREDICTED state (the LI updates, r_pad >= 128; and
     // pre3_bench_downdate).  The rescue stage's HI update -- a few dozen rows, at most a couple of panels early in a sequence -- is a
     // read-modify-write of P at HBM speed and would only dilute the figure, and with 'one in N' it would alias with the LI/HI alternation
-    const bool timed = c->kt.enabled && c->dd_done == 0 && r_pad >= 2 * NB && which_prior != PRE3_X_K_K && (c->kt.seen++ % c->kt.every) == 0;
+    const bool timed = c->kt.enabled && c->out.dd_done == 0 && r_pad >= 2 * NB && which_prior != PRE3_X_K_K && (c->kt.seen++ % c->kt.every) == 0;
     if (timed) {
         if ((size_t)c->kt.used + 2 > c->kt.ev.size()) {
             for (int i = 0; i < 2; ++i) { hipEvent_t e; PRE3_HIP(hipEventCreate(&e)); c->kt.ev.push_back(e); }
@@ -2540,8 +2543,8 @@ int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior)
         // k-stages of 16 rows: rows r .. r_pad-1 of W are zero (identity padding of S against zero rows of H*P), so the stages that hold nothing
         // else are skipped -- the tile loop wants an even count of at least four (r = 518: 34 stages instead of 36)
         const int nst = std::min(r_pad / B3_BK, std::max(4, 2 * ceil_div(r, 2 * B3_BK))), nst_total = c->rcap / B3_BK;
-        const int st0 = c->split_rows / B3_BK;                         // row blocks the factorisation's riders have already split
-        c->split_rows = 0;
+        const int st0 = std::max(c->out.split_rows, planes_rows) / B3_BK;      // row blocks the factorisation's riders have already split
+        c->out.split_rows = 0;
         if (st0 < nst) {
             dim3 gs(c->ld / B3_T, nst - st0);
             hipLaunchKernelGGL(k_split_w, gs, b, 0, c->stream, (const float *)W, c->ldw, (bf16x8_t *)c->Wp, nst_total, st0);
@@ -2550,27 +2553,26 @@ int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior)
         // -- nothing at N = 500 -- goes out as 64 x 64 tiles; the x-update and the rescue's projection ride in this launch either way
         const int2 *tiles = (const int2 *)c->tiles128;
         int n_tiles_launch = c->n_tiles128;
-        if (c->dd_done > 0) {
-            const int t0 = c->dd_tile_off[c->dd_done];
+        if (c->out.dd_done > 0) {
+            const int t0 = c->dd_tile_off[c->out.dd_done];
             tiles = (const int2 *)c->dd_tiles + t0;
             n_tiles_launch = c->dd_tile_off.back() - t0;
         }
-        c->dd_done = 0;
+        c->out.dd_done = 0;
         XUpd xu{ n_tiles_launch, c->n, r, which_prior == PRE3_X_K_K ? c->x_kk : c->x_km1, c->x_kk, c->pred_params, nullptr, 0 };
         xu.wt = k9_write_through();
-        const bool x_done = c->x_done && which_prior >= 0;            // the factorisation's strips have computed x_k_k already
-        c->x_done = false;
+        const bool x_done = c->out.x_done && which_prior >= 0;        // the factorisation's strips have computed x_k_k already
+        c->out.x_done = false;
         const int nx = (which_prior >= 0 && !x_done) ? ceil_div(c->n, 64) : 0;
         xu.nx = nx;
         ProjRide pr{};
-        if (which_prior >= 0 && c->ride_rescue_projection && c->N > 0) {
+        if (which_prior >= 0 && rescue_ride_open(c)) {
             if (n_tiles_launch + nx == 0) {                           // nothing left for this launch: the projection rides with the Jnorm pass
-                c->proj_with_jnorm = true;
+                c->out.proj_with_jnorm = true;
             } else {
                 pr = make_proj_ride(c, PRE3_X_K_K, 0, 1, nx);
-                c->rescue_projected = true;
+                c->out.rescue_projected = true;
             }
-            c->ride_rescue_projection = false;
         }
         dim3 g1(n_tiles_launch + nx + pr.n_blocks);
         if (g1.x > 0) {
@@ -2583,9 +2585,9 @@ int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior)
         const int nx = which_prior >= 0 ? ceil_div(c->n, 64) : 0;
         xu.nx = nx;
         ProjRide pr{};
-        if (nx > 0 && c->ride_rescue_projection && c->N > 0) {      // the rescue's projection (stale h kept: clear_first = 0) rides along
+        if (nx > 0 && rescue_ride_open(c)) {                        // the rescue's projection (stale h kept: clear_first = 0) rides along
             pr = make_proj_ride(c, PRE3_X_K_K, 0, 1, nx);
-            c->ride_rescue_projection = false; c->rescue_projected = true;
+            c->out.rescue_projected = true;
         }
         dim3 g1(c->n_tiles + nx + pr.n_blocks);
         // fp64 with few tiles per CU (configs[1]: 210 tiles on 256 CUs): two waves per wave tile, so that every SIMD has two waves to overlap
@@ -2631,16 +2633,16 @@ int hi_fused_max(const pre3_ctx *c)
 
 PendW pend_args(const pre3_ctx *c)
 {
-    if (c->pend_rows <= 0 || c->W_pend == nullptr) return PendW{};
-    return PendW{ c->W_pend, c->ldw, c->pend_rows, c->Wp_pend, c->rcap / B3_BK };
+    if (c->carry.pend_rows <= 0 || c->W_pend == nullptr) return PendW{};
+    return PendW{ c->W_pend, c->ldw, c->carry.pend_rows, c->Wp_pend, c->rcap / B3_BK };
 }
 
 // the pending HI down-date as the launch it would have been (tiles only: the x-update went out with k_hi_fused's launch pair)
 int pend_flush(pre3_ctx *c)
 {
-    if (c->pend_rows <= 0) return PRE3_OK;
-    const int rows = c->pend_rows;
-    c->pend_rows = 0;
+    if (c->carry.pend_rows <= 0) return PRE3_OK;
+    const int rows = c->carry.pend_rows;
+    c->carry.pend_rows = 0;
     XUpd xu{ c->n_tiles128, c->n, 0, c->x_kk, c->x_kk, c->pred_params, nullptr, 0 };
     xu.wt = k9_write_through();
     ProjRide pr{};
@@ -2673,11 +2675,11 @@ int launch_hi_fused(pre3_ctx *c, int32_t seq)
     // the x-update only, and P - W~'W~ stays pending (pre3_update_hi learns the row count; pend_flush / launch_cholp end it)
     const bool pend = c->pend_opt && c->W_pend != nullptr && c->Wp_pend != nullptr && c->hf_xy != nullptr && co_resident;
     if (pend) { a.W = c->W_pend; a.Wp = c->Wp_pend; a.n = c->n; a.x = c->x_kk; a.xflag = c->hf_xy; }
-    c->hi_pend_launched = pend;
+    c->carry.hi_pend_launched = pend;
     hipLaunchKernelGGL(k_hi_fused, dim3(1 + c->ldw / NB), dim3(CH_NTH), 0, c->stream, a);
     if (pend) {                                    // (the strips finish the state themselves: hf_x_update)
         PRE3_HIP(hipGetLastError());
-        c->split_rows = 0; c->dd_done = 0; c->x_done = false; c->cholp_done = false;
+        c->out.split_rows = 0; c->out.dd_done = 0; c->out.x_done = false; c->out.cholp_done = false;
         return PRE3_OK;
     }
     // the down-date of that update (one or two panels: four or eight k-stages, read on the device), the x-update riding along; every workgroup leaves at once unless stats[8] == 1
@@ -2688,7 +2690,7 @@ int launch_hi_fused(pre3_ctx *c, int32_t seq)
     hipLaunchKernelGGL(k_downdate_b3, dim3(c->n_tiles128 + nx), dim3(256), 0, c->stream, (float *)c->P, c->ld, (const bf16x8_t *)c->Wp, c->rcap / B3_BK, 4,
                        (const float *)c->W, c->ldw, (const int2 *)c->tiles128, xu, pr);
     PRE3_HIP(hipGetLastError());
-    c->split_rows = 0; c->dd_done = 0; c->x_done = false; c->cholp_done = false;
+    c->out.split_rows = 0; c->out.dd_done = 0; c->out.x_done = false; c->out.cholp_done = false;
     return PRE3_OK;
 }
 
@@ -2780,8 +2782,8 @@ int launch_chol_first_spec(pre3_ctx *c, int nsel_max)
 int run_update(pre3_ctx *c, int which_prior, int r, bool dense_R, void *Kt_out_dev, bool prebuilt, bool first_done, bool hp_built)
 {
     if (r == 0) {   // update.m:50-55: x_k_k = x_km1_k, p_k_k = p_km1_k
-        c->dd_done = 0; c->x_done = false; c->cholp_done = false;      // (a speculative persistent launch found no rows on the device either)
-        c->jn_q_valid = false; c->proj_in_cholp = false;               // (... so its consumers left no rows 3..6 behind and its strips projected nothing)
+        c->out.dd_done = 0; c->out.x_done = false; c->out.cholp_done = false;      // (a speculative persistent launch found no rows on the device either)
+        c->out.jn_q_valid = false; c->out.proj_in_cholp = false;                   // (... so its consumers left no rows 3..6 behind and its strips projected nothing)
         if (c->kt.pending) cholp_timing_rows(c, 0);
         if (which_prior == PRE3_X_K_KM1) PRE3_HIP(hipMemcpyAsync(c->x_kk, c->x_km1, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
         return PRE3_OK;
@@ -2795,16 +2797,16 @@ int run_update(pre3_ctx *c, int which_prior, int r, bool dense_R, void *Kt_out_d
     }
     // (a stateless update that wants K' back keeps the x-update where it was)
     PRE3_TRY(launch_chol_solve(c, r_pad, first_done, which_prior == PRE3_X_K_KM1, r, which_prior));
-    if (c->tail_done && first_done && which_prior == PRE3_X_K_KM1) {
+    if (c->carry.tail_done && first_done && which_prior == PRE3_X_K_KM1) {
         // the speculative persistent launch has carried everything: factorisation, solve, x-update, rescue stage, the HI update of up to 32
         // landmarks, and ONE down-date of P for both updates (pre3_cholp.hip, CpTail).  The rows / columns 3..6 pass that is left
         // (update.m:42-46 of both updates, params[96..]) is pre3_update_hi's to schedule, once it knows how the rescue stage ended.
-        c->dd_done = 0; c->x_done = false; c->split_rows = 0; c->ride_rescue_projection = false; c->proj_with_jnorm = false;
+        c->out.dd_done = 0; c->out.x_done = false; c->out.split_rows = 0;
         return PRE3_OK;
     }
     PRE3_TRY(launch_downdate(c, r, c->W, which_prior));
     // update.m:42-46.  leave_jn_to_predict (pre3_step completing the previous step's HI update): the prediction's launch that follows carries it
-    if (c->leave_jn_to_predict && !Kt_out_dev && !c->proj_with_jnorm) c->jn_pending = true;
+    if (c->req.leave_jn_to_predict && !Kt_out_dev && !c->out.proj_with_jnorm) c->carry.jn_pending = true;
     else PRE3_TRY(launch_jnorm(c, 0));
     if (Kt_out_dev) {
         dim3 g(ceil_div(c->n, 256)), b(256);
