@@ -512,6 +512,7 @@ int pre3_destroy(pre3_ctx *c)
     for (void *b : bufs) if (b) (void)hipFree(b);
     free_readers(c);
     free_rows(c);
+    free_plane(c);
     free_policy(c);
     for (int k2 = 0; k2 < 2; ++k2) { if (c->map_stage[k2]) (void)hipHostFree(c->map_stage[k2]); if (c->map_stage_ev[k2]) (void)hipEventDestroy(c->map_stage_ev[k2]); }
     for (int k2 = 0; k2 < 2; ++k2) { if (c->up_stage[k2]) (void)hipHostFree(c->up_stage[k2]); if (c->up_stage_ev[k2]) (void)hipEventDestroy(c->up_stage_ev[k2]); }
@@ -865,10 +866,11 @@ static bool copy_desc_checked(double *__restrict__ dst, const double *__restrict
     return bad == 0;
 }
 
+}  // extern "C"
 // A pinned block of the context for `bytes` of host data on their way to the device: two blocks, used alternately, grown on demand; a block is
 // written again only after the pull of its previous contents has run (its sequence number in the mailbox: stage_wait).  The caller fills *host, enqueues the pull from *dev on the
 // context's stream and calls stage_release.
-static int stage_acquire(pre3_ctx *c, size_t bytes, void **host, void **dev, int *slot)
+int pre3::stage_acquire(pre3_ctx *c, size_t bytes, void **host, void **dev, int *slot)
 {
     if (c->up_stage_bytes < bytes) {
         for (int k = 0; k < 2; ++k) {
@@ -889,13 +891,12 @@ static int stage_acquire(pre3_ctx *c, size_t bytes, void **host, void **dev, int
     PRE3_HIP(hipHostGetDevicePointer(dev, c->up_stage[k], 0));
     return PRE3_OK;
 }
-static int stage_release(pre3_ctx *c, int slot)        // (the pull launched with stage_done(c, slot) announces itself)
+int pre3::stage_release(pre3_ctx *c, int slot)        // (the pull launched with stage_done(c, slot) announces itself)
 {
     c->up_stage_used[slot] = true;
     return PRE3_OK;
 }
 
-}  // extern "C"
 int pre3::set_descriptors_impl(pre3_ctx *c, int first, int count, const double *desc)
 {
     PRE3_CHECK(first >= 0 && count >= 0 && first + count <= c->N && (count == 0 || desc), PRE3_E_ARG, "pre3_set_descriptors: range [%d, %d) outside the map (N=%d)", first, first + count, c->N);

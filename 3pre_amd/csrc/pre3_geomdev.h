@@ -499,4 +499,50 @@ __device__ __forceinline__ void ic_match_tile(const IcMatchRide &r, const int ti
     }
 }
 
+// ekf_heading_update.m:36-40: RR = J_z J_e2q diag((pi/180)^2 [1 1 1]) J_e2q' J_z' with [~, J_e2q] = e2q(q2e(R2q(R_plane))) and
+// J_z = observe_heading_jac(R2q(R_plane)).  R_plane 3 x 3 column-major; RR row-major.  One function for the host (pre3_heading_update)
+// and the device (the plane fit's launch, pre3_plane.hip).
+__host__ __device__ inline void heading_RR(const double *Rp, double RR[9])
+{
+    auto Rm = [&](int i, int j) { return Rp[(j - 1) * 3 + (i - 1)]; };       // R(i, j), MATLAB indices
+    // slamToolbox_11_02_18/FrameTransforms/Rotations/R2q.m:11-55
+    double a, b, cc, d;
+    const double T = Rm(1, 1) + Rm(2, 2) + Rm(3, 3) + 1.0;
+    if (T > 0.00000001) {
+        const double S = 2.0 * sqrt(T);
+        a = 0.25 * S; b = (Rm(2, 3) - Rm(3, 2)) / S; cc = (Rm(3, 1) - Rm(1, 3)) / S; d = (Rm(1, 2) - Rm(2, 1)) / S;
+    } else if (Rm(1, 1) > Rm(2, 2) && Rm(1, 1) > Rm(3, 3)) {
+        const double S = 2.0 * sqrt(1.0 + Rm(1, 1) - Rm(2, 2) - Rm(3, 3));
+        a = (Rm(2, 3) - Rm(3, 2)) / S; b = 0.25 * S; cc = (Rm(1, 2) + Rm(2, 1)) / S; d = (Rm(3, 1) + Rm(1, 3)) / S;
+    } else if (Rm(2, 2) > Rm(3, 3)) {
+        const double S = 2.0 * sqrt(1.0 + Rm(2, 2) - Rm(1, 1) - Rm(3, 3));
+        a = (Rm(3, 1) - Rm(1, 3)) / S; b = (Rm(1, 2) + Rm(2, 1)) / S; cc = 0.25 * S; d = (Rm(2, 3) + Rm(3, 2)) / S;
+    } else {
+        const double S = 2.0 * sqrt(1.0 + Rm(3, 3) - Rm(1, 1) - Rm(2, 2));
+        a = (Rm(1, 2) - Rm(2, 1)) / S; b = (Rm(3, 1) + Rm(1, 3)) / S; cc = (Rm(2, 3) + Rm(3, 2)) / S; d = 0.25 * S;
+    }
+    const double q[4] = { a, -b, -cc, -d };
+    // q2e.m:15-38
+    const double y1 = 2 * q[2] * q[3] + 2 * q[0] * q[1], x1 = q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3];
+    const double z2 = -2 * q[1] * q[3] + 2 * q[0] * q[2];
+    const double y3 = 2 * q[1] * q[2] + 2 * q[0] * q[3], x3 = q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3];
+    const double e[3] = { atan2(y1, x1), asin(z2), atan2(y3, x3) };
+    // e2q.m:22-35
+    const double sr = sin(e[0] / 2), sp = sin(e[1] / 2), sy = sin(e[2] / 2), cr = cos(e[0] / 2), cp = cos(e[1] / 2), cy = cos(e[2] / 2);
+    const double Qe[4][3] = {
+        { 0.5 * (-cy * cp * sr + sy * sp * cr), 0.5 * (-cy * sp * cr + sy * cp * sr), 0.5 * (-sy * cp * cr + cy * sp * sr) },
+        { 0.5 * (cy * cp * cr + sy * sp * sr), 0.5 * (-cy * sp * sr - sy * cp * cr), 0.5 * (-sy * cp * sr - cy * sp * cr) },
+        { 0.5 * (-cy * sp * sr + sy * cp * cr), 0.5 * (cy * cp * cr - sy * sp * sr), 0.5 * (-sy * sp * cr + cy * cp * sr) },
+        { 0.5 * (-sy * cp * sr - cy * sp * cr), 0.5 * (-cy * cp * sr - sy * sp * cr), 0.5 * (cy * cp * cr + sy * sp * sr) } };
+    // aux_code/observe_heading_jac.m:31-38 at R2q(R_plane)
+    const double q1 = q[0], q2 = q[1], q3 = q[2], q4 = q[3];
+    const double Jz[3][4] = { { -2 * q4, 2 * q3, 2 * q2, -2 * q1 }, { 2 * q1, -2 * q2, 2 * q3, -2 * q4 }, { 2 * q2, 2 * q1, 2 * q4, 2 * q3 } };
+    const double var = (M_PI / 180.0) * (M_PI / 180.0);
+    double A[3][3];                                              // J_z J_e2q
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 4; ++k) s += Jz[i][k] * Qe[k][j]; A[i][j] = s; }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 3; ++k) s += A[i][k] * var * A[j][k]; RR[i * 3 + j] = s; }
+}
+
 }  // namespace pre3

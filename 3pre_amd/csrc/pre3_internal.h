@@ -67,7 +67,9 @@ struct RowsBlock {
     double R[RMAX * RMAX];          // r x r, leading dimension r
     double q[4];                    // x_k_k(4:7) before the update (the sweep writes x)
 };
-struct RowsHeading { int on, strict; double z[3]; double RR[9]; };    // ekf_heading_update.m:29, :37-40 (RR row-major)
+// what the plane fit's launch leaves for the heading update queued behind it (pre3_heading_from_scan, pre3_plane.hip): sta != 1 -> the gate word is cleared
+struct HeadingSrc { double z[3]; double RR[9]; int32_t sta, pad_; };
+struct RowsHeading { int on, strict; double z[3]; double RR[9]; const HeadingSrc *src; };    // ekf_heading_update.m:29, :37-40 (RR row-major); src != null: z, RR from the device block
 
 struct KernelTiming {
     bool enabled = false;
@@ -242,6 +244,8 @@ struct pre3_ctx {
     // pre3_update_rows / pre3_heading_update (pre3_rows.hip), allocated on first use: the rows block and H*P (RMAX x ld, fp64)
     pre3::RowsBlock *rows_blk = nullptr; double *rows_hp = nullptr;
     int rows_form = 0;                            // PRE3_OPT_ROWS_FORM: 1 the single-sweep form, 0 run_update
+    // pre3_heading_from_scan (pre3_plane.hip), allocated on first use: [points | draws | scores | result] and the block the heading rows read
+    void *plane_buf = nullptr; size_t plane_bytes = 0; pre3::HeadingSrc *plane_src = nullptr;
     // features_info bookkeeping and the map policy (pre3_set_book / pre3_map_policy, pre3_map.hip).  A booked context carries
     // [capN][4] int32 (times_predicted, times_measured, init_frame, last_visible) through every map call; book_vis[i] = has_h || visible at x_k_k
     // after the LI update, recorded where the reference's rescue projects (pre3_step / pre3_step_predicted / pre3_rescue), cleared by every map call
@@ -363,6 +367,11 @@ void free_readers(pre3_ctx *c);
 int launch_rows_update(pre3_ctx *c, const RowsBlock *rows, const RowsHeading *hd);
 int rows_applied(pre3_ctx *c, int32_t *applied_host);
 void free_rows(pre3_ctx *c);
+
+// ---- the floor-plane fit behind pre3_heading_from_scan (pre3_plane.hip)
+void free_plane(pre3_ctx *c);
+int stage_acquire(pre3_ctx *c, size_t bytes, void **host, void **dev, int *slot);      /* pre3_api.hip: a pinned staging block of the context ... */
+int stage_release(pre3_ctx *c, int slot);                                              /* ... handed to the pull queued with launch_pull(.., slot) */
 
 // ---- map policy (pre3_map.hip): the rescue-visibility rider of a booked context (one small launch at the post-LI x_k_k), buffers
 int launch_book_vis(pre3_ctx *c);

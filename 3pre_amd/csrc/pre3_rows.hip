@@ -58,14 +58,21 @@ __global__ __launch_bounds__(RB) void k_rows_hp(const T *__restrict__ P, int ld,
     if (hd.on) {
         double q[4] = { x[3], x[4], x[5], x[6] }, h[3], H[12];
         heading_rows(q, h, H);
-        const bool skip = heading_gate_skips(hd.z, h, hd.strict);
+        // the by-value z / RR (pre3_heading_update), or what the plane fit queued ahead of this launch left on the device (pre3_heading_from_scan):
+        // a fit that is not sta == 1 skips like the gate
+        double z[3] = { hd.z[0], hd.z[1], hd.z[2] };
+        bool skip;
+        if (hd.src != nullptr) {
+            for (int k = 0; k < 3; ++k) z[k] = hd.src->z[k];
+            skip = hd.src->sta != 1 || heading_gate_skips(z, h, hd.strict);
+        } else skip = heading_gate_skips(z, h, hd.strict);
         if (blockIdx.x == 0 && a == 0 && tid == 0) {
             blk->r = 3; blk->applied = skip ? 0 : 1;
             for (int k = 0; k < 4; ++k) blk->q[k] = q[k];
             for (int i = 0; i < 3; ++i) {
                 for (int t = 0; t < RMAX; ++t) { blk->col[i * RMAX + t] = t < 4 ? 3 + t : 0; blk->val[i * RMAX + t] = t < 4 ? H[i * 4 + t] : 0.0; }
-                blk->nu[i] = hd.z[i] - h[i];
-                for (int j = 0; j < 3; ++j) blk->R[i * 3 + j] = hd.RR[i * 3 + j];
+                blk->nu[i] = z[i] - h[i];
+                for (int j = 0; j < 3; ++j) blk->R[i * 3 + j] = hd.src != nullptr ? hd.src->RR[i * 3 + j] : hd.RR[i * 3 + j];
             }
         }
         if (skip) return;                                   // (the same decision in every workgroup)

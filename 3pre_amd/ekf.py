@@ -154,6 +154,23 @@ class EkfFilter:
         check(lib.pre3_heading_update(self._ctx, dptr(Rc), int(bool(strict_reference)), C.byref(applied)))
         return bool(applied.value)
 
+    def heading_from_scan(self, x_sr, y_sr, z_sr, draws, box=None, t=0.02, transpose=True, strict_reference=True, wait=True):
+        """mono_slam.m:189-193 in one call: R_plane = plane_fit_to_data(step) on the range image (SR4000 coordinates, draws as for plane.plane_fit),
+        then ekf_heading_update(filter, R_plane') (transpose=False: R_plane itself) -- fit, gate and update queued on the filter's stream, nothing
+        read back in between.  A fit whose status is not 1 applies nothing.  wait=True synchronises and returns
+        (applied, fit dict as plane.plane_fit's without counts / inliers); wait=False returns None at once."""
+        from . import plane
+        imgs = plane._images(x_sr, y_sr, z_sr)
+        draws = i32(draws).reshape(-1, 3)
+        args = (self._ctx, imgs[0].shape[0], imgs[0].shape[1], dptr(imgs[0]), dptr(imgs[1]), dptr(imgs[2]), dptr(plane._box(box)), float(t),
+                draws.shape[0], dptr(draws), int(bool(transpose)), int(bool(strict_reference)))
+        if not wait:
+            check(lib.pre3_heading_from_scan(*args, None, None))
+            return None
+        applied, res = C.c_int32(0), plane.PlaneResult()
+        check(lib.pre3_heading_from_scan(*args, C.byref(applied), C.byref(res)))
+        return bool(applied.value), plane._result(res)
+
     def rows_form(self):
         """PRE3_OPT_ROWS_FORM: 1 if the last update() / ekf_heading_update() took the single-sweep form, 0 the general route"""
         v = C.c_int(0)

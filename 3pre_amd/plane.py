@@ -1,0 +1,98 @@
+"""Host-side mirror of the reference's floor-plane fit (plane_fit_to_data.m) over the C ABI; DESIGN.md section 17.
+
+    plane_fit_to_data.m:13-21,41        -> crop_points (camera coordinates, the box, the column-major point list)
+    plane_fitting/ransac.m:142-176      -> draw_plane_hypotheses (the reference's rejection rule, any numpy Generator)
+    plane_fit_to_data.m:7-149           -> plane_fit (RANSAC over the draws, refit, sign rule, R), EkfFilter.heading_from_scan in ekf.py
+
+All compute runs in libpre3.so on the GPU; this module marshals numpy arrays and draws random numbers.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import Pre3Error, check, dptr, f64, i32, lib
+
+DEFAULT_BOX = (80, 144, 50, 120)          # plane_fit_to_data.m:17-18: rows 80..144, columns 50..120, 1-based inclusive
+MAX_DRAWS = 1001                          # ransac.m:209: the loop breaks once trialcount exceeds maxTrials = 1000
+MAX_DATA_TRIALS = 100                     # ransac.m:122
+
+
+class PlaneResult(C.Structure):
+    _fields_ = [("B", C.c_double * 4), ("R", C.c_double * 9), ("p_orig", C.c_double * 3), ("p_ray", C.c_double * 3), ("N", C.c_double),
+                ("sta", C.c_int32), ("n_inliers", C.c_int32), ("n_trials", C.c_int32), ("best", C.c_int32)]
+
+
+def crop_points(x_sr, y_sr, z_sr, box=None):
+    """plane_fit_to_data.m:13, :19-21, :41: (x1, y1, z1, XYZ) -- the box of the range image in camera coordinates (x = -x_sr, y = -y_sr, z = z_sr)
+    and its points stacked column-major, XYZ (3, npts)."""
+    r0, r1, c0, c1 = DEFAULT_BOX if box is None else [int(v) for v in box]
+    x, y, z = -np.asarray(x_sr, dtype=np.float64), -np.asarray(y_sr, dtype=np.float64), np.asarray(z_sr, dtype=np.float64)
+    if not (1 <= r0 <= r1 <= x.shape[0] and 1 <= c0 <= c1 <= x.shape[1]):
+        raise Pre3Error(-1, "crop_points: box outside the image")
+    x1, y1, z1 = x[r0 - 1:r1, c0 - 1:c1], y[r0 - 1:r1, c0 - 1:c1], z[r0 - 1:r1, c0 - 1:c1]
+    return x1, y1, z1, np.stack([x1.ravel(order="F"), y1.ravel(order="F"), z1.ravel(order="F")])
+
+
+def draw_plane_hypotheses(XYZ, n_draw, rng):
+    """ransac.m:142-176, n_draw times: three distinct positions (randsample), redrawn while the points are collinear
+    (iscolinear.m:62: norm(cross(p2 - p1, p3 - p1)) < eps), at most 100 times -- the last sample is then kept, as the reference keeps it.
+    Returns 0-based positions (n_draw, 3), int32."""
+    X = np.asarray(XYZ, dtype=np.float64)
+    npts = X.shape[1]
+    eps = np.finfo(float).eps
+    out = np.zeros((int(n_draw), 3), np.int32)
+    for k in range(int(n_draw)):
+        for _ in range(MAX_DATA_TRIALS):
+            ind = rng.choice(npts, 3, replace=False)
+            p1, p2, p3 = X[:, ind[0]], X[:, ind[1]], X[:, ind[2]]
+            if not np.linalg.norm(np.cross(p2 - p1, p3 - p1)) < eps:
+                break
+        out[k] = ind
+    return out
+
+
+def _images(x_sr, y_sr, z_sr):
+    imgs = [np.asfortranarray(f64(a)) for a in (x_sr, y_sr, z_sr)]
+    if imgs[0].ndim != 2 or any(a.shape != imgs[0].shape for a in imgs):
+        raise Pre3Error(-1, "plane fit: x_sr, y_sr, z_sr must be equally sized 2-D range images")
+    return imgs
+
+
+def _box(box):
+    return None if box is None else i32(np.asarray(box).ravel())
+
+
+def _result(res):
+    return dict(B=np.array(res.B), R=np.array(res.R).reshape(3, 3, order="F"), p_orig=np.array(res.p_orig), p_ray=np.array(res.p_ray), N=res.N,
+                sta=int(res.sta), n_inliers=int(res.n_inliers), n_trials=int(res.n_trials), best=int(res.best))
+
+
+def plane_fit(x_sr, y_sr, z_sr, draws, box=None, t=0.02, device=0):
+    """[R, T] = plane_fit_to_data(idx) on the range image (rows, cols) in SR4000 coordinates; draws (n_draw, 3) 0-based positions in the cropped
+    point list (draw_plane_hypotheses).  Returns a dict: R (3, 3), B, p_orig, p_ray, N, sta (1 ok, 0 no inlier, 2 the stopping rule wanted more
+    draws, 3 axes undefined), n_inliers, n_trials, best, counts (the score of every draw), inliers (the winner's mask over the cropped points)."""
+    imgs = _images(x_sr, y_sr, z_sr)
+    rows, cols = imgs[0].shape
+    draws = i32(draws).reshape(-1, 3)
+    bx = _box(box)
+    if bx is not None and bx.shape[0] != 4:
+        raise Pre3Error(-1, "plane_fit: box is (row0, row1, col0, col1)")
+    r0, r1, c0, c1 = DEFAULT_BOX if bx is None else bx
+    npts = max(0, int(r1) - int(r0) + 1) * max(0, int(c1) - int(c0) + 1)
+    counts, inl = np.zeros(max(draws.shape[0], 1), np.int32), np.zeros(max(npts, 1), np.int32)
+    res = PlaneResult()
+    check(lib.pre3_plane_fit(int(device), rows, cols, dptr(imgs[0]), dptr(imgs[1]), dptr(imgs[2]), dptr(bx), float(t), draws.shape[0], dptr(draws),
+                             dptr(counts), dptr(inl), C.byref(res)))
+    out = _result(res)
+    out["counts"], out["inliers"] = counts[:draws.shape[0]], inl[:npts].astype(bool)
+    return out
+
+
+def plane_bench(x_sr, y_sr, z_sr, draws, box=None, t=0.02, reps=50, device=0):
+    """measurement only: average device time (ms) of one fit -- upload of the box from pinned memory and both launches"""
+    imgs = _images(x_sr, y_sr, z_sr)
+    draws = i32(draws).reshape(-1, 3)
+    ms = C.c_double(0)
+    check(lib.pre3_plane_bench(int(device), imgs[0].shape[0], imgs[0].shape[1], dptr(imgs[0]), dptr(imgs[1]), dptr(imgs[2]), dptr(_box(box)), float(t),
+                               draws.shape[0], dptr(draws), int(reps), C.byref(ms)))
+    return ms.value

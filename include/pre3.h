@@ -232,6 +232,42 @@ PRE3_API int pre3_update_rows(pre3_ctx *ctx, int r, int width, const int32_t *nn
  * *applied_out = 0) -- once: the words are cleared with the report, as the step's HI collection clears them. */
 PRE3_API int pre3_heading_update(pre3_ctx *ctx, const double R_plane[9], int strict_reference, int32_t *applied_out);
 
+/* ---- the floor-plane fit that produces R_plane (plane_fit_to_data.m) --------------------------------------------------------
+ * plane_fit_to_data.m:13-149 over ransacfitplane.m:51-116, ransac.m:113-225, fitplane.m:31-54, plane_imp_line_par_int_3d.m:56-100: the SR4000 range
+ * image in camera coordinates (x = -x_sr, y = -y_sr, z = z_sr), cropped to a box and stacked column-major; a 3-point RANSAC with inlier distance t,
+ * p = 0.99 and at most 1001 trials; a least-squares plane on the winner's inliers; the sign rule; R from the plane's normal and the intersections of
+ * the plane with the rays through the box's centre point and the point 20 rows above it.  MATLAB's random stream cannot be reproduced: the draws are an
+ * input (the caller applies ransac.m:142-176's rejection rule, 3pre_amd/plane.py: draw_plane_hypotheses).  A collinear or repeated draw is not an
+ * error: it scores 0 and counts as a trial (ransac.m:170-184 once the redraws are used up). */
+#define PRE3_PLANE_MAX_DRAWS 1001
+typedef struct pre3_plane_result {
+    double B[4];            /* the plane B(1) x + B(2) y + B(3) z + B(4) = 0, unit 4-vector, after the sign rule of plane_fit_to_data.m:56-58 */
+    double R[9];            /* column-major, as plane_fit_to_data returns it: columns x_axis, z_axis (the normal), y_axis; zeros unless sta is 1 or 2 */
+    double p_orig[3], p_ray[3];
+    double N;               /* ransac.m's N when the loop ended */
+    int32_t sta;            /* 1 ok; 0 no trial had an inlier (ransac.m:224; B = 0); 2 the rule wanted more trials than n_draw (the result is that of
+                               the n_draw trials); 3 the axes are undefined (a ray parallel to the plane, or a zero y_axis; B is valid) */
+    int32_t n_inliers, n_trials, best;   /* best 0-based: the first trial with the largest score; -1 when sta == 0 */
+} pre3_plane_result;
+/* x_sr, y_sr, z_sr: rows x cols column-major, SR4000 coordinates.  box = {row0, row1, col0, col1}, 1-based inclusive (NULL: {80, 144, 50, 120},
+ * plane_fit_to_data.m:17-18).  draws[n_draw][3]: 0-based positions in the cropped, column-major point list.  count_out[n_draw] (the scores of ALL
+ * draws, also those behind the stopping rule), inlier_out[npts] (the winner's mask): optional.  Only the box crosses PCIe.
+ * PRE3_E_ARG before anything is launched: a null pointer, a box outside the image or with fewer than 3 points, a box of fewer than 40 rows (p_ray's row
+ * lies outside it), a draw outside [0, npts), n_draw outside [1, PRE3_PLANE_MAX_DRAWS], t <= 0, a non-finite coordinate inside the box. */
+PRE3_API int pre3_plane_fit(int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr,
+                            const int32_t *box, double t, int n_draw, const int32_t *draws,
+                            int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res);
+/* The same fit on the context's stream, then ekf_heading_update.m:27-52 with R_plane = R' (transpose = 1, what mono_slam.m:192 passes) or R (0), in
+ * stream order: z, RR and the fit's status stay on the device and the heading rows read them there, nothing is read back in between.  sta != 1: no
+ * update (applied = 0), x and P untouched.  State, gate (strict_reference) and error words as pre3_heading_update.  applied_out / res_out may be
+ * NULL; with both NULL the call does not synchronise. */
+PRE3_API int pre3_heading_from_scan(pre3_ctx *ctx, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr,
+                                    const int32_t *box, double t, int n_draw, const int32_t *draws, int transpose,
+                                    int strict_reference, int32_t *applied_out, pre3_plane_result *res_out);
+/* measurement only: average device time of one fit (upload of the box from pinned memory + both launches) over reps calls */
+PRE3_API int pre3_plane_bench(int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr,
+                              const int32_t *box, double t, int n_draw, const int32_t *draws, int reps, double *ms_per_call);
+
 /* Stateless drop-in for `[x,P,K] = update(x,P,H,R,z,h)` (update.m:27): host in, host out.
  * H is r x n given by rows in ELL form: row a has nnz[a] <= width entries (col[a*width+t], val[...]);
  * R is r x r dense or NULL for eye(r) (every caller in the reference passes eye).  K_out (n x r,

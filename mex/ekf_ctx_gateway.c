@@ -14,6 +14,7 @@
  *   plots_complete.m:161-237        [xv, Pv] = pre3_mex('marginal', 0:6); s = pre3_mex('landmarks')     % without fetching P
  *   update(x_k_k, p_k_k, H, R, z, h) pre3_mex('update', H, R, z, h)             % in place on the resident estimate; R = [] for eye
  *   ekf_heading_update.m:27-52      applied = pre3_mex('heading', R_plane, 1)
+ *   mono_slam.m:189-193             applied = pre3_mex('plane_heading', x_sr, y_sr, z_sr, draws, 1)   % plane_fit_to_data + ekf_heading_update on the device
  *   map_management.m:27-79          [del, acc] = pre3_mex('map_policy', step, UV, XYZ, DESC, 50, 0.1, std_z, 1)   % policy on the device; pre3_mex('set_book', B) first
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
@@ -197,6 +198,24 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         int32_t applied = 0;
         if (mxGetNumberOfElements(in[1]) != 9) mexErrMsgTxt("pre3_mex('heading'): R_plane must be 3 x 3");
         check(pre3_heading_update(g_ctx, mxGetPr(in[1]), nin > 2 ? (int)mxGetScalar(in[2]) : 1, &applied));
+        out[0] = mxCreateDoubleScalar((double)applied);
+    }
+    else if (!strcmp(cmd, "plane_heading")) {     /* applied = pre3_mex('plane_heading', x_sr, y_sr, z_sr, draws (n_draw x 3, 0-based positions in the cropped
+                                                     point list), strict): mono_slam.m:189-193 -- plane_fit_to_data.m on the range image, then
+                                                     ekf_heading_update(filter, R_plane') -- fit, gate and update on the device (pre3_heading_from_scan) */
+        int32_t applied = 0;
+        int rows = (int)mxGetM(in[1]), cols = (int)mxGetN(in[1]), nd = (int)mxGetM(in[4]), i, j, rc;
+        int32_t *d;
+        if (nin < 5) mexErrMsgTxt("pre3_mex('plane_heading', x_sr, y_sr, z_sr, draws [, strict])");
+        if ((int)mxGetM(in[2]) != rows || (int)mxGetN(in[2]) != cols || (int)mxGetM(in[3]) != rows || (int)mxGetN(in[3]) != cols)
+            mexErrMsgTxt("pre3_mex('plane_heading'): x_sr, y_sr, z_sr must have the same size");
+        if (mxGetN(in[4]) != 3) mexErrMsgTxt("pre3_mex('plane_heading'): draws must be n_draw x 3");
+        d = (int32_t *)mxMalloc(sizeof(int32_t) * 3 * (nd ? nd : 1));
+        for (i = 0; i < nd; ++i) for (j = 0; j < 3; ++j) d[3 * i + j] = (int32_t)mxGetPr(in[4])[(size_t)j * nd + i];
+        rc = pre3_heading_from_scan(g_ctx, rows, cols, mxGetPr(in[1]), mxGetPr(in[2]), mxGetPr(in[3]), NULL, 0.02, nd, d, 1,
+                                    nin > 5 ? (int)mxGetScalar(in[5]) : 1, &applied, NULL);
+        mxFree(d);
+        check(rc);
         out[0] = mxCreateDoubleScalar((double)applied);
     }
     else if (!strcmp(cmd, "map_delete")) {        /* pre3_mex('map_delete', idx (0-based, ascending))   delete_features.m:54-74 */
