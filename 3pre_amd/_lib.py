@@ -32,6 +32,14 @@ lib.pre3_plane_fit.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p
 lib.pre3_plane_bench.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
 lib.pre3_heading_from_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
 lib.pre3_step_predicted.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_void_p]
+_P, _I, _D, _U = C.c_void_p, C.c_int, C.c_double, C.c_uint64
+lib.pre3_ransac_seeded.argtypes = [_P, _U, _U, _I, _D, _I, _P, _P, _P, _P, _P]
+lib.pre3_step_seeded.argtypes = [_P, _P, _I, _P, _P, _U, _U, _I, _D, _I, _D, _P, _P, _P]
+lib.pre3_step_predicted_seeded.argtypes = [_P, _U, _U, _I, _D, _I, _D, _P, _P, _P]
+lib.pre3_vo_ransac_seeded.argtypes = [_I, _I, _P, _P, _P, _I, _U, _U, _P, _P, _P, _P, _P, _P]
+lib.pre3_vo_ransac_frames_seeded.argtypes = [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _I, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P]
+lib.pre3_plane_fit_seeded.argtypes = [_I, _I, _I, _P, _P, _P, _P, _D, _I, _U, _U, _P, _P, _P, _P]
+lib.pre3_heading_from_scan_seeded.argtypes = [_P, _I, _I, _P, _P, _P, _P, _D, _I, _U, _U, _I, _I, _P, _P, _P]
 
 F64, F32 = 0, 1
 INVDEPTH, CARTESIAN = 0, 1
@@ -91,4 +99,6 @@ EXPORTS = [
     "pre3_match_bench_create", "pre3_match_bench_create_cls", "pre3_match_bench_info", "pre3_match_bench_run", "pre3_match_bench_fetch", "pre3_match_bench_destroy",
     "pre3_comm_unique_id", "pre3_comm_create", "pre3_comm_destroy", "pre3_comm_info", "pre3_comm_set_timeout", "pre3_set_comm", "pre3_comm_init", "pre3_match_shard_set_comm",
     "pre3_ransac_sharded", "pre3_match_shard_match",
+    "pre3_ransac_seeded", "pre3_step_seeded", "pre3_step_predicted_seeded", "pre3_vo_ransac_seeded", "pre3_vo_ransac_frames_seeded",
+    "pre3_plane_fit_seeded", "pre3_heading_from_scan_seeded",
 ]

@@ -373,6 +373,12 @@ void free_plane(pre3_ctx *c);
 int stage_acquire(pre3_ctx *c, size_t bytes, void **host, void **dev, int *slot);      /* pre3_api.hip: a pinned staging block of the context ... */
 int stage_release(pre3_ctx *c, int slot);                                              /* ... handed to the pull queued with launch_pull(.., slot) */
 
+// ---- seeded draw tables (pre3_draws.hip, pre3_philox.h): one lane per hypothesis, written where the scoring launch behind them reads
+int launch_draw_1p(unsigned long long seed, unsigned long long seq, int n_draw, int m, int k, int32_t *hyp_dev, hipStream_t st);
+int launch_draw_vo(unsigned long long seed, unsigned long long seq, int n_hyp, int pnum, const double *m1_dev, const double *m2_dev, int ms, int32_t *draws_dev,
+                   int32_t *capped_dev /* zero at launch */, hipStream_t st);
+int launch_draw_plane(unsigned long long seed, unsigned long long seq, int n_draw, int npts, const double *pts_dev, int32_t *draws_dev, hipStream_t st);
+
 // ---- map policy (pre3_map.hip): the rescue-visibility rider of a booked context (one small launch at the post-LI x_k_k), buffers
 int launch_book_vis(pre3_ctx *c);
 void free_policy(pre3_ctx *c);

@@ -299,15 +299,17 @@ __global__ __launch_bounds__(PB) void k_plane_fit(int npts, const double *__rest
 struct PlaneJob {
     int r0, c0, nr, nc, npts, po, pr, n_draw;
     size_t off_draws, bytes_in, off_counts, off_out, off_inl, bytes_total;
+    size_t bytes_up;            // what crosses PCIe: bytes_in, or the points alone when the draws are made on the device (the seeded forms)
 };
+struct PlaneSeed { unsigned long long seed, seq; };      // k_draw_plane writes the draws region behind the upload
 
 static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // every host check of both entry points, before anything is launched
 static int plane_check(const char *who, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
-                       int n_draw, const int32_t *draws, PlaneJob *job)
+                       int n_draw, const int32_t *draws, PlaneJob *job, bool seeded = false)
 {
-    PRE3_CHECK(x_sr && y_sr && z_sr && draws, PRE3_E_ARG, "%s: null argument", who);
+    PRE3_CHECK(x_sr && y_sr && z_sr && (draws || seeded), PRE3_E_ARG, "%s: null argument", who);
     PRE3_CHECK(rows >= 1 && cols >= 1, PRE3_E_ARG, "%s: a %d x %d image", who, rows, cols);
     const int32_t dflt[4] = { 80, 144, 50, 120 };           // plane_fit_to_data.m:17-18
     const int32_t *b = box ? box : dflt;
@@ -322,7 +324,7 @@ static int plane_check(const char *who, int rows, int cols, const double *x_sr, 
     j.po = jo * j.nr + io; j.pr = j.po - 20;
     PRE3_CHECK(n_draw >= 1 && n_draw <= PRE3_PLANE_MAX_DRAWS, PRE3_E_ARG, "%s: n_draw=%d outside [1, %d]", who, n_draw, PRE3_PLANE_MAX_DRAWS);
     PRE3_CHECK(t > 0.0 && std::isfinite(t), PRE3_E_ARG, "%s: t must be positive", who);
-    for (int i = 0; i < 3 * n_draw; ++i)
+    for (int i = 0; !seeded && i < 3 * n_draw; ++i)
         PRE3_CHECK(draws[i] >= 0 && draws[i] < j.npts, PRE3_E_ARG, "%s: draws[%d]=%d is not a point of the box (npts=%d)", who, i, draws[i], j.npts);
     for (int c = 0; c < j.nc; ++c) {
         const size_t o = (size_t)(j.c0 + c) * rows + j.r0;
@@ -337,6 +339,7 @@ static int plane_check(const char *who, int rows, int cols, const double *x_sr, 
     j.off_out = up16(j.off_counts + sizeof(int32_t) * (size_t)n_draw);
     j.off_inl = up16(j.off_out + sizeof(PlaneOut));
     j.bytes_total = up16(j.off_inl + sizeof(int32_t) * (size_t)j.npts);
+    j.bytes_up = seeded ? up16(j.off_draws) : j.bytes_in;
     *job = j;
     return PRE3_OK;
 }
@@ -349,13 +352,15 @@ static void plane_pack(const PlaneJob &j, int rows, const double *x_sr, const do
         const size_t o = (size_t)(j.c0 + c) * rows + j.r0, d = (size_t)c * j.nr;
         for (int r = 0; r < j.nr; ++r) { X[d + r] = -x_sr[o + r]; Y[d + r] = -y_sr[o + r]; Z[d + r] = z_sr[o + r]; }
     }
-    memcpy((char *)stage + j.off_draws, draws, sizeof(int32_t) * 3 * (size_t)j.n_draw);
+    if (draws) memcpy((char *)stage + j.off_draws, draws, sizeof(int32_t) * 3 * (size_t)j.n_draw);
+    else if (j.bytes_up > j.off_draws) memset((char *)stage + j.off_draws, 0, j.bytes_up - j.off_draws);
 }
 
-static int plane_launch(const PlaneJob &j, char *buf, double t, int transpose, bool want_inl, HeadingSrc *src, hipStream_t st)
+static int plane_launch(const PlaneJob &j, char *buf, double t, int transpose, bool want_inl, HeadingSrc *src, hipStream_t st, const PlaneSeed *sd = nullptr)
 {
     const double *pts = (const double *)buf;
     const int32_t *draws = (const int32_t *)(buf + j.off_draws);
+    if (sd) PRE3_TRY(launch_draw_plane(sd->seed, sd->seq, j.n_draw, j.npts, pts, (int32_t *)(buf + j.off_draws), st));
     int32_t *counts = (int32_t *)(buf + j.off_counts);
     hipLaunchKernelGGL(k_plane_score, dim3(ceil_div(j.n_draw, PG)), dim3(PB), 0, st, j.npts, pts, j.n_draw, draws, t, counts);
     PRE3_HIP(hipGetLastError());
@@ -399,12 +404,12 @@ using namespace pre3;
 
 extern "C" {
 
-int pre3_plane_fit(int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
-                   int n_draw, const int32_t *draws, int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res)
+static int plane_fit_impl(const char *who, int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
+                          int n_draw, const int32_t *draws, int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res, const PlaneSeed *sd, int32_t *draws_out)
 {
     PlaneJob j;
-    PRE3_CHECK(res != nullptr, PRE3_E_ARG, "pre3_plane_fit: null argument");
-    PRE3_TRY(plane_check("pre3_plane_fit", rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, draws, &j));
+    PRE3_CHECK(res != nullptr, PRE3_E_ARG, "%s: null argument", who);
+    PRE3_TRY(plane_check(who, rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, draws, &j, sd != nullptr));
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
     if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return PRE3_E_NODEVICE; }
@@ -421,14 +426,28 @@ int pre3_plane_fit(int device, int rows, int cols, const double *x_sr, const dou
             g_stage.cap = cap;
         }
         plane_pack(j, rows, x_sr, y_sr, z_sr, draws, g_stage.p);
-        PRE3_HIP(hipMemcpyAsync(d.p, g_stage.p, j.bytes_in, hipMemcpyHostToDevice, 0));
-        PRE3_TRY(plane_launch(j, (char *)d.p, t, 0, inlier_out != nullptr, nullptr, 0));
+        PRE3_HIP(hipMemcpyAsync(d.p, g_stage.p, j.bytes_up, hipMemcpyHostToDevice, 0));
+        PRE3_TRY(plane_launch(j, (char *)d.p, t, 0, inlier_out != nullptr, nullptr, 0, sd));
         PRE3_HIP(hipMemcpy(&o, (char *)d.p + j.off_out, sizeof o, hipMemcpyDeviceToHost));      // (synchronises: the block is free again)
     }
     if (count_out) PRE3_HIP(hipMemcpy(count_out, (char *)d.p + j.off_counts, sizeof(int32_t) * (size_t)n_draw, hipMemcpyDeviceToHost));
     if (inlier_out) PRE3_HIP(hipMemcpy(inlier_out, (char *)d.p + j.off_inl, sizeof(int32_t) * (size_t)j.npts, hipMemcpyDeviceToHost));
+    if (draws_out) PRE3_HIP(hipMemcpy(draws_out, (char *)d.p + j.off_draws, sizeof(int32_t) * 3 * (size_t)n_draw, hipMemcpyDeviceToHost));
     plane_result(o, res);
     return PRE3_OK;
+}
+
+int pre3_plane_fit(int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
+                   int n_draw, const int32_t *draws, int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res)
+{
+    return plane_fit_impl("pre3_plane_fit", device, rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, draws, count_out, inlier_out, res, nullptr, nullptr);
+}
+
+int pre3_plane_fit_seeded(int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
+                          int n_draw, uint64_t seed, uint64_t seq, int32_t *draws_out, int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res)
+{
+    const PlaneSeed sd{ seed, seq };
+    return plane_fit_impl("pre3_plane_fit_seeded", device, rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, nullptr, count_out, inlier_out, res, &sd, draws_out);
 }
 
 // measurement only: device time of one fit (upload + score + fit launches) between two events, averaged over reps warmed calls
@@ -467,12 +486,13 @@ int pre3_plane_bench(int device, int rows, int cols, const double *x_sr, const d
     return PRE3_OK;
 }
 
-int pre3_heading_from_scan(pre3_ctx *c, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
-                           int n_draw, const int32_t *draws, int transpose, int strict_reference, int32_t *applied_out, pre3_plane_result *res_out)
+static int heading_from_scan_impl(pre3_ctx *c, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
+                                  int n_draw, const int32_t *draws, int transpose, int strict_reference, int32_t *applied_out, pre3_plane_result *res_out,
+                                  const PlaneSeed *sd, int32_t *draws_out)
 {
     PlaneJob j;
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "pre3_heading_from_scan: null context");
-    PRE3_TRY(plane_check("pre3_heading_from_scan", rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, draws, &j));
+    PRE3_TRY(plane_check("pre3_heading_from_scan", rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, draws, &j, sd != nullptr));
     PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE,
                "pre3_heading_from_scan: acts on (x_k_k, p_k_k); the covariance buffer holds the prediction (update first)");
     EntryScope scope(c); PRE3_TRY(scope.rc);
@@ -487,21 +507,22 @@ int pre3_heading_from_scan(pre3_ctx *c, int rows, int cols, const double *x_sr, 
     void *st = nullptr, *st_dev = nullptr; int slot = 0;
     PRE3_TRY(stage_acquire(c, j.bytes_in, &st, &st_dev, &slot));
     plane_pack(j, rows, x_sr, y_sr, z_sr, draws, st);
-    PRE3_TRY(launch_pull(c, st, c->plane_buf, j.bytes_in, slot));
+    PRE3_TRY(launch_pull(c, st, c->plane_buf, j.bytes_up, slot));
     PRE3_TRY(stage_release(c, slot));
-    PRE3_TRY(plane_launch(j, (char *)c->plane_buf, t, transpose ? 1 : 0, false, c->plane_src, c->stream));
+    PRE3_TRY(plane_launch(j, (char *)c->plane_buf, t, transpose ? 1 : 0, false, c->plane_src, c->stream, sd));
     RowsHeading hd{};
     hd.on = 1; hd.strict = strict_reference ? 1 : 0; hd.src = c->plane_src;
     c->rows_form = 1;
     PRE3_TRY(launch_rows_update(c, nullptr, &hd));
     c->hp_all_valid = false;
-    if (applied_out == nullptr && res_out == nullptr) return PRE3_OK;
+    if (applied_out == nullptr && res_out == nullptr && draws_out == nullptr) return PRE3_OK;
     // as pre3_heading_update with applied_out: the gate word, the result block and the error words behind one wait
     int32_t applied = 0;
     PlaneOut o;
     PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
     PRE3_TRY(rows_applied(c, &applied));
     PRE3_HIP(hipMemcpyAsync(&o, (char *)c->plane_buf + j.off_out, sizeof o, hipMemcpyDeviceToHost, c->stream));
+    if (draws_out) PRE3_HIP(hipMemcpyAsync(draws_out, (char *)c->plane_buf + j.off_draws, sizeof(int32_t) * 3 * (size_t)n_draw, hipMemcpyDeviceToHost, c->stream));
     PRE3_TRY(stream_drain(c, __func__));
     if (res_out) plane_result(o, res_out);
     const int rc = stats_words(c);
@@ -512,6 +533,20 @@ int pre3_heading_from_scan(pre3_ctx *c, int rows, int cols, const double *x_sr, 
         PRE3_TRY(stream_drain(c, __func__));
     }
     return rc;
+}
+
+int pre3_heading_from_scan(pre3_ctx *c, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
+                           int n_draw, const int32_t *draws, int transpose, int strict_reference, int32_t *applied_out, pre3_plane_result *res_out)
+{
+    return heading_from_scan_impl(c, rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, draws, transpose, strict_reference, applied_out, res_out, nullptr, nullptr);
+}
+
+int pre3_heading_from_scan_seeded(pre3_ctx *c, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
+                                  int n_draw, uint64_t seed, uint64_t seq, int transpose, int strict_reference, int32_t *draws_out, int32_t *applied_out,
+                                  pre3_plane_result *res_out)
+{
+    const PlaneSeed sd{ seed, seq };
+    return heading_from_scan_impl(c, rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, nullptr, transpose, strict_reference, applied_out, res_out, &sd, draws_out);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include "pre3_internal.h"
 #include "pre3_geomdev.h"
 #include "pre3_cholp.h"
+#include "pre3_philox.h"
 
 using namespace pre3;
 
@@ -14,18 +15,20 @@ extern "C" {
 
 // ---- RANSAC ---------------------------------------------------------------------------------------
 // zero_words > 0 (the sliced forms): that many words of c->support (supports, masks [, the missing-slice word]) are cleared on the way
-static int ransac_prepare(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, int lo = 0, int hi = -1, bool slice_form = false, size_t zero_words = 0)
+// table_on_device (the seeded forms): c->hyp has been written by a draw kernel queued on the context's stream -- there is no host table to check or pull
+static int ransac_prepare(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, int lo = 0, int hi = -1, bool slice_form = false, size_t zero_words = 0,
+                          bool table_on_device = false)
 {
     PRE3_CHECK(c->measurements_set && c->projected, PRE3_E_STATE, "ransac: needs pre3_project and measurements");
     PRE3_CHECK(c->p_which == PRE3_X_K_KM1, PRE3_E_STATE, "ransac: needs the predicted estimate (call pre3_predict or set x_k_km1)");
     PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph, PRE3_E_ARG, "ransac: n_draw=%d exceeds capacity %d", n_draw, c->caph);
     PRE3_CHECK(k >= 1 && k <= MAXK, PRE3_E_ARG, "ransac: k=%d unsupported (1..%d)", k, MAXK);
-    PRE3_CHECK(hyp != nullptr, PRE3_E_ARG, "ransac: null hypothesis table");
+    PRE3_CHECK(hyp != nullptr || table_on_device, PRE3_E_ARG, "ransac: null hypothesis table");
     PRE3_CHECK(c->m >= k, PRE3_E_ARG, "ransac: %d measurements but k=%d", c->m, k);
-    for (int i = 0; i < n_draw * k; ++i) PRE3_CHECK(hyp[i] >= 0 && hyp[i] < c->m, PRE3_E_ARG, "ransac: hyp[%d]=%d not a position in the IC list (m=%d)", i, hyp[i], c->m);
+    for (int i = 0; !table_on_device && i < n_draw * k; ++i) PRE3_CHECK(hyp[i] >= 0 && hyp[i] < c->m, PRE3_E_ARG, "ransac: hyp[%d]=%d not a position in the IC list (m=%d)", i, hyp[i], c->m);
     if (hi < 0) hi = n_draw;
     const bool sliced = lo > 0 || hi < n_draw || slice_form;
-    const bool need_pull = hyp != (const int32_t *)(c->inbox_host + c->off_hyp);       // not already shipped with the measurements
+    const bool need_pull = !table_on_device && hyp != (const int32_t *)(c->inbox_host + c->off_hyp);       // not already shipped with the measurements
     if (need_pull) {
         if (c->inbox_pending) { PRE3_TRY(wait_mail(c, 10, c->seq_inbox)); c->inbox_pending = false; }
         memcpy(c->inbox_host + c->off_hyp, hyp, sizeof(int32_t) * n_draw * k);
@@ -184,10 +187,11 @@ int pre3_ransac_sharded(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, doub
     return ransac_results(c, n_draw, support, li_mask, stats);
 }
 
-static int ransac_impl(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, double threshold, int early_exit, int32_t *support, int32_t *li_mask, int32_t stats[4])
+static int ransac_impl(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, double threshold, int early_exit, int32_t *support, int32_t *li_mask, int32_t stats[4],
+                       bool table_on_device = false)
 {
     c->shard_round = false; c->carry.select_pending = false;
-    PRE3_TRY(ransac_prepare(c, n_draw, k, hyp));
+    PRE3_TRY(ransac_prepare(c, n_draw, k, hyp, 0, -1, false, 0, table_on_device));
     int words = ceil_div(c->m, 32);
     // Scoring, then the selection stage (the reference's loop replayed on the supports) as a launch of its own.  The selection can also ride
     // in the scoring launch's last workgroup (PRE3_SELECT_FUSE=1, round 1's form), but measured at N=500 / 200 hypotheses that launch then
@@ -212,6 +216,38 @@ int pre3_ransac(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, double thres
 {
     EntryScope scope(c); PRE3_TRY(scope.rc);
     return ransac_impl(c, n_draw, k, hyp, threshold, early_exit, support, li_mask, stats);
+}
+
+// ---- the seeded forms: the table is drawn on the device, on the context's stream, in front of the launches that read it
+struct DrawSeed { unsigned long long seed, seq; };
+static inline int seeded_k(int m) { return m > 3 ? 3 : 1; }          // select_random_match.m:47-51
+// the table back to the caller, on request only (synchronises)
+static int seeded_table_out(pre3_ctx *c, int n_draw, int k, int32_t *hyp_out, int32_t *k_out)
+{
+    if (k_out) *k_out = k;
+    if (hyp_out == nullptr) return PRE3_OK;
+    PRE3_HIP(hipMemcpyAsync(hyp_out, c->hyp, sizeof(int32_t) * (size_t)n_draw * k, hipMemcpyDeviceToHost, c->stream));
+    return stream_drain(c, __func__);
+}
+
+int pre3_ransac_seeded(pre3_ctx *c, uint64_t seed, uint64_t seq, int n_draw, double threshold, int early_exit, int32_t *hyp_out, int32_t *k_out,
+                       int32_t *support, int32_t *li_mask, int32_t stats[4])
+{
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph, PRE3_E_ARG, "ransac: n_draw=%d outside [1, %d]", n_draw, c->caph);
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    PRE3_CHECK(c->measurements_set && c->projected, PRE3_E_STATE, "ransac: needs pre3_project and measurements");
+    PRE3_CHECK(c->p_which == PRE3_X_K_KM1, PRE3_E_STATE, "ransac: needs the predicted estimate (call pre3_predict or set x_k_km1)");
+    const int k = seeded_k(c->m);
+    PRE3_TRY(launch_draw_1p(seed, seq, n_draw, c->m, k, c->hyp, c->stream));
+    if (c->m == 0) {
+        // nothing to score (pre3_step skips the stage likewise): the one-column table of zeros is all there is
+        if (support) for (int i = 0; i < n_draw; ++i) support[i] = -1;
+        if (stats) { stats[0] = -1; stats[1] = stats[2] = stats[3] = 0; }
+        return seeded_table_out(c, n_draw, k, hyp_out, k_out);
+    }
+    PRE3_TRY(ransac_impl(c, n_draw, k, nullptr, threshold, early_exit, support, li_mask, stats, true));
+    return seeded_table_out(c, n_draw, k, hyp_out, k_out);
 }
 
 // ---- updates --------------------------------------------------------------------------------------
@@ -478,14 +514,15 @@ int pre3_heading_update(pre3_ctx *c, const double R_plane[9], int strict_referen
 
 // mono_slam.m:178-187 behind the prediction and the IC search: RANSAC, LI update, rescue, HI update, every launch sized on the device.
 // hyp: the draw table -- the inbox's own copy when it was shipped with the measurements (pre3_step), the caller's otherwise.
-static int step_back(pre3_ctx *c, int m, int n_draw, int k, const int32_t *hyp, double threshold, int early_exit, double chi2, int32_t stats[8])
+static int step_back(pre3_ctx *c, int m, int n_draw, int k, const int32_t *hyp, double threshold, int early_exit, double chi2, int32_t stats[8],
+                     bool table_on_device = false)
 {
     int32_t st[8] = { -1, 0, 0, 0, 0, 0, 0, 0 };
     bool ran = false;
     if (m >= k && m > 0) {
         // mono_slam.m:178; the statistics are read after pre3_update_li's poll of the same mailbox
         c->req.defer_select = true;                                 // the selection stage rides in the LI gather's launch (update_li_impl below)
-        const int rc_r = ransac_impl(c, n_draw, k, hyp, threshold, early_exit, nullptr, nullptr, nullptr);
+        const int rc_r = ransac_impl(c, n_draw, k, hyp, threshold, early_exit, nullptr, nullptr, nullptr, table_on_device);
         if (c->req.ride_innovation && !c->out.innovation_rode) {    // the H*P launch did not go out (error before it): S_i on its own, flags cleared
             c->req.ride_innovation = false;
             PRE3_TRY(launch_innovation(c, 0, 0.0, true));
@@ -534,8 +571,9 @@ static int step_back(pre3_ctx *c, int m, int n_draw, int k, const int32_t *hyp, 
     return PRE3_OK;
 }
 
-int pre3_step(pre3_ctx *c, const double u[7], int m, const int32_t *meas_idx, const double *z, int n_draw, int k, const int32_t *hyp,
-              double threshold, int early_exit, double chi2, int32_t stats[8])
+// ds != null: the seeded form -- no table in the inbox; k_draw_1p writes c->hyp behind the prediction's launch (whose inbox pull covers that region)
+static int step_front(pre3_ctx *c, const double u[7], int m, const int32_t *meas_idx, const double *z, int n_draw, int k, const int32_t *hyp,
+                      double threshold, int early_exit, double chi2, int32_t stats[8], const DrawSeed *ds)
 {
     // Entry::step: the previous step's deferred HI update is completed here; its rows/cols 3..6 <- Jn pass (update.m:42-46) is left to the prediction's
     // launch below (one launch less per step; PRE3_FUSE_JN=0: as its own launch).  Any return before that launch flushes it.
@@ -551,11 +589,11 @@ int pre3_step(pre3_ctx *c, const double u[7], int m, const int32_t *meas_idx, co
     PRE3_CHECK(c->have_cam, PRE3_E_STATE, "pre3_step: camera not set");
     PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "pre3_step: needs (x_k_k, p_k_k) on the device");
     PRE3_CHECK(m == 0 || (meas_idx && z), PRE3_E_ARG, "pre3_step: null measurement pointers");
-    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph && k >= 1 && k <= MAXK && hyp, PRE3_E_ARG, "pre3_step: bad hypothesis table");
+    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph && k >= 1 && k <= MAXK && (hyp || ds), PRE3_E_ARG, "pre3_step: bad hypothesis table");
     // matching_sift_based.m:131-134 outcome (+ the draws) into the pinned inbox; it crosses PCIe in one extra block of the prediction's
     // launch (nothing in that launch reads it), so the copy costs neither a launch nor stream time.  Flags cleared by k_innovation.
     size_t inbox_bytes = 0;
-    PRE3_TRY(install_measurements(c, m, meas_idx, z, hyp, n_draw * k, c->N > 0, false, &inbox_bytes));
+    PRE3_TRY(install_measurements(c, m, meas_idx, z, ds ? nullptr : hyp, ds ? 0 : n_draw * k, c->N > 0, false, &inbox_bytes));
     // mono_slam.m:153 + search_IC_matches.m:31-32: prediction, with the projection of every landmark at x_k_km1 riding in the
     // same launch; then search_IC_matches.m:33-44 (S_i), which also clears the previous frame's inlier flags
     {
@@ -573,7 +611,8 @@ int pre3_step(pre3_ctx *c, const double u[7], int m, const int32_t *meas_idx, co
     if (c->N && !c->req.ride_innovation) PRE3_TRY(launch_innovation(c, 0, 0.0, true));
     c->innovated = true;
     if (trace) t1 = now();
-    const int rc_back = step_back(c, m, n_draw, k, (const int32_t *)(c->inbox_host + c->off_hyp), threshold, early_exit, chi2, stats);
+    if (ds) PRE3_TRY(launch_draw_1p(ds->seed, ds->seq, n_draw, m, k, c->hyp, c->stream));
+    const int rc_back = step_back(c, m, n_draw, k, ds ? nullptr : (const int32_t *)(c->inbox_host + c->off_hyp), threshold, early_exit, chi2, stats, ds != nullptr);
     if (trace) {
         t5 = now();
         acc[0] += t1 - t0; acc[1] += t5 - t1;
@@ -586,6 +625,24 @@ int pre3_step(pre3_ctx *c, const double u[7], int m, const int32_t *meas_idx, co
         }
     }
     return rc_back;
+}
+
+int pre3_step(pre3_ctx *c, const double u[7], int m, const int32_t *meas_idx, const double *z, int n_draw, int k, const int32_t *hyp,
+              double threshold, int early_exit, double chi2, int32_t stats[8])
+{
+    return step_front(c, u, m, meas_idx, z, n_draw, k, hyp, threshold, early_exit, chi2, stats, nullptr);
+}
+
+int pre3_step_seeded(pre3_ctx *c, const double u[7], int m, const int32_t *meas_idx, const double *z, uint64_t seed, uint64_t seq, int n_draw,
+                     double threshold, int early_exit, double chi2, int32_t *hyp_out, int32_t *k_out, int32_t stats[8])
+{
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph, PRE3_E_ARG, "pre3_step_seeded: n_draw=%d outside [1, %d]", n_draw, c->caph);
+    PRE3_CHECK(u != nullptr && m >= 0 && (m == 0 || (meas_idx && z)), PRE3_E_ARG, "pre3_step_seeded: null argument");
+    const DrawSeed ds{ seed, seq };
+    const int k = seeded_k(m);
+    PRE3_TRY(step_front(c, u, m, meas_idx, z, n_draw, k, nullptr, threshold, early_exit, chi2, stats, &ds));
+    return seeded_table_out(c, n_draw, k, hyp_out, k_out);
 }
 
 /* mono_slam.m:153-162 + :199 -- the 'PURE_EKF' branch (config_file.m:21): prediction, projection + Jacobians + S_i of every landmark, then ONE
@@ -625,6 +682,20 @@ int pre3_step_predicted(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, doub
     PRE3_CHECK(c->measurements_set && c->projected && c->innovated, PRE3_E_STATE, "pre3_step_predicted: needs projection, S_i and measurements (pre3_ic_search, or pre3_project + pre3_innovation + pre3_set_measurements)");
     PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph && k >= 1 && k <= MAXK && hyp, PRE3_E_ARG, "pre3_step_predicted: bad hypothesis table");
     return step_back(c, c->m, n_draw, k, hyp, threshold, early_exit, chi2, stats);
+}
+
+int pre3_step_predicted_seeded(pre3_ctx *c, uint64_t seed, uint64_t seq, int n_draw, double threshold, int early_exit, double chi2, int32_t *hyp_out,
+                               int32_t *k_out, int32_t stats[8])
+{
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_CHECK(n_draw >= 1 && n_draw <= c->caph, PRE3_E_ARG, "pre3_step_predicted_seeded: n_draw=%d outside [1, %d]", n_draw, c->caph);
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    PRE3_CHECK(c->x_valid[PRE3_X_K_KM1] && c->p_which == PRE3_X_K_KM1, PRE3_E_STATE, "pre3_step_predicted_seeded: needs the predicted estimate (pre3_predict)");
+    PRE3_CHECK(c->measurements_set && c->projected && c->innovated, PRE3_E_STATE, "pre3_step_predicted_seeded: needs projection, S_i and measurements (pre3_ic_search, or pre3_project + pre3_innovation + pre3_set_measurements)");
+    const int k = seeded_k(c->m);
+    PRE3_TRY(launch_draw_1p(seed, seq, n_draw, c->m, k, c->hyp, c->stream));
+    PRE3_TRY(step_back(c, c->m, n_draw, k, nullptr, threshold, early_exit, chi2, stats, true));
+    return seeded_table_out(c, n_draw, k, hyp_out, k_out);
 }
 
 }  // extern "C"

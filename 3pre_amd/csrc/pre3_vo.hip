@@ -282,14 +282,22 @@ struct DevMem {                    // pooled device scratch (pre3_match.hip): no
     template <typename T> T *as() { return (T *)p; }
 };
 
+// the seeded forms: the draws come from k_draw_vo, which reads the match list (2 x pnum doubles, column-major) on the device
+struct VoSeed { unsigned long long seed, seq; const double *match_dev; int32_t *draws_out, *capped_out; };
+
 static int vo_run(int pnum, const double *d_p1, const double *d_p2, int n_hyp, const int32_t *draws, int32_t *cnum_out, int32_t *state_out,
-                  int32_t *inlier_out, pre3_vo_result *res, int reps, double *ms_out)
+                  int32_t *inlier_out, pre3_vo_result *res, int reps, double *ms_out, const VoSeed *sd = nullptr)
 {
     const int words = ceil_div(pnum, 64);
-    DevMem dd, dm, dc, ds, dout, dinl;
+    DevMem dd, dm, dc, ds, dout, dinl, dcap;
     PRE3_TRY(dd.alloc(sizeof(int32_t) * 4 * (size_t)n_hyp)); PRE3_TRY(dm.alloc(sizeof(unsigned long long) * (size_t)n_hyp * words));
     PRE3_TRY(dc.alloc(sizeof(int32_t) * n_hyp)); PRE3_TRY(ds.alloc(sizeof(int32_t) * n_hyp)); PRE3_TRY(dout.alloc(sizeof(VoOut)));
     PRE3_TRY(dinl.alloc(sizeof(int32_t) * pnum));
+    if (sd) {
+        PRE3_TRY(dcap.alloc(sizeof(int32_t)));
+        PRE3_HIP(hipMemsetAsync(dcap.p, 0, sizeof(int32_t), 0));
+        PRE3_TRY(launch_draw_vo(sd->seed, sd->seq, n_hyp, pnum, sd->match_dev, sd->match_dev + 1, 2, dd.as<int32_t>(), dcap.as<int32_t>(), 0));
+    } else
     PRE3_HIP(hipMemcpy(dd.p, draws, sizeof(int32_t) * 4 * (size_t)n_hyp, hipMemcpyHostToDevice));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (ms_out) { PRE3_HIP(hipEventCreate(&e0)); PRE3_HIP(hipEventCreate(&e1)); PRE3_HIP(hipEventRecord(e0, 0)); }
@@ -313,6 +321,8 @@ static int vo_run(int pnum, const double *d_p1, const double *d_p2, int n_hyp, c
     PRE3_HIP(hipDeviceSynchronize());
     VoOut o;
     PRE3_HIP(hipMemcpy(&o, dout.p, sizeof o, hipMemcpyDeviceToHost));
+    if (sd && sd->draws_out) PRE3_HIP(hipMemcpy(sd->draws_out, dd.p, sizeof(int32_t) * 4 * (size_t)n_hyp, hipMemcpyDeviceToHost));
+    if (sd && sd->capped_out) PRE3_HIP(hipMemcpy(sd->capped_out, dcap.p, sizeof(int32_t), hipMemcpyDeviceToHost));
     PRE3_CHECK(o.dist_ok, PRE3_E_NUMERIC, "vo: no matched point is farther than 0.4 m from the camera (ransac_dr_ye.m:21 has no minimum there)");
     if (cnum_out) PRE3_HIP(hipMemcpy(cnum_out, dc.p, sizeof(int32_t) * n_hyp, hipMemcpyDeviceToHost));
     if (state_out) PRE3_HIP(hipMemcpy(state_out, ds.p, sizeof(int32_t) * n_hyp, hipMemcpyDeviceToHost));
@@ -326,13 +336,13 @@ static int vo_run(int pnum, const double *d_p1, const double *d_p2, int n_hyp, c
     return PRE3_OK;
 }
 
-static int vo_check(int device, int pnum, int n_hyp, const int32_t *draws)
+static int vo_check(int device, int pnum, int n_hyp, const int32_t *draws, bool seeded = false)
 {
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
     PRE3_CHECK(pnum >= 4, PRE3_E_ARG, "vo: number of points is smaller than 4: insufficient for ransac");      // ransac_dr_ye.m:5-11
-    PRE3_CHECK(n_hyp >= 1 && draws, PRE3_E_ARG, "vo: no hypotheses");
-    for (int i = 0; i < 4 * n_hyp; ++i) PRE3_CHECK(draws[i] >= 0 && draws[i] < pnum, PRE3_E_ARG, "vo: draws[%d]=%d is not a match position (pnum=%d)", i, draws[i], pnum);
+    PRE3_CHECK(n_hyp >= 1 && (draws || seeded), PRE3_E_ARG, "vo: no hypotheses");
+    for (int i = 0; !seeded && i < 4 * n_hyp; ++i) PRE3_CHECK(draws[i] >= 0 && draws[i] < pnum, PRE3_E_ARG, "vo: draws[%d]=%d is not a match position (pnum=%d)", i, draws[i], pnum);
     if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return PRE3_E_NODEVICE; }
     return PRE3_OK;
 }
@@ -355,12 +365,26 @@ int pre3_vo_ransac(int device, int pnum, const double *pset1, const double *pset
     return vo_run(pnum, p1.as<double>(), p2.as<double>(), n_hyp, draws, cnum_out, state_out, inlier_out, res, 1, nullptr);
 }
 
-int pre3_vo_ransac_frames(int device, int rows, int cols, const double *x1, const double *y1, const double *z1, const double *x2,
-                          const double *y2, const double *z2, int ldf, int K1, const double *frm1, int K2, const double *frm2, int pnum,
-                          const double *match, int n_hyp, const int32_t *draws, double *pset1_out, double *pset2_out, int32_t *cnum_out,
-                          int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res)
+int pre3_vo_ransac_seeded(int device, int pnum, const double *pset1, const double *pset2, const double *match, int n_hyp, uint64_t seed, uint64_t seq,
+                          int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out, int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res)
 {
-    PRE3_TRY(vo_check(device, pnum, n_hyp, draws));
+    PRE3_TRY(vo_check(device, pnum, n_hyp, nullptr, true));
+    PRE3_CHECK(pset1 && pset2 && match, PRE3_E_ARG, "pre3_vo_ransac_seeded: null point set or match list");
+    DevMem p1, p2, mt;
+    PRE3_TRY(p1.alloc(sizeof(double) * 3 * pnum)); PRE3_TRY(p2.alloc(sizeof(double) * 3 * pnum)); PRE3_TRY(mt.alloc(sizeof(double) * 2 * pnum));
+    PRE3_HIP(hipMemcpy(p1.p, pset1, sizeof(double) * 3 * pnum, hipMemcpyHostToDevice));
+    PRE3_HIP(hipMemcpy(p2.p, pset2, sizeof(double) * 3 * pnum, hipMemcpyHostToDevice));
+    PRE3_HIP(hipMemcpy(mt.p, match, sizeof(double) * 2 * pnum, hipMemcpyHostToDevice));
+    const VoSeed sd{ seed, seq, mt.as<double>(), draws_out, capped_out };
+    return vo_run(pnum, p1.as<double>(), p2.as<double>(), n_hyp, nullptr, cnum_out, state_out, inlier_out, res, 1, nullptr, &sd);
+}
+
+static int vo_frames(int device, int rows, int cols, const double *x1, const double *y1, const double *z1, const double *x2,
+                     const double *y2, const double *z2, int ldf, int K1, const double *frm1, int K2, const double *frm2, int pnum,
+                     const double *match, int n_hyp, const int32_t *draws, double *pset1_out, double *pset2_out, int32_t *cnum_out,
+                     int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res, VoSeed *sd)
+{
+    PRE3_TRY(vo_check(device, pnum, n_hyp, draws, sd != nullptr));
     PRE3_CHECK(rows > 0 && cols > 0 && x1 && y1 && z1 && x2 && y2 && z2 && frm1 && frm2 && match && ldf >= 2 && K1 > 0 && K2 > 0, PRE3_E_ARG,
                "pre3_vo_ransac_frames: bad arguments");
     const size_t img = sizeof(double) * (size_t)rows * cols;
@@ -386,7 +410,27 @@ int pre3_vo_ransac_frames(int device, int rows, int cols, const double *x1, cons
     PRE3_CHECK(b == 0, PRE3_E_ARG, "pre3_vo_ransac_frames: %s", (b & 1) ? "a match refers to a keypoint that does not exist" : "a keypoint rounds to a pixel outside the range image");
     if (pset1_out) PRE3_HIP(hipMemcpy(pset1_out, p1.p, sizeof(double) * 3 * pnum, hipMemcpyDeviceToHost));
     if (pset2_out) PRE3_HIP(hipMemcpy(pset2_out, p2.p, sizeof(double) * 3 * pnum, hipMemcpyDeviceToHost));
-    return vo_run(pnum, p1.as<double>(), p2.as<double>(), n_hyp, draws, cnum_out, state_out, inlier_out, res, 1, nullptr);
+    if (sd) sd->match_dev = mt.as<double>();
+    return vo_run(pnum, p1.as<double>(), p2.as<double>(), n_hyp, draws, cnum_out, state_out, inlier_out, res, 1, nullptr, sd);
+}
+
+int pre3_vo_ransac_frames(int device, int rows, int cols, const double *x1, const double *y1, const double *z1, const double *x2,
+                          const double *y2, const double *z2, int ldf, int K1, const double *frm1, int K2, const double *frm2, int pnum,
+                          const double *match, int n_hyp, const int32_t *draws, double *pset1_out, double *pset2_out, int32_t *cnum_out,
+                          int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res)
+{
+    return vo_frames(device, rows, cols, x1, y1, z1, x2, y2, z2, ldf, K1, frm1, K2, frm2, pnum, match, n_hyp, draws, pset1_out, pset2_out, cnum_out,
+                     state_out, inlier_out, res, nullptr);
+}
+
+int pre3_vo_ransac_frames_seeded(int device, int rows, int cols, const double *x1, const double *y1, const double *z1, const double *x2,
+                                 const double *y2, const double *z2, int ldf, int K1, const double *frm1, int K2, const double *frm2, int pnum,
+                                 const double *match, int n_hyp, uint64_t seed, uint64_t seq, int32_t *draws_out, int32_t *capped_out,
+                                 double *pset1_out, double *pset2_out, int32_t *cnum_out, int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res)
+{
+    VoSeed sd{ seed, seq, nullptr, draws_out, capped_out };
+    return vo_frames(device, rows, cols, x1, y1, z1, x2, y2, z2, ldf, K1, frm1, K2, frm2, pnum, match, n_hyp, nullptr, pset1_out, pset2_out, cnum_out,
+                     state_out, inlier_out, res, &sd);
 }
 
 // measurement only: kernels of one RANSAC (dist + score + final) on resident inputs, averaged over reps

@@ -8,6 +8,8 @@ matlab_code/ of the reference):
       .search_IC_matches()        <-> search_IC_matches.m:31-44 (projection, Jacobians, S_i)
       .matching(k1, zc)           <-> matching_sift_based.m:119-134 (window gate on siftmatch's output)
       .ransac_hypotheses(hyp)     <-> ransac_hypotheses.m:27-85 (draws are an input: MATLAB's RNG is not reproducible)
+      .ransac_hypotheses_seeded / .step_seeded / .step_predicted_seeded / .heading_from_scan_seeded
+                                  <-> the same with the draws made on the device from (seed, seq) (select_random_match.m:40-51, ransac.m:142-176)
       .ekf_update_li_inliers()    <-> @ekf_filter/ekf_update_li_inliers.m:45-58
       .rescue_hi_inliers()        <-> @ekf_filter/rescue_hi_inliers.m:29-47
       .ekf_update_hi_inliers()    <-> @ekf_filter/ekf_update_hi_inliers.m:45-58
@@ -170,6 +172,25 @@ class EkfFilter:
         applied, res = C.c_int32(0), plane.PlaneResult()
         check(lib.pre3_heading_from_scan(*args, C.byref(applied), C.byref(res)))
         return bool(applied.value), plane._result(res)
+
+    def heading_from_scan_seeded(self, x_sr, y_sr, z_sr, seed, seq=0, n_draw=1001, box=None, t=0.02, transpose=True, strict_reference=True, wait=True,
+                                 return_draws=False):
+        """heading_from_scan with the draws made on the device from (seed, seq) (plane.plane_fit_seeded's rule): only the box
+        crosses PCIe and nothing of the scan is needed on the host.  wait=False returns None at once, without any synchronisation."""
+        from . import plane
+        imgs = plane._images(x_sr, y_sr, z_sr)
+        args = (self._ctx, imgs[0].shape[0], imgs[0].shape[1], dptr(imgs[0]), dptr(imgs[1]), dptr(imgs[2]), dptr(plane._box(box)), float(t),
+                int(n_draw), int(seed), int(seq), int(bool(transpose)), int(bool(strict_reference)))
+        if not wait:
+            check(lib.pre3_heading_from_scan_seeded(*args, None, None, None))
+            return None
+        applied, res = C.c_int32(0), plane.PlaneResult()
+        draws = np.zeros((max(int(n_draw), 1), 3), np.int32) if return_draws else None
+        check(lib.pre3_heading_from_scan_seeded(*args, dptr(draws), C.byref(applied), C.byref(res)))
+        out = plane._result(res)
+        if return_draws:
+            out["draws"] = draws
+        return bool(applied.value), out
 
     def rows_form(self):
         """PRE3_OPT_ROWS_FORM: 1 if the last update() / ekf_heading_update() took the single-sweep form, 0 the general route"""
@@ -403,6 +424,19 @@ class EkfFilter:
         check(lib.pre3_ransac(self._ctx, n_draw, k, dptr(hyp), C.c_double(thr), int(bool(early_exit)), dptr(sup), dptr(li), dptr(st)))
         return dict(support=sup, li_mask=li[:self.m], best=int(st[0]), iters=int(st[1]), n_hyp=int(st[2]), max_support=int(st[3]))
 
+    def ransac_hypotheses_seeded(self, seed, seq, n_draw, threshold=None, early_exit=True, return_hyp=True):
+        """ransac_hypotheses with the table drawn on the device from (seed, seq) (select_random_match.m:40-51 on the library's counter-based
+        stream); the dict also carries the table, `hyp` (n_draw, k), unless return_hyp=False."""
+        n_draw = int(n_draw)
+        sup, li, st = np.zeros(max(n_draw, 1), np.int32), np.zeros(max(self.m, 1), np.int32), np.zeros(4, np.int32)
+        hyp, k = (np.zeros(max(n_draw, 1) * 3, np.int32) if return_hyp else None), C.c_int32(0)
+        thr = self.std_z if threshold is None else float(threshold)
+        check(lib.pre3_ransac_seeded(self._ctx, int(seed), int(seq), n_draw, thr, int(bool(early_exit)), dptr(hyp), C.byref(k), dptr(sup), dptr(li), dptr(st)))
+        out = dict(support=sup[:n_draw], li_mask=li[:self.m], best=int(st[0]), iters=int(st[1]), n_hyp=int(st[2]), max_support=int(st[3]), k=int(k.value))
+        if return_hyp:
+            out["hyp"] = hyp[:n_draw * k.value].reshape(n_draw, k.value).copy()
+        return out
+
     def ransac_score_shard(self, hyp, threshold, hyp_begin, hyp_end):
         """Score hypotheses [hyp_begin, hyp_end) only; returns (support_dev_ptr, mask_dev_ptr, mask_words)."""
         hyp = i32(hyp)
@@ -509,6 +543,40 @@ class EkfFilter:
             check(rc)
         s = self._st.tolist()
         return dict(best=s[0], iters=s[1], n_hyp=s[2], max_support=s[3], n_li=s[4], n_hi=s[5])
+
+    def _seeded_out(self, n_draw, return_hyp):
+        return (np.zeros(max(n_draw, 1) * 3, np.int32) if return_hyp else None), C.c_int32(0)
+
+    def _seeded_result(self, n_draw, hyp, k):
+        s = self._st.tolist()
+        out = dict(best=s[0], iters=s[1], n_hyp=s[2], max_support=s[3], n_li=s[4], n_hi=s[5])
+        if hyp is not None:
+            out["hyp"] = hyp[:n_draw * k.value].reshape(n_draw, k.value).copy()
+        return out
+
+    def step_seeded(self, u, meas_idx, z, seed, seq, n_draw, threshold=None, early_exit=True, chi2=CHI2INV_2_95, return_hyp=False):
+        """step() with the hypothesis table drawn on the device from (seed, seq): no table is built on the host or shipped.
+        return_hyp=True also fetches the table (synchronises)."""
+        u, meas_idx, z = f64(u), i32(meas_idx), f64(z)
+        self.m = int(meas_idx.shape[0])
+        self.meas_idx = meas_idx
+        n_draw = int(n_draw)
+        hyp, k = self._seeded_out(n_draw, return_hyp)
+        rc = lib.pre3_step_seeded(self._ctx, addr(u), self.m, addr(meas_idx), addr(z), int(seed), int(seq), n_draw,
+                                  self.std_z if threshold is None else threshold, 1 if early_exit else 0, chi2, dptr(hyp), C.byref(k), self._st_addr)
+        if rc:
+            check(rc)
+        return self._seeded_result(n_draw, hyp, k)
+
+    def step_predicted_seeded(self, seed, seq, n_draw, threshold=None, early_exit=True, chi2=CHI2INV_2_95, return_hyp=False):
+        """step_predicted() with the table drawn on the device from (seed, seq)."""
+        n_draw = int(n_draw)
+        hyp, k = self._seeded_out(n_draw, return_hyp)
+        rc = lib.pre3_step_predicted_seeded(self._ctx, int(seed), int(seq), n_draw, self.std_z if threshold is None else threshold,
+                                            1 if early_exit else 0, chi2, dptr(hyp), C.byref(k), self._st_addr)
+        if rc:
+            check(rc)
+        return self._seeded_result(n_draw, hyp, k)
 
     # ---- measurement hooks
     def timer_start(self):

@@ -2,6 +2,7 @@
 
     plane_fit_to_data.m:13-21,41        -> crop_points (camera coordinates, the box, the column-major point list)
     plane_fitting/ransac.m:142-176      -> draw_plane_hypotheses (the reference's rejection rule, any numpy Generator)
+    plane_fitting/ransac.m:142-176      -> plane_fit_seeded (the same rule on the device, from (seed, seq))
     plane_fit_to_data.m:7-149           -> plane_fit (RANSAC over the draws, refit, sign rule, R), EkfFilter.heading_from_scan in ekf.py
 
 All compute runs in libpre3.so on the GPU; this module marshals numpy arrays and draws random numbers.
@@ -85,6 +86,27 @@ def plane_fit(x_sr, y_sr, z_sr, draws, box=None, t=0.02, device=0):
                              dptr(counts), dptr(inl), C.byref(res)))
     out = _result(res)
     out["counts"], out["inliers"] = counts[:draws.shape[0]], inl[:npts].astype(bool)
+    return out
+
+
+def plane_fit_seeded(x_sr, y_sr, z_sr, seed, seq=0, n_draw=MAX_DRAWS, box=None, t=0.02, device=0):
+    """plane_fit with the draws made on the device from (seed, seq) by ransac.m:142-176's rule: only the box crosses PCIe.
+    The dict also carries draws (n_draw, 3)."""
+    imgs = _images(x_sr, y_sr, z_sr)
+    rows, cols = imgs[0].shape
+    bx = _box(box)
+    if bx is not None and bx.shape[0] != 4:
+        raise Pre3Error(-1, "plane_fit_seeded: box is (row0, row1, col0, col1)")
+    r0, r1, c0, c1 = DEFAULT_BOX if bx is None else bx
+    npts = max(0, int(r1) - int(r0) + 1) * max(0, int(c1) - int(c0) + 1)
+    n_draw = int(n_draw)
+    nd = min(max(n_draw, 1), MAX_DRAWS)
+    draws, counts, inl = np.zeros((nd, 3), np.int32), np.zeros(nd, np.int32), np.zeros(max(npts, 1), np.int32)
+    res = PlaneResult()
+    check(lib.pre3_plane_fit_seeded(int(device), rows, cols, dptr(imgs[0]), dptr(imgs[1]), dptr(imgs[2]), dptr(bx), float(t), n_draw, int(seed), int(seq),
+                                    dptr(draws), dptr(counts), dptr(inl), C.byref(res)))
+    out = _result(res)
+    out["counts"], out["inliers"], out["draws"] = counts[:n_draw], inl[:npts].astype(bool), draws[:n_draw]
     return out
 
 

@@ -2,6 +2,7 @@
 
     vodometry_dr_ye.m:162-236            -> vo_ransac / vo_ransac_frames (all hypotheses, winner, final fit, statistics)
     ransac_dr_ye.m:28-46                 -> draw_hypotheses (the reference's own rejection rule, any numpy Generator)
+    ransac_dr_ye.m:28-48                 -> vo_ransac_seeded / vo_ransac_frames_seeded (the same rule on the device, from (seed, seq))
     vodometry_dr_ye.m:171                -> vo_rst
     Calculate_V_Omega_RANSAC_dr_ye.m:40-50 -> result["u"] = [T; R2q(R)], the argument of EkfFilter.ekf_prediction
 
@@ -97,6 +98,52 @@ def vo_ransac_frames(frm1, frm2, match, x1, y1, z1, x2, y2, z2, draws, device=0)
                                     dptr(cnum), dptr(state), dptr(inl), C.byref(res)))
     out = _result(res, cnum, state, inl[:pnum])
     out["pset1"], out["pset2"] = p1[:pnum].T.copy(), p2[:pnum].T.copy()
+    return out
+
+
+def vo_ransac_seeded(pset1, pset2, match, seed, seq=0, n_hyp=None, device=0):
+    """vo_ransac with the draws made on the device from (seed, seq) by ransac_dr_ye.m:28-48's rule.  match: (2, pnum)
+    keypoint numbers; n_hyp None: vo_rst(pnum).  The dict also carries draws (n_hyp, 4) and capped (hypotheses a position of which hit the
+    64-redraw cap)."""
+    p1, p2 = np.ascontiguousarray(f64(pset1).T), np.ascontiguousarray(f64(pset2).T)
+    assert p1.shape == p2.shape and p1.shape[1] == 3
+    mt = np.asfortranarray(f64(match))
+    pnum = p1.shape[0]
+    assert mt.shape == (2, pnum)
+    n_hyp = vo_rst(pnum) if n_hyp is None else int(n_hyp)
+    nh = max(n_hyp, 1)
+    draws, capped = np.zeros((nh, 4), np.int32), C.c_int32(0)
+    cnum, state, inl = np.zeros(nh, np.int32), np.zeros(nh, np.int32), np.zeros(max(pnum, 1), np.int32)
+    res = VoResult()
+    check(lib.pre3_vo_ransac_seeded(int(device), pnum, dptr(p1), dptr(p2), mt.ctypes.data_as(C.c_void_p), n_hyp, int(seed), int(seq), dptr(draws),
+                                    C.byref(capped), dptr(cnum), dptr(state), dptr(inl), C.byref(res)))
+    out = _result(res, cnum[:n_hyp], state[:n_hyp], inl[:pnum])
+    out["draws"], out["capped"] = draws[:n_hyp], int(capped.value)
+    return out
+
+
+def vo_ransac_frames_seeded(frm1, frm2, match, x1, y1, z1, x2, y2, z2, seed, seq=0, n_hyp=None, device=0):
+    """vo_ransac_frames with the draws made on the device: the match list is read where the gather already has it."""
+    imgs = [np.asfortranarray(f64(a)) for a in (x1, y1, z1, x2, y2, z2)]
+    rows, cols = imgs[0].shape
+    assert all(a.shape == (rows, cols) for a in imgs)
+    f1, f2 = np.asfortranarray(f64(frm1)), np.asfortranarray(f64(frm2))
+    assert f1.shape[0] == f2.shape[0] >= 2
+    mt = np.asfortranarray(f64(match))
+    pnum = mt.shape[1]
+    n_hyp = vo_rst(pnum) if n_hyp is None else int(n_hyp)
+    nh = max(n_hyp, 1)
+    draws, capped = np.zeros((nh, 4), np.int32), C.c_int32(0)
+    p1, p2 = np.zeros((max(pnum, 1), 3)), np.zeros((max(pnum, 1), 3))
+    cnum, state, inl = np.zeros(nh, np.int32), np.zeros(nh, np.int32), np.zeros(max(pnum, 1), np.int32)
+    res = VoResult()
+    P = [a.ctypes.data_as(C.c_void_p) for a in imgs]
+    check(lib.pre3_vo_ransac_frames_seeded(int(device), rows, cols, *P, f1.shape[0], f1.shape[1], f1.ctypes.data_as(C.c_void_p), f2.shape[1],
+                                           f2.ctypes.data_as(C.c_void_p), pnum, mt.ctypes.data_as(C.c_void_p), n_hyp, int(seed), int(seq),
+                                           dptr(draws), C.byref(capped), dptr(p1), dptr(p2), dptr(cnum), dptr(state), dptr(inl), C.byref(res)))
+    out = _result(res, cnum[:n_hyp], state[:n_hyp], inl[:pnum])
+    out["pset1"], out["pset2"] = p1[:pnum].T.copy(), p2[:pnum].T.copy()
+    out["draws"], out["capped"] = draws[:n_hyp], int(capped.value)
     return out
 
 

@@ -439,6 +439,50 @@ PRE3_API int pre3_vo_ransac_frames(int device, int rows, int cols, const double 
 PRE3_API int pre3_vo_bench(int device, int pnum, const double *pset1, const double *pset2, int n_hyp, const int32_t *draws, int reps,
                            double *ms_per_call);
 
+/* ---- seeded RANSAC: the three hypothesis tables drawn on the device ----------------------------------------------------------
+ * Every RANSAC entry point above takes its random draws as an input.  The _seeded forms below take (seed, seq) instead and draw the table on the
+ * device, on the stream of the work it feeds, from a counter-based stream: Philox4x64-10 with key = [seed, stream] (stream 1: 1-point RANSAC, 2: VO,
+ * 3: floor plane) and counter = [hypothesis, attempt, seq, 0] -- a table is a pure function of (seed, seq) and the inputs its rejection rule reads,
+ * identical on every caller, rank and run; seq is the caller's frame or step number.  A bounded integer in [0, range) is the high 64 bits of
+ * word * range (no rejection; bias at most range / 2^64); a uniform double is (word >> 11) * 2^-53.  "Three distinct of m" are three ranks in
+ * [0,m), [0,m-1), [0,m-2), each later one shifted past the earlier picks: randperm(m)(1:3)'s distribution without redraws.
+ * Results are bit-identical to the unseeded entry point fed with the same table; the table comes back only on request (the *_out pointers, which
+ * synchronise).  Argument errors are PRE3_E_ARG before anything is launched, the context unchanged. */
+
+/* select_random_match.m:40-51: k = 3 positions per hypothesis when more than 3 measurements are individually compatible, else k = 1; no measurement:
+ * a one-column table of zeros.  n_draw in [1, max_hyp].  hyp_out[n_draw * 3] (the first n_draw * k entries are written, k per hypothesis) and k_out
+ * may be NULL.  pre3_ransac_seeded with no measurement scores nothing (stats = {-1, 0, 0, 0}, support = -1), as pre3_step skips the stage. */
+PRE3_API int pre3_ransac_seeded(pre3_ctx *ctx, uint64_t seed, uint64_t seq, int n_draw, double threshold, int early_exit,
+                                int32_t *hyp_out, int32_t *k_out, int32_t *support, int32_t *li_mask, int32_t stats[4]);
+/* pre3_step / pre3_step_predicted with the draw kernel queued in front of the scoring launch: no host wait is added, the inbox carries no table;
+ * PRE3_OPT_DEFER_HI, PRE3_OPT_PEND_HI and a booked context work as with a supplied table. */
+PRE3_API int pre3_step_seeded(pre3_ctx *ctx, const double u[7], int m, const int32_t *meas_idx, const double *z, uint64_t seed, uint64_t seq,
+                              int n_draw, double threshold, int early_exit, double chi2, int32_t *hyp_out, int32_t *k_out, int32_t stats[8]);
+PRE3_API int pre3_step_predicted_seeded(pre3_ctx *ctx, uint64_t seed, uint64_t seq, int n_draw, double threshold, int early_exit, double chi2,
+                                        int32_t *hyp_out, int32_t *k_out, int32_t stats[8]);
+/* ransac_dr_ye.m:28-48: a position is round((pnum - 1) * u + 1); the four first draws are words 0..3 of block(h, attempt 0); position p (2nd, 3rd,
+ * 4th) is redrawn -- word p of block(h, a), a = 1, 2, .. -- while it repeats an earlier position or shares a keypoint with one (ind_dup1/2/3 as the
+ * reference writes them).  match: 2 x pnum doubles, column-major (keypoint numbers of frame 1 / 2), read on the device.  The reference loops for ever
+ * when no admissible position exists; here a position stops after 64 redraws and keeps its last value: *capped_out = hypotheses with such a position.
+ * n_hyp is the caller's rst.  draws_out[n_hyp * 4], capped_out: may be NULL.  pnum < 4: PRE3_E_ARG. */
+PRE3_API int pre3_vo_ransac_seeded(int device, int pnum, const double *pset1, const double *pset2, const double *match, int n_hyp,
+                                   uint64_t seed, uint64_t seq, int32_t *draws_out, int32_t *capped_out,
+                                   int32_t *cnum_out, int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res);
+PRE3_API int pre3_vo_ransac_frames_seeded(int device, int rows, int cols, const double *x1, const double *y1, const double *z1,
+                                          const double *x2, const double *y2, const double *z2, int ldf, int K1, const double *frm1,
+                                          int K2, const double *frm2, int pnum, const double *match, int n_hyp, uint64_t seed, uint64_t seq,
+                                          int32_t *draws_out, int32_t *capped_out, double *pset1_out, double *pset2_out, int32_t *cnum_out,
+                                          int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res);
+/* ransac.m:142-176: per attempt three distinct of npts (block(h, attempt)); redrawn while norm(cross(p2 - p1, p3 - p1)) < eps on the cropped points,
+ * at most 100 attempts, the last one kept.  n_draw in [1, PRE3_PLANE_MAX_DRAWS]; draws_out[n_draw * 3] may be NULL.  Only the points cross PCIe.
+ * pre3_heading_from_scan_seeded with draws_out, applied_out and res_out all NULL does not synchronise. */
+PRE3_API int pre3_plane_fit_seeded(int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr,
+                                   const int32_t *box, double t, int n_draw, uint64_t seed, uint64_t seq, int32_t *draws_out,
+                                   int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res);
+PRE3_API int pre3_heading_from_scan_seeded(pre3_ctx *ctx, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr,
+                                           const int32_t *box, double t, int n_draw, uint64_t seed, uint64_t seq, int transpose,
+                                           int strict_reference, int32_t *draws_out, int32_t *applied_out, pre3_plane_result *res_out);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them

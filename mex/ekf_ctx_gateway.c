@@ -114,6 +114,37 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         for (i = 0; i < 6; ++i) mxGetPr(out[0])[i] = st[i];
         mxFree(hyp); check(rc);
     }
+    else if (!strcmp(cmd, "ransac_seeded")) {     /* [li_mask, stats, hyp] = pre3_mex('ransac_seeded', seed, seq, n_draw, thr, early_exit [, m]): 'ransac' with the table drawn
+                                                     on the device from (seed, seq) (pre3_ransac_seeded; select_random_match.m:40-51); hyp n_draw x k, 0-based.  seed and
+                                                     seq are doubles: whole numbers up to 2^53 */
+        int n_draw = (int)mxGetScalar(in[3]), i, j, rc, m;
+        int32_t st[4], *li, *hyp, k = 0;
+        if (nin < 6) mexErrMsgTxt("pre3_mex('ransac_seeded', seed, seq, n_draw, thr, early_exit [, m])");
+        m = nin > 6 ? (int)mxGetScalar(in[6]) : 4096;
+        li = (int32_t *)mxCalloc(m, sizeof(int32_t));
+        hyp = (int32_t *)mxCalloc(3 * (size_t)(n_draw > 0 ? n_draw : 1), sizeof(int32_t));
+        rc = pre3_ransac_seeded(g_ctx, (uint64_t)mxGetScalar(in[1]), (uint64_t)mxGetScalar(in[2]), n_draw, mxGetScalar(in[4]), (int)mxGetScalar(in[5]),
+                                nout > 2 ? hyp : NULL, &k, NULL, li, st);
+        out[0] = mxCreateDoubleMatrix(1, m, mxREAL);
+        for (i = 0; i < m; ++i) mxGetPr(out[0])[i] = li[i];
+        if (nout > 1) { out[1] = mxCreateDoubleMatrix(1, 4, mxREAL); for (i = 0; i < 4; ++i) mxGetPr(out[1])[i] = st[i]; }
+        if (nout > 2 && rc == PRE3_OK) {
+            out[2] = mxCreateDoubleMatrix(n_draw, k, mxREAL);
+            for (i = 0; i < n_draw; ++i) for (j = 0; j < k; ++j) mxGetPr(out[2])[(size_t)j * n_draw + i] = hyp[i * k + j];
+        }
+        mxFree(hyp); mxFree(li); check(rc);
+    }
+    else if (!strcmp(cmd, "step_predicted_seeded")) {   /* stats = pre3_mex('step_predicted_seeded', seed, seq, n_draw, thr, early_exit [, chi2]): 'step_predicted' with the table
+                                                           drawn on the device (pre3_step_predicted_seeded) */
+        int32_t st[8];
+        int i, rc;
+        if (nin < 6) mexErrMsgTxt("pre3_mex('step_predicted_seeded', seed, seq, n_draw, thr, early_exit [, chi2])");
+        rc = pre3_step_predicted_seeded(g_ctx, (uint64_t)mxGetScalar(in[1]), (uint64_t)mxGetScalar(in[2]), (int)mxGetScalar(in[3]), mxGetScalar(in[4]),
+                                        (int)mxGetScalar(in[5]), nin > 6 ? mxGetScalar(in[6]) : 5.9915, NULL, NULL, st);
+        check(rc);
+        out[0] = mxCreateDoubleMatrix(1, 6, mxREAL);
+        for (i = 0; i < 6; ++i) mxGetPr(out[0])[i] = st[i];
+    }
     else if (!strcmp(cmd, "rescue")) {            /* hi_mask = pre3_mex('rescue', chi2, m) */
         int m = nin > 2 ? (int)mxGetScalar(in[2]) : 4096, i, rc; int32_t *hi = (int32_t *)mxCalloc(m, sizeof(int32_t));
         rc = pre3_rescue(g_ctx, mxGetScalar(in[1]), hi);
@@ -216,6 +247,18 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
                                     nin > 5 ? (int)mxGetScalar(in[5]) : 1, &applied, NULL);
         mxFree(d);
         check(rc);
+        out[0] = mxCreateDoubleScalar((double)applied);
+    }
+    else if (!strcmp(cmd, "plane_heading_seeded")) {   /* applied = pre3_mex('plane_heading_seeded', x_sr, y_sr, z_sr, seed, seq [, n_draw, strict]): 'plane_heading' with
+                                                          ransac.m:142-176's draws made on the device from (seed, seq) (pre3_heading_from_scan_seeded); n_draw: 1001 */
+        int32_t applied = 0;
+        int rows = (int)mxGetM(in[1]), cols = (int)mxGetN(in[1]);
+        if (nin < 6) mexErrMsgTxt("pre3_mex('plane_heading_seeded', x_sr, y_sr, z_sr, seed, seq [, n_draw, strict])");
+        if ((int)mxGetM(in[2]) != rows || (int)mxGetN(in[2]) != cols || (int)mxGetM(in[3]) != rows || (int)mxGetN(in[3]) != cols)
+            mexErrMsgTxt("pre3_mex('plane_heading_seeded'): x_sr, y_sr, z_sr must have the same size");
+        check(pre3_heading_from_scan_seeded(g_ctx, rows, cols, mxGetPr(in[1]), mxGetPr(in[2]), mxGetPr(in[3]), NULL, 0.02,
+                                            nin > 6 ? (int)mxGetScalar(in[6]) : PRE3_PLANE_MAX_DRAWS, (uint64_t)mxGetScalar(in[4]), (uint64_t)mxGetScalar(in[5]), 1,
+                                            nin > 7 ? (int)mxGetScalar(in[7]) : 1, NULL, &applied, NULL));
         out[0] = mxCreateDoubleScalar((double)applied);
     }
     else if (!strcmp(cmd, "map_delete")) {        /* pre3_mex('map_delete', idx (0-based, ascending))   delete_features.m:54-74 */
