@@ -378,6 +378,9 @@ int launch_draw_1p(unsigned long long seed, unsigned long long seq, int n_draw, 
 int launch_draw_vo(unsigned long long seed, unsigned long long seq, int n_hyp, int pnum, const double *m1_dev, const double *m2_dev, int ms, int32_t *draws_dev,
                    int32_t *capped_dev /* zero at launch */, hipStream_t st);
 int launch_draw_plane(unsigned long long seed, unsigned long long seq, int n_draw, int npts, const double *pts_dev, int32_t *draws_dev, hipStream_t st);
+// the candidates' weighted order: keys, then their counting rank; cand_out_dev != nullptr: the [K][2] | rho[K] block re-laid in drawn order
+int launch_cand_order(unsigned long long seed, unsigned long long seq, int K, int box_w, int box_h, const double *raw_dev, double *keys_dev, int32_t *order_dev,
+                      double *cand_out_dev, hipStream_t st);
 
 // ---- map policy (pre3_map.hip): the rescue-visibility rider of a booked context (one small launch at the post-LI x_k_k), buffers
 int launch_book_vis(pre3_ctx *c);

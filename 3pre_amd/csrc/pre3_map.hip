@@ -14,6 +14,7 @@
 
 #include "pre3_internal.h"
 #include "pre3_geomdev.h"
+#include "pre3_philox.h"
 
 namespace pre3 {
 
@@ -1027,54 +1028,72 @@ int pre3_get_book(pre3_ctx *c, int first, int count, int32_t *book_out)
 }
 
 // map_management.m:27-79 with its policy: the decisions on the device (k_policy_lm, k_policy_prefilter, k_policy_walk), ONE host wait for the
-// result block, then the composition of pre3_map_management with those lists (one pass over P), the candidates' descriptors and the book rows
-int pre3_map_policy(pre3_ctx *c, int step, int min_features, double convert_threshold, double std_pxl, int strict_reference, int K,
-                    const double *cand_uv, const double *cand_xyz, const double *cand_desc, int32_t *del_out, int32_t *n_del_out,
-                    int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out, int32_t stats[4])
+// result block, then the composition of pre3_map_management with those lists (one pass over P), the candidates' descriptors and the book rows.
+// sd == nullptr: pre3_map_policy, the candidates walked in the caller's order.  sd != nullptr: pre3_map_policy_seeded -- the
+// candidates go up in the caller's order, k_cand_keys and k_cand_rank in front of k_policy_prefilter re-lay them in the drawn order, the order comes
+// back in the result block and maps the accepted positions to the caller's indices.
+struct CandSeed { uint64_t seed, seq; int box_w, box_h; };
+
+static int cand_box_check(const char *who, int box_w, int box_h)
+{
+    PRE3_CHECK(box_w > 0 && box_h > 0, PRE3_E_ARG, "%s: box sizes %d x %d must be positive", who, box_w, box_h);
+    const CandBox b = cand_box(box_w, box_h);
+    PRE3_CHECK(b.su > 0.0 && b.sv > 0.0, PRE3_E_ARG, "%s: box %d x %d gives a zero sigma (round(size / 6))", who, box_w, box_h);
+    return PRE3_OK;
+}
+
+static int map_policy_impl(const char *who, pre3_ctx *c, int step, int min_features, double convert_threshold, double std_pxl, int strict_reference, int K,
+                           const double *cand_uv, const double *cand_xyz, const double *cand_desc, const CandSeed *sd, int32_t *order_out,
+                           int32_t *del_out, int32_t *n_del_out, int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out, int32_t stats[4])
 {
     // ---- every argument and state check before anything is launched: an error leaves the context as it was
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
     PRE3_CHECK(K >= 0 && K <= PRE3_POLICY_MAX_CANDIDATES && (K == 0 || (cand_uv && cand_xyz)), PRE3_E_ARG,
-               "pre3_map_policy: K=%d candidates (at most %d, uv and xyz required)", K, PRE3_POLICY_MAX_CANDIDATES);
-    PRE3_CHECK(min_features >= 0 && min_features <= POL_MAX_FEATURES, PRE3_E_ARG, "pre3_map_policy: min_features=%d outside 0 .. %d", min_features, POL_MAX_FEATURES);
-    PRE3_CHECK(std::isfinite(std_pxl) && std::isfinite(convert_threshold), PRE3_E_ARG, "pre3_map_policy: std_pxl and the threshold must be finite");
+               "%s: K=%d candidates (at most %d, uv and xyz required)", who, K, PRE3_POLICY_MAX_CANDIDATES);
+    PRE3_CHECK(min_features >= 0 && min_features <= POL_MAX_FEATURES, PRE3_E_ARG, "%s: min_features=%d outside 0 .. %d", who, min_features, POL_MAX_FEATURES);
+    PRE3_CHECK(std::isfinite(std_pxl) && std::isfinite(convert_threshold), PRE3_E_ARG, "%s: std_pxl and the threshold must be finite", who);
+    if (sd) PRE3_TRY(cand_box_check(who, sd->box_w, sd->box_h));
     std::vector<double> rho(K);
     for (int k = 0; k < K; ++k) {
         const double x = cand_xyz[3 * k], y = cand_xyz[3 * k + 1], z = cand_xyz[3 * k + 2];
         rho[k] = 1.0 / sqrt(x * x + y * y + z * z);                 // initialize_a_feature_sift_3.m:116-117
-        PRE3_CHECK(std::isfinite(cand_uv[2 * k]) && std::isfinite(cand_uv[2 * k + 1]), PRE3_E_ARG, "pre3_map_policy: candidate %d has a non-finite pixel", k);
-        PRE3_CHECK(std::isfinite(rho[k]) && rho[k] > 0, PRE3_E_ARG, "pre3_map_policy: candidate %d has a zero or non-finite XYZ", k);
+        PRE3_CHECK(std::isfinite(cand_uv[2 * k]) && std::isfinite(cand_uv[2 * k + 1]), PRE3_E_ARG, "%s: candidate %d has a non-finite pixel", who, k);
+        PRE3_CHECK(std::isfinite(rho[k]) && rho[k] > 0, PRE3_E_ARG, "%s: candidate %d has a zero or non-finite XYZ", who, k);
     }
-    PRE3_CHECK(c->have_cam, PRE3_E_STATE, "pre3_map_policy: camera not set");
-    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "pre3_map_policy: needs (x_k_k, p_k_k) on the device (map management runs between steps)");
-    PRE3_CHECK(c->booked || c->N == 0, PRE3_E_STATE, "pre3_map_policy: the context has no book (pre3_set_book)");
+    PRE3_CHECK(c->have_cam, PRE3_E_STATE, "%s: camera not set", who);
+    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "%s: needs (x_k_k, p_k_k) on the device (map management runs between steps)", who);
+    PRE3_CHECK(c->booked || c->N == 0, PRE3_E_STATE, "%s: the context has no book (pre3_set_book)", who);
     // ---- a deferred HI update completed, pending work flushed (map_precheck); the book
     EntryScope scope(c); PRE3_TRY(scope.rc);
-    PRE3_TRY(map_precheck(c, "pre3_map_policy"));
+    PRE3_TRY(map_precheck(c, who));
     PRE3_TRY(start_book(c));
     const int N = c->N;
-    // ---- buffers: device scratch [cand 3K | puv 2capN | del, mh, pvis capN | blocked K], the mapped result block [hdr | del capN | acc K | conv capN | cand 3K]
-    const size_t cap = (size_t)std::max(c->capN, 1), Kc = (size_t)std::max(K, 1);
-    const size_t dev_bytes = sizeof(double) * (3 * Kc + 2 * cap) + sizeof(int32_t) * (7 * cap + Kc);
-    const size_t res_words = ((POL_HDR + 2 * cap + Kc) + 1) & ~(size_t)1, host_bytes = sizeof(int32_t) * res_words + sizeof(double) * 3 * Kc;
+    // ---- buffers: device scratch [cand 3K | puv 2capN | (seeded: raw 3K | keys K) | del, mh, pvis capN | blocked K], the mapped result block
+    // [hdr | del capN | acc K | conv capN | (seeded: order K) | cand 3K]
+    const size_t cap = (size_t)std::max(c->capN, 1), Kc = (size_t)std::max(K, 1), Ks = sd ? Kc : 0;
+    const size_t dev_bytes = sizeof(double) * (3 * Kc + 2 * cap + 4 * Ks) + sizeof(int32_t) * (7 * cap + Kc);
+    const size_t o_order = POL_HDR + 2 * (size_t)c->capN + (size_t)K;
+    const size_t res_words = ((POL_HDR + 2 * cap + Kc + Ks) + 1) & ~(size_t)1, host_bytes = sizeof(int32_t) * res_words + sizeof(double) * 3 * Kc;
     if (dev_bytes > c->pol_dev_bytes) {
         if (c->pol_dev) (void)hipFree(c->pol_dev);
         c->pol_dev = nullptr; c->pol_dev_bytes = 0;
-        PRE3_CHECK(hipMalloc(&c->pol_dev, dev_bytes) == hipSuccess, PRE3_E_NOMEM, "pre3_map_policy: device allocation of %zu bytes failed", dev_bytes);
+        PRE3_CHECK(hipMalloc(&c->pol_dev, dev_bytes) == hipSuccess, PRE3_E_NOMEM, "%s: device allocation of %zu bytes failed", who, dev_bytes);
         c->pol_dev_bytes = dev_bytes;
     }
     if (host_bytes > c->pol_host_bytes) {
         if (c->pol_host) (void)hipHostFree(c->pol_host);
         c->pol_host = c->pol_host_dev = nullptr; c->pol_host_bytes = 0;
-        PRE3_CHECK(hipHostMalloc((void **)&c->pol_host, host_bytes, hipHostMallocMapped) == hipSuccess, PRE3_E_NOMEM, "pre3_map_policy: pinned allocation failed");
+        PRE3_CHECK(hipHostMalloc((void **)&c->pol_host, host_bytes, hipHostMallocMapped) == hipSuccess, PRE3_E_NOMEM, "%s: pinned allocation failed", who);
         PRE3_HIP(hipHostGetDevicePointer((void **)&c->pol_host_dev, c->pol_host, 0));
         c->pol_host_bytes = host_bytes;
     }
     double *h_cand = reinterpret_cast<double *>(c->pol_host + res_words);
     for (int k = 0; k < K; ++k) { h_cand[2 * k] = cand_uv[2 * k]; h_cand[2 * k + 1] = cand_uv[2 * k + 1]; h_cand[2 * K + k] = rho[k]; }
-    double *d_cand = static_cast<double *>(c->pol_dev), *d_puv = d_cand + 3 * Kc;
-    int32_t *d_del = reinterpret_cast<int32_t *>(d_puv + 2 * cap), *d_mh = d_del + cap, *d_pvis = d_mh + cap, *d_nbook = d_pvis + cap, *d_blocked = d_nbook + 4 * cap;
-    if (K > 0) PRE3_HIP(hipMemcpyAsync(d_cand, h_cand, sizeof(double) * 3 * K, hipMemcpyHostToDevice, c->stream));
+    double *d_cand = static_cast<double *>(c->pol_dev), *d_puv = d_cand + 3 * Kc, *d_raw = d_puv + 2 * cap, *d_keys = d_raw + 3 * Ks;
+    int32_t *d_del = reinterpret_cast<int32_t *>(d_keys + Ks), *d_mh = d_del + cap, *d_pvis = d_mh + cap, *d_nbook = d_pvis + cap, *d_blocked = d_nbook + 4 * cap;
+    if (K > 0) PRE3_HIP(hipMemcpyAsync(sd ? d_raw : d_cand, h_cand, sizeof(double) * 3 * K, hipMemcpyHostToDevice, c->stream));
+    // ---- seeded: the keys and their rank re-lay the block in the drawn order (d_raw -> d_cand); the order goes into the result block
+    if (sd && K > 0) PRE3_TRY(launch_cand_order(sd->seed, sd->seq, K, sd->box_w, sd->box_h, d_raw, d_keys, c->pol_host_dev + o_order, d_cand, c->stream));
     // ---- inversedepth_2_cartesian's flags and points (the same launch pre3_map_management makes: the same linearity numbers)
     if (convert_threshold >= 0 && N > 0) {
         DISPATCH_T(c,
@@ -1090,13 +1109,21 @@ int pre3_map_policy(pre3_ctx *c, int step, int min_features, double convert_thre
     }
     hipLaunchKernelGGL(k_policy_walk, dim3(1), dim3(64), 0, c->stream, pa);
     PRE3_HIP(hipGetLastError());
-    PRE3_TRY(stream_drain(c, __func__));                            // the one host wait
+    PRE3_TRY(stream_drain(c, who));                                 // the one host wait
     const int32_t *res = c->pol_host, *r_del = res + POL_HDR, *r_acc = r_del + c->capN, *r_conv = r_acc + K;
     const int n_del = res[4], n_acc = res[5], n_surv = res[6];
-    PRE3_CHECK(n_del >= 0 && n_del <= N && n_acc >= 0 && n_acc <= K && n_surv == N - n_del && n_surv + n_acc <= c->capN, PRE3_E_HIP, "pre3_map_policy: inconsistent result block");
+    PRE3_CHECK(n_del >= 0 && n_del <= N && n_acc >= 0 && n_acc <= K && n_surv == N - n_del && n_surv + n_acc <= c->capN, PRE3_E_HIP, "%s: inconsistent result block", who);
     std::vector<int32_t> dl(r_del, r_del + n_del), acc(r_acc, r_acc + n_acc), flags(N ? N : 1, 0);
     for (int i = 0; i < N; ++i) flags[i] = r_conv[i];
     int32_t st[4] = { res[0], res[1], res[2], res[3] };
+    if (sd) {                                                       // drawn positions -> the caller's candidate indices (stats[2] stays a count of positions)
+        const int32_t *r_order = res + o_order;
+        for (int a = 0; a < n_acc; ++a) {
+            PRE3_CHECK(acc[a] >= 0 && acc[a] < K && r_order[acc[a]] >= 0 && r_order[acc[a]] < K, PRE3_E_HIP, "%s: inconsistent result block", who);
+            acc[a] = r_order[acc[a]];
+        }
+        if (order_out) for (int k = 0; k < K; ++k) order_out[k] = r_order[k];
+    }
     std::vector<double> uvd(2 * (size_t)n_acc), rho_acc(n_acc);
     for (int a = 0; a < n_acc; ++a) { uvd[2 * a] = cand_uv[2 * acc[a]]; uvd[2 * a + 1] = cand_uv[2 * acc[a] + 1]; rho_acc[a] = rho[acc[a]]; }
     // ---- the state: pre3_map_management's composition with these lists; the book rides along (new landmarks: {0, 0, step - 1, step - 1},
@@ -1116,6 +1143,47 @@ int pre3_map_policy(pre3_ctx *c, int step, int min_features, double convert_thre
     if (accepted_out) for (int a = 0; a < n_acc; ++a) accepted_out[a] = acc[a];
     if (n_acc_out) *n_acc_out = n_acc;
     if (stats) for (int q = 0; q < 4; ++q) stats[q] = st[q];
+    return PRE3_OK;
+}
+
+int pre3_map_policy(pre3_ctx *c, int step, int min_features, double convert_threshold, double std_pxl, int strict_reference, int K,
+                    const double *cand_uv, const double *cand_xyz, const double *cand_desc, int32_t *del_out, int32_t *n_del_out,
+                    int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out, int32_t stats[4])
+{
+    return map_policy_impl("pre3_map_policy", c, step, min_features, convert_threshold, std_pxl, strict_reference, K, cand_uv, cand_xyz, cand_desc, nullptr, nullptr,
+                           del_out, n_del_out, accepted_out, n_acc_out, converted_out, stats);
+}
+
+int pre3_map_policy_seeded(pre3_ctx *c, int step, int min_features, double convert_threshold, double std_pxl, int strict_reference, int K,
+                           const double *cand_uv, const double *cand_xyz, const double *cand_desc, int box_w, int box_h, uint64_t seed, uint64_t seq,
+                           int32_t *order_out, int32_t *del_out, int32_t *n_del_out, int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out,
+                           int32_t stats[4])
+{
+    const CandSeed sd{ seed, seq, box_w, box_h };
+    return map_policy_impl("pre3_map_policy_seeded", c, step, min_features, convert_threshold, std_pxl, strict_reference, K, cand_uv, cand_xyz, cand_desc, &sd,
+                           order_out, del_out, n_del_out, accepted_out, n_acc_out, converted_out, stats);
+}
+
+// Weighted_Smpl_wo_replacement.m on its own: the keys and the order of K candidates, stateless, on the pooled device scratch
+int pre3_candidate_order(int device, int K, const double *cand_uv, int box_w, int box_h, uint64_t seed, uint64_t seq, int32_t *order_out, double *keys_out)
+{
+    const char *who = "pre3_candidate_order";
+    PRE3_CHECK(K >= 0 && K <= PRE3_POLICY_MAX_CANDIDATES, PRE3_E_ARG, "%s: K=%d candidates (at most %d)", who, K, PRE3_POLICY_MAX_CANDIDATES);
+    PRE3_TRY(cand_box_check(who, box_w, box_h));
+    if (K == 0) return PRE3_OK;
+    PRE3_CHECK(cand_uv != nullptr && order_out != nullptr, PRE3_E_ARG, "%s: null argument", who);
+    for (int k = 0; k < 2 * K; ++k) PRE3_CHECK(std::isfinite(cand_uv[k]), PRE3_E_ARG, "%s: candidate %d has a non-finite pixel", who, k / 2);
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
+    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return PRE3_E_NODEVICE; }
+    struct Scratch { void *p = nullptr; int slot = -1; ~Scratch() { scratch_release(slot, p); } } d;
+    PRE3_TRY(scratch_acquire(sizeof(double) * 3 * (size_t)K + sizeof(int32_t) * (size_t)K, &d.p, &d.slot));      // [uv 2K | keys K | order K]
+    double *d_uv = static_cast<double *>(d.p), *d_keys = d_uv + 2 * (size_t)K;
+    int32_t *d_order = reinterpret_cast<int32_t *>(d_keys + K);
+    PRE3_HIP(hipMemcpy(d_uv, cand_uv, sizeof(double) * 2 * (size_t)K, hipMemcpyHostToDevice));
+    PRE3_TRY(launch_cand_order(seed, seq, K, box_w, box_h, d_uv, d_keys, d_order, nullptr, 0));
+    PRE3_HIP(hipMemcpy(order_out, d_order, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost));                  // (synchronises)
+    if (keys_out) PRE3_HIP(hipMemcpy(keys_out, d_keys, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost));
     return PRE3_OK;
 }
 

@@ -2,7 +2,7 @@
 // Philox4x64-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11) with its public constants: one block is a pure
 // function of (counter[4], key[2]); no state lives anywhere.  numpy.random.Philox is the same generator (it advances the counter before its first
 // block): tests/test_draws_ref.py pins tests/draws_ref.py's restatement against it, tests/test_gpu_draws.py the kernels against the restatement.
-//   key     = [seed, stream]               stream 1: 1-point RANSAC, 2: VO 4-point RANSAC, 3: floor-plane RANSAC
+//   key     = [seed, stream]               stream 1: 1-point RANSAC, 2: VO 4-point RANSAC, 3: floor-plane RANSAC, 4: the candidates' weighted order
 //   counter = [index, attempt, seq, 0]     index: the hypothesis; attempt: the redraw number (0 = first draw); seq: the caller's frame / step number
 // A bounded integer in [0, range) is the high 64 bits of word * range: no rejection, so value v is drawn with probability floor- or ceil-(2^64 / range)
 // / 2^64 -- a bias of at most range / 2^64 (below 2^-50 for every range of this library).  A uniform double is the word's top 53 bits times 2^-53.
@@ -21,7 +21,7 @@ namespace pre3 {
 
 constexpr uint64_t PHILOX_M0 = 0xD2E7470EE14C6C93ull, PHILOX_M1 = 0xCA5A826395121157ull;
 constexpr uint64_t PHILOX_W0 = 0x9E3779B97F4A7C15ull, PHILOX_W1 = 0xBB67AE8584CAA73Bull;
-enum { DRAW_STREAM_1P = 1, DRAW_STREAM_VO = 2, DRAW_STREAM_PLANE = 3 };
+enum { DRAW_STREAM_1P = 1, DRAW_STREAM_VO = 2, DRAW_STREAM_PLANE = 3, DRAW_STREAM_CAND = 4 };
 constexpr int VO_MAX_REDRAWS = 64;          // per position; ransac_dr_ye.m:28-46 loops for ever
 constexpr int PLANE_MAX_ATTEMPTS = 100;     // ransac.m:122 maxDataTrials
 
@@ -142,6 +142,45 @@ PRE3_HD void draw_rule_plane(uint64_t seed, uint64_t seq, int npts, const double
         const double nn = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
         if (!(nn < 2.220446049250313e-16)) return;
     }
+}
+
+// ---- Weighted_Smpl_wo_replacement.m:3-4,24,28-34: the order of the initialisation candidates.  The reference draws one index at a
+// time with probability proportional to the remaining weights w_i = mvnpdf(uv_i, mean, diag(sigma^2)) -- Plackett-Luce sampling, which an exponential
+// race samples with no sequential dependence: candidate i gets key_i = E_i / w_i, E_i = -log1p(-U_i) a unit exponential, and the order is the
+// candidates sorted by (key, index) ascending.  mean = round([W H] / 2), sigma = round([W H] / 6), MATLAB rounding (half away from zero); the
+// normalising constant of the weights drops out, so key_i = E_i * exp(q_i), q_i = ((u - mu) / su)^2 / 2 + ((v - mv) / sv)^2 / 2.
+struct CandBox { double mu, mv, su, sv; };
+
+PRE3_HD double round_half_away(double v) { return v < 0.0 ? -floor(-v + 0.5) : floor(v + 0.5); }
+
+// (su or sv == 0 -- a box below 3 pixels -- is refused by the entry points)
+PRE3_HD CandBox cand_box(int box_w, int box_h)
+{
+    CandBox b;
+    b.mu = round_half_away((double)box_w / 2.0); b.mv = round_half_away((double)box_h / 2.0);
+    b.su = round_half_away((double)box_w / 6.0); b.sv = round_half_away((double)box_h / 6.0);
+    return b;
+}
+
+// every quotient, product and sum rounded on its own, as numpy rounds them
+PRE3_HD double cand_q(double u, double v, const CandBox &b)
+{
+#pragma clang fp contract(off)
+    const double du = (u - b.mu) / b.su, dv = (v - b.mv) / b.sv;
+    const double su2 = du * du, sv2 = dv * dv;
+    const double s = su2 + sv2;
+    return 0.5 * s;
+}
+
+// U = uniform(word 0 of block(i, 0, seq; seed, stream 4)).  For finite (u, v) the key is never NaN: q >= 0, so exp(q) is in [1, +inf]; E is in
+// [0, 37) and E == 0 (U == 0) gives key 0 whatever exp(q) is -- the one product that could be 0 * inf is not formed.  +inf (a pixel absurdly far from
+// the image) and 0 are legal keys: they sort by value, then by index.
+PRE3_HD double cand_key(uint64_t seed, uint64_t seq, int i, double u, double v, const CandBox &b)
+{
+    const double U = draw_uniform(draw_block(seed, DRAW_STREAM_CAND, (uint64_t)i, 0, seq).w[0]);
+    const double E = -log1p(-U);
+    if (!(E > 0.0)) return 0.0;
+    return E * exp(cand_q(u, v, b));
 }
 
 }  // namespace pre3

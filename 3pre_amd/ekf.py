@@ -347,6 +347,33 @@ class EkfFilter:
         return dict(deleted=dl[:nd.value].copy(), accepted=acc[:na.value].copy(), converted=conv[:N0].copy(), measured=int(st[0]),
                     target=int(st[1]), examined=int(st[2]), N=int(st[3]))
 
+    def map_management_policy_seeded(self, step, cand_uv, cand_xyz, seed, seq=0, cand_desc=None, box=(176, 144), min_features=50,
+                                     linearity_index_threshold=0.1, std_pxl=None, strict_reference=True):
+        """map_management_policy with the candidates' order -- Weighted_Smpl_wo_replacement.m, the draw initialize_a_feature_sift_3.m:42-46 makes
+        -- drawn on the device from (seed, seq) (synth.candidate_order's rule; DESIGN.md section 19).  The candidates are given in any order;
+        box = (BoxLimX(2), BoxLimY(2)).  Returns map_management_policy's dict plus order (K,): order[p] = the candidate at drawn position p;
+        accepted holds indices into the arrays as given."""
+        uv = f64(np.asarray(cand_uv, float).reshape(-1, 2))
+        xyz = f64(np.asarray(cand_xyz, float).reshape(-1, 3))
+        K = int(uv.shape[0])
+        if xyz.shape[0] != K:
+            raise ValueError("cand_uv and cand_xyz disagree on K")
+        desc = None
+        if cand_desc is not None:
+            d = np.asarray(cand_desc, dtype=np.float64)
+            desc = np.ascontiguousarray(d.T) if d.ndim == 2 and d.shape[0] == 128 and d.shape[1] == K else f64(d).reshape(K, 128)
+        N0 = self.N
+        dl, acc, conv = np.zeros(max(N0, 1), np.int32), np.zeros(max(K, 1), np.int32), np.zeros(max(N0, 1), np.int32)
+        order = np.zeros(max(K, 1), np.int32)
+        nd, na, st = C.c_int32(0), C.c_int32(0), np.zeros(4, np.int32)
+        thr = -1.0 if linearity_index_threshold is None else float(linearity_index_threshold)
+        check(lib.pre3_map_policy_seeded(self._ctx, int(step), int(min_features), thr, float(self.std_z if std_pxl is None else std_pxl),
+                                         int(bool(strict_reference)), K, dptr(uv), dptr(xyz), dptr(desc), int(box[0]), int(box[1]), int(seed), int(seq),
+                                         dptr(order), dptr(dl), C.byref(nd), dptr(acc), C.byref(na), dptr(conv), dptr(st)))
+        self._refresh_map()
+        return dict(deleted=dl[:nd.value].copy(), accepted=acc[:na.value].copy(), converted=conv[:N0].copy(), measured=int(st[0]),
+                    target=int(st[1]), examined=int(st[2]), N=int(st[3]), order=order[:K].copy())
+
     # ---- IC search on the device (search_IC_matches.m:31-44 + matching_sift_based.m:104-149)
     def set_descriptors(self, desc, first=0):
         """features_info(first+i).Descriptor; desc is (128, count) as MATLAB stores it (or (count, 128) C-order rows)."""

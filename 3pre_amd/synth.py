@@ -105,6 +105,19 @@ def draw_hypotheses(rng, m, n_hyp, k=3):
     return np.stack([rng.permutation(m)[:kk] for _ in range(n_hyp)]).astype(np.int32)
 
 
+def candidate_order(uv, seed, seq=0, box=(176, 144), device=0, return_keys=False):
+    """Weighted_Smpl_wo_replacement.m on the device (pre3_candidate_order): the order in which map_management.m walks the
+    initialisation candidates uv (K, 2), drawn from (seed, seq) with weights mvnpdf(uv, round(box / 2), diag(round(box / 6)^2)).  Returns order (K,)
+    int32 -- order[p] = the candidate at drawn position p -- and, with return_keys, the exponential-race keys (K,) it sorts."""
+    import ctypes as C
+    from ._lib import check, dptr, f64, lib
+    uv = f64(np.asarray(uv, float).reshape(-1, 2))
+    K = int(uv.shape[0])
+    order, keys = np.zeros(max(K, 1), np.int32), np.zeros(max(K, 1))
+    check(lib.pre3_candidate_order(int(device), K, dptr(uv), int(box[0]), int(box[1]), int(seed), int(seq), dptr(order), dptr(keys) if return_keys else None))
+    return (order[:K].copy(), keys[:K].copy()) if return_keys else order[:K].copy()
+
+
 def make_sequence(N, steps, n_hyp, k=3, meas_frac=0.8, outlier_frac=0.2, sigma_z=0.25, seed=None, motion_noise=0.5):
     """A whole input sequence: per step the odometry u, the measured landmark list, their pixels and the
     RANSAC draws.  The truth moves by u_true = u + noise (motion_noise x the process noise the filter assumes,

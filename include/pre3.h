@@ -483,6 +483,33 @@ PRE3_API int pre3_heading_from_scan_seeded(pre3_ctx *ctx, int rows, int cols, co
                                            const int32_t *box, double t, int n_draw, uint64_t seed, uint64_t seq, int transpose,
                                            int strict_reference, int32_t *draws_out, int32_t *applied_out, pre3_plane_result *res_out);
 
+/* ---- seeded map policy: the candidates' weighted order drawn on the device ---------------------------------------------------
+ * Weighted_Smpl_wo_replacement.m, the draw initialize_a_feature_sift_3.m:42-46 makes once per frame: the order in which map_management.m walks its
+ * initialisation candidates.  The reference draws one index at a time with probability proportional to the remaining weights
+ * w_i = mvnpdf(uv_i, mean, diag(sigma^2)), mean = round([box_w box_h] / 2), sigma = round([box_w box_h] / 6) (MATLAB rounding; the reference's box is
+ * 176 x 144: mean (88, 72), sigma (29, 24)).  That distribution (Plackett-Luce) is sampled here as an exponential race:
+ *   key_i = -log1p(-U_i) * exp(q_i),  q_i = (((u_i - mu) / su)^2 + ((v_i - mv) / sv)^2) / 2,
+ *   U_i = the uniform double of word 0 of the Philox block with key = [seed, stream 4] and counter = [i, 0, seq, 0],
+ * and the order is the candidates sorted by (key, index) ascending -- a pure function of (seed, seq, box, uv), bit-equal on every run.  A key of 0
+ * (U = 0) or +inf (a pixel absurdly far from the image) is legal and sorts by its value, then by index; no key is NaN.
+ *
+ * pre3_candidate_order: stateless, on the library's per-device scratch.  cand_uv[2K] distorted pixels; order_out[K]: order_out[p] = the candidate at
+ * drawn position p (0-based); keys_out[K] (may be NULL): key_i per candidate.  K == 0 is PRE3_OK and writes nothing.  K outside
+ * 0 .. PRE3_POLICY_MAX_CANDIDATES, a non-positive box size, a sigma that rounds to 0 (a size below 3), a null or non-finite uv: PRE3_E_ARG before
+ * anything is launched. */
+PRE3_API int pre3_candidate_order(int device, int K, const double *cand_uv, int box_w, int box_h, uint64_t seed, uint64_t seq,
+                                  int32_t *order_out, double *keys_out);
+/* pre3_map_policy with step 5's order drawn on the device: the candidates are given in ANY order (uploaded as they are), two launches in front of the
+ * walk's on the context's stream re-lay them in the drawn order, and the call's one host wait stays the only one.  Every check, state requirement
+ * and output of pre3_map_policy is kept, plus the box checks above.  accepted_out holds the CALLER's candidate indices, in the order of acceptance
+ * (the descriptors are taken from cand_desc by them); order_out[K] (may be NULL) is the drawn order; stats[2] ("examined") counts drawn positions.
+ * Results are bit-identical to pre3_map_policy fed with the candidate arrays permuted by order_out.  Argument errors are PRE3_E_ARG before anything
+ * is launched: the context and the book are unchanged. */
+PRE3_API int pre3_map_policy_seeded(pre3_ctx *ctx, int step, int min_features, double convert_threshold, double std_pxl, int strict_reference,
+                                    int K, const double *cand_uv, const double *cand_xyz, const double *cand_desc, int box_w, int box_h,
+                                    uint64_t seed, uint64_t seq, int32_t *order_out, int32_t *del_out, int32_t *n_del_out,
+                                    int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out, int32_t stats[4]);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them

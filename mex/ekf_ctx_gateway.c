@@ -16,6 +16,7 @@
  *   ekf_heading_update.m:27-52      applied = pre3_mex('heading', R_plane, 1)
  *   mono_slam.m:189-193             applied = pre3_mex('plane_heading', x_sr, y_sr, z_sr, draws, 1)   % plane_fit_to_data + ekf_heading_update on the device
  *   map_management.m:27-79          [del, acc] = pre3_mex('map_policy', step, UV, XYZ, DESC, 50, 0.1, std_z, 1)   % policy on the device; pre3_mex('set_book', B) first
+ *   Weighted_Smpl_wo_replacement.m  [del, acc, cv, st, order] = pre3_mex('map_policy_seeded', step, UV, XYZ, DESC, 50, 0.1, std_z, 1, [176 144], seed, step)   % ... and its draw
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
  * corrcoef_partitioned_mex.c:25-57).  NOT compiled in the build container (no MATLAB / mex.h there).
@@ -318,6 +319,30 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
             if (nout > 3) { out[3] = mxCreateDoubleMatrix(1, 4, mxREAL); for (i = 0; i < 4; ++i) mxGetPr(out[3])[i] = st[i]; }
         }
         mxFree(dl); mxFree(acc); mxFree(cv); check(rc);
+    }
+    else if (!strcmp(cmd, "map_policy_seeded")) { /* [deleted, accepted, converted, stats, order] = pre3_mex('map_policy_seeded', step, UV (2xK), XYZ (3xK), DESC (128xK or []),
+                                                     min_features, linearity_thr (< 0: none), std_pxl, strict, [BoxLimX(2) BoxLimY(2)], seed, seq): 'map_policy' with
+                                                     Weighted_Smpl_wo_replacement.m drawn on the device; UV is UV_GoodFeaturesToInitialize(:, 1:2)' as it stands;
+                                                     accepted and order index its columns, 1-based (seed, seq: integers below 2^53) */
+        int K, N, i, rc; int32_t nd = 0, na = 0, st[4] = { 0, 0, 0, 0 }, *dl, *acc, *cv, *ord;
+        if (nin != 12) mexErrMsgTxt("pre3_mex('map_policy_seeded', step, UV, XYZ, DESC, min_features, thr, std_pxl, strict, box, seed, seq): eleven arguments");
+        K = (int)mxGetN(in[2]); N = pre3_get_map(g_ctx, NULL);
+        if ((K > 0 && mxGetM(in[2]) != 2) || (int)mxGetN(in[3]) != K || (K > 0 && mxGetM(in[3]) != 3)) mexErrMsgTxt("pre3_mex('map_policy_seeded'): UV is 2xK, XYZ 3xK");
+        if (!mxIsEmpty(in[4]) && ((int)mxGetN(in[4]) != K || mxGetM(in[4]) != 128)) mexErrMsgTxt("pre3_mex('map_policy_seeded'): DESC is 128xK or []");
+        if (mxGetNumberOfElements(in[9]) != 2) mexErrMsgTxt("pre3_mex('map_policy_seeded'): box is [BoxLimX(2) BoxLimY(2)]");
+        dl = (int32_t *)mxCalloc(N ? N : 1, sizeof(int32_t)); acc = (int32_t *)mxCalloc(K ? K : 1, sizeof(int32_t)); cv = (int32_t *)mxCalloc(N ? N : 1, sizeof(int32_t));
+        ord = (int32_t *)mxCalloc(K ? K : 1, sizeof(int32_t));
+        rc = pre3_map_policy_seeded(g_ctx, (int)mxGetScalar(in[1]), (int)mxGetScalar(in[5]), mxGetScalar(in[6]), mxGetScalar(in[7]), (int)mxGetScalar(in[8]), K,
+                                    mxGetPr(in[2]), mxGetPr(in[3]), mxIsEmpty(in[4]) ? NULL : mxGetPr(in[4]), (int)mxGetPr(in[9])[0], (int)mxGetPr(in[9])[1],
+                                    (uint64_t)mxGetScalar(in[10]), (uint64_t)mxGetScalar(in[11]), ord, dl, &nd, acc, &na, cv, st);
+        if (rc == PRE3_OK) {
+            out[0] = mxCreateDoubleMatrix(1, nd, mxREAL); for (i = 0; i < nd; ++i) mxGetPr(out[0])[i] = dl[i] + 1;
+            if (nout > 1) { out[1] = mxCreateDoubleMatrix(1, na, mxREAL); for (i = 0; i < na; ++i) mxGetPr(out[1])[i] = acc[i] + 1; }
+            if (nout > 2) { out[2] = mxCreateDoubleMatrix(1, N, mxREAL); for (i = 0; i < N; ++i) mxGetPr(out[2])[i] = cv[i]; }
+            if (nout > 3) { out[3] = mxCreateDoubleMatrix(1, 4, mxREAL); for (i = 0; i < 4; ++i) mxGetPr(out[3])[i] = st[i]; }
+            if (nout > 4) { out[4] = mxCreateDoubleMatrix(1, K, mxREAL); for (i = 0; i < K; ++i) mxGetPr(out[4])[i] = ord[i] + 1; }
+        }
+        mxFree(dl); mxFree(acc); mxFree(cv); mxFree(ord); check(rc);
     }
     else if (!strcmp(cmd, "set_descriptors")) {   /* pre3_mex('set_descriptors', [features_info.Descriptor] (128xN), first (0-based)) */
         check(pre3_set_descriptors(g_ctx, nin > 2 ? (int)mxGetScalar(in[2]) : 0, (int)mxGetN(in[1]), mxGetPr(in[1])));
