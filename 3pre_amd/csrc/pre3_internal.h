@@ -382,6 +382,16 @@ int launch_draw_plane(unsigned long long seed, unsigned long long seq, int n_dra
 int launch_cand_order(unsigned long long seed, unsigned long long seq, int K, int box_w, int box_h, const double *raw_dev, double *keys_dev, int32_t *order_dev,
                       double *cand_out_dev, hipStream_t st);
 
+// ---- the resident SR4000 frame (pre3_sr.hip): the handle's device pointers and stream for other translation units -- a plane fit
+// that crops from the resident frame, a VO gather from two resident frames, the candidate build.  Planes are rows x cols, column-major; conf is null when
+// the frame was loaded without a confidence map; maxima = { imax, cmax }.  Work queued on `stream` is ordered behind the frame's conditioning launches.
+struct SrFrameView {
+    int device, rows, cols, mode, has_conf;
+    const double *x, *y, *z, *img, *conf, *maxima;
+    hipStream_t stream;
+};
+int sr_frame_view(pre3_sr_frame *f, SrFrameView *v);      /* PRE3_E_STATE before the first load */
+
 // ---- map policy (pre3_map.hip): the rescue-visibility rider of a booked context (one small launch at the post-LI x_k_k), buffers
 int launch_book_vis(pre3_ctx *c);
 void free_policy(pre3_ctx *c);

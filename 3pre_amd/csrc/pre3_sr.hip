@@ -1,0 +1,384 @@
+// pre3_sr.hip -- one resident, conditioned SR4000 frame per .dat scan and the keypoint stage on it (pre3_sr_frame_*).
+//   read_xyz_sr4000.m:8-21, read_image_sr4000.m:10-24, normalzie_image.m:4             (mode 0: sigma = 2, zero padding)
+//   code_from_dr_ye/read_sr4000_data_dr_ye.m:8,11-21,42,70,88-90                       (mode 1: sigma = 1, replicated border)
+//   SIFT_extract_save.m:71-88 over inittialize_depth_my_version.m:16,40-45,74-92       (gate 0: the depth gate, XYZ_DATA, rho)
+//   code_from_dr_ye/confidence_filtering.m:1-13                                        (gate 1)
+// Three launches, all fp64, on the handle's own stream:
+//   k_sr_maxima     one workgroup: imax (the largest unsaturated amplitude) and cmax (max(confidence_map(:)), NaNs skipped) -- xor butterfly per wave,
+//                   the waves combined through LDS.
+//   k_sr_condition  16 x 16 tiles with a one-pixel halo in LDS: the filtered x, y, z and the filtered uint8 image.  Halo pixels recompute the
+//                   normalisation from the raw amplitude; the image exists only filtered.
+//   k_sr_keypoints  a workgroup owns 256 consecutive keypoints; its base offset is the predicate of every earlier keypoint re-evaluated by itself
+//                   (ballot + popcount), ranks inside it are a ballot prefix per wave plus the wave sums through LDS; then one wave per kept keypoint
+//                   copies its frame entries and descriptor to slot `rank`.
+// No workgroup waits on another, there are no atomics, every output slot has one writer: results are bit-equal from run to run.  The arithmetic is
+// pre3_sr.h's, compiled without contraction.
+#include <cmath>
+
+#include "pre3_internal.h"
+#include "pre3_sr.h"
+
+struct pre3_sr_frame {
+    int device = 0, rows = 0, cols = 0;
+    int loaded = 0, mode = 0, has_conf = 0;
+    hipStream_t stream = nullptr;
+    double *raw = nullptr;          // [5][npix]: z, x, y, amplitude, confidence -- as uploaded
+    double *filt = nullptr;         // [4][npix]: x, y, z, image
+    double *maxima = nullptr;       // imax, cmax
+    void *stage = nullptr;          // pinned: the five planes of a load, or the keypoints of a call
+    size_t stage_bytes = 0;
+    void *kp = nullptr;             // device: the keypoint stage's input and output block
+    size_t kp_bytes = 0;
+    int32_t *pinned_n = nullptr;    // n_kept
+};
+
+namespace pre3 {
+
+namespace {
+
+constexpr int ST = 16;              // tile edge of k_sr_condition
+constexpr int SH = ST + 2;          // ... with its halo
+constexpr int MB = 1024;            // threads of k_sr_maxima's one workgroup
+constexpr int KB = 256;             // keypoints (and threads) per workgroup of k_sr_keypoints
+constexpr int KW = KB / 64;
+static_assert(PRE3_SR_MAX_KEYPOINTS % KB == 0 && PRE3_SR_MAX_KEYPOINTS / KB == 32, "32 predicate batches per workgroup at the cap");
+
+struct SrWeights { double w[9]; };
+
+__global__ __launch_bounds__(MB) void k_sr_maxima(int npix, const double *__restrict__ amp, const double *__restrict__ conf /* null: none */,
+                                                  double *__restrict__ out /* imax, cmax */)
+{
+    __shared__ double s_a[MB / 64], s_c[MB / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double a = 0.0, c = NAN;
+    for (int i = tid; i < npix; i += MB) {
+        const double v = amp[i];
+        if (v <= SR_SATURATED && v > a) a = v;               // read_image_sr4000.m:12-17: saturated pixels count as 0
+        if (conf != nullptr) c = sr_nanmax(c, conf[i]);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double a2 = __shfl_xor(a, o, 64), c2 = __shfl_xor(c, o, 64);
+        a = a2 > a ? a2 : a;
+        c = sr_nanmax(c, c2);
+    }
+    if (lane == 0) { s_a[wave] = a; s_c[wave] = c; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < MB / 64; ++w) { a = s_a[w] > a ? s_a[w] : a; c = sr_nanmax(c, s_c[w]); }
+        out[0] = a; out[1] = c;
+    }
+}
+
+__global__ __launch_bounds__(ST * ST) void k_sr_condition(int rows, int cols, int mode, SrWeights W, const double *__restrict__ raw,
+                                                          const double *__restrict__ maxima, double *__restrict__ filt)
+{
+    __shared__ double s_p[4][SH * SH];                       // x, y, z, uint8 image; [lc * SH + lr]
+    const size_t npix = (size_t)rows * cols;
+    const double *Z = raw, *X = raw + npix, *Y = raw + 2 * npix, *A = raw + 3 * npix;
+    const int tid = threadIdx.x, r0 = blockIdx.x * ST, c0 = blockIdx.y * ST;
+    const double imax = maxima[0];
+    for (int i = tid; i < SH * SH; i += ST * ST) {
+        const int lr = i % SH, lc = i / SH;
+        int gr = r0 + lr - 1, gc = c0 + lc - 1;
+        const bool inside = gr >= 0 && gr < rows && gc >= 0 && gc < cols;
+        double x = 0.0, y = 0.0, z = 0.0, u = 0.0;           // mode 0: imfilter(.., 'same') pads with zeros (the uint8 image too)
+        if (inside || mode == 1) {                           // mode 1: 'replicate' reads the nearest edge pixel
+            gr = min(max(gr, 0), rows - 1); gc = min(max(gc, 0), cols - 1);
+            const size_t g = (size_t)gc * rows + gr;
+            x = X[g]; y = Y[g]; z = Z[g]; u = sr_norm_pixel(A[g], imax);
+        }
+        s_p[0][i] = x; s_p[1][i] = y; s_p[2][i] = z; s_p[3][i] = u;
+    }
+    __syncthreads();
+    const int tr = tid % ST, tc = tid / ST, r = r0 + tr, c = c0 + tc;
+    if (r >= rows || c >= cols) return;
+    const size_t g = (size_t)c * rows + r;
+#pragma unroll
+    for (int pl = 0; pl < 4; ++pl) {
+        double p[9];
+#pragma unroll
+        for (int dj = 0; dj < 3; ++dj)
+#pragma unroll
+            for (int di = 0; di < 3; ++di) p[3 * dj + di] = s_p[pl][(tc + dj) * SH + tr + di];
+        const double v = sr_tap9(W.w, p);
+        filt[pl * npix + g] = pl == 3 ? matlab_uint8(v) : v;  // imfilter on a uint8 image returns uint8
+    }
+}
+
+struct KpArgs {
+    int K, ldf, ND, gate, rows, cols, has_conf;
+    const double *frm, *des;                                 // [K][ldf], [K][ND]
+    const double *xf, *yf, *zf, *conf, *maxima;
+    int32_t *n_kept, *keep_idx;
+    double *frm_out, *des_out, *xyz_out, *rho_out;
+};
+
+// n doubles by one wave; 16-byte accesses when both ends are 16-byte aligned and n is even
+__device__ inline void wave_copy(double *__restrict__ dst, const double *__restrict__ src, int n, int lane)
+{
+    if ((((uintptr_t)dst | (uintptr_t)src) & 15) == 0 && (n & 1) == 0) {
+        const double2 *s2 = (const double2 *)src;
+        double2 *d2 = (double2 *)dst;
+        for (int i = lane; i < n / 2; i += 64) d2[i] = s2[i];
+    } else {
+        for (int i = lane; i < n; i += 64) dst[i] = src[i];
+    }
+}
+
+// the pixel of keypoint k (0-based, column-major offset).  The host has checked that it lies inside the image; the clamp changes no valid position and
+// keeps the gather inside the planes whatever the block holds
+__device__ inline size_t kp_pixel(const KpArgs &a, int k)
+{
+    const double u = a.frm[(size_t)k * a.ldf], v = a.frm[(size_t)k * a.ldf + 1];      // row 1: the pixel column, row 2: the pixel row, both 1-based
+    const int r = min(max((int)matlab_round(v) - 1, 0), a.rows - 1), c = min(max((int)matlab_round(u) - 1, 0), a.cols - 1);
+    return (size_t)c * a.rows + r;
+}
+
+__device__ inline bool kp_keep(const KpArgs &a, int k, double cmax)
+{
+    const size_t g = kp_pixel(a, k);
+    if (a.gate == 1) return sr_gate_confidence(a.conf[g], cmax);
+    const double xf = a.xf[g];
+    return sr_gate_depth(xf, sr_range(xf, a.yf[g], a.zf[g]), a.has_conf != 0, a.has_conf ? a.conf[g] : 0.0, cmax);
+}
+
+__global__ __launch_bounds__(KB) void k_sr_keypoints(KpArgs a)
+{
+    __shared__ int s_base[KW], s_cnt[KW], s_k[KB];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double cmax = a.maxima[1];
+    // the base offset: how many of the keypoints in front of this workgroup's are kept
+    int before = 0;
+    for (int b = 0; b < (int)blockIdx.x; ++b) before += __popcll(__ballot(kp_keep(a, b * KB + tid, cmax)));      // (earlier batches are full)
+    const int k = blockIdx.x * KB + tid;
+    const bool keep = k < a.K && kp_keep(a, k, cmax);
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) { s_base[wave] = before; s_cnt[wave] = __popcll(bal); }
+    __syncthreads();
+    int base = 0, off = 0, n_local = 0;
+    for (int w = 0; w < KW; ++w) { base += s_base[w]; if (w < wave) off += s_cnt[w]; n_local += s_cnt[w]; }
+    if (keep) s_k[off + __popcll(bal & ((1ull << lane) - 1ull))] = k;
+    __syncthreads();
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) *a.n_kept = base + n_local;
+    // one wave per kept keypoint, in the caller's order
+    for (int j = wave; j < n_local; j += KW) {
+        const int kk = s_k[j], slot = base + j;
+        wave_copy(a.frm_out + (size_t)slot * a.ldf, a.frm + (size_t)kk * a.ldf, a.ldf, lane);
+        if (a.ND > 0) wave_copy(a.des_out + (size_t)slot * a.ND, a.des + (size_t)kk * a.ND, a.ND, lane);
+        if (lane == 0) a.keep_idx[slot] = kk;
+        if (a.gate == 0 && lane < 4) {
+            const size_t g = kp_pixel(a, kk);
+            const double xf = a.xf[g], yf = a.yf[g], zf = a.zf[g];
+            if (lane < 3) a.xyz_out[3 * (size_t)slot + lane] = lane == 0 ? -xf : (lane == 1 ? -yf : zf);      // inittialize_depth_my_version.m:85
+            else a.rho_out[slot] = 1.0 / sr_range(xf, yf, zf);                                                  // :87-92 (norm restated as df)
+        }
+    }
+}
+
+static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+static int sr_device(const char *who, int device)
+{
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("%s: no HIP device available (libpre3 has no CPU fallback)", who); return PRE3_E_NODEVICE; }
+    if (hipSetDevice(device) != hipSuccess) { set_error("%s: no HIP device %d", who, device); return PRE3_E_NODEVICE; }
+    return PRE3_OK;
+}
+
+// Device memory of the handle, zeroed ON THE HANDLE'S STREAM: the stream does not synchronise with the null stream (hipStreamNonBlocking), so a
+// hipMemset there -- asynchronous to the host -- could land behind the first transfer queued into the block.
+static int sr_dmalloc(pre3_sr_frame *f, void **p, size_t bytes)
+{
+    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; set_error("hipMalloc of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
+    PRE3_HIP(hipMemsetAsync(*p, 0, bytes, f->stream));
+    return PRE3_OK;
+}
+
+static int sr_grow_stage(pre3_sr_frame *f, size_t bytes)
+{
+    if (f->stage_bytes >= bytes) return PRE3_OK;
+    if (f->stage) (void)hipHostFree(f->stage);
+    f->stage = nullptr; f->stage_bytes = 0;
+    const size_t cap = (bytes + 65535) & ~(size_t)65535;
+    PRE3_HIP(hipHostMalloc(&f->stage, cap, hipHostMallocDefault));
+    f->stage_bytes = cap;
+    return PRE3_OK;
+}
+
+}  // namespace
+
+int sr_frame_view(pre3_sr_frame *f, SrFrameView *v)
+{
+    PRE3_CHECK(f != nullptr && v != nullptr, PRE3_E_ARG, "sr_frame_view: null argument");
+    PRE3_CHECK(f->loaded, PRE3_E_STATE, "sr_frame_view: no frame has been loaded");
+    const size_t npix = (size_t)f->rows * f->cols;
+    v->device = f->device; v->rows = f->rows; v->cols = f->cols; v->mode = f->mode; v->has_conf = f->has_conf;
+    v->x = f->filt; v->y = f->filt + npix; v->z = f->filt + 2 * npix; v->img = f->filt + 3 * npix;
+    v->conf = f->has_conf ? f->raw + 4 * npix : nullptr;
+    v->maxima = f->maxima; v->stream = f->stream;
+    return PRE3_OK;
+}
+
+}  // namespace pre3
+
+using namespace pre3;
+
+extern "C" {
+
+int pre3_sr_gauss3(double sigma, double w[9])
+{
+    PRE3_CHECK(w != nullptr && sigma > 0.0 && std::isfinite(sigma), PRE3_E_ARG, "pre3_sr_gauss3: sigma must be positive and finite, w non-null");
+    sr_gauss3(sigma, w);
+    return PRE3_OK;
+}
+
+int pre3_sr_frame_destroy(pre3_sr_frame *f)
+{
+    if (f == nullptr) return PRE3_OK;
+    (void)hipSetDevice(f->device);
+    if (f->stream) { (void)hipStreamSynchronize(f->stream); (void)hipStreamDestroy(f->stream); }
+    if (f->raw) (void)hipFree(f->raw);
+    if (f->filt) (void)hipFree(f->filt);
+    if (f->maxima) (void)hipFree(f->maxima);
+    if (f->kp) (void)hipFree(f->kp);
+    if (f->stage) (void)hipHostFree(f->stage);
+    if (f->pinned_n) (void)hipHostFree(f->pinned_n);
+    delete f;
+    return PRE3_OK;
+}
+
+static int sr_create_buffers(pre3_sr_frame *f)
+{
+    const size_t npix = (size_t)f->rows * f->cols;
+    PRE3_HIP(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    PRE3_TRY(sr_dmalloc(f, (void **)&f->raw, sizeof(double) * 5 * npix));
+    PRE3_TRY(sr_dmalloc(f, (void **)&f->filt, sizeof(double) * 4 * npix));
+    PRE3_TRY(sr_dmalloc(f, (void **)&f->maxima, sizeof(double) * 2));
+    PRE3_HIP(hipHostMalloc((void **)&f->pinned_n, 64, hipHostMallocDefault));
+    return sr_grow_stage(f, sizeof(double) * 5 * npix);
+}
+
+int pre3_sr_frame_create(pre3_sr_frame **out, int device, int rows, int cols)
+{
+    PRE3_CHECK(out != nullptr, PRE3_E_ARG, "pre3_sr_frame_create: null argument");
+    *out = nullptr;
+    PRE3_CHECK(rows >= 1 && cols >= 1 && (long long)rows * cols <= (1ll << 26), PRE3_E_ARG, "pre3_sr_frame_create: a %d x %d frame", rows, cols);
+    PRE3_TRY(sr_device("pre3_sr_frame_create", device));
+    pre3_sr_frame *f = new pre3_sr_frame;
+    f->device = device; f->rows = rows; f->cols = cols;
+    const int rc = sr_create_buffers(f);
+    if (rc != PRE3_OK) { (void)pre3_sr_frame_destroy(f); return rc; }
+    *out = f;
+    return PRE3_OK;
+}
+
+int pre3_sr_frame_load(pre3_sr_frame *f, int mode, const double *z, const double *x, const double *y, const double *amp, const double *conf)
+{
+    PRE3_CHECK(f != nullptr && z != nullptr && x != nullptr && y != nullptr && amp != nullptr, PRE3_E_ARG, "pre3_sr_frame_load: null argument");
+    PRE3_CHECK(mode == 0 || mode == 1, PRE3_E_ARG, "pre3_sr_frame_load: mode %d is neither 0 (read_xyz_sr4000) nor 1 (read_sr4000_data_dr_ye)", mode);
+    const size_t npix = (size_t)f->rows * f->cols;
+    for (size_t i = 0; i < npix; ++i)                         // MATLAB's sqrt of a negative amplitude goes complex
+        PRE3_CHECK(std::isfinite(amp[i]) && amp[i] >= 0.0, PRE3_E_ARG, "pre3_sr_frame_load: the amplitude at row %d, column %d is negative or not finite",
+                   (int)(i % f->rows) + 1, (int)(i / f->rows) + 1);
+    PRE3_TRY(sr_device("pre3_sr_frame_load", f->device));
+    PRE3_HIP(hipStreamSynchronize(f->stream));                // the staging block may still be the source of the previous load's transfer
+    double *st = (double *)f->stage;
+    memcpy(st, z, sizeof(double) * npix); memcpy(st + npix, x, sizeof(double) * npix); memcpy(st + 2 * npix, y, sizeof(double) * npix);
+    memcpy(st + 3 * npix, amp, sizeof(double) * npix);
+    if (conf != nullptr) memcpy(st + 4 * npix, conf, sizeof(double) * npix);
+    f->loaded = 0;
+    PRE3_HIP(hipMemcpyAsync(f->raw, st, sizeof(double) * (conf != nullptr ? 5 : 4) * npix, hipMemcpyHostToDevice, f->stream));
+    hipLaunchKernelGGL(k_sr_maxima, dim3(1), dim3(MB), 0, f->stream, (int)npix, (const double *)(f->raw + 3 * npix),
+                       conf != nullptr ? (const double *)(f->raw + 4 * npix) : (const double *)nullptr, f->maxima);
+    PRE3_HIP(hipGetLastError());
+    SrWeights W;
+    sr_gauss3(mode == 0 ? 2.0 : 1.0, W.w);
+    hipLaunchKernelGGL(k_sr_condition, dim3(ceil_div(f->rows, ST), ceil_div(f->cols, ST)), dim3(ST * ST), 0, f->stream, f->rows, f->cols, mode, W,
+                       (const double *)f->raw, (const double *)f->maxima, f->filt);
+    PRE3_HIP(hipGetLastError());
+    f->mode = mode; f->has_conf = conf != nullptr ? 1 : 0; f->loaded = 1;
+    return PRE3_OK;
+}
+
+int pre3_sr_frame_get(pre3_sr_frame *f, double *x, double *y, double *z, double *img, double *conf, double *imax, double *cmax)
+{
+    PRE3_CHECK(f != nullptr, PRE3_E_ARG, "pre3_sr_frame_get: null handle");
+    PRE3_CHECK(f->loaded, PRE3_E_STATE, "pre3_sr_frame_get: no frame has been loaded");
+    PRE3_CHECK(conf == nullptr || f->has_conf, PRE3_E_ARG, "pre3_sr_frame_get: the frame was loaded without a confidence map");
+    PRE3_TRY(sr_device("pre3_sr_frame_get", f->device));
+    const size_t npix = (size_t)f->rows * f->cols, nb = sizeof(double) * npix;
+    double mx[2];
+    if (x) PRE3_HIP(hipMemcpyAsync(x, f->filt, nb, hipMemcpyDeviceToHost, f->stream));
+    if (y) PRE3_HIP(hipMemcpyAsync(y, f->filt + npix, nb, hipMemcpyDeviceToHost, f->stream));
+    if (z) PRE3_HIP(hipMemcpyAsync(z, f->filt + 2 * npix, nb, hipMemcpyDeviceToHost, f->stream));
+    if (img) PRE3_HIP(hipMemcpyAsync(img, f->filt + 3 * npix, nb, hipMemcpyDeviceToHost, f->stream));
+    if (conf) PRE3_HIP(hipMemcpyAsync(conf, f->raw + 4 * npix, nb, hipMemcpyDeviceToHost, f->stream));
+    if (imax || cmax) PRE3_HIP(hipMemcpyAsync(mx, f->maxima, sizeof mx, hipMemcpyDeviceToHost, f->stream));
+    PRE3_HIP(hipStreamSynchronize(f->stream));
+    if (imax) *imax = mx[0];
+    if (cmax) *cmax = mx[1];
+    return PRE3_OK;
+}
+
+int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K, const double *frm, int ND, const double *des, int32_t *n_kept, int32_t *keep_idx,
+                            double *frm_out, double *des_out, double *xyz_out, double *rho_out)
+{
+    PRE3_CHECK(f != nullptr && n_kept != nullptr, PRE3_E_ARG, "pre3_sr_frame_keypoints: null argument");
+    PRE3_CHECK(gate == 0 || gate == 1, PRE3_E_ARG, "pre3_sr_frame_keypoints: gate %d is neither 0 (depth) nor 1 (confidence)", gate);
+    PRE3_CHECK(K >= 0 && K <= PRE3_SR_MAX_KEYPOINTS, PRE3_E_ARG, "pre3_sr_frame_keypoints: K=%d outside [0, %d]", K, PRE3_SR_MAX_KEYPOINTS);
+    PRE3_CHECK(ldf >= 2 && ldf <= 4096, PRE3_E_ARG, "pre3_sr_frame_keypoints: ldf=%d (a frame holds at least the pixel column and row)", ldf);
+    PRE3_CHECK(ND >= 0 && ND <= 4096, PRE3_E_ARG, "pre3_sr_frame_keypoints: ND=%d", ND);
+    PRE3_CHECK(K == 0 || (frm != nullptr && (ND == 0 || des != nullptr)), PRE3_E_ARG, "pre3_sr_frame_keypoints: null frames or descriptors");
+    PRE3_CHECK(f->loaded, PRE3_E_STATE, "pre3_sr_frame_keypoints: no frame has been loaded");
+    PRE3_CHECK(gate == 0 || f->has_conf, PRE3_E_ARG, "pre3_sr_frame_keypoints: gate 1 needs the confidence map (the frame was loaded without one)");
+    for (int k = 0; k < K; ++k) {                             // MATLAB would raise an index error
+        const double u = frm[(size_t)k * ldf], v = frm[(size_t)k * ldf + 1];
+        PRE3_CHECK(std::isfinite(u) && std::isfinite(v), PRE3_E_ARG, "pre3_sr_frame_keypoints: the position of keypoint %d is not finite", k);
+        const double r = matlab_round(v), c = matlab_round(u);
+        PRE3_CHECK(r >= 1.0 && r <= (double)f->rows && c >= 1.0 && c <= (double)f->cols, PRE3_E_ARG,
+                   "pre3_sr_frame_keypoints: keypoint %d rounds to row %.0f, column %.0f outside the %d x %d frame", k, r, c, f->rows, f->cols);
+    }
+    PRE3_TRY(sr_device("pre3_sr_frame_keypoints", f->device));
+    *n_kept = 0;
+    if (K == 0) return PRE3_OK;
+    // [frm | des] up; [frm_out | des_out | xyz | rho | keep_idx | n_kept] behind them
+    const size_t b_frm = up16(sizeof(double) * (size_t)K * ldf), b_des = up16(sizeof(double) * (size_t)K * ND);
+    const size_t o_frm_out = b_frm + b_des, o_des_out = o_frm_out + b_frm, o_xyz = o_des_out + b_des, o_rho = o_xyz + up16(sizeof(double) * 3 * (size_t)K);
+    const size_t o_idx = o_rho + up16(sizeof(double) * (size_t)K), o_n = o_idx + up16(sizeof(int32_t) * (size_t)K), total = o_n + 16;
+    PRE3_HIP(hipStreamSynchronize(f->stream));                // the staging block and the keypoint block are free again
+    if (f->kp_bytes < total) {
+        if (f->kp) (void)hipFree(f->kp);
+        f->kp = nullptr; f->kp_bytes = 0;
+        PRE3_TRY(sr_dmalloc(f, &f->kp, total + total / 4));
+        f->kp_bytes = total + total / 4;
+    }
+    PRE3_TRY(sr_grow_stage(f, b_frm + b_des));
+    memcpy(f->stage, frm, sizeof(double) * (size_t)K * ldf);
+    if (ND > 0) memcpy((char *)f->stage + b_frm, des, sizeof(double) * (size_t)K * ND);
+    char *d = (char *)f->kp;
+    PRE3_HIP(hipMemcpyAsync(d, f->stage, b_frm + b_des, hipMemcpyHostToDevice, f->stream));
+    const size_t npix = (size_t)f->rows * f->cols;
+    KpArgs a;
+    a.K = K; a.ldf = ldf; a.ND = ND; a.gate = gate; a.rows = f->rows; a.cols = f->cols; a.has_conf = f->has_conf;
+    a.frm = (const double *)d; a.des = (const double *)(d + b_frm);
+    a.xf = f->filt; a.yf = f->filt + npix; a.zf = f->filt + 2 * npix; a.conf = f->raw + 4 * npix; a.maxima = f->maxima;
+    a.n_kept = (int32_t *)(d + o_n); a.keep_idx = (int32_t *)(d + o_idx);
+    a.frm_out = (double *)(d + o_frm_out); a.des_out = (double *)(d + o_des_out); a.xyz_out = (double *)(d + o_xyz); a.rho_out = (double *)(d + o_rho);
+    hipLaunchKernelGGL(k_sr_keypoints, dim3(ceil_div(K, KB)), dim3(KB), 0, f->stream, a);
+    PRE3_HIP(hipGetLastError());
+    PRE3_HIP(hipMemcpyAsync(f->pinned_n, a.n_kept, sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+    PRE3_HIP(hipStreamSynchronize(f->stream));
+    const int n = *f->pinned_n;
+    PRE3_CHECK(n >= 0 && n <= K, PRE3_E_HIP, "pre3_sr_frame_keypoints: the device kept %d of %d keypoints", n, K);
+    *n_kept = n;
+    if (n == 0) return PRE3_OK;
+    if (keep_idx) PRE3_HIP(hipMemcpyAsync(keep_idx, a.keep_idx, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, f->stream));
+    if (frm_out) PRE3_HIP(hipMemcpyAsync(frm_out, a.frm_out, sizeof(double) * (size_t)n * ldf, hipMemcpyDeviceToHost, f->stream));
+    if (des_out && ND > 0) PRE3_HIP(hipMemcpyAsync(des_out, a.des_out, sizeof(double) * (size_t)n * ND, hipMemcpyDeviceToHost, f->stream));
+    if (xyz_out && gate == 0) PRE3_HIP(hipMemcpyAsync(xyz_out, a.xyz_out, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, f->stream));
+    if (rho_out && gate == 0) PRE3_HIP(hipMemcpyAsync(rho_out, a.rho_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, f->stream));
+    PRE3_HIP(hipStreamSynchronize(f->stream));
+    return PRE3_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,169 @@
+"""The SR4000 frame conditioned on the device: the .dat reader, the resident frame handle and mirrors of the reference's
+readers and keypoint filters over the C ABI.
+
+    read_xyz_sr4000.m:8-21                                   -> read_xyz_sr4000        (sigma = 2, zero padding)
+    read_image_sr4000.m:10-24, normalzie_image.m:4           -> read_image_sr4000
+    code_from_dr_ye/read_sr4000_data_dr_ye.m:8-90            -> read_sr4000_data_dr_ye (sigma = 1, replicated border)
+    code_from_dr_ye/confidence_filtering.m:1-13              -> confidence_filtering
+    SIFT_extract_save.m:68-88 over inittialize_depth_my_version.m:16-92 -> sift_extract (the SCAN_SIFT dict scanio.save_sift_result writes)
+
+All compute runs in libpre3.so on the GPU; this module reads the text file and marshals numpy arrays.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import Pre3Error, check, dptr, f64, lib
+
+ROWS, COLS = 144, 176                     # a d1_%04d.dat frame
+MAX_KEYPOINTS = 8192                      # PRE3_SR_MAX_KEYPOINTS
+MODE_XYZ, MODE_DR_YE = 0, 1               # read_xyz_sr4000.m / read_image_sr4000.m; read_sr4000_data_dr_ye.m
+GATE_DEPTH, GATE_CONFIDENCE = 0, 1        # inittialize_depth_my_version.m:40,74; confidence_filtering.m:8
+
+
+def gauss3(sigma):
+    """fspecial('gaussian', [3 3], sigma) as the library forms it: (3, 3), G[i + 1, j + 1] = h(i, j)."""
+    w = np.zeros(9)
+    check(lib.pre3_sr_gauss3(float(sigma), dptr(w)))
+    return w.reshape(3, 3).T.copy()
+
+
+def load_dat(path, rows=ROWS):
+    """A d1_%04d.dat frame (numpy.loadtxt): rows 1-144 z, 145-288 x, 289-432 y, 433-576 amplitude, 577-720 confidence (when the file has them),
+    row 721 the timestamp in its first entry (when the file has it).  Returns dict(z, x, y, amp, conf or None, timestamp or -1)."""
+    a = np.loadtxt(path, dtype=np.float64, ndmin=2)
+    if a.shape[0] < 4 * rows:
+        raise ValueError("%s: %d rows, fewer than the %d of z, x, y and the amplitude" % (path, a.shape[0], 4 * rows))
+    out = {k: np.asfortranarray(a[i * rows:(i + 1) * rows]) for i, k in enumerate(("z", "x", "y", "amp"))}
+    out["conf"] = np.asfortranarray(a[4 * rows:5 * rows]) if a.shape[0] >= 5 * rows else None      # read_xyz_sr4000.m:25-34
+    out["timestamp"] = float(a[5 * rows, 0]) if a.shape[0] == 5 * rows + 1 else -1.0                # :36-42
+    return out
+
+
+class SrFrame:
+    """One resident, conditioned frame (pre3_sr_frame): load(planes, mode) queues the upload and the two conditioning launches and returns;
+    planes(), image(), maxima() and keypoints() wait for them."""
+
+    def __init__(self, rows=ROWS, cols=COLS, device=0):
+        self.rows, self.cols = int(rows), int(cols)
+        self._h = C.c_void_p()
+        self.has_conf = False
+        check(lib.pre3_sr_frame_create(C.byref(self._h), int(device), self.rows, self.cols))
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.pre3_sr_frame_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _plane(self, a, name):
+        a = np.asfortranarray(f64(a))
+        if a.shape != (self.rows, self.cols):
+            raise Pre3Error(-1, "SrFrame.load: %s is %s, the handle holds %d x %d frames" % (name, a.shape, self.rows, self.cols))
+        return a
+
+    def load(self, planes, mode=MODE_XYZ):
+        """planes: dict(z, x, y, amp, conf or None) as load_dat returns it; mode 0: sigma = 2, zero padding; 1: sigma = 1, replicate"""
+        p = [self._plane(planes[k], k) for k in ("z", "x", "y", "amp")]
+        conf = planes.get("conf")
+        conf = None if conf is None else self._plane(conf, "conf")
+        check(lib.pre3_sr_frame_load(self._h, int(mode), dptr(p[0]), dptr(p[1]), dptr(p[2]), dptr(p[3]), dptr(conf)))
+        self.has_conf = conf is not None
+        return self
+
+    def _new(self):
+        return np.zeros((self.rows, self.cols), order="F")
+
+    def planes(self):
+        """(x, y, z, confidence_map or None): the filtered planes, the confidence map as loaded"""
+        x, y, z = self._new(), self._new(), self._new()
+        conf = self._new() if self.has_conf else None
+        check(lib.pre3_sr_frame_get(self._h, dptr(x), dptr(y), dptr(z), None, dptr(conf), None, None))
+        return x, y, z, conf
+
+    def image(self):
+        """the filtered amplitude image, uint8"""
+        img = self._new()
+        check(lib.pre3_sr_frame_get(self._h, None, None, None, dptr(img), None, None, None))
+        return img.astype(np.uint8)
+
+    def maxima(self):
+        """(imax, cmax)"""
+        imax, cmax = C.c_double(0), C.c_double(0)
+        check(lib.pre3_sr_frame_get(self._h, None, None, None, None, None, C.byref(imax), C.byref(cmax)))
+        return imax.value, cmax.value
+
+    def keypoints(self, frm, des=None, gate=GATE_DEPTH):
+        """frm (ldf, K): SIFT frames, row 1 the pixel column, row 2 the pixel row (1-based); des (ND, K) or None.  Returns dict(keep_idx (0-based),
+        frames (ldf, n), descriptors (ND, n), and for gate 0 xyz (3, n) = [-x; -y; z] and rho (n,) = 1 / range)."""
+        frm = np.asfortranarray(f64(frm))
+        if frm.ndim != 2:
+            raise Pre3Error(-1, "SrFrame.keypoints: frm must be ldf x K")
+        ldf, K = frm.shape
+        des = np.zeros((0, K), order="F") if des is None else np.asfortranarray(f64(des))
+        if des.ndim != 2 or des.shape[1] != K:
+            raise Pre3Error(-1, "SrFrame.keypoints: des must be ND x K")
+        ND = des.shape[0]
+        n = C.c_int32(0)
+        Kb = min(max(K, 1), MAX_KEYPOINTS)
+        idx, frm_o, des_o = np.zeros(Kb, np.int32), np.zeros((ldf, Kb), order="F"), np.zeros((ND, Kb), order="F")
+        xyz, rho = np.zeros((3, Kb), order="F"), np.zeros(Kb)
+        check(lib.pre3_sr_frame_keypoints(self._h, int(gate), ldf, K, dptr(frm), ND, dptr(des), C.byref(n), dptr(idx), dptr(frm_o), dptr(des_o),
+                                          dptr(xyz), dptr(rho)))
+        n = n.value
+        out = dict(keep_idx=idx[:n].copy(), frames=frm_o[:, :n].copy(order="F"), descriptors=des_o[:, :n].copy(order="F"))
+        if int(gate) == GATE_DEPTH:
+            out["xyz"], out["rho"] = xyz[:, :n].copy(order="F"), rho[:n].copy()
+        return out
+
+
+def _conditioned(path, mode, device):
+    d = load_dat(path)
+    f = SrFrame(d["z"].shape[0], d["z"].shape[1], device).load(d, mode)
+    return d, f
+
+
+def read_xyz_sr4000(path, with_timestamp=False, device=0):
+    """[x, y, z, confidence_map (, timestamp)] = read_xyz_sr4000(...) on the file `path`; confidence_map is None for a frame without one"""
+    d, f = _conditioned(path, MODE_XYZ, device)
+    with f:
+        out = f.planes()
+    return out + (d["timestamp"],) if with_timestamp else out
+
+
+def read_image_sr4000(path, device=0):
+    """im = read_image_sr4000(...) on the file `path`: uint8"""
+    d, f = _conditioned(path, MODE_XYZ, device)
+    with f:
+        return f.image()
+
+
+def read_sr4000_data_dr_ye(path, with_timestamp=False, device=0):
+    """[x, y, z, confidence_map, img1 (, timestamp)] = read_sr4000_data_dr_ye(path).  Deviation: a frame without confidence rows gets the same
+    normalised image as one with them (the reference leaves it un-normalised, :34-59)."""
+    d, f = _conditioned(path, MODE_DR_YE, device)
+    with f:
+        out = f.planes() + (f.image(),)
+    return out + (d["timestamp"],) if with_timestamp else out
+
+
+def confidence_filtering(frm, des, frame):
+    """[frm, des] = confidence_filtering(frm, des, confidence_map), the map being the resident frame's"""
+    out = frame.keypoints(frm, des, GATE_CONFIDENCE)
+    return out["frames"], out["descriptors"]
+
+
+def sift_extract(frames, descriptors, frame, idx_scan, image=None):
+    """SIFT_extract_save.m:44-45,68-88: the SCAN_SIFT dict of scan idx_scan from its 1-based SIFT frames (4, K) (as :55-56 leave them) and descriptors
+    (128, K), the depth gate run on the resident frame.  image: SCAN_SIFT.Image (default: the frame's own)."""
+    out = frame.keypoints(frames, descriptors, GATE_DEPTH)
+    return dict(idxScan=int(idx_scan), Image=frame.image() if image is None else np.asarray(image),
+                Descriptor_RAW=np.array(descriptors, dtype=np.float64), SCALE_ORIENT_POS_RAW=np.array(frames, dtype=np.float64),
+                Descriptor=out["descriptors"], SCALE_ORIENT_POS=out["frames"], XYZ_DATA=out["xyz"], initial_rho=out["rho"], keep_idx=out["keep_idx"])

@@ -510,6 +510,54 @@ PRE3_API int pre3_map_policy_seeded(pre3_ctx *ctx, int step, int min_features, d
                                     uint64_t seed, uint64_t seq, int32_t *order_out, int32_t *del_out, int32_t *n_del_out,
                                     int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out, int32_t stats[4]);
 
+/* ---- the SR4000 frame conditioned on the device: filter, image, keypoint depth gate -------------------------------------------
+ * One handle holds one resident frame: the raw planes of a d1_%04d.dat scan, their 3 x 3 Gaussian-filtered x, y, z, the filtered uint8 amplitude image
+ * (stored as doubles holding 0 .. 255) and the two scalars imax (the largest amplitude <= 65000; 0 when every pixel is saturated) and cmax
+ * (max(confidence_map(:)): NaNs skipped, NaN only when every entry is NaN).  Planes are rows x cols, column-major, as pre3_plane_fit takes them; a .dat
+ * frame is 144 x 176, any size >= 1 x 1 is accepted.  The handle owns its stream, its device buffers and its pinned staging; it touches no pre3_ctx and
+ * no pooled scratch.  Calls on one handle must be serialised by the caller.  Results are bit-equal from run to run.
+ *   mode 0: read_xyz_sr4000.m:8-21 with read_image_sr4000.m:3,10-24 -- fspecial('gaussian', [3 3], 2), imfilter(.., 'same') (a tap outside the image
+ *           reads 0);
+ *   mode 1: code_from_dr_ye/read_sr4000_data_dr_ye.m:8,11-21,42,70,88-90 -- sigma = 1, imfilter(.., 'replicate') (the nearest edge pixel).
+ * A pixel is acc = w[0] p[0]; acc = acc + w[k] p[k], k = 1 .. 8, taps column-major, every product and sum rounded on its own; a NaN in the neighbourhood
+ * makes the pixel NaN.  The image: per tap uint8(sqrt(v) / sqrt(imax) * 255), v = imax where the amplitude is above 65000 (normalzie_image.m:4), the tap
+ * sum rounded and saturated again (imfilter on uint8).  uint8 is MATLAB's: half away from zero, saturated to [0, 255], NaN -> 0.
+ * Deviation: read_sr4000_data_dr_ye.m:34-59 leaves the image un-normalised when the frame has no confidence rows; here conf == NULL changes nothing in
+ * the image pipeline -- only gate 0 skips its confidence term and gate 1 is refused. */
+#define PRE3_SR_MAX_KEYPOINTS 8192
+typedef struct pre3_sr_frame pre3_sr_frame;
+/* fspecial('gaussian', [3 3], sigma) (read_xyz_sr4000.m:8, read_sr4000_data_dr_ye.m:8): w[3 (j + 1) + (i + 1)] = exp(-(i^2 + j^2) / (2 sigma^2)) over
+ * the sum of the nine values taken column-major -- the bits the conditioning launch uses.  Host only: needs no device. */
+PRE3_API int pre3_sr_gauss3(double sigma, double w[9]);
+PRE3_API int pre3_sr_frame_create(pre3_sr_frame **out, int device, int rows, int cols);
+PRE3_API int pre3_sr_frame_destroy(pre3_sr_frame *f);
+/* read_xyz_sr4000.m:10-21 / read_image_sr4000.m:10-24 / read_sr4000_data_dr_ye.m:11-21,27-29,88-90 on the five planes of a frame (conf may be NULL): one
+ * staged transfer, then the maxima launch and the conditioning launch queued on the handle's stream; returns without waiting.  PRE3_E_ARG before
+ * anything is launched, the previous frame left intact: a null plane, a mode other than 0 or 1, a negative or non-finite amplitude (MATLAB's sqrt
+ * would go complex). */
+PRE3_API int pre3_sr_frame_load(pre3_sr_frame *f, int mode, const double *z, const double *x, const double *y,
+                                const double *amp, const double *conf /* may be NULL */);
+/* the filtered x, y, z, the image, the confidence map as loaded, imax, cmax: any may be NULL; synchronises.  PRE3_E_STATE before the first load;
+ * conf != NULL on a frame loaded without one: PRE3_E_ARG. */
+PRE3_API int pre3_sr_frame_get(pre3_sr_frame *f, double *x, double *y, double *z, double *img, double *conf,
+                               double *imax, double *cmax);
+/* The keypoint stage on the resident frame.  frm[K][ldf]: one SIFT frame per keypoint (a column of SCALE_ORIENT_POS_RAW), entry 0 the pixel column,
+ * entry 1 the pixel row, both 1-based; the pixel is (round(row), round(column)), MATLAB rounding.  des[K][ND]: its descriptor (ND = 128 in the
+ * reference; ND == 0: none).
+ *   gate 0: SIFT_extract_save.m:71-88 over inittialize_depth_my_version.m:16,40-45,74-92 -- on the FILTERED planes: dropped when x is NaN, when
+ *           df = sqrt(x^2 + y^2 + z^2) < 0.4, or (with a confidence map) when conf <= 0.5 cmax; kept keypoints give xyz_out = [-x; -y; z] and
+ *           rho_out = 1 / df (the reference's norm([-x -y z]) restated as df).  A NaN y or z alone survives with NaN coordinates, as in the reference.
+ *   gate 1: code_from_dr_ye/confidence_filtering.m:1-13 -- dropped when conf < 0.5 cmax (strictly); needs the confidence map; xyz_out and rho_out
+ *           are not written.
+ * The kept keypoints keep the caller's order: keep_idx[n_kept] (0-based), frm_out[n_kept][ldf], des_out[n_kept][ND], xyz_out 3 x n_kept column-major
+ * (XYZ_DATA's layout), rho_out[n_kept]; each output except n_kept may be NULL.  Synchronises.  K == 0 launches nothing.  PRE3_E_ARG before anything is
+ * launched: a null handle, n_kept, frm or des; a gate other than 0 or 1; gate 1 without a confidence map; K outside 0 .. PRE3_SR_MAX_KEYPOINTS;
+ * ldf < 2 or ND < 0 (or either above 4096); a non-finite position, or one whose rounded pixel lies outside the image (MATLAB would raise an index
+ * error).  PRE3_E_STATE before the first load. */
+PRE3_API int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K, const double *frm, int ND, const double *des,
+                                     int32_t *n_kept, int32_t *keep_idx, double *frm_out, double *des_out,
+                                     double *xyz_out /* 3 x n_kept, gate 0 */, double *rho_out);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them

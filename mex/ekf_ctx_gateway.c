@@ -17,6 +17,8 @@
  *   mono_slam.m:189-193             applied = pre3_mex('plane_heading', x_sr, y_sr, z_sr, draws, 1)   % plane_fit_to_data + ekf_heading_update on the device
  *   map_management.m:27-79          [del, acc] = pre3_mex('map_policy', step, UV, XYZ, DESC, 50, 0.1, std_z, 1)   % policy on the device; pre3_mex('set_book', B) first
  *   Weighted_Smpl_wo_replacement.m  [del, acc, cv, st, order] = pre3_mex('map_policy_seeded', step, UV, XYZ, DESC, 50, 0.1, std_z, 1, [176 144], seed, step)   % ... and its draw
+ *   read_xyz_sr4000.m, read_image_sr4000.m, read_sr4000_data_dr_ye.m   [x, y, z, img, imax, cmax] = pre3_mex('sr_frame', mode, z, x, y, amp, conf)   % conf = [] for none; the frame stays resident
+ *   SIFT_extract_save.m:71-88, confidence_filtering.m                  [frm, des, idx, xyz, rho] = pre3_mex('sr_keypoints', gate, frames, descriptors)    % on the resident frame; no filter context needed
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
  * corrcoef_partitioned_mex.c:25-57).  NOT compiled in the build container (no MATLAB / mex.h there).
@@ -26,7 +28,10 @@
 #include "pre3.h"
 
 static pre3_ctx *g_ctx = NULL;
+static pre3_sr_frame *g_sr = NULL;          /* the resident SR4000 frame of 'sr_frame' / 'sr_keypoints' */
+static int g_sr_rows = 0, g_sr_cols = 0;
 static void at_exit(void) { if (g_ctx) { pre3_destroy(g_ctx); g_ctx = NULL; } }
+static void sr_at_exit(void) { if (g_sr) { pre3_sr_frame_destroy(g_sr); g_sr = NULL; } at_exit(); }
 static void check(int rc) { if (rc != PRE3_OK) mexErrMsgTxt(pre3_last_error()); }
 
 void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
@@ -40,10 +45,46 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         mxGetString(in[3], dt, sizeof dt);
         at_exit();
         check(pre3_create(&g_ctx, 0, !strcmp(dt, "f64") ? PRE3_F64 : PRE3_F32, N, (int)mxGetScalar(in[4])));
-        mexAtExit(at_exit); if (!mexIsLocked()) mexLock();
+        mexAtExit(sr_at_exit); if (!mexIsLocked()) mexLock();
         t = (int32_t *)mxMalloc(sizeof(int32_t) * (N ? N : 1));
         for (i = 0; i < N; ++i) t[i] = (int32_t)mxGetPr(in[2])[i];
         check(pre3_set_cam(g_ctx, &cam)); check(pre3_set_map(g_ctx, N, t)); mxFree(t);
+        return;
+    }
+    if (!strcmp(cmd, "sr_frame")) {          /* [x, y, z, img, imax, cmax] = pre3_mex('sr_frame', mode (0: read_xyz_sr4000 / read_image_sr4000, 1: read_sr4000_data_dr_ye),
+                                                 z, x, y, amp, conf ([]: none)): the planes of a .dat frame conditioned on the device; img is double 0..255 */
+        int rows, cols, i; double imax = 0, cmax = 0;
+        if (nin != 7) mexErrMsgTxt("pre3_mex('sr_frame', mode, z, x, y, amp, conf): six arguments");
+        rows = (int)mxGetM(in[2]); cols = (int)mxGetN(in[2]);
+        for (i = 3; i < 7; ++i)
+            if (!(i == 6 && mxIsEmpty(in[6])) && ((int)mxGetM(in[i]) != rows || (int)mxGetN(in[i]) != cols)) mexErrMsgTxt("pre3_mex('sr_frame'): the planes must have the same size");
+        if (g_sr && (rows != g_sr_rows || cols != g_sr_cols)) { pre3_sr_frame_destroy(g_sr); g_sr = NULL; }
+        if (!g_sr) { check(pre3_sr_frame_create(&g_sr, 0, rows, cols)); g_sr_rows = rows; g_sr_cols = cols; mexAtExit(sr_at_exit); if (!mexIsLocked()) mexLock(); }
+        check(pre3_sr_frame_load(g_sr, (int)mxGetScalar(in[1]), mxGetPr(in[2]), mxGetPr(in[3]), mxGetPr(in[4]), mxGetPr(in[5]), mxIsEmpty(in[6]) ? NULL : mxGetPr(in[6])));
+        for (i = 0; i < 4; ++i) out[i] = mxCreateDoubleMatrix(rows, cols, mxREAL);
+        check(pre3_sr_frame_get(g_sr, mxGetPr(out[0]), mxGetPr(out[1]), mxGetPr(out[2]), mxGetPr(out[3]), NULL, &imax, &cmax));
+        out[4] = mxCreateDoubleScalar(imax); out[5] = mxCreateDoubleScalar(cmax);
+        (void)nout;
+        return;
+    }
+    if (!strcmp(cmd, "sr_keypoints")) {      /* [frm, des, idx (1-based), xyz, rho] = pre3_mex('sr_keypoints', gate (0: SIFT_extract_save.m:71-88 over inittialize_depth_my_version.m,
+                                                 1: confidence_filtering.m), frames (ldf x K, rows 1:2 = pixel column, row, 1-based), descriptors (ND x K or [])) */
+        int ldf, K, ND, gate, i; int32_t n = 0, *idx; double *f2, *d2, *xyz, *rho;
+        if (nin != 4) mexErrMsgTxt("pre3_mex('sr_keypoints', gate, frames, descriptors): three arguments");
+        if (!g_sr) mexErrMsgTxt("pre3_mex('sr_keypoints'): call pre3_mex('sr_frame', ...) first");
+        gate = (int)mxGetScalar(in[1]); ldf = (int)mxGetM(in[2]); K = (int)mxGetN(in[2]); ND = mxIsEmpty(in[3]) ? 0 : (int)mxGetM(in[3]);
+        if (ND > 0 && (int)mxGetN(in[3]) != K) mexErrMsgTxt("pre3_mex('sr_keypoints'): descriptors must be ND x K");
+        idx = (int32_t *)mxMalloc(sizeof(int32_t) * (K ? K : 1));
+        f2 = (double *)mxMalloc(sizeof(double) * (size_t)(K ? K : 1) * (ldf ? ldf : 1)); d2 = (double *)mxMalloc(sizeof(double) * (size_t)(K ? K : 1) * (ND ? ND : 1));
+        xyz = (double *)mxMalloc(sizeof(double) * 3 * (K ? K : 1)); rho = (double *)mxMalloc(sizeof(double) * (K ? K : 1));
+        check(pre3_sr_frame_keypoints(g_sr, gate, ldf, K, mxGetPr(in[2]), ND, ND ? mxGetPr(in[3]) : NULL, &n, idx, f2, d2, xyz, rho));
+        out[0] = mxCreateDoubleMatrix(ldf, n, mxREAL); memcpy(mxGetPr(out[0]), f2, sizeof(double) * (size_t)n * ldf);
+        out[1] = mxCreateDoubleMatrix(ND, n, mxREAL); memcpy(mxGetPr(out[1]), d2, sizeof(double) * (size_t)n * ND);
+        out[2] = mxCreateDoubleMatrix(1, n, mxREAL); for (i = 0; i < n; ++i) mxGetPr(out[2])[i] = idx[i] + 1;
+        out[3] = mxCreateDoubleMatrix(3, gate == 0 ? n : 0, mxREAL); out[4] = mxCreateDoubleMatrix(1, gate == 0 ? n : 0, mxREAL);
+        if (gate == 0) { memcpy(mxGetPr(out[3]), xyz, sizeof(double) * 3 * (size_t)n); memcpy(mxGetPr(out[4]), rho, sizeof(double) * (size_t)n); }
+        mxFree(idx); mxFree(f2); mxFree(d2); mxFree(xyz); mxFree(rho);
+        (void)nout;
         return;
     }
     if (!g_ctx) mexErrMsgTxt("pre3_mex: call pre3_mex('create', ...) first");
