@@ -8,6 +8,7 @@
 // stream reads; a table crosses PCIe only when the caller asks for it back.  The rules themselves are pre3_philox.h's __host__ __device__ functions.
 #include "pre3_internal.h"
 #include "pre3_philox.h"
+#include "pre3_vodev.h"
 
 namespace pre3 {
 
@@ -28,15 +29,7 @@ __global__ __launch_bounds__(DB) void k_draw_1p(uint64_t seed, uint64_t seq, int
 __global__ __launch_bounds__(DB) void k_draw_vo(uint64_t seed, uint64_t seq, int n_hyp, int pnum, const double *__restrict__ m1, const double *__restrict__ m2,
                                                 int ms, int32_t *__restrict__ draws, int32_t *__restrict__ capped)
 {
-    const int h = blockIdx.x * DB + threadIdx.x;
-    int cap = 0;
-    if (h < n_hyp) {
-        int32_t r[4];
-        cap = draw_rule_vo(seed, seq, pnum, m1, m2, ms, h, r);
-        *reinterpret_cast<int4 *>(draws + 4 * (size_t)h) = make_int4(r[0], r[1], r[2], r[3]);
-    }
-    const int n = __popcll(__ballot(cap != 0));         // (every lane of the wave reaches the ballot)
-    if (threadIdx.x == 0 && n) atomicAdd(capped, n);
+    vo_draw_lane(blockIdx.x * DB + threadIdx.x, seed, seq, n_hyp, pnum, m1, m2, ms, draws, capped);
 }
 
 __global__ __launch_bounds__(DB) void k_draw_plane(uint64_t seed, uint64_t seq, int n_draw, int npts, const double *__restrict__ pts, int32_t *__restrict__ draws)

@@ -391,6 +391,12 @@ struct SrFrameView {
     hipStream_t stream;
 };
 int sr_frame_view(pre3_sr_frame *f, SrFrameView *v);      /* PRE3_E_STATE before the first load */
+// the handle's last keypoint result (pre3_sr_frame_keypoints), which stays in its keypoint block: the kept frames [n_kept][ldf] and descriptors
+// [n_kept][ND] in the caller's order.  A load makes it stale; a keypoint call with K == 0, or one that fails behind its argument checks, leaves a valid
+// empty one (n_kept == 0, frm == des == nullptr).  PRE3_E_STATE when there is none or it is stale.
+struct SrKeypointView { int K, ldf, ND, gate, n_kept; const double *frm, *des; };
+int sr_frame_keypoint_view(pre3_sr_frame *f, SrKeypointView *v);
+int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, void **dev, void **pin, hipEvent_t *ev);      /* pre3_vopair.hip's blocks and event */
 
 // ---- map policy (pre3_map.hip): the rescue-visibility rider of a booked context (one small launch at the post-LI x_k_k), buffers
 int launch_book_vis(pre3_ctx *c);

@@ -30,6 +30,13 @@ struct pre3_sr_frame {
     void *kp = nullptr;             // device: the keypoint stage's input and output block
     size_t kp_bytes = 0;
     int32_t *pinned_n = nullptr;    // n_kept
+    // the last keypoint call's result, still in `kp` (sr_frame_keypoint_view): kp_valid 0 = none yet, or stale after a load
+    int kp_valid = 0, kp_K = 0, kp_ldf = 0, kp_ND = 0, kp_gate = 0, kp_n = 0;
+    size_t kp_o_frm = 0, kp_o_des = 0;      // offsets of frm_out / des_out inside kp
+    // the pair stage's work block, its pinned image and the event other streams wait for (pre3_vopair.hip), allocated on its first use
+    void *pair_dev = nullptr, *pair_pin = nullptr;
+    size_t pair_dev_bytes = 0, pair_pin_bytes = 0;
+    hipEvent_t pair_ev = nullptr;
 };
 
 namespace pre3 {
@@ -219,6 +226,41 @@ int sr_frame_view(pre3_sr_frame *f, SrFrameView *v)
     return PRE3_OK;
 }
 
+int sr_frame_keypoint_view(pre3_sr_frame *f, SrKeypointView *v)
+{
+    PRE3_CHECK(f != nullptr && v != nullptr, PRE3_E_ARG, "sr_frame_keypoint_view: null argument");
+    PRE3_CHECK(f->loaded && f->kp_valid, PRE3_E_STATE, "the frame holds no keypoint result (none yet, or a frame was loaded after it)");
+    v->K = f->kp_K; v->ldf = f->kp_ldf; v->ND = f->kp_ND; v->gate = f->kp_gate; v->n_kept = f->kp_n;
+    v->frm = f->kp_n > 0 ? (const double *)((const char *)f->kp + f->kp_o_frm) : nullptr;
+    v->des = f->kp_n > 0 ? (const double *)((const char *)f->kp + f->kp_o_des) : nullptr;
+    return PRE3_OK;
+}
+
+// dev_bytes of device memory and pin_bytes of pinned host memory owned by the handle, grown on demand; a new device block is zeroed on the handle's stream
+// (sr_dmalloc's rule).  The caller has made sure that nothing queued still uses the old blocks.
+int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, void **dev, void **pin, hipEvent_t *ev)
+{
+    PRE3_CHECK(f != nullptr, PRE3_E_ARG, "sr_frame_pair_work: null handle");
+    if (f->pair_ev == nullptr) PRE3_HIP(hipEventCreateWithFlags(&f->pair_ev, hipEventDisableTiming));
+    if (f->pair_dev_bytes < dev_bytes) {
+        if (f->pair_dev) (void)hipFree(f->pair_dev);
+        f->pair_dev = nullptr; f->pair_dev_bytes = 0;
+        PRE3_TRY(sr_dmalloc(f, &f->pair_dev, dev_bytes + dev_bytes / 4));
+        f->pair_dev_bytes = dev_bytes + dev_bytes / 4;
+    }
+    if (f->pair_pin_bytes < pin_bytes) {
+        if (f->pair_pin) (void)hipHostFree(f->pair_pin);
+        f->pair_pin = nullptr; f->pair_pin_bytes = 0;
+        const size_t cap = (pin_bytes + pin_bytes / 4 + 65535) & ~(size_t)65535;
+        PRE3_HIP(hipHostMalloc(&f->pair_pin, cap, hipHostMallocDefault));
+        f->pair_pin_bytes = cap;
+    }
+    if (dev) *dev = f->pair_dev;
+    if (pin) *pin = f->pair_pin;
+    if (ev) *ev = f->pair_ev;
+    return PRE3_OK;
+}
+
 }  // namespace pre3
 
 using namespace pre3;
@@ -243,6 +285,9 @@ int pre3_sr_frame_destroy(pre3_sr_frame *f)
     if (f->kp) (void)hipFree(f->kp);
     if (f->stage) (void)hipHostFree(f->stage);
     if (f->pinned_n) (void)hipHostFree(f->pinned_n);
+    if (f->pair_dev) (void)hipFree(f->pair_dev);
+    if (f->pair_pin) (void)hipHostFree(f->pair_pin);
+    if (f->pair_ev) (void)hipEventDestroy(f->pair_ev);
     delete f;
     return PRE3_OK;
 }
@@ -286,7 +331,7 @@ int pre3_sr_frame_load(pre3_sr_frame *f, int mode, const double *z, const double
     memcpy(st, z, sizeof(double) * npix); memcpy(st + npix, x, sizeof(double) * npix); memcpy(st + 2 * npix, y, sizeof(double) * npix);
     memcpy(st + 3 * npix, amp, sizeof(double) * npix);
     if (conf != nullptr) memcpy(st + 4 * npix, conf, sizeof(double) * npix);
-    f->loaded = 0;
+    f->loaded = 0; f->kp_valid = 0;                           // the keypoint record belongs to the frame that is being replaced
     PRE3_HIP(hipMemcpyAsync(f->raw, st, sizeof(double) * (conf != nullptr ? 5 : 4) * npix, hipMemcpyHostToDevice, f->stream));
     hipLaunchKernelGGL(k_sr_maxima, dim3(1), dim3(MB), 0, f->stream, (int)npix, (const double *)(f->raw + 3 * npix),
                        conf != nullptr ? (const double *)(f->raw + 4 * npix) : (const double *)nullptr, f->maxima);
@@ -320,8 +365,9 @@ int pre3_sr_frame_get(pre3_sr_frame *f, double *x, double *y, double *z, double 
     return PRE3_OK;
 }
 
-int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K, const double *frm, int ND, const double *des, int32_t *n_kept, int32_t *keep_idx,
-                            double *frm_out, double *des_out, double *xyz_out, double *rho_out)
+// touched: set once the call is past its checks -- from there on the keypoint block no longer holds the previous result
+static int sr_keypoints_impl(pre3_sr_frame *f, int gate, int ldf, int K, const double *frm, int ND, const double *des, int32_t *n_kept, int32_t *keep_idx,
+                             double *frm_out, double *des_out, double *xyz_out, double *rho_out, bool *touched)
 {
     PRE3_CHECK(f != nullptr && n_kept != nullptr, PRE3_E_ARG, "pre3_sr_frame_keypoints: null argument");
     PRE3_CHECK(gate == 0 || gate == 1, PRE3_E_ARG, "pre3_sr_frame_keypoints: gate %d is neither 0 (depth) nor 1 (confidence)", gate);
@@ -340,6 +386,8 @@ int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K, const do
     }
     PRE3_TRY(sr_device("pre3_sr_frame_keypoints", f->device));
     *n_kept = 0;
+    *touched = true;
+    f->kp_valid = 1; f->kp_K = K; f->kp_ldf = ldf; f->kp_ND = ND; f->kp_gate = gate; f->kp_n = 0;      // a valid empty record until the count is in
     if (K == 0) return PRE3_OK;
     // [frm | des] up; [frm_out | des_out | xyz | rho | keep_idx | n_kept] behind them
     const size_t b_frm = up16(sizeof(double) * (size_t)K * ldf), b_des = up16(sizeof(double) * (size_t)K * ND);
@@ -371,6 +419,7 @@ int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K, const do
     const int n = *f->pinned_n;
     PRE3_CHECK(n >= 0 && n <= K, PRE3_E_HIP, "pre3_sr_frame_keypoints: the device kept %d of %d keypoints", n, K);
     *n_kept = n;
+    f->kp_n = n; f->kp_o_frm = o_frm_out; f->kp_o_des = o_des_out;
     if (n == 0) return PRE3_OK;
     if (keep_idx) PRE3_HIP(hipMemcpyAsync(keep_idx, a.keep_idx, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, f->stream));
     if (frm_out) PRE3_HIP(hipMemcpyAsync(frm_out, a.frm_out, sizeof(double) * (size_t)n * ldf, hipMemcpyDeviceToHost, f->stream));
@@ -379,6 +428,15 @@ int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K, const do
     if (rho_out && gate == 0) PRE3_HIP(hipMemcpyAsync(rho_out, a.rho_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, f->stream));
     PRE3_HIP(hipStreamSynchronize(f->stream));
     return PRE3_OK;
+}
+
+int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K, const double *frm, int ND, const double *des, int32_t *n_kept, int32_t *keep_idx,
+                            double *frm_out, double *des_out, double *xyz_out, double *rho_out)
+{
+    bool touched = false;
+    const int rc = sr_keypoints_impl(f, gate, ldf, K, frm, ND, des, n_kept, keep_idx, frm_out, des_out, xyz_out, rho_out, &touched);
+    if (rc != PRE3_OK && touched) f->kp_n = 0;                // a call that failed behind its checks leaves a valid empty record
+    return rc;
 }
 
 }  // extern "C"

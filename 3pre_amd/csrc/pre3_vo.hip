@@ -10,139 +10,24 @@
 #include <vector>
 
 #include "pre3_internal.h"
+#include "pre3_vodev.h"
 
 namespace pre3 {
 
-struct VoOut {                 // device-side result block
-    double rot[9], trans[3], euler[3], u[7];
-    double error_mean, error_std, dist;
-    int32_t sta, n_support, n_iterations, best, dist_ok, pad[3];
-};
-
-// svd of a 3x3 by one-sided Jacobi; returns U, sv, V with H = U diag(sv) V'
-__device__ void vo_svd3(const double *H, double *U, double *sv, double *V)
-{
-#pragma clang fp contract(off)
-    double A[9];
-    for (int i = 0; i < 9; ++i) { A[i] = H[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; U[i] = 0.0; }
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        int rotated = 0;
-#pragma unroll
-        for (int pq = 0; pq < 3; ++pq) {
-            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-            double alpha = 0, beta = 0, gamma = 0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { alpha += A[3 * i + p] * A[3 * i + p]; beta += A[3 * i + q] * A[3 * i + q]; gamma += A[3 * i + p] * A[3 * i + q]; }
-            if (gamma == 0.0 || fabs(gamma) <= 2.2e-16 * sqrt(alpha * beta)) continue;
-            rotated = 1;
-            const double zeta = (beta - alpha) / (2.0 * gamma);
-            const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-            const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const double ap = A[3 * i + p], aq = A[3 * i + q];
-                A[3 * i + p] = c * ap - s * aq; A[3 * i + q] = s * ap + c * aq;
-                const double vp = V[3 * i + p], vq = V[3 * i + q];
-                V[3 * i + p] = c * vp - s * vq; V[3 * i + q] = s * vp + c * vq;
-            }
-        }
-        if (!rotated) break;
-    }
-    int ok[3];
-    double big = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { sv[j] = sqrt(A[j] * A[j] + A[3 + j] * A[3 + j] + A[6 + j] * A[6 + j]); big = sv[j] > big ? sv[j] : big; }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        ok[j] = sv[j] > 1e-300 && sv[j] > 1e-18 * big;
-        if (ok[j]) for (int i = 0; i < 3; ++i) U[3 * i + j] = A[3 * i + j] / sv[j];
-    }
-    const int nok = ok[0] + ok[1] + ok[2];
-    if (nok == 2) {                       // orthonormal completion for a zero singular value
-        const int j = !ok[0] ? 0 : (!ok[1] ? 1 : 2), a = (j + 1) % 3, b = (j + 2) % 3;
-        const double ua[3] = { U[a], U[3 + a], U[6 + a] }, ub[3] = { U[b], U[3 + b], U[6 + b] };
-        const double w[3] = { ua[1] * ub[2] - ua[2] * ub[1], ua[2] * ub[0] - ua[0] * ub[2], ua[0] * ub[1] - ua[1] * ub[0] };
-        for (int i = 0; i < 3; ++i) U[3 * i + j] = w[i];
-    } else if (nok < 2) {
-        for (int i = 0; i < 9; ++i) U[i] = (i % 4 == 0) ? 1.0 : 0.0;
-        if (nok == 1) {
-            const int j = ok[0] ? 0 : (ok[1] ? 1 : 2), a = (j + 1) % 3, b = (j + 2) % 3;
-            const double u[3] = { A[j] / sv[j], A[3 + j] / sv[j], A[6 + j] / sv[j] };
-            const int m = fabs(u[0]) < fabs(u[1]) ? (fabs(u[0]) < fabs(u[2]) ? 0 : 2) : (fabs(u[1]) < fabs(u[2]) ? 1 : 2);
-            double e[3] = { 0, 0, 0 }; e[m] = 1;
-            double w[3] = { u[1] * e[2] - u[2] * e[1], u[2] * e[0] - u[0] * e[2], u[0] * e[1] - u[1] * e[0] };
-            const double nw = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-            for (int i = 0; i < 3; ++i) w[i] /= nw;
-            const double x[3] = { u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0] };
-            for (int i = 0; i < 3; ++i) { U[3 * i + j] = u[i]; U[3 * i + a] = w[i]; U[3 * i + b] = x[i]; }
-        }
-    }
-}
-
-// find_transform_matrix_dr_ye.m:19-44 from the centroids and H
-__device__ int vo_solve(const double *H, const double *ct1, const double *ct2, double *rot, double *trans)
-{
-#pragma clang fp contract(off)
-    double U[9], sv[3], V[9], Xq[9];
-    vo_svd3(H, U, sv, V);
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Xq[3 * i + j] = V[3 * i] * U[3 * j] + V[3 * i + 1] * U[3 * j + 1] + V[3 * i + 2] * U[3 * j + 2];
-    const double mdet = Xq[0] * (Xq[4] * Xq[8] - Xq[5] * Xq[7]) - Xq[1] * (Xq[3] * Xq[8] - Xq[5] * Xq[6]) + Xq[2] * (Xq[3] * Xq[7] - Xq[4] * Xq[6]);
-    int state;
-    if (round(mdet) == 1) state = 1;
-    else if (round(mdet) == -1) {
-        int zn = -1, cnt = 0;
-        for (int j = 0; j < 3; ++j) if (fabs(sv[j]) < 0.00000000000001) { zn = j; ++cnt; }
-        if (cnt == 1) {
-            for (int i = 0; i < 3; ++i) V[3 * i + zn] = -V[3 * i + zn];
-            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Xq[3 * i + j] = V[3 * i] * U[3 * j] + V[3 * i + 1] * U[3 * j + 1] + V[3 * i + 2] * U[3 * j + 2];
-            state = 2;
-        } else state = -1;
-    } else state = 0;
-    if (state >= 1) {
-        for (int i = 0; i < 9; ++i) rot[i] = Xq[i];
-        for (int i = 0; i < 3; ++i) trans[i] = ct1[i] - (rot[3 * i] * ct2[0] + rot[3 * i + 1] * ct2[1] + rot[3 * i + 2] * ct2[2]);
-    } else {
-        for (int i = 0; i < 9; ++i) rot[i] = H[i];
-        trans[0] = trans[1] = trans[2] = 0;
-    }
-    return state;
-}
-
-// ransac_dr_ye.m:13-19 for one frame: pset(:,i) = [-x(ROW,COL); -y(ROW,COL); z(ROW,COL)]
+// ransac_dr_ye.m:13-19 for one frame
 __global__ void k_vo_gather(int rows, int cols, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
                             int ldf, const double *__restrict__ frm, int K, int pnum, const double *__restrict__ sel, int sel_stride,
                             double *__restrict__ pset, int32_t *__restrict__ bad)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= pnum) return;
-    const int k = (int)sel[(size_t)i * sel_stride] - 1;
-    if (k < 0 || k >= K) { atomicOr(bad, 1); return; }
-    const int COL = (int)round(frm[(size_t)ldf * k]), ROW = (int)round(frm[(size_t)ldf * k + 1]);
-    if (ROW < 1 || ROW > rows || COL < 1 || COL > cols) { atomicOr(bad, 2); return; }
-    const size_t o = (size_t)(COL - 1) * rows + (ROW - 1);
-    pset[3 * i] = -x[o]; pset[3 * i + 1] = -y[o]; pset[3 * i + 2] = z[o];
+    vo_gather_one(i, rows, cols, x, y, z, ldf, frm, K, sel, sel_stride, pset, bad);
 }
 
 // ransac_dr_ye.m:20-23 -- one wave
 __global__ void k_vo_dist(int pnum, const double *__restrict__ pset2, VoOut *__restrict__ out)
 {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x;
-    double mz = INFINITY;
-    for (int k = lane; k < pnum; k += 64) {
-        const double a = pset2[3 * k], b = pset2[3 * k + 1], c = pset2[3 * k + 2];
-        const double nr = sqrt(c * c + b * b + a * a);
-        if (nr > 0.4 && c < mz) mz = c;
-    }
-    for (int o = 32; o > 0; o >>= 1) { const double v = __shfl_xor(mz, o, 64); mz = v < mz ? v : mz; }
-    int first = 0x7fffffff;
-    for (int k = lane; k < pnum; k += 64) if (pset2[3 * k + 2] == mz && k < first) first = k;
-    for (int o = 32; o > 0; o >>= 1) { const int v = __shfl_xor(first, o, 64); first = v < first ? v : first; }
-    if (lane == 0) {
-        const bool ok = mz < INFINITY && first < pnum;
-        out->dist_ok = ok;
-        out->dist = ok ? sqrt(pset2[3 * first] * pset2[3 * first] + pset2[3 * first + 1] * pset2[3 * first + 1] + pset2[3 * first + 2] * pset2[3 * first + 2]) : 0.0;
-    }
+    vo_dist_wave(pnum, pset2, out);
 }
 
 // ransac_dr_ye.m:48-72 for hypothesis blockIdx.x
@@ -150,129 +35,17 @@ __global__ __launch_bounds__(64) void k_vo_score(int pnum, const double *__restr
                                                  const int32_t *__restrict__ draws, const VoOut *__restrict__ out, int words,
                                                  unsigned long long *__restrict__ masks, int32_t *__restrict__ cnum, int32_t *__restrict__ state)
 {
-#pragma clang fp contract(off)
-    const int hyp = blockIdx.x, lane = threadIdx.x;
-    double ct1[3] = { 0, 0, 0 }, ct2[3] = { 0, 0, 0 }, H[9], rot[9], tr[3];
-    int d[4];
-    for (int s = 0; s < 4; ++s) d[s] = draws[4 * hyp + s];
-    for (int s = 0; s < 4; ++s) for (int i = 0; i < 3; ++i) { ct1[i] += pset1[3 * d[s] + i]; ct2[i] += pset2[3 * d[s] + i]; }
-    for (int i = 0; i < 3; ++i) { ct1[i] /= 4; ct2[i] /= 4; }
-    for (int i = 0; i < 9; ++i) H[i] = 0;
-    for (int s = 0; s < 4; ++s) {
-        double q1[3], q2[3];
-        for (int i = 0; i < 3; ++i) { q1[i] = pset1[3 * d[s] + i] - ct1[i]; q2[i] = pset2[3 * d[s] + i] - ct2[i]; }
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) H[3 * i + j] += q2[i] * q1[j];
-    }
-    const int st = vo_solve(H, ct1, ct2, rot, tr);
-    const double thr = 0.001 * out->dist;
-    int cnt = 0;
-    for (int w = 0; w < words; ++w) {
-        const int k = w * 64 + lane;
-        int in = 0;
-        if (k < pnum) {
-            double dd = 0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                double v = rot[3 * i] * pset2[3 * k] + rot[3 * i + 1] * pset2[3 * k + 1] + rot[3 * i + 2] * pset2[3 * k + 2];
-                v = v + tr[i];
-                const double e = v - pset1[3 * k + i];
-                dd = dd + e * e;
-            }
-            in = dd < thr;
-        }
-        const unsigned long long b = __ballot(in);
-        if (lane == 0) masks[(size_t)hyp * words + w] = b;
-        cnt += __popcll(b);
-    }
-    if (lane == 0) { cnum[hyp] = cnt; state[hyp] = st; }
+    vo_score_hyp(blockIdx.x, pnum, pset1, pset2, draws, out, words, masks, cnum, state);
 }
 
-// vodometry_dr_ye.m:185-236: winner = first maximum, adaptive count, final fit on its inliers, error statistics -- one wave
+// vodometry_dr_ye.m:185-236 -- one wave
 __global__ void k_vo_final(int pnum, int n_hyp, const double *__restrict__ pset1, const double *__restrict__ pset2,
                            const int32_t *__restrict__ cnum, int words, const unsigned long long *__restrict__ masks,
                            VoOut *__restrict__ out, int32_t *__restrict__ inl_out)
 {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x;
-    int bc = -1, bi = 0x7fffffff;
-    for (int i = lane; i < n_hyp; i += 64) { const int c = cnum[i]; if (c > bc) { bc = c; bi = i; } }
-    for (int o = 32; o > 0; o >>= 1) {
-        const int oc = __shfl_xor(bc, o, 64), oi = __shfl_xor(bi, o, 64);
-        if (oc > bc || (oc == bc && oi < bi)) { bc = oc; bi = oi; }
-    }
-    // nIterations is overwritten at every strict improvement, so its final value belongs to the global maximum (:185-188)
-    double nIter = n_hyp;
-    if (bc > 0) nIter = 5 * ceil(log(0.01) / log(1 - pow((double)bc / pnum, 4)));
-    const int n_it = (int)(nIter < n_hyp ? nIter : n_hyp);
-    for (int k = lane; k < pnum; k += 64) inl_out[k] = bc >= 3 ? (int)((masks[(size_t)bi * words + (k >> 6)] >> (k & 63)) & 1ull) : 0;
-    if (bc < 3) {                                                                          // :198-205
-        if (lane == 0) { out->sta = 4; out->n_support = bc < 0 ? 0 : bc; out->n_iterations = n_it; out->best = bi;
-                         for (int i = 0; i < 9; ++i) out->rot[i] = 0; for (int i = 0; i < 3; ++i) { out->trans[i] = 0; out->euler[i] = 0; }
-                         out->error_mean = out->error_std = 0; out->u[0] = out->u[1] = out->u[2] = 0; out->u[3] = 1; out->u[4] = out->u[5] = out->u[6] = 0; }
-        return;
-    }
-    const unsigned long long *mk = masks + (size_t)bi * words;
-    // centroids, then H = sum q2 q1' over the inliers (lane-strided partial sums, butterfly-reduced)
-    double s[6] = { 0, 0, 0, 0, 0, 0 };
-    for (int k = lane; k < pnum; k += 64)
-        if ((mk[k >> 6] >> (k & 63)) & 1ull) for (int i = 0; i < 3; ++i) { s[i] += pset1[3 * k + i]; s[3 + i] += pset2[3 * k + i]; }
-    for (int o = 32; o > 0; o >>= 1) for (int i = 0; i < 6; ++i) s[i] += __shfl_xor(s[i], o, 64);
-    double ct1[3], ct2[3], H[9];
-    for (int i = 0; i < 3; ++i) { ct1[i] = s[i] / bc; ct2[i] = s[3 + i] / bc; }
-    for (int i = 0; i < 9; ++i) H[i] = 0;
-    for (int k = lane; k < pnum; k += 64)
-        if ((mk[k >> 6] >> (k & 63)) & 1ull) {
-            double q1[3], q2[3];
-            for (int i = 0; i < 3; ++i) { q1[i] = pset1[3 * k + i] - ct1[i]; q2[i] = pset2[3 * k + i] - ct2[i]; }
-            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) H[3 * i + j] += q2[i] * q1[j];
-        }
-    for (int o = 32; o > 0; o >>= 1) for (int i = 0; i < 9; ++i) H[i] += __shfl_xor(H[i], o, 64);
-    double rot[9], tr[3];
-    const int sta = vo_solve(H, ct1, ct2, rot, tr);
-    // ErrorRANSAC_Norm, mean and (N-1)-normalised std (:222-225)
-    double se = 0;
-    for (int k = lane; k < pnum; k += 64)
-        if ((mk[k >> 6] >> (k & 63)) & 1ull) {
-            double s2 = 0;
-            for (int i = 0; i < 3; ++i) {
-                const double v = rot[3 * i] * pset2[3 * k] + rot[3 * i + 1] * pset2[3 * k + 1] + rot[3 * i + 2] * pset2[3 * k + 2] + tr[i] - pset1[3 * k + i];
-                s2 += v * v;
-            }
-            se += sqrt(s2);
-        }
-    for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
-    const double mean = se / bc;
-    double var = 0;
-    for (int k = lane; k < pnum; k += 64)
-        if ((mk[k >> 6] >> (k & 63)) & 1ull) {
-            double s2 = 0;
-            for (int i = 0; i < 3; ++i) {
-                const double v = rot[3 * i] * pset2[3 * k] + rot[3 * i + 1] * pset2[3 * k + 1] + rot[3 * i + 2] * pset2[3 * k + 2] + tr[i] - pset1[3 * k + i];
-                s2 += v * v;
-            }
-            const double e = sqrt(s2) - mean;
-            var += e * e;
-        }
-    for (int o = 32; o > 0; o >>= 1) var += __shfl_xor(var, o, 64);
-    if (lane == 0) {
-        for (int i = 0; i < 9; ++i) out->rot[i] = rot[i];
-        for (int i = 0; i < 3; ++i) out->trans[i] = tr[i];
-        out->error_mean = mean; out->error_std = bc > 1 ? sqrt(var / (bc - 1)) : 0.0;
-        out->sta = sta; out->n_support = bc; out->n_iterations = n_it; out->best = bi;
-        out->euler[0] = out->euler[1] = out->euler[2] = 0;
-        if (sta >= 1) { out->euler[0] = atan2(rot[7], rot[8]); out->euler[1] = asin(-rot[6]); out->euler[2] = atan2(rot[3], rot[0]); }   // R2e.m:21-23
-        // Calculate_V_Omega_RANSAC_dr_ye.m:40-50: u = [T; R2q(R)], identity unless sta == 1
-        double R[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, T3[3] = { 0, 0, 0 };
-        if (sta == 1) { for (int i = 0; i < 9; ++i) R[i] = rot[i]; for (int i = 0; i < 3; ++i) T3[i] = tr[i]; }
-        const double Tq = R[0] + R[4] + R[8] + 1;
-        double a, b, c, d, S;
-        if (Tq > 0.00000001) { S = 2 * sqrt(Tq); a = 0.25 * S; b = (R[5] - R[7]) / S; c = (R[6] - R[2]) / S; d = (R[1] - R[3]) / S; }
-        else if (R[0] > R[4] && R[0] > R[8]) { S = 2 * sqrt(1.0 + R[0] - R[4] - R[8]); a = (R[5] - R[7]) / S; b = 0.25 * S; c = (R[1] + R[3]) / S; d = (R[6] + R[2]) / S; }
-        else if (R[4] > R[8]) { S = 2 * sqrt(1.0 + R[4] - R[0] - R[8]); a = (R[6] - R[2]) / S; b = (R[1] + R[3]) / S; c = 0.25 * S; d = (R[5] + R[7]) / S; }
-        else { S = 2 * sqrt(1.0 + R[8] - R[0] - R[4]); a = (R[1] - R[3]) / S; b = (R[6] + R[2]) / S; c = (R[5] + R[7]) / S; d = 0.25 * S; }
-        out->u[0] = T3[0]; out->u[1] = T3[1]; out->u[2] = T3[2]; out->u[3] = a; out->u[4] = -b; out->u[5] = -c; out->u[6] = -d;
-    }
+    vo_final_wave(pnum, n_hyp, pset1, pset2, cnum, words, masks, out, inl_out);
 }
+
 
 struct DevMem {                    // pooled device scratch (pre3_match.hip): no hipMalloc / hipFree per call once warm
     void *p = nullptr;

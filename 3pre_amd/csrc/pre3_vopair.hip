@@ -1,0 +1,225 @@
+// pre3_vopair.hip -- the VO front end between the keypoint sets two resident SR4000 frames hold, in one call (pre3_vo_pair_seeded).
+//   vodometry_dr_ye.m:139-236  (siftmatch on the filtered keypoint sets, pnum < 4, rst, the RANSAC and its statistics)
+//   sift/siftmatch.c:97-122    (every pair's bins in order, first index on ties, the ratio test in float)
+//   ransac_dr_ye.m:13-72, find_transform_matrix_dr_ye.m:8-41, Calculate_V_Omega_RANSAC_dr_ye.m:41-50 (pre3_vodev.h)
+// Eight launches on cur's stream, every hand-off a launch boundary; no workgroup waits on another.  The host knows n1 and n2 (the kept keypoints of the
+// two frames) and sizes buffers and grids by the caps pnum <= n1 and rst <= 700; the real pnum and rst are written by k_vp_pairs into a device header
+// (VoPairHeader) that every launch behind it reads: work items beyond them leave at once.
+//   k_vp_match   ic_match_tile (pre3_geomdev.h): 32 x 32 pairs per workgroup, prev's kept descriptors the queries, cur's the scan; partial
+//                (best, second, first index) per (column tile, query)
+//   k_vp_pairs   ONE workgroup: the column tiles merged in scan order (merge3), siftmatch.c:122 in float, the accepted pairs compacted in increasing k1 by
+//                ballot prefix into match (2 x pnum doubles, 1-based); then pnum and rst into the header
+//   k_vp_gather  vo_gather_one for both frames (blockIdx.y), the bad flags into the header
+//   k_vp_dist, k_vp_draw, k_vp_score, k_vp_final    the bodies of k_vo_dist, k_draw_vo, k_vo_score, k_vo_final with pnum / rst from the header
+// Every output slot has one writer (the capped count is an integer sum): results are bit-equal from run to run, and bit-equal to
+// pre3_vo_ransac_frames_seeded fed the same match list with n_hyp = rst.
+#include <cmath>
+
+#include "pre3_internal.h"
+#include "pre3_geomdev.h"
+#include "pre3_vodev.h"
+#include "pre3_vopair.h"
+
+namespace pre3 {
+
+namespace {
+
+constexpr int VP_NTH = 1024;                  // threads of k_vp_pairs' one workgroup
+constexpr int VP_NW = VP_NTH / 64;
+
+__global__ __launch_bounds__(256) void k_vp_match(IcMatchRide r)
+{
+    __shared__ double Qs[ICS_T][ICS_LD], Bs[ICS_T][ICS_LD];
+    ic_match_tile(r, blockIdx.x, Qs, Bs);
+}
+
+__global__ __launch_bounds__(VP_NTH) void k_vp_pairs(int n1, int ntn, float thresh, const double *__restrict__ pb, const double *__restrict__ ps,
+                                                     const int32_t *__restrict__ pa, double *__restrict__ match, VoPairHeader *__restrict__ hdr)
+{
+    __shared__ int s_cnt[VP_NW];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int base = 0;
+    for (int q0 = 0; q0 < n1; q0 += VP_NTH) {
+        const int k1 = q0 + tid;
+        int ok = 0, k2 = -1;
+        if (k1 < n1) {
+            double best = acc_max<double>(), second = acc_max<double>();
+            for (int t = 0; t < ntn; ++t) {                                // scan order: ties keep the first index (siftmatch.c:110)
+                const size_t o = (size_t)t * n1 + k1;
+                merge3(best, second, k2, pb[o], ps[o], pa[o]);
+            }
+            ok = k2 >= 0 && thresh * (float)best <= (float)second;        // siftmatch.c:122; one scan keypoint: second stays at the accumulator's maximum
+        }
+        const unsigned long long b = __ballot(ok);
+        if (lane == 0) s_cnt[wv] = __popcll(b);
+        __syncthreads();
+        int off = 0, tot = 0;
+#pragma unroll
+        for (int w = 0; w < VP_NW; ++w) { const int cw = s_cnt[w]; if (w < wv) off += cw; tot += cw; }
+        if (ok) {
+            const int c = base + off + __popcll(b & ((1ull << lane) - 1ull));      // c <= k1 < n1: inside match
+            match[2 * (size_t)c] = (double)(k1 + 1); match[2 * (size_t)c + 1] = (double)(k2 + 1);
+        }
+        base += tot;
+        __syncthreads();                                                    // (s_cnt is rewritten by the next pass)
+    }
+    if (tid == 0) { hdr->pnum = base; hdr->rst = vo_rst(base); hdr->bad = 0; hdr->capped = 0; }
+}
+
+struct VpFrame { const double *x, *y, *z, *frm; int ldf, K; };
+
+__global__ __launch_bounds__(64) void k_vp_gather(int rows, int cols, VpFrame f1, VpFrame f2, const double *__restrict__ match, double *__restrict__ pset1,
+                                                  double *__restrict__ pset2, VoPairHeader *__restrict__ hdr)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= hdr->pnum) return;
+    const VpFrame &f = blockIdx.y == 0 ? f1 : f2;
+    vo_gather_one(i, rows, cols, f.x, f.y, f.z, f.ldf, f.frm, f.K, match + blockIdx.y, 2, blockIdx.y == 0 ? pset1 : pset2, &hdr->bad);
+}
+
+__global__ __launch_bounds__(64) void k_vp_dist(const VoPairHeader *__restrict__ hdr, const double *__restrict__ pset2, VoOut *__restrict__ out)
+{
+    const int pnum = hdr->pnum;
+    if (pnum < 4 || hdr->bad != 0) return;
+    vo_dist_wave(pnum, pset2, out);
+}
+
+__global__ __launch_bounds__(64) void k_vp_draw(uint64_t seed, uint64_t seq, VoPairHeader *__restrict__ hdr, const double *__restrict__ match,
+                                                int32_t *__restrict__ draws)
+{
+    if (hdr->bad != 0) return;
+    vo_draw_lane(blockIdx.x * 64 + threadIdx.x, seed, seq, hdr->rst, hdr->pnum, match, match + 1, 2, draws, &hdr->capped);
+}
+
+__global__ __launch_bounds__(64) void k_vp_score(const VoPairHeader *__restrict__ hdr, const double *__restrict__ pset1, const double *__restrict__ pset2,
+                                                 const int32_t *__restrict__ draws, const VoOut *__restrict__ out, unsigned long long *__restrict__ masks,
+                                                 int32_t *__restrict__ cnum, int32_t *__restrict__ state)
+{
+    const int pnum = hdr->pnum;
+    if ((int)blockIdx.x >= hdr->rst || hdr->bad != 0) return;
+    vo_score_hyp(blockIdx.x, pnum, pset1, pset2, draws, out, (pnum + 63) / 64, masks, cnum, state);
+}
+
+__global__ __launch_bounds__(64) void k_vp_final(const VoPairHeader *__restrict__ hdr, const double *__restrict__ pset1, const double *__restrict__ pset2,
+                                                 const int32_t *__restrict__ cnum, const unsigned long long *__restrict__ masks, VoOut *__restrict__ out,
+                                                 int32_t *__restrict__ inl_out)
+{
+    const int pnum = hdr->pnum;
+    if (pnum < 4 || hdr->bad != 0) return;
+    vo_final_wave(pnum, hdr->rst, pset1, pset2, cnum, (pnum + 63) / 64, masks, out, inl_out);
+}
+
+size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// vodometry_dr_ye.m:152-160: fewer than four matches
+void vo_no_solution(pre3_vo_result *res)
+{
+    if (res == nullptr) return;
+    memset(res, 0, sizeof *res);
+    res->sta = 4; res->u[3] = 1.0;
+}
+
+}  // namespace
+
+}  // namespace pre3
+
+using namespace pre3;
+
+extern "C" {
+
+int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out, double *match_out,
+                        double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out, int32_t *state_out,
+                        int32_t *inlier_out, pre3_vo_result *res)
+{
+    PRE3_CHECK(prev != nullptr && cur != nullptr, PRE3_E_ARG, "pre3_vo_pair_seeded: null handle");
+    PRE3_CHECK(prev != cur, PRE3_E_ARG, "pre3_vo_pair_seeded: prev and cur are the same handle");
+    PRE3_CHECK(std::isfinite(thresh) && thresh > 0.0, PRE3_E_ARG, "pre3_vo_pair_seeded: thresh must be positive and finite");
+    SrFrameView v1, v2;
+    SrKeypointView k1, k2;
+    PRE3_TRY(sr_frame_view(prev, &v1)); PRE3_TRY(sr_frame_view(cur, &v2));
+    PRE3_CHECK(v1.device == v2.device && v1.rows == v2.rows && v1.cols == v2.cols, PRE3_E_ARG,
+               "pre3_vo_pair_seeded: the frames differ (device %d, %d x %d against device %d, %d x %d)", v1.device, v1.rows, v1.cols, v2.device, v2.rows, v2.cols);
+    PRE3_TRY(sr_frame_keypoint_view(prev, &k1)); PRE3_TRY(sr_frame_keypoint_view(cur, &k2));
+    PRE3_CHECK(k1.ND == DESC_DIM && k2.ND == DESC_DIM, PRE3_E_ARG, "pre3_vo_pair_seeded: descriptors of %d and %d entries (the matcher's tile is written for %d)",
+               k1.ND, k2.ND, DESC_DIM);
+    if (hipSetDevice(v2.device) != hipSuccess) { set_error("pre3_vo_pair_seeded: no HIP device %d", v2.device); return PRE3_E_NODEVICE; }
+    const int n1 = k1.n_kept, n2 = k2.n_kept;
+    if (pnum_out) *pnum_out = 0;
+    if (n1 == 0 || n2 == 0) { vo_no_solution(res); return PRE3_OK; }      // siftmatch of an empty set: no match, nothing to queue
+
+    // [header | VoOut | match | pset1 | pset2 | draws | cnum | state | inliers] come back in one transfer; the partials and the masks stay
+    const int ntn = ceil_div(n2, ICS_T), wcap = ceil_div(n1, 64);
+    const size_t o_out = sizeof(VoPairHeader), o_match = up16(o_out + sizeof(VoOut)), o_p1 = o_match + up16(sizeof(double) * 2 * (size_t)n1);
+    const size_t o_p2 = o_p1 + up16(sizeof(double) * 3 * (size_t)n1), o_draws = o_p2 + up16(sizeof(double) * 3 * (size_t)n1);
+    const size_t o_cnum = o_draws + up16(sizeof(int32_t) * 4 * VO_RST_CAP), o_state = o_cnum + up16(sizeof(int32_t) * VO_RST_CAP);
+    const size_t o_inl = o_state + up16(sizeof(int32_t) * VO_RST_CAP), o_end = o_inl + up16(sizeof(int32_t) * (size_t)n1);
+    const size_t o_pb = o_end, o_ps = o_pb + up16(sizeof(double) * (size_t)ntn * n1), o_pa = o_ps + up16(sizeof(double) * (size_t)ntn * n1);
+    const size_t o_masks = o_pa + up16(sizeof(int32_t) * (size_t)ntn * n1), total = o_masks + sizeof(unsigned long long) * (size_t)VO_RST_CAP * wcap;
+    size_t need = o_match;                      // the prefix of the block the caller's outputs reach into
+    if (match_out) need = o_p1;
+    if (pset1_out) need = o_p2;
+    if (pset2_out) need = o_draws;
+    if (draws_out) need = o_cnum;
+    if (cnum_out) need = o_state;
+    if (state_out) need = o_inl;
+    if (inlier_out) need = o_end;
+    char *d = nullptr, *pin = nullptr;
+    hipEvent_t ev_cur = nullptr, ev_prev = nullptr;
+    PRE3_TRY(sr_frame_pair_work(prev, 0, 0, nullptr, nullptr, &ev_prev));
+    PRE3_TRY(sr_frame_pair_work(cur, total, o_end, (void **)&d, (void **)&pin, &ev_cur));
+    hipStream_t st = v2.stream;
+    PRE3_HIP(hipEventRecord(ev_prev, v1.stream));
+    PRE3_HIP(hipStreamWaitEvent(st, ev_prev, 0));
+    PRE3_HIP(hipMemsetAsync(d, 0, o_match, st));                          // the header (*capped starts at zero) and the result block
+
+    VoPairHeader *hdr = (VoPairHeader *)d;
+    VoOut *out = (VoOut *)(d + o_out);
+    double *match = (double *)(d + o_match), *p1 = (double *)(d + o_p1), *p2 = (double *)(d + o_p2);
+    int32_t *draws = (int32_t *)(d + o_draws), *cnum = (int32_t *)(d + o_cnum), *state = (int32_t *)(d + o_state), *inl = (int32_t *)(d + o_inl);
+    unsigned long long *masks = (unsigned long long *)(d + o_masks);
+    IcMatchRide r{};
+    r.ntn = ntn; r.N = n1; r.K2 = n2; r.n_blocks = ntn * ceil_div(n1, ICS_T);
+    r.bank = k1.des; r.scan = k2.des; r.has_h = nullptr; r.pb = (double *)(d + o_pb); r.ps = (double *)(d + o_ps); r.pa = (int32_t *)(d + o_pa);
+    hipLaunchKernelGGL(k_vp_match, dim3(r.n_blocks), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(k_vp_pairs, dim3(1), dim3(VP_NTH), 0, st, n1, ntn, (float)thresh, (const double *)r.pb, (const double *)r.ps, (const int32_t *)r.pa, match, hdr);
+    const VpFrame f1{ v1.x, v1.y, v1.z, k1.frm, k1.ldf, n1 }, f2{ v2.x, v2.y, v2.z, k2.frm, k2.ldf, n2 };
+    hipLaunchKernelGGL(k_vp_gather, dim3(ceil_div(n1, 64), 2), dim3(64), 0, st, v2.rows, v2.cols, f1, f2, (const double *)match, p1, p2, hdr);
+    hipLaunchKernelGGL(k_vp_dist, dim3(1), dim3(64), 0, st, (const VoPairHeader *)hdr, (const double *)p2, out);
+    hipLaunchKernelGGL(k_vp_draw, dim3(ceil_div(VO_RST_CAP, 64)), dim3(64), 0, st, seed, seq, hdr, (const double *)match, draws);
+    hipLaunchKernelGGL(k_vp_score, dim3(VO_RST_CAP), dim3(64), 0, st, (const VoPairHeader *)hdr, (const double *)p1, (const double *)p2, (const int32_t *)draws,
+                       (const VoOut *)out, masks, cnum, state);
+    hipLaunchKernelGGL(k_vp_final, dim3(1), dim3(64), 0, st, (const VoPairHeader *)hdr, (const double *)p1, (const double *)p2, (const int32_t *)cnum,
+                       (const unsigned long long *)masks, out, inl);
+    PRE3_HIP(hipGetLastError());
+    PRE3_HIP(hipMemcpyAsync(pin, d, need, hipMemcpyDeviceToHost, st));
+    PRE3_HIP(hipEventRecord(ev_cur, st));
+    PRE3_HIP(hipStreamWaitEvent(v1.stream, ev_cur, 0));                   // a later load into prev stays behind these reads
+    PRE3_HIP(hipStreamSynchronize(st));
+
+    const VoPairHeader h = *(const VoPairHeader *)pin;
+    const VoOut o = *(const VoOut *)(pin + o_out);
+    PRE3_CHECK(h.pnum >= 0 && h.pnum <= n1 && h.rst == vo_rst(h.pnum), PRE3_E_HIP, "pre3_vo_pair_seeded: the device reports %d matches of %d keypoints and %d hypotheses",
+               h.pnum, n1, h.rst);
+    const int pnum = h.pnum, rst = h.rst;
+    if (pnum_out) *pnum_out = pnum;
+    if (match_out) memcpy(match_out, pin + o_match, sizeof(double) * 2 * (size_t)pnum);
+    if (pnum < 4) { vo_no_solution(res); return PRE3_OK; }
+    PRE3_CHECK(h.bad == 0, PRE3_E_HIP, "pre3_vo_pair_seeded: %s", (h.bad & 1) ? "a match refers to a keypoint that does not exist" : "a kept keypoint rounds to a pixel outside the range image");
+    if (pset1_out) memcpy(pset1_out, pin + o_p1, sizeof(double) * 3 * (size_t)pnum);
+    if (pset2_out) memcpy(pset2_out, pin + o_p2, sizeof(double) * 3 * (size_t)pnum);
+    if (draws_out) memcpy(draws_out, pin + o_draws, sizeof(int32_t) * 4 * (size_t)rst);
+    if (capped_out) *capped_out = h.capped;
+    PRE3_CHECK(o.dist_ok, PRE3_E_NUMERIC, "vo: no matched point is farther than 0.4 m from the camera (ransac_dr_ye.m:21 has no minimum there)");
+    if (cnum_out) memcpy(cnum_out, pin + o_cnum, sizeof(int32_t) * (size_t)rst);
+    if (state_out) memcpy(state_out, pin + o_state, sizeof(int32_t) * (size_t)rst);
+    if (inlier_out) memcpy(inlier_out, pin + o_inl, sizeof(int32_t) * (size_t)pnum);
+    if (res) {
+        memcpy(res->rot, o.rot, sizeof o.rot); memcpy(res->trans, o.trans, sizeof o.trans); memcpy(res->euler, o.euler, sizeof o.euler);
+        memcpy(res->u, o.u, sizeof o.u);
+        res->error_mean = o.error_mean; res->error_std = o.error_std; res->dist = o.dist;
+        res->sta = o.sta; res->n_support = o.n_support; res->n_iterations = o.n_iterations; res->best = o.best;
+    }
+    return PRE3_OK;
+}
+
+}  // extern "C"

@@ -6,6 +6,8 @@ readers and keypoint filters over the C ABI.
     code_from_dr_ye/read_sr4000_data_dr_ye.m:8-90            -> read_sr4000_data_dr_ye (sigma = 1, replicated border)
     code_from_dr_ye/confidence_filtering.m:1-13              -> confidence_filtering
     SIFT_extract_save.m:68-88 over inittialize_depth_my_version.m:16-92 -> sift_extract (the SCAN_SIFT dict scanio.save_sift_result writes)
+    code_from_dr_ye/vodometry_dr_ye.m:139-236                -> vodometry_dr_ye        (two resident frames, gate 1 on each, then vo.vo_pair_seeded)
+    Calculate_V_Omega_RANSAC_dr_ye.m:25-50                   -> calculate_v_omega      (T, q, R, sta)
 
 All compute runs in libpre3.so on the GPU; this module reads the text file and marshals numpy arrays.
 """
@@ -48,6 +50,7 @@ class SrFrame:
         self.rows, self.cols = int(rows), int(cols)
         self._h = C.c_void_p()
         self.has_conf = False
+        self.n_kept = 0                       # of the last keypoints() call: sizes vo.vo_pair_seeded's outputs
         check(lib.pre3_sr_frame_create(C.byref(self._h), int(device), self.rows, self.cols))
 
     def close(self):
@@ -117,7 +120,7 @@ class SrFrame:
         xyz, rho = np.zeros((3, Kb), order="F"), np.zeros(Kb)
         check(lib.pre3_sr_frame_keypoints(self._h, int(gate), ldf, K, dptr(frm), ND, dptr(des), C.byref(n), dptr(idx), dptr(frm_o), dptr(des_o),
                                           dptr(xyz), dptr(rho)))
-        n = n.value
+        n = self.n_kept = n.value
         out = dict(keep_idx=idx[:n].copy(), frames=frm_o[:, :n].copy(order="F"), descriptors=des_o[:, :n].copy(order="F"))
         if int(gate) == GATE_DEPTH:
             out["xyz"], out["rho"] = xyz[:, :n].copy(order="F"), rho[:n].copy()
@@ -167,3 +170,34 @@ def sift_extract(frames, descriptors, frame, idx_scan, image=None):
     return dict(idxScan=int(idx_scan), Image=frame.image() if image is None else np.asarray(image),
                 Descriptor_RAW=np.array(descriptors, dtype=np.float64), SCALE_ORIENT_POS_RAW=np.array(frames, dtype=np.float64),
                 Descriptor=out["descriptors"], SCALE_ORIENT_POS=out["frames"], XYZ_DATA=out["xyz"], initial_rho=out["rho"], keep_idx=out["keep_idx"])
+
+
+def vodometry_dr_ye(dat1, dat2, sift1, sift2, seed, seq=0, thresh=1.5, device=0, frames=None):
+    """vodometry_dr_ye.m:139-236 on the files dat1, dat2 (frame 1 the earlier one) and their SIFT sets sift1, sift2 = (frames (>=2, K), descriptors
+    (128, K)): each file is conditioned on the device in mode 1 and stays there, confidence_filtering (gate 1) drops the keypoints of low confidence --
+    the depth gate (gate 0) stands in on a frame without confidence rows --, then vo.vo_pair_seeded runs siftmatch, rst and the seeded RANSAC between
+    the two resident frames.  Returns vo_pair_seeded's dict plus kept1 / kept2 (the keep_idx of each frame: match holds positions in those lists).
+    frames: an optional (SrFrame, SrFrame) pair to reuse instead of creating two."""
+    from . import vo
+    d1, d2 = load_dat(dat1), load_dat(dat2)
+    own = frames is None
+    f1, f2 = (SrFrame(d1["z"].shape[0], d1["z"].shape[1], device), SrFrame(d2["z"].shape[0], d2["z"].shape[1], device)) if own else frames
+    try:
+        kept = []
+        for f, d, (frm, des) in ((f1, d1, sift1), (f2, d2, sift2)):
+            f.load(d, MODE_DR_YE)
+            kept.append(f.keypoints(frm, des, GATE_CONFIDENCE if d["conf"] is not None else GATE_DEPTH)["keep_idx"])
+        out = vo.vo_pair_seeded(f1, f2, seed, seq, thresh)
+    finally:
+        if own:
+            f1.close(); f2.close()
+    out["kept1"], out["kept2"] = kept
+    return out
+
+
+def calculate_v_omega(dat1, dat2, sift1, sift2, seed, seq=0, **kw):
+    """[T, q, R, sta] of Calculate_V_Omega_RANSAC_dr_ye.m:25-50: the translation, R2q(R), the rotation and the solution state; the identity motion unless
+    sta == 1 (:41-50) -- u = [T; q] is what EkfFilter.ekf_prediction takes"""
+    out = vodometry_dr_ye(dat1, dat2, sift1, sift2, seed, seq, **kw)
+    ok = out["sta"] == 1
+    return out["u"][:3].copy(), out["u"][3:].copy(), (out["rot"].copy() if ok else np.eye(3)), out["sta"]

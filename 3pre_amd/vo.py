@@ -4,6 +4,7 @@
     ransac_dr_ye.m:28-46                 -> draw_hypotheses (the reference's own rejection rule, any numpy Generator)
     ransac_dr_ye.m:28-48                 -> vo_ransac_seeded / vo_ransac_frames_seeded (the same rule on the device, from (seed, seq))
     vodometry_dr_ye.m:171                -> vo_rst
+    vodometry_dr_ye.m:139-236            -> vo_pair_seeded (siftmatch, rst and the RANSAC between two resident SR4000 frames, one call)
     Calculate_V_Omega_RANSAC_dr_ye.m:40-50 -> result["u"] = [T; R2q(R)], the argument of EkfFilter.ekf_prediction
 
 All compute runs in libpre3.so on the GPU; this module marshals numpy arrays and draws random numbers.
@@ -144,6 +145,28 @@ def vo_ransac_frames_seeded(frm1, frm2, match, x1, y1, z1, x2, y2, z2, seed, seq
     out = _result(res, cnum[:n_hyp], state[:n_hyp], inl[:pnum])
     out["pset1"], out["pset2"] = p1[:pnum].T.copy(), p2[:pnum].T.copy()
     out["draws"], out["capped"] = draws[:n_hyp], int(capped.value)
+    return out
+
+
+def vo_pair_seeded(prev, cur, seed, seq=0, thresh=1.5):
+    """vodometry_dr_ye.m:139-236 between the keypoint sets two resident frames hold (sr4000.SrFrame after keypoints()):
+    siftmatch(des1, des2, thresh), rst = min(700, nchoosek(pnum, 4)) and the seeded RANSAC, all on the device.  The dict of vo_ransac_frames_seeded
+    plus match (2, pnum) -- 1-based positions in the KEPT keypoint sets --, pnum and rst.  Fewer than four matches: sta = 4, u the identity, empty
+    point sets, tables and inlier list."""
+    n1 = max(int(getattr(prev, "n_kept", 0)), 1)
+    pnum, capped = C.c_int32(0), C.c_int32(0)
+    match = np.zeros((2, n1), order="F")
+    p1, p2 = np.zeros((n1, 3)), np.zeros((n1, 3))
+    draws, cnum, state, inl = np.zeros((700, 4), np.int32), np.zeros(700, np.int32), np.zeros(700, np.int32), np.zeros(n1, np.int32)
+    res = VoResult()
+    check(lib.pre3_vo_pair_seeded(prev._h, cur._h, float(thresh), int(seed), int(seq), C.byref(pnum), dptr(match), dptr(p1), dptr(p2), dptr(draws),
+                                  C.byref(capped), dptr(cnum), dptr(state), dptr(inl), C.byref(res)))
+    pnum = int(pnum.value)
+    rst = vo_rst(pnum) if pnum >= 4 else 0
+    out = _result(res, cnum[:rst].copy(), state[:rst].copy(), inl[:pnum if rst else 0].copy())
+    out["pset1"], out["pset2"] = p1[:pnum if rst else 0].T.copy(), p2[:pnum if rst else 0].T.copy()
+    out["draws"], out["capped"] = draws[:rst].copy(), int(capped.value)
+    out["match"], out["pnum"], out["rst"] = match[:, :pnum].copy(order="F"), pnum, rst
     return out
 
 

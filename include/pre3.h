@@ -558,6 +558,29 @@ PRE3_API int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K,
                                      int32_t *n_kept, int32_t *keep_idx, double *frm_out, double *des_out,
                                      double *xyz_out /* 3 x n_kept, gate 0 */, double *rho_out);
 
+/* ---- the VO front end between two resident SR4000 frames, in one call ---------------------------------------------------------
+ * vodometry_dr_ye.m:139-236 + Calculate_V_Omega_RANSAC_dr_ye.m:41-50 between the keypoint sets held by two resident frames: prev and cur each hold the
+ * result of their last pre3_sr_frame_keypoints (gate 1 in the reference: confidence_filtering.m on both frames).  siftmatch(des1, des2, thresh)
+ * (sift/siftmatch.c:97-122: every pair's bins in order, the first index on ties, the ratio test in float) with prev's kept descriptors as the queries;
+ * pnum = size(match, 2); rst = min(700, nchoosek(pnum, 4)) (:171); ransac_dr_ye.m:13-72 with the draws of pre3_vo_ransac_frames_seeded's rule from
+ * (seed, seq); the winner, the final fit and its statistics (:185-236); u = [T; R2q(R)].  Everything runs on the device on cur's stream, pnum and rst never
+ * leave it, and the call ends in ONE host wait.  Seeded only: the caller does not know pnum before the call, so it cannot supply a draw table.
+ * Results are bit-equal from run to run, and bit-equal to pre3_siftmatch_f64 on the kept descriptors followed by pre3_vo_ransac_frames_seeded on the
+ * filtered planes, the kept frames and that match list with n_hyp = rst and the same (seed, seq).
+ * Outputs (each may be NULL; arrays sized by the caller for the worst case, n1 = prev's kept keypoints and 700 hypotheses): *pnum_out;
+ * match_out 2 x pnum doubles, column-major, 1-based positions in the KEPT sets (what pre3_sr_frame_keypoints returned, not the caller's indices);
+ * pset1_out / pset2_out 3 x pnum; draws_out[rst * 4]; *capped_out; cnum_out[rst], state_out[rst], inlier_out[pnum]; res.
+ * pnum < 4 is a result (:152-160): PRE3_OK with sta = 4, n_support = n_iterations = 0, u = [0 0 0 1 0 0 0], every other field of res zero; only pnum_out
+ * and match_out are written besides.  op_num < 3: sta = 4 as in pre3_vo_ransac.  No matched point beyond 0.4 m: PRE3_E_NUMERIC.
+ * PRE3_E_ARG before anything is queued, both handles unchanged: a null handle, prev == cur, handles of different devices or frame sizes, descriptors of
+ * other than 128 entries on either side, a thresh that is not positive and finite.  PRE3_E_STATE likewise: a handle without a loaded frame, or without a
+ * keypoint result for the frame it holds (none yet, or a pre3_sr_frame_load after it).  Calls that share a handle must be serialised by the caller. */
+PRE3_API int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh /* siftmatch's, 1.5 in the reference */,
+                                 uint64_t seed, uint64_t seq,
+                                 int32_t *pnum_out, double *match_out /* 2 x pnum, 1-based, kept positions */,
+                                 double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out,
+                                 int32_t *cnum_out, int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them

@@ -19,6 +19,7 @@
  *   Weighted_Smpl_wo_replacement.m  [del, acc, cv, st, order] = pre3_mex('map_policy_seeded', step, UV, XYZ, DESC, 50, 0.1, std_z, 1, [176 144], seed, step)   % ... and its draw
  *   read_xyz_sr4000.m, read_image_sr4000.m, read_sr4000_data_dr_ye.m   [x, y, z, img, imax, cmax] = pre3_mex('sr_frame', mode, z, x, y, amp, conf)   % conf = [] for none; the frame stays resident
  *   SIFT_extract_save.m:71-88, confidence_filtering.m                  [frm, des, idx, xyz, rho] = pre3_mex('sr_keypoints', gate, frames, descriptors)    % on the resident frame; no filter context needed
+ *   vodometry_dr_ye.m:139-236, Calculate_V_Omega_RANSAC_dr_ye.m:41-50  pre3_mex('sr_keep'); ... next frame's 'sr_frame' + 'sr_keypoints' (gate 1) ...; [T, q, R, sta, match, stat] = pre3_mex('vo_pair', seed, seq)
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
  * corrcoef_partitioned_mex.c:25-57).  NOT compiled in the build container (no MATLAB / mex.h there).
@@ -29,9 +30,10 @@
 
 static pre3_ctx *g_ctx = NULL;
 static pre3_sr_frame *g_sr = NULL;          /* the resident SR4000 frame of 'sr_frame' / 'sr_keypoints' */
+static pre3_sr_frame *g_sr_prev = NULL;     /* the frame 'sr_keep' put aside: prev of 'vo_pair' */
 static int g_sr_rows = 0, g_sr_cols = 0;
 static void at_exit(void) { if (g_ctx) { pre3_destroy(g_ctx); g_ctx = NULL; } }
-static void sr_at_exit(void) { if (g_sr) { pre3_sr_frame_destroy(g_sr); g_sr = NULL; } at_exit(); }
+static void sr_at_exit(void) { if (g_sr) { pre3_sr_frame_destroy(g_sr); g_sr = NULL; } if (g_sr_prev) { pre3_sr_frame_destroy(g_sr_prev); g_sr_prev = NULL; } at_exit(); }
 static void check(int rc) { if (rc != PRE3_OK) mexErrMsgTxt(pre3_last_error()); }
 
 void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
@@ -58,7 +60,10 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         rows = (int)mxGetM(in[2]); cols = (int)mxGetN(in[2]);
         for (i = 3; i < 7; ++i)
             if (!(i == 6 && mxIsEmpty(in[6])) && ((int)mxGetM(in[i]) != rows || (int)mxGetN(in[i]) != cols)) mexErrMsgTxt("pre3_mex('sr_frame'): the planes must have the same size");
-        if (g_sr && (rows != g_sr_rows || cols != g_sr_cols)) { pre3_sr_frame_destroy(g_sr); g_sr = NULL; }
+        if (g_sr && (rows != g_sr_rows || cols != g_sr_cols)) {
+            pre3_sr_frame_destroy(g_sr); g_sr = NULL;
+            if (g_sr_prev) { pre3_sr_frame_destroy(g_sr_prev); g_sr_prev = NULL; }
+        }
         if (!g_sr) { check(pre3_sr_frame_create(&g_sr, 0, rows, cols)); g_sr_rows = rows; g_sr_cols = cols; mexAtExit(sr_at_exit); if (!mexIsLocked()) mexLock(); }
         check(pre3_sr_frame_load(g_sr, (int)mxGetScalar(in[1]), mxGetPr(in[2]), mxGetPr(in[3]), mxGetPr(in[4]), mxGetPr(in[5]), mxIsEmpty(in[6]) ? NULL : mxGetPr(in[6])));
         for (i = 0; i < 4; ++i) out[i] = mxCreateDoubleMatrix(rows, cols, mxREAL);
@@ -85,6 +90,40 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         if (gate == 0) { memcpy(mxGetPr(out[3]), xyz, sizeof(double) * 3 * (size_t)n); memcpy(mxGetPr(out[4]), rho, sizeof(double) * (size_t)n); }
         mxFree(idx); mxFree(f2); mxFree(d2); mxFree(xyz); mxFree(rho);
         (void)nout;
+        return;
+    }
+    if (!strcmp(cmd, "sr_keep")) {           /* pre3_mex('sr_keep'): the resident frame, with its last 'sr_keypoints' result, becomes the previous frame of 'vo_pair';
+                                                 the next 'sr_frame' loads into the other handle */
+        pre3_sr_frame *t = g_sr_prev;
+        if (!g_sr) mexErrMsgTxt("pre3_mex('sr_keep'): call pre3_mex('sr_frame', ...) first");
+        g_sr_prev = g_sr; g_sr = t;
+        (void)nout;
+        return;
+    }
+    if (!strcmp(cmd, "vo_pair")) {           /* [T, q, R, sta, match, stat] = pre3_mex('vo_pair', seed, seq [, thresh = 1.5]): vodometry_dr_ye.m:139-236 between the frame
+                                                 'sr_keep' put aside and the resident one, each with its 'sr_keypoints' (gate 1) result; seed, seq: whole numbers up to 2^53.
+                                                 T 3 x 1, q = R2q(R) 4 x 1 and R 3 x 3 are the identity motion unless sta == 1 (Calculate_V_Omega_RANSAC_dr_ye.m:41-50);
+                                                 match 2 x pnum (1-based positions in the kept sets); stat = [nIterationRansac nSupport ErrorMean ErrorStd phi theta psi pnum capped] */
+        pre3_vo_result r; int32_t pnum = 0, capped = 0; int i, k; mwSize n1; double *mt, *m;
+        if (nin < 3 || nin > 4) mexErrMsgTxt("pre3_mex('vo_pair', seed, seq [, thresh]): two or three arguments");
+        if (!g_sr || !g_sr_prev) mexErrMsgTxt("pre3_mex('vo_pair'): needs two frames -- 'sr_frame' + 'sr_keypoints', 'sr_keep', then 'sr_frame' + 'sr_keypoints' again");
+        n1 = (mwSize)PRE3_SR_MAX_KEYPOINTS;
+        mt = (double *)mxMalloc(sizeof(double) * 2 * n1);
+        check(pre3_vo_pair_seeded(g_sr_prev, g_sr, nin > 3 ? mxGetScalar(in[3]) : 1.5, (uint64_t)mxGetScalar(in[1]), (uint64_t)mxGetScalar(in[2]), &pnum, mt,
+                                  NULL, NULL, NULL, &capped, NULL, NULL, NULL, &r));
+        out[0] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[0]), r.u, sizeof(double) * 3);
+        if (nout > 1) { out[1] = mxCreateDoubleMatrix(4, 1, mxREAL); memcpy(mxGetPr(out[1]), r.u + 3, sizeof(double) * 4); }
+        if (nout > 2) {
+            out[2] = mxCreateDoubleMatrix(3, 3, mxREAL);
+            for (i = 0; i < 3; ++i) for (k = 0; k < 3; ++k) mxGetPr(out[2])[i + 3 * k] = r.sta == 1 ? r.rot[3 * i + k] : (i == k ? 1.0 : 0.0);      /* row-major -> column-major */
+        }
+        if (nout > 3) out[3] = mxCreateDoubleScalar(r.sta);
+        if (nout > 4) { out[4] = mxCreateDoubleMatrix(2, pnum, mxREAL); memcpy(mxGetPr(out[4]), mt, sizeof(double) * 2 * (size_t)pnum); }
+        if (nout > 5) {
+            out[5] = mxCreateDoubleMatrix(1, 9, mxREAL); m = mxGetPr(out[5]);
+            m[0] = r.n_iterations; m[1] = r.n_support; m[2] = r.error_mean; m[3] = r.error_std; memcpy(m + 4, r.euler, sizeof r.euler); m[7] = pnum; m[8] = capped;
+        }
+        mxFree(mt);
         return;
     }
     if (!g_ctx) mexErrMsgTxt("pre3_mex: call pre3_mex('create', ...) first");
