@@ -177,6 +177,15 @@ __global__ __launch_bounds__(256) void k_scan_pull(const int4 *__restrict__ src,
         }
     }
 }
+// the accepted candidates' descriptors from a resident frame's keypoint block into the bank (pre3_map_policy_frames_seeded):
+// one wave per new landmark, 16 bytes per lane; rows[a] is clamped to the block, so no read leaves it whatever the walk wrote
+__global__ __launch_bounds__(64) void k_fc_desc(int n_rows, const int32_t *__restrict__ rows, const double *__restrict__ des, double *__restrict__ bank_dst)
+{
+    const int row = min(max(rows[blockIdx.x], 0), n_rows - 1);
+    const double2 *s2 = (const double2 *)(des + (size_t)row * DESC_DIM);
+    double2 *d2 = (double2 *)(bank_dst + (size_t)blockIdx.x * DESC_DIM);
+    d2[threadIdx.x] = s2[threadIdx.x];
+}
 // the staging block `k` (0, 1: uploads; 2, 3: map management) has been pulled: one read of host memory (after 2 ms: a stream synchronisation)
 int stage_wait(pre3_ctx *c, int k)
 {
@@ -916,6 +925,22 @@ int pre3::set_descriptors_impl(pre3_ctx *c, int first, int count, const double *
     }
     c->bank_set = true;
     if (!ok) c->bank_ok = false;            // (sticky until the whole bank is rewritten: a bad descriptor may stay in the map)
+    else if (first == 0 && count >= c->N) c->bank_ok = true;
+    return PRE3_OK;
+}
+// set_descriptors_impl with the source on the device: nothing is staged; in_bounds is the caller's knowledge of copy_desc_checked's test
+int pre3::set_descriptors_rows_dev(pre3_ctx *c, int first, int count, const double *des_dev, const int32_t *rows_dev, int n_rows, bool in_bounds)
+{
+    PRE3_CHECK(first >= 0 && count >= 0 && first + count <= c->N && (count == 0 || (des_dev && rows_dev && n_rows > 0)), PRE3_E_ARG,
+               "descriptors from a keypoint block: range [%d, %d) outside the map (N=%d)", first, first + count, c->N);
+    PRE3_CHECK(((uintptr_t)des_dev & 15) == 0, PRE3_E_ARG, "descriptors from a keypoint block: the block is not 16-byte aligned");
+    PRE3_TRY(ensure_ic_buffers(c));
+    if (count) {
+        hipLaunchKernelGGL(k_fc_desc, dim3(count), dim3(DESC_DIM / 2), 0, c->stream, n_rows, rows_dev, des_dev, c->bank + (size_t)first * DESC_DIM);
+        PRE3_HIP(hipGetLastError());
+    }
+    c->bank_set = true;
+    if (!in_bounds) c->bank_ok = false;
     else if (first == 0 && count >= c->N) c->bank_ok = true;
     return PRE3_OK;
 }

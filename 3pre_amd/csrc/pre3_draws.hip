@@ -42,9 +42,13 @@ __global__ __launch_bounds__(DB) void k_draw_plane(uint64_t seed, uint64_t seq, 
 }
 
 // ---- the candidates' weighted order.  raw: [K][2] pixels (| rho[K] behind them in the context form), in the caller's order
-__global__ __launch_bounds__(DB) void k_cand_keys(uint64_t seed, uint64_t seq, int K, CandBox box, const double *__restrict__ raw, double *__restrict__ keys)
+// k_real != nullptr (both kernels): K is the layout count -- the grid and the offset of rho behind the pixels -- and min(*k_real, K) candidates exist;
+// work items at or beyond that count leave at once, every loop stays bounded by K.
+__global__ __launch_bounds__(DB) void k_cand_keys(uint64_t seed, uint64_t seq, int K, CandBox box, const double *__restrict__ raw, double *__restrict__ keys,
+                                                  const int32_t *__restrict__ k_real)
 {
     const int i = blockIdx.x * DB + threadIdx.x;
+    if (k_real != nullptr) K = max(0, min(*k_real, K));
     if (i >= K) return;
     keys[i] = cand_key(seed, seq, i, raw[2 * (size_t)i], raw[2 * (size_t)i + 1], box);
 }
@@ -57,12 +61,15 @@ __global__ __launch_bounds__(DB) void k_cand_keys(uint64_t seed, uint64_t seq, i
 // position rank_i of the [K][2] | rho[K] block k_policy_prefilter and k_policy_walk read.
 constexpr int CR_I = 64, CR_WAVES = 4, CR_TJ = 1024;
 __global__ __launch_bounds__(CR_I * CR_WAVES) void k_cand_rank(int K, const double *__restrict__ keys, const double *__restrict__ raw, int32_t *__restrict__ order,
-                                                                 double *__restrict__ cand_out)
+                                                                 double *__restrict__ cand_out, const int32_t *__restrict__ k_real, int32_t *__restrict__ order2)
 {
     __shared__ double s_key[CR_TJ];
     __shared__ int s_cnt[CR_WAVES][CR_I];
     const int lane = threadIdx.x & (CR_I - 1), wv = threadIdx.x / CR_I;
     const int i = blockIdx.x * CR_I + lane;
+    const int Klay = K;                                                  // where rho starts in raw and cand_out
+    if (k_real != nullptr) K = max(0, min(*k_real, K));
+    if ((int)blockIdx.x * CR_I >= K) return;                             // (the whole workgroup: nothing of it is ranked)
     const double ki = i < K ? keys[i] : 0.0;
     int cnt = 0;
     for (int j0 = 0; j0 < K; j0 += CR_TJ) {
@@ -81,9 +88,10 @@ __global__ __launch_bounds__(CR_I * CR_WAVES) void k_cand_rank(int K, const doub
     if (wv != 0 || i >= K) return;
     const int r = s_cnt[0][lane] + s_cnt[1][lane] + s_cnt[2][lane] + s_cnt[3][lane];
     order[r] = i;
+    if (order2 != nullptr) order2[r] = i;
     if (cand_out != nullptr) {
         cand_out[2 * (size_t)r] = raw[2 * (size_t)i]; cand_out[2 * (size_t)r + 1] = raw[2 * (size_t)i + 1];
-        cand_out[2 * (size_t)K + r] = raw[2 * (size_t)K + i];
+        cand_out[2 * (size_t)Klay + r] = raw[2 * (size_t)Klay + i];
     }
 }
 
@@ -92,10 +100,10 @@ __global__ __launch_bounds__(CR_I * CR_WAVES) void k_cand_rank(int K, const doub
 // raw_dev: [K][2] pixels in the caller's order (cand_out_dev != nullptr: rho[K] behind them); keys_dev[K], order_dev[K] (device addresses; order_dev
 // may be mapped host memory).  K >= 1, box checked by the caller.
 int launch_cand_order(unsigned long long seed, unsigned long long seq, int K, int box_w, int box_h, const double *raw_dev, double *keys_dev, int32_t *order_dev,
-                      double *cand_out_dev, hipStream_t st)
+                      double *cand_out_dev, hipStream_t st, const int32_t *k_real_dev, int32_t *order2_dev)
 {
-    hipLaunchKernelGGL(k_cand_keys, dim3(ceil_div(K, DB)), dim3(DB), 0, st, (uint64_t)seed, (uint64_t)seq, K, cand_box(box_w, box_h), raw_dev, keys_dev);
-    hipLaunchKernelGGL(k_cand_rank, dim3(ceil_div(K, CR_I)), dim3(CR_I * CR_WAVES), 0, st, K, keys_dev, raw_dev, order_dev, cand_out_dev);
+    hipLaunchKernelGGL(k_cand_keys, dim3(ceil_div(K, DB)), dim3(DB), 0, st, (uint64_t)seed, (uint64_t)seq, K, cand_box(box_w, box_h), raw_dev, keys_dev, k_real_dev);
+    hipLaunchKernelGGL(k_cand_rank, dim3(ceil_div(K, CR_I)), dim3(CR_I * CR_WAVES), 0, st, K, keys_dev, raw_dev, order_dev, cand_out_dev, k_real_dev, order2_dev);
     PRE3_HIP(hipGetLastError());
     return PRE3_OK;
 }

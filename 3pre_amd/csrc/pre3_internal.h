@@ -379,8 +379,10 @@ int launch_draw_vo(unsigned long long seed, unsigned long long seq, int n_hyp, i
                    int32_t *capped_dev /* zero at launch */, hipStream_t st);
 int launch_draw_plane(unsigned long long seed, unsigned long long seq, int n_draw, int npts, const double *pts_dev, int32_t *draws_dev, hipStream_t st);
 // the candidates' weighted order: keys, then their counting rank; cand_out_dev != nullptr: the [K][2] | rho[K] block re-laid in drawn order
+// k_real_dev != nullptr: K is the layout count (grids, the offset of rho behind the pixels) and *k_real_dev <= K, on the device, the number of candidates
+// there are -- work items at or beyond it leave at once; order2_dev != nullptr: a second copy of the order (device memory, for the launches behind)
 int launch_cand_order(unsigned long long seed, unsigned long long seq, int K, int box_w, int box_h, const double *raw_dev, double *keys_dev, int32_t *order_dev,
-                      double *cand_out_dev, hipStream_t st);
+                      double *cand_out_dev, hipStream_t st, const int32_t *k_real_dev = nullptr, int32_t *order2_dev = nullptr);
 
 // ---- the resident SR4000 frame (pre3_sr.hip): the handle's device pointers and stream for other translation units -- a plane fit
 // that crops from the resident frame, a VO gather from two resident frames, the candidate build.  Planes are rows x cols, column-major; conf is null when
@@ -394,9 +396,17 @@ int sr_frame_view(pre3_sr_frame *f, SrFrameView *v);      /* PRE3_E_STATE before
 // the handle's last keypoint result (pre3_sr_frame_keypoints), which stays in its keypoint block: the kept frames [n_kept][ldf] and descriptors
 // [n_kept][ND] in the caller's order.  A load makes it stale; a keypoint call with K == 0, or one that fails behind its argument checks, leaves a valid
 // empty one (n_kept == 0, frm == des == nullptr).  PRE3_E_STATE when there is none or it is stale.
-struct SrKeypointView { int K, ldf, ND, gate, n_kept; const double *frm, *des; };
+// xyz [n_kept][3] = [-x, -y, z], rho [n_kept] (gate 0 only: null otherwise) and keep_idx [n_kept] sit in the same block.
+struct SrKeypointView { int K, ldf, ND, gate, n_kept; const double *frm, *des; const double *xyz, *rho; const int32_t *keep_idx; };
 int sr_frame_keypoint_view(pre3_sr_frame *f, SrKeypointView *v);
 int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, void **dev, void **pin, hipEvent_t *ev);      /* pre3_vopair.hip's blocks and event */
+// ---- the match stage of the pair call on its own (pre3_vopair.hip: k_vp_match, k_vp_pairs), for pre3_map_policy_frames_seeded.  des1 [n1][128] the
+// queries, des2 [n2][128] the scan (n1, n2 >= 1); part: vp_match_part_bytes(n1, n2) of device scratch; match 2 x n1 doubles; hdr_dev a VoPairHeader
+// (pnum, rst written; bad and capped cleared).  Everything on `st`.
+size_t vp_match_part_bytes(int n1, int n2);
+int launch_vp_match(int n1, int n2, const double *des1, const double *des2, double thresh, void *part, double *match, void *hdr_dev, hipStream_t st);
+// the accepted candidates' descriptors from a keypoint block into the bank (pre3_api.hip): landmark first + a takes row rows_dev[a] of des_dev [..][128]
+int set_descriptors_rows_dev(pre3_ctx *c, int first, int count, const double *des_dev, const int32_t *rows_dev, int n_rows, bool in_bounds);
 
 // ---- map policy (pre3_map.hip): the rescue-visibility rider of a booked context (one small launch at the post-LI x_k_k), buffers
 int launch_book_vis(pre3_ctx *c);

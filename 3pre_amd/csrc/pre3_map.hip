@@ -15,6 +15,7 @@
 #include "pre3_internal.h"
 #include "pre3_geomdev.h"
 #include "pre3_philox.h"
+#include "pre3_vopair.h"
 
 namespace pre3 {
 
@@ -680,7 +681,15 @@ struct PolicyArgs {
     const double *cand;                 // [K][2] distorted pixels, then rho[K]
     int32_t *blocked;                   // [K]
     int32_t *res;                       // the result block (device address of mapped pinned memory)
+    // pre3_map_policy_frames_seeded; all null in the other entry points.  k_real: K above is the LAYOUT count (grids, the offset
+    // of rho in cand, the place of conv behind acc in res) and min(*k_real, K) candidates exist.  The walk then leaves each accepted candidate's
+    // (u, v, rho) in acc_uvr (mapped host memory, 3 doubles each) and the row of prev's keypoint block it came from in acc_row.
+    const int32_t *k_real;
+    double *acc_uvr; int32_t *acc_row;
+    const int32_t *order; const double *match;      // drawn position -> candidate; candidate -> 1-based kept position (2 doubles per candidate)
 };
+
+__device__ __forceinline__ int pol_count(const PolicyArgs &a) { return a.k_real != nullptr ? max(0, min(*a.k_real, a.K)) : a.K; }
 
 __device__ __forceinline__ bool pol_in_box(double pu, double pv, double cu, double cv, int strict)
 {
@@ -719,6 +728,7 @@ __global__ __launch_bounds__(64) void k_policy_lm(PolicyArgs a)
 __global__ __launch_bounds__(256) void k_policy_prefilter(PolicyArgs a)
 {
     const int c = blockIdx.x;
+    if (c >= pol_count(a)) return;                                          // (the whole workgroup)
     const double cu = a.cand[2 * c], cv = a.cand[2 * c + 1];
     int hit = 0;
     for (int j = threadIdx.x; j < a.N; j += blockDim.x)
@@ -775,11 +785,12 @@ __global__ __launch_bounds__(64) void k_policy_walk(PolicyArgs a)
     const int T = measured == 0 ? a.min_features : max(0, a.min_features - measured);
     const int goal = min(a.strict ? (T + 1) / 2 : T, a.capN - n_surv);      // (additions stop at the capacity: stats[3] shows it)
     int n_acc = 0, nh = 0, examined = 0;
-    for (int c0 = 0; c0 < a.K && n_acc < goal; c0 += 64) {
+    const int K = pol_count(a);                                             // (a.K stays the layout: r_conv above, rho below)
+    for (int c0 = 0; c0 < K && n_acc < goal; c0 += 64) {
         const int cl = c0 + lane;
-        const int blk = cl < a.K ? a.blocked[cl] : 1;
-        const double u = cl < a.K ? a.cand[2 * cl] : 0.0, v = cl < a.K ? a.cand[2 * cl + 1] : 0.0;
-        for (int k = 0; k < 64 && c0 + k < a.K && n_acc < goal; ++k) {
+        const int blk = cl < K ? a.blocked[cl] : 1;
+        const double u = cl < K ? a.cand[2 * cl] : 0.0, v = cl < K ? a.cand[2 * cl + 1] : 0.0;
+        for (int k = 0; k < 64 && c0 + k < K && n_acc < goal; ++k) {
             examined = c0 + k + 1;
             if (__shfl(blk, k)) continue;                                   // a survivor of the map is in its box
             const double cu = __shfl(u, k), cv = __shfl(v, k);
@@ -789,7 +800,12 @@ __global__ __launch_bounds__(64) void k_policy_walk(PolicyArgs a)
             if (lane == 0) {
                 r_acc[n_acc] = c0 + k;
                 double zi[2];
-                const bool vis = pol_new_feature_h(cu, cv, a.cand[2 * a.K + c0 + k], a.x, a.cam, zi);
+                const double rho = a.cand[2 * a.K + c0 + k];
+                if (a.acc_uvr != nullptr) {                                 // n_acc < goal <= POL_MAX_FEATURES
+                    a.acc_uvr[3 * n_acc] = cu; a.acc_uvr[3 * n_acc + 1] = cv; a.acc_uvr[3 * n_acc + 2] = rho;
+                    a.acc_row[n_acc] = (int)a.match[2 * (size_t)a.order[c0 + k]] - 1;
+                }
+                const bool vis = pol_new_feature_h(cu, cv, rho, a.x, a.cam, zi);
                 if (vis) { s_hu[nh] = zi[0]; s_hv[nh] = zi[1]; }
                 s_newvis = vis ? 1 : 0;
             }
@@ -815,6 +831,34 @@ __global__ __launch_bounds__(64) void k_book_vis(int N, const int32_t *__restric
     bool fresh = false;
     (void)project_core(type[i], x, x + off[i], cam, 0, nullptr, zi, fresh, hc, hl);
     vis[i] = (has_h[i] || fresh) ? 1 : 0;
+}
+
+// initialize_features.m:95-99 on the device (pre3_map_policy_frames_seeded): candidate c is prev's kept keypoint match[0][c] - 1.  One lane per
+// c < pnum writes the [Kcap][2] | rho[Kcap] block k_cand_keys / k_cand_rank read and raises the header flags the host looks at behind the call's one
+// wait: a pixel that is not finite, a rho that is not finite and positive (gate 0 keeps a keypoint whose y or z is NaN), a descriptor entry outside
+// the bounds of pre3_set_descriptors' check (finite, |x| <= 2^60, no non-zero |x| < 2^-40), a match naming a keypoint that does not exist (clamped).
+// Each lane stores its bits to its own word flags[c] -- one writer per slot, no atomics; the words come back behind match in the same transfer and the
+// host ORs them.
+__global__ __launch_bounds__(64) void k_fc_gather(int Kcap, int n1, int ldf, const double *__restrict__ frm, const double *__restrict__ rho,
+                                                  const double *__restrict__ des, const double *__restrict__ match, const VoPairHeader *__restrict__ hdr,
+                                                  double *__restrict__ raw, int32_t *__restrict__ flags)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= min(hdr->pnum, Kcap)) return;
+    int k1 = (int)match[2 * (size_t)c] - 1, bad = 0;
+    if (k1 < 0 || k1 >= n1) { bad |= FC_BAD_INDEX; k1 = min(max(k1, 0), n1 - 1); }
+    const double u = frm[(size_t)k1 * ldf], v = frm[(size_t)k1 * ldf + 1], r = rho[k1];
+    if (!(isfinite(u) && isfinite(v))) bad |= FC_BAD_PIXEL;
+    if (!(isfinite(r) && r > 0.0)) bad |= FC_BAD_RHO;
+    const double *d = des + (size_t)k1 * DESC_DIM;
+    int db = 0;
+    for (int q = 0; q < DESC_DIM; ++q) {
+        const double ax = fabs(d[q]);
+        db |= (int)!(ax <= 0x1p60) | ((int)(ax != 0.0) & (int)(ax < 0x1p-40));
+    }
+    if (db) bad |= FC_BAD_DESC;
+    raw[2 * (size_t)c] = u; raw[2 * (size_t)c + 1] = v; raw[2 * (size_t)Kcap + c] = r;
+    flags[c] = bad;
 }
 
 static CamD cam_d(const pre3_ctx *c) { return CamD{ c->cam.f, c->cam.Cx, c->cam.Cy, c->cam.k1, c->cam.k2, c->cam.nRows, c->cam.nCols }; }
@@ -1033,6 +1077,10 @@ int pre3_get_book(pre3_ctx *c, int first, int count, int32_t *book_out)
 // candidates go up in the caller's order, k_cand_keys and k_cand_rank in front of k_policy_prefilter re-lay them in the drawn order, the order comes
 // back in the result block and maps the accepted positions to the caller's indices.
 struct CandSeed { uint64_t seed, seq; int box_w, box_h; };
+// fc != nullptr: pre3_map_policy_frames_seeded -- the candidates are built on the device from two resident frames (k_vp_match,
+// k_vp_pairs, k_fc_gather on cur's stream); K is then the cap n1 every buffer, grid and the result block are laid out by, the real count pnum stays in
+// the device header and reaches the host with the one wait.  The views have been checked by the caller.
+struct FrameCand { pre3_sr_frame *prev, *cur; double thresh; SrFrameView v1, v2; SrKeypointView k1, k2; int32_t *K_out; double *match_out; };
 
 static int cand_box_check(const char *who, int box_w, int box_h)
 {
@@ -1044,17 +1092,18 @@ static int cand_box_check(const char *who, int box_w, int box_h)
 
 static int map_policy_impl(const char *who, pre3_ctx *c, int step, int min_features, double convert_threshold, double std_pxl, int strict_reference, int K,
                            const double *cand_uv, const double *cand_xyz, const double *cand_desc, const CandSeed *sd, int32_t *order_out,
-                           int32_t *del_out, int32_t *n_del_out, int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out, int32_t stats[4])
+                           int32_t *del_out, int32_t *n_del_out, int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out, int32_t stats[4],
+                           const FrameCand *fc = nullptr)
 {
     // ---- every argument and state check before anything is launched: an error leaves the context as it was
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
-    PRE3_CHECK(K >= 0 && K <= PRE3_POLICY_MAX_CANDIDATES && (K == 0 || (cand_uv && cand_xyz)), PRE3_E_ARG,
+    PRE3_CHECK(K >= 0 && K <= PRE3_POLICY_MAX_CANDIDATES && (K == 0 || fc != nullptr || (cand_uv && cand_xyz)), PRE3_E_ARG,
                "%s: K=%d candidates (at most %d, uv and xyz required)", who, K, PRE3_POLICY_MAX_CANDIDATES);
     PRE3_CHECK(min_features >= 0 && min_features <= POL_MAX_FEATURES, PRE3_E_ARG, "%s: min_features=%d outside 0 .. %d", who, min_features, POL_MAX_FEATURES);
     PRE3_CHECK(std::isfinite(std_pxl) && std::isfinite(convert_threshold), PRE3_E_ARG, "%s: std_pxl and the threshold must be finite", who);
     if (sd) PRE3_TRY(cand_box_check(who, sd->box_w, sd->box_h));
-    std::vector<double> rho(K);
-    for (int k = 0; k < K; ++k) {
+    std::vector<double> rho(fc ? 0 : K);
+    for (int k = 0; k < K && !fc; ++k) {
         const double x = cand_xyz[3 * k], y = cand_xyz[3 * k + 1], z = cand_xyz[3 * k + 2];
         rho[k] = 1.0 / sqrt(x * x + y * y + z * z);                 // initialize_a_feature_sift_3.m:116-117
         PRE3_CHECK(std::isfinite(cand_uv[2 * k]) && std::isfinite(cand_uv[2 * k + 1]), PRE3_E_ARG, "%s: candidate %d has a non-finite pixel", who, k);
@@ -1071,9 +1120,20 @@ static int map_policy_impl(const char *who, pre3_ctx *c, int step, int min_featu
     // ---- buffers: device scratch [cand 3K | puv 2capN | (seeded: raw 3K | keys K) | del, mh, pvis capN | blocked K], the mapped result block
     // [hdr | del capN | acc K | conv capN | (seeded: order K) | cand 3K]
     const size_t cap = (size_t)std::max(c->capN, 1), Kc = (size_t)std::max(K, 1), Ks = sd ? Kc : 0;
-    const size_t dev_bytes = sizeof(double) * (3 * Kc + 2 * cap + 4 * Ks) + sizeof(int32_t) * (7 * cap + Kc);
+    // (frames: order2 K | acc_row behind blocked on the device; the accepted candidates' (u, v, rho) behind cand in the result block)
+    const bool fcq = fc != nullptr && K > 0;                       // K == 0 (no kept keypoint on either side): nothing to match, the plain K = 0 call
+    const size_t dev_bytes = sizeof(double) * (3 * Kc + 2 * cap + 4 * Ks) + sizeof(int32_t) * (7 * cap + Kc + (fcq ? Kc + POL_MAX_FEATURES : 0));
     const size_t o_order = POL_HDR + 2 * (size_t)c->capN + (size_t)K;
-    const size_t res_words = ((POL_HDR + 2 * cap + Kc + Ks) + 1) & ~(size_t)1, host_bytes = sizeof(int32_t) * res_words + sizeof(double) * 3 * Kc;
+    const size_t res_words = ((POL_HDR + 2 * cap + Kc + Ks) + 1) & ~(size_t)1;
+    const size_t host_bytes = sizeof(int32_t) * res_words + sizeof(double) * 3 * (Kc + (fcq ? POL_MAX_FEATURES : 0));
+    // (frames) cur's work block [header | match 2K | flags K | the matcher's partials]; header, match and flags come back in one transfer
+    const size_t fo_match = sizeof(VoPairHeader), fo_flags = fo_match + sizeof(double) * 2 * Kc, fo_part = (fo_flags + sizeof(int32_t) * Kc + 15) & ~(size_t)15;
+    char *f_dev = nullptr, *f_pin = nullptr;
+    hipEvent_t ev_prev = nullptr, ev_cur = nullptr;
+    if (fcq) {
+        PRE3_TRY(sr_frame_pair_work(fc->prev, 0, 0, nullptr, nullptr, &ev_prev));
+        PRE3_TRY(sr_frame_pair_work(fc->cur, fo_part + vp_match_part_bytes(K, fc->k2.n_kept), fo_part, (void **)&f_dev, (void **)&f_pin, &ev_cur));
+    }
     if (dev_bytes > c->pol_dev_bytes) {
         if (c->pol_dev) (void)hipFree(c->pol_dev);
         c->pol_dev = nullptr; c->pol_dev_bytes = 0;
@@ -1088,12 +1148,32 @@ static int map_policy_impl(const char *who, pre3_ctx *c, int step, int min_featu
         c->pol_host_bytes = host_bytes;
     }
     double *h_cand = reinterpret_cast<double *>(c->pol_host + res_words);
-    for (int k = 0; k < K; ++k) { h_cand[2 * k] = cand_uv[2 * k]; h_cand[2 * k + 1] = cand_uv[2 * k + 1]; h_cand[2 * K + k] = rho[k]; }
+    for (int k = 0; k < K && !fc; ++k) { h_cand[2 * k] = cand_uv[2 * k]; h_cand[2 * k + 1] = cand_uv[2 * k + 1]; h_cand[2 * K + k] = rho[k]; }
     double *d_cand = static_cast<double *>(c->pol_dev), *d_puv = d_cand + 3 * Kc, *d_raw = d_puv + 2 * cap, *d_keys = d_raw + 3 * Ks;
     int32_t *d_del = reinterpret_cast<int32_t *>(d_keys + Ks), *d_mh = d_del + cap, *d_pvis = d_mh + cap, *d_nbook = d_pvis + cap, *d_blocked = d_nbook + 4 * cap;
-    if (K > 0) PRE3_HIP(hipMemcpyAsync(sd ? d_raw : d_cand, h_cand, sizeof(double) * 3 * K, hipMemcpyHostToDevice, c->stream));
+    int32_t *d_order2 = fcq ? d_blocked + Kc : nullptr, *d_acc_row = fcq ? d_order2 + Kc : nullptr;
+    const int32_t *d_kreal = nullptr;
+    if (fcq) {
+        // ---- on cur's stream, behind an event on prev's: the match list and its count (pre3_vo_pair_seeded's launches), the gather; header, match and
+        // flags towards the host; then the context's stream waits for all of it
+        hipStream_t fs = fc->v2.stream;
+        VoPairHeader *hdr = reinterpret_cast<VoPairHeader *>(f_dev);
+        double *d_match = reinterpret_cast<double *>(f_dev + fo_match);
+        int32_t *d_flags = reinterpret_cast<int32_t *>(f_dev + fo_flags);
+        PRE3_HIP(hipEventRecord(ev_prev, fc->v1.stream));
+        PRE3_HIP(hipStreamWaitEvent(fs, ev_prev, 0));
+        PRE3_HIP(hipMemsetAsync(f_dev, 0, fo_part, fs));
+        PRE3_TRY(launch_vp_match(K, fc->k2.n_kept, fc->k1.des, fc->k2.des, fc->thresh, f_dev + fo_part, d_match, hdr, fs));
+        hipLaunchKernelGGL(k_fc_gather, dim3(ceil_div(K, 64)), dim3(64), 0, fs, K, K, fc->k1.ldf, fc->k1.frm, fc->k1.rho, fc->k1.des, (const double *)d_match,
+                           (const VoPairHeader *)hdr, d_raw, d_flags);
+        PRE3_HIP(hipGetLastError());
+        PRE3_HIP(hipMemcpyAsync(f_pin, f_dev, fo_part, hipMemcpyDeviceToHost, fs));
+        PRE3_HIP(hipEventRecord(ev_cur, fs));
+        PRE3_HIP(hipStreamWaitEvent(c->stream, ev_cur, 0));
+        d_kreal = &hdr->pnum;
+    } else if (K > 0) PRE3_HIP(hipMemcpyAsync(sd ? d_raw : d_cand, h_cand, sizeof(double) * 3 * K, hipMemcpyHostToDevice, c->stream));
     // ---- seeded: the keys and their rank re-lay the block in the drawn order (d_raw -> d_cand); the order goes into the result block
-    if (sd && K > 0) PRE3_TRY(launch_cand_order(sd->seed, sd->seq, K, sd->box_w, sd->box_h, d_raw, d_keys, c->pol_host_dev + o_order, d_cand, c->stream));
+    if (sd && K > 0) PRE3_TRY(launch_cand_order(sd->seed, sd->seq, K, sd->box_w, sd->box_h, d_raw, d_keys, c->pol_host_dev + o_order, d_cand, c->stream, d_kreal, d_order2));
     // ---- inversedepth_2_cartesian's flags and points (the same launch pre3_map_management makes: the same linearity numbers)
     if (convert_threshold >= 0 && N > 0) {
         DISPATCH_T(c,
@@ -1101,7 +1181,9 @@ static int map_policy_impl(const char *who, pre3_ctx *c, int step, int min_featu
             hipLaunchKernelGGL(k_map_convert_flags<float>, dim3(ceil_div(N, 64)), dim3(64), 0, c->stream, N, c->lm.type, c->lm.off, c->x_kk, (const float *)c->P, c->ld, convert_threshold, c->map_flags, c->map_conv));
     } else if (N > 0) PRE3_HIP(hipMemsetAsync(c->map_flags, 0, sizeof(int32_t) * N, c->stream));
     const PolicyArgs pa{ N, K, step, min_features, strict_reference ? 1 : 0, c->capN, c->lm.type, c->lm.off, c->lm.ic, c->lm.li, c->lm.hi, c->lm.has_h, c->book_vis,
-                         c->map_flags, c->map_conv, c->x_kk, cam_d(c), c->book, d_nbook, d_del, d_mh, d_pvis, d_puv, d_cand, d_blocked, c->pol_host_dev };
+                         c->map_flags, c->map_conv, c->x_kk, cam_d(c), c->book, d_nbook, d_del, d_mh, d_pvis, d_puv, d_cand, d_blocked, c->pol_host_dev,
+                         d_kreal, fcq ? reinterpret_cast<double *>(c->pol_host_dev + res_words) + 3 * Kc : nullptr, d_acc_row, d_order2,
+                         fcq ? reinterpret_cast<const double *>(f_dev + fo_match) : nullptr };
     if (N > 0) hipLaunchKernelGGL(k_policy_lm, dim3(ceil_div(N, 64)), dim3(64), 0, c->stream, pa);
     if (K > 0) {
         if (N > 0) hipLaunchKernelGGL(k_policy_prefilter, dim3(K), dim3(256), 0, c->stream, pa);
@@ -1112,20 +1194,38 @@ static int map_policy_impl(const char *who, pre3_ctx *c, int step, int min_featu
     PRE3_TRY(stream_drain(c, who));                                 // the one host wait
     const int32_t *res = c->pol_host, *r_del = res + POL_HDR, *r_acc = r_del + c->capN, *r_conv = r_acc + K;
     const int n_del = res[4], n_acc = res[5], n_surv = res[6];
-    PRE3_CHECK(n_del >= 0 && n_del <= N && n_acc >= 0 && n_acc <= K && n_surv == N - n_del && n_surv + n_acc <= c->capN, PRE3_E_HIP, "%s: inconsistent result block", who);
+    // (frames) the real count and the gather's flags arrived with the same wait; K stays the layout of the result block
+    int Kr = K, fc_bad = 0;
+    if (fcq) {
+        const VoPairHeader h = *reinterpret_cast<const VoPairHeader *>(f_pin);
+        PRE3_CHECK(h.pnum >= 0 && h.pnum <= K, PRE3_E_HIP, "%s: the device reports %d matches of %d keypoints", who, h.pnum, K);
+        Kr = h.pnum;
+        const int32_t *fl = reinterpret_cast<const int32_t *>(f_pin + fo_flags);
+        for (int k = 0; k < Kr; ++k) fc_bad |= fl[k];
+        PRE3_CHECK(!(fc_bad & FC_BAD_INDEX), PRE3_E_HIP, "%s: a match refers to a keypoint that does not exist", who);
+        // (the counters reach the book only with the re-layout below: context, book, map and both handles are as they were)
+        PRE3_CHECK(!(fc_bad & FC_BAD_PIXEL), PRE3_E_NUMERIC, "%s: a matched keypoint of prev has a non-finite pixel", who);
+        PRE3_CHECK(!(fc_bad & FC_BAD_RHO), PRE3_E_NUMERIC, "%s: a matched keypoint of prev has a rho that is not finite and positive (a NaN y or z passes the depth gate)", who);
+        PRE3_CHECK(n_acc <= POL_MAX_FEATURES, PRE3_E_HIP, "%s: inconsistent result block", who);
+    }
+    PRE3_CHECK(n_del >= 0 && n_del <= N && n_acc >= 0 && n_acc <= Kr && n_surv == N - n_del && n_surv + n_acc <= c->capN, PRE3_E_HIP, "%s: inconsistent result block", who);
     std::vector<int32_t> dl(r_del, r_del + n_del), acc(r_acc, r_acc + n_acc), flags(N ? N : 1, 0);
     for (int i = 0; i < N; ++i) flags[i] = r_conv[i];
     int32_t st[4] = { res[0], res[1], res[2], res[3] };
     if (sd) {                                                       // drawn positions -> the caller's candidate indices (stats[2] stays a count of positions)
         const int32_t *r_order = res + o_order;
         for (int a = 0; a < n_acc; ++a) {
-            PRE3_CHECK(acc[a] >= 0 && acc[a] < K && r_order[acc[a]] >= 0 && r_order[acc[a]] < K, PRE3_E_HIP, "%s: inconsistent result block", who);
+            PRE3_CHECK(acc[a] >= 0 && acc[a] < Kr && r_order[acc[a]] >= 0 && r_order[acc[a]] < Kr, PRE3_E_HIP, "%s: inconsistent result block", who);
             acc[a] = r_order[acc[a]];
         }
-        if (order_out) for (int k = 0; k < K; ++k) order_out[k] = r_order[k];
+        if (order_out) for (int k = 0; k < Kr; ++k) order_out[k] = r_order[k];
     }
     std::vector<double> uvd(2 * (size_t)n_acc), rho_acc(n_acc);
-    for (int a = 0; a < n_acc; ++a) { uvd[2 * a] = cand_uv[2 * acc[a]]; uvd[2 * a + 1] = cand_uv[2 * acc[a] + 1]; rho_acc[a] = rho[acc[a]]; }
+    if (fcq) {                                                      // the walk left them in the result block: the host never had the candidates
+        const double *uvr = reinterpret_cast<const double *>(c->pol_host + res_words) + 3 * Kc;
+        for (int a = 0; a < n_acc; ++a) { uvd[2 * a] = uvr[3 * a]; uvd[2 * a + 1] = uvr[3 * a + 1]; rho_acc[a] = uvr[3 * a + 2]; }
+    } else
+        for (int a = 0; a < n_acc; ++a) { uvd[2 * a] = cand_uv[2 * acc[a]]; uvd[2 * a + 1] = cand_uv[2 * acc[a] + 1]; rho_acc[a] = rho[acc[a]]; }
     // ---- the state: pre3_map_management's composition with these lists; the book rides along (new landmarks: {0, 0, step - 1, step - 1},
     // initialize_features.m:120 passes step - 1 to add_feature_to_info_vector_my_version_sift.m:42-60)
     // (the counters reach the book only through this re-layout: a failure before it leaves the book as it was)
@@ -1138,6 +1238,17 @@ static int map_policy_impl(const char *who, pre3_ctx *c, int step, int min_featu
         for (int a = 0; a < n_acc; ++a) memcpy(dsc.data() + 128 * (size_t)a, cand_desc + 128 * (size_t)acc[a], sizeof(double) * 128);
         PRE3_TRY(set_descriptors_impl(c, n_surv, n_acc, dsc.data()));
     }
+    if (fcq) {
+        // initialize_a_feature_sift_3.m:132 from prev's keypoint block, on the context's stream; then both handles' streams wait for the context's, so
+        // that a later load or keypoint call cannot overwrite blocks that are still being read
+        if (n_acc > 0) PRE3_TRY(set_descriptors_rows_dev(c, n_surv, n_acc, fc->k1.des, d_acc_row, K, !(fc_bad & FC_BAD_DESC)));
+        PRE3_HIP(hipEventRecord(ev_prev, c->stream));
+        PRE3_HIP(hipStreamWaitEvent(fc->v1.stream, ev_prev, 0));
+        PRE3_HIP(hipEventRecord(ev_cur, c->stream));
+        PRE3_HIP(hipStreamWaitEvent(fc->v2.stream, ev_cur, 0));
+        if (fc->match_out) memcpy(fc->match_out, f_pin + fo_match, sizeof(double) * 2 * (size_t)Kr);
+    }
+    if (fc && fc->K_out) *fc->K_out = Kr;
     if (del_out) for (int d = 0; d < n_del; ++d) del_out[d] = dl[d];
     if (n_del_out) *n_del_out = n_del;
     if (accepted_out) for (int a = 0; a < n_acc; ++a) accepted_out[a] = acc[a];
@@ -1162,6 +1273,33 @@ int pre3_map_policy_seeded(pre3_ctx *c, int step, int min_features, double conve
     const CandSeed sd{ seed, seq, box_w, box_h };
     return map_policy_impl("pre3_map_policy_seeded", c, step, min_features, convert_threshold, std_pxl, strict_reference, K, cand_uv, cand_xyz, cand_desc, &sd,
                            order_out, del_out, n_del_out, accepted_out, n_acc_out, converted_out, stats);
+}
+
+// map_management.m:27-79 with initialize_features.m:95-99 in front of it, from two resident frames
+int pre3_map_policy_frames_seeded(pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, int step, int min_features, double convert_threshold,
+                                  double std_pxl, int strict_reference, int box_w, int box_h, uint64_t seed, uint64_t seq, int32_t *K_out, double *match_out,
+                                  int32_t *order_out, int32_t *del_out, int32_t *n_del_out, int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out,
+                                  int32_t stats[4])
+{
+    const char *who = "pre3_map_policy_frames_seeded";
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_CHECK(prev != nullptr && cur != nullptr, PRE3_E_ARG, "%s: null handle", who);
+    PRE3_CHECK(prev != cur, PRE3_E_ARG, "%s: prev and cur are the same handle", who);
+    PRE3_CHECK(std::isfinite(thresh) && thresh > 0.0, PRE3_E_ARG, "%s: thresh must be positive and finite", who);
+    FrameCand fc{};
+    fc.prev = prev; fc.cur = cur; fc.thresh = thresh; fc.K_out = K_out; fc.match_out = match_out;
+    PRE3_TRY(sr_frame_view(prev, &fc.v1)); PRE3_TRY(sr_frame_view(cur, &fc.v2));
+    PRE3_CHECK(fc.v1.device == fc.v2.device && fc.v1.rows == fc.v2.rows && fc.v1.cols == fc.v2.cols, PRE3_E_ARG,
+               "%s: the frames differ (device %d, %d x %d against device %d, %d x %d)", who, fc.v1.device, fc.v1.rows, fc.v1.cols, fc.v2.device, fc.v2.rows, fc.v2.cols);
+    PRE3_CHECK(fc.v1.device == c->device, PRE3_E_ARG, "%s: the frames are on device %d, the context on device %d", who, fc.v1.device, c->device);
+    PRE3_TRY(sr_frame_keypoint_view(prev, &fc.k1)); PRE3_TRY(sr_frame_keypoint_view(cur, &fc.k2));
+    PRE3_CHECK(fc.k1.ND == DESC_DIM && fc.k2.ND == DESC_DIM, PRE3_E_ARG, "%s: descriptors of %d and %d entries (the matcher's tile is written for %d)", who,
+               fc.k1.ND, fc.k2.ND, DESC_DIM);
+    PRE3_CHECK(fc.k1.gate == 0, PRE3_E_ARG, "%s: prev's keypoints went through gate %d; the candidates' rho comes from gate 0 (the depth gate)", who, fc.k1.gate);
+    const int K = fc.k2.n_kept > 0 ? fc.k1.n_kept : 0;             // the cap: pnum <= n1; siftmatch against an empty set matches nothing
+    const CandSeed sd{ seed, seq, box_w, box_h };
+    return map_policy_impl(who, c, step, min_features, convert_threshold, std_pxl, strict_reference, K, nullptr, nullptr, nullptr, &sd, order_out, del_out,
+                           n_del_out, accepted_out, n_acc_out, converted_out, stats, &fc);
 }
 
 // Weighted_Smpl_wo_replacement.m on its own: the keys and the order of K candidates, stateless, on the pooled device scratch

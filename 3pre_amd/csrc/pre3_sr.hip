@@ -33,6 +33,7 @@ struct pre3_sr_frame {
     // the last keypoint call's result, still in `kp` (sr_frame_keypoint_view): kp_valid 0 = none yet, or stale after a load
     int kp_valid = 0, kp_K = 0, kp_ldf = 0, kp_ND = 0, kp_gate = 0, kp_n = 0;
     size_t kp_o_frm = 0, kp_o_des = 0;      // offsets of frm_out / des_out inside kp
+    size_t kp_o_xyz = 0, kp_o_rho = 0, kp_o_idx = 0;      // ... of xyz_out / rho_out (written by gate 0 only) and keep_idx
     // the pair stage's work block, its pinned image and the event other streams wait for (pre3_vopair.hip), allocated on its first use
     void *pair_dev = nullptr, *pair_pin = nullptr;
     size_t pair_dev_bytes = 0, pair_pin_bytes = 0;
@@ -233,6 +234,10 @@ int sr_frame_keypoint_view(pre3_sr_frame *f, SrKeypointView *v)
     v->K = f->kp_K; v->ldf = f->kp_ldf; v->ND = f->kp_ND; v->gate = f->kp_gate; v->n_kept = f->kp_n;
     v->frm = f->kp_n > 0 ? (const double *)((const char *)f->kp + f->kp_o_frm) : nullptr;
     v->des = f->kp_n > 0 ? (const double *)((const char *)f->kp + f->kp_o_des) : nullptr;
+    const bool depth = f->kp_n > 0 && f->kp_gate == 0;
+    v->xyz = depth ? (const double *)((const char *)f->kp + f->kp_o_xyz) : nullptr;
+    v->rho = depth ? (const double *)((const char *)f->kp + f->kp_o_rho) : nullptr;
+    v->keep_idx = f->kp_n > 0 ? (const int32_t *)((const char *)f->kp + f->kp_o_idx) : nullptr;
     return PRE3_OK;
 }
 
@@ -419,7 +424,7 @@ static int sr_keypoints_impl(pre3_sr_frame *f, int gate, int ldf, int K, const d
     const int n = *f->pinned_n;
     PRE3_CHECK(n >= 0 && n <= K, PRE3_E_HIP, "pre3_sr_frame_keypoints: the device kept %d of %d keypoints", n, K);
     *n_kept = n;
-    f->kp_n = n; f->kp_o_frm = o_frm_out; f->kp_o_des = o_des_out;
+    f->kp_n = n; f->kp_o_frm = o_frm_out; f->kp_o_des = o_des_out; f->kp_o_xyz = o_xyz; f->kp_o_rho = o_rho; f->kp_o_idx = o_idx;
     if (n == 0) return PRE3_OK;
     if (keep_idx) PRE3_HIP(hipMemcpyAsync(keep_idx, a.keep_idx, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, f->stream));
     if (frm_out) PRE3_HIP(hipMemcpyAsync(frm_out, a.frm_out, sizeof(double) * (size_t)n * ldf, hipMemcpyDeviceToHost, f->stream));

@@ -30,7 +30,10 @@ struct VoPairHeader {
     int32_t rst;        // vo_rst(pnum)
     int32_t bad;        // k_vo_gather's flags: bit 0 a match names a keypoint that does not exist, bit 1 a keypoint rounds to a pixel outside the image
     int32_t capped;     // hypotheses with a position that hit the redraw cap
-    int32_t pad[12];
+    int32_t cand_bad;   // k_fc_gather's flags (pre3_map.hip); the pair call leaves it at zero
+    int32_t pad[11];
 };
+// k_fc_gather's flags
+constexpr int FC_BAD_PIXEL = 1, FC_BAD_RHO = 2, FC_BAD_DESC = 4, FC_BAD_INDEX = 8;
 
 }  // namespace pre3

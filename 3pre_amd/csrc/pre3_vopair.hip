@@ -121,6 +121,24 @@ void vo_no_solution(pre3_vo_result *res)
 
 }  // namespace
 
+static size_t vp_part_each(int n1, int n2) { return up16(sizeof(double) * (size_t)ceil_div(n2, ICS_T) * n1); }
+size_t vp_match_part_bytes(int n1, int n2) { return 3 * vp_part_each(n1, n2); }      // pb | ps | pa (pa needs half of its share)
+
+int launch_vp_match(int n1, int n2, const double *des1, const double *des2, double thresh, void *part, double *match, void *hdr_dev, hipStream_t st)
+{
+    const int ntn = ceil_div(n2, ICS_T);
+    char *p = (char *)part;
+    IcMatchRide r{};
+    r.ntn = ntn; r.N = n1; r.K2 = n2; r.n_blocks = ntn * ceil_div(n1, ICS_T);
+    r.bank = des1; r.scan = des2; r.has_h = nullptr;
+    r.pb = (double *)p; r.ps = (double *)(p + vp_part_each(n1, n2)); r.pa = (int32_t *)(p + 2 * vp_part_each(n1, n2));
+    hipLaunchKernelGGL(k_vp_match, dim3(r.n_blocks), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(k_vp_pairs, dim3(1), dim3(VP_NTH), 0, st, n1, ntn, (float)thresh, (const double *)r.pb, (const double *)r.ps, (const int32_t *)r.pa, match,
+                       (VoPairHeader *)hdr_dev);
+    PRE3_HIP(hipGetLastError());
+    return PRE3_OK;
+}
+
 }  // namespace pre3
 
 using namespace pre3;
@@ -148,13 +166,12 @@ int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, 
     if (n1 == 0 || n2 == 0) { vo_no_solution(res); return PRE3_OK; }      // siftmatch of an empty set: no match, nothing to queue
 
     // [header | VoOut | match | pset1 | pset2 | draws | cnum | state | inliers] come back in one transfer; the partials and the masks stay
-    const int ntn = ceil_div(n2, ICS_T), wcap = ceil_div(n1, 64);
+    const int wcap = ceil_div(n1, 64);
     const size_t o_out = sizeof(VoPairHeader), o_match = up16(o_out + sizeof(VoOut)), o_p1 = o_match + up16(sizeof(double) * 2 * (size_t)n1);
     const size_t o_p2 = o_p1 + up16(sizeof(double) * 3 * (size_t)n1), o_draws = o_p2 + up16(sizeof(double) * 3 * (size_t)n1);
     const size_t o_cnum = o_draws + up16(sizeof(int32_t) * 4 * VO_RST_CAP), o_state = o_cnum + up16(sizeof(int32_t) * VO_RST_CAP);
     const size_t o_inl = o_state + up16(sizeof(int32_t) * VO_RST_CAP), o_end = o_inl + up16(sizeof(int32_t) * (size_t)n1);
-    const size_t o_pb = o_end, o_ps = o_pb + up16(sizeof(double) * (size_t)ntn * n1), o_pa = o_ps + up16(sizeof(double) * (size_t)ntn * n1);
-    const size_t o_masks = o_pa + up16(sizeof(int32_t) * (size_t)ntn * n1), total = o_masks + sizeof(unsigned long long) * (size_t)VO_RST_CAP * wcap;
+    const size_t o_part = o_end, o_masks = o_part + vp_match_part_bytes(n1, n2), total = o_masks + sizeof(unsigned long long) * (size_t)VO_RST_CAP * wcap;
     size_t need = o_match;                      // the prefix of the block the caller's outputs reach into
     if (match_out) need = o_p1;
     if (pset1_out) need = o_p2;
@@ -177,11 +194,7 @@ int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, 
     double *match = (double *)(d + o_match), *p1 = (double *)(d + o_p1), *p2 = (double *)(d + o_p2);
     int32_t *draws = (int32_t *)(d + o_draws), *cnum = (int32_t *)(d + o_cnum), *state = (int32_t *)(d + o_state), *inl = (int32_t *)(d + o_inl);
     unsigned long long *masks = (unsigned long long *)(d + o_masks);
-    IcMatchRide r{};
-    r.ntn = ntn; r.N = n1; r.K2 = n2; r.n_blocks = ntn * ceil_div(n1, ICS_T);
-    r.bank = k1.des; r.scan = k2.des; r.has_h = nullptr; r.pb = (double *)(d + o_pb); r.ps = (double *)(d + o_ps); r.pa = (int32_t *)(d + o_pa);
-    hipLaunchKernelGGL(k_vp_match, dim3(r.n_blocks), dim3(256), 0, st, r);
-    hipLaunchKernelGGL(k_vp_pairs, dim3(1), dim3(VP_NTH), 0, st, n1, ntn, (float)thresh, (const double *)r.pb, (const double *)r.ps, (const int32_t *)r.pa, match, hdr);
+    PRE3_TRY(launch_vp_match(n1, n2, k1.des, k2.des, thresh, d + o_part, match, hdr, st));
     const VpFrame f1{ v1.x, v1.y, v1.z, k1.frm, k1.ldf, n1 }, f2{ v2.x, v2.y, v2.z, k2.frm, k2.ldf, n2 };
     hipLaunchKernelGGL(k_vp_gather, dim3(ceil_div(n1, 64), 2), dim3(64), 0, st, v2.rows, v2.cols, f1, f2, (const double *)match, p1, p2, hdr);
     hipLaunchKernelGGL(k_vp_dist, dim3(1), dim3(64), 0, st, (const VoPairHeader *)hdr, (const double *)p2, out);

@@ -374,6 +374,27 @@ class EkfFilter:
         return dict(deleted=dl[:nd.value].copy(), accepted=acc[:na.value].copy(), converted=conv[:N0].copy(), measured=int(st[0]),
                     target=int(st[1]), examined=int(st[2]), N=int(st[3]), order=order[:K].copy())
 
+    def map_management_policy_frames_seeded(self, step, prev, cur, seed, seq=0, thresh=1.5, box=(176, 144), min_features=50,
+                                            linearity_index_threshold=0.1, std_pxl=None, strict_reference=True):
+        """map_management_policy_seeded with the candidates built on the device from two resident frames (sr4000.SrFrame; initialize_features.m:95-99,
+        DESIGN.md section 22): matches = siftmatch(prev's kept descriptors, cur's kept descriptors, thresh), candidate c is prev's kept keypoint
+        match[0, c] - 1 with its pixel, its rho (prev's last keypoints() call must have been gate 0) and its descriptor.  Returns
+        map_management_policy_seeded's dict plus match (2, K), 1-based positions in the kept sets, and K; accepted holds candidate indices c."""
+        n1 = max(int(prev.n_kept), 1)
+        N0 = self.N
+        dl, acc, conv = np.zeros(max(N0, 1), np.int32), np.zeros(n1, np.int32), np.zeros(max(N0, 1), np.int32)
+        order, match = np.zeros(n1, np.int32), np.zeros((2, n1), order="F")
+        K, nd, na, st = C.c_int32(0), C.c_int32(0), C.c_int32(0), np.zeros(4, np.int32)
+        thr = -1.0 if linearity_index_threshold is None else float(linearity_index_threshold)
+        check(lib.pre3_map_policy_frames_seeded(self._ctx, prev._h, cur._h, float(thresh), int(step), int(min_features), thr,
+                                                float(self.std_z if std_pxl is None else std_pxl), int(bool(strict_reference)), int(box[0]), int(box[1]),
+                                                int(seed), int(seq), C.byref(K), dptr(match), dptr(order), dptr(dl), C.byref(nd), dptr(acc), C.byref(na),
+                                                dptr(conv), dptr(st)))
+        self._refresh_map()
+        K = K.value
+        return dict(deleted=dl[:nd.value].copy(), accepted=acc[:na.value].copy(), converted=conv[:N0].copy(), measured=int(st[0]),
+                    target=int(st[1]), examined=int(st[2]), N=int(st[3]), order=order[:K].copy(), match=match[:, :K].copy(order="F"), K=K)
+
     # ---- IC search on the device (search_IC_matches.m:31-44 + matching_sift_based.m:104-149)
     def set_descriptors(self, desc, first=0):
         """features_info(first+i).Descriptor; desc is (128, count) as MATLAB stores it (or (count, 128) C-order rows)."""

@@ -8,6 +8,7 @@ readers and keypoint filters over the C ABI.
     SIFT_extract_save.m:68-88 over inittialize_depth_my_version.m:16-92 -> sift_extract (the SCAN_SIFT dict scanio.save_sift_result writes)
     code_from_dr_ye/vodometry_dr_ye.m:139-236                -> vodometry_dr_ye        (two resident frames, gate 1 on each, then vo.vo_pair_seeded)
     Calculate_V_Omega_RANSAC_dr_ye.m:25-50                   -> calculate_v_omega      (T, q, R, sta)
+    initialize_features.m:95-99 + map_management.m:27-79     -> initialize_features_frames (two resident frames, gate 0 on each, then the policy)
 
 All compute runs in libpre3.so on the GPU; this module reads the text file and marshals numpy arrays.
 """
@@ -201,3 +202,27 @@ def calculate_v_omega(dat1, dat2, sift1, sift2, seed, seq=0, **kw):
     out = vodometry_dr_ye(dat1, dat2, sift1, sift2, seed, seq, **kw)
     ok = out["sta"] == 1
     return out["u"][:3].copy(), out["u"][3:].copy(), (out["rot"].copy() if ok else np.eye(3)), out["sta"]
+
+
+def initialize_features_frames(filt, step, dat_prev, dat_cur, sift_prev, sift_cur, seed, seq=0, thresh=1.5, mode=MODE_XYZ, device=0, frames=None, **policy):
+    """initialize_features.m:95-99 in front of map_management.m:27-79 on the files dat_prev, dat_cur (the previous and the current scan) and their SIFT
+    sets = (frames (>=2, K), descriptors (128, K)): each file is conditioned on the device and stays there, the depth gate (gate 0,
+    SIFT_extract_save.m:71-88) keeps Descriptor / SCALE_ORIENT_POS / XYZ_DATA of each scan, then
+    EkfFilter.map_management_policy_frames_seeded matches the two kept sets, takes the candidates from the previous scan and runs the policy on `filt`.
+    Returns that call's dict plus kept_prev / kept_cur (each scan's keep_idx: match holds 1-based positions in those lists) and cand_idx, the caller's
+    index into sift_prev of every candidate.  frames: an optional (SrFrame, SrFrame) pair to reuse; policy: min_features, box, std_pxl, ..."""
+    d1, d2 = load_dat(dat_prev), load_dat(dat_cur)
+    own = frames is None
+    f1, f2 = (SrFrame(d1["z"].shape[0], d1["z"].shape[1], device), SrFrame(d2["z"].shape[0], d2["z"].shape[1], device)) if own else frames
+    try:
+        kept = []
+        for f, d, (frm, des) in ((f1, d1, sift_prev), (f2, d2, sift_cur)):
+            f.load(d, mode)
+            kept.append(f.keypoints(frm, des, GATE_DEPTH)["keep_idx"])
+        out = filt.map_management_policy_frames_seeded(step, f1, f2, seed, seq, thresh, **policy)
+    finally:
+        if own:
+            f1.close(); f2.close()
+    out["kept_prev"], out["kept_cur"] = kept
+    out["cand_idx"] = kept[0][out["match"][0].astype(np.int64) - 1] if out["K"] else np.zeros(0, np.int32)
+    return out

@@ -581,6 +581,30 @@ PRE3_API int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double
                                  double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out,
                                  int32_t *cnum_out, int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res);
 
+/* ---- map management's candidate build and policy from two resident frames, in one call ---------------------------------------
+ * map_management.m:27-79 for frame `step` with initialize_features.m:95-99 in front of it: matches = siftmatch(DataPre.Descriptor,
+ * DataCurrent.Descriptor) between the keypoint sets two resident frames hold (pre3_vo_pair_seeded's matcher: prev's kept descriptors the queries), and
+ * candidate c (0-based column of match) is prev's kept keypoint match[0][c] - 1: uv = entries 0 and 1 of its kept frame, rho = the keypoint stage's rho,
+ * descriptor = its kept descriptor.  prev's last pre3_sr_frame_keypoints must have been gate 0 (it supplies rho); cur's may be either gate; ND == 128 on
+ * both.  From there on the call is pre3_map_policy_seeded with K = pnum = size(match, 2): the order rule from (seed, seq, box), the state checks, the
+ * flush of deferred work, outputs and stats are that call's.  pnum never reaches the host before the walk: buffers, grids and the result block are laid
+ * out by the cap n1 = prev's kept count (<= PRE3_POLICY_MAX_CANDIDATES), the real count stays in a device header, and the call ends in ONE host wait.
+ * The accepted candidates' descriptors go from prev's keypoint block into the context's bank on the device.
+ * Outputs (each may be NULL; arrays sized by the caller for n1 candidates): *K_out = pnum; match_out 2 x pnum doubles, column-major, 1-based positions
+ * in the KEPT sets; order_out[pnum]; accepted_out holds candidate indices c (map them through match_out and prev's keep_idx); the rest as
+ * pre3_map_policy_seeded.  pnum == 0 (n1 == 0 or n2 == 0 included) is a result: the deletion, counters and conversion still happen.
+ * Bit-identical to pre3_siftmatch_f64 on the kept descriptors, the gather of prev's kept frames / xyz / descriptors by match[0], and
+ * pre3_map_policy_seeded on those arrays.
+ * A matched keypoint with a non-finite pixel, or a rho that is not finite and positive (gate 0 lets a NaN y or z through): PRE3_E_NUMERIC after the
+ * wait and before the map is touched -- context, book, map and both handles as they were.  PRE3_E_ARG / PRE3_E_STATE before anything is queued, with
+ * the context, the book and both handles unchanged: everything pre3_map_policy_seeded and pre3_vo_pair_seeded refuse, prev's record not gate 0, a
+ * handle on another device than the context.  Calls that share a handle or the context must be serialised by the caller. */
+PRE3_API int pre3_map_policy_frames_seeded(pre3_ctx *ctx, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, int step, int min_features,
+                                           double convert_threshold, double std_pxl, int strict_reference, int box_w, int box_h, uint64_t seed,
+                                           uint64_t seq, int32_t *K_out, double *match_out /* 2 x K, 1-based kept positions */, int32_t *order_out,
+                                           int32_t *del_out, int32_t *n_del_out, int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out,
+                                           int32_t stats[4]);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them

@@ -20,6 +20,7 @@
  *   read_xyz_sr4000.m, read_image_sr4000.m, read_sr4000_data_dr_ye.m   [x, y, z, img, imax, cmax] = pre3_mex('sr_frame', mode, z, x, y, amp, conf)   % conf = [] for none; the frame stays resident
  *   SIFT_extract_save.m:71-88, confidence_filtering.m                  [frm, des, idx, xyz, rho] = pre3_mex('sr_keypoints', gate, frames, descriptors)    % on the resident frame; no filter context needed
  *   vodometry_dr_ye.m:139-236, Calculate_V_Omega_RANSAC_dr_ye.m:41-50  pre3_mex('sr_keep'); ... next frame's 'sr_frame' + 'sr_keypoints' (gate 1) ...; [T, q, R, sta, match, stat] = pre3_mex('vo_pair', seed, seq)
+ *   initialize_features.m:95-99 + map_management.m:27-79               pre3_mex('sr_keep'); ... next frame's 'sr_frame' + 'sr_keypoints' (gate 0 on both) ...; [del, acc, cv, st, order, match] = pre3_mex('map_policy_frames', step, 50, 0.1, std_z, 1, [176 144], seed, step)
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
  * corrcoef_partitioned_mex.c:25-57).  NOT compiled in the build container (no MATLAB / mex.h there).
@@ -423,6 +424,30 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
             if (nout > 4) { out[4] = mxCreateDoubleMatrix(1, K, mxREAL); for (i = 0; i < K; ++i) mxGetPr(out[4])[i] = ord[i] + 1; }
         }
         mxFree(dl); mxFree(acc); mxFree(cv); mxFree(ord); check(rc);
+    }
+    else if (!strcmp(cmd, "map_policy_frames")) { /* [deleted, accepted, converted, stats, order, match] = pre3_mex('map_policy_frames', step, min_features, linearity_thr (< 0: none),
+                                                     std_pxl, strict, [BoxLimX(2) BoxLimY(2)], seed, seq [, thresh = 1.5]): 'map_policy_seeded' with the candidates of
+                                                     initialize_features.m:95-99 built on the device from the frame 'sr_keep' put aside (its 'sr_keypoints' result through gate 0) and
+                                                     the resident one; accepted and order index the columns of match, 1-based; match holds 1-based positions in the kept sets */
+        int N, K1, i, rc; int32_t K = 0, nd = 0, na = 0, st[4] = { 0, 0, 0, 0 }, *dl, *acc, *cv, *ord; double *mt;
+        if (nin < 9 || nin > 10) mexErrMsgTxt("pre3_mex('map_policy_frames', step, min_features, thr, std_pxl, strict, box, seed, seq [, thresh]): eight or nine arguments");
+        if (!g_sr || !g_sr_prev) mexErrMsgTxt("pre3_mex('map_policy_frames'): needs two frames -- 'sr_frame' + 'sr_keypoints', 'sr_keep', then 'sr_frame' + 'sr_keypoints' again");
+        if (mxGetNumberOfElements(in[6]) != 2) mexErrMsgTxt("pre3_mex('map_policy_frames'): box is [BoxLimX(2) BoxLimY(2)]");
+        N = pre3_get_map(g_ctx, NULL); K1 = PRE3_SR_MAX_KEYPOINTS;
+        dl = (int32_t *)mxCalloc(N ? N : 1, sizeof(int32_t)); acc = (int32_t *)mxCalloc(K1, sizeof(int32_t)); cv = (int32_t *)mxCalloc(N ? N : 1, sizeof(int32_t));
+        ord = (int32_t *)mxCalloc(K1, sizeof(int32_t)); mt = (double *)mxCalloc(2 * (size_t)K1, sizeof(double));
+        rc = pre3_map_policy_frames_seeded(g_ctx, g_sr_prev, g_sr, nin > 9 ? mxGetScalar(in[9]) : 1.5, (int)mxGetScalar(in[1]), (int)mxGetScalar(in[2]), mxGetScalar(in[3]),
+                                           mxGetScalar(in[4]), (int)mxGetScalar(in[5]), (int)mxGetPr(in[6])[0], (int)mxGetPr(in[6])[1], (uint64_t)mxGetScalar(in[7]),
+                                           (uint64_t)mxGetScalar(in[8]), &K, mt, ord, dl, &nd, acc, &na, cv, st);
+        if (rc == PRE3_OK) {
+            out[0] = mxCreateDoubleMatrix(1, nd, mxREAL); for (i = 0; i < nd; ++i) mxGetPr(out[0])[i] = dl[i] + 1;
+            if (nout > 1) { out[1] = mxCreateDoubleMatrix(1, na, mxREAL); for (i = 0; i < na; ++i) mxGetPr(out[1])[i] = acc[i] + 1; }
+            if (nout > 2) { out[2] = mxCreateDoubleMatrix(1, N, mxREAL); for (i = 0; i < N; ++i) mxGetPr(out[2])[i] = cv[i]; }
+            if (nout > 3) { out[3] = mxCreateDoubleMatrix(1, 4, mxREAL); for (i = 0; i < 4; ++i) mxGetPr(out[3])[i] = st[i]; }
+            if (nout > 4) { out[4] = mxCreateDoubleMatrix(1, K, mxREAL); for (i = 0; i < K; ++i) mxGetPr(out[4])[i] = ord[i] + 1; }
+            if (nout > 5) { out[5] = mxCreateDoubleMatrix(2, K, mxREAL); memcpy(mxGetPr(out[5]), mt, sizeof(double) * 2 * (size_t)K); }
+        }
+        mxFree(dl); mxFree(acc); mxFree(cv); mxFree(ord); mxFree(mt); check(rc);
     }
     else if (!strcmp(cmd, "set_descriptors")) {   /* pre3_mex('set_descriptors', [features_info.Descriptor] (128xN), first (0-based)) */
         check(pre3_set_descriptors(g_ctx, nin > 2 ? (int)mxGetScalar(in[2]) : 0, (int)mxGetN(in[1]), mxGetPr(in[1])));
