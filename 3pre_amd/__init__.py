@@ -13,10 +13,10 @@ from ._lib import CARTESIAN, F32, F64, INVDEPTH, LIB_PATH, X_K_K, X_K_KM1, Pre3E
 from .ekf import (CHI2INV_2_95, EkfFilter, compute_hypothesis_support_fast, generate_state_vector_pattern,
                   predict_state_and_covariance, update)
 from .matcher import kNearestNeighbors, siftmatch, siftmatch_merge, siftmatch_partial
-from .plane import crop_points, draw_plane_hypotheses, plane_fit, plane_fit_seeded
+from .plane import crop_points, draw_plane_hypotheses, plane_fit, plane_fit_frame, plane_fit_frame_seeded, plane_fit_seeded
 from . import sr4000
 from .sr4000 import SrFrame, load_dat
 
 __all__ = ["EkfFilter", "update", "predict_state_and_covariance", "compute_hypothesis_support_fast", "generate_state_vector_pattern", "siftmatch", "siftmatch_partial", "siftmatch_merge",
-           "kNearestNeighbors", "crop_points", "draw_plane_hypotheses", "plane_fit", "plane_fit_seeded", "sr4000", "SrFrame", "load_dat", "Pre3Error", "device_count", "LIB_PATH", "F64", "F32", "INVDEPTH", "CARTESIAN", "X_K_K", "X_K_KM1",
+           "kNearestNeighbors", "crop_points", "draw_plane_hypotheses", "plane_fit", "plane_fit_seeded", "plane_fit_frame", "plane_fit_frame_seeded", "sr4000", "SrFrame", "load_dat", "Pre3Error", "device_count", "LIB_PATH", "F64", "F32", "INVDEPTH", "CARTESIAN", "X_K_K", "X_K_KM1",
            "CHI2INV_2_95"]

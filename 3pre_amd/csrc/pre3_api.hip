@@ -186,6 +186,28 @@ __global__ __launch_bounds__(64) void k_fc_desc(int n_rows, const int32_t *__res
     double2 *d2 = (double2 *)(bank_dst + (size_t)blockIdx.x * DESC_DIM);
     d2[threadIdx.x] = s2[threadIdx.x];
 }
+// the IC search's scan out of a resident frame's keypoint block (pre3_set_scan_frame): [K2][128] descriptors into scan_desc, 16
+// bytes per lane, and entries 0..3 of every keypoint's frame [K2][ldf] into scan_pos[K2][4] (entries at or beyond ldf: zero), one lane per keypoint --
+// 16-byte reads where ldf is even, 16-byte writes always.  des, frm (when ldf is even), scan_desc and scan_pos are 16-byte aligned (checked on the host).
+__global__ __launch_bounds__(256) void k_scan_frame(int K2, int ldf, const double *__restrict__ frm, const double *__restrict__ des,
+                                                    double *__restrict__ scan_desc, double *__restrict__ scan_pos)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, n16 = K2 * (DESC_DIM / 2);
+    if (i < n16) { reinterpret_cast<double2 *>(scan_desc)[i] = reinterpret_cast<const double2 *>(des)[i]; return; }
+    const int k = i - n16;
+    if (k >= K2) return;
+    const double *fk = frm + (size_t)k * ldf;
+    double2 a, b = make_double2(0.0, 0.0);
+    if ((ldf & 1) == 0) {
+        a = reinterpret_cast<const double2 *>(fk)[0];
+        if (ldf >= 4) b = reinterpret_cast<const double2 *>(fk)[1];
+    } else {
+        a = make_double2(fk[0], fk[1]);
+        b = make_double2(fk[2], ldf > 3 ? fk[3] : 0.0);      // (ldf is odd and >= 2: entry 2 exists)
+    }
+    reinterpret_cast<double2 *>(scan_pos)[2 * (size_t)k] = a;
+    reinterpret_cast<double2 *>(scan_pos)[2 * (size_t)k + 1] = b;
+}
 // the staging block `k` (0, 1: uploads; 2, 3: map management) has been pulled: one read of host memory (after 2 ms: a stream synchronisation)
 int stage_wait(pre3_ctx *c, int k)
 {
@@ -876,6 +898,7 @@ static bool copy_desc_checked(double *__restrict__ dst, const double *__restrict
 }
 
 }  // extern "C"
+bool pre3::desc_copy_checked(double *dst, const double *src, size_t count) { return copy_desc_checked(dst, src, count); }
 // A pinned block of the context for `bytes` of host data on their way to the device: two blocks, used alternately, grown on demand; a block is
 // written again only after the pull of its previous contents has run (its sequence number in the mailbox: stage_wait).  The caller fills *host, enqueues the pull from *dev on the
 // context's stream and calls stage_release.
@@ -962,10 +985,10 @@ int pre3_get_descriptors(pre3_ctx *c, int first, int count, double *desc)
     return PRE3_OK;
 }
 
-int pre3_set_scan(pre3_ctx *c, int K2, const double *descriptor_raw, const double *scale_orient_pos_raw)
+// room for a scan of K2 keypoints and the IC search's partial arrays; *grew (may be null): the buffers were replaced
+static int scan_reserve(pre3_ctx *c, int K2, bool *grew)
 {
-    EntryScope scope(c); PRE3_TRY(scope.rc);
-    PRE3_CHECK(K2 >= 0 && (K2 == 0 || (descriptor_raw && scale_orient_pos_raw)), PRE3_E_ARG, "pre3_set_scan: bad arguments");
+    if (grew) *grew = false;
     if (K2 > c->scan_cap) {
         PRE3_TRY(stream_drain(c, __func__));             // (the buffers being replaced may still be read by queued kernels)
         if (c->scan_desc) (void)hipFree(c->scan_desc);
@@ -980,7 +1003,16 @@ int pre3_set_scan(pre3_ctx *c, int K2, const double *descriptor_raw, const doubl
         c->ic_pcap = np;
         PRE3_TRY(dmalloc(&c->ic_pb, np)); PRE3_TRY(dmalloc(&c->ic_ps, np)); PRE3_TRY(dmalloc(&c->ic_pa, np));
         c->scan_cap = cap;
+        if (grew) *grew = true;
     }
+    return PRE3_OK;
+}
+
+int pre3_set_scan(pre3_ctx *c, int K2, const double *descriptor_raw, const double *scale_orient_pos_raw)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    PRE3_CHECK(K2 >= 0 && (K2 == 0 || (descriptor_raw && scale_orient_pos_raw)), PRE3_E_ARG, "pre3_set_scan: bad arguments");
+    PRE3_TRY(scan_reserve(c, K2, nullptr));
     bool in_bounds = true;
     if (K2) {
         // The frame's scan crosses PCIe from a pinned block of the context's own, enqueued on its stream: the call neither waits for the queued
@@ -1008,6 +1040,44 @@ int pre3_set_scan(pre3_ctx *c, int K2, const double *descriptor_raw, const doubl
     }
     c->scan_K2 = K2;
     return ic_rank_set_scan(c, in_bounds);
+}
+
+// matching_sift_based.m:104,129-135 with the scan taken from a resident frame's keypoint block
+int pre3_set_scan_frame(pre3_ctx *c, pre3_sr_frame *f, int which)
+{
+    const char *who = "pre3_set_scan_frame";
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "%s: null context", who);
+    PRE3_CHECK(f != nullptr, PRE3_E_ARG, "%s: null handle", who);
+    PRE3_CHECK(which == 0 || which == 1, PRE3_E_ARG, "%s: which=%d is neither 0 (the raw set) nor 1 (the kept set)", who, which);
+    SrFrameView v;
+    SrKeypointView kv;
+    PRE3_TRY(sr_frame_view(f, &v));
+    PRE3_CHECK(v.device == c->device, PRE3_E_ARG, "%s: the frame is on device %d, the context on device %d", who, v.device, c->device);
+    PRE3_TRY(sr_frame_keypoint_view(f, &kv));
+    PRE3_CHECK(kv.ND == DESC_DIM, PRE3_E_ARG, "%s: descriptors of %d entries (the IC search matches %d)", who, kv.ND, DESC_DIM);
+    PRE3_CHECK(kv.ldf >= 2, PRE3_E_ARG, "%s: ldf=%d (a frame holds at least the pixel column and row)", who, kv.ldf);
+    const int K2 = which == 0 ? kv.K_in : kv.n_kept;
+    const double *frm = which == 0 ? kv.frm_in : kv.frm, *des = which == 0 ? kv.des_in : kv.des;
+    PRE3_CHECK(K2 == 0 || (frm != nullptr && des != nullptr && ((uintptr_t)des & 15) == 0 && ((uintptr_t)frm & 15) == 0), PRE3_E_HIP,
+               "%s: the keypoint block is not laid out as expected", who);
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    bool grew = false;
+    PRE3_TRY(scan_reserve(c, K2, &grew));
+    if (grew) PRE3_HIP(hipStreamSynchronize(0));         // (the new buffers are zeroed on the null stream, which the context's stream does not wait for)
+    if (K2) {
+        // the hand-off and the release of section 22: the context's stream waits for what the handle's has queued (the keypoint stage has been waited
+        // for already); the handle's stream then waits for the copy, so that a load or a keypoint call that follows cannot overwrite the block under it
+        hipEvent_t ev = nullptr;
+        PRE3_TRY(sr_frame_pair_work(f, 0, 0, nullptr, nullptr, &ev));
+        PRE3_HIP(hipEventRecord(ev, v.stream));
+        PRE3_HIP(hipStreamWaitEvent(c->stream, ev, 0));
+        hipLaunchKernelGGL(k_scan_frame, dim3(ceil_div(K2 * (DESC_DIM / 2) + K2, 256)), dim3(256), 0, c->stream, K2, kv.ldf, frm, des, c->scan_desc, c->scan_pos);
+        PRE3_HIP(hipGetLastError());
+        PRE3_HIP(hipEventRecord(ev, c->stream));
+        PRE3_HIP(hipStreamWaitEvent(v.stream, ev, 0));
+    }
+    c->scan_K2 = K2;
+    return ic_rank_set_scan(c, kv.raw_in_bounds);        // (which = 1: the kept set is a subset of the raw one)
 }
 
 int pre3_ic_search(pre3_ctx *c, double thresh, int strict_reference, int32_t *n_matches_out, int32_t *m_out, int32_t *meas_idx_out,

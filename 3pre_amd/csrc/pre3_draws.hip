@@ -32,9 +32,11 @@ __global__ __launch_bounds__(DB) void k_draw_vo(uint64_t seed, uint64_t seq, int
     vo_draw_lane(blockIdx.x * DB + threadIdx.x, seed, seq, n_hyp, pnum, m1, m2, ms, draws, capped);
 }
 
-__global__ __launch_bounds__(DB) void k_draw_plane(uint64_t seed, uint64_t seq, int n_draw, int npts, const double *__restrict__ pts, int32_t *__restrict__ draws)
+__global__ __launch_bounds__(DB) void k_draw_plane(uint64_t seed, uint64_t seq, int n_draw, int npts, const double *__restrict__ pts, int32_t *__restrict__ draws,
+                                                   const int32_t *__restrict__ flag /* null, or the crop's word: non-zero = a non-finite point, no draw is made */)
 {
     const int h = blockIdx.x * DB + threadIdx.x;
+    if (flag != nullptr && *flag != 0) return;              // (the redraw rule compares norms of the points: a NaN never satisfies it)
     if (h >= n_draw) return;
     int32_t r[3];
     draw_rule_plane(seed, seq, npts, pts, pts + npts, pts + 2 * (size_t)npts, h, r);
@@ -125,9 +127,10 @@ int launch_draw_vo(unsigned long long seed, unsigned long long seq, int n_hyp, i
 }
 
 // pts: [X | Y | Z] of npts cropped points, as k_plane_score reads them
-int launch_draw_plane(unsigned long long seed, unsigned long long seq, int n_draw, int npts, const double *pts_dev, int32_t *draws_dev, hipStream_t st)
+int launch_draw_plane(unsigned long long seed, unsigned long long seq, int n_draw, int npts, const double *pts_dev, int32_t *draws_dev, hipStream_t st,
+                      const int32_t *flag_dev)
 {
-    hipLaunchKernelGGL(k_draw_plane, dim3(ceil_div(n_draw, DB)), dim3(DB), 0, st, (uint64_t)seed, (uint64_t)seq, n_draw, npts, pts_dev, draws_dev);
+    hipLaunchKernelGGL(k_draw_plane, dim3(ceil_div(n_draw, DB)), dim3(DB), 0, st, (uint64_t)seed, (uint64_t)seq, n_draw, npts, pts_dev, draws_dev, flag_dev);
     PRE3_HIP(hipGetLastError());
     return PRE3_OK;
 }

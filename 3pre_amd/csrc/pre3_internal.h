@@ -377,7 +377,9 @@ int stage_release(pre3_ctx *c, int slot);                                       
 int launch_draw_1p(unsigned long long seed, unsigned long long seq, int n_draw, int m, int k, int32_t *hyp_dev, hipStream_t st);
 int launch_draw_vo(unsigned long long seed, unsigned long long seq, int n_hyp, int pnum, const double *m1_dev, const double *m2_dev, int ms, int32_t *draws_dev,
                    int32_t *capped_dev /* zero at launch */, hipStream_t st);
-int launch_draw_plane(unsigned long long seed, unsigned long long seq, int n_draw, int npts, const double *pts_dev, int32_t *draws_dev, hipStream_t st);
+// flag_dev != nullptr: the word k_plane_crop ORs into; non-zero when the launch runs: it leaves at once, the table is not written
+int launch_draw_plane(unsigned long long seed, unsigned long long seq, int n_draw, int npts, const double *pts_dev, int32_t *draws_dev, hipStream_t st,
+                      const int32_t *flag_dev = nullptr);
 // the candidates' weighted order: keys, then their counting rank; cand_out_dev != nullptr: the [K][2] | rho[K] block re-laid in drawn order
 // k_real_dev != nullptr: K is the layout count (grids, the offset of rho behind the pixels) and *k_real_dev <= K, on the device, the number of candidates
 // there are -- work items at or beyond it leave at once; order2_dev != nullptr: a second copy of the order (device memory, for the launches behind)
@@ -397,7 +399,11 @@ int sr_frame_view(pre3_sr_frame *f, SrFrameView *v);      /* PRE3_E_STATE before
 // [n_kept][ND] in the caller's order.  A load makes it stale; a keypoint call with K == 0, or one that fails behind its argument checks, leaves a valid
 // empty one (n_kept == 0, frm == des == nullptr).  PRE3_E_STATE when there is none or it is stale.
 // xyz [n_kept][3] = [-x, -y, z], rho [n_kept] (gate 0 only: null otherwise) and keep_idx [n_kept] sit in the same block.
-struct SrKeypointView { int K, ldf, ND, gate, n_kept; const double *frm, *des; const double *xyz, *rho; const int32_t *keep_idx; };
+// frm_in [K_in][ldf] / des_in [K_in][ND]: the RAW set handed to that call, at the front of the same block (K_in == K, or 0 with null pointers for an
+// empty record); raw_in_bounds: every raw descriptor entry passed copy_desc_checked's test on its way through the handle's staging
+// (pre3_set_scan_frame hands it to ic_rank_set_scan).
+struct SrKeypointView { int K, ldf, ND, gate, n_kept; const double *frm, *des; const double *xyz, *rho; const int32_t *keep_idx;
+                        int K_in; const double *frm_in, *des_in; bool raw_in_bounds; };
 int sr_frame_keypoint_view(pre3_sr_frame *f, SrKeypointView *v);
 int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, void **dev, void **pin, hipEvent_t *ev);      /* pre3_vopair.hip's blocks and event */
 // ---- the match stage of the pair call on its own (pre3_vopair.hip: k_vp_match, k_vp_pairs), for pre3_map_policy_frames_seeded.  des1 [n1][128] the
@@ -407,6 +413,9 @@ size_t vp_match_part_bytes(int n1, int n2);
 int launch_vp_match(int n1, int n2, const double *des1, const double *des2, double thresh, void *part, double *match, void *hdr_dev, hipStream_t st);
 // the accepted candidates' descriptors from a keypoint block into the bank (pre3_api.hip): landmark first + a takes row rows_dev[a] of des_dev [..][128]
 int set_descriptors_rows_dev(pre3_ctx *c, int first, int count, const double *des_dev, const int32_t *rows_dev, int n_rows, bool in_bounds);
+// copy_desc_checked for other translation units (pre3_api.hip): count doubles src -> dst; true when every value is finite with |x| <= 2^60 and no
+// non-zero |x| < 2^-40 (the ranked IC route's bounds)
+bool desc_copy_checked(double *dst, const double *src, size_t count);
 
 // ---- map policy (pre3_map.hip): the rescue-visibility rider of a booked context (one small launch at the post-LI x_k_k), buffers
 int launch_book_vis(pre3_ctx *c);

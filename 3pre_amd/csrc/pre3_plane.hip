@@ -5,7 +5,11 @@
 //   plane_fitting/fitplane.m:47-54                      (least squares on the winner's inliers: the last right singular vector of [XYZ' 1])
 //   plane_fitting/plane_imp_line_par_int_3d.m:56-100    (ray / plane intersection with its parallel test)
 //   aux_code/find_angle_bw_2_vecs.m:12                  (the angle of the sign rule)
-// Two launches behind the upload of the cropped points:
+// Two launches behind the upload of the cropped points -- or, from a resident SR4000 frame (pre3_plane_fit_frame, pre3_heading_from_frame; DESIGN.md
+// section 23), behind k_plane_crop, which gathers the box from the handle's filtered planes into the same point block:
+//   k_plane_crop   one lane per point of the box, adjacent lanes adjacent rows of a column (the planes are column-major): X = -x, Y = -y, Z = z into
+//                  [X | Y | Z] (plane_pack's layout, pre3_planecrop.h's arithmetic); a wave that met a non-finite value ORs 1 into the flag word.  The
+//                  launches behind it read that word first and leave at once when it is set (k_plane_fit reports sta = 5).
 //   k_plane_score  one workgroup per PG hypotheses.  Every lane builds the PG planes from their draws (uniform), then the lanes stride over the points:
 //                  a point is loaded once and tested against the PG planes; ballot + popcount per wave, the four waves summed through LDS.  Every draw
 //                  supplied is scored; no atomics, no workgroup waits for another.
@@ -21,6 +25,7 @@
 
 #include "pre3_internal.h"
 #include "pre3_geomdev.h"
+#include "pre3_planecrop.h"
 
 namespace pre3 {
 
@@ -72,10 +77,21 @@ __device__ inline double ransac_N(int c, int npts)
     return log(1.0 - 0.99) / log(pno);
 }
 
+// the box of a resident frame into the fit's point block; flag (zero at launch) |= 1 when a point of the box is not finite.  Reads stay inside the
+// planes (the host has checked the box against the frame), writes inside [0, 3 npts).
+__global__ __launch_bounds__(PB) void k_plane_crop(PlaneCrop b, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
+                                                   double *__restrict__ pts, int32_t *__restrict__ flag)
+{
+    const int k = blockIdx.x * PB + threadIdx.x;
+    const bool bad = k < b.nr * b.nc && plane_crop_point(b, k, x, y, z, pts);
+    if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1);      // (one word, one value: the result does not depend on the order)
+}
+
 __global__ __launch_bounds__(PB) void k_plane_score(int npts, const double *__restrict__ pts, int n_draw, const int32_t *__restrict__ draws, double t,
-                                                    int32_t *__restrict__ counts)
+                                                    int32_t *__restrict__ counts, const int32_t *__restrict__ flag /* null, or the crop's word */)
 {
     __shared__ int32_t s_cnt[PW][PG];
+    if (flag != nullptr && *flag != 0) return;              // (uniform: a non-finite point in the box, nothing is scored)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h0 = blockIdx.x * PG;
     const double *X = pts, *Y = pts + npts, *Z = pts + 2 * (size_t)npts;
     Plane3 pl[PG];
@@ -175,11 +191,32 @@ __device__ inline bool plane_ray(const double *B, const double *dir, double *p)
 
 __global__ __launch_bounds__(PB) void k_plane_fit(int npts, const double *__restrict__ pts, int n_draw, const int32_t *__restrict__ draws,
                                                   const int32_t *__restrict__ counts, double t, int po, int pr, int transpose,
-                                                  PlaneOut *__restrict__ out, int32_t *__restrict__ inl_out, HeadingSrc *__restrict__ src)
+                                                  PlaneOut *__restrict__ out, int32_t *__restrict__ inl_out, HeadingSrc *__restrict__ src,
+                                                  const int32_t *__restrict__ flag /* null, or the crop's word */)
 {
     __shared__ int s_w[PW], s_M;
     __shared__ double s_m[PW][10];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // ---- a non-finite point in the box of a resident frame (uniform): neither the draws nor the scores were written, and a NaN in the ten sums would
+    // never meet the Jacobi sweep's relative stopping rule.  sta = 5, an empty result, and the heading rows skip on that status.
+    if (flag != nullptr && *flag != 0) {
+        if (inl_out != nullptr) for (int k = tid; k < npts; k += PB) inl_out[k] = 0;
+        if (tid != 0) return;
+        PlaneOut o;
+        for (int i = 0; i < 4; ++i) o.B[i] = 0.0;
+        for (int i = 0; i < 9; ++i) o.R[i] = 0.0;
+        for (int i = 0; i < 3; ++i) { o.p_orig[i] = 0.0; o.p_ray[i] = 0.0; }
+        o.N = 0.0; o.sta = 5; o.n_inliers = 0; o.n_trials = 0; o.best = -1;
+        *out = o;
+        if (src != nullptr) {
+            HeadingSrc hs;
+            hs.sta = 5; hs.pad_ = 0;
+            for (int i = 0; i < 3; ++i) hs.z[i] = 0.0;
+            for (int i = 0; i < 9; ++i) hs.RR[i] = 0.0;
+            *src = hs;
+        }
+        return;
+    }
     const double *X = pts, *Y = pts + npts, *Z = pts + 2 * (size_t)npts;
     // ---- ransac.m:135-215 replayed: thread tid owns trials 4 tid .. 4 tid + 3
     int v[4], run[4], m = 0;
@@ -298,18 +335,17 @@ __global__ __launch_bounds__(PB) void k_plane_fit(int npts, const double *__rest
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------------
 struct PlaneJob {
     int r0, c0, nr, nc, npts, po, pr, n_draw;
-    size_t off_draws, bytes_in, off_counts, off_out, off_inl, bytes_total;
+    size_t off_draws, bytes_in, off_counts, off_out, off_inl, off_flag, bytes_total;      // off_flag: the crop's word (the frame forms)
     size_t bytes_up;            // what crosses PCIe: bytes_in, or the points alone when the draws are made on the device (the seeded forms)
 };
 struct PlaneSeed { unsigned long long seed, seq; };      // k_draw_plane writes the draws region behind the upload
 
 static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-// every host check of both entry points, before anything is launched
-static int plane_check(const char *who, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
-                       int n_draw, const int32_t *draws, PlaneJob *job, bool seeded = false)
+// every host check that needs no coordinate, and the layout of the work block
+static int plane_job(const char *who, int rows, int cols, const int32_t *box, double t, int n_draw, const int32_t *draws, PlaneJob *job, bool seeded)
 {
-    PRE3_CHECK(x_sr && y_sr && z_sr && (draws || seeded), PRE3_E_ARG, "%s: null argument", who);
+    PRE3_CHECK(draws || seeded, PRE3_E_ARG, "%s: null argument", who);
     PRE3_CHECK(rows >= 1 && cols >= 1, PRE3_E_ARG, "%s: a %d x %d image", who, rows, cols);
     const int32_t dflt[4] = { 80, 144, 50, 120 };           // plane_fit_to_data.m:17-18
     const int32_t *b = box ? box : dflt;
@@ -326,20 +362,32 @@ static int plane_check(const char *who, int rows, int cols, const double *x_sr, 
     PRE3_CHECK(t > 0.0 && std::isfinite(t), PRE3_E_ARG, "%s: t must be positive", who);
     for (int i = 0; !seeded && i < 3 * n_draw; ++i)
         PRE3_CHECK(draws[i] >= 0 && draws[i] < j.npts, PRE3_E_ARG, "%s: draws[%d]=%d is not a point of the box (npts=%d)", who, i, draws[i], j.npts);
+    j.n_draw = n_draw;
+    j.off_draws = up16(sizeof(double) * 3 * (size_t)j.npts);      // (16-byte aligned: the frame forms pull a supplied table there on its own)
+    j.bytes_in = up16(j.off_draws + sizeof(int32_t) * 3 * (size_t)n_draw);
+    j.off_counts = j.bytes_in;
+    j.off_out = up16(j.off_counts + sizeof(int32_t) * (size_t)n_draw);
+    j.off_inl = up16(j.off_out + sizeof(PlaneOut));
+    j.off_flag = up16(j.off_inl + sizeof(int32_t) * (size_t)j.npts);
+    j.bytes_total = j.off_flag + 16;
+    j.bytes_up = seeded ? j.off_draws : j.bytes_in;
+    *job = j;
+    return PRE3_OK;
+}
+
+// every host check of the entry points that take the planes from the host, before anything is launched
+static int plane_check(const char *who, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
+                       int n_draw, const int32_t *draws, PlaneJob *job, bool seeded = false)
+{
+    PRE3_CHECK(x_sr && y_sr && z_sr && (draws || seeded), PRE3_E_ARG, "%s: null argument", who);
+    PlaneJob j;
+    PRE3_TRY(plane_job(who, rows, cols, box, t, n_draw, draws, &j, seeded));
     for (int c = 0; c < j.nc; ++c) {
         const size_t o = (size_t)(j.c0 + c) * rows + j.r0;
         for (int r = 0; r < j.nr; ++r)
             PRE3_CHECK(std::isfinite(x_sr[o + r]) && std::isfinite(y_sr[o + r]) && std::isfinite(z_sr[o + r]), PRE3_E_ARG,
                        "%s: a coordinate at row %d, column %d is not finite", who, j.r0 + r + 1, j.c0 + c + 1);
     }
-    j.n_draw = n_draw;
-    j.off_draws = sizeof(double) * 3 * (size_t)j.npts;
-    j.bytes_in = up16(j.off_draws + sizeof(int32_t) * 3 * (size_t)n_draw);
-    j.off_counts = j.bytes_in;
-    j.off_out = up16(j.off_counts + sizeof(int32_t) * (size_t)n_draw);
-    j.off_inl = up16(j.off_out + sizeof(PlaneOut));
-    j.bytes_total = up16(j.off_inl + sizeof(int32_t) * (size_t)j.npts);
-    j.bytes_up = seeded ? up16(j.off_draws) : j.bytes_in;
     *job = j;
     return PRE3_OK;
 }
@@ -352,20 +400,31 @@ static void plane_pack(const PlaneJob &j, int rows, const double *x_sr, const do
         const size_t o = (size_t)(j.c0 + c) * rows + j.r0, d = (size_t)c * j.nr;
         for (int r = 0; r < j.nr; ++r) { X[d + r] = -x_sr[o + r]; Y[d + r] = -y_sr[o + r]; Z[d + r] = z_sr[o + r]; }
     }
+    const size_t end_pts = sizeof(double) * 3 * (size_t)j.npts;
+    if (j.off_draws > end_pts) memset((char *)stage + end_pts, 0, j.off_draws - end_pts);
     if (draws) memcpy((char *)stage + j.off_draws, draws, sizeof(int32_t) * 3 * (size_t)j.n_draw);
-    else if (j.bytes_up > j.off_draws) memset((char *)stage + j.off_draws, 0, j.bytes_up - j.off_draws);
 }
 
-static int plane_launch(const PlaneJob &j, char *buf, double t, int transpose, bool want_inl, HeadingSrc *src, hipStream_t st, const PlaneSeed *sd = nullptr)
+// crop != nullptr (the frame forms): the point block comes from the view's planes by k_plane_crop, queued here in front of the draws; the flag word at
+// j.off_flag is zeroed on `st` first and every launch behind the crop reads it
+static int plane_launch(const PlaneJob &j, char *buf, double t, int transpose, bool want_inl, HeadingSrc *src, hipStream_t st, const PlaneSeed *sd = nullptr,
+                        const SrFrameView *crop = nullptr)
 {
     const double *pts = (const double *)buf;
     const int32_t *draws = (const int32_t *)(buf + j.off_draws);
-    if (sd) PRE3_TRY(launch_draw_plane(sd->seed, sd->seq, j.n_draw, j.npts, pts, (int32_t *)(buf + j.off_draws), st));
+    int32_t *flag = crop ? (int32_t *)(buf + j.off_flag) : nullptr;
+    if (crop) {
+        PRE3_HIP(hipMemsetAsync(flag, 0, 16, st));
+        const PlaneCrop b{ crop->rows, j.r0, j.c0, j.nr, j.nc };
+        hipLaunchKernelGGL(k_plane_crop, dim3(ceil_div(j.npts, PB)), dim3(PB), 0, st, b, crop->x, crop->y, crop->z, (double *)buf, flag);
+        PRE3_HIP(hipGetLastError());
+    }
+    if (sd) PRE3_TRY(launch_draw_plane(sd->seed, sd->seq, j.n_draw, j.npts, pts, (int32_t *)(buf + j.off_draws), st, flag));
     int32_t *counts = (int32_t *)(buf + j.off_counts);
-    hipLaunchKernelGGL(k_plane_score, dim3(ceil_div(j.n_draw, PG)), dim3(PB), 0, st, j.npts, pts, j.n_draw, draws, t, counts);
+    hipLaunchKernelGGL(k_plane_score, dim3(ceil_div(j.n_draw, PG)), dim3(PB), 0, st, j.npts, pts, j.n_draw, draws, t, counts, (const int32_t *)flag);
     PRE3_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_plane_fit, dim3(1), dim3(PB), 0, st, j.npts, pts, j.n_draw, draws, (const int32_t *)counts, t, j.po, j.pr, transpose,
-                       (PlaneOut *)(buf + j.off_out), want_inl ? (int32_t *)(buf + j.off_inl) : (int32_t *)nullptr, src);
+                       (PlaneOut *)(buf + j.off_out), want_inl ? (int32_t *)(buf + j.off_inl) : (int32_t *)nullptr, src, (const int32_t *)flag);
     PRE3_HIP(hipGetLastError());
     return PRE3_OK;
 }
@@ -486,6 +545,30 @@ int pre3_plane_bench(int device, int rows, int cols, const double *x_sr, const d
     return PRE3_OK;
 }
 
+// the wait of the context forms, as pre3_heading_update with applied_out: the gate word, the result block and the error words behind one wait.
+// sta == 5 (the frame forms: a non-finite point in the box) is PRE3_E_NUMERIC with res filled, applied = 0 and a table of zeros.
+static int heading_wait(pre3_ctx *c, const char *who, const PlaneJob &j, int32_t *applied_out, pre3_plane_result *res_out, int32_t *draws_out)
+{
+    int32_t applied = 0;
+    PlaneOut o;
+    PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
+    PRE3_TRY(rows_applied(c, &applied));
+    PRE3_HIP(hipMemcpyAsync(&o, (char *)c->plane_buf + j.off_out, sizeof o, hipMemcpyDeviceToHost, c->stream));
+    if (draws_out) PRE3_HIP(hipMemcpyAsync(draws_out, (char *)c->plane_buf + j.off_draws, sizeof(int32_t) * 3 * (size_t)j.n_draw, hipMemcpyDeviceToHost, c->stream));
+    PRE3_TRY(stream_drain(c, who));
+    if (res_out) plane_result(o, res_out);
+    if (o.sta == 5 && draws_out) memset(draws_out, 0, sizeof(int32_t) * 3 * (size_t)j.n_draw);      // (no draw was made: the region holds an earlier call's)
+    int rc = stats_words(c);
+    if (applied_out) *applied_out = rc == PRE3_OK ? applied : 0;
+    if (rc != PRE3_OK) {
+        (void)hipMemsetAsync(c->stats + 6, 0, sizeof(int32_t) * 2, c->stream);
+        c->mail_host[6] = 0; c->mail_host[7] = 0;
+        PRE3_TRY(stream_drain(c, who));
+    }
+    if (rc == PRE3_OK && o.sta == 5) { set_error("%s: a coordinate inside the box of the resident frame is not finite (sta = 5); x and P are untouched", who); rc = PRE3_E_NUMERIC; }
+    return rc;
+}
+
 static int heading_from_scan_impl(pre3_ctx *c, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
                                   int n_draw, const int32_t *draws, int transpose, int strict_reference, int32_t *applied_out, pre3_plane_result *res_out,
                                   const PlaneSeed *sd, int32_t *draws_out)
@@ -516,23 +599,7 @@ static int heading_from_scan_impl(pre3_ctx *c, int rows, int cols, const double 
     PRE3_TRY(launch_rows_update(c, nullptr, &hd));
     c->hp_all_valid = false;
     if (applied_out == nullptr && res_out == nullptr && draws_out == nullptr) return PRE3_OK;
-    // as pre3_heading_update with applied_out: the gate word, the result block and the error words behind one wait
-    int32_t applied = 0;
-    PlaneOut o;
-    PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
-    PRE3_TRY(rows_applied(c, &applied));
-    PRE3_HIP(hipMemcpyAsync(&o, (char *)c->plane_buf + j.off_out, sizeof o, hipMemcpyDeviceToHost, c->stream));
-    if (draws_out) PRE3_HIP(hipMemcpyAsync(draws_out, (char *)c->plane_buf + j.off_draws, sizeof(int32_t) * 3 * (size_t)n_draw, hipMemcpyDeviceToHost, c->stream));
-    PRE3_TRY(stream_drain(c, __func__));
-    if (res_out) plane_result(o, res_out);
-    const int rc = stats_words(c);
-    if (applied_out) *applied_out = rc == PRE3_OK ? applied : 0;
-    if (rc != PRE3_OK) {
-        (void)hipMemsetAsync(c->stats + 6, 0, sizeof(int32_t) * 2, c->stream);
-        c->mail_host[6] = 0; c->mail_host[7] = 0;
-        PRE3_TRY(stream_drain(c, __func__));
-    }
-    return rc;
+    return heading_wait(c, "pre3_heading_from_scan", j, applied_out, res_out, draws_out);
 }
 
 int pre3_heading_from_scan(pre3_ctx *c, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
@@ -547,6 +614,145 @@ int pre3_heading_from_scan_seeded(pre3_ctx *c, int rows, int cols, const double 
 {
     const PlaneSeed sd{ seed, seq };
     return heading_from_scan_impl(c, rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, nullptr, transpose, strict_reference, applied_out, res_out, &sd, draws_out);
+}
+
+// ---- the same fit and heading update fed from a resident SR4000 frame --------------------------------------------------------
+namespace {
+struct StreamIdle {             // a work block goes back to its pool only once the stream that used it is idle, on every way out
+    hipStream_t st;
+    ~StreamIdle() { (void)hipStreamSynchronize(st); }
+};
+}  // namespace
+
+static int plane_fit_frame_impl(const char *who, pre3_sr_frame *f, const int32_t *box, double t, int n_draw, const int32_t *draws, int32_t *count_out,
+                                int32_t *inlier_out, pre3_plane_result *res, const PlaneSeed *sd, int32_t *draws_out)
+{
+    PlaneJob j;
+    SrFrameView v;
+    PRE3_CHECK(f != nullptr && res != nullptr, PRE3_E_ARG, "%s: null argument", who);
+    PRE3_TRY(sr_frame_view(f, &v));
+    PRE3_TRY(plane_job(who, v.rows, v.cols, box, t, n_draw, draws, &j, sd != nullptr));
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
+    if (hipSetDevice(v.device) != hipSuccess) { set_error("no HIP device %d", v.device); return PRE3_E_NODEVICE; }
+    PlaneScratch d;
+    PRE3_TRY(scratch_acquire(j.bytes_total, &d.p, &d.slot));
+    StreamIdle idle{ v.stream };
+    PlaneOut o;
+    {
+        std::lock_guard<std::mutex> lk(g_stage.mu);
+        const size_t b_draws = j.bytes_in - j.off_draws;
+        if (draws != nullptr) {                             // the table is the only thing that crosses PCIe
+            if (g_stage.cap < b_draws) {
+                if (g_stage.p) (void)hipHostFree(g_stage.p);
+                g_stage.p = nullptr; g_stage.cap = 0;
+                const size_t cap = (b_draws + 65535) & ~(size_t)65535;
+                PRE3_HIP(hipHostMalloc(&g_stage.p, cap, hipHostMallocDefault));
+                g_stage.cap = cap;
+            }
+            memset(g_stage.p, 0, b_draws);
+            memcpy(g_stage.p, draws, sizeof(int32_t) * 3 * (size_t)n_draw);
+            PRE3_HIP(hipMemcpyAsync((char *)d.p + j.off_draws, g_stage.p, b_draws, hipMemcpyHostToDevice, v.stream));
+        }
+        PRE3_TRY(plane_launch(j, (char *)d.p, t, 0, inlier_out != nullptr, nullptr, v.stream, sd, &v));
+        PRE3_HIP(hipMemcpyAsync(&o, (char *)d.p + j.off_out, sizeof o, hipMemcpyDeviceToHost, v.stream));
+        PRE3_HIP(hipStreamSynchronize(v.stream));           // (the staging block is free again)
+    }
+    plane_result(o, res);
+    if (o.sta == 5) {                                       // neither the table nor the scores were written
+        if (count_out) memset(count_out, 0, sizeof(int32_t) * (size_t)n_draw);
+        if (inlier_out) memset(inlier_out, 0, sizeof(int32_t) * (size_t)j.npts);
+        if (draws_out) memset(draws_out, 0, sizeof(int32_t) * 3 * (size_t)n_draw);
+        set_error("%s: a coordinate inside the box of the resident frame is not finite (sta = 5)", who);
+        return PRE3_E_NUMERIC;
+    }
+    if (count_out) PRE3_HIP(hipMemcpy(count_out, (char *)d.p + j.off_counts, sizeof(int32_t) * (size_t)n_draw, hipMemcpyDeviceToHost));
+    if (inlier_out) PRE3_HIP(hipMemcpy(inlier_out, (char *)d.p + j.off_inl, sizeof(int32_t) * (size_t)j.npts, hipMemcpyDeviceToHost));
+    if (draws_out) PRE3_HIP(hipMemcpy(draws_out, (char *)d.p + j.off_draws, sizeof(int32_t) * 3 * (size_t)n_draw, hipMemcpyDeviceToHost));
+    return PRE3_OK;
+}
+
+int pre3_plane_fit_frame(pre3_sr_frame *f, const int32_t *box, double t, int n_draw, const int32_t *draws, int32_t *count_out, int32_t *inlier_out,
+                         pre3_plane_result *res)
+{
+    return plane_fit_frame_impl("pre3_plane_fit_frame", f, box, t, n_draw, draws, count_out, inlier_out, res, nullptr, nullptr);
+}
+
+int pre3_plane_fit_frame_seeded(pre3_sr_frame *f, const int32_t *box, double t, int n_draw, uint64_t seed, uint64_t seq, int32_t *draws_out,
+                                int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res)
+{
+    const PlaneSeed sd{ seed, seq };
+    return plane_fit_frame_impl("pre3_plane_fit_frame_seeded", f, box, t, n_draw, nullptr, count_out, inlier_out, res, &sd, draws_out);
+}
+
+// a block of the context that the frame form allocates: zeroed on the context's stream, which does not synchronise with the null stream
+static int plane_dmalloc(pre3_ctx *c, void **p, size_t bytes)
+{
+    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; set_error("hipMalloc of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
+    PRE3_HIP(hipMemsetAsync(*p, 0, bytes, c->stream));
+    return PRE3_OK;
+}
+
+static int heading_from_frame_impl(pre3_ctx *c, pre3_sr_frame *f, const int32_t *box, double t, int n_draw, const int32_t *draws, int transpose,
+                                   int strict_reference, int32_t *applied_out, pre3_plane_result *res_out, const PlaneSeed *sd, int32_t *draws_out)
+{
+    const char *who = "pre3_heading_from_frame";
+    PlaneJob j;
+    SrFrameView v;
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "%s: null context", who);
+    PRE3_CHECK(f != nullptr, PRE3_E_ARG, "%s: null handle", who);
+    PRE3_TRY(sr_frame_view(f, &v));
+    PRE3_CHECK(v.device == c->device, PRE3_E_ARG, "%s: the frame is on device %d, the context on device %d", who, v.device, c->device);
+    PRE3_TRY(plane_job(who, v.rows, v.cols, box, t, n_draw, draws, &j, sd != nullptr));
+    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE,
+               "%s: acts on (x_k_k, p_k_k); the covariance buffer holds the prediction (update first)", who);
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    hipEvent_t ev = nullptr;
+    PRE3_TRY(sr_frame_pair_work(f, 0, 0, nullptr, nullptr, &ev));
+    if (c->plane_bytes < j.bytes_total) {
+        if (c->plane_buf) { PRE3_TRY(stream_drain(c, who)); (void)hipFree(c->plane_buf); }
+        c->plane_buf = nullptr; c->plane_bytes = 0;
+        const size_t cap = j.bytes_total + j.bytes_total / 4;
+        PRE3_TRY(plane_dmalloc(c, &c->plane_buf, cap));
+        c->plane_bytes = cap;
+    }
+    if (c->plane_src == nullptr) { void *p = nullptr; PRE3_TRY(plane_dmalloc(c, &p, sizeof(HeadingSrc))); c->plane_src = (HeadingSrc *)p; }
+    if (draws != nullptr) {                                 // a supplied table: the only bytes that cross PCIe, pulled where plane_pack would have put them
+        const size_t b_draws = j.bytes_in - j.off_draws;
+        void *st = nullptr, *st_dev = nullptr; int slot = 0;
+        PRE3_TRY(stage_acquire(c, b_draws, &st, &st_dev, &slot));
+        memset(st, 0, b_draws);
+        memcpy(st, draws, sizeof(int32_t) * 3 * (size_t)n_draw);
+        PRE3_TRY(launch_pull(c, st, (char *)c->plane_buf + j.off_draws, b_draws, slot));
+        PRE3_TRY(stage_release(c, slot));
+    }
+    // the hand-off: the context's stream waits for the frame's conditioning launches; the release: the handle's stream waits for the crop, so that a
+    // load that follows cannot overwrite planes that are still being read (section 22's pattern)
+    PRE3_HIP(hipEventRecord(ev, v.stream));
+    PRE3_HIP(hipStreamWaitEvent(c->stream, ev, 0));
+    PRE3_TRY(plane_launch(j, (char *)c->plane_buf, t, transpose ? 1 : 0, false, c->plane_src, c->stream, sd, &v));
+    PRE3_HIP(hipEventRecord(ev, c->stream));
+    PRE3_HIP(hipStreamWaitEvent(v.stream, ev, 0));
+    RowsHeading hd{};
+    hd.on = 1; hd.strict = strict_reference ? 1 : 0; hd.src = c->plane_src;
+    c->rows_form = 1;
+    PRE3_TRY(launch_rows_update(c, nullptr, &hd));
+    c->hp_all_valid = false;
+    if (applied_out == nullptr && res_out == nullptr && draws_out == nullptr) return PRE3_OK;
+    return heading_wait(c, who, j, applied_out, res_out, draws_out);
+}
+
+int pre3_heading_from_frame(pre3_ctx *c, pre3_sr_frame *f, const int32_t *box, double t, int n_draw, const int32_t *draws, int transpose,
+                            int strict_reference, int32_t *applied_out, pre3_plane_result *res_out)
+{
+    return heading_from_frame_impl(c, f, box, t, n_draw, draws, transpose, strict_reference, applied_out, res_out, nullptr, nullptr);
+}
+
+int pre3_heading_from_frame_seeded(pre3_ctx *c, pre3_sr_frame *f, const int32_t *box, double t, int n_draw, uint64_t seed, uint64_t seq, int transpose,
+                                   int strict_reference, int32_t *draws_out, int32_t *applied_out, pre3_plane_result *res_out)
+{
+    const PlaneSeed sd{ seed, seq };
+    return heading_from_frame_impl(c, f, box, t, n_draw, nullptr, transpose, strict_reference, applied_out, res_out, &sd, draws_out);
 }
 
 }  // extern "C"

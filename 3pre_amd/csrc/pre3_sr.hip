@@ -32,6 +32,9 @@ struct pre3_sr_frame {
     int32_t *pinned_n = nullptr;    // n_kept
     // the last keypoint call's result, still in `kp` (sr_frame_keypoint_view): kp_valid 0 = none yet, or stale after a load
     int kp_valid = 0, kp_K = 0, kp_ldf = 0, kp_ND = 0, kp_gate = 0, kp_n = 0;
+    int kp_K_in = 0;                        // the raw set of that call, once its transfer is queued: [kp_K_in][ldf] frames at offset 0 of kp,
+    size_t kp_o_des_in = 0;                 // [kp_K_in][ND] descriptors here (sr_frame_keypoint_view: K_in, frm_in, des_in)
+    bool kp_raw_ok = true;                  // its descriptors passed the ranked IC route's bounds on their way through `stage`
     size_t kp_o_frm = 0, kp_o_des = 0;      // offsets of frm_out / des_out inside kp
     size_t kp_o_xyz = 0, kp_o_rho = 0, kp_o_idx = 0;      // ... of xyz_out / rho_out (written by gate 0 only) and keep_idx
     // the pair stage's work block, its pinned image and the event other streams wait for (pre3_vopair.hip), allocated on its first use
@@ -238,6 +241,10 @@ int sr_frame_keypoint_view(pre3_sr_frame *f, SrKeypointView *v)
     v->xyz = depth ? (const double *)((const char *)f->kp + f->kp_o_xyz) : nullptr;
     v->rho = depth ? (const double *)((const char *)f->kp + f->kp_o_rho) : nullptr;
     v->keep_idx = f->kp_n > 0 ? (const int32_t *)((const char *)f->kp + f->kp_o_idx) : nullptr;
+    v->K_in = f->kp_K_in;
+    v->frm_in = f->kp_K_in > 0 ? (const double *)f->kp : nullptr;
+    v->des_in = f->kp_K_in > 0 ? (const double *)((const char *)f->kp + f->kp_o_des_in) : nullptr;
+    v->raw_in_bounds = f->kp_raw_ok;
     return PRE3_OK;
 }
 
@@ -393,6 +400,7 @@ static int sr_keypoints_impl(pre3_sr_frame *f, int gate, int ldf, int K, const d
     *n_kept = 0;
     *touched = true;
     f->kp_valid = 1; f->kp_K = K; f->kp_ldf = ldf; f->kp_ND = ND; f->kp_gate = gate; f->kp_n = 0;      // a valid empty record until the count is in
+    f->kp_K_in = 0; f->kp_o_des_in = 0; f->kp_raw_ok = true;
     if (K == 0) return PRE3_OK;
     // [frm | des] up; [frm_out | des_out | xyz | rho | keep_idx | n_kept] behind them
     const size_t b_frm = up16(sizeof(double) * (size_t)K * ldf), b_des = up16(sizeof(double) * (size_t)K * ND);
@@ -407,9 +415,12 @@ static int sr_keypoints_impl(pre3_sr_frame *f, int gate, int ldf, int K, const d
     }
     PRE3_TRY(sr_grow_stage(f, b_frm + b_des));
     memcpy(f->stage, frm, sizeof(double) * (size_t)K * ldf);
-    if (ND > 0) memcpy((char *)f->stage + b_frm, des, sizeof(double) * (size_t)K * ND);
+    // (the same copy, with the bounds of the ranked IC route noted on the way: pre3_set_scan_frame takes the raw set from this block)
+    if (ND > 0) f->kp_raw_ok = desc_copy_checked((double *)((char *)f->stage + b_frm), des, (size_t)K * ND);
+    f->kp_o_des_in = b_frm;
     char *d = (char *)f->kp;
     PRE3_HIP(hipMemcpyAsync(d, f->stage, b_frm + b_des, hipMemcpyHostToDevice, f->stream));
+    f->kp_K_in = K;
     const size_t npix = (size_t)f->rows * f->cols;
     KpArgs a;
     a.K = K; a.ldf = ldf; a.ND = ND; a.gate = gate; a.rows = f->rows; a.cols = f->cols; a.has_conf = f->has_conf;
@@ -440,7 +451,7 @@ int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K, const do
 {
     bool touched = false;
     const int rc = sr_keypoints_impl(f, gate, ldf, K, frm, ND, des, n_kept, keep_idx, frm_out, des_out, xyz_out, rho_out, &touched);
-    if (rc != PRE3_OK && touched) f->kp_n = 0;                // a call that failed behind its checks leaves a valid empty record
+    if (rc != PRE3_OK && touched) { f->kp_n = 0; f->kp_K_in = 0; }      // a call that failed behind its checks leaves a valid empty record
     return rc;
 }
 

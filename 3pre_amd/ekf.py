@@ -192,6 +192,37 @@ class EkfFilter:
             out["draws"] = draws
         return bool(applied.value), out
 
+    def heading_from_frame(self, frame, draws, box=None, t=0.02, transpose=True, strict_reference=True, wait=True):
+        """heading_from_scan with the range image taken from a resident sr4000.SrFrame: the box is gathered from its filtered
+        planes on the device behind an event on the frame's stream; only the draw table crosses PCIe.  Bit-identical to heading_from_scan fed with
+        frame.planes().  A non-finite coordinate inside the box applies nothing; with wait=True it raises Pre3Error with code -5 (.result: sta = 5)."""
+        from . import plane
+        draws = i32(draws).reshape(-1, 3)
+        args = (self._ctx, frame._h, dptr(plane._box(box)), float(t), draws.shape[0], dptr(draws), int(bool(transpose)), int(bool(strict_reference)))
+        if not wait:
+            check(lib.pre3_heading_from_frame(*args, None, None))
+            return None
+        applied, res = C.c_int32(0), plane.PlaneResult()
+        plane._check_frame(lib.pre3_heading_from_frame(*args, C.byref(applied), C.byref(res)), res)
+        return bool(applied.value), plane._result(res)
+
+    def heading_from_frame_seeded(self, frame, seed, seq=0, n_draw=1001, box=None, t=0.02, transpose=True, strict_reference=True, wait=True,
+                                  return_draws=False):
+        """heading_from_scan_seeded with the range image taken from a resident sr4000.SrFrame: nothing crosses PCIe on the way in, and wait=False
+        returns None at once -- a frame.load() that follows stays behind the gather (the frame's stream waits for it)."""
+        from . import plane
+        args = (self._ctx, frame._h, dptr(plane._box(box)), float(t), int(n_draw), int(seed), int(seq), int(bool(transpose)), int(bool(strict_reference)))
+        if not wait:
+            check(lib.pre3_heading_from_frame_seeded(*args, None, None, None))
+            return None
+        applied, res = C.c_int32(0), plane.PlaneResult()
+        draws = np.zeros((max(int(n_draw), 1), 3), np.int32) if return_draws else None
+        plane._check_frame(lib.pre3_heading_from_frame_seeded(*args, dptr(draws), C.byref(applied), C.byref(res)), res)
+        out = plane._result(res)
+        if return_draws:
+            out["draws"] = draws
+        return bool(applied.value), out
+
     def rows_form(self):
         """PRE3_OPT_ROWS_FORM: 1 if the last update() / ekf_heading_update() took the single-sweep form, 0 the general route"""
         v = C.c_int(0)
@@ -414,6 +445,11 @@ class EkfFilter:
         p = np.ascontiguousarray(np.asarray(SCALE_ORIENT_POS_RAW, dtype=np.float64).reshape(4, -1).T)
         assert d.shape[0] == p.shape[0], "Descriptor_RAW and SCALE_ORIENT_POS_RAW disagree on K2"
         check(lib.pre3_set_scan(self._ctx, int(d.shape[0]), dptr(d), dptr(p)))
+
+    def set_scan_frame(self, frame, which=0):
+        """load_scan from a resident sr4000.SrFrame: which=0 the raw set handed to its last keypoints() call (Descriptor_RAW /
+        SCALE_ORIENT_POS_RAW, what matching_sift_based.m reads), which=1 the set that call kept.  One copy on the device, no wait."""
+        check(lib.pre3_set_scan_frame(self._ctx, frame._h, int(which)))
 
     def matching_sift_based(self, thresh=1.5, strict_reference=True):
         """The whole IC-search stage in one call; the accepted matches become the measurement list."""

@@ -4,6 +4,8 @@
     plane_fitting/ransac.m:142-176      -> draw_plane_hypotheses (the reference's rejection rule, any numpy Generator)
     plane_fitting/ransac.m:142-176      -> plane_fit_seeded (the same rule on the device, from (seed, seq))
     plane_fit_to_data.m:7-149           -> plane_fit (RANSAC over the draws, refit, sign rule, R), EkfFilter.heading_from_scan in ekf.py
+    plane_fit_to_data.m:7-149           -> plane_fit_frame, plane_fit_frame_seeded (the same fit on a resident sr4000.SrFrame: the box is gathered
+                                           from its filtered planes on the device), EkfFilter.heading_from_frame in ekf.py
 
 All compute runs in libpre3.so on the GPU; this module marshals numpy arrays and draws random numbers.
 """
@@ -105,6 +107,52 @@ def plane_fit_seeded(x_sr, y_sr, z_sr, seed, seq=0, n_draw=MAX_DRAWS, box=None, 
     res = PlaneResult()
     check(lib.pre3_plane_fit_seeded(int(device), rows, cols, dptr(imgs[0]), dptr(imgs[1]), dptr(imgs[2]), dptr(bx), float(t), n_draw, int(seed), int(seq),
                                     dptr(draws), dptr(counts), dptr(inl), C.byref(res)))
+    out = _result(res)
+    out["counts"], out["inliers"], out["draws"] = counts[:n_draw], inl[:npts].astype(bool), draws[:n_draw]
+    return out
+
+
+def _frame_box(who, frame, box):
+    bx = _box(box)
+    if bx is not None and bx.shape[0] != 4:
+        raise Pre3Error(-1, "%s: box is (row0, row1, col0, col1)" % who)
+    r0, r1, c0, c1 = DEFAULT_BOX if bx is None else bx
+    return bx, max(0, int(r1) - int(r0) + 1) * max(0, int(c1) - int(c0) + 1)
+
+
+def _check_frame(rc, res):
+    """check() that hands the result block of a refused box to the caller: Pre3Error.result (sta = 5) on PRE3_E_NUMERIC"""
+    try:
+        check(rc)
+    except Pre3Error as e:
+        if e.code == -5:
+            e.result = _result(res)
+        raise
+
+
+def plane_fit_frame(frame, draws, box=None, t=0.02):
+    """plane_fit on the filtered planes a resident sr4000.SrFrame holds: the box is gathered on the device, only the draw table
+    crosses PCIe.  The dict is plane_fit's, bit for bit what plane_fit(*frame.planes()[:3], draws, box, t) returns.  A non-finite coordinate inside the
+    box raises Pre3Error with code -5 (PRE3_E_NUMERIC); its .result carries sta = 5."""
+    draws = i32(draws).reshape(-1, 3)
+    bx, npts = _frame_box("plane_fit_frame", frame, box)
+    counts, inl = np.zeros(max(draws.shape[0], 1), np.int32), np.zeros(max(npts, 1), np.int32)
+    res = PlaneResult()
+    _check_frame(lib.pre3_plane_fit_frame(frame._h, dptr(bx), float(t), draws.shape[0], dptr(draws), dptr(counts), dptr(inl), C.byref(res)), res)
+    out = _result(res)
+    out["counts"], out["inliers"] = counts[:draws.shape[0]], inl[:npts].astype(bool)
+    return out
+
+
+def plane_fit_frame_seeded(frame, seed, seq=0, n_draw=MAX_DRAWS, box=None, t=0.02):
+    """plane_fit_seeded on the filtered planes a resident sr4000.SrFrame holds: nothing crosses PCIe on the way in.  The dict also carries draws."""
+    bx, npts = _frame_box("plane_fit_frame_seeded", frame, box)
+    n_draw = int(n_draw)
+    nd = min(max(n_draw, 1), MAX_DRAWS)
+    draws, counts, inl = np.zeros((nd, 3), np.int32), np.zeros(nd, np.int32), np.zeros(max(npts, 1), np.int32)
+    res = PlaneResult()
+    _check_frame(lib.pre3_plane_fit_frame_seeded(frame._h, dptr(bx), float(t), n_draw, int(seed), int(seq), dptr(draws), dptr(counts), dptr(inl),
+                                                 C.byref(res)), res)
     out = _result(res)
     out["counts"], out["inliers"], out["draws"] = counts[:n_draw], inl[:npts].astype(bool), draws[:n_draw]
     return out

@@ -9,6 +9,7 @@ readers and keypoint filters over the C ABI.
     code_from_dr_ye/vodometry_dr_ye.m:139-236                -> vodometry_dr_ye        (two resident frames, gate 1 on each, then vo.vo_pair_seeded)
     Calculate_V_Omega_RANSAC_dr_ye.m:25-50                   -> calculate_v_omega      (T, q, R, sta)
     initialize_features.m:95-99 + map_management.m:27-79     -> initialize_features_frames (two resident frames, gate 0 on each, then the policy)
+    plane_fit_to_data.m:7-149                                -> plane_fit_to_data      (the fit on a resident frame, plane.plane_fit_frame_seeded)
 
 All compute runs in libpre3.so on the GPU; this module reads the text file and marshals numpy arrays.
 """
@@ -171,6 +172,15 @@ def sift_extract(frames, descriptors, frame, idx_scan, image=None):
     return dict(idxScan=int(idx_scan), Image=frame.image() if image is None else np.asarray(image),
                 Descriptor_RAW=np.array(descriptors, dtype=np.float64), SCALE_ORIENT_POS_RAW=np.array(frames, dtype=np.float64),
                 Descriptor=out["descriptors"], SCALE_ORIENT_POS=out["frames"], XYZ_DATA=out["xyz"], initial_rho=out["rho"], keep_idx=out["keep_idx"])
+
+
+def plane_fit_to_data(frame, seed, seq=0, n_draw=1001, box=None, t=0.02):
+    """[R, T] = plane_fit_to_data(idx) with the scan already resident (plane_fit_to_data.m:13 reads read_xyz_sr4000: a frame loaded in mode 0): the box
+    is gathered from the frame's filtered planes on the device and nothing is read back to be sent again.  Returns
+    plane.plane_fit_frame_seeded's dict; R = out["R"], and mono_slam.m:192 passes R' to the heading update (EkfFilter.heading_from_frame_seeded does
+    both in one call)."""
+    from . import plane
+    return plane.plane_fit_frame_seeded(frame, seed, seq, n_draw, box, t)
 
 
 def vodometry_dr_ye(dat1, dat2, sift1, sift2, seed, seq=0, thresh=1.5, device=0, frames=None):

@@ -246,7 +246,9 @@ typedef struct pre3_plane_result {
     double p_orig[3], p_ray[3];
     double N;               /* ransac.m's N when the loop ended */
     int32_t sta;            /* 1 ok; 0 no trial had an inlier (ransac.m:224; B = 0); 2 the rule wanted more trials than n_draw (the result is that of
-                               the n_draw trials); 3 the axes are undefined (a ray parallel to the plane, or a zero y_axis; B is valid) */
+                               the n_draw trials); 3 the axes are undefined (a ray parallel to the plane, or a zero y_axis; B is valid);
+                               5 (the *_frame forms only) a coordinate inside the box of the resident frame is not finite: nothing was drawn, scored
+                               or fitted -- B = R = p_orig = p_ray = N = 0, n_inliers = n_trials = 0, best = -1 */
     int32_t n_inliers, n_trials, best;   /* best 0-based: the first trial with the largest score; -1 when sta == 0 */
 } pre3_plane_result;
 /* x_sr, y_sr, z_sr: rows x cols column-major, SR4000 coordinates.  box = {row0, row1, col0, col1}, 1-based inclusive (NULL: {80, 144, 50, 120},
@@ -604,6 +606,48 @@ PRE3_API int pre3_map_policy_frames_seeded(pre3_ctx *ctx, pre3_sr_frame *prev, p
                                            uint64_t seq, int32_t *K_out, double *match_out /* 2 x K, 1-based kept positions */, int32_t *order_out,
                                            int32_t *del_out, int32_t *n_del_out, int32_t *accepted_out, int32_t *n_acc_out, int32_t *converted_out,
                                            int32_t stats[4]);
+
+/* ---- the plane fit, the heading update and the IC search's scan fed from a resident frame --------------------------------------
+ * plane_fit_to_data.m:13-149 over ransacfitplane.m:51-116, ransac.m:113-225, fitplane.m:31-54, plane_imp_line_par_int_3d.m:56-100, as pre3_plane_fit,
+ * on the FILTERED x, y, z a handle holds (what read_xyz_sr4000 returns when the frame was loaded in mode 0, plane_fit_to_data.m:13's input; mode 1 is
+ * taken as it is): the box is gathered from the resident planes on the device into the fit's point block (x = -x_sr, y = -y_sr, z = z_sr, column-major
+ * inside the box), and the draw, score and fit launches of pre3_plane_fit[_seeded] run behind that gather.  Nothing of the frame is read back or sent
+ * again: a supplied table is the only thing that crosses PCIe, the seeded form sends nothing.  box, t, n_draw, draws, (seed, seq) and every output as
+ * pre3_plane_fit / pre3_plane_fit_seeded.  Bit-identical -- every integer and every double of res, count_out, inlier_out, draws_out -- to that call fed
+ * with the planes pre3_sr_frame_get returns.  Runs on the handle's stream and the library's per-device scratch; synchronises.
+ * A non-finite coordinate inside the box (the filter turns a NaN into a 3 x 3 patch of NaNs) cannot be seen by the host any more: the gather raises a
+ * device flag, the launches behind it leave at once, and the call returns PRE3_E_NUMERIC with res filled (sta = 5) and the optional outputs zeroed --
+ * a status where pre3_plane_fit has an argument error.
+ * PRE3_E_ARG before anything is queued: a null handle or res, and everything pre3_plane_fit refuses except the non-finite coordinate (a box outside
+ * the frame or with fewer than 3 points, a box of fewer than 40 rows, n_draw outside [1, PRE3_PLANE_MAX_DRAWS], t <= 0, a null table or a draw
+ * outside [0, npts)).  PRE3_E_STATE: a handle without a loaded frame. */
+PRE3_API int pre3_plane_fit_frame(pre3_sr_frame *f, const int32_t *box, double t, int n_draw, const int32_t *draws,
+                                  int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res);
+PRE3_API int pre3_plane_fit_frame_seeded(pre3_sr_frame *f, const int32_t *box, double t, int n_draw, uint64_t seed, uint64_t seq,
+                                         int32_t *draws_out, int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res);
+/* mono_slam.m:189-193 (and initialize_x_and_p.m:36-37's fit) from a resident frame: pre3_heading_from_scan[_seeded] with the box gathered from the
+ * handle's filtered planes.  The context's stream waits for an event on the handle's, the gather, the draws, the score, the fit and the heading rows
+ * are queued on the context's stream, and the handle's stream then waits for an event behind them: a pre3_sr_frame_load that follows cannot overwrite
+ * planes the gather still reads.  State, gate (strict_reference), transpose, outputs and error words as pre3_heading_from_scan; x, P, applied and res
+ * are bit-identical to that call fed with the planes pre3_sr_frame_get returns.  With applied_out, res_out and draws_out all NULL the call does not
+ * synchronise.  A non-finite coordinate inside the box: the update is skipped on the device (x and P untouched); a call that waits returns
+ * PRE3_E_NUMERIC with res filled (sta = 5), applied = 0 and a table of zeros.  PRE3_E_ARG before anything is queued, context and handle unchanged:
+ * a null context or handle, a handle on another device than the context, and the argument errors above.  PRE3_E_STATE: a handle without a loaded
+ * frame; a context whose covariance buffer does not hold (x_k_k, p_k_k).  Calls that share the handle or the context must be serialised by the caller. */
+PRE3_API int pre3_heading_from_frame(pre3_ctx *ctx, pre3_sr_frame *f, const int32_t *box, double t, int n_draw, const int32_t *draws,
+                                     int transpose, int strict_reference, int32_t *applied_out, pre3_plane_result *res_out);
+PRE3_API int pre3_heading_from_frame_seeded(pre3_ctx *ctx, pre3_sr_frame *f, const int32_t *box, double t, int n_draw, uint64_t seed, uint64_t seq,
+                                            int transpose, int strict_reference, int32_t *draws_out, int32_t *applied_out,
+                                            pre3_plane_result *res_out);
+/* matching_sift_based.m:104,129-135: pre3_set_scan with Descriptor_RAW / SCALE_ORIENT_POS_RAW taken from the handle's keypoint block instead of the
+ * host.  which = 0: the raw set handed to the handle's last pre3_sr_frame_keypoints (des[K][128], entries 0..3 of frm[K][ldf]; entries at or beyond
+ * ldf are zero -- only the pixel column and row are read); which = 1: the kept set that call left.  One copy launch on the context's stream behind an
+ * event on the handle's, released by an event the handle's stream waits for; nothing crosses PCIe, the call does not synchronise.  The bounds the
+ * ranked route needs of the descriptors were noted when the raw set passed through the handle's staging (the kept set inherits them).  Afterwards the
+ * context is as after pre3_set_scan with the same arrays.  K == 0 is legal.  PRE3_E_ARG: a null context or handle, which outside {0, 1}, descriptors
+ * of other than 128 entries, a handle on another device than the context.  PRE3_E_STATE: a handle without a loaded frame, or without a keypoint
+ * result for the frame it holds (none yet, or a pre3_sr_frame_load after it). */
+PRE3_API int pre3_set_scan_frame(pre3_ctx *ctx, pre3_sr_frame *f, int which);
 
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).

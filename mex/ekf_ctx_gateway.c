@@ -21,6 +21,9 @@
  *   SIFT_extract_save.m:71-88, confidence_filtering.m                  [frm, des, idx, xyz, rho] = pre3_mex('sr_keypoints', gate, frames, descriptors)    % on the resident frame; no filter context needed
  *   vodometry_dr_ye.m:139-236, Calculate_V_Omega_RANSAC_dr_ye.m:41-50  pre3_mex('sr_keep'); ... next frame's 'sr_frame' + 'sr_keypoints' (gate 1) ...; [T, q, R, sta, match, stat] = pre3_mex('vo_pair', seed, seq)
  *   initialize_features.m:95-99 + map_management.m:27-79               pre3_mex('sr_keep'); ... next frame's 'sr_frame' + 'sr_keypoints' (gate 0 on both) ...; [del, acc, cv, st, order, match] = pre3_mex('map_policy_frames', step, 50, 0.1, std_z, 1, [176 144], seed, step)
+ *   plane_fit_to_data.m:7-149 on the resident frame                     [R, sta, B, n_inliers] = pre3_mex('plane_frame', seed, seq)                          % the box is gathered on the device
+ *   mono_slam.m:189-193 on the resident frame                           applied = pre3_mex('heading_frame', seed, step)                                  % fit + ekf_heading_update, nothing read back
+ *   matching_sift_based.m:104,129-135 on the resident frame             pre3_mex('set_scan_frame')                                                       % the scan 'sr_keypoints' was handed, copied on the device
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
  * corrcoef_partitioned_mex.c:25-57).  NOT compiled in the build container (no MATLAB / mex.h there).
@@ -125,6 +128,23 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
             m[0] = r.n_iterations; m[1] = r.n_support; m[2] = r.error_mean; m[3] = r.error_std; memcpy(m + 4, r.euler, sizeof r.euler); m[7] = pnum; m[8] = capped;
         }
         mxFree(mt);
+        return;
+    }
+    if (!strcmp(cmd, "plane_frame")) {       /* [R, sta, B, n_inliers] = pre3_mex('plane_frame', seed, seq [, n_draw = 1001, box = [80 144 50 120], t = 0.02]): plane_fit_to_data.m:7-149 on
+                                                 the resident frame's filtered x, y, z (load it with mode 0: read_xyz_sr4000) -- the box is gathered on the device, ransac.m:142-176's draws
+                                                 come from (seed, seq), nothing is read back to be sent again (pre3_plane_fit_frame_seeded).  R 3 x 3 as plane_fit_to_data returns it.
+                                                 A non-finite coordinate inside the box is an error (sta = 5). */
+        pre3_plane_result r; int32_t bx[4]; int i;
+        if (nin < 3 || nin > 6) mexErrMsgTxt("pre3_mex('plane_frame', seed, seq [, n_draw, box, t]): two to five arguments");
+        if (!g_sr) mexErrMsgTxt("pre3_mex('plane_frame'): call pre3_mex('sr_frame', ...) first");
+        if (nin > 4 && mxGetNumberOfElements(in[4]) != 4) mexErrMsgTxt("pre3_mex('plane_frame'): box is [row0 row1 col0 col1]");
+        for (i = 0; nin > 4 && i < 4; ++i) bx[i] = (int32_t)mxGetPr(in[4])[i];
+        check(pre3_plane_fit_frame_seeded(g_sr, nin > 4 ? bx : NULL, nin > 5 ? mxGetScalar(in[5]) : 0.02, nin > 3 ? (int)mxGetScalar(in[3]) : PRE3_PLANE_MAX_DRAWS,
+                                          (uint64_t)mxGetScalar(in[1]), (uint64_t)mxGetScalar(in[2]), NULL, NULL, NULL, &r));
+        out[0] = mxCreateDoubleMatrix(3, 3, mxREAL); memcpy(mxGetPr(out[0]), r.R, sizeof r.R);
+        if (nout > 1) out[1] = mxCreateDoubleScalar(r.sta);
+        if (nout > 2) { out[2] = mxCreateDoubleMatrix(4, 1, mxREAL); memcpy(mxGetPr(out[2]), r.B, sizeof r.B); }
+        if (nout > 3) out[3] = mxCreateDoubleScalar(r.n_inliers);
         return;
     }
     if (!g_ctx) mexErrMsgTxt("pre3_mex: call pre3_mex('create', ...) first");
@@ -343,6 +363,16 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
                                             nin > 7 ? (int)mxGetScalar(in[7]) : 1, NULL, &applied, NULL));
         out[0] = mxCreateDoubleScalar((double)applied);
     }
+    else if (!strcmp(cmd, "heading_frame")) {     /* applied = pre3_mex('heading_frame', seed, seq [, n_draw = 1001, strict = 1]): mono_slam.m:189-193 on the resident frame -- the box
+                                                     gathered from its filtered planes, fit, gate and update on the device (pre3_heading_from_frame_seeded); a non-finite coordinate
+                                                     inside the box is an error and leaves x and P untouched */
+        int32_t applied = 0;
+        if (nin < 3 || nin > 5) mexErrMsgTxt("pre3_mex('heading_frame', seed, seq [, n_draw, strict]): two to four arguments");
+        if (!g_sr) mexErrMsgTxt("pre3_mex('heading_frame'): call pre3_mex('sr_frame', ...) first");
+        check(pre3_heading_from_frame_seeded(g_ctx, g_sr, NULL, 0.02, nin > 3 ? (int)mxGetScalar(in[3]) : PRE3_PLANE_MAX_DRAWS, (uint64_t)mxGetScalar(in[1]),
+                                             (uint64_t)mxGetScalar(in[2]), 1, nin > 4 ? (int)mxGetScalar(in[4]) : 1, NULL, &applied, NULL));
+        out[0] = mxCreateDoubleScalar((double)applied);
+    }
     else if (!strcmp(cmd, "map_delete")) {        /* pre3_mex('map_delete', idx (0-based, ascending))   delete_features.m:54-74 */
         int k = (int)mxGetNumberOfElements(in[1]), i, rc; int32_t *d = (int32_t *)mxMalloc(sizeof(int32_t) * (k ? k : 1));
         for (i = 0; i < k; ++i) d[i] = (int32_t)mxGetPr(in[1])[i];
@@ -454,6 +484,12 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
     }
     else if (!strcmp(cmd, "set_scan")) {          /* pre3_mex('set_scan', SCAN_SIFT.Descriptor_RAW, SCAN_SIFT.SCALE_ORIENT_POS_RAW) */
         check(pre3_set_scan(g_ctx, (int)mxGetN(in[1]), mxGetPr(in[1]), mxGetPr(in[2])));
+    }
+    else if (!strcmp(cmd, "set_scan_frame")) {    /* pre3_mex('set_scan_frame' [, which = 0]): 'set_scan' with the arrays taken from the resident frame's keypoint block on the device --
+                                                     which = 0: the set handed to the last 'sr_keypoints' (Descriptor_RAW / SCALE_ORIENT_POS_RAW), 1: the set it kept */
+        if (nin > 2) mexErrMsgTxt("pre3_mex('set_scan_frame' [, which]): at most one argument");
+        if (!g_sr) mexErrMsgTxt("pre3_mex('set_scan_frame'): call pre3_mex('sr_frame', ...) and pre3_mex('sr_keypoints', ...) first");
+        check(pre3_set_scan_frame(g_ctx, g_sr, nin > 1 ? (int)mxGetScalar(in[1]) : 0));
     }
     else if (!strcmp(cmd, "ic_search")) {         /* [meas_idx, z, match_idx] = pre3_mex('ic_search', 1.5, strict)   matching_sift_based.m:104-149 */
         int N = pre3_get_map(g_ctx, NULL), i, rc; int32_t nm = 0, m = 0;
