@@ -1065,16 +1065,12 @@ int pre3_set_scan_frame(pre3_ctx *c, pre3_sr_frame *f, int which)
     PRE3_TRY(scan_reserve(c, K2, &grew));
     if (grew) PRE3_HIP(hipStreamSynchronize(0));         // (the new buffers are zeroed on the null stream, which the context's stream does not wait for)
     if (K2) {
-        // the hand-off and the release of section 22: the context's stream waits for what the handle's has queued (the keypoint stage has been waited
-        // for already); the handle's stream then waits for the copy, so that a load or a keypoint call that follows cannot overwrite the block under it
-        hipEvent_t ev = nullptr;
-        PRE3_TRY(sr_frame_pair_work(f, 0, 0, nullptr, nullptr, &ev));
-        PRE3_HIP(hipEventRecord(ev, v.stream));
-        PRE3_HIP(hipStreamWaitEvent(c->stream, ev, 0));
+        // the frame is lent to the context's stream (the keypoint stage has been waited for already) and reclaimed behind the copy, so that a load or a
+        // keypoint call that follows cannot overwrite the block under it
+        PRE3_TRY(sr_frame_lend(f, c->stream));
         hipLaunchKernelGGL(k_scan_frame, dim3(ceil_div(K2 * (DESC_DIM / 2) + K2, 256)), dim3(256), 0, c->stream, K2, kv.ldf, frm, des, c->scan_desc, c->scan_pos);
         PRE3_HIP(hipGetLastError());
-        PRE3_HIP(hipEventRecord(ev, c->stream));
-        PRE3_HIP(hipStreamWaitEvent(v.stream, ev, 0));
+        PRE3_TRY(sr_frame_reclaim(f, c->stream));
     }
     c->scan_K2 = K2;
     return ic_rank_set_scan(c, kv.raw_in_bounds);        // (which = 1: the kept set is a subset of the raw one)
@@ -1219,9 +1215,7 @@ int pre3_update_ell(int device, int dtype, int n, int r, const double *x, const 
     if (r == 0) {            // update.m:50-55
         if (x_out != x) memcpy(x_out, x, sizeof(double) * n);
         if (P_out != P) memcpy(P_out, P, sizeof(double) * (size_t)n * n);
-        int nd = 0;
-        if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
-        return PRE3_OK;
+        return select_device("pre3_update_ell", device);
     }
     for (int a = 0; a < r; ++a) {
         PRE3_CHECK(nnz[a] >= 0 && nnz[a] <= width && nnz[a] <= ELLW, PRE3_E_ARG, "pre3_update_ell: row %d has %d non-zeros (max %d)", a, nnz[a], ELLW);
@@ -1285,9 +1279,7 @@ int pre3_hypothesis_support(int device, int n, const double *xi, const pre3_cam 
 {
     PRE3_CHECK(n >= 13 && xi && cam && state_vector_pattern && support_out, PRE3_E_ARG, "pre3_hypothesis_support: bad arguments");
     PRE3_CHECK(n_id >= 0 && n_euc >= 0 && (n_id == 0 || z_id) && (n_euc == 0 || z_euc), PRE3_E_ARG, "pre3_hypothesis_support: bad measurement arrays");
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
-    PRE3_CHECK(device >= 0 && device < nd, PRE3_E_ARG, "pre3_hypothesis_support: device %d of %d", device, nd);
+    PRE3_TRY(select_device("pre3_hypothesis_support", device));
     // xi(logical(state_vector_pattern(:,c))): the selected entries in state order, column c of the n x 4 column-major pattern
     std::vector<int32_t> idx[4];
     for (int c = 0; c < 4; ++c)
@@ -1298,7 +1290,6 @@ int pre3_hypothesis_support(int device, int n, const double *xi, const pre3_cam 
                idx[0].size(), idx[1].size(), idx[2].size(), n_id);
     PRE3_CHECK((int)idx[3].size() == 3 * n_euc, PRE3_E_ARG, "pre3_hypothesis_support: pattern selects %zu entries for %d cartesian measurements", idx[3].size(), n_euc);
     if (n_id + n_euc == 0) { *support_out = 0; return PRE3_OK; }                       // :29, both branches empty
-    PRE3_HIP(hipSetDevice(device));
     std::vector<int32_t> out(1 + (size_t)n_id + n_euc);
     PRE3_TRY(run_hypothesis_support(n, xi, *cam, n_id, idx[0].data(), idx[1].data(), idx[2].data(), z_id, n_euc, idx[3].data(), z_euc, threshold, out.data()));
     *support_out = out[0];
@@ -1398,8 +1389,7 @@ static int siftmatch_any(int device, int cls, int ND, int K1, const void *L1, in
     PRE3_CHECK(M_out != nullptr, PRE3_E_ARG, "siftmatch: null M_out");
     *M_out = 0;
     PRE3_CHECK(ND > 0 && K1 >= 0 && K2 >= 0, PRE3_E_ARG, "siftmatch: bad sizes");
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
+    PRE3_TRY(select_device("siftmatch", device));
     if (K1 == 0) return PRE3_OK;
     std::vector<double> b(K1), s(K1); std::vector<int32_t> a(K1);
     PRE3_TRY(match_partial(device, cls, ND, K1, L1, K2, L2, 0, b.data(), s.data(), a.data()));
@@ -1494,8 +1484,7 @@ int pre3_bench_downdate(pre3_ctx *c, int r, int reps, double *ms_per_launch_out)
 int pre3_match_shard_create_cls(pre3_match_shard **out, int device, int cls, int ND, int K1, const void *L1, int K2_local, const void *L2_local, int k2_offset)
 {
     PRE3_CHECK(out != nullptr, PRE3_E_ARG, "pre3_match_shard_create: null output");
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
+    PRE3_TRY(select_device("pre3_match_shard_create", device));
     void *h = match_shard_create(device, cls, ND, K1, L1, K2_local, L2_local, k2_offset);
     if (!h) return PRE3_E_ARG;
     *out = (pre3_match_shard *)h;
@@ -1525,14 +1514,14 @@ int pre3_match_shard_test_stall(pre3_match_shard *s, int release)
 // matcher roofline/bench probe (inputs resident in HBM); not part of the reference-shaped API
 PRE3_API void *pre3_match_bench_create(int device, int ND, int K1, const uint8_t *L1, int K2, const uint8_t *L2)
 {
-    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return nullptr; }
+    if (select_device("pre3_match_bench_create", device) != PRE3_OK) return nullptr;
     return match_bench_create(2, ND, K1, L1, K2, L2);
 }
 // the same probe for any class (0 double, 1 float, 2 uint8); pre3_match_bench_info: [route (0 exact kernels, 1 int8 MFMA, 2 bf16 rank +
 // exact re-evaluation), queries scanned in full, candidates re-evaluated] of the last run
 PRE3_API void *pre3_match_bench_create_cls(int device, int cls, int ND, int K1, const void *L1, int K2, const void *L2)
 {
-    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return nullptr; }
+    if (select_device("pre3_match_bench_create_cls", device) != PRE3_OK) return nullptr;
     return match_bench_create(cls, ND, K1, L1, K2, L2);
 }
 PRE3_API int pre3_match_bench_info(void *h, int32_t info[3]) { return h ? match_bench_info(h, info) : PRE3_E_ARG; }

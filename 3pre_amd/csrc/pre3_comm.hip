@@ -164,7 +164,7 @@ int pre3_comm_create(pre3_comm **out, int device, const void *id, int rank, int 
     *out = nullptr;
     const Rccl *R = rccl();
     if (!R) return PRE3_E_COMM;
-    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return PRE3_E_NODEVICE; }
+    PRE3_TRY(select_device("pre3_comm_create", device));
     ncclUniqueId uid; memcpy(&uid, id, sizeof(uid));
     Comm *cm = new Comm();
     cm->device = device; cm->rank = rank; cm->world = world;

@@ -1396,9 +1396,8 @@ int run_hypothesis_support(int n, const double *xi, const pre3_cam &cam, int n_i
     const int m = n_id + n_euc;
     // one pooled device block: [xi n | z 2m | res m] doubles, then [i1 3n_id | i2 2n_id | i3 n_id | i4 3n_euc | out 1+m] int32
     const size_t nd = (size_t)n + 3 * (size_t)m, ni = 6 * (size_t)n_id + 3 * (size_t)n_euc + 1 + m;
-    void *blk = nullptr; int slot = -1;
-    PRE3_TRY(scratch_acquire(sizeof(double) * nd + sizeof(int32_t) * ni, &blk, &slot));
-    struct Rel { int slot; void *p; ~Rel() { scratch_release(slot, p); } } rel{ slot, blk };
+    Scratch blk;
+    PRE3_TRY(blk.alloc(sizeof(double) * nd + sizeof(int32_t) * ni));
     std::vector<double> hd(nd, 0.0);
     std::vector<int32_t> hi(ni, 0);
     memcpy(hd.data(), xi, sizeof(double) * n);
@@ -1406,7 +1405,7 @@ int run_hypothesis_support(int n, const double *xi, const pre3_cam &cam, int n_i
     if (n_euc) memcpy(hd.data() + n + 2 * (size_t)n_id, z_euc, sizeof(double) * 2 * n_euc);
     if (n_id) { memcpy(hi.data(), i1, sizeof(int32_t) * 3 * n_id); memcpy(hi.data() + 3 * (size_t)n_id, i2, sizeof(int32_t) * 2 * n_id); memcpy(hi.data() + 5 * (size_t)n_id, i3, sizeof(int32_t) * n_id); }
     if (n_euc) memcpy(hi.data() + 6 * (size_t)n_id, i4, sizeof(int32_t) * 3 * n_euc);
-    double *dd = (double *)blk; int32_t *di = (int32_t *)(dd + nd);
+    double *dd = blk.as<double>(); int32_t *di = (int32_t *)(dd + nd);
     PRE3_HIP(hipMemcpy(dd, hd.data(), sizeof(double) * nd, hipMemcpyHostToDevice));
     PRE3_HIP(hipMemcpy(di, hi.data(), sizeof(int32_t) * ni, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_hyp_support, dim3(1), dim3(256), 0, 0, dd, to_camd(cam), n_id, di, di + 3 * (size_t)n_id, di + 5 * (size_t)n_id, dd + n,

@@ -32,6 +32,7 @@ void set_error(const char *fmt, ...);
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }      // offsets inside a work block: 16-byte aligned
 
 constexpr int TILE = 128;       // K9 output tile; P's leading dimension is a multiple of this
 constexpr int NB = 64;          // Cholesky / triangular-solve panel width
@@ -295,6 +296,18 @@ int update_hi_impl(pre3_ctx *c);         /* pre3_step.hip: pre3_update_hi withou
 int scratch_acquire(size_t bytes, void **p_out, int *slot_out);
 void scratch_release(int slot, void *p);
 void release_scratch();
+struct Scratch {                // one block of it, held for a scope: no hipMalloc / hipFree per call once warm
+    void *p = nullptr;
+    int slot = -1;
+    Scratch() = default;
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() { scratch_release(slot, p); }
+    int alloc(size_t bytes) { return scratch_acquire(bytes, &p, &slot); }
+    template <typename T> T *as() const { return (T *)p; }
+};
+// the device of a stateless entry point selected, or PRE3_E_NODEVICE with `who` in the message: none at all, or no such index (pre3_sr.hip)
+int select_device(const char *who, int device);
 // ---- matchers (pre3_match.hip)
 int match_partial(int device, int cls, int ND, int K1, const void *L1, int K2, const void *L2, int k2_offset, double *best, double *second, int32_t *arg);
 int knn_run(int device, int D, int N, const double *data, int M, const double *query, int k, double *ids, double *dist);
@@ -405,7 +418,16 @@ int sr_frame_view(pre3_sr_frame *f, SrFrameView *v);      /* PRE3_E_STATE before
 struct SrKeypointView { int K, ldf, ND, gate, n_kept; const double *frm, *des; const double *xyz, *rho; const int32_t *keep_idx;
                         int K_in; const double *frm_in, *des_in; bool raw_in_bounds; };
 int sr_frame_keypoint_view(pre3_sr_frame *f, SrKeypointView *v);
-int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, void **dev, void **pin, hipEvent_t *ev);      /* pre3_vopair.hip's blocks and event */
+int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, void **dev, void **pin);      /* pre3_vopair.hip's work blocks */
+// the hand-off between the handle's stream and a consumer's, on the handle's own event.  lend: `consumer` waits for everything
+// queued on the handle's stream so far (a load, the conditioning launches).  reclaim: the handle's stream waits for everything queued on `consumer` so
+// far, so that a load or a keypoint call that follows cannot overwrite blocks the consumer's launches still read.
+int sr_frame_lend(pre3_sr_frame *f, hipStream_t consumer);
+int sr_frame_reclaim(pre3_sr_frame *f, hipStream_t consumer);
+// every check the calls on a (prev, cur) pair of resident frames share, `who` in every message: two distinct handles, thresh, both views on one
+// device with one size, both keypoint results with DESC_DIM entries per descriptor
+int sr_frame_pair_views(const char *who, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, SrFrameView *v1, SrFrameView *v2, SrKeypointView *k1,
+                        SrKeypointView *k2);
 // ---- the match stage of the pair call on its own (pre3_vopair.hip: k_vp_match, k_vp_pairs), for pre3_map_policy_frames_seeded.  des1 [n1][128] the
 // queries, des2 [n2][128] the scan (n1, n2 >= 1); part: vp_match_part_bytes(n1, n2) of device scratch; match 2 x n1 doubles; hdr_dev a VoPairHeader
 // (pnum, rst written; bad and capped cleared).  Everything on `st`.

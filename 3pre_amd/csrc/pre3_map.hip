@@ -1129,11 +1129,7 @@ static int map_policy_impl(const char *who, pre3_ctx *c, int step, int min_featu
     // (frames) cur's work block [header | match 2K | flags K | the matcher's partials]; header, match and flags come back in one transfer
     const size_t fo_match = sizeof(VoPairHeader), fo_flags = fo_match + sizeof(double) * 2 * Kc, fo_part = (fo_flags + sizeof(int32_t) * Kc + 15) & ~(size_t)15;
     char *f_dev = nullptr, *f_pin = nullptr;
-    hipEvent_t ev_prev = nullptr, ev_cur = nullptr;
-    if (fcq) {
-        PRE3_TRY(sr_frame_pair_work(fc->prev, 0, 0, nullptr, nullptr, &ev_prev));
-        PRE3_TRY(sr_frame_pair_work(fc->cur, fo_part + vp_match_part_bytes(K, fc->k2.n_kept), fo_part, (void **)&f_dev, (void **)&f_pin, &ev_cur));
-    }
+    if (fcq) PRE3_TRY(sr_frame_pair_work(fc->cur, fo_part + vp_match_part_bytes(K, fc->k2.n_kept), fo_part, (void **)&f_dev, (void **)&f_pin));
     if (dev_bytes > c->pol_dev_bytes) {
         if (c->pol_dev) (void)hipFree(c->pol_dev);
         c->pol_dev = nullptr; c->pol_dev_bytes = 0;
@@ -1154,22 +1150,20 @@ static int map_policy_impl(const char *who, pre3_ctx *c, int step, int min_featu
     int32_t *d_order2 = fcq ? d_blocked + Kc : nullptr, *d_acc_row = fcq ? d_order2 + Kc : nullptr;
     const int32_t *d_kreal = nullptr;
     if (fcq) {
-        // ---- on cur's stream, behind an event on prev's: the match list and its count (pre3_vo_pair_seeded's launches), the gather; header, match and
-        // flags towards the host; then the context's stream waits for all of it
+        // ---- prev lent to cur's stream: the match list and its count (pre3_vo_pair_seeded's launches), the gather; header, match and flags towards the
+        // host; then cur lent to the context's stream, which waits for all of it
         hipStream_t fs = fc->v2.stream;
         VoPairHeader *hdr = reinterpret_cast<VoPairHeader *>(f_dev);
         double *d_match = reinterpret_cast<double *>(f_dev + fo_match);
         int32_t *d_flags = reinterpret_cast<int32_t *>(f_dev + fo_flags);
-        PRE3_HIP(hipEventRecord(ev_prev, fc->v1.stream));
-        PRE3_HIP(hipStreamWaitEvent(fs, ev_prev, 0));
+        PRE3_TRY(sr_frame_lend(fc->prev, fs));
         PRE3_HIP(hipMemsetAsync(f_dev, 0, fo_part, fs));
         PRE3_TRY(launch_vp_match(K, fc->k2.n_kept, fc->k1.des, fc->k2.des, fc->thresh, f_dev + fo_part, d_match, hdr, fs));
         hipLaunchKernelGGL(k_fc_gather, dim3(ceil_div(K, 64)), dim3(64), 0, fs, K, K, fc->k1.ldf, fc->k1.frm, fc->k1.rho, fc->k1.des, (const double *)d_match,
                            (const VoPairHeader *)hdr, d_raw, d_flags);
         PRE3_HIP(hipGetLastError());
         PRE3_HIP(hipMemcpyAsync(f_pin, f_dev, fo_part, hipMemcpyDeviceToHost, fs));
-        PRE3_HIP(hipEventRecord(ev_cur, fs));
-        PRE3_HIP(hipStreamWaitEvent(c->stream, ev_cur, 0));
+        PRE3_TRY(sr_frame_lend(fc->cur, c->stream));
         d_kreal = &hdr->pnum;
     } else if (K > 0) PRE3_HIP(hipMemcpyAsync(sd ? d_raw : d_cand, h_cand, sizeof(double) * 3 * K, hipMemcpyHostToDevice, c->stream));
     // ---- seeded: the keys and their rank re-lay the block in the drawn order (d_raw -> d_cand); the order goes into the result block
@@ -1239,13 +1233,11 @@ static int map_policy_impl(const char *who, pre3_ctx *c, int step, int min_featu
         PRE3_TRY(set_descriptors_impl(c, n_surv, n_acc, dsc.data()));
     }
     if (fcq) {
-        // initialize_a_feature_sift_3.m:132 from prev's keypoint block, on the context's stream; then both handles' streams wait for the context's, so
-        // that a later load or keypoint call cannot overwrite blocks that are still being read
+        // initialize_a_feature_sift_3.m:132 from prev's keypoint block, on the context's stream; then both handles are reclaimed from it, so that a
+        // later load or keypoint call cannot overwrite blocks that are still being read
         if (n_acc > 0) PRE3_TRY(set_descriptors_rows_dev(c, n_surv, n_acc, fc->k1.des, d_acc_row, K, !(fc_bad & FC_BAD_DESC)));
-        PRE3_HIP(hipEventRecord(ev_prev, c->stream));
-        PRE3_HIP(hipStreamWaitEvent(fc->v1.stream, ev_prev, 0));
-        PRE3_HIP(hipEventRecord(ev_cur, c->stream));
-        PRE3_HIP(hipStreamWaitEvent(fc->v2.stream, ev_cur, 0));
+        PRE3_TRY(sr_frame_reclaim(fc->prev, c->stream));
+        PRE3_TRY(sr_frame_reclaim(fc->cur, c->stream));
         if (fc->match_out) memcpy(fc->match_out, f_pin + fo_match, sizeof(double) * 2 * (size_t)Kr);
     }
     if (fc && fc->K_out) *fc->K_out = Kr;
@@ -1283,18 +1275,10 @@ int pre3_map_policy_frames_seeded(pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_fram
 {
     const char *who = "pre3_map_policy_frames_seeded";
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
-    PRE3_CHECK(prev != nullptr && cur != nullptr, PRE3_E_ARG, "%s: null handle", who);
-    PRE3_CHECK(prev != cur, PRE3_E_ARG, "%s: prev and cur are the same handle", who);
-    PRE3_CHECK(std::isfinite(thresh) && thresh > 0.0, PRE3_E_ARG, "%s: thresh must be positive and finite", who);
     FrameCand fc{};
     fc.prev = prev; fc.cur = cur; fc.thresh = thresh; fc.K_out = K_out; fc.match_out = match_out;
-    PRE3_TRY(sr_frame_view(prev, &fc.v1)); PRE3_TRY(sr_frame_view(cur, &fc.v2));
-    PRE3_CHECK(fc.v1.device == fc.v2.device && fc.v1.rows == fc.v2.rows && fc.v1.cols == fc.v2.cols, PRE3_E_ARG,
-               "%s: the frames differ (device %d, %d x %d against device %d, %d x %d)", who, fc.v1.device, fc.v1.rows, fc.v1.cols, fc.v2.device, fc.v2.rows, fc.v2.cols);
+    PRE3_TRY(sr_frame_pair_views(who, prev, cur, thresh, &fc.v1, &fc.v2, &fc.k1, &fc.k2));
     PRE3_CHECK(fc.v1.device == c->device, PRE3_E_ARG, "%s: the frames are on device %d, the context on device %d", who, fc.v1.device, c->device);
-    PRE3_TRY(sr_frame_keypoint_view(prev, &fc.k1)); PRE3_TRY(sr_frame_keypoint_view(cur, &fc.k2));
-    PRE3_CHECK(fc.k1.ND == DESC_DIM && fc.k2.ND == DESC_DIM, PRE3_E_ARG, "%s: descriptors of %d and %d entries (the matcher's tile is written for %d)", who,
-               fc.k1.ND, fc.k2.ND, DESC_DIM);
     PRE3_CHECK(fc.k1.gate == 0, PRE3_E_ARG, "%s: prev's keypoints went through gate %d; the candidates' rho comes from gate 0 (the depth gate)", who, fc.k1.gate);
     const int K = fc.k2.n_kept > 0 ? fc.k1.n_kept : 0;             // the cap: pnum <= n1; siftmatch against an empty set matches nothing
     const CandSeed sd{ seed, seq, box_w, box_h };
@@ -1311,12 +1295,10 @@ int pre3_candidate_order(int device, int K, const double *cand_uv, int box_w, in
     if (K == 0) return PRE3_OK;
     PRE3_CHECK(cand_uv != nullptr && order_out != nullptr, PRE3_E_ARG, "%s: null argument", who);
     for (int k = 0; k < 2 * K; ++k) PRE3_CHECK(std::isfinite(cand_uv[k]), PRE3_E_ARG, "%s: candidate %d has a non-finite pixel", who, k / 2);
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
-    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return PRE3_E_NODEVICE; }
-    struct Scratch { void *p = nullptr; int slot = -1; ~Scratch() { scratch_release(slot, p); } } d;
-    PRE3_TRY(scratch_acquire(sizeof(double) * 3 * (size_t)K + sizeof(int32_t) * (size_t)K, &d.p, &d.slot));      // [uv 2K | keys K | order K]
-    double *d_uv = static_cast<double *>(d.p), *d_keys = d_uv + 2 * (size_t)K;
+    PRE3_TRY(select_device(who, device));
+    Scratch d;
+    PRE3_TRY(d.alloc(sizeof(double) * 3 * (size_t)K + sizeof(int32_t) * (size_t)K));      // [uv 2K | keys K | order K]
+    double *d_uv = d.as<double>(), *d_keys = d_uv + 2 * (size_t)K;
     int32_t *d_order = reinterpret_cast<int32_t *>(d_keys + K);
     PRE3_HIP(hipMemcpy(d_uv, cand_uv, sizeof(double) * 2 * (size_t)K, hipMemcpyHostToDevice));
     PRE3_TRY(launch_cand_order(seed, seq, K, box_w, box_h, d_uv, d_keys, d_order, nullptr, 0));

@@ -1154,12 +1154,9 @@ void scratch_release(int slot, void *p)
     else if (p) (void)hipFree(p);
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    int slot = -1;
+struct DevBuf : Scratch {
     bool borrowed = false;                                   // p points into another DevBuf's allocation
-    ~DevBuf() { if (!borrowed) scratch_release(slot, p); }
-    int alloc(size_t bytes) { return scratch_acquire(bytes, &p, &slot); }
+    ~DevBuf() { if (borrowed) p = nullptr; }                 // (slot is -1: the guard has nothing to release)
     void borrow(void *q) { if (!borrowed) scratch_release(slot, p); p = q; slot = -1; borrowed = true; }
 };
 
@@ -1380,7 +1377,7 @@ int match_partial(int device, int cls, int ND, int K1, const void *L1, int K2, c
     PRE3_CHECK(ND > 0 && K1 >= 0 && K2 >= 0, PRE3_E_ARG, "siftmatch: bad sizes ND=%d K1=%d K2=%d", ND, K1, K2);
     PRE3_CHECK(K1 == 0 || (L1 && best && second && arg), PRE3_E_ARG, "siftmatch: null pointer");
     if (K1 == 0) return PRE3_OK;
-    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return PRE3_E_NODEVICE; }
+    PRE3_TRY(select_device("siftmatch", device));
     if (K2 == 0) {
         for (int i = 0; i < K1; ++i) { best[i] = (cls >= 2) ? 2147483647.0 : INFINITY; second[i] = best[i]; arg[i] = -1; }
         return PRE3_OK;
@@ -1794,7 +1791,7 @@ int knn_run(int device, int D, int N, const double *data, int M, const double *q
 {
     PRE3_CHECK(D > 0 && N > 0 && M >= 0 && k >= 1 && k <= N, PRE3_E_ARG, "kNearestNeighbors: bad sizes D=%d N=%d M=%d k=%d", D, N, M, k);
     if (M == 0) return PRE3_OK;
-    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return PRE3_E_NODEVICE; }
+    PRE3_TRY(select_device("kNearestNeighbors", device));
     DevBuf dd, dq, sc, di, ds;
     PRE3_TRY(dd.alloc(sizeof(double) * (size_t)N * D)); PRE3_TRY(dq.alloc(sizeof(double) * (size_t)M * D));
     PRE3_TRY(sc.alloc(sizeof(double) * (size_t)M * N)); PRE3_TRY(di.alloc(sizeof(double) * (size_t)M * k)); PRE3_TRY(ds.alloc(sizeof(double) * (size_t)M * k));
@@ -1914,7 +1911,7 @@ __global__ __launch_bounds__(1024) void k_shard_merge(int G, int K1, const doubl
 void *match_shard_create(int device, int cls, int ND, int K1, const void *L1, int K2, const void *L2, int k2_offset)
 {
     if (ND <= 0 || K1 <= 0 || K2 < 0 || !L1 || (K2 && !L2) || cls < 0 || cls > 2) { set_error("match shard: bad arguments"); return nullptr; }
-    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return nullptr; }
+    if (select_device("match shard", device) != PRE3_OK) return nullptr;
     MatchShard *sh = new MatchShard();
     sh->device = device; sh->k2_offset = k2_offset; sh->cls = cls;
     int rc = PRE3_OK;

@@ -335,12 +335,34 @@ __global__ __launch_bounds__(PB) void k_plane_fit(int npts, const double *__rest
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------------
 struct PlaneJob {
     int r0, c0, nr, nc, npts, po, pr, n_draw;
-    size_t off_draws, bytes_in, off_counts, off_out, off_inl, off_flag, bytes_total;      // off_flag: the crop's word (the frame forms)
-    size_t bytes_up;            // what crosses PCIe: bytes_in, or the points alone when the draws are made on the device (the seeded forms)
+    size_t off_draws, bytes_in, off_counts, off_out, off_inl, off_flag, bytes_total;      // off_flag: the crop's word (a resident frame)
+    size_t bytes_up;            // what crosses PCIe from host planes: bytes_in, or the points alone when the draws are made on the device (the seeded forms)
 };
 struct PlaneSeed { unsigned long long seed, seq; };      // k_draw_plane writes the draws region behind the upload
 
-static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+// where the points come from: three host planes (rows x cols, column-major) for `device`, or a resident SR4000 frame, whose
+// view plane_check fills
+struct PlaneSource {
+    bool resident;
+    int device, rows, cols;
+    const double *x, *y, *z;
+    pre3_sr_frame *frame;
+    SrFrameView v;
+    hipStream_t stream() const { return resident ? v.stream : nullptr; }      // of the stateless fit: the handle's, or the null stream
+    const SrFrameView *crop() const { return resident ? &v : nullptr; }
+};
+static PlaneSource host_planes(int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr)
+{
+    PlaneSource s{};
+    s.device = device; s.rows = rows; s.cols = cols; s.x = x_sr; s.y = y_sr; s.z = z_sr;
+    return s;
+}
+static PlaneSource resident_frame(pre3_sr_frame *f)
+{
+    PlaneSource s{};
+    s.resident = true; s.frame = f;
+    return s;
+}
 
 // every host check that needs no coordinate, and the layout of the work block
 static int plane_job(const char *who, int rows, int cols, const int32_t *box, double t, int n_draw, const int32_t *draws, PlaneJob *job, bool seeded)
@@ -363,7 +385,7 @@ static int plane_job(const char *who, int rows, int cols, const int32_t *box, do
     for (int i = 0; !seeded && i < 3 * n_draw; ++i)
         PRE3_CHECK(draws[i] >= 0 && draws[i] < j.npts, PRE3_E_ARG, "%s: draws[%d]=%d is not a point of the box (npts=%d)", who, i, draws[i], j.npts);
     j.n_draw = n_draw;
-    j.off_draws = up16(sizeof(double) * 3 * (size_t)j.npts);      // (16-byte aligned: the frame forms pull a supplied table there on its own)
+    j.off_draws = up16(sizeof(double) * 3 * (size_t)j.npts);      // (16-byte aligned: a table for a resident frame is pulled there on its own)
     j.bytes_in = up16(j.off_draws + sizeof(int32_t) * 3 * (size_t)n_draw);
     j.off_counts = j.bytes_in;
     j.off_out = up16(j.off_counts + sizeof(int32_t) * (size_t)n_draw);
@@ -375,17 +397,21 @@ static int plane_job(const char *who, int rows, int cols, const int32_t *box, do
     return PRE3_OK;
 }
 
-// every host check of the entry points that take the planes from the host, before anything is launched
-static int plane_check(const char *who, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
-                       int n_draw, const int32_t *draws, PlaneJob *job, bool seeded = false)
+// every host check on the source and the job, before anything is launched: a resident frame gives its view (the device tests its coordinates, sta = 5);
+// host planes are tested here, coordinate by coordinate
+static int plane_check(const char *who, PlaneSource *s, const int32_t *box, double t, int n_draw, const int32_t *draws, PlaneJob *job, bool seeded = false)
 {
-    PRE3_CHECK(x_sr && y_sr && z_sr && (draws || seeded), PRE3_E_ARG, "%s: null argument", who);
+    PRE3_CHECK(s->resident ? s->frame != nullptr : s->x && s->y && s->z && (draws || seeded), PRE3_E_ARG, "%s: null argument", who);
+    if (s->resident) {
+        PRE3_TRY(sr_frame_view(s->frame, &s->v));
+        s->device = s->v.device; s->rows = s->v.rows; s->cols = s->v.cols;
+    }
     PlaneJob j;
-    PRE3_TRY(plane_job(who, rows, cols, box, t, n_draw, draws, &j, seeded));
-    for (int c = 0; c < j.nc; ++c) {
-        const size_t o = (size_t)(j.c0 + c) * rows + j.r0;
+    PRE3_TRY(plane_job(who, s->rows, s->cols, box, t, n_draw, draws, &j, seeded));
+    for (int c = 0; !s->resident && c < j.nc; ++c) {
+        const size_t o = (size_t)(j.c0 + c) * s->rows + j.r0;
         for (int r = 0; r < j.nr; ++r)
-            PRE3_CHECK(std::isfinite(x_sr[o + r]) && std::isfinite(y_sr[o + r]) && std::isfinite(z_sr[o + r]), PRE3_E_ARG,
+            PRE3_CHECK(std::isfinite(s->x[o + r]) && std::isfinite(s->y[o + r]) && std::isfinite(s->z[o + r]), PRE3_E_ARG,
                        "%s: a coordinate at row %d, column %d is not finite", who, j.r0 + r + 1, j.c0 + c + 1);
     }
     *job = j;
@@ -393,19 +419,35 @@ static int plane_check(const char *who, int rows, int cols, const double *x_sr, 
 }
 
 // plane_fit_to_data.m:13, :19-21, :41: the box in camera coordinates, column-major, as [X | Y | Z | draws] -- the only bytes that cross PCIe
-static void plane_pack(const PlaneJob &j, int rows, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *draws, void *stage)
+static void plane_pack(const PlaneJob &j, const PlaneSource &s, const int32_t *draws, void *stage)
 {
     double *X = (double *)stage, *Y = X + j.npts, *Z = Y + j.npts;
     for (int c = 0; c < j.nc; ++c) {
-        const size_t o = (size_t)(j.c0 + c) * rows + j.r0, d = (size_t)c * j.nr;
-        for (int r = 0; r < j.nr; ++r) { X[d + r] = -x_sr[o + r]; Y[d + r] = -y_sr[o + r]; Z[d + r] = z_sr[o + r]; }
+        const size_t o = (size_t)(j.c0 + c) * s.rows + j.r0, d = (size_t)c * j.nr;
+        for (int r = 0; r < j.nr; ++r) { X[d + r] = -s.x[o + r]; Y[d + r] = -s.y[o + r]; Z[d + r] = s.z[o + r]; }
     }
     const size_t end_pts = sizeof(double) * 3 * (size_t)j.npts;
     if (j.off_draws > end_pts) memset((char *)stage + end_pts, 0, j.off_draws - end_pts);
     if (draws) memcpy((char *)stage + j.off_draws, draws, sizeof(int32_t) * 3 * (size_t)j.n_draw);
 }
 
-// crop != nullptr (the frame forms): the point block comes from the view's planes by k_plane_crop, queued here in front of the draws; the flag word at
+// what a call stages and sends up, and where it lands in the work block: plane_pack's image of host planes (stage bytes_in, send bytes_up); for a
+// resident frame a supplied table alone, padded to where the scores begin -- nothing when the draws are seeded
+struct PlaneUpload { size_t off, stage_bytes, bytes; };
+static PlaneUpload plane_upload(const PlaneJob &j, const PlaneSource &s, const int32_t *draws)
+{
+    if (!s.resident) return { 0, j.bytes_in, j.bytes_up };
+    const size_t b = draws ? j.bytes_in - j.off_draws : 0;
+    return { j.off_draws, b, b };
+}
+static void plane_stage_fill(const PlaneJob &j, const PlaneSource &s, const int32_t *draws, const PlaneUpload &up, void *stage)
+{
+    if (!s.resident) { plane_pack(j, s, draws, stage); return; }
+    memset(stage, 0, up.stage_bytes);
+    memcpy(stage, draws, sizeof(int32_t) * 3 * (size_t)j.n_draw);
+}
+
+// crop != nullptr (a resident frame): the point block comes from the view's planes by k_plane_crop, queued here in front of the draws; the flag word at
 // j.off_flag is zeroed on `st` first and every launch behind the crop reads it
 static int plane_launch(const PlaneJob &j, char *buf, double t, int transpose, bool want_inl, HeadingSrc *src, hipStream_t st, const PlaneSeed *sd = nullptr,
                         const SrFrameView *crop = nullptr)
@@ -436,6 +478,15 @@ static void plane_result(const PlaneOut &o, pre3_plane_result *res)
     res->N = o.N; res->sta = o.sta; res->n_inliers = o.n_inliers; res->n_trials = o.n_trials; res->best = o.best;
 }
 
+// the scores, the winner's mask and the table from the work block of a fit that has finished (any may be null)
+static int plane_read_back(const PlaneJob &j, const char *buf, int32_t *count_out, int32_t *inlier_out, int32_t *draws_out)
+{
+    if (count_out) PRE3_HIP(hipMemcpy(count_out, buf + j.off_counts, sizeof(int32_t) * (size_t)j.n_draw, hipMemcpyDeviceToHost));
+    if (inlier_out) PRE3_HIP(hipMemcpy(inlier_out, buf + j.off_inl, sizeof(int32_t) * (size_t)j.npts, hipMemcpyDeviceToHost));
+    if (draws_out) PRE3_HIP(hipMemcpy(draws_out, buf + j.off_draws, sizeof(int32_t) * 3 * (size_t)j.n_draw, hipMemcpyDeviceToHost));
+    return PRE3_OK;
+}
+
 // pinned staging of the stateless entry point: one block per process, grown on demand, held for the length of a call
 struct PlaneStage {
     void *p = nullptr; size_t cap = 0; std::mutex mu;
@@ -443,10 +494,43 @@ struct PlaneStage {
 };
 static PlaneStage g_stage;
 
-struct PlaneScratch {           // pooled device scratch (pre3_match.hip)
-    void *p = nullptr; int slot = -1;
-    ~PlaneScratch() { scratch_release(slot, p); }
+static int stage_reserve(size_t bytes)      // (the caller holds g_stage.mu)
+{
+    if (g_stage.cap >= bytes) return PRE3_OK;
+    if (g_stage.p) (void)hipHostFree(g_stage.p);
+    g_stage.p = nullptr; g_stage.cap = 0;
+    const size_t cap = (bytes + 65535) & ~(size_t)65535;
+    PRE3_HIP(hipHostMalloc(&g_stage.p, cap, hipHostMallocDefault));
+    g_stage.cap = cap;
+    return PRE3_OK;
+}
+
+struct StreamIdle {             // a work block fed from a handle's stream goes back to its pool only once that stream is idle, on every way out
+    hipStream_t st;
+    ~StreamIdle() { if (st) (void)hipStreamSynchronize(st); }
 };
+
+// a block of the context: zeroed on the context's stream, which does not synchronise with the null stream
+static int plane_dmalloc(pre3_ctx *c, void **p, size_t bytes)
+{
+    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; set_error("hipMalloc of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
+    PRE3_HIP(hipMemsetAsync(*p, 0, bytes, c->stream));
+    return PRE3_OK;
+}
+
+// the context's work block [points | draws | scores | result | mask | flag], grown on demand, and the block the heading rows read
+static int plane_reserve(pre3_ctx *c, const char *who, size_t bytes)
+{
+    if (c->plane_bytes < bytes) {
+        if (c->plane_buf) { PRE3_TRY(stream_drain(c, who)); (void)hipFree(c->plane_buf); }
+        c->plane_buf = nullptr; c->plane_bytes = 0;
+        const size_t cap = bytes + bytes / 4;
+        PRE3_TRY(plane_dmalloc(c, &c->plane_buf, cap));
+        c->plane_bytes = cap;
+    }
+    if (c->plane_src == nullptr) { void *p = nullptr; PRE3_TRY(plane_dmalloc(c, &p, sizeof(HeadingSrc))); c->plane_src = (HeadingSrc *)p; }
+    return PRE3_OK;
+}
 
 }  // namespace
 
@@ -463,78 +547,100 @@ using namespace pre3;
 
 extern "C" {
 
-static int plane_fit_impl(const char *who, int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
-                          int n_draw, const int32_t *draws, int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res, const PlaneSeed *sd, int32_t *draws_out)
+// the stateless fit, from host planes on the null stream or from a resident frame on the handle's (DESIGN.md sections 17 and 23).  A frame's box with
+// a non-finite coordinate: sta = 5, PRE3_E_NUMERIC with res filled and every other output zeroed (neither the table nor the scores were written).
+static int plane_fit_impl(const char *who, PlaneSource s, const int32_t *box, double t, int n_draw, const int32_t *draws, int32_t *count_out,
+                          int32_t *inlier_out, pre3_plane_result *res, const PlaneSeed *sd, int32_t *draws_out)
 {
     PlaneJob j;
     PRE3_CHECK(res != nullptr, PRE3_E_ARG, "%s: null argument", who);
-    PRE3_TRY(plane_check(who, rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, draws, &j, sd != nullptr));
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
-    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return PRE3_E_NODEVICE; }
-    PlaneScratch d;
-    PRE3_TRY(scratch_acquire(j.bytes_total, &d.p, &d.slot));
+    PRE3_TRY(plane_check(who, &s, box, t, n_draw, draws, &j, sd != nullptr));
+    PRE3_TRY(select_device(who, s.device));
+    Scratch d;
+    PRE3_TRY(d.alloc(j.bytes_total));
+    const hipStream_t st = s.stream();
+    StreamIdle idle{ st };
+    const PlaneUpload up = plane_upload(j, s, draws);
     PlaneOut o;
     {
         std::lock_guard<std::mutex> lk(g_stage.mu);
-        if (g_stage.cap < j.bytes_in) {
-            if (g_stage.p) (void)hipHostFree(g_stage.p);
-            g_stage.p = nullptr; g_stage.cap = 0;
-            const size_t cap = (j.bytes_in + 65535) & ~(size_t)65535;
-            PRE3_HIP(hipHostMalloc(&g_stage.p, cap, hipHostMallocDefault));
-            g_stage.cap = cap;
+        if (up.bytes) {
+            PRE3_TRY(stage_reserve(up.stage_bytes));
+            plane_stage_fill(j, s, draws, up, g_stage.p);
+            PRE3_HIP(hipMemcpyAsync(d.as<char>() + up.off, g_stage.p, up.bytes, hipMemcpyHostToDevice, st));
         }
-        plane_pack(j, rows, x_sr, y_sr, z_sr, draws, g_stage.p);
-        PRE3_HIP(hipMemcpyAsync(d.p, g_stage.p, j.bytes_up, hipMemcpyHostToDevice, 0));
-        PRE3_TRY(plane_launch(j, (char *)d.p, t, 0, inlier_out != nullptr, nullptr, 0, sd));
-        PRE3_HIP(hipMemcpy(&o, (char *)d.p + j.off_out, sizeof o, hipMemcpyDeviceToHost));      // (synchronises: the block is free again)
+        PRE3_TRY(plane_launch(j, d.as<char>(), t, 0, inlier_out != nullptr, nullptr, st, sd, s.crop()));
+        // (either way the stream is idle afterwards: the staging block is free again)
+        if (st == nullptr) PRE3_HIP(hipMemcpy(&o, d.as<char>() + j.off_out, sizeof o, hipMemcpyDeviceToHost));
+        else {
+            PRE3_HIP(hipMemcpyAsync(&o, d.as<char>() + j.off_out, sizeof o, hipMemcpyDeviceToHost, st));
+            PRE3_HIP(hipStreamSynchronize(st));
+        }
     }
-    if (count_out) PRE3_HIP(hipMemcpy(count_out, (char *)d.p + j.off_counts, sizeof(int32_t) * (size_t)n_draw, hipMemcpyDeviceToHost));
-    if (inlier_out) PRE3_HIP(hipMemcpy(inlier_out, (char *)d.p + j.off_inl, sizeof(int32_t) * (size_t)j.npts, hipMemcpyDeviceToHost));
-    if (draws_out) PRE3_HIP(hipMemcpy(draws_out, (char *)d.p + j.off_draws, sizeof(int32_t) * 3 * (size_t)n_draw, hipMemcpyDeviceToHost));
     plane_result(o, res);
-    return PRE3_OK;
+    if (o.sta == 5) {
+        if (count_out) memset(count_out, 0, sizeof(int32_t) * (size_t)n_draw);
+        if (inlier_out) memset(inlier_out, 0, sizeof(int32_t) * (size_t)j.npts);
+        if (draws_out) memset(draws_out, 0, sizeof(int32_t) * 3 * (size_t)n_draw);
+        set_error("%s: a coordinate inside the box of the resident frame is not finite (sta = 5)", who);
+        return PRE3_E_NUMERIC;
+    }
+    return plane_read_back(j, d.as<char>(), count_out, inlier_out, draws_out);
 }
 
 int pre3_plane_fit(int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
                    int n_draw, const int32_t *draws, int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res)
 {
-    return plane_fit_impl("pre3_plane_fit", device, rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, draws, count_out, inlier_out, res, nullptr, nullptr);
+    return plane_fit_impl("pre3_plane_fit", host_planes(device, rows, cols, x_sr, y_sr, z_sr), box, t, n_draw, draws, count_out, inlier_out, res, nullptr, nullptr);
 }
 
 int pre3_plane_fit_seeded(int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
                           int n_draw, uint64_t seed, uint64_t seq, int32_t *draws_out, int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res)
 {
     const PlaneSeed sd{ seed, seq };
-    return plane_fit_impl("pre3_plane_fit_seeded", device, rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, nullptr, count_out, inlier_out, res, &sd, draws_out);
+    return plane_fit_impl("pre3_plane_fit_seeded", host_planes(device, rows, cols, x_sr, y_sr, z_sr), box, t, n_draw, nullptr, count_out, inlier_out, res, &sd,
+                          draws_out);
+}
+
+int pre3_plane_fit_frame(pre3_sr_frame *f, const int32_t *box, double t, int n_draw, const int32_t *draws, int32_t *count_out, int32_t *inlier_out,
+                         pre3_plane_result *res)
+{
+    return plane_fit_impl("pre3_plane_fit_frame", resident_frame(f), box, t, n_draw, draws, count_out, inlier_out, res, nullptr, nullptr);
+}
+
+int pre3_plane_fit_frame_seeded(pre3_sr_frame *f, const int32_t *box, double t, int n_draw, uint64_t seed, uint64_t seq, int32_t *draws_out,
+                                int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res)
+{
+    const PlaneSeed sd{ seed, seq };
+    return plane_fit_impl("pre3_plane_fit_frame_seeded", resident_frame(f), box, t, n_draw, nullptr, count_out, inlier_out, res, &sd, draws_out);
 }
 
 // measurement only: device time of one fit (upload + score + fit launches) between two events, averaged over reps warmed calls
 int pre3_plane_bench(int device, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
                      int n_draw, const int32_t *draws, int reps, double *ms_per_call)
 {
+    const char *who = "pre3_plane_bench";
     PlaneJob j;
-    PRE3_CHECK(reps >= 1 && ms_per_call != nullptr, PRE3_E_ARG, "pre3_plane_bench: bad arguments");
-    PRE3_TRY(plane_check("pre3_plane_bench", rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, draws, &j));
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
-    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return PRE3_E_NODEVICE; }
-    PlaneScratch d;
-    PRE3_TRY(scratch_acquire(j.bytes_total, &d.p, &d.slot));
+    PlaneSource s = host_planes(device, rows, cols, x_sr, y_sr, z_sr);
+    PRE3_CHECK(reps >= 1 && ms_per_call != nullptr, PRE3_E_ARG, "%s: bad arguments", who);
+    PRE3_TRY(plane_check(who, &s, box, t, n_draw, draws, &j));
+    PRE3_TRY(select_device(who, device));
+    Scratch d;
+    PRE3_TRY(d.alloc(j.bytes_total));
     void *st = nullptr;
     PRE3_HIP(hipHostMalloc(&st, j.bytes_in, hipHostMallocDefault));
-    plane_pack(j, rows, x_sr, y_sr, z_sr, draws, st);
+    plane_pack(j, s, draws, st);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = PRE3_OK;
     float ms = 0;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { set_error("pre3_plane_bench: event creation failed"); rc = PRE3_E_HIP; }
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { set_error("%s: event creation failed", who); rc = PRE3_E_HIP; }
     for (int r = -3; r < reps && rc == PRE3_OK; ++r) {       // three warm-up calls
-        if (r == 0 && hipEventRecord(e0, 0) != hipSuccess) { set_error("pre3_plane_bench: event record failed"); rc = PRE3_E_HIP; break; }
-        if (hipMemcpyAsync(d.p, st, j.bytes_in, hipMemcpyHostToDevice, 0) != hipSuccess) { set_error("pre3_plane_bench: upload failed"); rc = PRE3_E_HIP; break; }
-        rc = plane_launch(j, (char *)d.p, t, 0, false, nullptr, 0);
+        if (r == 0 && hipEventRecord(e0, 0) != hipSuccess) { set_error("%s: event record failed", who); rc = PRE3_E_HIP; break; }
+        if (hipMemcpyAsync(d.p, st, j.bytes_in, hipMemcpyHostToDevice, 0) != hipSuccess) { set_error("%s: upload failed", who); rc = PRE3_E_HIP; break; }
+        rc = plane_launch(j, d.as<char>(), t, 0, false, nullptr, 0);
     }
     if (rc == PRE3_OK && (hipEventRecord(e1, 0) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) {
-        set_error("pre3_plane_bench: event timing failed"); rc = PRE3_E_HIP;
+        set_error("%s: event timing failed", who); rc = PRE3_E_HIP;
     }
     (void)hipDeviceSynchronize();
     if (e0) (void)hipEventDestroy(e0);
@@ -546,7 +652,7 @@ int pre3_plane_bench(int device, int rows, int cols, const double *x_sr, const d
 }
 
 // the wait of the context forms, as pre3_heading_update with applied_out: the gate word, the result block and the error words behind one wait.
-// sta == 5 (the frame forms: a non-finite point in the box) is PRE3_E_NUMERIC with res filled, applied = 0 and a table of zeros.
+// sta == 5 (a resident frame: a non-finite point in the box) is PRE3_E_NUMERIC with res filled, applied = 0 and a table of zeros.
 static int heading_wait(pre3_ctx *c, const char *who, const PlaneJob &j, int32_t *applied_out, pre3_plane_result *res_out, int32_t *draws_out)
 {
     int32_t applied = 0;
@@ -569,170 +675,31 @@ static int heading_wait(pre3_ctx *c, const char *who, const PlaneJob &j, int32_t
     return rc;
 }
 
-static int heading_from_scan_impl(pre3_ctx *c, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
-                                  int n_draw, const int32_t *draws, int transpose, int strict_reference, int32_t *applied_out, pre3_plane_result *res_out,
-                                  const PlaneSeed *sd, int32_t *draws_out)
+// the fit in front of the heading rows, on the context's stream (DESIGN.md sections 17 and 23).  A resident frame is lent to that stream for the crop
+// and reclaimed behind the fit's launches, so that a load that follows cannot overwrite planes that are still being read.
+static int heading_impl(const char *who, pre3_ctx *c, PlaneSource s, const int32_t *box, double t, int n_draw, const int32_t *draws, int transpose,
+                        int strict_reference, int32_t *applied_out, pre3_plane_result *res_out, const PlaneSeed *sd, int32_t *draws_out)
 {
     PlaneJob j;
-    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "pre3_heading_from_scan: null context");
-    PRE3_TRY(plane_check("pre3_heading_from_scan", rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, draws, &j, sd != nullptr));
-    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE,
-               "pre3_heading_from_scan: acts on (x_k_k, p_k_k); the covariance buffer holds the prediction (update first)");
-    EntryScope scope(c); PRE3_TRY(scope.rc);
-    if (c->plane_bytes < j.bytes_total) {
-        if (c->plane_buf) { PRE3_TRY(stream_drain(c, __func__)); (void)hipFree(c->plane_buf); }
-        c->plane_buf = nullptr; c->plane_bytes = 0;
-        const size_t cap = j.bytes_total + j.bytes_total / 4;
-        PRE3_TRY(dmalloc_bytes(&c->plane_buf, cap));
-        c->plane_bytes = cap;
-    }
-    if (c->plane_src == nullptr) { void *p = nullptr; PRE3_TRY(dmalloc_bytes(&p, sizeof(HeadingSrc))); c->plane_src = (HeadingSrc *)p; }
-    void *st = nullptr, *st_dev = nullptr; int slot = 0;
-    PRE3_TRY(stage_acquire(c, j.bytes_in, &st, &st_dev, &slot));
-    plane_pack(j, rows, x_sr, y_sr, z_sr, draws, st);
-    PRE3_TRY(launch_pull(c, st, c->plane_buf, j.bytes_up, slot));
-    PRE3_TRY(stage_release(c, slot));
-    PRE3_TRY(plane_launch(j, (char *)c->plane_buf, t, transpose ? 1 : 0, false, c->plane_src, c->stream, sd));
-    RowsHeading hd{};
-    hd.on = 1; hd.strict = strict_reference ? 1 : 0; hd.src = c->plane_src;
-    c->rows_form = 1;
-    PRE3_TRY(launch_rows_update(c, nullptr, &hd));
-    c->hp_all_valid = false;
-    if (applied_out == nullptr && res_out == nullptr && draws_out == nullptr) return PRE3_OK;
-    return heading_wait(c, "pre3_heading_from_scan", j, applied_out, res_out, draws_out);
-}
-
-int pre3_heading_from_scan(pre3_ctx *c, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
-                           int n_draw, const int32_t *draws, int transpose, int strict_reference, int32_t *applied_out, pre3_plane_result *res_out)
-{
-    return heading_from_scan_impl(c, rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, draws, transpose, strict_reference, applied_out, res_out, nullptr, nullptr);
-}
-
-int pre3_heading_from_scan_seeded(pre3_ctx *c, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
-                                  int n_draw, uint64_t seed, uint64_t seq, int transpose, int strict_reference, int32_t *draws_out, int32_t *applied_out,
-                                  pre3_plane_result *res_out)
-{
-    const PlaneSeed sd{ seed, seq };
-    return heading_from_scan_impl(c, rows, cols, x_sr, y_sr, z_sr, box, t, n_draw, nullptr, transpose, strict_reference, applied_out, res_out, &sd, draws_out);
-}
-
-// ---- the same fit and heading update fed from a resident SR4000 frame --------------------------------------------------------
-namespace {
-struct StreamIdle {             // a work block goes back to its pool only once the stream that used it is idle, on every way out
-    hipStream_t st;
-    ~StreamIdle() { (void)hipStreamSynchronize(st); }
-};
-}  // namespace
-
-static int plane_fit_frame_impl(const char *who, pre3_sr_frame *f, const int32_t *box, double t, int n_draw, const int32_t *draws, int32_t *count_out,
-                                int32_t *inlier_out, pre3_plane_result *res, const PlaneSeed *sd, int32_t *draws_out)
-{
-    PlaneJob j;
-    SrFrameView v;
-    PRE3_CHECK(f != nullptr && res != nullptr, PRE3_E_ARG, "%s: null argument", who);
-    PRE3_TRY(sr_frame_view(f, &v));
-    PRE3_TRY(plane_job(who, v.rows, v.cols, box, t, n_draw, draws, &j, sd != nullptr));
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
-    if (hipSetDevice(v.device) != hipSuccess) { set_error("no HIP device %d", v.device); return PRE3_E_NODEVICE; }
-    PlaneScratch d;
-    PRE3_TRY(scratch_acquire(j.bytes_total, &d.p, &d.slot));
-    StreamIdle idle{ v.stream };
-    PlaneOut o;
-    {
-        std::lock_guard<std::mutex> lk(g_stage.mu);
-        const size_t b_draws = j.bytes_in - j.off_draws;
-        if (draws != nullptr) {                             // the table is the only thing that crosses PCIe
-            if (g_stage.cap < b_draws) {
-                if (g_stage.p) (void)hipHostFree(g_stage.p);
-                g_stage.p = nullptr; g_stage.cap = 0;
-                const size_t cap = (b_draws + 65535) & ~(size_t)65535;
-                PRE3_HIP(hipHostMalloc(&g_stage.p, cap, hipHostMallocDefault));
-                g_stage.cap = cap;
-            }
-            memset(g_stage.p, 0, b_draws);
-            memcpy(g_stage.p, draws, sizeof(int32_t) * 3 * (size_t)n_draw);
-            PRE3_HIP(hipMemcpyAsync((char *)d.p + j.off_draws, g_stage.p, b_draws, hipMemcpyHostToDevice, v.stream));
-        }
-        PRE3_TRY(plane_launch(j, (char *)d.p, t, 0, inlier_out != nullptr, nullptr, v.stream, sd, &v));
-        PRE3_HIP(hipMemcpyAsync(&o, (char *)d.p + j.off_out, sizeof o, hipMemcpyDeviceToHost, v.stream));
-        PRE3_HIP(hipStreamSynchronize(v.stream));           // (the staging block is free again)
-    }
-    plane_result(o, res);
-    if (o.sta == 5) {                                       // neither the table nor the scores were written
-        if (count_out) memset(count_out, 0, sizeof(int32_t) * (size_t)n_draw);
-        if (inlier_out) memset(inlier_out, 0, sizeof(int32_t) * (size_t)j.npts);
-        if (draws_out) memset(draws_out, 0, sizeof(int32_t) * 3 * (size_t)n_draw);
-        set_error("%s: a coordinate inside the box of the resident frame is not finite (sta = 5)", who);
-        return PRE3_E_NUMERIC;
-    }
-    if (count_out) PRE3_HIP(hipMemcpy(count_out, (char *)d.p + j.off_counts, sizeof(int32_t) * (size_t)n_draw, hipMemcpyDeviceToHost));
-    if (inlier_out) PRE3_HIP(hipMemcpy(inlier_out, (char *)d.p + j.off_inl, sizeof(int32_t) * (size_t)j.npts, hipMemcpyDeviceToHost));
-    if (draws_out) PRE3_HIP(hipMemcpy(draws_out, (char *)d.p + j.off_draws, sizeof(int32_t) * 3 * (size_t)n_draw, hipMemcpyDeviceToHost));
-    return PRE3_OK;
-}
-
-int pre3_plane_fit_frame(pre3_sr_frame *f, const int32_t *box, double t, int n_draw, const int32_t *draws, int32_t *count_out, int32_t *inlier_out,
-                         pre3_plane_result *res)
-{
-    return plane_fit_frame_impl("pre3_plane_fit_frame", f, box, t, n_draw, draws, count_out, inlier_out, res, nullptr, nullptr);
-}
-
-int pre3_plane_fit_frame_seeded(pre3_sr_frame *f, const int32_t *box, double t, int n_draw, uint64_t seed, uint64_t seq, int32_t *draws_out,
-                                int32_t *count_out, int32_t *inlier_out, pre3_plane_result *res)
-{
-    const PlaneSeed sd{ seed, seq };
-    return plane_fit_frame_impl("pre3_plane_fit_frame_seeded", f, box, t, n_draw, nullptr, count_out, inlier_out, res, &sd, draws_out);
-}
-
-// a block of the context that the frame form allocates: zeroed on the context's stream, which does not synchronise with the null stream
-static int plane_dmalloc(pre3_ctx *c, void **p, size_t bytes)
-{
-    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; set_error("hipMalloc of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
-    PRE3_HIP(hipMemsetAsync(*p, 0, bytes, c->stream));
-    return PRE3_OK;
-}
-
-static int heading_from_frame_impl(pre3_ctx *c, pre3_sr_frame *f, const int32_t *box, double t, int n_draw, const int32_t *draws, int transpose,
-                                   int strict_reference, int32_t *applied_out, pre3_plane_result *res_out, const PlaneSeed *sd, int32_t *draws_out)
-{
-    const char *who = "pre3_heading_from_frame";
-    PlaneJob j;
-    SrFrameView v;
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "%s: null context", who);
-    PRE3_CHECK(f != nullptr, PRE3_E_ARG, "%s: null handle", who);
-    PRE3_TRY(sr_frame_view(f, &v));
-    PRE3_CHECK(v.device == c->device, PRE3_E_ARG, "%s: the frame is on device %d, the context on device %d", who, v.device, c->device);
-    PRE3_TRY(plane_job(who, v.rows, v.cols, box, t, n_draw, draws, &j, sd != nullptr));
+    PRE3_CHECK(!s.resident || s.frame != nullptr, PRE3_E_ARG, "%s: null handle", who);
+    PRE3_TRY(plane_check(who, &s, box, t, n_draw, draws, &j, sd != nullptr));
+    PRE3_CHECK(!s.resident || s.device == c->device, PRE3_E_ARG, "%s: the frame is on device %d, the context on device %d", who, s.device, c->device);
     PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE,
                "%s: acts on (x_k_k, p_k_k); the covariance buffer holds the prediction (update first)", who);
     EntryScope scope(c); PRE3_TRY(scope.rc);
-    hipEvent_t ev = nullptr;
-    PRE3_TRY(sr_frame_pair_work(f, 0, 0, nullptr, nullptr, &ev));
-    if (c->plane_bytes < j.bytes_total) {
-        if (c->plane_buf) { PRE3_TRY(stream_drain(c, who)); (void)hipFree(c->plane_buf); }
-        c->plane_buf = nullptr; c->plane_bytes = 0;
-        const size_t cap = j.bytes_total + j.bytes_total / 4;
-        PRE3_TRY(plane_dmalloc(c, &c->plane_buf, cap));
-        c->plane_bytes = cap;
-    }
-    if (c->plane_src == nullptr) { void *p = nullptr; PRE3_TRY(plane_dmalloc(c, &p, sizeof(HeadingSrc))); c->plane_src = (HeadingSrc *)p; }
-    if (draws != nullptr) {                                 // a supplied table: the only bytes that cross PCIe, pulled where plane_pack would have put them
-        const size_t b_draws = j.bytes_in - j.off_draws;
+    PRE3_TRY(plane_reserve(c, who, j.bytes_total));
+    const PlaneUpload up = plane_upload(j, s, draws);
+    if (up.bytes) {
         void *st = nullptr, *st_dev = nullptr; int slot = 0;
-        PRE3_TRY(stage_acquire(c, b_draws, &st, &st_dev, &slot));
-        memset(st, 0, b_draws);
-        memcpy(st, draws, sizeof(int32_t) * 3 * (size_t)n_draw);
-        PRE3_TRY(launch_pull(c, st, (char *)c->plane_buf + j.off_draws, b_draws, slot));
+        PRE3_TRY(stage_acquire(c, up.stage_bytes, &st, &st_dev, &slot));
+        plane_stage_fill(j, s, draws, up, st);
+        PRE3_TRY(launch_pull(c, st, (char *)c->plane_buf + up.off, up.bytes, slot));
         PRE3_TRY(stage_release(c, slot));
     }
-    // the hand-off: the context's stream waits for the frame's conditioning launches; the release: the handle's stream waits for the crop, so that a
-    // load that follows cannot overwrite planes that are still being read (section 22's pattern)
-    PRE3_HIP(hipEventRecord(ev, v.stream));
-    PRE3_HIP(hipStreamWaitEvent(c->stream, ev, 0));
-    PRE3_TRY(plane_launch(j, (char *)c->plane_buf, t, transpose ? 1 : 0, false, c->plane_src, c->stream, sd, &v));
-    PRE3_HIP(hipEventRecord(ev, c->stream));
-    PRE3_HIP(hipStreamWaitEvent(v.stream, ev, 0));
+    if (s.resident) PRE3_TRY(sr_frame_lend(s.frame, c->stream));
+    PRE3_TRY(plane_launch(j, (char *)c->plane_buf, t, transpose ? 1 : 0, false, c->plane_src, c->stream, sd, s.crop()));
+    if (s.resident) PRE3_TRY(sr_frame_reclaim(s.frame, c->stream));
     RowsHeading hd{};
     hd.on = 1; hd.strict = strict_reference ? 1 : 0; hd.src = c->plane_src;
     c->rows_form = 1;
@@ -742,17 +709,35 @@ static int heading_from_frame_impl(pre3_ctx *c, pre3_sr_frame *f, const int32_t 
     return heading_wait(c, who, j, applied_out, res_out, draws_out);
 }
 
+int pre3_heading_from_scan(pre3_ctx *c, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
+                           int n_draw, const int32_t *draws, int transpose, int strict_reference, int32_t *applied_out, pre3_plane_result *res_out)
+{
+    return heading_impl("pre3_heading_from_scan", c, host_planes(0, rows, cols, x_sr, y_sr, z_sr), box, t, n_draw, draws, transpose, strict_reference,
+                        applied_out, res_out, nullptr, nullptr);
+}
+
+int pre3_heading_from_scan_seeded(pre3_ctx *c, int rows, int cols, const double *x_sr, const double *y_sr, const double *z_sr, const int32_t *box, double t,
+                                  int n_draw, uint64_t seed, uint64_t seq, int transpose, int strict_reference, int32_t *draws_out, int32_t *applied_out,
+                                  pre3_plane_result *res_out)
+{
+    const PlaneSeed sd{ seed, seq };
+    return heading_impl("pre3_heading_from_scan", c, host_planes(0, rows, cols, x_sr, y_sr, z_sr), box, t, n_draw, nullptr, transpose, strict_reference,
+                        applied_out, res_out, &sd, draws_out);
+}
+
 int pre3_heading_from_frame(pre3_ctx *c, pre3_sr_frame *f, const int32_t *box, double t, int n_draw, const int32_t *draws, int transpose,
                             int strict_reference, int32_t *applied_out, pre3_plane_result *res_out)
 {
-    return heading_from_frame_impl(c, f, box, t, n_draw, draws, transpose, strict_reference, applied_out, res_out, nullptr, nullptr);
+    return heading_impl("pre3_heading_from_frame", c, resident_frame(f), box, t, n_draw, draws, transpose, strict_reference, applied_out, res_out, nullptr,
+                        nullptr);
 }
 
 int pre3_heading_from_frame_seeded(pre3_ctx *c, pre3_sr_frame *f, const int32_t *box, double t, int n_draw, uint64_t seed, uint64_t seq, int transpose,
                                    int strict_reference, int32_t *draws_out, int32_t *applied_out, pre3_plane_result *res_out)
 {
     const PlaneSeed sd{ seed, seq };
-    return heading_from_frame_impl(c, f, box, t, n_draw, nullptr, transpose, strict_reference, applied_out, res_out, &sd, draws_out);
+    return heading_impl("pre3_heading_from_frame", c, resident_frame(f), box, t, n_draw, nullptr, transpose, strict_reference, applied_out, res_out, &sd,
+                        draws_out);
 }
 
 }  // extern "C"

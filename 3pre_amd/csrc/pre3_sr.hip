@@ -37,10 +37,10 @@ struct pre3_sr_frame {
     bool kp_raw_ok = true;                  // its descriptors passed the ranked IC route's bounds on their way through `stage`
     size_t kp_o_frm = 0, kp_o_des = 0;      // offsets of frm_out / des_out inside kp
     size_t kp_o_xyz = 0, kp_o_rho = 0, kp_o_idx = 0;      // ... of xyz_out / rho_out (written by gate 0 only) and keep_idx
-    // the pair stage's work block, its pinned image and the event other streams wait for (pre3_vopair.hip), allocated on its first use
+    // the pair stage's work block and its pinned image (pre3_vopair.hip), allocated on its first use
     void *pair_dev = nullptr, *pair_pin = nullptr;
     size_t pair_dev_bytes = 0, pair_pin_bytes = 0;
-    hipEvent_t pair_ev = nullptr;
+    hipEvent_t pair_ev = nullptr;   // carries the hand-offs to and from a consumer's stream (sr_frame_lend, sr_frame_reclaim)
 };
 
 namespace pre3 {
@@ -186,16 +186,6 @@ __global__ __launch_bounds__(KB) void k_sr_keypoints(KpArgs a)
     }
 }
 
-static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-static int sr_device(const char *who, int device)
-{
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("%s: no HIP device available (libpre3 has no CPU fallback)", who); return PRE3_E_NODEVICE; }
-    if (hipSetDevice(device) != hipSuccess) { set_error("%s: no HIP device %d", who, device); return PRE3_E_NODEVICE; }
-    return PRE3_OK;
-}
-
 // Device memory of the handle, zeroed ON THE HANDLE'S STREAM: the stream does not synchronise with the null stream (hipStreamNonBlocking), so a
 // hipMemset there -- asynchronous to the host -- could land behind the first transfer queued into the block.
 static int sr_dmalloc(pre3_sr_frame *f, void **p, size_t bytes)
@@ -217,6 +207,14 @@ static int sr_grow_stage(pre3_sr_frame *f, size_t bytes)
 }
 
 }  // namespace
+
+int select_device(const char *who, int device)
+{
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("%s: no HIP device available (libpre3 has no CPU fallback)", who); return PRE3_E_NODEVICE; }
+    if (hipSetDevice(device) != hipSuccess) { set_error("%s: no HIP device %d", who, device); return PRE3_E_NODEVICE; }
+    return PRE3_OK;
+}
 
 int sr_frame_view(pre3_sr_frame *f, SrFrameView *v)
 {
@@ -250,10 +248,9 @@ int sr_frame_keypoint_view(pre3_sr_frame *f, SrKeypointView *v)
 
 // dev_bytes of device memory and pin_bytes of pinned host memory owned by the handle, grown on demand; a new device block is zeroed on the handle's stream
 // (sr_dmalloc's rule).  The caller has made sure that nothing queued still uses the old blocks.
-int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, void **dev, void **pin, hipEvent_t *ev)
+int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, void **dev, void **pin)
 {
     PRE3_CHECK(f != nullptr, PRE3_E_ARG, "sr_frame_pair_work: null handle");
-    if (f->pair_ev == nullptr) PRE3_HIP(hipEventCreateWithFlags(&f->pair_ev, hipEventDisableTiming));
     if (f->pair_dev_bytes < dev_bytes) {
         if (f->pair_dev) (void)hipFree(f->pair_dev);
         f->pair_dev = nullptr; f->pair_dev_bytes = 0;
@@ -267,9 +264,38 @@ int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, voi
         PRE3_HIP(hipHostMalloc(&f->pair_pin, cap, hipHostMallocDefault));
         f->pair_pin_bytes = cap;
     }
-    if (dev) *dev = f->pair_dev;
-    if (pin) *pin = f->pair_pin;
-    if (ev) *ev = f->pair_ev;
+    *dev = f->pair_dev; *pin = f->pair_pin;
+    return PRE3_OK;
+}
+
+int sr_frame_lend(pre3_sr_frame *f, hipStream_t consumer)
+{
+    PRE3_CHECK(f != nullptr, PRE3_E_ARG, "sr_frame_lend: null handle");
+    PRE3_HIP(hipEventRecord(f->pair_ev, f->stream));
+    PRE3_HIP(hipStreamWaitEvent(consumer, f->pair_ev, 0));
+    return PRE3_OK;
+}
+
+int sr_frame_reclaim(pre3_sr_frame *f, hipStream_t consumer)
+{
+    PRE3_CHECK(f != nullptr, PRE3_E_ARG, "sr_frame_reclaim: null handle");
+    PRE3_HIP(hipEventRecord(f->pair_ev, consumer));
+    PRE3_HIP(hipStreamWaitEvent(f->stream, f->pair_ev, 0));
+    return PRE3_OK;
+}
+
+int sr_frame_pair_views(const char *who, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, SrFrameView *v1, SrFrameView *v2, SrKeypointView *k1,
+                        SrKeypointView *k2)
+{
+    PRE3_CHECK(prev != nullptr && cur != nullptr, PRE3_E_ARG, "%s: null handle", who);
+    PRE3_CHECK(prev != cur, PRE3_E_ARG, "%s: prev and cur are the same handle", who);
+    PRE3_CHECK(std::isfinite(thresh) && thresh > 0.0, PRE3_E_ARG, "%s: thresh must be positive and finite", who);
+    PRE3_TRY(sr_frame_view(prev, v1)); PRE3_TRY(sr_frame_view(cur, v2));
+    PRE3_CHECK(v1->device == v2->device && v1->rows == v2->rows && v1->cols == v2->cols, PRE3_E_ARG,
+               "%s: the frames differ (device %d, %d x %d against device %d, %d x %d)", who, v1->device, v1->rows, v1->cols, v2->device, v2->rows, v2->cols);
+    PRE3_TRY(sr_frame_keypoint_view(prev, k1)); PRE3_TRY(sr_frame_keypoint_view(cur, k2));
+    PRE3_CHECK(k1->ND == DESC_DIM && k2->ND == DESC_DIM, PRE3_E_ARG, "%s: descriptors of %d and %d entries (the matcher's tile is written for %d)", who,
+               k1->ND, k2->ND, DESC_DIM);
     return PRE3_OK;
 }
 
@@ -308,6 +334,7 @@ static int sr_create_buffers(pre3_sr_frame *f)
 {
     const size_t npix = (size_t)f->rows * f->cols;
     PRE3_HIP(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    PRE3_HIP(hipEventCreateWithFlags(&f->pair_ev, hipEventDisableTiming));
     PRE3_TRY(sr_dmalloc(f, (void **)&f->raw, sizeof(double) * 5 * npix));
     PRE3_TRY(sr_dmalloc(f, (void **)&f->filt, sizeof(double) * 4 * npix));
     PRE3_TRY(sr_dmalloc(f, (void **)&f->maxima, sizeof(double) * 2));
@@ -320,7 +347,7 @@ int pre3_sr_frame_create(pre3_sr_frame **out, int device, int rows, int cols)
     PRE3_CHECK(out != nullptr, PRE3_E_ARG, "pre3_sr_frame_create: null argument");
     *out = nullptr;
     PRE3_CHECK(rows >= 1 && cols >= 1 && (long long)rows * cols <= (1ll << 26), PRE3_E_ARG, "pre3_sr_frame_create: a %d x %d frame", rows, cols);
-    PRE3_TRY(sr_device("pre3_sr_frame_create", device));
+    PRE3_TRY(select_device("pre3_sr_frame_create", device));
     pre3_sr_frame *f = new pre3_sr_frame;
     f->device = device; f->rows = rows; f->cols = cols;
     const int rc = sr_create_buffers(f);
@@ -337,7 +364,7 @@ int pre3_sr_frame_load(pre3_sr_frame *f, int mode, const double *z, const double
     for (size_t i = 0; i < npix; ++i)                         // MATLAB's sqrt of a negative amplitude goes complex
         PRE3_CHECK(std::isfinite(amp[i]) && amp[i] >= 0.0, PRE3_E_ARG, "pre3_sr_frame_load: the amplitude at row %d, column %d is negative or not finite",
                    (int)(i % f->rows) + 1, (int)(i / f->rows) + 1);
-    PRE3_TRY(sr_device("pre3_sr_frame_load", f->device));
+    PRE3_TRY(select_device("pre3_sr_frame_load", f->device));
     PRE3_HIP(hipStreamSynchronize(f->stream));                // the staging block may still be the source of the previous load's transfer
     double *st = (double *)f->stage;
     memcpy(st, z, sizeof(double) * npix); memcpy(st + npix, x, sizeof(double) * npix); memcpy(st + 2 * npix, y, sizeof(double) * npix);
@@ -362,7 +389,7 @@ int pre3_sr_frame_get(pre3_sr_frame *f, double *x, double *y, double *z, double 
     PRE3_CHECK(f != nullptr, PRE3_E_ARG, "pre3_sr_frame_get: null handle");
     PRE3_CHECK(f->loaded, PRE3_E_STATE, "pre3_sr_frame_get: no frame has been loaded");
     PRE3_CHECK(conf == nullptr || f->has_conf, PRE3_E_ARG, "pre3_sr_frame_get: the frame was loaded without a confidence map");
-    PRE3_TRY(sr_device("pre3_sr_frame_get", f->device));
+    PRE3_TRY(select_device("pre3_sr_frame_get", f->device));
     const size_t npix = (size_t)f->rows * f->cols, nb = sizeof(double) * npix;
     double mx[2];
     if (x) PRE3_HIP(hipMemcpyAsync(x, f->filt, nb, hipMemcpyDeviceToHost, f->stream));
@@ -396,7 +423,7 @@ static int sr_keypoints_impl(pre3_sr_frame *f, int gate, int ldf, int K, const d
         PRE3_CHECK(r >= 1.0 && r <= (double)f->rows && c >= 1.0 && c <= (double)f->cols, PRE3_E_ARG,
                    "pre3_sr_frame_keypoints: keypoint %d rounds to row %.0f, column %.0f outside the %d x %d frame", k, r, c, f->rows, f->cols);
     }
-    PRE3_TRY(sr_device("pre3_sr_frame_keypoints", f->device));
+    PRE3_TRY(select_device("pre3_sr_frame_keypoints", f->device));
     *n_kept = 0;
     *touched = true;
     f->kp_valid = 1; f->kp_K = K; f->kp_ldf = ldf; f->kp_ND = ND; f->kp_gate = gate; f->kp_n = 0;      // a valid empty record until the count is in

@@ -47,14 +47,6 @@ __global__ void k_vo_final(int pnum, int n_hyp, const double *__restrict__ pset1
 }
 
 
-struct DevMem {                    // pooled device scratch (pre3_match.hip): no hipMalloc / hipFree per call once warm
-    void *p = nullptr;
-    int slot = -1;
-    ~DevMem() { scratch_release(slot, p); }
-    int alloc(size_t bytes) { return scratch_acquire(bytes, &p, &slot); }
-    template <typename T> T *as() { return (T *)p; }
-};
-
 // the seeded forms: the draws come from k_draw_vo, which reads the match list (2 x pnum doubles, column-major) on the device
 struct VoSeed { unsigned long long seed, seq; const double *match_dev; int32_t *draws_out, *capped_out; };
 
@@ -62,7 +54,7 @@ static int vo_run(int pnum, const double *d_p1, const double *d_p2, int n_hyp, c
                   int32_t *inlier_out, pre3_vo_result *res, int reps, double *ms_out, const VoSeed *sd = nullptr)
 {
     const int words = ceil_div(pnum, 64);
-    DevMem dd, dm, dc, ds, dout, dinl, dcap;
+    Scratch dd, dm, dc, ds, dout, dinl, dcap;
     PRE3_TRY(dd.alloc(sizeof(int32_t) * 4 * (size_t)n_hyp)); PRE3_TRY(dm.alloc(sizeof(unsigned long long) * (size_t)n_hyp * words));
     PRE3_TRY(dc.alloc(sizeof(int32_t) * n_hyp)); PRE3_TRY(ds.alloc(sizeof(int32_t) * n_hyp)); PRE3_TRY(dout.alloc(sizeof(VoOut)));
     PRE3_TRY(dinl.alloc(sizeof(int32_t) * pnum));
@@ -100,23 +92,16 @@ static int vo_run(int pnum, const double *d_p1, const double *d_p2, int n_hyp, c
     if (cnum_out) PRE3_HIP(hipMemcpy(cnum_out, dc.p, sizeof(int32_t) * n_hyp, hipMemcpyDeviceToHost));
     if (state_out) PRE3_HIP(hipMemcpy(state_out, ds.p, sizeof(int32_t) * n_hyp, hipMemcpyDeviceToHost));
     if (inlier_out) PRE3_HIP(hipMemcpy(inlier_out, dinl.p, sizeof(int32_t) * pnum, hipMemcpyDeviceToHost));
-    if (res) {
-        memcpy(res->rot, o.rot, sizeof o.rot); memcpy(res->trans, o.trans, sizeof o.trans); memcpy(res->euler, o.euler, sizeof o.euler);
-        memcpy(res->u, o.u, sizeof o.u);
-        res->error_mean = o.error_mean; res->error_std = o.error_std; res->dist = o.dist;
-        res->sta = o.sta; res->n_support = o.n_support; res->n_iterations = o.n_iterations; res->best = o.best;
-    }
+    if (res) vo_result(o, res);
     return PRE3_OK;
 }
 
 static int vo_check(int device, int pnum, int n_hyp, const int32_t *draws, bool seeded = false)
 {
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device available (libpre3 has no CPU fallback)"); return PRE3_E_NODEVICE; }
+    PRE3_TRY(select_device("vo", device));
     PRE3_CHECK(pnum >= 4, PRE3_E_ARG, "vo: number of points is smaller than 4: insufficient for ransac");      // ransac_dr_ye.m:5-11
     PRE3_CHECK(n_hyp >= 1 && (draws || seeded), PRE3_E_ARG, "vo: no hypotheses");
     for (int i = 0; !seeded && i < 4 * n_hyp; ++i) PRE3_CHECK(draws[i] >= 0 && draws[i] < pnum, PRE3_E_ARG, "vo: draws[%d]=%d is not a match position (pnum=%d)", i, draws[i], pnum);
-    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device %d", device); return PRE3_E_NODEVICE; }
     return PRE3_OK;
 }
 
@@ -131,7 +116,7 @@ int pre3_vo_ransac(int device, int pnum, const double *pset1, const double *pset
 {
     PRE3_TRY(vo_check(device, pnum, n_hyp, draws));
     PRE3_CHECK(pset1 && pset2, PRE3_E_ARG, "pre3_vo_ransac: null point set");
-    DevMem p1, p2;
+    Scratch p1, p2;
     PRE3_TRY(p1.alloc(sizeof(double) * 3 * pnum)); PRE3_TRY(p2.alloc(sizeof(double) * 3 * pnum));
     PRE3_HIP(hipMemcpy(p1.p, pset1, sizeof(double) * 3 * pnum, hipMemcpyHostToDevice));
     PRE3_HIP(hipMemcpy(p2.p, pset2, sizeof(double) * 3 * pnum, hipMemcpyHostToDevice));
@@ -143,7 +128,7 @@ int pre3_vo_ransac_seeded(int device, int pnum, const double *pset1, const doubl
 {
     PRE3_TRY(vo_check(device, pnum, n_hyp, nullptr, true));
     PRE3_CHECK(pset1 && pset2 && match, PRE3_E_ARG, "pre3_vo_ransac_seeded: null point set or match list");
-    DevMem p1, p2, mt;
+    Scratch p1, p2, mt;
     PRE3_TRY(p1.alloc(sizeof(double) * 3 * pnum)); PRE3_TRY(p2.alloc(sizeof(double) * 3 * pnum)); PRE3_TRY(mt.alloc(sizeof(double) * 2 * pnum));
     PRE3_HIP(hipMemcpy(p1.p, pset1, sizeof(double) * 3 * pnum, hipMemcpyHostToDevice));
     PRE3_HIP(hipMemcpy(p2.p, pset2, sizeof(double) * 3 * pnum, hipMemcpyHostToDevice));
@@ -161,7 +146,7 @@ static int vo_frames(int device, int rows, int cols, const double *x1, const dou
     PRE3_CHECK(rows > 0 && cols > 0 && x1 && y1 && z1 && x2 && y2 && z2 && frm1 && frm2 && match && ldf >= 2 && K1 > 0 && K2 > 0, PRE3_E_ARG,
                "pre3_vo_ransac_frames: bad arguments");
     const size_t img = sizeof(double) * (size_t)rows * cols;
-    DevMem im, f1, f2, mt, p1, p2, bad;
+    Scratch im, f1, f2, mt, p1, p2, bad;
     PRE3_TRY(im.alloc(6 * img)); PRE3_TRY(f1.alloc(sizeof(double) * (size_t)ldf * K1)); PRE3_TRY(f2.alloc(sizeof(double) * (size_t)ldf * K2));
     PRE3_TRY(mt.alloc(sizeof(double) * 2 * pnum)); PRE3_TRY(p1.alloc(sizeof(double) * 3 * pnum)); PRE3_TRY(p2.alloc(sizeof(double) * 3 * pnum));
     PRE3_TRY(bad.alloc(sizeof(int32_t)));
@@ -211,7 +196,7 @@ int pre3_vo_bench(int device, int pnum, const double *pset1, const double *pset2
 {
     PRE3_TRY(vo_check(device, pnum, n_hyp, draws));
     PRE3_CHECK(pset1 && pset2 && reps >= 1 && ms_per_call, PRE3_E_ARG, "pre3_vo_bench: bad arguments");
-    DevMem p1, p2;
+    Scratch p1, p2;
     PRE3_TRY(p1.alloc(sizeof(double) * 3 * pnum)); PRE3_TRY(p2.alloc(sizeof(double) * 3 * pnum));
     PRE3_HIP(hipMemcpy(p1.p, pset1, sizeof(double) * 3 * pnum, hipMemcpyHostToDevice));
     PRE3_HIP(hipMemcpy(p2.p, pset2, sizeof(double) * 3 * pnum, hipMemcpyHostToDevice));

@@ -17,6 +17,13 @@ struct VoOut {                 // device-side result block
     double error_mean, error_std, dist;
     int32_t sta, n_support, n_iterations, best, dist_ok, pad[3];
 };
+inline void vo_result(const VoOut &o, pre3_vo_result *res)      // the block as the ABI hands it out
+{
+    memcpy(res->rot, o.rot, sizeof o.rot); memcpy(res->trans, o.trans, sizeof o.trans); memcpy(res->euler, o.euler, sizeof o.euler);
+    memcpy(res->u, o.u, sizeof o.u);
+    res->error_mean = o.error_mean; res->error_std = o.error_std; res->dist = o.dist;
+    res->sta = o.sta; res->n_support = o.n_support; res->n_iterations = o.n_iterations; res->best = o.best;
+}
 
 // svd of a 3x3 by one-sided Jacobi; returns U, sv, V with H = U diag(sv) V'
 __device__ inline void vo_svd3(const double *H, double *U, double *sv, double *V)

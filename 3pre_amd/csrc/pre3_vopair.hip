@@ -109,8 +109,6 @@ __global__ __launch_bounds__(64) void k_vp_final(const VoPairHeader *__restrict_
     vo_final_wave(pnum, hdr->rst, pset1, pset2, cnum, (pnum + 63) / 64, masks, out, inl_out);
 }
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 // vodometry_dr_ye.m:152-160: fewer than four matches
 void vo_no_solution(pre3_vo_result *res)
 {
@@ -149,18 +147,11 @@ int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, 
                         double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out, int32_t *state_out,
                         int32_t *inlier_out, pre3_vo_result *res)
 {
-    PRE3_CHECK(prev != nullptr && cur != nullptr, PRE3_E_ARG, "pre3_vo_pair_seeded: null handle");
-    PRE3_CHECK(prev != cur, PRE3_E_ARG, "pre3_vo_pair_seeded: prev and cur are the same handle");
-    PRE3_CHECK(std::isfinite(thresh) && thresh > 0.0, PRE3_E_ARG, "pre3_vo_pair_seeded: thresh must be positive and finite");
+    const char *who = "pre3_vo_pair_seeded";
     SrFrameView v1, v2;
     SrKeypointView k1, k2;
-    PRE3_TRY(sr_frame_view(prev, &v1)); PRE3_TRY(sr_frame_view(cur, &v2));
-    PRE3_CHECK(v1.device == v2.device && v1.rows == v2.rows && v1.cols == v2.cols, PRE3_E_ARG,
-               "pre3_vo_pair_seeded: the frames differ (device %d, %d x %d against device %d, %d x %d)", v1.device, v1.rows, v1.cols, v2.device, v2.rows, v2.cols);
-    PRE3_TRY(sr_frame_keypoint_view(prev, &k1)); PRE3_TRY(sr_frame_keypoint_view(cur, &k2));
-    PRE3_CHECK(k1.ND == DESC_DIM && k2.ND == DESC_DIM, PRE3_E_ARG, "pre3_vo_pair_seeded: descriptors of %d and %d entries (the matcher's tile is written for %d)",
-               k1.ND, k2.ND, DESC_DIM);
-    if (hipSetDevice(v2.device) != hipSuccess) { set_error("pre3_vo_pair_seeded: no HIP device %d", v2.device); return PRE3_E_NODEVICE; }
+    PRE3_TRY(sr_frame_pair_views(who, prev, cur, thresh, &v1, &v2, &k1, &k2));
+    PRE3_TRY(select_device(who, v2.device));
     const int n1 = k1.n_kept, n2 = k2.n_kept;
     if (pnum_out) *pnum_out = 0;
     if (n1 == 0 || n2 == 0) { vo_no_solution(res); return PRE3_OK; }      // siftmatch of an empty set: no match, nothing to queue
@@ -181,12 +172,9 @@ int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, 
     if (state_out) need = o_inl;
     if (inlier_out) need = o_end;
     char *d = nullptr, *pin = nullptr;
-    hipEvent_t ev_cur = nullptr, ev_prev = nullptr;
-    PRE3_TRY(sr_frame_pair_work(prev, 0, 0, nullptr, nullptr, &ev_prev));
-    PRE3_TRY(sr_frame_pair_work(cur, total, o_end, (void **)&d, (void **)&pin, &ev_cur));
+    PRE3_TRY(sr_frame_pair_work(cur, total, o_end, (void **)&d, (void **)&pin));
     hipStream_t st = v2.stream;
-    PRE3_HIP(hipEventRecord(ev_prev, v1.stream));
-    PRE3_HIP(hipStreamWaitEvent(st, ev_prev, 0));
+    PRE3_TRY(sr_frame_lend(prev, st));
     PRE3_HIP(hipMemsetAsync(d, 0, o_match, st));                          // the header (*capped starts at zero) and the result block
 
     VoPairHeader *hdr = (VoPairHeader *)d;
@@ -205,8 +193,7 @@ int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, 
                        (const unsigned long long *)masks, out, inl);
     PRE3_HIP(hipGetLastError());
     PRE3_HIP(hipMemcpyAsync(pin, d, need, hipMemcpyDeviceToHost, st));
-    PRE3_HIP(hipEventRecord(ev_cur, st));
-    PRE3_HIP(hipStreamWaitEvent(v1.stream, ev_cur, 0));                   // a later load into prev stays behind these reads
+    PRE3_TRY(sr_frame_reclaim(prev, st));                                 // a later load into prev stays behind these reads
     PRE3_HIP(hipStreamSynchronize(st));
 
     const VoPairHeader h = *(const VoPairHeader *)pin;
@@ -226,12 +213,7 @@ int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, 
     if (cnum_out) memcpy(cnum_out, pin + o_cnum, sizeof(int32_t) * (size_t)rst);
     if (state_out) memcpy(state_out, pin + o_state, sizeof(int32_t) * (size_t)rst);
     if (inlier_out) memcpy(inlier_out, pin + o_inl, sizeof(int32_t) * (size_t)pnum);
-    if (res) {
-        memcpy(res->rot, o.rot, sizeof o.rot); memcpy(res->trans, o.trans, sizeof o.trans); memcpy(res->euler, o.euler, sizeof o.euler);
-        memcpy(res->u, o.u, sizeof o.u);
-        res->error_mean = o.error_mean; res->error_std = o.error_std; res->dist = o.dist;
-        res->sta = o.sta; res->n_support = o.n_support; res->n_iterations = o.n_iterations; res->best = o.best;
-    }
+    if (res) vo_result(o, res);
     return PRE3_OK;
 }
 

@@ -70,56 +70,6 @@ def _result(res):
                 sta=int(res.sta), n_inliers=int(res.n_inliers), n_trials=int(res.n_trials), best=int(res.best))
 
 
-def plane_fit(x_sr, y_sr, z_sr, draws, box=None, t=0.02, device=0):
-    """[R, T] = plane_fit_to_data(idx) on the range image (rows, cols) in SR4000 coordinates; draws (n_draw, 3) 0-based positions in the cropped
-    point list (draw_plane_hypotheses).  Returns a dict: R (3, 3), B, p_orig, p_ray, N, sta (1 ok, 0 no inlier, 2 the stopping rule wanted more
-    draws, 3 axes undefined), n_inliers, n_trials, best, counts (the score of every draw), inliers (the winner's mask over the cropped points)."""
-    imgs = _images(x_sr, y_sr, z_sr)
-    rows, cols = imgs[0].shape
-    draws = i32(draws).reshape(-1, 3)
-    bx = _box(box)
-    if bx is not None and bx.shape[0] != 4:
-        raise Pre3Error(-1, "plane_fit: box is (row0, row1, col0, col1)")
-    r0, r1, c0, c1 = DEFAULT_BOX if bx is None else bx
-    npts = max(0, int(r1) - int(r0) + 1) * max(0, int(c1) - int(c0) + 1)
-    counts, inl = np.zeros(max(draws.shape[0], 1), np.int32), np.zeros(max(npts, 1), np.int32)
-    res = PlaneResult()
-    check(lib.pre3_plane_fit(int(device), rows, cols, dptr(imgs[0]), dptr(imgs[1]), dptr(imgs[2]), dptr(bx), float(t), draws.shape[0], dptr(draws),
-                             dptr(counts), dptr(inl), C.byref(res)))
-    out = _result(res)
-    out["counts"], out["inliers"] = counts[:draws.shape[0]], inl[:npts].astype(bool)
-    return out
-
-
-def plane_fit_seeded(x_sr, y_sr, z_sr, seed, seq=0, n_draw=MAX_DRAWS, box=None, t=0.02, device=0):
-    """plane_fit with the draws made on the device from (seed, seq) by ransac.m:142-176's rule (DESIGN.md section 18): only the box crosses PCIe.
-    The dict also carries draws (n_draw, 3)."""
-    imgs = _images(x_sr, y_sr, z_sr)
-    rows, cols = imgs[0].shape
-    bx = _box(box)
-    if bx is not None and bx.shape[0] != 4:
-        raise Pre3Error(-1, "plane_fit_seeded: box is (row0, row1, col0, col1)")
-    r0, r1, c0, c1 = DEFAULT_BOX if bx is None else bx
-    npts = max(0, int(r1) - int(r0) + 1) * max(0, int(c1) - int(c0) + 1)
-    n_draw = int(n_draw)
-    nd = min(max(n_draw, 1), MAX_DRAWS)
-    draws, counts, inl = np.zeros((nd, 3), np.int32), np.zeros(nd, np.int32), np.zeros(max(npts, 1), np.int32)
-    res = PlaneResult()
-    check(lib.pre3_plane_fit_seeded(int(device), rows, cols, dptr(imgs[0]), dptr(imgs[1]), dptr(imgs[2]), dptr(bx), float(t), n_draw, int(seed), int(seq),
-                                    dptr(draws), dptr(counts), dptr(inl), C.byref(res)))
-    out = _result(res)
-    out["counts"], out["inliers"], out["draws"] = counts[:n_draw], inl[:npts].astype(bool), draws[:n_draw]
-    return out
-
-
-def _frame_box(who, frame, box):
-    bx = _box(box)
-    if bx is not None and bx.shape[0] != 4:
-        raise Pre3Error(-1, "%s: box is (row0, row1, col0, col1)" % who)
-    r0, r1, c0, c1 = DEFAULT_BOX if bx is None else bx
-    return bx, max(0, int(r1) - int(r0) + 1) * max(0, int(c1) - int(c0) + 1)
-
-
 def _check_frame(rc, res):
     """check() that hands the result block of a refused box to the caller: Pre3Error.result (sta = 5) on PRE3_E_NUMERIC"""
     try:
@@ -130,32 +80,66 @@ def _check_frame(rc, res):
         raise
 
 
+def _fit(who, box, draws, n_draw, call, frame=False):
+    """The marshalling of the four fit wrappers: the box and its point count, the output arrays, the call and the result dict.  draws: the supplied
+    table (n_draw, 3), or None for a seeded form, whose table of n_draw rows comes back in the dict.  call(box, n_draw, draws, counts, inliers, res)
+    makes the library call and returns its status."""
+    bx = _box(box)
+    if bx is not None and bx.shape[0] != 4:
+        raise Pre3Error(-1, "%s: box is (row0, row1, col0, col1)" % who)
+    r0, r1, c0, c1 = DEFAULT_BOX if bx is None else bx
+    npts = max(0, int(r1) - int(r0) + 1) * max(0, int(c1) - int(c0) + 1)
+    seeded = draws is None
+    if seeded:
+        n_draw = int(n_draw)
+        draws = np.zeros((min(max(n_draw, 1), MAX_DRAWS), 3), np.int32)
+    else:
+        n_draw = draws.shape[0]
+    counts, inl = np.zeros(max(draws.shape[0], 1), np.int32), np.zeros(max(npts, 1), np.int32)
+    res = PlaneResult()
+    rc = call(dptr(bx), n_draw, dptr(draws), dptr(counts), dptr(inl), C.byref(res))
+    if frame:
+        _check_frame(rc, res)
+    else:
+        check(rc)
+    out = _result(res)
+    out["counts"], out["inliers"] = counts[:n_draw], inl[:npts].astype(bool)
+    if seeded:
+        out["draws"] = draws[:n_draw]
+    return out
+
+
+def plane_fit(x_sr, y_sr, z_sr, draws, box=None, t=0.02, device=0):
+    """[R, T] = plane_fit_to_data(idx) on the range image (rows, cols) in SR4000 coordinates; draws (n_draw, 3) 0-based positions in the cropped
+    point list (draw_plane_hypotheses).  Returns a dict: R (3, 3), B, p_orig, p_ray, N, sta (1 ok, 0 no inlier, 2 the stopping rule wanted more
+    draws, 3 axes undefined), n_inliers, n_trials, best, counts (the score of every draw), inliers (the winner's mask over the cropped points)."""
+    imgs = _images(x_sr, y_sr, z_sr)
+    rows, cols = imgs[0].shape
+    return _fit("plane_fit", box, i32(draws).reshape(-1, 3), None, lambda bx, nd, dr, cnt, inl, res: lib.pre3_plane_fit(
+        int(device), rows, cols, dptr(imgs[0]), dptr(imgs[1]), dptr(imgs[2]), bx, float(t), nd, dr, cnt, inl, res))
+
+
+def plane_fit_seeded(x_sr, y_sr, z_sr, seed, seq=0, n_draw=MAX_DRAWS, box=None, t=0.02, device=0):
+    """plane_fit with the draws made on the device from (seed, seq) by ransac.m:142-176's rule (DESIGN.md section 18): only the box crosses PCIe.
+    The dict also carries draws (n_draw, 3)."""
+    imgs = _images(x_sr, y_sr, z_sr)
+    rows, cols = imgs[0].shape
+    return _fit("plane_fit_seeded", box, None, n_draw, lambda bx, nd, dr, cnt, inl, res: lib.pre3_plane_fit_seeded(
+        int(device), rows, cols, dptr(imgs[0]), dptr(imgs[1]), dptr(imgs[2]), bx, float(t), nd, int(seed), int(seq), dr, cnt, inl, res))
+
+
 def plane_fit_frame(frame, draws, box=None, t=0.02):
     """plane_fit on the filtered planes a resident sr4000.SrFrame holds: the box is gathered on the device, only the draw table
     crosses PCIe.  The dict is plane_fit's, bit for bit what plane_fit(*frame.planes()[:3], draws, box, t) returns.  A non-finite coordinate inside the
     box raises Pre3Error with code -5 (PRE3_E_NUMERIC); its .result carries sta = 5."""
-    draws = i32(draws).reshape(-1, 3)
-    bx, npts = _frame_box("plane_fit_frame", frame, box)
-    counts, inl = np.zeros(max(draws.shape[0], 1), np.int32), np.zeros(max(npts, 1), np.int32)
-    res = PlaneResult()
-    _check_frame(lib.pre3_plane_fit_frame(frame._h, dptr(bx), float(t), draws.shape[0], dptr(draws), dptr(counts), dptr(inl), C.byref(res)), res)
-    out = _result(res)
-    out["counts"], out["inliers"] = counts[:draws.shape[0]], inl[:npts].astype(bool)
-    return out
+    return _fit("plane_fit_frame", box, i32(draws).reshape(-1, 3), None, lambda bx, nd, dr, cnt, inl, res: lib.pre3_plane_fit_frame(
+        frame._h, bx, float(t), nd, dr, cnt, inl, res), frame=True)
 
 
 def plane_fit_frame_seeded(frame, seed, seq=0, n_draw=MAX_DRAWS, box=None, t=0.02):
     """plane_fit_seeded on the filtered planes a resident sr4000.SrFrame holds: nothing crosses PCIe on the way in.  The dict also carries draws."""
-    bx, npts = _frame_box("plane_fit_frame_seeded", frame, box)
-    n_draw = int(n_draw)
-    nd = min(max(n_draw, 1), MAX_DRAWS)
-    draws, counts, inl = np.zeros((nd, 3), np.int32), np.zeros(nd, np.int32), np.zeros(max(npts, 1), np.int32)
-    res = PlaneResult()
-    _check_frame(lib.pre3_plane_fit_frame_seeded(frame._h, dptr(bx), float(t), n_draw, int(seed), int(seq), dptr(draws), dptr(counts), dptr(inl),
-                                                 C.byref(res)), res)
-    out = _result(res)
-    out["counts"], out["inliers"], out["draws"] = counts[:n_draw], inl[:npts].astype(bool), draws[:n_draw]
-    return out
+    return _fit("plane_fit_frame_seeded", box, None, n_draw, lambda bx, nd, dr, cnt, inl, res: lib.pre3_plane_fit_frame_seeded(
+        frame._h, bx, float(t), nd, int(seed), int(seq), dr, cnt, inl, res), frame=True)
 
 
 def plane_bench(x_sr, y_sr, z_sr, draws, box=None, t=0.02, reps=50, device=0):

@@ -264,6 +264,57 @@ def test_a_load_straight_after_the_no_wait_form_stays_behind_the_crop(pre3):
     filt.close()
 
 
+def _synth4(pre3):
+    x0, P0, _ = synth.make_map(4, None)
+    f = pre3.EkfFilter(synth.CAM, _types(4), dtype="f32", max_hyp=8)
+    f.set_x_p_k_k(x0, P0)
+    return f, *f._get(0)
+
+
+@pytest.mark.parametrize("feed", ["host", "frame"])
+def test_a_larger_box_straight_after_the_no_wait_form_replaces_the_work_block_in_stream_order(pre3, feed):
+    """The context's work block is grown, and zeroed, on the context's stream.  On a 64 x 48 image: the no-wait form with the smallest box (rows 1..41,
+    columns 1..3: 123 points, 8 draws), at once the waiting form with the whole image, which replaces the block while the first call may still be
+    queued.  State, covariance, applied and the result block are bit-equal to a fresh context given the same two calls with a sync() between them.
+    The scene is fitted with sta = 1 in both boxes from either feed (tests/plane_fit_ref.py on the raw and on the conditioned planes)."""
+    small, full = (1, 41, 1, 3), (1, 64, 1, 48)
+    x, y, z, _ = pr.scene(1, 0.0)
+    fr = sr.make_frame(64, 48, seed=1)
+    fr["x"], fr["y"], fr["z"] = (np.asfortranarray(a[70:134, 64:112]) for a in (x, y, z))
+    d_small, d_full = pr.scene_draws(2, npts_of(small), 8), pr.scene_draws(3, npts_of(full), 8)
+    with srm.SrFrame(64, 48) as f:
+        f.load(fr, 1)
+        if feed == "host":
+            def fit(box, draws):
+                return plane.plane_fit(fr["x"], fr["y"], fr["z"], draws, box=box)
+
+            def heading(filt, box, draws, wait):
+                return filt.heading_from_scan(fr["x"], fr["y"], fr["z"], draws, box=box, wait=wait)
+        else:
+            def fit(box, draws):
+                return plane.plane_fit_frame(f, draws, box=box)
+
+            def heading(filt, box, draws, wait):
+                return filt.heading_from_frame(f, draws, box=box, wait=wait)
+        first, second = fit(small, d_small), fit(full, d_full)
+        assert first["sta"] == 1 and second["sta"] == 1
+        got = []
+        for between in (False, True):
+            filt, x0, P0 = _synth4(pre3)                                            # a fresh context: no work block yet
+            _aimed(filt, x0, P0, second["R"])
+            assert heading(filt, small, d_small, False) is None
+            if between:
+                filt.sync()
+            a, r = heading(filt, full, d_full, True)
+            got.append((a, r, *filt._get(0)))
+            filt.close()
+    (a, r, xg, Pg), (a_ref, r_ref, x_ref, P_ref) = got
+    assert a and a_ref and r["sta"] == 1
+    same_fit(r, r_ref)
+    same_fit(r, {k: second[k] for k in r})
+    assert xg.tobytes() == x_ref.tobytes() and Pg.tobytes() == P_ref.tobytes()
+
+
 def test_errors_of_the_context_form(pre3):
     filt, x0, P0 = _synth8(pre3)
     good = pr.scene_draws(0, 65 * 71, 8)
