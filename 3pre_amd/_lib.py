@@ -55,6 +55,7 @@ lib.pre3_plane_fit_frame_seeded.argtypes = [_P, _P, _D, _I, _U, _U, _P, _P, _P, 
 lib.pre3_heading_from_frame.argtypes = [_P, _P, _P, _D, _I, _P, _I, _I, _P, _P]
 lib.pre3_heading_from_frame_seeded.argtypes = [_P, _P, _P, _D, _I, _U, _U, _I, _I, _P, _P, _P]
 lib.pre3_set_scan_frame.argtypes = [_P, _P, _I]
+lib.pre3_predict_pair_seeded.argtypes = [_P, _P, _P, _D, _U, _U, _P, _P]
 
 F64, F32 = 0, 1
 INVDEPTH, CARTESIAN = 0, 1
@@ -120,4 +121,5 @@ EXPORTS = [
     "pre3_sr_gauss3", "pre3_sr_frame_create", "pre3_sr_frame_destroy", "pre3_sr_frame_load", "pre3_sr_frame_get", "pre3_sr_frame_keypoints",
     "pre3_vo_pair_seeded", "pre3_map_policy_frames_seeded",
     "pre3_plane_fit_frame", "pre3_plane_fit_frame_seeded", "pre3_heading_from_frame", "pre3_heading_from_frame_seeded", "pre3_set_scan_frame",
+    "pre3_predict_pair_seeded",
 ]

@@ -11,6 +11,7 @@
 #include "pre3_internal.h"
 #include "pre3_test_hooks.h"
 #include "pre3_geomdev.h"
+#include "pre3_predictu.h"
 #include <mutex>
 #include "pre3_cholp.h"
 
@@ -145,10 +146,24 @@ int wait_mail(pre3_ctx *c, int slot, int32_t seq)
     return PRE3_OK;
 }
 
+const char *numeric_word_message(int32_t word)
+{
+    switch (pu_word_refusal(word)) {
+    case PU_REFUSED_NEAR: return "pre3_predict_pair_seeded: the pair was refused -- no matched point is farther than 0.4 m from the camera; the prediction was made with the identity increment";
+    case PU_REFUSED_BAD: return "pre3_predict_pair_seeded: the pair was refused -- a match names a keypoint that does not exist, or a kept keypoint rounds to a pixel outside the range image; the prediction was made with the identity increment";
+    default: return "innovation covariance S is not positive definite";
+    }
+}
 int stats_words(pre3_ctx *c)
 {
     PRE3_CHECK(c->pinned_stats[7] == 0, PRE3_E_HIP, "a device-side wait on another workgroup gave up (counter never arrived): results are invalid");
-    PRE3_CHECK(c->pinned_stats[6] == 0, PRE3_E_NUMERIC, "innovation covariance S is not positive definite");
+    const int32_t w = c->pinned_stats[6];
+    if (pu_word_refusal(w) != PU_OK) {
+        // a refused pair belongs to one call, not to the state (x and P hold a valid prediction): reported once, the word cleared with the report
+        (void)hipMemsetAsync(c->stats + 6, 0, sizeof(int32_t), c->stream);
+        if (c->mail_host) c->mail_host[6] = 0;
+    }
+    PRE3_CHECK(w == 0, PRE3_E_NUMERIC, "%s", numeric_word_message(w));
     return PRE3_OK;
 }
 int fetch_stats(pre3_ctx *c)

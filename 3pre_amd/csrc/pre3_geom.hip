@@ -15,6 +15,9 @@
 #include "pre3_internal.h"
 #include "pre3_geomdev.h"
 #include "pre3_chain.h"
+#include "pre3_vodev.h"
+#include "pre3_vopair.h"
+#include "pre3_predictu.h"
 
 namespace pre3 {
 
@@ -48,8 +51,19 @@ __device__ inline void d_process_noise(double *Pn)
 // k_predict_x and k_predict_P in ONE launch (a kernel boundary costs ~5 us on this platform, more than either kernel):
 // lane 0 of every block recomputes the quaternion product and its normalisation Jacobian (a few dozen flops) instead of
 // reading them from a previous kernel; block 0 additionally owns x_out[0:13], the process noise and the 7x7 pose block.
-template <typename T>
-__global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in, double *x_out, T *__restrict__ P, int n, int ld, U7 u,
+// The increment u: by value (U7: pre3_predict, pre3_step), or -- US = PredictUDev, pre3_predict_pair_seeded -- chosen by lane 0 of every block from the
+// result block and the header of the VO pair whose launches ran in front of this one (predict_u_select, pre3_predictu.h).  Those words were written by
+// earlier launches, so every block reads the same ones and takes the same branch; no workgroup waits on another.  Block 0 reports a refused pair in the
+// context's numeric error word (left alone when it already holds an error).  Everything behind the load of u is one text for both forms.
+__device__ __forceinline__ const U7 &predict_u(const U7 &u, U7 &) { return u; }
+__device__ __forceinline__ const U7 &predict_u(const PredictUDev &s, U7 &ud)
+{
+    const int refusal = predict_u_select(s.out->sta, s.hdr->pnum, s.hdr->bad, s.out->dist_ok, s.out->u, ud.v);
+    if (refusal != PU_OK && blockIdx.x == 0) atomicCAS(s.err, 0, pu_error_word(refusal));
+    return ud;
+}
+template <typename T, typename US = U7>
+__global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in, double *x_out, T *__restrict__ P, int n, int ld, US u,
                                                  double *__restrict__ params, int n_pred_blocks, ProjRide pr, InboxRide ib, int fuse_jn, PendW pw = PendW{})
 {
     if ((int)blockIdx.x >= n_pred_blocks + pr.n_blocks) { inbox_pull_block(ib); return; }               // the step's inbox crosses PCIe beside the prediction
@@ -68,10 +82,12 @@ __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in
     if (threadIdx.x == 0) {
         const double *q = x_in + 3;
         const double a = q[0], b = q[1], c = q[2], d = q[3];
-        const double w = u.v[3], x = u.v[4], y = u.v[5], z = u.v[6];
+        U7 ud;                                                     // (the device form's choice; the by-value form never touches it)
+        const U7 &uu = predict_u(u, ud);
+        const double w = uu.v[3], x = uu.v[4], y = uu.v[5], z = uu.v[6];
         // the predicted pose (predict_pose, pre3_geomdev.h: the projection riders of this launch compute the same thing for themselves)
         double xo[7], pose[7];
-        predict_pose(x_in, u, xo, pose);
+        predict_pose(x_in, uu, xo, pose);
         double R[9];
         if (blockIdx.x == 0) {
             d_q2R_sola(q, R);
@@ -1085,8 +1101,21 @@ ProjRide make_proj_ride(pre3_ctx *c, int which, int clear_first, int slot, int n
 }
 
 // with_projection: the IC-search projection at x_k_km1 (clear_first = 1) rides in the same launch
-int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection, size_t inbox_n16, int32_t inbox_seq)
+// u_dev != nullptr: the increment is chosen on the device from a VO pair's result block (PredictUDev); u is not read.  That form carries neither riders
+// nor an inbox pull -- ProjRide::u is by value, and pre3_predict_pair_seeded asks for neither.
+int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection, size_t inbox_n16, int32_t inbox_seq, const PredictUDev *u_dev)
 {
+    if (u_dev != nullptr) {
+        PRE3_CHECK(!with_projection && inbox_n16 == 0, PRE3_E_STATE, "launch_predict_impl: the device form of u carries no riders");
+        const int blocks = ceil_div(c->n, 256);
+        const int fuse_jn = c->carry.jn_pending ? 1 : 0;
+        DISPATCH_T(c,
+            hipLaunchKernelGGL((k_predict<double, PredictUDev>), dim3(blocks), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (double *)c->P, c->n, c->ld, *u_dev, c->pred_params, blocks, ProjRide{}, InboxRide{}, fuse_jn, PendW{}),
+            hipLaunchKernelGGL((k_predict<float, PredictUDev>), dim3(blocks), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (float *)c->P, c->n, c->ld, *u_dev, c->pred_params, blocks, ProjRide{}, InboxRide{}, fuse_jn, pend_args(c)));
+        PRE3_HIP(hipGetLastError());
+        c->carry.jn_pending = false;
+        return PRE3_OK;
+    }
     U7 uu; for (int i = 0; i < 7; ++i) uu.v[i] = u[i];
     int blocks = ceil_div(c->n, 256);
     ProjRide pr{};

@@ -7,6 +7,10 @@ namespace pre3 {
 
 struct CamD { double f, Cx, Cy, k1, k2, nRows, nCols; };
 struct U7 { double v[7]; };
+// k_predict's increment where it stays on the device (pre3_predict_pair_seeded): the result block and the header a VO pair's
+// launches left in front of the prediction (pre3_vodev.h, pre3_vopair.h), and the context's numeric error word for a pair that is refused
+struct VoOut; struct VoPairHeader;
+struct PredictUDev { const VoOut *out; const VoPairHeader *hdr; int32_t *err; };
 
 // ------------------------------------------------------------------------------------------------
 // device math (fp64)
@@ -227,7 +231,7 @@ __device__ __forceinline__ void predict_pose(const double *__restrict__ x_in, co
 struct ProjRide {
     int n_blocks;                       // 0: no rider in this launch
     int own_pose;                       // 1: the riders compute the predicted pose themselves from (x_prev, u) -- no producer to wait for
-    const double *x_prev; U7 u;
+    const double *x_prev; U7 u;        // by value only: the one prediction whose increment stays on the device (PredictUDev) launches no riders
     int N, clear_first;
     const int32_t *lm_type, *lm_off; const double *x; const double *x_lm /* landmark entries (null: x) */; CamD cam;
     double *h; int32_t *has_h; double *Hc, *Hl;

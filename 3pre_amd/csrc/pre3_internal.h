@@ -285,6 +285,7 @@ void drop_carried(pre3_ctx *c);          /* the deferred work of a state that is
 int dmalloc_bytes(void **p, size_t bytes);
 int wait_mail(pre3_ctx *c, int slot, int32_t seq);      /* poll the pinned mailbox until the kernel launched with `seq` has published in word `slot` */
 int stats_words(pre3_ctx *c);            /* the device's error words, once a copy of them into pinned_stats has completed */
+const char *numeric_word_message(int32_t word);      /* what a non-zero numeric error word (stats[6]) says: the factorisation's, or a refused VO pair's (pre3_predictu.h) */
 int fetch_stats(pre3_ctx *c);
 // Fill the pinned inbox and ship it: [meas | ic | (hyp) | z].  pull == false: the caller's next launch carries the pull of *nbytes_out bytes (pre3_step: k_predict)
 int install_measurements(pre3_ctx *c, int m, const int32_t *meas_idx, const double *z /* 2m, null: z already on device */, const int32_t *hyp, int n_hyp_ints,
@@ -359,7 +360,9 @@ struct IcMatchRide;
 int launch_project_innovation(pre3_ctx *c, int which, int clear_first, int mode, double chi2, bool collect = true, bool clear_ic = false, const IcMatchRide *ride = nullptr);
 int launch_update_x(pre3_ctx *c, int which_prior, int r);
 int launch_jnorm(pre3_ctx *c, int which);
-int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection = false, size_t inbox_n16 = 0, int32_t inbox_seq = 0);
+struct PredictUDev;
+int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection = false, size_t inbox_n16 = 0, int32_t inbox_seq = 0,
+                        const PredictUDev *u_dev = nullptr /* the increment from a VO pair's device result block (pre3_geomdev.h); u unused */);
 // (either direction: 16-byte words between device memory and a mapped pinned block, then `seq` into mailbox word `slot`)
 int launch_inbox_pull(pre3_ctx *c, const void *src_host_mapped, void *dst_dev, size_t n16, int32_t seq, int slot = 10, int32_t *clear = nullptr, int n_clear = 0);
 int launch_slice_prepare(pre3_ctx *c, const void *src_host_mapped, size_t n16, int32_t seq, int n_zero, int k, int lo, int hi, int tag);

@@ -362,7 +362,7 @@ int pre3::update_hi_impl(pre3_ctx *c)
             (void)hipMemsetAsync(c->stats + 6, 0, sizeof(int32_t) * 2, c->stream);
         }
         PRE3_CHECK(e_wait == 0, PRE3_E_HIP, "a device-side wait on another workgroup gave up (counter never arrived): results are invalid");
-        PRE3_CHECK(e_npd == 0, PRE3_E_NUMERIC, "innovation covariance S is not positive definite");
+        PRE3_CHECK(e_npd == 0, PRE3_E_NUMERIC, "%s", numeric_word_message(e_npd));
     }
     if (tail_done) {
         // The persistent launch of the LI update has run the rescue stage and (up to 32 landmarks) the HI update as well (pre3_cholp.hip, CpTail):

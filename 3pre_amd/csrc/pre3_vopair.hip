@@ -13,12 +13,15 @@
 //   k_vp_dist, k_vp_draw, k_vp_score, k_vp_final    the bodies of k_vo_dist, k_draw_vo, k_vo_score, k_vo_final with pnum / rst from the header
 // Every output slot has one writer (the capped count is an integer sum): results are bit-equal from run to run, and bit-equal to
 // pre3_vo_ransac_frames_seeded fed the same match list with n_hyp = rst.
+// pre3_predict_pair_seeded queues the same eight launches through the same host path (vp_queue) and puts the prediction behind
+// them on the context's stream: k_predict reads u from the VoOut block k_vp_final wrote, so the increment never reaches the host.
 #include <cmath>
 
 #include "pre3_internal.h"
 #include "pre3_geomdev.h"
 #include "pre3_vodev.h"
 #include "pre3_vopair.h"
+#include "pre3_predictu.h"
 
 namespace pre3 {
 
@@ -141,38 +144,33 @@ int launch_vp_match(int n1, int n2, const double *des1, const double *des2, doub
 
 using namespace pre3;
 
-extern "C" {
+// ---- one host path for the pair (pre3_vo_pair_seeded, pre3_predict_pair_seeded): the views, the layout of cur's work block, the launches, and the checks
+// of what comes back.  [header | VoOut | match | pset1 | pset2 | draws | cnum | state | inliers] come back in one transfer; the partials and masks stay
+namespace {
+struct VpPair {
+    SrFrameView v1, v2; SrKeypointView k1, k2;
+    size_t o_out, o_match, o_p1, o_p2, o_draws, o_cnum, o_state, o_inl, o_end;
+    char *d = nullptr, *pin = nullptr;              // cur's device work block and its pinned image
+};
+bool vp_empty(const VpPair &p) { return p.k1.n_kept == 0 || p.k2.n_kept == 0; }
 
-int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out, double *match_out,
-                        double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out, int32_t *state_out,
-                        int32_t *inlier_out, pre3_vo_result *res)
+// offsets, work blocks, prev lent to cur's stream, the memset of header and result block, the eight launches -- everything on cur's stream, no wait
+int vp_queue(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, VpPair *q)
 {
-    const char *who = "pre3_vo_pair_seeded";
-    SrFrameView v1, v2;
-    SrKeypointView k1, k2;
-    PRE3_TRY(sr_frame_pair_views(who, prev, cur, thresh, &v1, &v2, &k1, &k2));
-    PRE3_TRY(select_device(who, v2.device));
+    const SrFrameView &v1 = q->v1, &v2 = q->v2;
+    const SrKeypointView &k1 = q->k1, &k2 = q->k2;
     const int n1 = k1.n_kept, n2 = k2.n_kept;
-    if (pnum_out) *pnum_out = 0;
-    if (n1 == 0 || n2 == 0) { vo_no_solution(res); return PRE3_OK; }      // siftmatch of an empty set: no match, nothing to queue
-
-    // [header | VoOut | match | pset1 | pset2 | draws | cnum | state | inliers] come back in one transfer; the partials and the masks stay
     const int wcap = ceil_div(n1, 64);
     const size_t o_out = sizeof(VoPairHeader), o_match = up16(o_out + sizeof(VoOut)), o_p1 = o_match + up16(sizeof(double) * 2 * (size_t)n1);
     const size_t o_p2 = o_p1 + up16(sizeof(double) * 3 * (size_t)n1), o_draws = o_p2 + up16(sizeof(double) * 3 * (size_t)n1);
     const size_t o_cnum = o_draws + up16(sizeof(int32_t) * 4 * VO_RST_CAP), o_state = o_cnum + up16(sizeof(int32_t) * VO_RST_CAP);
     const size_t o_inl = o_state + up16(sizeof(int32_t) * VO_RST_CAP), o_end = o_inl + up16(sizeof(int32_t) * (size_t)n1);
     const size_t o_part = o_end, o_masks = o_part + vp_match_part_bytes(n1, n2), total = o_masks + sizeof(unsigned long long) * (size_t)VO_RST_CAP * wcap;
-    size_t need = o_match;                      // the prefix of the block the caller's outputs reach into
-    if (match_out) need = o_p1;
-    if (pset1_out) need = o_p2;
-    if (pset2_out) need = o_draws;
-    if (draws_out) need = o_cnum;
-    if (cnum_out) need = o_state;
-    if (state_out) need = o_inl;
-    if (inlier_out) need = o_end;
-    char *d = nullptr, *pin = nullptr;
-    PRE3_TRY(sr_frame_pair_work(cur, total, o_end, (void **)&d, (void **)&pin));
+    q->o_out = o_out; q->o_match = o_match; q->o_p1 = o_p1; q->o_p2 = o_p2; q->o_draws = o_draws; q->o_cnum = o_cnum; q->o_state = o_state;
+    q->o_inl = o_inl; q->o_end = o_end;
+    char *d = nullptr;
+    PRE3_TRY(sr_frame_pair_work(cur, total, o_end, (void **)&d, (void **)&q->pin));
+    q->d = d;
     hipStream_t st = v2.stream;
     PRE3_TRY(sr_frame_lend(prev, st));
     PRE3_HIP(hipMemsetAsync(d, 0, o_match, st));                          // the header (*capped starts at zero) and the result block
@@ -192,28 +190,120 @@ int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, 
     hipLaunchKernelGGL(k_vp_final, dim3(1), dim3(64), 0, st, (const VoPairHeader *)hdr, (const double *)p1, (const double *)p2, (const int32_t *)cnum,
                        (const unsigned long long *)masks, out, inl);
     PRE3_HIP(hipGetLastError());
-    PRE3_HIP(hipMemcpyAsync(pin, d, need, hipMemcpyDeviceToHost, st));
+    return PRE3_OK;
+}
+
+// what the transfer brought: the header (checked against the sizing rule) and the result block; then the two pairs that are refused (pnum >= 4)
+int vp_header(const VpPair &p, VoPairHeader *h, VoOut *o)
+{
+    *h = *(const VoPairHeader *)p.pin;
+    *o = *(const VoOut *)(p.pin + p.o_out);
+    PRE3_CHECK(h->pnum >= 0 && h->pnum <= p.k1.n_kept && h->rst == vo_rst(h->pnum), PRE3_E_HIP, "pre3_vo_pair_seeded: the device reports %d matches of %d keypoints and %d hypotheses",
+               h->pnum, p.k1.n_kept, h->rst);
+    return PRE3_OK;
+}
+int vp_refuse_bad(const VoPairHeader &h)
+{
+    PRE3_CHECK(h.bad == 0, PRE3_E_HIP, "pre3_vo_pair_seeded: %s", (h.bad & 1) ? "a match refers to a keypoint that does not exist" : "a kept keypoint rounds to a pixel outside the range image");
+    return PRE3_OK;
+}
+int vp_refuse_near(const VoOut &o)
+{
+    PRE3_CHECK(o.dist_ok, PRE3_E_NUMERIC, "vo: no matched point is farther than 0.4 m from the camera (ransac_dr_ye.m:21 has no minimum there)");
+    return PRE3_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out, double *match_out,
+                        double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out, int32_t *state_out,
+                        int32_t *inlier_out, pre3_vo_result *res)
+{
+    const char *who = "pre3_vo_pair_seeded";
+    VpPair p;
+    PRE3_TRY(sr_frame_pair_views(who, prev, cur, thresh, &p.v1, &p.v2, &p.k1, &p.k2));
+    PRE3_TRY(select_device(who, p.v2.device));
+    if (pnum_out) *pnum_out = 0;
+    if (vp_empty(p)) { vo_no_solution(res); return PRE3_OK; }      // siftmatch of an empty set: no match, nothing to queue
+    PRE3_TRY(vp_queue(prev, cur, thresh, seed, seq, &p));
+    size_t need = p.o_match;                    // the prefix of the block the caller's outputs reach into
+    if (match_out) need = p.o_p1;
+    if (pset1_out) need = p.o_p2;
+    if (pset2_out) need = p.o_draws;
+    if (draws_out) need = p.o_cnum;
+    if (cnum_out) need = p.o_state;
+    if (state_out) need = p.o_inl;
+    if (inlier_out) need = p.o_end;
+    const hipStream_t st = p.v2.stream;
+    char *pin = p.pin;
+    PRE3_HIP(hipMemcpyAsync(pin, p.d, need, hipMemcpyDeviceToHost, st));
     PRE3_TRY(sr_frame_reclaim(prev, st));                                 // a later load into prev stays behind these reads
     PRE3_HIP(hipStreamSynchronize(st));
 
-    const VoPairHeader h = *(const VoPairHeader *)pin;
-    const VoOut o = *(const VoOut *)(pin + o_out);
-    PRE3_CHECK(h.pnum >= 0 && h.pnum <= n1 && h.rst == vo_rst(h.pnum), PRE3_E_HIP, "pre3_vo_pair_seeded: the device reports %d matches of %d keypoints and %d hypotheses",
-               h.pnum, n1, h.rst);
+    VoPairHeader h; VoOut o;
+    PRE3_TRY(vp_header(p, &h, &o));
     const int pnum = h.pnum, rst = h.rst;
     if (pnum_out) *pnum_out = pnum;
-    if (match_out) memcpy(match_out, pin + o_match, sizeof(double) * 2 * (size_t)pnum);
+    if (match_out) memcpy(match_out, pin + p.o_match, sizeof(double) * 2 * (size_t)pnum);
     if (pnum < 4) { vo_no_solution(res); return PRE3_OK; }
-    PRE3_CHECK(h.bad == 0, PRE3_E_HIP, "pre3_vo_pair_seeded: %s", (h.bad & 1) ? "a match refers to a keypoint that does not exist" : "a kept keypoint rounds to a pixel outside the range image");
-    if (pset1_out) memcpy(pset1_out, pin + o_p1, sizeof(double) * 3 * (size_t)pnum);
-    if (pset2_out) memcpy(pset2_out, pin + o_p2, sizeof(double) * 3 * (size_t)pnum);
-    if (draws_out) memcpy(draws_out, pin + o_draws, sizeof(int32_t) * 4 * (size_t)rst);
+    PRE3_TRY(vp_refuse_bad(h));
+    if (pset1_out) memcpy(pset1_out, pin + p.o_p1, sizeof(double) * 3 * (size_t)pnum);
+    if (pset2_out) memcpy(pset2_out, pin + p.o_p2, sizeof(double) * 3 * (size_t)pnum);
+    if (draws_out) memcpy(draws_out, pin + p.o_draws, sizeof(int32_t) * 4 * (size_t)rst);
     if (capped_out) *capped_out = h.capped;
-    PRE3_CHECK(o.dist_ok, PRE3_E_NUMERIC, "vo: no matched point is farther than 0.4 m from the camera (ransac_dr_ye.m:21 has no minimum there)");
-    if (cnum_out) memcpy(cnum_out, pin + o_cnum, sizeof(int32_t) * (size_t)rst);
-    if (state_out) memcpy(state_out, pin + o_state, sizeof(int32_t) * (size_t)rst);
-    if (inlier_out) memcpy(inlier_out, pin + o_inl, sizeof(int32_t) * (size_t)pnum);
+    PRE3_TRY(vp_refuse_near(o));
+    if (cnum_out) memcpy(cnum_out, pin + p.o_cnum, sizeof(int32_t) * (size_t)rst);
+    if (state_out) memcpy(state_out, pin + p.o_state, sizeof(int32_t) * (size_t)rst);
+    if (inlier_out) memcpy(inlier_out, pin + p.o_inl, sizeof(int32_t) * (size_t)pnum);
     if (res) vo_result(o, res);
+    return PRE3_OK;
+}
+
+// fv.m:47 + Calculate_V_Omega_RANSAC_dr_ye.m:41-50 + predict_state_and_covariance.m:27-143: the pair's launches on cur's stream,
+// then k_predict on the context's stream with the increment chosen on the device from the pair's result block; u never reaches the host
+int pre3_predict_pair_seeded(pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out,
+                             pre3_vo_result *res_out)
+{
+    const char *who = "pre3_predict_pair_seeded";
+    static const double u_identity[7] = { 0, 0, 0, 1, 0, 0, 0 };
+    VpPair p;
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "%s: null context", who);
+    PRE3_TRY(sr_frame_pair_views(who, prev, cur, thresh, &p.v1, &p.v2, &p.k1, &p.k2));
+    PRE3_CHECK(p.v2.device == c->device, PRE3_E_ARG, "%s: the frames are on device %d, the context on device %d", who, p.v2.device, c->device);
+    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "%s: needs (x_k_k, p_k_k) on the device", who);
+    EntryScope scope(c); PRE3_TRY(scope.rc);            // as pre3_predict's
+    const bool wait = pnum_out != nullptr || res_out != nullptr;
+    if (pnum_out) *pnum_out = 0;
+    if (vp_empty(p)) {                                  // no pair launches: the ordinary prediction with the identity increment
+        PRE3_TRY(launch_predict_impl(c, u_identity));
+        c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
+        vo_no_solution(res_out);
+        return PRE3_OK;
+    }
+    PRE3_TRY(vp_queue(prev, cur, thresh, seed, seq, &p));
+    const hipStream_t st = p.v2.stream;
+    PRE3_TRY(sr_frame_reclaim(prev, st));               // prev is read by the pair's launches only
+    PRE3_TRY(sr_frame_lend(cur, c->stream));            // the prediction reads cur's work block behind k_vp_final
+    const PredictUDev ud{ (const VoOut *)(p.d + p.o_out), (const VoPairHeader *)p.d, c->stats + 6 };
+    PRE3_TRY(launch_predict_impl(c, nullptr, false, 0, 0, &ud));
+    c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
+    // the next pair call's memset of this work block, a load or a keypoint call on cur stay behind the read of u
+    if (wait) PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
+    PRE3_TRY(sr_frame_reclaim(cur, c->stream));
+    if (!wait) return PRE3_OK;
+
+    // one wait, on cur's stream, which now stands behind the prediction as well: header and result block in one transfer
+    PRE3_HIP(hipMemcpyAsync(p.pin, p.d, p.o_match, hipMemcpyDeviceToHost, st));
+    PRE3_TRY(stream_drain_on(st, c->comm, who));
+    if (pu_word_refusal(c->pinned_stats[6]) != PU_OK) (void)hipMemsetAsync(c->stats + 6, 0, sizeof(int32_t), c->stream);      // reported by this call's return code
+    VoPairHeader h; VoOut o;
+    PRE3_TRY(vp_header(p, &h, &o));
+    if (pnum_out) *pnum_out = h.pnum;
+    if (h.pnum < 4) { vo_no_solution(res_out); return PRE3_OK; }
+    PRE3_TRY(vp_refuse_bad(h));
+    PRE3_TRY(vp_refuse_near(o));
+    if (res_out) vo_result(o, res_out);
     return PRE3_OK;
 }
 

@@ -468,6 +468,28 @@ class EkfFilter:
         assert u.shape == (7,), "u = [dX(3); dq(4)]"
         check(lib.pre3_predict(self._ctx, dptr(u)))
 
+    def ekf_prediction_pair_seeded(self, prev, cur, seed, seq=0, thresh=1.5, wait=True):
+        """fv.m:47 + predict_state_and_covariance.m in one call: vo.vo_pair_seeded between the keypoint records of the resident
+        frames prev and cur (sr4000.SrFrame after keypoints()), then ekf_prediction with that pair's u = [T; R2q(R)] -- the identity motion unless
+        sta == 1 -- read on the device: u never crosses PCIe.  Bit-identical to vo.vo_pair_seeded(prev, cur, seed, seq, thresh) followed by
+        ekf_prediction(res["u"]).  wait=True: one host wait; returns dict(pnum, rst, sta, u, rot, trans, euler, n_support, n_iterations, best,
+        error_mean, error_std, dist) as vo.vo_pair_seeded reports them.  wait=False: returns None at once, nothing is synchronised; a pair that
+        vo_pair_seeded would refuse (no matched point beyond 0.4 m) is predicted with the identity motion and the next call that reads the device's
+        error words raises Pre3Error with code -5 once."""
+        from . import vo
+        args = (self._ctx, prev._h, cur._h, float(thresh), int(seed), int(seq))
+        if not wait:
+            check(lib.pre3_predict_pair_seeded(*args, None, None))
+            return None
+        pnum, res = C.c_int32(0), vo.VoResult()
+        check(lib.pre3_predict_pair_seeded(*args, C.byref(pnum), C.byref(res)))
+        pnum = int(pnum.value)
+        out = vo._result(res, None, None, None)
+        for k in ("cnum", "state", "inliers"):             # the per-hypothesis tables stay on the device
+            del out[k]
+        out["pnum"], out["rst"] = pnum, (vo.vo_rst(pnum) if pnum >= 4 else 0)
+        return out
+
     def predict_camera_measurements(self, which=_lib.X_K_KM1, clear_first=True):
         """Also computes the Jacobians (calculate_derivatives.m) -- the reference always calls them as a pair."""
         check(lib.pre3_project(self._ctx, int(which), int(bool(clear_first))))

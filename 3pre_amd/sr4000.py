@@ -10,6 +10,7 @@ readers and keypoint filters over the C ABI.
     Calculate_V_Omega_RANSAC_dr_ye.m:25-50                   -> calculate_v_omega      (T, q, R, sta)
     initialize_features.m:95-99 + map_management.m:27-79     -> initialize_features_frames (two resident frames, gate 0 on each, then the policy)
     plane_fit_to_data.m:7-149                                -> plane_fit_to_data      (the fit on a resident frame, plane.plane_fit_frame_seeded)
+    fv.m:41-48 + ekf_prediction.m                            -> fv_pair, ekf_prediction_frames (the VO pair and the prediction, u on the device)
 
 All compute runs in libpre3.so on the GPU; this module reads the text file and marshals numpy arrays.
 """
@@ -212,6 +213,25 @@ def calculate_v_omega(dat1, dat2, sift1, sift2, seed, seq=0, **kw):
     out = vodometry_dr_ye(dat1, dat2, sift1, sift2, seed, seq, **kw)
     ok = out["sta"] == 1
     return out["u"][:3].copy(), out["u"][3:].copy(), (out["rot"].copy() if ok else np.eye(3)), out["sta"]
+
+
+def fv_pair(step):
+    """fv.m:41-48's index rule: None for the frames whose prediction takes the identity motion (step - 1 <= 1), else the scans (step - 2, step - 1)
+    whose VO increment Calculate_V_Omega_RANSAC_dr_ye(step - 2, step - 1) supplies"""
+    step = int(step)
+    return None if step - 1 <= 1 else (step - 2, step - 1)
+
+
+def ekf_prediction_frames(filt, step, frames, seed, seq=0, thresh=1.5, wait=True):
+    """fv.m:41-48 + ekf_prediction.m for frame `step` with the scans resident: frames maps a scan number to its SrFrame, each with a keypoint record
+    (gate 1, as vodometry_dr_ye).  The first frames are predicted with the identity motion; from then on EkfFilter.ekf_prediction_pair_seeded runs the VO
+    front end between frames[step - 2] and frames[step - 1] and the prediction behind it, u staying on the device.  Returns that
+    call's result (None for the identity frames, or with wait=False)."""
+    pair = fv_pair(step)
+    if pair is None:
+        filt.ekf_prediction([0, 0, 0, 1, 0, 0, 0])
+        return None
+    return filt.ekf_prediction_pair_seeded(frames[pair[0]], frames[pair[1]], seed, seq, thresh, wait)
 
 
 def initialize_features_frames(filt, step, dat_prev, dat_cur, sift_prev, sift_cur, seed, seq=0, thresh=1.5, mode=MODE_XYZ, device=0, frames=None, **policy):

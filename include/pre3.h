@@ -649,6 +649,33 @@ PRE3_API int pre3_heading_from_frame_seeded(pre3_ctx *ctx, pre3_sr_frame *f, con
  * result for the frame it holds (none yet, or a pre3_sr_frame_load after it). */
 PRE3_API int pre3_set_scan_frame(pre3_ctx *ctx, pre3_sr_frame *f, int which);
 
+/* ---- the prediction fed from a resident VO pair: u never leaves the device -----------------------------------------------------
+ * fv.m:47 + Calculate_V_Omega_RANSAC_dr_ye.m:41-50 + predict_state_and_covariance.m:27-143 in one call: the VO front end between the keypoint records of
+ * prev and cur -- exactly pre3_vo_pair_seeded's launches, draw rule and (seed, seq), on cur's stream with prev lent to it --, then the prediction
+ * (x_k_k, p_k_k) -> (x_k_km1, p_k_km1) on the context's stream with the increment read from the pair's device result block: cur is lent to the context's
+ * stream for that launch and reclaimed behind it, so the next pair call's clearing of the same work block, a pre3_sr_frame_load or a
+ * pre3_sr_frame_keypoints on either handle stays behind the read of u.  The increment rule is evaluated on the device: u = [T; R2q(R)] of the pair when
+ * its solution state is 1, else [0 0 0 1 0 0 0] -- fewer than four matches (nothing behind the match stage has written the result block, and it is not
+ * read), no consensus (sta = 4), sta = 2 / 0 / -1.
+ * With pnum_out == NULL and res_out == NULL the call queues everything and returns without synchronising any stream (pre3_heading_from_frame's no-wait
+ * form); with either output it ends in ONE host wait, and *pnum_out and *res_out are pre3_vo_pair_seeded's, bit for bit.
+ * Afterwards x_k_km1, P, the prediction's parameters, a pending HI down-date's rows (PRE3_OPT_PEND_HI) and a pending update.m:42-46 pass are bit-identical
+ * to pre3_vo_pair_seeded(prev, cur, thresh, seed, seq, ..., &res) followed by pre3_predict(ctx, res.u), and the context's flags change as pre3_predict
+ * changes them: pending work is carried, not flushed.  (For sta = 2 / 0 / -1 the chain's res.u holds R2q of the identity with negative zeros in
+ * u[4..6]; this call takes +0 there.  The values are equal; zero entries of the prediction's parameters may differ in sign.)
+ * The two pairs pre3_vo_pair_seeded refuses after its wait -- no matched point beyond 0.4 m (PRE3_E_NUMERIC), a match or a keypoint outside its range
+ * (PRE3_E_HIP) -- cannot be refused by a call that does not wait: the prediction is made with the identity increment, which is what the reference's own
+ * rule gives every pair that does not end in sta = 1, and x, P and every flag of the context are those of a prediction that has happened.  The no-wait
+ * form leaves a value of its own in the context's numeric error word: the next call that reads the error words (pre3_get_state, a step, a reader)
+ * returns PRE3_E_NUMERIC once, with a message that names the refused pair, and the word is cleared with that report.  The waiting form returns the code
+ * and the message pre3_vo_pair_seeded would, clears the word itself and leaves the context usable, holding that identity prediction.
+ * n1 == 0 or n2 == 0 is a result: no pair launches, the ordinary prediction with the identity increment, pnum = 0 and sta = 4.
+ * PRE3_E_ARG / PRE3_E_STATE before anything is queued, with the context and both handles unchanged: a null context, everything pre3_vo_pair_seeded
+ * refuses before it queues, a handle on another device than the context, a context whose covariance buffer does not hold (x_k_k, p_k_k).
+ * Calls that share a handle or the context must be serialised by the caller. */
+PRE3_API int pre3_predict_pair_seeded(pre3_ctx *ctx, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq,
+                                      int32_t *pnum_out, pre3_vo_result *res_out);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them

@@ -24,6 +24,7 @@
  *   plane_fit_to_data.m:7-149 on the resident frame                     [R, sta, B, n_inliers] = pre3_mex('plane_frame', seed, seq)                          % the box is gathered on the device
  *   mono_slam.m:189-193 on the resident frame                           applied = pre3_mex('heading_frame', seed, step)                                  % fit + ekf_heading_update, nothing read back
  *   matching_sift_based.m:104,129-135 on the resident frame             pre3_mex('set_scan_frame')                                                       % the scan 'sr_keypoints' was handed, copied on the device
+ *   fv.m:47 + ekf_prediction.m:29 on two resident frames                pre3_mex('predict_pair', seed, seq)                                              % 'vo_pair' + 'predict' in one call, u stays on the device
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
  * corrcoef_partitioned_mex.c:25-57).  NOT compiled in the build container (no MATLAB / mex.h there).
@@ -372,6 +373,20 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         check(pre3_heading_from_frame_seeded(g_ctx, g_sr, NULL, 0.02, nin > 3 ? (int)mxGetScalar(in[3]) : PRE3_PLANE_MAX_DRAWS, (uint64_t)mxGetScalar(in[1]),
                                              (uint64_t)mxGetScalar(in[2]), 1, nin > 4 ? (int)mxGetScalar(in[4]) : 1, NULL, &applied, NULL));
         out[0] = mxCreateDoubleScalar((double)applied);
+    }
+    else if (!strcmp(cmd, "predict_pair")) {      /* [T, q, sta, pnum] = pre3_mex('predict_pair', seed, seq [, thresh = 1.5]): fv.m:47 + ekf_prediction.m:29 -- 'vo_pair' between the
+                                                     frame 'sr_keep' put aside and the resident one, then 'predict' with that pair's u = [T; q] (the identity motion unless
+                                                     sta == 1) read on the device (pre3_predict_pair_seeded).  Without output arguments nothing is waited for: a pair 'vo_pair'
+                                                     would refuse is then predicted with the identity motion and reported by the next call that reads the device's error words */
+        pre3_vo_result r; int32_t pnum = 0;
+        if (nin < 3 || nin > 4) mexErrMsgTxt("pre3_mex('predict_pair', seed, seq [, thresh]): two or three arguments");
+        if (!g_sr || !g_sr_prev) mexErrMsgTxt("pre3_mex('predict_pair'): needs two frames -- 'sr_frame' + 'sr_keypoints', 'sr_keep', then 'sr_frame' + 'sr_keypoints' again");
+        check(pre3_predict_pair_seeded(g_ctx, g_sr_prev, g_sr, nin > 3 ? mxGetScalar(in[3]) : 1.5, (uint64_t)mxGetScalar(in[1]), (uint64_t)mxGetScalar(in[2]),
+                                       nout > 0 ? &pnum : NULL, nout > 0 ? &r : NULL));
+        if (nout > 0) { out[0] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[0]), r.u, sizeof(double) * 3); }
+        if (nout > 1) { out[1] = mxCreateDoubleMatrix(4, 1, mxREAL); memcpy(mxGetPr(out[1]), r.u + 3, sizeof(double) * 4); }
+        if (nout > 2) out[2] = mxCreateDoubleScalar(r.sta);
+        if (nout > 3) out[3] = mxCreateDoubleScalar(pnum);
     }
     else if (!strcmp(cmd, "map_delete")) {        /* pre3_mex('map_delete', idx (0-based, ascending))   delete_features.m:54-74 */
         int k = (int)mxGetNumberOfElements(in[1]), i, rc; int32_t *d = (int32_t *)mxMalloc(sizeof(int32_t) * (k ? k : 1));
