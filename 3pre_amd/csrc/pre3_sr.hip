@@ -17,31 +17,7 @@
 
 #include "pre3_internal.h"
 #include "pre3_sr.h"
-
-struct pre3_sr_frame {
-    int device = 0, rows = 0, cols = 0;
-    int loaded = 0, mode = 0, has_conf = 0;
-    hipStream_t stream = nullptr;
-    double *raw = nullptr;          // [5][npix]: z, x, y, amplitude, confidence -- as uploaded
-    double *filt = nullptr;         // [4][npix]: x, y, z, image
-    double *maxima = nullptr;       // imax, cmax
-    void *stage = nullptr;          // pinned: the five planes of a load, or the keypoints of a call
-    size_t stage_bytes = 0;
-    void *kp = nullptr;             // device: the keypoint stage's input and output block
-    size_t kp_bytes = 0;
-    int32_t *pinned_n = nullptr;    // n_kept
-    // the last keypoint call's result, still in `kp` (sr_frame_keypoint_view): kp_valid 0 = none yet, or stale after a load
-    int kp_valid = 0, kp_K = 0, kp_ldf = 0, kp_ND = 0, kp_gate = 0, kp_n = 0;
-    int kp_K_in = 0;                        // the raw set of that call, once its transfer is queued: [kp_K_in][ldf] frames at offset 0 of kp,
-    size_t kp_o_des_in = 0;                 // [kp_K_in][ND] descriptors here (sr_frame_keypoint_view: K_in, frm_in, des_in)
-    bool kp_raw_ok = true;                  // its descriptors passed the ranked IC route's bounds on their way through `stage`
-    size_t kp_o_frm = 0, kp_o_des = 0;      // offsets of frm_out / des_out inside kp
-    size_t kp_o_xyz = 0, kp_o_rho = 0, kp_o_idx = 0;      // ... of xyz_out / rho_out (written by gate 0 only) and keep_idx
-    // the pair stage's work block and its pinned image (pre3_vopair.hip), allocated on its first use
-    void *pair_dev = nullptr, *pair_pin = nullptr;
-    size_t pair_dev_bytes = 0, pair_pin_bytes = 0;
-    hipEvent_t pair_ev = nullptr;   // carries the hand-offs to and from a consumer's stream (sr_frame_lend, sr_frame_reclaim)
-};
+#include "pre3_srframe.h"
 
 namespace pre3 {
 
@@ -195,7 +171,9 @@ static int sr_dmalloc(pre3_sr_frame *f, void **p, size_t bytes)
     return PRE3_OK;
 }
 
-static int sr_grow_stage(pre3_sr_frame *f, size_t bytes)
+}  // namespace
+
+int sr_grow_stage(pre3_sr_frame *f, size_t bytes)
 {
     if (f->stage_bytes >= bytes) return PRE3_OK;
     if (f->stage) (void)hipHostFree(f->stage);
@@ -206,7 +184,25 @@ static int sr_grow_stage(pre3_sr_frame *f, size_t bytes)
     return PRE3_OK;
 }
 
-}  // namespace
+KpLayout kp_layout(int K, int ldf, int ND)
+{
+    KpLayout l;
+    l.b_frm = up16(sizeof(double) * (size_t)K * ldf); l.b_des = up16(sizeof(double) * (size_t)K * ND);
+    l.o_frm_out = l.b_frm + l.b_des; l.o_des_out = l.o_frm_out + l.b_frm; l.o_xyz = l.o_des_out + l.b_des;
+    l.o_rho = l.o_xyz + up16(sizeof(double) * 3 * (size_t)K); l.o_idx = l.o_rho + up16(sizeof(double) * (size_t)K);
+    l.o_n = l.o_idx + up16(sizeof(int32_t) * (size_t)K); l.total = l.o_n + 16;
+    return l;
+}
+
+int sr_frame_kp_reserve(pre3_sr_frame *f, size_t total)
+{
+    if (f->kp_bytes >= total) return PRE3_OK;
+    if (f->kp) (void)hipFree(f->kp);
+    f->kp = nullptr; f->kp_bytes = 0;
+    PRE3_TRY(sr_dmalloc(f, &f->kp, total + total / 4));
+    f->kp_bytes = total + total / 4;
+    return PRE3_OK;
+}
 
 int select_device(const char *who, int device)
 {
@@ -326,6 +322,7 @@ int pre3_sr_frame_destroy(pre3_sr_frame *f)
     if (f->pair_dev) (void)hipFree(f->pair_dev);
     if (f->pair_pin) (void)hipHostFree(f->pair_pin);
     if (f->pair_ev) (void)hipEventDestroy(f->pair_ev);
+    if (f->sift) sift_work_free(f->sift);
     delete f;
     return PRE3_OK;
 }
@@ -404,6 +401,39 @@ int pre3_sr_frame_get(pre3_sr_frame *f, double *x, double *y, double *z, double 
     return PRE3_OK;
 }
 
+// the gate launch over the raw set in the keypoint block (kp_K_in frames of kp_ldf entries at offset 0, descriptors of kp_ND at kp_o_des_in), the
+// count read back, then the outputs the caller asked for
+static int sr_gate_run(pre3_sr_frame *f, const char *who, int gate, int32_t *n_kept, int32_t *keep_idx, double *frm_out, double *des_out, double *xyz_out,
+                       double *rho_out)
+{
+    const int K = f->kp_K_in, ldf = f->kp_ldf, ND = f->kp_ND;
+    const KpLayout l = kp_layout(K, ldf, ND);
+    char *d = (char *)f->kp;
+    const size_t npix = (size_t)f->rows * f->cols;
+    KpArgs a;
+    a.K = K; a.ldf = ldf; a.ND = ND; a.gate = gate; a.rows = f->rows; a.cols = f->cols; a.has_conf = f->has_conf;
+    a.frm = (const double *)d; a.des = (const double *)(d + l.b_frm);
+    a.xf = f->filt; a.yf = f->filt + npix; a.zf = f->filt + 2 * npix; a.conf = f->raw + 4 * npix; a.maxima = f->maxima;
+    a.n_kept = (int32_t *)(d + l.o_n); a.keep_idx = (int32_t *)(d + l.o_idx);
+    a.frm_out = (double *)(d + l.o_frm_out); a.des_out = (double *)(d + l.o_des_out); a.xyz_out = (double *)(d + l.o_xyz); a.rho_out = (double *)(d + l.o_rho);
+    hipLaunchKernelGGL(k_sr_keypoints, dim3(ceil_div(K, KB)), dim3(KB), 0, f->stream, a);
+    PRE3_HIP(hipGetLastError());
+    PRE3_HIP(hipMemcpyAsync(f->pinned_n, a.n_kept, sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+    PRE3_HIP(hipStreamSynchronize(f->stream));
+    const int n = *f->pinned_n;
+    PRE3_CHECK(n >= 0 && n <= K, PRE3_E_HIP, "%s: the device kept %d of %d keypoints", who, n, K);
+    *n_kept = n;
+    f->kp_n = n; f->kp_o_frm = l.o_frm_out; f->kp_o_des = l.o_des_out; f->kp_o_xyz = l.o_xyz; f->kp_o_rho = l.o_rho; f->kp_o_idx = l.o_idx;
+    if (n == 0) return PRE3_OK;
+    if (keep_idx) PRE3_HIP(hipMemcpyAsync(keep_idx, a.keep_idx, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, f->stream));
+    if (frm_out) PRE3_HIP(hipMemcpyAsync(frm_out, a.frm_out, sizeof(double) * (size_t)n * ldf, hipMemcpyDeviceToHost, f->stream));
+    if (des_out && ND > 0) PRE3_HIP(hipMemcpyAsync(des_out, a.des_out, sizeof(double) * (size_t)n * ND, hipMemcpyDeviceToHost, f->stream));
+    if (xyz_out && gate == 0) PRE3_HIP(hipMemcpyAsync(xyz_out, a.xyz_out, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, f->stream));
+    if (rho_out && gate == 0) PRE3_HIP(hipMemcpyAsync(rho_out, a.rho_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, f->stream));
+    PRE3_HIP(hipStreamSynchronize(f->stream));
+    return PRE3_OK;
+}
+
 // touched: set once the call is past its checks -- from there on the keypoint block no longer holds the previous result
 static int sr_keypoints_impl(pre3_sr_frame *f, int gate, int ldf, int K, const double *frm, int ND, const double *des, int32_t *n_kept, int32_t *keep_idx,
                              double *frm_out, double *des_out, double *xyz_out, double *rho_out, bool *touched)
@@ -430,47 +460,17 @@ static int sr_keypoints_impl(pre3_sr_frame *f, int gate, int ldf, int K, const d
     f->kp_K_in = 0; f->kp_o_des_in = 0; f->kp_raw_ok = true;
     if (K == 0) return PRE3_OK;
     // [frm | des] up; [frm_out | des_out | xyz | rho | keep_idx | n_kept] behind them
-    const size_t b_frm = up16(sizeof(double) * (size_t)K * ldf), b_des = up16(sizeof(double) * (size_t)K * ND);
-    const size_t o_frm_out = b_frm + b_des, o_des_out = o_frm_out + b_frm, o_xyz = o_des_out + b_des, o_rho = o_xyz + up16(sizeof(double) * 3 * (size_t)K);
-    const size_t o_idx = o_rho + up16(sizeof(double) * (size_t)K), o_n = o_idx + up16(sizeof(int32_t) * (size_t)K), total = o_n + 16;
+    const KpLayout l = kp_layout(K, ldf, ND);
     PRE3_HIP(hipStreamSynchronize(f->stream));                // the staging block and the keypoint block are free again
-    if (f->kp_bytes < total) {
-        if (f->kp) (void)hipFree(f->kp);
-        f->kp = nullptr; f->kp_bytes = 0;
-        PRE3_TRY(sr_dmalloc(f, &f->kp, total + total / 4));
-        f->kp_bytes = total + total / 4;
-    }
-    PRE3_TRY(sr_grow_stage(f, b_frm + b_des));
+    PRE3_TRY(sr_frame_kp_reserve(f, l.total));
+    PRE3_TRY(sr_grow_stage(f, l.b_frm + l.b_des));
     memcpy(f->stage, frm, sizeof(double) * (size_t)K * ldf);
     // (the same copy, with the bounds of the ranked IC route noted on the way: pre3_set_scan_frame takes the raw set from this block)
-    if (ND > 0) f->kp_raw_ok = desc_copy_checked((double *)((char *)f->stage + b_frm), des, (size_t)K * ND);
-    f->kp_o_des_in = b_frm;
-    char *d = (char *)f->kp;
-    PRE3_HIP(hipMemcpyAsync(d, f->stage, b_frm + b_des, hipMemcpyHostToDevice, f->stream));
+    if (ND > 0) f->kp_raw_ok = desc_copy_checked((double *)((char *)f->stage + l.b_frm), des, (size_t)K * ND);
+    f->kp_o_des_in = l.b_frm;
+    PRE3_HIP(hipMemcpyAsync(f->kp, f->stage, l.b_frm + l.b_des, hipMemcpyHostToDevice, f->stream));
     f->kp_K_in = K;
-    const size_t npix = (size_t)f->rows * f->cols;
-    KpArgs a;
-    a.K = K; a.ldf = ldf; a.ND = ND; a.gate = gate; a.rows = f->rows; a.cols = f->cols; a.has_conf = f->has_conf;
-    a.frm = (const double *)d; a.des = (const double *)(d + b_frm);
-    a.xf = f->filt; a.yf = f->filt + npix; a.zf = f->filt + 2 * npix; a.conf = f->raw + 4 * npix; a.maxima = f->maxima;
-    a.n_kept = (int32_t *)(d + o_n); a.keep_idx = (int32_t *)(d + o_idx);
-    a.frm_out = (double *)(d + o_frm_out); a.des_out = (double *)(d + o_des_out); a.xyz_out = (double *)(d + o_xyz); a.rho_out = (double *)(d + o_rho);
-    hipLaunchKernelGGL(k_sr_keypoints, dim3(ceil_div(K, KB)), dim3(KB), 0, f->stream, a);
-    PRE3_HIP(hipGetLastError());
-    PRE3_HIP(hipMemcpyAsync(f->pinned_n, a.n_kept, sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-    PRE3_HIP(hipStreamSynchronize(f->stream));
-    const int n = *f->pinned_n;
-    PRE3_CHECK(n >= 0 && n <= K, PRE3_E_HIP, "pre3_sr_frame_keypoints: the device kept %d of %d keypoints", n, K);
-    *n_kept = n;
-    f->kp_n = n; f->kp_o_frm = o_frm_out; f->kp_o_des = o_des_out; f->kp_o_xyz = o_xyz; f->kp_o_rho = o_rho; f->kp_o_idx = o_idx;
-    if (n == 0) return PRE3_OK;
-    if (keep_idx) PRE3_HIP(hipMemcpyAsync(keep_idx, a.keep_idx, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, f->stream));
-    if (frm_out) PRE3_HIP(hipMemcpyAsync(frm_out, a.frm_out, sizeof(double) * (size_t)n * ldf, hipMemcpyDeviceToHost, f->stream));
-    if (des_out && ND > 0) PRE3_HIP(hipMemcpyAsync(des_out, a.des_out, sizeof(double) * (size_t)n * ND, hipMemcpyDeviceToHost, f->stream));
-    if (xyz_out && gate == 0) PRE3_HIP(hipMemcpyAsync(xyz_out, a.xyz_out, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, f->stream));
-    if (rho_out && gate == 0) PRE3_HIP(hipMemcpyAsync(rho_out, a.rho_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, f->stream));
-    PRE3_HIP(hipStreamSynchronize(f->stream));
-    return PRE3_OK;
+    return sr_gate_run(f, "pre3_sr_frame_keypoints", gate, n_kept, keep_idx, frm_out, des_out, xyz_out, rho_out);
 }
 
 int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K, const double *frm, int ND, const double *des, int32_t *n_kept, int32_t *keep_idx,
@@ -479,6 +479,24 @@ int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K, const do
     bool touched = false;
     const int rc = sr_keypoints_impl(f, gate, ldf, K, frm, ND, des, n_kept, keep_idx, frm_out, des_out, xyz_out, rho_out, &touched);
     if (rc != PRE3_OK && touched) { f->kp_n = 0; f->kp_K_in = 0; }      // a call that failed behind its checks leaves a valid empty record
+    return rc;
+}
+
+// pre3_sr_frame_keypoints' gate over the raw set that is already in the block (a pre3_sr_frame_sift's, or an earlier upload's): nothing is sent
+int pre3_sr_frame_gate(pre3_sr_frame *f, int gate, int32_t *n_kept, int32_t *keep_idx, double *frm_out, double *des_out, double *xyz_out, double *rho_out)
+{
+    PRE3_CHECK(f != nullptr && n_kept != nullptr, PRE3_E_ARG, "pre3_sr_frame_gate: null argument");
+    PRE3_CHECK(gate == 0 || gate == 1, PRE3_E_ARG, "pre3_sr_frame_gate: gate %d is neither 0 (depth) nor 1 (confidence)", gate);
+    PRE3_CHECK(f->loaded && f->kp_valid, PRE3_E_STATE, "pre3_sr_frame_gate: the frame holds no keypoint set (none yet, or a frame was loaded after it)");
+    PRE3_CHECK(gate == 0 || f->has_conf, PRE3_E_ARG, "pre3_sr_frame_gate: gate 1 needs the confidence map (the frame was loaded without one)");
+    PRE3_CHECK(f->kp_ldf == 4 && f->kp_ND == DESC_DIM, PRE3_E_ARG, "pre3_sr_frame_gate: the set in the block has ldf = %d, ND = %d; the outputs are sized for 4 and %d",
+               f->kp_ldf, f->kp_ND, DESC_DIM);
+    PRE3_TRY(select_device("pre3_sr_frame_gate", f->device));
+    *n_kept = 0;
+    f->kp_gate = gate; f->kp_n = 0;
+    if (f->kp_K_in == 0) return PRE3_OK;
+    const int rc = sr_gate_run(f, "pre3_sr_frame_gate", gate, n_kept, keep_idx, frm_out, des_out, xyz_out, rho_out);
+    if (rc != PRE3_OK) f->kp_n = 0;                           // (the raw set stays: it was not this call's)
     return rc;
 }
 

@@ -11,6 +11,8 @@ readers and keypoint filters over the C ABI.
     initialize_features.m:95-99 + map_management.m:27-79     -> initialize_features_frames (two resident frames, gate 0 on each, then the policy)
     plane_fit_to_data.m:7-149                                -> plane_fit_to_data      (the fit on a resident frame, plane.plane_fit_frame_seeded)
     fv.m:41-48 + ekf_prediction.m                            -> fv_pair, ekf_prediction_frames (the VO pair and the prediction, u on the device)
+    sift/sift_vedal.m:127-323 (+ the five MEX files)         -> SrFrame.sift, sift_vedal, sift_plan (the SIFT set made on the device)
+    SIFT_extract_save.m:44-88                                -> sift_extract_frame     (sift + gate 0 on a resident frame, nothing uploaded)
 
 All compute runs in libpre3.so on the GPU; this module reads the text file and marshals numpy arrays.
 """
@@ -24,6 +26,7 @@ ROWS, COLS = 144, 176                     # a d1_%04d.dat frame
 MAX_KEYPOINTS = 8192                      # PRE3_SR_MAX_KEYPOINTS
 MODE_XYZ, MODE_DR_YE = 0, 1               # read_xyz_sr4000.m / read_image_sr4000.m; read_sr4000_data_dr_ye.m
 GATE_DEPTH, GATE_CONFIDENCE = 0, 1        # inittialize_depth_my_version.m:40,74; confidence_filtering.m:8
+SIFT_LEVELS, SIFT_MAX_TAPS = 6, 32        # PRE3_SIFT_LEVELS, PRE3_SIFT_MAX_TAPS
 
 
 def gauss3(sigma):
@@ -31,6 +34,18 @@ def gauss3(sigma):
     w = np.zeros(9)
     check(lib.pre3_sr_gauss3(float(sigma), dptr(w)))
     return w.reshape(3, 3).T.copy()
+
+
+def sift_plan(rows, cols):
+    """pre3_sift_plan_get: dict(O, rows (O,), cols (O,), sigma0, pow2 (5,), sigma (O, 6), W (O, 6), taps (O, 6, 32)) -- the bits the launches use"""
+    O = C.c_int32(0)
+    orows, ocols = np.zeros(32, np.int32), np.zeros(32, np.int32)
+    sigma0, pow2 = C.c_double(0), np.zeros(5)
+    sigma, W, taps = np.zeros((32, SIFT_LEVELS)), np.zeros((32, SIFT_LEVELS), np.int32), np.zeros((32, SIFT_LEVELS, SIFT_MAX_TAPS))
+    check(lib.pre3_sift_plan_get(int(rows), int(cols), C.byref(O), dptr(orows), dptr(ocols), C.byref(sigma0), dptr(pow2), dptr(sigma), dptr(W), dptr(taps)))
+    O = O.value
+    return dict(O=O, rows=orows[:O].copy(), cols=ocols[:O].copy(), sigma0=sigma0.value, pow2=pow2, sigma=sigma[:O].copy(), W=W[:O].copy(),
+                taps=taps[:O].copy())
 
 
 def load_dat(path, rows=ROWS):
@@ -124,10 +139,76 @@ class SrFrame:
         check(lib.pre3_sr_frame_keypoints(self._h, int(gate), ldf, K, dptr(frm), ND, dptr(des), C.byref(n), dptr(idx), dptr(frm_o), dptr(des_o),
                                           dptr(xyz), dptr(rho)))
         n = self.n_kept = n.value
+        return self._gate_outputs(gate, n, idx, frm_o, des_o, xyz, rho)
+
+    @staticmethod
+    def _gate_outputs(gate, n, idx, frm_o, des_o, xyz, rho):
         out = dict(keep_idx=idx[:n].copy(), frames=frm_o[:, :n].copy(order="F"), descriptors=des_o[:, :n].copy(order="F"))
         if int(gate) == GATE_DEPTH:
             out["xyz"], out["rho"] = xyz[:, :n].copy(order="F"), rho[:n].copy()
         return out
+
+    def sift(self, image=None, strict_reference=1, one_based=True, want_arrays=True):
+        """sift_vedal on `image` (rows x cols) or on the frame's own filtered image; the set stays in the handle's keypoint block as the raw set
+        (1-based frames), ready for gate().  Returns dict(frames (4, K), descriptors (128, K), counts (O, 4) = maxima, inside the boundary, refined,
+        oriented per octave); one_based=False: sift_vedal's own 0-based x, y in `frames`.  want_arrays=False brings back the counts only."""
+        img = None if image is None else self._plane(image, "image")
+        K = C.c_int32(0)
+        counts = np.zeros((32, 4), np.int32)
+        frm = np.zeros((4, MAX_KEYPOINTS), order="F") if want_arrays else None
+        des = np.zeros((128, MAX_KEYPOINTS), order="F") if want_arrays else None
+        check(lib.pre3_sr_frame_sift(self._h, dptr(img), int(strict_reference), int(bool(one_based)), C.byref(K), dptr(frm), dptr(des), dptr(counts)))
+        K = K.value
+        O = sift_plan(self.rows, self.cols)["O"]
+        out = dict(K=K, counts=counts[:O].astype(np.int64))
+        if want_arrays:
+            out["frames"], out["descriptors"] = frm[:, :K].copy(order="F"), des[:, :K].copy(order="F")
+        return out
+
+    def gate(self, gate=GATE_DEPTH):
+        """keypoints()' gate over the raw set already in the block -- sift()'s, or a keypoints() upload of (4, K) frames and (128, K) descriptors; any
+        other shape is refused by the library (the outputs are sized for 4 and 128): nothing is uploaded.  Returns what keypoints() returns."""
+        n = C.c_int32(0)
+        Kb = MAX_KEYPOINTS
+        idx, frm_o, des_o = np.zeros(Kb, np.int32), np.zeros((4, Kb), order="F"), np.zeros((128, Kb), order="F")
+        xyz, rho = np.zeros((3, Kb), order="F"), np.zeros(Kb)
+        check(lib.pre3_sr_frame_gate(self._h, int(gate), C.byref(n), dptr(idx), dptr(frm_o), dptr(des_o), dptr(xyz), dptr(rho)))
+        n = self.n_kept = n.value
+        return self._gate_outputs(gate, n, idx, frm_o, des_o, xyz, rho)
+
+    def sift_refined(self):
+        """the refined points of the last sift(), before the orientations: (4, n) = x, y, s, octave (0-based, octave coordinates), all octaves in order"""
+        n = C.c_int32(0)
+        check(lib.pre3_sr_frame_sift_refined(self._h, C.byref(n), None))
+        out = np.zeros((4, max(n.value, 1)), order="F")
+        check(lib.pre3_sr_frame_sift_refined(self._h, C.byref(n), dptr(out)))
+        return out[:, :n.value].copy(order="F")
+
+    def sift_level(self, o, s, dog=False):
+        """level s (0-based) of octave o of gss (dog=False) or dogss (dog=True) of the last sift()"""
+        pl = sift_plan(self.rows, self.cols)
+        if not 0 <= int(o) < pl["O"]:
+            raise Pre3Error(-1, "SrFrame.sift_level: octave %d outside %d octaves" % (o, pl["O"]))
+        out = np.zeros((pl["rows"][o], pl["cols"][o]), order="F")
+        check(lib.pre3_sr_frame_sift_level(self._h, int(o), int(s), int(bool(dog)), dptr(out)))
+        return out
+
+
+def sift_vedal(I, strict_reference=1, device=0):
+    """[frames, descriptors] = sift_vedal(I) (0-based frames, as the reference returns them) on a handle of I's size, used once"""
+    I = np.asfortranarray(f64(I))
+    with SrFrame(I.shape[0], I.shape[1], device) as f:
+        out = f.sift(I, strict_reference, one_based=False)
+    return out["frames"], out["descriptors"]
+
+
+def sift_extract_frame(frame, idx_scan):
+    """SIFT_extract_save.m:44-88 on a resident frame: sift on its own image, :55-56's 1-based frames, the depth gate -- the SCAN_SIFT dict of
+    sift_extract, with no SIFT array uploaded"""
+    raw = frame.sift()
+    out = frame.gate(GATE_DEPTH)
+    return dict(idxScan=int(idx_scan), Image=frame.image(), Descriptor_RAW=raw["descriptors"], SCALE_ORIENT_POS_RAW=raw["frames"],
+                Descriptor=out["descriptors"], SCALE_ORIENT_POS=out["frames"], XYZ_DATA=out["xyz"], initial_rho=out["rho"], keep_idx=out["keep_idx"])
 
 
 def _conditioned(path, mode, device):
@@ -249,6 +330,53 @@ def initialize_features_frames(filt, step, dat_prev, dat_cur, sift_prev, sift_cu
         for f, d, (frm, des) in ((f1, d1, sift_prev), (f2, d2, sift_cur)):
             f.load(d, mode)
             kept.append(f.keypoints(frm, des, GATE_DEPTH)["keep_idx"])
+        out = filt.map_management_policy_frames_seeded(step, f1, f2, seed, seq, thresh, **policy)
+    finally:
+        if own:
+            f1.close(); f2.close()
+    out["kept_prev"], out["kept_cur"] = kept
+    out["cand_idx"] = kept[0][out["match"][0].astype(np.int64) - 1] if out["K"] else np.zeros(0, np.int32)
+    return out
+
+
+def _two_frames(d1, d2, device, frames):
+    own = frames is None
+    f1, f2 = (SrFrame(d1["z"].shape[0], d1["z"].shape[1], device), SrFrame(d2["z"].shape[0], d2["z"].shape[1], device)) if own else frames
+    return own, f1, f2
+
+
+def vodometry_frames(dat1, dat2, seed, seq=0, thresh=1.5, device=0, frames=None):
+    """vodometry_dr_ye with the SIFT sets made on the device: each file is conditioned in mode 1, SrFrame.sift runs on its filtered image, gate 1 (gate 0
+    on a frame without confidence rows) drops keypoints, then vo.vo_pair_seeded.  The gated set is 1-based, as vodometry_dr_ye.m:73-74,120-122 make
+    it before confidence_filtering."""
+    from . import vo
+    d1, d2 = load_dat(dat1), load_dat(dat2)
+    own, f1, f2 = _two_frames(d1, d2, device, frames)
+    try:
+        kept = []
+        for f, d in ((f1, d1), (f2, d2)):
+            f.load(d, MODE_DR_YE)
+            f.sift(want_arrays=False)
+            kept.append(f.gate(GATE_CONFIDENCE if d["conf"] is not None else GATE_DEPTH)["keep_idx"])
+        out = vo.vo_pair_seeded(f1, f2, seed, seq, thresh)
+    finally:
+        if own:
+            f1.close(); f2.close()
+    out["kept1"], out["kept2"] = kept
+    return out
+
+
+def initialize_features_scans(filt, step, dat_prev, dat_cur, seed, seq=0, thresh=1.5, mode=MODE_XYZ, device=0, frames=None, **policy):
+    """initialize_features_frames with the SIFT sets made on the device (SrFrame.sift on each conditioned scan, then the depth gate); cand_idx indexes the
+    previous scan's raw set"""
+    d1, d2 = load_dat(dat_prev), load_dat(dat_cur)
+    own, f1, f2 = _two_frames(d1, d2, device, frames)
+    try:
+        kept = []
+        for f, d in ((f1, d1), (f2, d2)):
+            f.load(d, mode)
+            f.sift(want_arrays=False)
+            kept.append(f.gate(GATE_DEPTH)["keep_idx"])
         out = filt.map_management_policy_frames_seeded(step, f1, f2, seed, seq, thresh, **policy)
     finally:
         if own:

@@ -560,6 +560,52 @@ PRE3_API int pre3_sr_frame_keypoints(pre3_sr_frame *f, int gate, int ldf, int K,
                                      int32_t *n_kept, int32_t *keep_idx, double *frm_out, double *des_out,
                                      double *xyz_out /* 3 x n_kept, gate 0 */, double *rho_out);
 
+/* ---- the SIFT extractor on a resident frame -----------------------------------------------------------------------------------
+ * [frames, descriptors, gss, dogss] = sift_vedal(I) (sift/sift_vedal.m:127-323) with its defaults -- S = 3, omin = -1, O = floor(log2(min(M, N))) + 1 - 3,
+ * sigma0 = 1.6 2^(1/3), sigman = 0.5, thresh = 0.04 / 3 / 2, r = 10, NBP = 4, NBO = 8, magnif = 3, boundary points discarded -- on the handle's stream.
+ * It replaces the reference's native per-frame code: imsmooth.c:44-80,128-160 (the fp64 separable Gaussian; PAD_BY_CONTINUITY is defined, so a tap
+ * outside the image reads the nearest edge pixel), gaussianss.m:133-227 (the level chain, doubleSize, halveSize), diffss.m:57-66,
+ * siftlocalmax.c:229-249, sift_vedal.m:259-265 (the boundary discard), siftrefinemx.c:150-303, siftormx.c:138-253, siftdescriptor.c:310-513.
+ * Bit-exact against tests/sift_ref.py: every level of gss and dogss, the counts, the refined points and their order.  Equal: the number and order of
+ * the orientations.  Toleranced (they pass through pow, exp, atan2, sqrt, fmod, sin, cos of the device's library and a summation order of their own):
+ * sigma, theta and the descriptor entries.  Results are bit-equal from run to run. */
+#define PRE3_SIFT_MAX_TAPS 32
+#define PRE3_SIFT_LEVELS 6                                  /* Gaussian levels per octave (smin = -1 .. smax = 4); one DoG level fewer */
+#define PRE3_SIFT_MAX_CANDIDATES (4 * PRE3_SR_MAX_KEYPOINTS)   /* refined keypoints (before the orientations multiply them), all octaves together */
+/* The scale-space plan of a rows x cols image, made with the host's exp / pow / sqrt: the bits the launches use (gaussianss.m:72-80,129-203,
+ * imsmooth.c:130-142).  O_out: the number of octaves; oct_rows / oct_cols [O]: their sizes (the first is 2 rows x 2 cols); sigma0_out;
+ * pow2_out[5] = 2^(s / S), s = -1 .. 3 (the boundary test's); for octave o and level l at [o * PRE3_SIFT_LEVELS + l]: sigma_out (the smoothing that
+ * makes the level from the one before it; <= 0.01: a copy), W_out = ceil(4 sigma), taps_out[.. * PRE3_SIFT_MAX_TAPS] the 2 W + 1 taps (zeros behind
+ * them).  Every output except O_out may be NULL.  Host only: needs no device.  min(rows, cols) < 8: PRE3_E_ARG. */
+PRE3_API int pre3_sift_plan_get(int rows, int cols, int32_t *O_out, int32_t *oct_rows, int32_t *oct_cols, double *sigma0_out, double *pow2_out,
+                                double *sigma_out, int32_t *W_out, double *taps_out);
+/* sift_vedal on `image` (rows x cols doubles, column-major) or, with image == NULL, on the handle's own filtered image.  strict_reference = 1: the image
+ * is uint8 and doubleSize (gaussianss.m:210-224) interpolates in uint8 class -- every 0.25 I / 0.5 I term rounded half away from zero, the sums
+ * saturated at 255 left to right; 0: in double.  The set is left in the handle's keypoint block as the RAW set, as after the transfer of a
+ * pre3_sr_frame_keypoints with ldf = 4, ND = 128: frames [K][4] = (x + 1, y + 1, sigma, theta), 1-based as SIFT_extract_save.m:55-56 leaves them,
+ * descriptors [K][128] behind them.  No gate has run: pre3_sr_frame_gate is next.  K_out; frm_out 4 x K (one_based = 0: sift_vedal's own 0-based x, y;
+ * the block is unaffected); des_out 128 x K; counts_out[4 * O]: per octave the maxima of +D and -D, those inside the boundary, the refined, the oriented.
+ * Outputs other than K_out may be NULL; they must hold PRE3_SR_MAX_KEYPOINTS columns unless K is known.  Waits once, at the end.
+ * The descriptor bounds of the ranked IC route (finite, |x| <= 2^60, no non-zero |x| < 2^-40) are or-reduced on the device and come back with the counts.
+ * PRE3_E_ARG before anything is queued, the previous record intact: a null handle or K_out; min(rows, cols) < 8; a non-finite image entry; with
+ * strict_reference an entry that is not an integer in 0 .. 255.  PRE3_E_STATE likewise: image == NULL before the first load.  PRE3_E_NOMEM after the
+ * wait, leaving a valid empty record: more than PRE3_SIFT_MAX_CANDIDATES refined keypoints or more than PRE3_SR_MAX_KEYPOINTS keypoints. */
+PRE3_API int pre3_sr_frame_sift(pre3_sr_frame *f, const double *image /* NULL: the handle's own filtered image */, int strict_reference, int one_based,
+                                int32_t *K_out, double *frm_out /* 4 x K */, double *des_out /* 128 x K */, int32_t *counts_out /* 4 per octave */);
+/* pre3_sr_frame_keypoints' gate launch (SIFT_extract_save.m:71-88, confidence_filtering.m:1-13) over the raw set ALREADY in the block -- a
+ * pre3_sr_frame_sift's, or an earlier pre3_sr_frame_keypoints' with ldf = 4 and ND = 128 -- with no upload; a position is clamped into the image.
+ * Same outputs and the same record as pre3_sr_frame_keypoints fed with that set: frm_out[n_kept][4], des_out[n_kept][128].  PRE3_E_STATE: no frame
+ * loaded, or no raw set for the frame the handle holds.  PRE3_E_ARG: the set in the block has another ldf or ND (the outputs are sized for 4 and 128). */
+PRE3_API int pre3_sr_frame_gate(pre3_sr_frame *f, int gate, int32_t *n_kept, int32_t *keep_idx, double *frm_out, double *des_out,
+                                double *xyz_out /* 3 x n_kept, gate 0 */, double *rho_out);
+/* a level of gss (dog = 0: level 0 .. 5) or dogss (dog = 1: 0 .. 4) of octave `octave` of the last pre3_sr_frame_sift -- sift_vedal's third and fourth
+ * outputs -- into out[oct_rows x oct_cols], column-major.  Synchronises.  PRE3_E_STATE before the first pre3_sr_frame_sift. */
+PRE3_API int pre3_sr_frame_sift_level(pre3_sr_frame *f, int octave, int level, int dog, double *out);
+/* the refined points of the last pre3_sr_frame_sift (siftrefinemx's output, before the orientations), all octaves in order: n_out, and out[n][4] =
+ * (x, y, s, octave) with x, y, s in the octave's own coordinates, 0-based, and octave counted from 0.  out may be NULL (the count alone), else it holds
+ * PRE3_SIFT_MAX_CANDIDATES rows unless n is known.  Synchronises.  PRE3_E_STATE before the first pre3_sr_frame_sift, or after one that overflowed. */
+PRE3_API int pre3_sr_frame_sift_refined(pre3_sr_frame *f, int32_t *n_out, double *out);
+
 /* ---- the VO front end between two resident SR4000 frames, in one call ---------------------------------------------------------
  * vodometry_dr_ye.m:139-236 + Calculate_V_Omega_RANSAC_dr_ye.m:41-50 between the keypoint sets held by two resident frames: prev and cur each hold the
  * result of their last pre3_sr_frame_keypoints (gate 1 in the reference: confidence_filtering.m on both frames).  siftmatch(des1, des2, thresh)

@@ -19,6 +19,7 @@
  *   Weighted_Smpl_wo_replacement.m  [del, acc, cv, st, order] = pre3_mex('map_policy_seeded', step, UV, XYZ, DESC, 50, 0.1, std_z, 1, [176 144], seed, step)   % ... and its draw
  *   read_xyz_sr4000.m, read_image_sr4000.m, read_sr4000_data_dr_ye.m   [x, y, z, img, imax, cmax] = pre3_mex('sr_frame', mode, z, x, y, amp, conf)   % conf = [] for none; the frame stays resident
  *   SIFT_extract_save.m:71-88, confidence_filtering.m                  [frm, des, idx, xyz, rho] = pre3_mex('sr_keypoints', gate, frames, descriptors)    % on the resident frame; no filter context needed
+ *   sift_vedal.m:127-323, SIFT_extract_save.m:44-88                    [frames, descriptors, counts] = pre3_mex('sr_sift'); [frm, des, idx, xyz, rho] = pre3_mex('sr_gate', gate)   % the SIFT set made on the device
  *   vodometry_dr_ye.m:139-236, Calculate_V_Omega_RANSAC_dr_ye.m:41-50  pre3_mex('sr_keep'); ... next frame's 'sr_frame' + 'sr_keypoints' (gate 1) ...; [T, q, R, sta, match, stat] = pre3_mex('vo_pair', seed, seq)
  *   initialize_features.m:95-99 + map_management.m:27-79               pre3_mex('sr_keep'); ... next frame's 'sr_frame' + 'sr_keypoints' (gate 0 on both) ...; [del, acc, cv, st, order, match] = pre3_mex('map_policy_frames', step, 50, 0.1, std_z, 1, [176 144], seed, step)
  *   plane_fit_to_data.m:7-149 on the resident frame                     [R, sta, B, n_inliers] = pre3_mex('plane_frame', seed, seq)                          % the box is gathered on the device
@@ -90,6 +91,41 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         check(pre3_sr_frame_keypoints(g_sr, gate, ldf, K, mxGetPr(in[2]), ND, ND ? mxGetPr(in[3]) : NULL, &n, idx, f2, d2, xyz, rho));
         out[0] = mxCreateDoubleMatrix(ldf, n, mxREAL); memcpy(mxGetPr(out[0]), f2, sizeof(double) * (size_t)n * ldf);
         out[1] = mxCreateDoubleMatrix(ND, n, mxREAL); memcpy(mxGetPr(out[1]), d2, sizeof(double) * (size_t)n * ND);
+        out[2] = mxCreateDoubleMatrix(1, n, mxREAL); for (i = 0; i < n; ++i) mxGetPr(out[2])[i] = idx[i] + 1;
+        out[3] = mxCreateDoubleMatrix(3, gate == 0 ? n : 0, mxREAL); out[4] = mxCreateDoubleMatrix(1, gate == 0 ? n : 0, mxREAL);
+        if (gate == 0) { memcpy(mxGetPr(out[3]), xyz, sizeof(double) * 3 * (size_t)n); memcpy(mxGetPr(out[4]), rho, sizeof(double) * (size_t)n); }
+        mxFree(idx); mxFree(f2); mxFree(d2); mxFree(xyz); mxFree(rho);
+        (void)nout;
+        return;
+    }
+    if (!strcmp(cmd, "sr_sift")) {           /* [frames, descriptors, counts] = pre3_mex('sr_sift' [, strict_reference = 1 [, one_based = 1]]): sift_vedal.m:127-323 on the
+                                                 resident frame's own image, made on the device; the set stays in the handle as the raw set (1-based, SIFT_extract_save.m:55-56).
+                                                 frames 4 x K (one_based = 0: sift_vedal's own 0-based x, y), descriptors 128 x K, counts 4 x O (maxima, inside the boundary,
+                                                 refined, oriented per octave) */
+        int32_t K = 0, counts[4 * 32], O = 0; int i; double *f2, *d2;
+        if (nin > 3) mexErrMsgTxt("pre3_mex('sr_sift' [, strict_reference [, one_based]]): at most two arguments");
+        if (!g_sr) mexErrMsgTxt("pre3_mex('sr_sift'): call pre3_mex('sr_frame', ...) first");
+        f2 = (double *)mxMalloc(sizeof(double) * 4 * PRE3_SR_MAX_KEYPOINTS); d2 = (double *)mxMalloc(sizeof(double) * 128 * (size_t)PRE3_SR_MAX_KEYPOINTS);
+        check(pre3_sift_plan_get(g_sr_rows, g_sr_cols, &O, NULL, NULL, NULL, NULL, NULL, NULL, NULL));
+        check(pre3_sr_frame_sift(g_sr, NULL, nin > 1 ? (int)mxGetScalar(in[1]) : 1, nin > 2 ? (int)mxGetScalar(in[2]) : 1, &K, f2, d2, counts));
+        out[0] = mxCreateDoubleMatrix(4, K, mxREAL); memcpy(mxGetPr(out[0]), f2, sizeof(double) * 4 * (size_t)K);
+        out[1] = mxCreateDoubleMatrix(128, K, mxREAL); memcpy(mxGetPr(out[1]), d2, sizeof(double) * 128 * (size_t)K);
+        out[2] = mxCreateDoubleMatrix(4, O, mxREAL); for (i = 0; i < 4 * O; ++i) mxGetPr(out[2])[i] = counts[i];
+        mxFree(f2); mxFree(d2);
+        (void)nout;
+        return;
+    }
+    if (!strcmp(cmd, "sr_gate")) {           /* [frm, des, idx (1-based), xyz, rho] = pre3_mex('sr_gate', gate): 'sr_keypoints'' gate over the raw set already in the handle
+                                                 ('sr_sift''s, or a 'sr_keypoints' upload of 4 x K frames and 128 x K descriptors: the library refuses any other shape), nothing uploaded */
+        int gate, i; int32_t n = 0, *idx; double *f2, *d2, *xyz, *rho; const size_t cap = PRE3_SR_MAX_KEYPOINTS;
+        if (nin != 2) mexErrMsgTxt("pre3_mex('sr_gate', gate): one argument");
+        if (!g_sr) mexErrMsgTxt("pre3_mex('sr_gate'): call pre3_mex('sr_frame', ...) and pre3_mex('sr_sift') first");
+        gate = (int)mxGetScalar(in[1]);
+        idx = (int32_t *)mxMalloc(sizeof(int32_t) * cap); f2 = (double *)mxMalloc(sizeof(double) * 4 * cap); d2 = (double *)mxMalloc(sizeof(double) * 128 * cap);
+        xyz = (double *)mxMalloc(sizeof(double) * 3 * cap); rho = (double *)mxMalloc(sizeof(double) * cap);
+        check(pre3_sr_frame_gate(g_sr, gate, &n, idx, f2, d2, xyz, rho));
+        out[0] = mxCreateDoubleMatrix(4, n, mxREAL); memcpy(mxGetPr(out[0]), f2, sizeof(double) * 4 * (size_t)n);
+        out[1] = mxCreateDoubleMatrix(128, n, mxREAL); memcpy(mxGetPr(out[1]), d2, sizeof(double) * 128 * (size_t)n);
         out[2] = mxCreateDoubleMatrix(1, n, mxREAL); for (i = 0; i < n; ++i) mxGetPr(out[2])[i] = idx[i] + 1;
         out[3] = mxCreateDoubleMatrix(3, gate == 0 ? n : 0, mxREAL); out[4] = mxCreateDoubleMatrix(1, gate == 0 ? n : 0, mxREAL);
         if (gate == 0) { memcpy(mxGetPr(out[3]), xyz, sizeof(double) * 3 * (size_t)n); memcpy(mxGetPr(out[4]), rho, sizeof(double) * (size_t)n); }
