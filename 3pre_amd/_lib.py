@@ -61,6 +61,9 @@ lib.pre3_sr_frame_sift.argtypes = [_P, _P, _I, _I, _P, _P, _P, _P]
 lib.pre3_sr_frame_gate.argtypes = [_P, _I, _P, _P, _P, _P, _P, _P]
 lib.pre3_sr_frame_sift_level.argtypes = [_P, _I, _I, _I, _P]
 lib.pre3_sr_frame_sift_refined.argtypes = [_P, _P, _P]
+lib.pre3_sr_text_limits.argtypes = [_P, _P]
+lib.pre3_sr_text_parse.argtypes = [_I, _P, C.c_size_t, _P, C.c_size_t, _P]
+lib.pre3_sr_frame_load_text.argtypes = [_P, _I, _P, C.c_size_t, _P]
 
 F64, F32 = 0, 1
 INVDEPTH, CARTESIAN = 0, 1
@@ -128,4 +131,5 @@ EXPORTS = [
     "pre3_plane_fit_frame", "pre3_plane_fit_frame_seeded", "pre3_heading_from_frame", "pre3_heading_from_frame_seeded", "pre3_set_scan_frame",
     "pre3_predict_pair_seeded",
     "pre3_sift_plan_get", "pre3_sr_frame_sift", "pre3_sr_frame_gate", "pre3_sr_frame_sift_level", "pre3_sr_frame_sift_refined",
+    "pre3_sr_text_limits", "pre3_sr_text_parse", "pre3_sr_frame_load_text",
 ]

@@ -204,6 +204,37 @@ int sr_frame_kp_reserve(pre3_sr_frame *f, size_t total)
     return PRE3_OK;
 }
 
+// the device half of a load, behind whatever put the planes into `raw` (the staged transfer of pre3_sr_frame_load, the text parse of
+// pre3_sr_frame_load_text): the maxima launch and the conditioning launch on the handle's stream, then the handle holds the frame
+int sr_condition_run(pre3_sr_frame *f, int mode, bool has_conf)
+{
+    const size_t npix = (size_t)f->rows * f->cols;
+    hipLaunchKernelGGL(k_sr_maxima, dim3(1), dim3(MB), 0, f->stream, (int)npix, (const double *)(f->raw + 3 * npix),
+                       has_conf ? (const double *)(f->raw + 4 * npix) : (const double *)nullptr, f->maxima);
+    PRE3_HIP(hipGetLastError());
+    SrWeights W;
+    sr_gauss3(mode == 0 ? 2.0 : 1.0, W.w);
+    hipLaunchKernelGGL(k_sr_condition, dim3(ceil_div(f->rows, ST), ceil_div(f->cols, ST)), dim3(ST * ST), 0, f->stream, f->rows, f->cols, mode, W,
+                       (const double *)f->raw, (const double *)f->maxima, f->filt);
+    PRE3_HIP(hipGetLastError());
+    f->mode = mode; f->has_conf = has_conf ? 1 : 0; f->loaded = 1;
+    return PRE3_OK;
+}
+
+// the text stage's blocks (pre3_dattext.hip), allocated on its first use: the work block behind the text, grown on demand, and the spare plane block
+// the parse writes -- it and `raw` swap once a text is accepted.  The caller has waited for the stream.
+int sr_frame_text_work(pre3_sr_frame *f, size_t work_bytes, size_t spare_bytes)
+{
+    if (f->text_dev_bytes < work_bytes) {
+        if (f->text_dev) (void)hipFree(f->text_dev);
+        f->text_dev = nullptr; f->text_dev_bytes = 0;
+        PRE3_TRY(sr_dmalloc(f, &f->text_dev, work_bytes + work_bytes / 4));
+        f->text_dev_bytes = work_bytes + work_bytes / 4;
+    }
+    if (f->spare == nullptr) PRE3_TRY(sr_dmalloc(f, (void **)&f->spare, spare_bytes));
+    return PRE3_OK;
+}
+
 int select_device(const char *who, int device)
 {
     int nd = 0;
@@ -320,6 +351,8 @@ int pre3_sr_frame_destroy(pre3_sr_frame *f)
     if (f->stage) (void)hipHostFree(f->stage);
     if (f->pinned_n) (void)hipHostFree(f->pinned_n);
     if (f->pair_dev) (void)hipFree(f->pair_dev);
+    if (f->text_dev) (void)hipFree(f->text_dev);
+    if (f->spare) (void)hipFree(f->spare);
     if (f->pair_pin) (void)hipHostFree(f->pair_pin);
     if (f->pair_ev) (void)hipEventDestroy(f->pair_ev);
     if (f->sift) sift_work_free(f->sift);
@@ -369,16 +402,7 @@ int pre3_sr_frame_load(pre3_sr_frame *f, int mode, const double *z, const double
     if (conf != nullptr) memcpy(st + 4 * npix, conf, sizeof(double) * npix);
     f->loaded = 0; f->kp_valid = 0;                           // the keypoint record belongs to the frame that is being replaced
     PRE3_HIP(hipMemcpyAsync(f->raw, st, sizeof(double) * (conf != nullptr ? 5 : 4) * npix, hipMemcpyHostToDevice, f->stream));
-    hipLaunchKernelGGL(k_sr_maxima, dim3(1), dim3(MB), 0, f->stream, (int)npix, (const double *)(f->raw + 3 * npix),
-                       conf != nullptr ? (const double *)(f->raw + 4 * npix) : (const double *)nullptr, f->maxima);
-    PRE3_HIP(hipGetLastError());
-    SrWeights W;
-    sr_gauss3(mode == 0 ? 2.0 : 1.0, W.w);
-    hipLaunchKernelGGL(k_sr_condition, dim3(ceil_div(f->rows, ST), ceil_div(f->cols, ST)), dim3(ST * ST), 0, f->stream, f->rows, f->cols, mode, W,
-                       (const double *)f->raw, (const double *)f->maxima, f->filt);
-    PRE3_HIP(hipGetLastError());
-    f->mode = mode; f->has_conf = conf != nullptr ? 1 : 0; f->loaded = 1;
-    return PRE3_OK;
+    return sr_condition_run(f, mode, conf != nullptr);
 }
 
 int pre3_sr_frame_get(pre3_sr_frame *f, double *x, double *y, double *z, double *img, double *conf, double *imax, double *cmax)

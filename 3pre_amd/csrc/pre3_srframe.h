@@ -32,6 +32,11 @@ struct pre3_sr_frame {
     hipEvent_t pair_ev = nullptr;   // carries the hand-offs to and from a consumer's stream (sr_frame_lend, sr_frame_reclaim)
     // the SIFT extractor's plan, scale space and lists (pre3_sift.hip), allocated on its first use
     pre3::SiftWork *sift = nullptr;
+    // the text stage (pre3_dattext.hip), allocated on its first use: [text | chunk records | token offsets | status], and the plane block the parse
+    // writes, which swaps with `raw` when a text is accepted
+    void *text_dev = nullptr;
+    size_t text_dev_bytes = 0;
+    double *spare = nullptr;
 };
 
 namespace pre3 {
@@ -41,4 +46,6 @@ KpLayout kp_layout(int K, int ldf, int ND);
 // the keypoint block grown to `total` bytes (zeroed on the handle's stream when it is new).  The caller has waited for the stream.
 int sr_frame_kp_reserve(pre3_sr_frame *f, size_t total);
 int sr_grow_stage(pre3_sr_frame *f, size_t bytes);
+int sr_condition_run(pre3_sr_frame *f, int mode, bool has_conf);                       // the maxima and conditioning launches over `raw`
+int sr_frame_text_work(pre3_sr_frame *f, size_t work_bytes, size_t spare_bytes);        // pre3_dattext.hip's blocks
 }  // namespace pre3

@@ -14,7 +14,10 @@ readers and keypoint filters over the C ABI.
     sift/sift_vedal.m:127-323 (+ the five MEX files)         -> SrFrame.sift, sift_vedal, sift_plan (the SIFT set made on the device)
     SIFT_extract_save.m:44-88                                -> sift_extract_frame     (sift + gate 0 on a resident frame, nothing uploaded)
 
-All compute runs in libpre3.so on the GPU; this module reads the text file and marshals numpy arrays.
+    read_xyz_sr4000.m:2-3,25-42 (load of d1_%04d.dat)        -> loadtxt_device, SrFrame.load_text, parse="device" (the text parsed on the device, section 26)
+
+All compute runs in libpre3.so on the GPU; this module reads the file's bytes -- parsed on the host (numpy.loadtxt, the default) or handed to the device
+as they are (parse="device") -- and marshals numpy arrays.
 """
 import ctypes as C
 
@@ -60,6 +63,53 @@ def load_dat(path, rows=ROWS):
     return out
 
 
+TEXT_STATUS = ("ok", "bad token", "ragged rows", "wrong shape for this handle", "undecided token", "negative or non-finite amplitude", "empty text")
+
+
+class TextInfo(C.Structure):
+    """pre3_sr_text_info"""
+    _fields_ = [(k, C.c_int32) for k in ("status", "rows", "cols", "has_conf", "has_timestamp", "n_tokens", "n_undecided", "bad_row", "bad_col")] + [
+        ("bad_offset", C.c_int64), ("timestamp", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["status_text"] = TEXT_STATUS[self.status] if 0 <= self.status < len(TEXT_STATUS) else "?"
+        return d
+
+
+def text_limits():
+    """(chunk_bytes, max_bytes) of the device parse"""
+    chunk, top = C.c_int32(0), C.c_int64(0)
+    check(lib.pre3_sr_text_limits(C.byref(chunk), C.byref(top)))
+    return chunk.value, top.value
+
+
+def _text_bytes(data):
+    """the bytes themselves, or the contents of the file `data` names"""
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return bytes(data)
+    with open(data, "rb") as fh:
+        return fh.read()
+
+
+def _text_check(rc, info):
+    if rc != 0:
+        e = Pre3Error(rc, lib.pre3_last_error().decode(errors="replace"))
+        e.info = info.as_dict()
+        raise e
+
+
+def loadtxt_device(data, device=0):
+    """MATLAB's load / numpy.loadtxt of a rectangular ASCII matrix, parsed on the device (pre3_sr_text_parse): data is bytes or a path.  Returns
+    (ndarray (rows, cols), info dict); a refused text raises Pre3Error with the status text, its .info the same dict."""
+    text = _text_bytes(data)
+    info = TextInfo()
+    cap = (len(text) + 1) // 2                                # a token and its separator take two bytes
+    out = np.zeros(max(cap, 1))
+    _text_check(lib.pre3_sr_text_parse(int(device), text, len(text), dptr(out), cap, C.byref(info)), info)
+    return out[:info.rows * info.cols].reshape((info.rows, info.cols), order="F").copy(), info.as_dict()
+
+
 class SrFrame:
     """One resident, conditioned frame (pre3_sr_frame): load(planes, mode) queues the upload and the two conditioning launches and returns;
     planes(), image(), maxima() and keypoints() wait for them."""
@@ -98,6 +148,16 @@ class SrFrame:
         check(lib.pre3_sr_frame_load(self._h, int(mode), dptr(p[0]), dptr(p[1]), dptr(p[2]), dptr(p[3]), dptr(conf)))
         self.has_conf = conf is not None
         return self
+
+    def load_text(self, data, mode=MODE_XYZ):
+        """load() from the .dat file's bytes (or its path), parsed on the device (pre3_sr_frame_load_text): one wait for the status, then the
+        conditioning launches are queued as in load().  Returns dict(has_conf, timestamp (-1 without one), rows); a refused file raises Pre3Error
+        with the status text and leaves the handle as it was."""
+        text = _text_bytes(data)
+        info = TextInfo()
+        _text_check(lib.pre3_sr_frame_load_text(self._h, int(mode), text, len(text), C.byref(info)), info)
+        self.has_conf = bool(info.has_conf)
+        return dict(has_conf=self.has_conf, timestamp=float(info.timestamp), rows=int(info.rows))
 
     def _new(self):
         return np.zeros((self.rows, self.cols), order="F")
@@ -211,31 +271,55 @@ def sift_extract_frame(frame, idx_scan):
                 Descriptor=out["descriptors"], SCALE_ORIENT_POS=out["frames"], XYZ_DATA=out["xyz"], initial_rho=out["rho"], keep_idx=out["keep_idx"])
 
 
-def _conditioned(path, mode, device):
+def _check_parse(parse):
+    if parse not in ("host", "device"):
+        raise ValueError("parse must be 'host' or 'device', not %r" % (parse,))
+    return parse == "device"
+
+
+def _load_into(f, path, mode, parse):
+    """the file `path` into the handle f, parsed on the host or on the device: dict(conf (None without a map), timestamp)"""
+    if _check_parse(parse):
+        r = f.load_text(path, mode)
+        return dict(conf=True if r["has_conf"] else None, timestamp=r["timestamp"])
+    d = load_dat(path, f.rows)
+    f.load(d, mode)
+    return d
+
+
+def _conditioned(path, mode, device, parse="host"):
+    if _check_parse(parse):                                   # a d1_%04d.dat frame (the handle's size is fixed before the text is seen)
+        f = SrFrame(ROWS, COLS, device)
+        try:
+            return _load_into(f, path, mode, parse), f
+        except Exception:
+            f.close()
+            raise
     d = load_dat(path)
     f = SrFrame(d["z"].shape[0], d["z"].shape[1], device).load(d, mode)
     return d, f
 
 
-def read_xyz_sr4000(path, with_timestamp=False, device=0):
-    """[x, y, z, confidence_map (, timestamp)] = read_xyz_sr4000(...) on the file `path`; confidence_map is None for a frame without one"""
-    d, f = _conditioned(path, MODE_XYZ, device)
+def read_xyz_sr4000(path, with_timestamp=False, device=0, parse="host"):
+    """[x, y, z, confidence_map (, timestamp)] = read_xyz_sr4000(...) on the file `path`; confidence_map is None for a frame without one.
+    parse="device": the text is parsed on the device (a 144 x 176 frame)."""
+    d, f = _conditioned(path, MODE_XYZ, device, parse)
     with f:
         out = f.planes()
     return out + (d["timestamp"],) if with_timestamp else out
 
 
-def read_image_sr4000(path, device=0):
+def read_image_sr4000(path, device=0, parse="host"):
     """im = read_image_sr4000(...) on the file `path`: uint8"""
-    d, f = _conditioned(path, MODE_XYZ, device)
+    d, f = _conditioned(path, MODE_XYZ, device, parse)
     with f:
         return f.image()
 
 
-def read_sr4000_data_dr_ye(path, with_timestamp=False, device=0):
+def read_sr4000_data_dr_ye(path, with_timestamp=False, device=0, parse="host"):
     """[x, y, z, confidence_map, img1 (, timestamp)] = read_sr4000_data_dr_ye(path).  Deviation: a frame without confidence rows gets the same
     normalised image as one with them (the reference leaves it un-normalised, :34-59)."""
-    d, f = _conditioned(path, MODE_DR_YE, device)
+    d, f = _conditioned(path, MODE_DR_YE, device, parse)
     with f:
         out = f.planes() + (f.image(),)
     return out + (d["timestamp"],) if with_timestamp else out
@@ -345,17 +429,33 @@ def _two_frames(d1, d2, device, frames):
     return own, f1, f2
 
 
-def vodometry_frames(dat1, dat2, seed, seq=0, thresh=1.5, device=0, frames=None):
+def _two_frames_for(dat1, dat2, device, frames, parse):
+    """(own, f1, f2, d1, d2): the pair of handles and, for the host parse, the two files' planes (None for the device parse: _load_into reads them)"""
+    if _check_parse(parse):
+        own = frames is None
+        f1, f2 = (SrFrame(ROWS, COLS, device), SrFrame(ROWS, COLS, device)) if own else frames
+        return own, f1, f2, None, None
+    d1, d2 = load_dat(dat1), load_dat(dat2)
+    return _two_frames(d1, d2, device, frames) + (d1, d2)
+
+
+def _load_pair_member(f, path, d, mode, parse):
+    if d is None:
+        return _load_into(f, path, mode, parse)
+    f.load(d, mode)
+    return d
+
+
+def vodometry_frames(dat1, dat2, seed, seq=0, thresh=1.5, device=0, frames=None, parse="host"):
     """vodometry_dr_ye with the SIFT sets made on the device: each file is conditioned in mode 1, SrFrame.sift runs on its filtered image, gate 1 (gate 0
     on a frame without confidence rows) drops keypoints, then vo.vo_pair_seeded.  The gated set is 1-based, as vodometry_dr_ye.m:73-74,120-122 make
-    it before confidence_filtering."""
+    it before confidence_filtering.  parse="device": the two texts are parsed on the device too (SrFrame.load_text)."""
     from . import vo
-    d1, d2 = load_dat(dat1), load_dat(dat2)
-    own, f1, f2 = _two_frames(d1, d2, device, frames)
+    own, f1, f2, d1, d2 = _two_frames_for(dat1, dat2, device, frames, parse)
     try:
         kept = []
-        for f, d in ((f1, d1), (f2, d2)):
-            f.load(d, MODE_DR_YE)
+        for f, path, d in ((f1, dat1, d1), (f2, dat2, d2)):
+            d = _load_pair_member(f, path, d, MODE_DR_YE, parse)
             f.sift(want_arrays=False)
             kept.append(f.gate(GATE_CONFIDENCE if d["conf"] is not None else GATE_DEPTH)["keep_idx"])
         out = vo.vo_pair_seeded(f1, f2, seed, seq, thresh)
@@ -366,15 +466,14 @@ def vodometry_frames(dat1, dat2, seed, seq=0, thresh=1.5, device=0, frames=None)
     return out
 
 
-def initialize_features_scans(filt, step, dat_prev, dat_cur, seed, seq=0, thresh=1.5, mode=MODE_XYZ, device=0, frames=None, **policy):
+def initialize_features_scans(filt, step, dat_prev, dat_cur, seed, seq=0, thresh=1.5, mode=MODE_XYZ, device=0, frames=None, parse="host", **policy):
     """initialize_features_frames with the SIFT sets made on the device (SrFrame.sift on each conditioned scan, then the depth gate); cand_idx indexes the
-    previous scan's raw set"""
-    d1, d2 = load_dat(dat_prev), load_dat(dat_cur)
-    own, f1, f2 = _two_frames(d1, d2, device, frames)
+    previous scan's raw set.  parse="device": the two texts are parsed on the device too."""
+    own, f1, f2, d1, d2 = _two_frames_for(dat_prev, dat_cur, device, frames, parse)
     try:
         kept = []
-        for f, d in ((f1, d1), (f2, d2)):
-            f.load(d, mode)
+        for f, path, d in ((f1, dat_prev, d1), (f2, dat_cur, d2)):
+            _load_pair_member(f, path, d, mode, parse)
             f.sift(want_arrays=False)
             kept.append(f.gate(GATE_DEPTH)["keep_idx"])
         out = filt.map_management_policy_frames_seeded(step, f1, f2, seed, seq, thresh, **policy)

@@ -543,6 +543,30 @@ PRE3_API int pre3_sr_frame_load(pre3_sr_frame *f, int mode, const double *z, con
  * conf != NULL on a frame loaded without one: PRE3_E_ARG. */
 PRE3_API int pre3_sr_frame_get(pre3_sr_frame *f, double *x, double *y, double *z, double *img, double *conf,
                                double *imax, double *cmax);
+/* ---- The .dat text of a frame parsed on the device (read_xyz_sr4000.m:2-3,25-42: load() of d1_%04d.dat).
+ * Grammar -- what MATLAB's load and numpy.loadtxt both accept for these files, nothing more: space, tab and \r separate; a row ends at \n or at the
+ * end of the text; a line without a token is skipped; a token is [+-]?digits[.digits*]?([eE][+-]?digits)?, [+-]?.digits with the same exponent,
+ * [+-]?inf or [+-]?nan in any letter case.  Anything else -- d/D exponents, % or # comments, commas, a NUL byte, a lone sign or dot -- is a bad token.
+ * Every double equals strtod's / Python float()'s bit for bit (correctly rounded, ties to even, signed zeros); a token the conversion cannot decide
+ * exactly is never stored as a guess: it fails the call.
+ * status: 0 ok, 1 bad token, 2 ragged rows, 3 wrong shape for this handle (or more tokens than the handle holds), 4 undecided token, 5 negative or
+ * non-finite amplitude, 6 empty text; checked in the order 6, 2, 1, 4, 3, 5.  Any non-zero status returns PRE3_E_ARG with info filled.  rows, cols:
+ * the non-empty lines and the token count of the first.  bad_row, bad_col (0-based), bad_offset (bytes): the bad token; for ragged rows the first row
+ * whose token count differs, min(its count, cols), and the offset of its first extra token or of the next row's first token (nbytes when none). */
+typedef struct { int32_t status, rows, cols, has_conf, has_timestamp, n_tokens, n_undecided, bad_row, bad_col;
+                 int64_t bad_offset; double timestamp; } pre3_sr_text_info;
+/* the chunk of the byte passes and the longest text the calls below take.  Host only: needs no device. */
+PRE3_API int pre3_sr_text_limits(int32_t *chunk_bytes, int64_t *max_bytes);
+/* MATLAB's load for any rectangular ASCII matrix: out[rows x cols], column-major, cap doubles of room.  Stateless, on the library's per-device
+ * scratch; synchronises.  out is written on success only.  More than cap tokens: PRE3_E_NOMEM with info->rows, cols, n_tokens filled. */
+PRE3_API int pre3_sr_text_parse(int device, const char *text, size_t nbytes, double *out /* column-major */, size_t cap,
+                                pre3_sr_text_info *info);
+/* pre3_sr_frame_load from the file's bytes: exactly 4 rows, 5 rows or 5 rows + 1 lines of cols tokens (read_xyz_sr4000.m:25-42: z, x, y, amplitude,
+ * then the confidence map, then the timestamp in the last line's first entry).  One copy of the bytes through the handle's pinned staging, the three
+ * parse launches into a spare plane block, ONE wait on the pinned status (has_conf, the timestamp, and whether the file is taken at all), then -- on
+ * success only -- the spare block becomes the frame and the maxima and conditioning launches of pre3_sr_frame_load are queued; returns without a
+ * second wait.  On any failure the previous frame, its keypoint record and the handle's state are untouched. */
+PRE3_API int pre3_sr_frame_load_text(pre3_sr_frame *f, int mode, const char *text, size_t nbytes, pre3_sr_text_info *info);
 /* The keypoint stage on the resident frame.  frm[K][ldf]: one SIFT frame per keypoint (a column of SCALE_ORIENT_POS_RAW), entry 0 the pixel column,
  * entry 1 the pixel row, both 1-based; the pixel is (round(row), round(column)), MATLAB rounding.  des[K][ND]: its descriptor (ND = 128 in the
  * reference; ND == 0: none).

@@ -18,6 +18,7 @@
  *   map_management.m:27-79          [del, acc] = pre3_mex('map_policy', step, UV, XYZ, DESC, 50, 0.1, std_z, 1)   % policy on the device; pre3_mex('set_book', B) first
  *   Weighted_Smpl_wo_replacement.m  [del, acc, cv, st, order] = pre3_mex('map_policy_seeded', step, UV, XYZ, DESC, 50, 0.1, std_z, 1, [176 144], seed, step)   % ... and its draw
  *   read_xyz_sr4000.m, read_image_sr4000.m, read_sr4000_data_dr_ye.m   [x, y, z, img, imax, cmax] = pre3_mex('sr_frame', mode, z, x, y, amp, conf)   % conf = [] for none; the frame stays resident
+ *   read_xyz_sr4000.m:2-3,25-42 (load of d1_%04d.dat)                  info = pre3_mex('sr_frame_text', mode, fileread(name))                               % the text parsed on the device; the frame stays resident
  *   SIFT_extract_save.m:71-88, confidence_filtering.m                  [frm, des, idx, xyz, rho] = pre3_mex('sr_keypoints', gate, frames, descriptors)    % on the resident frame; no filter context needed
  *   sift_vedal.m:127-323, SIFT_extract_save.m:44-88                    [frames, descriptors, counts] = pre3_mex('sr_sift'); [frm, des, idx, xyz, rho] = pre3_mex('sr_gate', gate)   % the SIFT set made on the device
  *   vodometry_dr_ye.m:139-236, Calculate_V_Omega_RANSAC_dr_ye.m:41-50  pre3_mex('sr_keep'); ... next frame's 'sr_frame' + 'sr_keypoints' (gate 1) ...; [T, q, R, sta, match, stat] = pre3_mex('vo_pair', seed, seq)
@@ -75,6 +76,38 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         for (i = 0; i < 4; ++i) out[i] = mxCreateDoubleMatrix(rows, cols, mxREAL);
         check(pre3_sr_frame_get(g_sr, mxGetPr(out[0]), mxGetPr(out[1]), mxGetPr(out[2]), mxGetPr(out[3]), NULL, &imax, &cmax));
         out[4] = mxCreateDoubleScalar(imax); out[5] = mxCreateDoubleScalar(cmax);
+        (void)nout;
+        return;
+    }
+    if (!strcmp(cmd, "sr_frame_text")) {     /* info = pre3_mex('sr_frame_text', mode, text (char or uint8) [, rows = 144, cols = 176]): the text of a .dat frame parsed and
+                                                 conditioned on the device (pre3_sr_frame_load_text); the frame stays resident as after 'sr_frame'.  info: the fields of
+                                                 pre3_sr_text_info; a refused text (info.status ~= 0) leaves the resident frame as it was and is no MATLAB error */
+        const char *fn[11] = { "status", "rows", "cols", "has_conf", "has_timestamp", "n_tokens", "n_undecided", "bad_row", "bad_col", "bad_offset", "timestamp" };
+        pre3_sr_text_info ti; int rows, cols, rc, is_char; size_t n, i; char *buf = NULL; const char *text; double v[11];
+        if (nin != 3 && nin != 5) mexErrMsgTxt("pre3_mex('sr_frame_text', mode, text [, rows, cols]): two or four arguments");
+        is_char = mxIsChar(in[2]) ? 1 : 0;
+        if (!is_char && mxGetClassID(in[2]) != mxUINT8_CLASS) mexErrMsgTxt("pre3_mex('sr_frame_text'): text must be a char or a uint8 array");
+        rows = nin == 5 ? (int)mxGetScalar(in[3]) : 144; cols = nin == 5 ? (int)mxGetScalar(in[4]) : 176;
+        if (g_sr && (rows != g_sr_rows || cols != g_sr_cols)) {
+            pre3_sr_frame_destroy(g_sr); g_sr = NULL;
+            if (g_sr_prev) { pre3_sr_frame_destroy(g_sr_prev); g_sr_prev = NULL; }
+        }
+        if (!g_sr) { check(pre3_sr_frame_create(&g_sr, 0, rows, cols)); g_sr_rows = rows; g_sr_cols = cols; mexAtExit(sr_at_exit); if (!mexIsLocked()) mexLock(); }
+        n = mxGetNumberOfElements(in[2]);
+        if (is_char) {                       /* MATLAB's char is 16 bits wide */
+            const unsigned short *c = (const unsigned short *)mxGetData(in[2]);
+            buf = (char *)mxMalloc(n ? n : 1);
+            for (i = 0; i < n; ++i) buf[i] = c[i] < 256 ? (char)c[i] : '?';
+            text = buf;
+        } else text = (const char *)mxGetData(in[2]);
+        memset(&ti, 0, sizeof ti);
+        rc = pre3_sr_frame_load_text(g_sr, (int)mxGetScalar(in[1]), text, n, &ti);
+        if (buf) mxFree(buf);
+        if (rc != PRE3_OK && ti.status == 0) check(rc);
+        v[0] = ti.status; v[1] = ti.rows; v[2] = ti.cols; v[3] = ti.has_conf; v[4] = ti.has_timestamp; v[5] = ti.n_tokens; v[6] = ti.n_undecided;
+        v[7] = ti.bad_row; v[8] = ti.bad_col; v[9] = (double)ti.bad_offset; v[10] = ti.timestamp;
+        out[0] = mxCreateStructMatrix(1, 1, 11, fn);
+        for (i = 0; i < 11; ++i) mxSetField(out[0], 0, fn[i], mxCreateDoubleScalar(v[i]));
         (void)nout;
         return;
     }
