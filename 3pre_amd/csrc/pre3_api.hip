@@ -408,7 +408,7 @@ int pre3_create(pre3_ctx **out, int device, int dtype, int max_landmarks, int ma
     A(dmalloc(&c->support, (size_t)c->caph + 4 + (size_t)c->caph * c->mask_words_cap));
     if (rc == PRE3_OK) c->masks = reinterpret_cast<uint32_t *>(c->support + c->caph + 4);
     A(dmalloc(&c->stats, 16));
-    A(dmalloc(&c->pred_params, 128));
+    A(dmalloc(&c->pred_params, 192));
     {
         // K9 tile schedule: upper-triangle 64x64 tiles in 4x4 super-tile order, so that the tiles in flight at
         // any moment (tickets are handed out in this order) share W panels in L2 / Infinity Cache.
@@ -769,6 +769,38 @@ int pre3_predict(pre3_ctx *c, const double u[7])
     PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "pre3_predict: needs (x_k_k, p_k_k) on the device");
     PRE3_TRY(launch_predict_impl(c, u));
     c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
+    return PRE3_OK;
+}
+
+// predict_state_and_covariance.m:98-102,115: the Pn every prediction of this context takes.  A setting, not a step: deferred and
+// pending work is left where it is (no EntryScope), and the block changes in stream order behind the predictions already queued.
+int pre3_set_process_noise(pre3_ctx *c, const double *Pn)
+{
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "pre3_set_process_noise: null context");
+    if (Pn == nullptr) { c->pn_set = false; return PRE3_OK; }
+    for (int i = 0; i < 49; ++i) PRE3_CHECK(std::isfinite(Pn[i]), PRE3_E_ARG, "pre3_set_process_noise: Pn[%d] is not finite", i);
+    for (int i = 0; i < 7; ++i) {
+        PRE3_CHECK(Pn[8 * i] >= 0, PRE3_E_ARG, "pre3_set_process_noise: the diagonal entry %d is negative", i);
+        for (int j = 0; j < i; ++j) PRE3_CHECK(Pn[7 * i + j] == Pn[7 * j + i], PRE3_E_ARG, "pre3_set_process_noise: Pn(%d,%d) != Pn(%d,%d)", i, j, j, i);
+    }
+    PRE3_HIP(hipSetDevice(c->device));
+    PRE3_TRY(launch_set_pn(c, Pn));
+    memcpy(c->pn_host, Pn, sizeof c->pn_host);
+    c->pn_set = true;
+    return PRE3_OK;
+}
+
+int pre3_get_process_noise(pre3_ctx *c, double *Pn_out, int *source_out)
+{
+    PRE3_CHECK(c != nullptr && (Pn_out != nullptr || source_out != nullptr), PRE3_E_ARG, "pre3_get_process_noise: null argument");
+    if (source_out) *source_out = c->pn_set ? 1 : 0;
+    if (Pn_out == nullptr) return PRE3_OK;
+    if (c->pn_set) { memcpy(Pn_out, c->pn_host, sizeof c->pn_host); return PRE3_OK; }
+    // the constant as the prediction's launch builds it: written into the (unused while nothing is set) block on the context's stream and read back
+    PRE3_HIP(hipSetDevice(c->device));
+    PRE3_TRY(launch_get_pn_const(c, c->pred_params + PRED_PN_OFF));
+    PRE3_HIP(hipMemcpyAsync(Pn_out, c->pred_params + PRED_PN_OFF, sizeof(double) * 49, hipMemcpyDeviceToHost, c->stream));
+    PRE3_TRY(stream_drain(c, "pre3_get_process_noise"));
     return PRE3_OK;
 }
 

@@ -18,6 +18,8 @@
 #include "pre3_vodev.h"
 #include "pre3_vopair.h"
 #include "pre3_predictu.h"
+#include "pre3_vocov.h"
+#include <type_traits>
 
 namespace pre3 {
 
@@ -62,9 +64,19 @@ __device__ __forceinline__ const U7 &predict_u(const PredictUDev &s, U7 &ud)
     if (refusal != PU_OK && blockIdx.x == 0) atomicCAS(s.err, 0, pu_error_word(refusal));
     return ud;
 }
-template <typename T, typename US = U7>
+// The process noise Pn (NS), in block 0: a null source is the constant, rebuilt by lane 0 (PnConst: always -- the text every launch
+// ran before there was a choice); otherwise 49 lanes of the second wave copy the block -- the context's (PnBlock), or, PnPair, the covariance k_vo_cov left
+// behind the pair when the status rule takes it (vc_predict_takes, pre3_vocov.h) with the context's block or the constant behind it.  Those words were
+// written by earlier launches.  Everything behind the load of Pn, the summation order of G Pn G' included, is one text for the three forms.
+__device__ __forceinline__ const double *predict_pn_src(const PnConst &) { return nullptr; }
+__device__ __forceinline__ const double *predict_pn_src(const PnBlock &s) { return s.pn; }
+__device__ __forceinline__ const double *predict_pn_src(const PnPair &s)
+{
+    return vc_predict_takes(s.out->sta, s.hdr->pnum, s.hdr->bad, s.out->dist_ok, s.cov->status) ? s.cov->cov : s.behind;
+}
+template <typename T, typename US = U7, typename NS = PnConst>
 __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in, double *x_out, T *__restrict__ P, int n, int ld, US u,
-                                                 double *__restrict__ params, int n_pred_blocks, ProjRide pr, InboxRide ib, int fuse_jn, PendW pw = PendW{})
+                                                 double *__restrict__ params, int n_pred_blocks, ProjRide pr, InboxRide ib, int fuse_jn, PendW pw = PendW{}, NS ns = NS{})
 {
     if ((int)blockIdx.x >= n_pred_blocks + pr.n_blocks) { inbox_pull_block(ib); return; }               // the step's inbox crosses PCIe beside the prediction
     if ((int)blockIdx.x >= n_pred_blocks) { proj_ride_block(pr, blockIdx.x - n_pred_blocks); return; }   // IC-search projection rides along
@@ -73,6 +85,9 @@ __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in
     // fuse_jn: the previous update's rows/cols 3..6 <- Jn pass (update.m:42-46, k_jnorm_P) is applied here first, value for value as
     // that kernel would have stored it (rounded to T), so the launch in front of this one is saved (pre3_step with PRE3_OPT_DEFER_HI)
     if (fuse_jn && threadIdx.x >= 64 && threadIdx.x < 80) sJu[threadIdx.x - 64] = params[96 + threadIdx.x - 64];
+    if constexpr (!std::is_same<NS, PnConst>::value) {
+        if (blockIdx.x == 0 && threadIdx.x >= 64 && threadIdx.x < 64 + 49) { const double *src = predict_pn_src(ns); if (src != nullptr) sPn[threadIdx.x - 64] = src[threadIdx.x - 64]; }
+    }
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     // landmarks copied (predict_state_and_covariance.m:79)
     for (int i = 13 + j; i < n; i += n_pred_blocks * blockDim.x) x_out[i] = x_in[i];
@@ -108,8 +123,10 @@ __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in
             for (int i = 0; i < 49; ++i) sG[i] = 0;
             for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) sG[i * 7 + k] = R[i * 3 + k];
             for (int i = 0; i < 4; ++i) for (int k = 0; k < 4; ++k) sG[(3 + i) * 7 + 3 + k] = Qq2[i * 4 + k];
-            d_process_noise(Pn);
-            for (int i = 0; i < 49; ++i) sPn[i] = Pn[i];
+            if (predict_pn_src(ns) == nullptr) {
+                d_process_noise(Pn);
+                for (int i = 0; i < 49; ++i) sPn[i] = Pn[i];
+            }
             for (int i = 0; i < 16; ++i) { params[i] = Qq1[i]; params[16 + i] = Jn[i]; }
         }
     }
@@ -1103,19 +1120,30 @@ ProjRide make_proj_ride(pre3_ctx *c, int which, int clear_first, int slot, int n
 // with_projection: the IC-search projection at x_k_km1 (clear_first = 1) rides in the same launch
 // u_dev != nullptr: the increment is chosen on the device from a VO pair's result block (PredictUDev); u is not read.  That form carries neither riders
 // nor an inbox pull -- ProjRide::u is by value, and pre3_predict_pair_seeded asks for neither.
-int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection, size_t inbox_n16, int32_t inbox_seq, const PredictUDev *u_dev)
+// The process noise: the constant on a context on which nothing is set -- the instantiations every launch used before there was a
+// choice --, the context's block once pre3_set_process_noise has filled it, and, pn_pair != nullptr (with u_dev only), the pair's covariance with either behind it.
+template <typename US, typename NS>
+static void predict_launch(pre3_ctx *c, int nb, const US &u, const NS &ns, int blocks, const ProjRide &pr, const InboxRide &ib, int fuse_jn)
 {
+    DISPATCH_T(c,
+        hipLaunchKernelGGL((k_predict<double, US, NS>), dim3(nb), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (double *)c->P, c->n, c->ld, u, c->pred_params, blocks, pr, ib, fuse_jn, PendW{}, ns),
+        hipLaunchKernelGGL((k_predict<float, US, NS>), dim3(nb), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (float *)c->P, c->n, c->ld, u, c->pred_params, blocks, pr, ib, fuse_jn, pend_args(c), ns));
+}
+int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection, size_t inbox_n16, int32_t inbox_seq, const PredictUDev *u_dev, const PnPair *pn_pair)
+{
+    const PnBlock own{ c->pred_params + PRED_PN_OFF };
     if (u_dev != nullptr) {
         PRE3_CHECK(!with_projection && inbox_n16 == 0, PRE3_E_STATE, "launch_predict_impl: the device form of u carries no riders");
         const int blocks = ceil_div(c->n, 256);
         const int fuse_jn = c->carry.jn_pending ? 1 : 0;
-        DISPATCH_T(c,
-            hipLaunchKernelGGL((k_predict<double, PredictUDev>), dim3(blocks), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (double *)c->P, c->n, c->ld, *u_dev, c->pred_params, blocks, ProjRide{}, InboxRide{}, fuse_jn, PendW{}),
-            hipLaunchKernelGGL((k_predict<float, PredictUDev>), dim3(blocks), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (float *)c->P, c->n, c->ld, *u_dev, c->pred_params, blocks, ProjRide{}, InboxRide{}, fuse_jn, pend_args(c)));
+        if (pn_pair != nullptr) { PnPair pp = *pn_pair; pp.behind = c->pn_set ? own.pn : nullptr; predict_launch(c, blocks, *u_dev, pp, blocks, ProjRide{}, InboxRide{}, fuse_jn); }
+        else if (c->pn_set) predict_launch(c, blocks, *u_dev, own, blocks, ProjRide{}, InboxRide{}, fuse_jn);
+        else predict_launch(c, blocks, *u_dev, PnConst{}, blocks, ProjRide{}, InboxRide{}, fuse_jn);
         PRE3_HIP(hipGetLastError());
         c->carry.jn_pending = false;
         return PRE3_OK;
     }
+    PRE3_CHECK(pn_pair == nullptr, PRE3_E_STATE, "launch_predict_impl: a pair's covariance comes with the pair's increment");
     U7 uu; for (int i = 0; i < 7; ++i) uu.v[i] = u[i];
     int blocks = ceil_div(c->n, 256);
     ProjRide pr{};
@@ -1127,11 +1155,30 @@ int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection, si
     InboxRide ib{ (const int4 *)c->inbox_host_dev, (int4 *)c->inbox_dev, (int)inbox_n16, c->mail_dev, inbox_seq };     // one more block when inbox_n16 > 0
     const int nb = blocks + pr.n_blocks + (inbox_n16 ? 1 : 0);
     const int fuse_jn = c->carry.jn_pending ? 1 : 0;          // the pending update.m:42-46 pass of the update in front (run_update left it to this launch)
-    DISPATCH_T(c,
-        hipLaunchKernelGGL(k_predict<double>, dim3(nb), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (double *)c->P, c->n, c->ld, uu, c->pred_params, blocks, pr, ib, fuse_jn, PendW{}),
-        hipLaunchKernelGGL(k_predict<float>, dim3(nb), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (float *)c->P, c->n, c->ld, uu, c->pred_params, blocks, pr, ib, fuse_jn, pend_args(c)));
+    if (c->pn_set) predict_launch(c, nb, uu, own, blocks, pr, ib, fuse_jn);
+    else predict_launch(c, nb, uu, PnConst{}, blocks, pr, ib, fuse_jn);
     PRE3_HIP(hipGetLastError());
     c->carry.jn_pending = false;
+    return PRE3_OK;
+}
+
+// pre3_set_process_noise: the 49 doubles travel as a launch argument, so the block changes in stream order -- behind every prediction queued before
+// the call -- and no host buffer has to outlive it
+struct Pn49 { double v[49]; };
+__global__ void k_set_pn(Pn49 pn, double *__restrict__ dst) { if (threadIdx.x < 49) dst[threadIdx.x] = pn.v[threadIdx.x]; }
+int launch_set_pn(pre3_ctx *c, const double *Pn)
+{
+    Pn49 a; for (int i = 0; i < 49; ++i) a.v[i] = Pn[i];
+    hipLaunchKernelGGL(k_set_pn, dim3(1), dim3(64), 0, c->stream, a, c->pred_params + PRED_PN_OFF);
+    PRE3_HIP(hipGetLastError());
+    return PRE3_OK;
+}
+// the constant as k_predict builds it, for pre3_get_process_noise: one wave writes it to dst
+__global__ void k_get_pn_const(double *__restrict__ dst) { if (threadIdx.x == 0) d_process_noise(dst); }
+int launch_get_pn_const(pre3_ctx *c, double *dst_dev)
+{
+    hipLaunchKernelGGL(k_get_pn_const, dim3(1), dim3(64), 0, c->stream, dst_dev);
+    PRE3_HIP(hipGetLastError());
     return PRE3_OK;
 }
 

@@ -11,6 +11,13 @@ struct U7 { double v[7]; };
 // launches left in front of the prediction (pre3_vodev.h, pre3_vopair.h), and the context's numeric error word for a pair that is refused
 struct VoOut; struct VoPairHeader;
 struct PredictUDev { const VoOut *out; const VoPairHeader *hdr; int32_t *err; };
+// k_predict's process noise Pn: the constant of predict_state_and_covariance.m:98-102 rebuilt in the launch (PnConst: every
+// prediction of a context on which nothing is set), the context's 49-double block (PnBlock: pre3_set_process_noise), or the covariance k_vo_cov left
+// behind the VO pair in front of this launch (PnPair: taken under the status rule of pre3_vocov.h, else `behind` -- the context's block, or null: the constant)
+struct VoCov;
+struct PnConst {};
+struct PnBlock { const double *pn; };
+struct PnPair { const VoCov *cov; const VoOut *out; const VoPairHeader *hdr; const double *behind; };
 
 // ------------------------------------------------------------------------------------------------
 // device math (fp64)

@@ -178,7 +178,8 @@ struct pre3_ctx {
     int scored_n_draw = 0, scored_k = 0;          // the round pre3_ransac_score / pre3_ransac laid the support + mask buffer out for
     int32_t *stats = nullptr;                     // [16] device: best, iters, n_hyp, max_support, n_li, n_hi, status
     int32_t *li_meas = nullptr, *hi_meas = nullptr;   // [capm] flags in measurement order
-    double *pred_params = nullptr;                // [64] predict: Qq1(16) Jn(16) Q(49->7x7) etc.
+    double *pred_params = nullptr;                // [192] predict: Qq1(16) Jn(16) Q(49->7x7) etc.; [128 .. 176] the process noise block
+    bool pn_set = false; double pn_host[49] = {};  // pre3_set_process_noise: the caller's Pn is in force (pre3_set_state does not reset it); its host copy
     int32_t *pinned_stats = nullptr;              // host pinned [16]
     // mailbox: pinned, host-coherent; the selection and HI-collection stages store their counts here and bump a
     // sequence word, so the host learns r for the next launches by polling instead of a copy + stream sync
@@ -360,9 +361,15 @@ struct IcMatchRide;
 int launch_project_innovation(pre3_ctx *c, int which, int clear_first, int mode, double chi2, bool collect = true, bool clear_ic = false, const IcMatchRide *ride = nullptr);
 int launch_update_x(pre3_ctx *c, int which_prior, int r);
 int launch_jnorm(pre3_ctx *c, int which);
-struct PredictUDev;
+struct PredictUDev; struct PnPair;
 int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection = false, size_t inbox_n16 = 0, int32_t inbox_seq = 0,
-                        const PredictUDev *u_dev = nullptr /* the increment from a VO pair's device result block (pre3_geomdev.h); u unused */);
+                        const PredictUDev *u_dev = nullptr /* the increment from a VO pair's device result block (pre3_geomdev.h); u unused */,
+                        const PnPair *pn_pair = nullptr /* with u_dev: the pair's covariance as Pn under the status rule (pre3_vocov.h); its `behind` is filled here */);
+constexpr int PRED_PN_OFF = 128;         /* pred_params[128 .. 176]: the context's process noise block (pre3_set_process_noise) */
+int launch_set_pn(pre3_ctx *c, const double *Pn);
+int launch_get_pn_const(pre3_ctx *c, double *dst_dev);      /* d_process_noise's 49 doubles into device memory, on the context's stream */
+struct VoOut; struct VoPairHeader; struct VoCov;
+int launch_vo_cov_pair(const VoPairHeader *hdr, const VoOut *out, int cap, const double *pset1, const double *pset2, const int32_t *inl, VoCov *cov, hipStream_t st);
 // (either direction: 16-byte words between device memory and a mapped pinned block, then `seq` into mailbox word `slot`)
 int launch_inbox_pull(pre3_ctx *c, const void *src_host_mapped, void *dst_dev, size_t n16, int32_t seq, int slot = 10, int32_t *clear = nullptr, int n_clear = 0);
 int launch_slice_prepare(pre3_ctx *c, const void *src_host_mapped, size_t n16, int32_t seq, int n_zero, int k, int lo, int hi, int tag);

@@ -22,6 +22,7 @@
 #include "pre3_vodev.h"
 #include "pre3_vopair.h"
 #include "pre3_predictu.h"
+#include "pre3_vocov.h"
 
 namespace pre3 {
 
@@ -150,6 +151,7 @@ namespace {
 struct VpPair {
     SrFrameView v1, v2; SrKeypointView k1, k2;
     size_t o_out, o_match, o_p1, o_p2, o_draws, o_cnum, o_state, o_inl, o_end;
+    bool with_cov = false; size_t o_cov = 0;        // the *_cov_* entry points: a VoCov block behind the result block, k_vo_cov behind k_vp_final
     char *d = nullptr, *pin = nullptr;              // cur's device work block and its pinned image
 };
 bool vp_empty(const VpPair &p) { return p.k1.n_kept == 0 || p.k2.n_kept == 0; }
@@ -161,13 +163,14 @@ int vp_queue(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t se
     const SrKeypointView &k1 = q->k1, &k2 = q->k2;
     const int n1 = k1.n_kept, n2 = k2.n_kept;
     const int wcap = ceil_div(n1, 64);
-    const size_t o_out = sizeof(VoPairHeader), o_match = up16(o_out + sizeof(VoOut)), o_p1 = o_match + up16(sizeof(double) * 2 * (size_t)n1);
+    const size_t o_out = sizeof(VoPairHeader), o_cov = up16(o_out + sizeof(VoOut)), o_match = q->with_cov ? up16(o_cov + sizeof(VoCov)) : o_cov;
+    const size_t o_p1 = o_match + up16(sizeof(double) * 2 * (size_t)n1);
     const size_t o_p2 = o_p1 + up16(sizeof(double) * 3 * (size_t)n1), o_draws = o_p2 + up16(sizeof(double) * 3 * (size_t)n1);
     const size_t o_cnum = o_draws + up16(sizeof(int32_t) * 4 * VO_RST_CAP), o_state = o_cnum + up16(sizeof(int32_t) * VO_RST_CAP);
     const size_t o_inl = o_state + up16(sizeof(int32_t) * VO_RST_CAP), o_end = o_inl + up16(sizeof(int32_t) * (size_t)n1);
     const size_t o_part = o_end, o_masks = o_part + vp_match_part_bytes(n1, n2), total = o_masks + sizeof(unsigned long long) * (size_t)VO_RST_CAP * wcap;
     q->o_out = o_out; q->o_match = o_match; q->o_p1 = o_p1; q->o_p2 = o_p2; q->o_draws = o_draws; q->o_cnum = o_cnum; q->o_state = o_state;
-    q->o_inl = o_inl; q->o_end = o_end;
+    q->o_inl = o_inl; q->o_end = o_end; q->o_cov = o_cov;
     char *d = nullptr;
     PRE3_TRY(sr_frame_pair_work(cur, total, o_end, (void **)&d, (void **)&q->pin));
     q->d = d;
@@ -190,6 +193,8 @@ int vp_queue(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t se
     hipLaunchKernelGGL(k_vp_final, dim3(1), dim3(64), 0, st, (const VoPairHeader *)hdr, (const double *)p1, (const double *)p2, (const int32_t *)cnum,
                        (const unsigned long long *)masks, out, inl);
     PRE3_HIP(hipGetLastError());
+    // (the memset above left status = 0 in the block; pset1, pset2 and inl hold n1 positions, which bounds the launch whatever the header says)
+    if (q->with_cov) PRE3_TRY(launch_vo_cov_pair(hdr, out, n1, p1, p2, inl, (VoCov *)(d + o_cov), st));
     return PRE3_OK;
 }
 
@@ -212,19 +217,26 @@ int vp_refuse_near(const VoOut &o)
     PRE3_CHECK(o.dist_ok, PRE3_E_NUMERIC, "vo: no matched point is farther than 0.4 m from the camera (ransac_dr_ye.m:21 has no minimum there)");
     return PRE3_OK;
 }
-}  // namespace
 
-extern "C" {
-
-int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out, double *match_out,
-                        double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out, int32_t *state_out,
-                        int32_t *inlier_out, pre3_vo_result *res)
+// the pair's covariance block as the ABI hands it out: cov on status 1 only
+void vp_cov_out(const VpPair &p, double *cov_out, int32_t *cov_status_out)
 {
-    const char *who = "pre3_vo_pair_seeded";
+    const VoCov *cv = (const VoCov *)(p.pin + p.o_cov);
+    if (cov_status_out) *cov_status_out = cv->status;
+    if (cov_out && cv->status == VC_VALID) memcpy(cov_out, cv->cov, sizeof cv->cov);
+}
+
+// pre3_vo_pair_seeded, and -- with_cov -- pre3_vo_pair_cov_seeded: the same launches, transfer and checks, k_vo_cov and its block besides
+int vo_pair_impl(const char *who, bool with_cov, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out, double *match_out,
+                 double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out, int32_t *state_out,
+                 int32_t *inlier_out, pre3_vo_result *res, double *cov_out, int32_t *cov_status_out)
+{
     VpPair p;
+    p.with_cov = with_cov;
     PRE3_TRY(sr_frame_pair_views(who, prev, cur, thresh, &p.v1, &p.v2, &p.k1, &p.k2));
     PRE3_TRY(select_device(who, p.v2.device));
     if (pnum_out) *pnum_out = 0;
+    if (cov_status_out) *cov_status_out = VC_NOT_COMPUTED;
     if (vp_empty(p)) { vo_no_solution(res); return PRE3_OK; }      // siftmatch of an empty set: no match, nothing to queue
     PRE3_TRY(vp_queue(prev, cur, thresh, seed, seq, &p));
     size_t need = p.o_match;                    // the prefix of the block the caller's outputs reach into
@@ -248,6 +260,7 @@ int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, 
     if (match_out) memcpy(match_out, pin + p.o_match, sizeof(double) * 2 * (size_t)pnum);
     if (pnum < 4) { vo_no_solution(res); return PRE3_OK; }
     PRE3_TRY(vp_refuse_bad(h));
+    if (with_cov) vp_cov_out(p, cov_out, cov_status_out);
     if (pset1_out) memcpy(pset1_out, pin + p.o_p1, sizeof(double) * 3 * (size_t)pnum);
     if (pset2_out) memcpy(pset2_out, pin + p.o_p2, sizeof(double) * 3 * (size_t)pnum);
     if (draws_out) memcpy(draws_out, pin + p.o_draws, sizeof(int32_t) * 4 * (size_t)rst);
@@ -261,20 +274,22 @@ int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, 
 }
 
 // fv.m:47 + Calculate_V_Omega_RANSAC_dr_ye.m:41-50 + predict_state_and_covariance.m:27-143: the pair's launches on cur's stream,
-// then k_predict on the context's stream with the increment chosen on the device from the pair's result block; u never reaches the host
-int pre3_predict_pair_seeded(pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out,
-                             pre3_vo_result *res_out)
+// then k_predict on the context's stream with the increment chosen on the device from the pair's result block; u never reaches the host.
+// with_cov (pre3_predict_pair_cov_seeded): k_vo_cov behind k_vp_final, and its block is this one prediction's Pn under the status rule
+int predict_pair_impl(const char *who, bool with_cov, pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out,
+                      pre3_vo_result *res_out, double *cov_out, int32_t *cov_status_out)
 {
-    const char *who = "pre3_predict_pair_seeded";
     static const double u_identity[7] = { 0, 0, 0, 1, 0, 0, 0 };
     VpPair p;
+    p.with_cov = with_cov;
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "%s: null context", who);
     PRE3_TRY(sr_frame_pair_views(who, prev, cur, thresh, &p.v1, &p.v2, &p.k1, &p.k2));
     PRE3_CHECK(p.v2.device == c->device, PRE3_E_ARG, "%s: the frames are on device %d, the context on device %d", who, p.v2.device, c->device);
     PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "%s: needs (x_k_k, p_k_k) on the device", who);
     EntryScope scope(c); PRE3_TRY(scope.rc);            // as pre3_predict's
-    const bool wait = pnum_out != nullptr || res_out != nullptr;
+    const bool wait = pnum_out != nullptr || res_out != nullptr || cov_out != nullptr || cov_status_out != nullptr;
     if (pnum_out) *pnum_out = 0;
+    if (cov_status_out) *cov_status_out = VC_NOT_COMPUTED;
     if (vp_empty(p)) {                                  // no pair launches: the ordinary prediction with the identity increment
         PRE3_TRY(launch_predict_impl(c, u_identity));
         c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
@@ -286,7 +301,8 @@ int pre3_predict_pair_seeded(pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cu
     PRE3_TRY(sr_frame_reclaim(prev, st));               // prev is read by the pair's launches only
     PRE3_TRY(sr_frame_lend(cur, c->stream));            // the prediction reads cur's work block behind k_vp_final
     const PredictUDev ud{ (const VoOut *)(p.d + p.o_out), (const VoPairHeader *)p.d, c->stats + 6 };
-    PRE3_TRY(launch_predict_impl(c, nullptr, false, 0, 0, &ud));
+    const PnPair pp{ (const VoCov *)(p.d + p.o_cov), ud.out, ud.hdr, nullptr };
+    PRE3_TRY(launch_predict_impl(c, nullptr, false, 0, 0, &ud, with_cov ? &pp : nullptr));
     c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
     // the next pair call's memset of this work block, a load or a keypoint call on cur stay behind the read of u
     if (wait) PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
@@ -303,8 +319,42 @@ int pre3_predict_pair_seeded(pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cu
     if (h.pnum < 4) { vo_no_solution(res_out); return PRE3_OK; }
     PRE3_TRY(vp_refuse_bad(h));
     PRE3_TRY(vp_refuse_near(o));
+    if (with_cov) vp_cov_out(p, cov_out, cov_status_out);
     if (res_out) vo_result(o, res_out);
     return PRE3_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out, double *match_out,
+                        double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out, int32_t *state_out,
+                        int32_t *inlier_out, pre3_vo_result *res)
+{
+    return vo_pair_impl("pre3_vo_pair_seeded", false, prev, cur, thresh, seed, seq, pnum_out, match_out, pset1_out, pset2_out, draws_out, capped_out, cnum_out, state_out,
+                        inlier_out, res, nullptr, nullptr);
+}
+
+// calc_cov_RANSAC_dr_ye.m:17-30 behind vodometry_dr_ye.m: pre3_vo_pair_seeded with k_vo_cov behind k_vp_final, still one host wait
+int pre3_vo_pair_cov_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out, double *match_out,
+                            double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out, int32_t *state_out,
+                            int32_t *inlier_out, pre3_vo_result *res, double *cov_out, int32_t *cov_status_out)
+{
+    return vo_pair_impl("pre3_vo_pair_cov_seeded", true, prev, cur, thresh, seed, seq, pnum_out, match_out, pset1_out, pset2_out, draws_out, capped_out, cnum_out, state_out,
+                        inlier_out, res, cov_out, cov_status_out);
+}
+
+int pre3_predict_pair_seeded(pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out,
+                             pre3_vo_result *res_out)
+{
+    return predict_pair_impl("pre3_predict_pair_seeded", false, c, prev, cur, thresh, seed, seq, pnum_out, res_out, nullptr, nullptr);
+}
+
+// predict_state_and_covariance.m:115: pre3_predict_pair_seeded with the pair's own covariance as this one prediction's Pn
+int pre3_predict_pair_cov_seeded(pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out,
+                                 pre3_vo_result *res_out, double *cov_out, int32_t *cov_status_out)
+{
+    return predict_pair_impl("pre3_predict_pair_cov_seeded", true, c, prev, cur, thresh, seed, seq, pnum_out, res_out, cov_out, cov_status_out);
 }
 
 }  // extern "C"

@@ -490,6 +490,46 @@ class EkfFilter:
         out["pnum"], out["rst"] = pnum, (vo.vo_rst(pnum) if pnum >= 4 else 0)
         return out
 
+    def ekf_prediction_pair_cov_seeded(self, prev, cur, seed, seq=0, thresh=1.5, wait=True):
+        """ekf_prediction_pair_seeded with the pair's own covariance as this one prediction's process noise (predict_state_and_covariance.m:115,
+        DESIGN.md section 27): vo.vo_pair_cov_seeded's extra launch behind the final fit, and the prediction takes that 7 x 7 block as Pn when its
+        status is 1 and the pair's u is taken (sta == 1) -- else this filter's own noise (set_process_noise, or the constant).  u and Pn stay on the
+        device; the filter's noise setting is unchanged afterwards.  wait=True: one host wait; the dict of ekf_prediction_pair_seeded plus cov_status
+        and cov ((7, 7) on status 1, else None).  wait=False: returns None at once."""
+        from . import vo
+        args = (self._ctx, prev._h, cur._h, float(thresh), int(seed), int(seq))
+        if not wait:
+            check(lib.pre3_predict_pair_cov_seeded(*args, None, None, None, None))
+            return None
+        pnum, res, cov, status = C.c_int32(0), vo.VoResult(), np.zeros((7, 7)), C.c_int32(0)
+        check(lib.pre3_predict_pair_cov_seeded(*args, C.byref(pnum), C.byref(res), dptr(cov), C.byref(status)))
+        pnum = int(pnum.value)
+        out = vo._result(res, None, None, None)
+        for k in ("cnum", "state", "inliers"):
+            del out[k]
+        out["pnum"], out["rst"] = pnum, (vo.vo_rst(pnum) if pnum >= 4 else 0)
+        out["cov_status"] = int(status.value)
+        out["cov"] = cov if out["cov_status"] == 1 else None
+        return out
+
+    def set_process_noise(self, Pn=None):
+        """predict_state_and_covariance.m:98-102: the 7 x 7 process noise Pn of every prediction this filter makes from now on (ekf_prediction, step*,
+        ekf_prediction_pair_seeded); None returns to the reference's constant.  Must be finite, exactly symmetric and without a negative diagonal
+        entry (Pre3Error -1, nothing changed).  set_x_p_k_k does not reset it."""
+        if Pn is None:
+            check(lib.pre3_set_process_noise(self._ctx, None))
+            return
+        Pn = f64(Pn)
+        assert Pn.shape == (7, 7), "Pn is 7 x 7 over [dX(3); dq(4)]"
+        check(lib.pre3_set_process_noise(self._ctx, dptr(Pn)))
+
+    @property
+    def process_noise(self):
+        """(Pn (7, 7), source): the process noise in force and where it comes from -- "constant" (predict_state_and_covariance.m:98-102) or "caller" (set_process_noise)"""
+        Pn, src = np.zeros((7, 7)), C.c_int(0)
+        check(lib.pre3_get_process_noise(self._ctx, dptr(Pn), C.byref(src)))
+        return Pn, ("caller" if src.value else "constant")
+
     def predict_camera_measurements(self, which=_lib.X_K_KM1, clear_first=True):
         """Also computes the Jacobians (calculate_derivatives.m) -- the reference always calls them as a pair."""
         check(lib.pre3_project(self._ctx, int(which), int(bool(clear_first))))

@@ -391,12 +391,25 @@ def ekf_prediction_frames(filt, step, frames, seed, seq=0, thresh=1.5, wait=True
     """fv.m:41-48 + ekf_prediction.m for frame `step` with the scans resident: frames maps a scan number to its SrFrame, each with a keypoint record
     (gate 1, as vodometry_dr_ye).  The first frames are predicted with the identity motion; from then on EkfFilter.ekf_prediction_pair_seeded runs the VO
     front end between frames[step - 2] and frames[step - 1] and the prediction behind it, u staying on the device.  Returns that
-    call's result (None for the identity frames, or with wait=False)."""
+    call's result (None for the identity frames, or with wait=False).  The process noise is the filter's own (the reference's constant, or
+    EkfFilter.set_process_noise); ekf_prediction_frames_cov takes the pair's."""
+    return _prediction_frames(filt, step, frames, seed, seq, thresh, wait, "context")
+
+
+def ekf_prediction_frames_cov(filt, step, frames, seed, seq=0, thresh=1.5, wait=True):
+    """ekf_prediction_frames with the pair's covariance, computed on the device from its inliers, as that prediction's process noise
+    (predict_state_and_covariance.m:115; EkfFilter.ekf_prediction_pair_cov_seeded).  The identity frames, and a pair whose
+    covariance is not valid or whose u is not taken, are predicted with the filter's own noise."""
+    return _prediction_frames(filt, step, frames, seed, seq, thresh, wait, "pair")
+
+
+def _prediction_frames(filt, step, frames, seed, seq, thresh, wait, noise):
     pair = fv_pair(step)
     if pair is None:
         filt.ekf_prediction([0, 0, 0, 1, 0, 0, 0])
         return None
-    return filt.ekf_prediction_pair_seeded(frames[pair[0]], frames[pair[1]], seed, seq, thresh, wait)
+    call = filt.ekf_prediction_pair_cov_seeded if noise == "pair" else filt.ekf_prediction_pair_seeded
+    return call(frames[pair[0]], frames[pair[1]], seed, seq, thresh, wait)
 
 
 def initialize_features_frames(filt, step, dat_prev, dat_cur, sift_prev, sift_cur, seed, seq=0, thresh=1.5, mode=MODE_XYZ, device=0, frames=None, **policy):

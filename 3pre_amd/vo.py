@@ -6,6 +6,8 @@
     vodometry_dr_ye.m:171                -> vo_rst
     vodometry_dr_ye.m:139-236            -> vo_pair_seeded (siftmatch, rst and the RANSAC between two resident SR4000 frames, one call)
     Calculate_V_Omega_RANSAC_dr_ye.m:40-50 -> result["u"] = [T; R2q(R)], the argument of EkfFilter.ekf_prediction
+    aux_code/cov_pose_shift_calc.m       -> cov_pose_shift_calc (the 7 x 7 covariance of [T; q] from the points' range and angle noise)
+    aux_code/calc_cov_RANSAC_dr_ye.m:17-30 -> vo_cov, vo_pair_cov_seeded (the same from a pair's inliers, on the device behind the final fit)
 
 All compute runs in libpre3.so on the GPU; this module marshals numpy arrays and draws random numbers.
 """
@@ -153,14 +155,18 @@ def vo_pair_seeded(prev, cur, seed, seq=0, thresh=1.5):
     siftmatch(des1, des2, thresh), rst = min(700, nchoosek(pnum, 4)) and the seeded RANSAC, all on the device.  The dict of vo_ransac_frames_seeded
     plus match (2, pnum) -- 1-based positions in the KEPT keypoint sets --, pnum and rst.  Fewer than four matches: sta = 4, u the identity, empty
     point sets, tables and inlier list."""
+    return _pair_call(lib.pre3_vo_pair_seeded, prev, cur, seed, seq, thresh)
+
+
+def _pair_call(fn, prev, cur, seed, seq, thresh, *extra):
     n1 = max(int(getattr(prev, "n_kept", 0)), 1)
     pnum, capped = C.c_int32(0), C.c_int32(0)
     match = np.zeros((2, n1), order="F")
     p1, p2 = np.zeros((n1, 3)), np.zeros((n1, 3))
     draws, cnum, state, inl = np.zeros((700, 4), np.int32), np.zeros(700, np.int32), np.zeros(700, np.int32), np.zeros(n1, np.int32)
     res = VoResult()
-    check(lib.pre3_vo_pair_seeded(prev._h, cur._h, float(thresh), int(seed), int(seq), C.byref(pnum), dptr(match), dptr(p1), dptr(p2), dptr(draws),
-                                  C.byref(capped), dptr(cnum), dptr(state), dptr(inl), C.byref(res)))
+    check(fn(prev._h, cur._h, float(thresh), int(seed), int(seq), C.byref(pnum), dptr(match), dptr(p1), dptr(p2), dptr(draws),
+             C.byref(capped), dptr(cnum), dptr(state), dptr(inl), C.byref(res), *extra))
     pnum = int(pnum.value)
     rst = vo_rst(pnum) if pnum >= 4 else 0
     out = _result(res, cnum[:rst].copy(), state[:rst].copy(), inl[:pnum if rst else 0].copy())
@@ -168,6 +174,61 @@ def vo_pair_seeded(prev, cur, seed, seq=0, thresh=1.5):
     out["draws"], out["capped"] = draws[:rst].copy(), int(capped.value)
     out["match"], out["pnum"], out["rst"] = match[:, :pnum].copy(order="F"), pnum, rst
     return out
+
+
+def vo_pair_cov_seeded(prev, cur, seed, seq=0, thresh=1.5):
+    """vo_pair_seeded with calc_cov_RANSAC_dr_ye.m:17-30 behind it on the device: one more launch behind the final fit, still one
+    host wait.  The dict of vo_pair_seeded, bit for bit, plus cov_status (0 not computed: pnum < 4 or sta != 1; 1 valid; 2 unusable) and cov -- the
+    (7, 7) covariance of u = [T; q] on status 1, else None."""
+    cov, status = np.zeros((7, 7)), C.c_int32(0)
+    out = _pair_call(lib.pre3_vo_pair_cov_seeded, prev, cur, seed, seq, thresh, dptr(cov), C.byref(status))
+    out["cov_status"] = int(status.value)
+    out["cov"] = cov if out["cov_status"] == 1 else None
+    return out
+
+
+def R2q(R):
+    """R2q.m with Calculate_V_Omega_RANSAC_dr_ye.m:48's sign: the quaternion part of u = [T; R2q(R)] as k_vo_final forms it"""
+    R = f64(R).reshape(3, 3)
+    Tq = R[0, 0] + R[1, 1] + R[2, 2] + 1
+    if Tq > 0.00000001:
+        S = 2 * np.sqrt(Tq)
+        a, b, c, d = 0.25 * S, (R[1, 2] - R[2, 1]) / S, (R[2, 0] - R[0, 2]) / S, (R[0, 1] - R[1, 0]) / S
+    elif R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
+        S = 2 * np.sqrt(1.0 + R[0, 0] - R[1, 1] - R[2, 2])
+        a, b, c, d = (R[1, 2] - R[2, 1]) / S, 0.25 * S, (R[0, 1] + R[1, 0]) / S, (R[2, 0] + R[0, 2]) / S
+    elif R[1, 1] > R[2, 2]:
+        S = 2 * np.sqrt(1.0 + R[1, 1] - R[0, 0] - R[2, 2])
+        a, b, c, d = (R[2, 0] - R[0, 2]) / S, (R[0, 1] + R[1, 0]) / S, 0.25 * S, (R[1, 2] + R[2, 1]) / S
+    else:
+        S = 2 * np.sqrt(1.0 + R[2, 2] - R[0, 0] - R[1, 1])
+        a, b, c, d = (R[0, 1] - R[1, 0]) / S, (R[2, 0] + R[0, 2]) / S, (R[1, 2] + R[2, 1]) / S, 0.25 * S
+    return np.array([a, -b, -c, -d])
+
+
+def vo_cov(pset1, pset2, u, inliers=None, device=0):
+    """calc_cov_RANSAC_dr_ye.m:17-30, stateless: pset1, pset2 (3, pnum) = op_pset1, op_pset2; u = [trans; R2q(rot)]; inliers (pnum,) 0/1 or None
+    (every point counts).  Returns dict(cov (7, 7) or None, status, n_inliers): status 0 not computed (pnum < 4), 1 valid, 2 unusable."""
+    p1, p2 = np.ascontiguousarray(f64(pset1).T), np.ascontiguousarray(f64(pset2).T)
+    assert p1.shape == p2.shape and p1.ndim == 2 and p1.shape[1] == 3
+    pnum = p1.shape[0]
+    u = f64(u).reshape(7)
+    inl = None if inliers is None else i32(inliers).reshape(pnum)
+    cov, status, n = np.zeros((7, 7)), C.c_int32(0), C.c_int32(0)
+    check(lib.pre3_vo_cov(int(device), pnum, dptr(p1), dptr(p2), dptr(inl), dptr(u), dptr(cov), C.byref(status), C.byref(n)))
+    st = int(status.value)
+    return dict(cov=cov if st == 1 else None, status=st, n_inliers=int(n.value))
+
+
+def cov_pose_shift_calc(Ya, Yb, R, T, device=0):
+    """aux_code/cov_pose_shift_calc.m's signature over pre3_vo_cov: Ya, Yb (3, n) the matched inlier points of the two frames, R, T the fitted motion
+    (Ya ~ R Yb + T).  Forms u = [T; R2q(R)] itself.  Returns the (7, 7) covariance of [T; q]; raises ValueError when it is not valid (fewer than four
+    points, a singular fit, a non-finite coordinate).  The summed implicit-function form, not the .m file's per-point pinv."""
+    u = np.concatenate([f64(T).reshape(3), R2q(R)])
+    r = vo_cov(Ya, Yb, u, None, device)
+    if r["status"] != 1:
+        raise ValueError("cov_pose_shift_calc: status %d (0: fewer than four points, 2: singular fit or non-finite input)" % r["status"])
+    return r["cov"]
 
 
 def vo_bench(pset1, pset2, draws, reps=20, device=0):

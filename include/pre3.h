@@ -746,6 +746,47 @@ PRE3_API int pre3_set_scan_frame(pre3_ctx *ctx, pre3_sr_frame *f, int which);
 PRE3_API int pre3_predict_pair_seeded(pre3_ctx *ctx, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq,
                                       int32_t *pnum_out, pre3_vo_result *res_out);
 
+/* ---- the prediction's process noise: caller-set, or from the VO pair's inliers on the device ------------------------------------
+ * predict_state_and_covariance.m:98-102: Pn (7 x 7, row-major; it is symmetric) of every prediction this context makes -- pre3_predict, pre3_step*,
+ * pre3_step_all, pre3_step_seeded, pre3_predict_pair_seeded -- in Q = G Pn G' (:120).  NULL returns to the constant of :98-102, which a context on
+ * which nothing was ever set uses exactly as before, bit for bit.  Checked on the host before anything is queued: every entry finite,
+ * Pn[i][j] == Pn[j][i], no negative diagonal entry; otherwise PRE3_E_ARG with the context and its setting unchanged.  The block changes in stream order,
+ * behind the predictions already queued; nothing is synchronised, and deferred or pending work (PRE3_OPT_DEFER_HI / PRE3_OPT_PEND_HI) is left alone and
+ * carried by the predictions as before.  pre3_set_state does not reset the setting; the stateless pre3_predict_dense / pre3_predict_state_and_covariance
+ * and snapshots do not know it. */
+PRE3_API int pre3_set_process_noise(pre3_ctx *ctx, const double *Pn /* [49] or NULL */);
+/* *source_out: 0 the constant, 1 the caller's.  Pn_out[49]: the values in force (source 0: the constant as the prediction's launch builds it on the
+ * device; that form synchronises the context's stream).  Either output may be NULL. */
+PRE3_API int pre3_get_process_noise(pre3_ctx *ctx, double *Pn_out, int *source_out);
+
+/* aux_code/calc_cov_RANSAC_dr_ye.m:17-30 + aux_code/cov_pose_shift_calc.m:4-40 -- the Pn of predict_state_and_covariance.m:115 --, stateless and fed from
+ * the host: pset1 = op_pset1, pset2 = op_pset2 (3 x pnum, column-major), u = [trans; R2q(rot)] of a cached RANSAC_RESULT_%d_%d.mat, inlier[pnum] int32
+ * 0/1 (NULL: every point counts).  The SR4000's per-point range and angle noise is propagated through the rigid fit to the 7 x 7 covariance of [T; q]:
+ * cov = H^-1 M H^-1 with H = sum H_i the Hessian of E = sum 1/2 |T + R(q) pset2_i - pset1_i|^2 in [T; q] and M = sum B_i Sigma_i B_i' (pre3_vocov.h).
+ * This is the implicit-function covariance of the fit; cov_pose_shift_calc.m:14,19's pinv of each point's own rank-deficient Hessian is not built.
+ * *status_out: 0 not computed (pnum < 4), 1 valid, 2 unusable (a non-finite inlier coordinate, a Cholesky pivot of H at or below 7 eps times its
+ * diagonal entry, a non-finite result).  cov_out[49] (row-major, symmetric) is written on status 1 only.  n_inliers_out may be NULL.  Synchronises. */
+PRE3_API int pre3_vo_cov(int device, int pnum, const double *pset1, const double *pset2, const int32_t *inlier, const double u[7], double *cov_out,
+                         int32_t *status_out, int32_t *n_inliers_out);
+
+/* pre3_vo_pair_seeded (vodometry_dr_ye.m:84-236) with calc_cov_RANSAC_dr_ye.m:17-30 behind it: one more launch (k_vo_cov) behind the final fit on the same
+ * stream, reading the winner's inlier list, pset1 / pset2 and u where they lie; still one host wait.  Every output shared with pre3_vo_pair_seeded is
+ * bit-equal to that call's, as are its refusals and errors.  *cov_status_out: 0 not computed (pnum < 4, sta != 1, a refused pair), 1, 2 as pre3_vo_cov's;
+ * cov_out[49] is written on status 1 only and is then bit-equal to pre3_vo_cov fed this call's pset1, pset2, inlier list and res->u.  Either may be NULL. */
+PRE3_API int pre3_vo_pair_cov_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out,
+                                     double *match_out, double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out,
+                                     int32_t *cnum_out, int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res, double *cov_out,
+                                     int32_t *cov_status_out);
+
+/* pre3_predict_pair_seeded with the pair's own covariance as this one prediction's Pn (predict_state_and_covariance.m:115): k_vo_cov behind the pair's
+ * final fit, and the prediction's launch takes its block when status == 1 and the pair's u is taken (sta == 1, not refused); otherwise the context's own
+ * noise -- the caller's (pre3_set_process_noise) or the constant.  u and Pn both stay on the device.  With all four outputs NULL nothing is synchronised;
+ * with any of them the call waits once.  The context's noise setting is unchanged afterwards, and the context is bit-identical to the chain
+ * pre3_vo_pair_cov_seeded -> (status == 1 and sta == 1: pre3_set_process_noise(cov)) -> pre3_predict(res.u) -> the previous setting restored.
+ * Refusals, argument and state errors are pre3_predict_pair_seeded's. */
+PRE3_API int pre3_predict_pair_cov_seeded(pre3_ctx *ctx, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq,
+                                          int32_t *pnum_out, pre3_vo_result *res_out, double *cov_out, int32_t *cov_status_out);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them

@@ -27,10 +27,14 @@
  *   mono_slam.m:189-193 on the resident frame                           applied = pre3_mex('heading_frame', seed, step)                                  % fit + ekf_heading_update, nothing read back
  *   matching_sift_based.m:104,129-135 on the resident frame             pre3_mex('set_scan_frame')                                                       % the scan 'sr_keypoints' was handed, copied on the device
  *   fv.m:47 + ekf_prediction.m:29 on two resident frames                pre3_mex('predict_pair', seed, seq)                                              % 'vo_pair' + 'predict' in one call, u stays on the device
+ *   predict_state_and_covariance.m:98-102 (Pn)                          [Pn, source] = pre3_mex('process_noise' [, Pn])                                  % the Pn of every prediction; [] -> the constant
+ *   aux_code/calc_cov_RANSAC_dr_ye.m:17-30                              [cov, status, n] = pre3_mex('vo_cov', op_pset1, op_pset2, rot, trans [, inliers])  % cached RANSAC_RESULT contents
+ *   predict_state_and_covariance.m:115 on two resident frames           [T, q, sta, pnum, cov, cst] = pre3_mex('predict_pair_cov', seed, seq)            % 'predict_pair' with the pair's covariance as Pn
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
  * corrcoef_partitioned_mex.c:25-57).  NOT compiled in the build container (no MATLAB / mex.h there).
  */
+#include <math.h>
 #include <string.h>
 #include "mex.h"
 #include "pre3.h"
@@ -456,6 +460,63 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         if (nout > 1) { out[1] = mxCreateDoubleMatrix(4, 1, mxREAL); memcpy(mxGetPr(out[1]), r.u + 3, sizeof(double) * 4); }
         if (nout > 2) out[2] = mxCreateDoubleScalar(r.sta);
         if (nout > 3) out[3] = mxCreateDoubleScalar(pnum);
+    }
+    else if (!strcmp(cmd, "process_noise")) {     /* [Pn, source] = pre3_mex('process_noise' [, Pn]): predict_state_and_covariance.m:98-102 -- with a 7 x 7 Pn every prediction from now
+                                                     on takes it (finite, symmetric, no negative diagonal entry); with [] the reference's constant is back; without it nothing is
+                                                     set.  Pn out: the noise in force; source 0 the constant, 1 the caller's (pre3_set_process_noise / pre3_get_process_noise) */
+        int src = 0;
+        if (nin > 2) mexErrMsgTxt("pre3_mex('process_noise' [, Pn]): at most one argument");
+        if (nin > 1) {
+            if (!mxIsEmpty(in[1]) && (!mxIsDouble(in[1]) || mxIsComplex(in[1]) || mxGetM(in[1]) != 7 || mxGetN(in[1]) != 7)) mexErrMsgTxt("pre3_mex('process_noise', Pn): Pn is a real 7 x 7 double matrix, or []");
+            check(pre3_set_process_noise(g_ctx, mxIsEmpty(in[1]) ? NULL : mxGetPr(in[1])));      /* (symmetric: row-major == column-major) */
+        }
+        if (nout > 0 || nin == 1) {
+            out[0] = mxCreateDoubleMatrix(7, 7, mxREAL);
+            check(pre3_get_process_noise(g_ctx, mxGetPr(out[0]), &src));
+            if (nout > 1) out[1] = mxCreateDoubleScalar(src);
+        }
+    }
+    else if (!strcmp(cmd, "vo_cov")) {            /* [cov, status, n] = pre3_mex('vo_cov', op_pset1, op_pset2, rot, trans [, inliers]): calc_cov_RANSAC_dr_ye.m:17-30 on the cached
+                                                     contents of a RANSAC_RESULT_%d_%d.mat -- op_pset1, op_pset2 3 x pnum, rot 3 x 3 with op_pset1 ~ rot * op_pset2 + trans.  cov 7 x 7
+                                                     over [T; q] (zeros unless status == 1); status 0 fewer than four points, 1 valid, 2 unusable (pre3_vo_cov, on device 0) */
+        double u[7], R[9], Tq, S, a, b, c, d, *rp; int32_t status = 0, n = 0, *inl = NULL; int i, k, rc; mwSize pnum;
+        if (nin < 5 || nin > 6) mexErrMsgTxt("pre3_mex('vo_cov', op_pset1, op_pset2, rot, trans [, inliers]): four or five arguments");
+        pnum = mxGetN(in[1]);
+        if (!mxIsDouble(in[1]) || !mxIsDouble(in[2]) || !mxIsDouble(in[3]) || !mxIsDouble(in[4]) || mxGetM(in[1]) != 3 || mxGetM(in[2]) != 3 || mxGetN(in[2]) != pnum
+            || mxGetNumberOfElements(in[3]) != 9 || mxGetNumberOfElements(in[4]) != 3 || (nin > 5 && mxGetNumberOfElements(in[5]) != pnum))
+            mexErrMsgTxt("pre3_mex('vo_cov'): op_pset1, op_pset2 are 3 x pnum, rot 3 x 3, trans 3 x 1, inliers pnum x 1 (all double)");
+        rp = mxGetPr(in[3]);
+        for (i = 0; i < 3; ++i) for (k = 0; k < 3; ++k) R[3 * i + k] = rp[i + 3 * k];      /* column-major -> row-major */
+        Tq = R[0] + R[4] + R[8] + 1;                                                       /* R2q.m, the sign of Calculate_V_Omega_RANSAC_dr_ye.m:48 */
+        if (Tq > 0.00000001) { S = 2 * sqrt(Tq); a = 0.25 * S; b = (R[5] - R[7]) / S; c = (R[6] - R[2]) / S; d = (R[1] - R[3]) / S; }
+        else if (R[0] > R[4] && R[0] > R[8]) { S = 2 * sqrt(1.0 + R[0] - R[4] - R[8]); a = (R[5] - R[7]) / S; b = 0.25 * S; c = (R[1] + R[3]) / S; d = (R[6] + R[2]) / S; }
+        else if (R[4] > R[8]) { S = 2 * sqrt(1.0 + R[4] - R[0] - R[8]); a = (R[6] - R[2]) / S; b = (R[1] + R[3]) / S; c = 0.25 * S; d = (R[5] + R[7]) / S; }
+        else { S = 2 * sqrt(1.0 + R[8] - R[0] - R[4]); a = (R[1] - R[3]) / S; b = (R[6] + R[2]) / S; c = (R[5] + R[7]) / S; d = 0.25 * S; }
+        memcpy(u, mxGetPr(in[4]), sizeof(double) * 3); u[3] = a; u[4] = -b; u[5] = -c; u[6] = -d;
+        if (nin > 5) { inl = (int32_t *)mxMalloc(sizeof(int32_t) * (pnum ? pnum : 1)); for (i = 0; i < (int)pnum; ++i) inl[i] = mxGetPr(in[5])[i] != 0; }
+        out[0] = mxCreateDoubleMatrix(7, 7, mxREAL);
+        rc = pre3_vo_cov(0, (int)pnum, mxGetPr(in[1]), mxGetPr(in[2]), inl, u, mxGetPr(out[0]), &status, &n);
+        if (inl) mxFree(inl);
+        check(rc);
+        if (nout > 1) out[1] = mxCreateDoubleScalar(status);
+        if (nout > 2) out[2] = mxCreateDoubleScalar(n);
+    }
+    else if (!strcmp(cmd, "predict_pair_cov")) {  /* [T, q, sta, pnum, cov, cov_status] = pre3_mex('predict_pair_cov', seed, seq [, thresh = 1.5]): 'predict_pair' with the pair's own
+                                                     covariance, computed on the device from its inliers, as this one prediction's Pn (predict_state_and_covariance.m:115) when
+                                                     cov_status == 1 and sta == 1 -- else the noise 'process_noise' reports.  cov 7 x 7 (zeros unless cov_status == 1).  Without
+                                                     output arguments nothing is waited for (pre3_predict_pair_cov_seeded) */
+        pre3_vo_result r; int32_t pnum = 0, cst = 0; double cov[49]; int i;
+        if (nin < 3 || nin > 4) mexErrMsgTxt("pre3_mex('predict_pair_cov', seed, seq [, thresh]): two or three arguments");
+        if (!g_sr || !g_sr_prev) mexErrMsgTxt("pre3_mex('predict_pair_cov'): needs two frames -- 'sr_frame' + 'sr_keypoints', 'sr_keep', then 'sr_frame' + 'sr_keypoints' again");
+        for (i = 0; i < 49; ++i) cov[i] = 0;
+        check(pre3_predict_pair_cov_seeded(g_ctx, g_sr_prev, g_sr, nin > 3 ? mxGetScalar(in[3]) : 1.5, (uint64_t)mxGetScalar(in[1]), (uint64_t)mxGetScalar(in[2]),
+                                           nout > 0 ? &pnum : NULL, nout > 0 ? &r : NULL, nout > 4 ? cov : NULL, nout > 4 ? &cst : NULL));
+        if (nout > 0) { out[0] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[0]), r.u, sizeof(double) * 3); }
+        if (nout > 1) { out[1] = mxCreateDoubleMatrix(4, 1, mxREAL); memcpy(mxGetPr(out[1]), r.u + 3, sizeof(double) * 4); }
+        if (nout > 2) out[2] = mxCreateDoubleScalar(r.sta);
+        if (nout > 3) out[3] = mxCreateDoubleScalar(pnum);
+        if (nout > 4) { out[4] = mxCreateDoubleMatrix(7, 7, mxREAL); memcpy(mxGetPr(out[4]), cov, sizeof cov); }
+        if (nout > 5) out[5] = mxCreateDoubleScalar(cst);
     }
     else if (!strcmp(cmd, "map_delete")) {        /* pre3_mex('map_delete', idx (0-based, ascending))   delete_features.m:54-74 */
         int k = (int)mxGetNumberOfElements(in[1]), i, rc; int32_t *d = (int32_t *)mxMalloc(sizeof(int32_t) * (k ? k : 1));
