@@ -56,6 +56,7 @@ lib.pre3_heading_from_frame.argtypes = [_P, _P, _P, _D, _I, _P, _I, _I, _P, _P]
 lib.pre3_heading_from_frame_seeded.argtypes = [_P, _P, _P, _D, _I, _U, _U, _I, _I, _P, _P, _P]
 lib.pre3_set_scan_frame.argtypes = [_P, _P, _I]
 lib.pre3_predict_pair_seeded.argtypes = [_P, _P, _P, _D, _U, _U, _P, _P]
+lib.pre3_predict_cv.argtypes = [_P, _I, _D, _D, _D]
 lib.pre3_set_process_noise.argtypes = [_P, _P]
 lib.pre3_get_process_noise.argtypes = [_P, _P, _P]
 lib.pre3_vo_cov.argtypes = [_I, _I, _P, _P, _P, _P, _P, _P, _P]
@@ -134,7 +135,7 @@ EXPORTS = [
     "pre3_sr_gauss3", "pre3_sr_frame_create", "pre3_sr_frame_destroy", "pre3_sr_frame_load", "pre3_sr_frame_get", "pre3_sr_frame_keypoints",
     "pre3_vo_pair_seeded", "pre3_map_policy_frames_seeded",
     "pre3_plane_fit_frame", "pre3_plane_fit_frame_seeded", "pre3_heading_from_frame", "pre3_heading_from_frame_seeded", "pre3_set_scan_frame",
-    "pre3_predict_pair_seeded",
+    "pre3_predict_pair_seeded", "pre3_predict_cv",
     "pre3_set_process_noise", "pre3_get_process_noise", "pre3_vo_cov", "pre3_vo_pair_cov_seeded", "pre3_predict_pair_cov_seeded",
     "pre3_sift_plan_get", "pre3_sr_frame_sift", "pre3_sr_frame_gate", "pre3_sr_frame_sift_level", "pre3_sr_frame_sift_refined",
     "pre3_sr_text_limits", "pre3_sr_text_parse", "pre3_sr_frame_load_text",

@@ -12,6 +12,7 @@
 #include "pre3_test_hooks.h"
 #include "pre3_geomdev.h"
 #include "pre3_predictu.h"
+#include "pre3_predictcv.h"
 #include <mutex>
 #include "pre3_cholp.h"
 
@@ -768,6 +769,23 @@ int pre3_predict(pre3_ctx *c, const double u[7])
     PRE3_CHECK(u != nullptr, PRE3_E_ARG, "pre3_predict: null u");
     PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "pre3_predict: needs (x_k_k, p_k_k) on the device");
     PRE3_TRY(launch_predict_impl(c, u));
+    c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
+    return PRE3_OK;
+}
+
+// The camera-only prediction (include/pre3.h).  The argument and state checks come before the scope: a refused call queues nothing and
+// leaves deferred and pending work where it was.  A pending update.m:42-46 pass belongs IN FRONT of this prediction: it goes out as its own launch here --
+// left to the scope's destructor it would run behind k_predict_cv, on the predicted covariance.
+int pre3_predict_cv(pre3_ctx *c, int type, double dt, double sigma_a, double sigma_alpha)
+{
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
+    PRE3_CHECK(type >= 0 && type < CV_N_TYPES, PRE3_E_ARG, "pre3_predict_cv: type %d outside 0..3", type);
+    PRE3_CHECK(std::isfinite(dt) && dt > 0, PRE3_E_ARG, "pre3_predict_cv: dt must be finite and positive");
+    PRE3_CHECK(std::isfinite(sigma_a) && sigma_a >= 0 && std::isfinite(sigma_alpha) && sigma_alpha >= 0, PRE3_E_ARG, "pre3_predict_cv: the sigmas must be finite and not negative");
+    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "pre3_predict_cv: needs (x_k_k, p_k_k) on the device");
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    if (c->carry.jn_pending) { c->carry.jn_pending = false; PRE3_TRY(launch_jnorm(c, 0)); }
+    PRE3_TRY(launch_predict_cv(c, type, dt, sigma_a, sigma_alpha));
     c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
     return PRE3_OK;
 }

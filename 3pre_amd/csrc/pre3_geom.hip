@@ -7,6 +7,7 @@
 //
 // Reference statements reproduced (paths under matlab_code/):
 //   predict        predict_state_and_covariance.m:59-143, aux_code/odometry_model.m:44-68
+//   predict (cv)   predict_state_and_covariance.m:82,89-90,127-143, fv.m:64-87,98-106, dfv_by_dxv.m:38-116, func_Q.m:41-54 (pre3_predictcv.h)
 //   project        predict_camera_measurements.m:27-68, hi_inverse_depth.m:33-85, hi_cartesian.m:33-81
 //   jacobian       calculate_Hi_inverse_depth_my_version.m:46-183, calculate_Hi_cartesian_my_version.m
 //   innovation     search_IC_matches.m:33-44; rescue gate @ekf_filter/rescue_hi_inliers.m:35-46
@@ -18,6 +19,7 @@
 #include "pre3_vodev.h"
 #include "pre3_vopair.h"
 #include "pre3_predictu.h"
+#include "pre3_predictcv.h"
 #include "pre3_vocov.h"
 #include <type_traits>
 
@@ -200,6 +202,90 @@ __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in
             __syncthreads();
             const int nst = (pw.rows + B3_BK - 1) / B3_BK;
             for (int st = 0; st < nst; ++st) b3_split_block(pw.W, pw.ldw, static_cast<bf16x8_t *>(pw.Wp), pw.nst_total, 0, st, threadIdx.x);
+        }
+    }
+}
+
+// The camera-only prediction (pre3_predict_cv; the model: pre3_predictcv.h) as ONE launch.  F is 13 x 13 here, not blkdiag(I3, Qq1, I6):
+// every column j >= 13 of P takes P[0:13, j] <- Jn13 F P[0:13, j] (one column per thread, 13 loads, fp64), stores the rows that change and their mirror
+// P[j, 0:13]; rows >= 13 are never read and entries with both indices >= 13 never written.  Block 0 owns the 13 x 13 corner, in LDS: it reads it before any
+// store to it (threads j < 13 do no strip work, and no strip store lands in it), forms F C F' + G Pn G', then the Jnorm congruence, and writes x_out[0:13].
+// Lane 0 of every block builds F and Jnorm for itself from x_in, as k_predict's does: no block waits on another.  T appears at loads and stores of P only.
+// No projection rider, no inbox pull, no word of pred_params: the update's pass (k_jnorm_P), the gate rider and the pending form read params[16..] / [96..]
+// as the update in front of THEM wrote it, pre3_get_process_noise reads [128..], and nobody reads [0..15] or [32..80].
+template <typename T>
+__global__ __launch_bounds__(256) void k_predict_cv(const double *__restrict__ x_in, double *__restrict__ x_out, T *__restrict__ P, int n, int ld, CvArgs a)
+{
+    __shared__ double sRq[16], sM[12], sJn[16], sX[13];              // lane 0's pieces: F(4:7,4:7), the 4 x 3 block of F and G, Jnorm, x_out[0:13]
+    __shared__ double sF[169], sJ[169], sC[169], sT[169];            // block 0: dense F and J = blkdiag(I3, Jnorm, I6), the corner, a product
+    const int tid = threadIdx.x, j = blockIdx.x * blockDim.x + tid;
+    // landmarks copied (predict_state_and_covariance.m:79)
+    for (int i = 13 + j; i < n; i += gridDim.x * blockDim.x) x_out[i] = x_in[i];
+    const bool strip = j >= 13 && j < n;
+    double c[13];
+#pragma unroll
+    for (int i = 0; i < 13; ++i) c[i] = strip ? (double)P[(size_t)i * ld + j] : 0.0;
+    if (blockIdx.x == 0 && tid < 169) sC[tid] = (double)P[(size_t)(tid / 13) * ld + (tid % 13)];
+    if (tid == 0) {
+        // (one lane's serial code is the launch's critical path: cv_model is written for it, and normJac's power is a square root and a division here)
+        CvModel m;
+        cv_model(x_in, a.type, a.dt, m);
+        for (int i = 0; i < 16; ++i) sRq[i] = m.Rq[i];
+        for (int i = 0; i < 12; ++i) sM[i] = m.M[i];
+        const double *q = m.xo + 3;                                  // normJac.m:27-38 at the un-normalised q (predict_state_and_covariance.m:137)
+        const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3], qn = sqrt(n2), s = 1.0 / (n2 * qn);
+        for (int i = 0; i < 4; ++i) for (int k = 0; k < 4; ++k) sJn[i * 4 + k] = s * (i == k ? n2 - q[i] * q[i] : -q[i] * q[k]);
+        if (blockIdx.x == 0) for (int i = 0; i < 13; ++i) sX[i] = (i >= 3 && i < 7) ? m.xo[i] / qn : m.xo[i];      // :143
+    }
+    __syncthreads();
+    const double dtv = a.type == CV_CONSTANT_VELOCITY ? a.dt : 0.0;
+    if (strip) {
+        // F c by F's structure (cv_F_entry): rows 0..2 are I and dt I at columns 7..9 (type 0), rows 3..6 the 4 x 4 block at columns 3..6 and (type 0) the
+        // 4 x 3 block at columns 10..12, rows 7..12 a diagonal of ones or zeros; then Jnorm on rows 3..6
+        double f[13], b[13];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) f[i] = c[i] + dtv * c[7 + i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            f[3 + i] = sRq[i * 4] * c[3] + sRq[i * 4 + 1] * c[4] + sRq[i * 4 + 2] * c[5] + sRq[i * 4 + 3] * c[6];
+            if (a.type == CV_CONSTANT_VELOCITY) f[3 + i] += sM[i * 3] * c[10] + sM[i * 3 + 1] * c[11] + sM[i * 3 + 2] * c[12];
+        }
+#pragma unroll
+        for (int i = 7; i < 13; ++i) f[i] = cv_row_changes(i, a.type) ? 0.0 : c[i];
+#pragma unroll
+        for (int i = 0; i < 13; ++i) b[i] = f[i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) b[3 + i] = sJn[i * 4] * f[3] + sJn[i * 4 + 1] * f[4] + sJn[i * 4 + 2] * f[5] + sJn[i * 4 + 3] * f[6];
+#pragma unroll
+        for (int i = 0; i < 13; ++i)
+            if (cv_row_changes(i, a.type)) { P[(size_t)i * ld + j] = (T)b[i]; P[(size_t)j * ld + i] = (T)b[i]; }
+    }
+    if (blockIdx.x == 0) {
+        // the corner: C1 = F C F' + G Pn G' (:131), then J C1 J' with J = blkdiag(I3, Jnorm, I6) (:139-141).  The last product is evaluated for the
+        // entry (max, min) by both threads of a mirrored pair, so the corner comes out exactly symmetric, as the strips and their mirrors do.
+        const int i = tid / 13, k = tid % 13;
+        if (tid < 13) x_out[tid] = sX[tid];
+        if (tid < 169) {
+            sF[tid] = cv_F_entry(i, k, a.type, a.dt, sRq, sM);
+            sJ[tid] = (i >= 3 && i < 7 && k >= 3 && k < 7) ? sJn[(i - 3) * 4 + k - 3] : (i == k ? 1.0 : 0.0);
+        }
+        __syncthreads();
+        if (tid < 169) { double s = 0; for (int t = 0; t < 13; ++t) s += sF[i * 13 + t] * sC[t * 13 + k]; sT[tid] = s; }
+        __syncthreads();
+        if (tid < 169) {                                            // (the old corner was last read in front of the barrier above)
+            double s = 0, q = 0;
+            for (int t = 0; t < 13; ++t) s += sT[i * 13 + t] * sF[k * 13 + t];
+            for (int t = 0; t < 6; ++t) q += cv_G_entry(i, t, a.dt, sM) * (t < 3 ? a.var_a : a.var_alpha) * cv_G_entry(k, t, a.dt, sM);
+            sC[tid] = s + q;
+        }
+        __syncthreads();
+        if (tid < 169) { double s = 0; for (int t = 0; t < 13; ++t) s += sJ[i * 13 + t] * sC[t * 13 + k]; sT[tid] = s; }
+        __syncthreads();
+        if (tid < 169) {
+            const int hi = i > k ? i : k, lo = i > k ? k : i;
+            double s = 0;
+            for (int t = 0; t < 13; ++t) s += sT[hi * 13 + t] * sJ[lo * 13 + t];
+            P[(size_t)i * ld + k] = (T)s;
         }
     }
 }
@@ -1159,6 +1245,19 @@ int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection, si
     else predict_launch(c, nb, uu, PnConst{}, blocks, pr, ib, fuse_jn);
     PRE3_HIP(hipGetLastError());
     c->carry.jn_pending = false;
+    return PRE3_OK;
+}
+
+// pre3_predict_cv's launch.  A pending HI down-date (PRE3_OPT_PEND_HI) has been flushed by the caller's EntryScope: W~ is not carried through the 13-row congruence.
+int launch_predict_cv(pre3_ctx *c, int type, double dt, double sigma_a, double sigma_alpha)
+{
+    PRE3_TRY(pend_flush(c));
+    const CvArgs a{ type, dt, (sigma_a * dt) * (sigma_a * dt), (sigma_alpha * dt) * (sigma_alpha * dt) };
+    const int blocks = ceil_div(c->n, 256);
+    DISPATCH_T(c,
+        hipLaunchKernelGGL(k_predict_cv<double>, dim3(blocks), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (double *)c->P, c->n, c->ld, a),
+        hipLaunchKernelGGL(k_predict_cv<float>, dim3(blocks), dim3(256), 0, c->stream, c->x_kk, c->x_km1, (float *)c->P, c->n, c->ld, a));
+    PRE3_HIP(hipGetLastError());
     return PRE3_OK;
 }
 

@@ -365,6 +365,8 @@ struct PredictUDev; struct PnPair;
 int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection = false, size_t inbox_n16 = 0, int32_t inbox_seq = 0,
                         const PredictUDev *u_dev = nullptr /* the increment from a VO pair's device result block (pre3_geomdev.h); u unused */,
                         const PnPair *pn_pair = nullptr /* with u_dev: the pair's covariance as Pn under the status rule (pre3_vocov.h); its `behind` is filled here */);
+// the camera-only prediction (pre3_predict_cv; pre3_predictcv.h): one launch, no riders, pred_params untouched
+int launch_predict_cv(pre3_ctx *c, int type, double dt, double sigma_a, double sigma_alpha);
 constexpr int PRED_PN_OFF = 128;         /* pred_params[128 .. 176]: the context's process noise block (pre3_set_process_noise) */
 int launch_set_pn(pre3_ctx *c, const double *Pn);
 int launch_get_pn_const(pre3_ctx *c, double *dst_dev);      /* d_process_noise's 49 doubles into device memory, on the context's stream */

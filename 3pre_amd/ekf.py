@@ -5,6 +5,7 @@ matlab_code/ of the reference):
 
     EkfFilter                     <-> @ekf_filter/ekf_filter.m:27-89 (x_k_k, p_k_k, x_k_km1, p_k_km1, std_z ...)
       .ekf_prediction(u)          <-> @ekf_filter/ekf_prediction.m:29 -> predict_state_and_covariance.m:27
+      .ekf_prediction_cv(dt, sigma_a, sigma_alpha, type)  <-> the same with the camera-only models (fv.m:64-106, dfv_by_dxv.m, func_Q.m)
       .search_IC_matches()        <-> search_IC_matches.m:31-44 (projection, Jacobians, S_i)
       .matching(k1, zc)           <-> matching_sift_based.m:119-134 (window gate on siftmatch's output)
       .ransac_hypotheses(hyp)     <-> ransac_hypotheses.m:27-85 (draws are an input: MATLAB's RNG is not reproducible)
@@ -467,6 +468,19 @@ class EkfFilter:
         u = f64(u)
         assert u.shape == (7,), "u = [dX(3); dq(4)]"
         check(lib.pre3_predict(self._ctx, dptr(u)))
+
+    CV_TYPES = ("constant_velocity", "constant_orientation", "constant_position", "constant_position_and_orientation")
+
+    def ekf_prediction_cv(self, dt, sigma_a, sigma_alpha, type="constant_velocity"):
+        """predict_state_and_covariance.m with the camera-only models the fork switched off: no u -- the prediction comes from the
+        v and omega the state carries.  State functions fv.m:64-87 / :98-106, F = dfv_by_dxv.m:38-116, Q = func_Q.m:41-54 with the acceleration noise
+        (sigma_a dt)^2, (sigma_alpha dt)^2 (predict_state_and_covariance.m:89-90); dt is the reference's delta_t (:35: 0.1).  type: one of CV_TYPES (or
+        its index); constant_position_and_orientation_location_noise is not built.  At omega = 0 exactly -- what ekf_prediction and the steps leave in
+        x[10:13] -- dqomegadt_by_domega takes its limit where the reference has 0/0.  One launch, in place, nothing waited for."""
+        t = self.CV_TYPES.index(type) if isinstance(type, str) and type in self.CV_TYPES else type
+        if isinstance(t, str):
+            raise Pre3Error(-1, "ekf_prediction_cv: type %r is not one of %s" % (type, ", ".join(self.CV_TYPES)))
+        check(lib.pre3_predict_cv(self._ctx, int(t), float(dt), float(sigma_a), float(sigma_alpha)))
 
     def ekf_prediction_pair_seeded(self, prev, cur, seed, seq=0, thresh=1.5, wait=True):
         """fv.m:47 + predict_state_and_covariance.m in one call: vo.vo_pair_seeded between the keypoint records of the resident

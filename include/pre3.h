@@ -108,6 +108,26 @@ PRE3_API int pre3_get_marginal(pre3_ctx *ctx, int which, int k, const int32_t *i
  * and the 7x7 pose block change), so p_k_k is no longer available afterwards. */
 PRE3_API int pre3_predict(pre3_ctx *ctx, const double u[7]);
 
+/* The camera-only prediction the fork left in place and switched off: (x_k_k, p_k_k) -> (x_k_km1, p_k_km1) without a u, from
+ * the v and omega the state carries.  State functions fv.m:64-87 and the commented original :98-106; F = dfv_by_dxv (predict_state_and_covariance.m:82,
+ * dfv_by_dxv.m:38-116); Q = func_Q = G Pn G' (:127, func_Q.m:41-54) with Pn = diag((sigma_a dt)^2 [1 1 1], (sigma_alpha dt)^2 [1 1 1]) (:89-90,
+ * :103-104); the covariance assembly and the quaternion's normalisation are :129-143 as they stand.  dt is the reference's delta_t (:35: 0.1).
+ *   type 0 constant_velocity                    x = [r + v dt; q (x) v2q(omega dt); v; omega]
+ *   type 1 constant_orientation                 x = [r + v dt; q; v; 0]
+ *   type 2 constant_position                    x = [r; q (x) v2q(omega dt); 0; omega]
+ *   type 3 constant_position_and_orientation    x = [r; q; 0; 0]
+ * F and G are the reference's for each type: the blocks dfv_by_dxv.m:51-66 zeroes, and no others -- F(4:7,4:7) = dq3_by_dq2(v2q(omega dt)) in all four.
+ * Not built: constant_position_and_orientation_location_noise (its G goes through dq_by_deuler(tr2rpy(q2tr(q))), func_Q.m:29-37).
+ * One deviation: at |omega| = 0 the reference's dqomegadt_by_domega is 0/0 (it relies on the prior w_0 = 1e-15, initialize_x_and_p.m:29-32); here the
+ * limit is taken -- row 1 zero, dt/2 on the diagonal of rows 2:4.  pre3_predict and the steps leave exactly that omega behind.
+ * The covariance is transformed IN PLACE (rows/cols 1:13 change), one launch.  PRE3_E_ARG, with nothing queued and the context as it was, for a type
+ * outside 0..3, a dt that is not finite and positive, a sigma that is negative or not finite; PRE3_E_STATE as pre3_predict. */
+#define PRE3_CV_CONSTANT_VELOCITY 0
+#define PRE3_CV_CONSTANT_ORIENTATION 1
+#define PRE3_CV_CONSTANT_POSITION 2
+#define PRE3_CV_CONSTANT_POSITION_AND_ORIENTATION 3
+PRE3_API int pre3_predict_cv(pre3_ctx *ctx, int type, double dt, double sigma_a, double sigma_alpha);
+
 /* Stateless drop-in for `[X_km1_k, P_km1_k] = predict_state_and_covariance(X_k, P_k, type, SD_A_component_filter,
  * SD_alpha_component_filter)` (predict_state_and_covariance.m:27, caller @ekf_filter/ekf_prediction.m:29): host in, host out.
  * `type` is 'constant_velocity' in every call of the reference and the two standard deviations are unused by this fork (:98-102 hard-

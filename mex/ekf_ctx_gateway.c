@@ -27,6 +27,7 @@
  *   mono_slam.m:189-193 on the resident frame                           applied = pre3_mex('heading_frame', seed, step)                                  % fit + ekf_heading_update, nothing read back
  *   matching_sift_based.m:104,129-135 on the resident frame             pre3_mex('set_scan_frame')                                                       % the scan 'sr_keypoints' was handed, copied on the device
  *   fv.m:47 + ekf_prediction.m:29 on two resident frames                pre3_mex('predict_pair', seed, seq)                                              % 'vo_pair' + 'predict' in one call, u stays on the device
+ *   predict_state_and_covariance.m:82,89-90,127 (fv.m:64-106, dfv_by_dxv.m, func_Q.m)   pre3_mex('predict_cv', dt, sigma_a, sigma_alpha [, type])                  % the camera-only models: no u; type 0..3 or its name
  *   predict_state_and_covariance.m:98-102 (Pn)                          [Pn, source] = pre3_mex('process_noise' [, Pn])                                  % the Pn of every prediction; [] -> the constant
  *   aux_code/calc_cov_RANSAC_dr_ye.m:17-30                              [cov, status, n] = pre3_mex('vo_cov', op_pset1, op_pset2, rot, trans [, inliers])  % cached RANSAC_RESULT contents
  *   predict_state_and_covariance.m:115 on two resident frames           [T, q, sta, pnum, cov, cst] = pre3_mex('predict_pair_cov', seed, seq)            % 'predict_pair' with the pair's covariance as Pn
@@ -230,6 +231,20 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         check(pre3_get_state(g_ctx, (int)mxGetScalar(in[1]), n, mxGetPr(out[0]), nout > 1 ? mxGetPr(out[1]) : NULL));
     }
     else if (!strcmp(cmd, "predict")) check(pre3_predict(g_ctx, mxGetPr(in[1])));
+    else if (!strcmp(cmd, "predict_cv")) {        /* pre3_mex('predict_cv', dt, sigma_a, sigma_alpha [, type = 'constant_velocity']): the prediction with the camera-only models the fork
+                                                     switched off (pre3_predict_cv): fv.m:64-87 / :98-106, dfv_by_dxv.m:38-116, func_Q.m:41-54.  type: 0..3 or 'constant_velocity',
+                                                     'constant_orientation', 'constant_position', 'constant_position_and_orientation' */
+        static const char *names[4] = { "constant_velocity", "constant_orientation", "constant_position", "constant_position_and_orientation" };
+        int type = PRE3_CV_CONSTANT_VELOCITY;
+        if (nin < 4 || nin > 5) mexErrMsgTxt("pre3_mex('predict_cv', dt, sigma_a, sigma_alpha [, type]): three or four arguments");
+        if (nin > 4 && mxIsChar(in[4])) {
+            char name[64]; int t;
+            if (mxGetString(in[4], name, sizeof name)) mexErrMsgTxt("pre3_mex('predict_cv'): type name too long");
+            for (t = 0, type = -1; t < 4; ++t) if (!strcmp(name, names[t])) type = t;
+            if (type < 0) mexErrMsgTxt("pre3_mex('predict_cv'): unknown type (constant_position_and_orientation_location_noise is not built)");
+        } else if (nin > 4) type = (int)mxGetScalar(in[4]);
+        check(pre3_predict_cv(g_ctx, type, mxGetScalar(in[1]), mxGetScalar(in[2]), mxGetScalar(in[3])));
+    }
     else if (!strcmp(cmd, "project")) check(pre3_project(g_ctx, (int)mxGetScalar(in[1]), (int)mxGetScalar(in[2])));
     else if (!strcmp(cmd, "innovation")) check(pre3_innovation(g_ctx));
     else if (!strcmp(cmd, "update_li")) check(pre3_update_li(g_ctx));
