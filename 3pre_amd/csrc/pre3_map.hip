@@ -36,6 +36,11 @@ __device__ inline void m_q2r(const double *q, double *R)
 __global__ void k_map_new_features(int n_new, const double *__restrict__ uvd, const double *__restrict__ rho0, double std_pxl,
                                    const double *__restrict__ x, CamM cam, double *__restrict__ feat)
 {
+    // No fma contraction here: where a Jacobian entry cancels exactly (q_wc = (1, 0, 0, 0): d(theta, phi)/dq0 = 0) what is left of it is the rounding
+    // residue of the products, and a contracted sum leaves another residue than the reference's plain products and sums -- one ulp of the cancelled
+    // terms, which the congruence then multiplies with P[3][c] (tests/test_gpu_map_blocks.py: 218 units of the entry's rounding bound at N = 340).
+    // Product by product, in the order of add_a_feature_covariance_inverse_depth.m:54-60, the residue is the reference's.  (One lane per new feature.)
+#pragma clang fp contract(off)
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n_new) return;
     const double ud = uvd[2 * f], vd = uvd[2 * f + 1];
