@@ -62,18 +62,12 @@ int flush_unless_kept(pre3_ctx *c)
     return PRE3_OK;
 }
 void drop_carried(pre3_ctx *c) { c->carry = {}; }
-// PRE3_FUSE_JN (default 1): the rows/cols 3..6 pass of a HI update completed at the start of a step rides in that step's prediction launch
-static bool fuse_jn_env()
-{
-    static const int v = getenv("PRE3_FUSE_JN") ? atoi(getenv("PRE3_FUSE_JN")) : 1;
-    return v != 0;
-}
 static int enter_ctx(pre3_ctx *c, Entry kind, bool pend_keep)
 {
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
     PRE3_HIP(hipSetDevice(c->device));
     // step: the completed update's rows/cols 3..6 pass (or one a reader has left pending since) is left to the prediction's launch (PRE3_FUSE_JN=0: its own launch)
-    c->req.leave_jn_to_predict = kind != Entry::ordinary && fuse_jn_env() && (c->carry.hi_pending || (kind == Entry::step && c->carry.jn_pending));
+    c->req.leave_jn_to_predict = kind != Entry::ordinary && knob::fuse_jn() && (c->carry.hi_pending || (kind == Entry::step && c->carry.jn_pending));
     c->req.pend_keep = pend_keep;
     int rc = complete_deferred_hi(c);
     if (rc == PRE3_OK && kind != Entry::reader) rc = flush_unless_kept(c);
@@ -121,7 +115,7 @@ int wait_mail(pre3_ctx *c, int slot, int32_t seq)
     // host for ever -- the wait has a wall-clock deadline (pre3_comm_set_timeout), and never ends in a bare hipStreamSynchronize.
     const bool coll = c->comm != nullptr;
     const double t0 = coll ? now_ms() : 0;
-    static const int query_env = getenv("PRE3_WAIT_QUERY") ? atoi(getenv("PRE3_WAIT_QUERY")) : 0;      // 1: hipStreamQuery from the first 1024 spins on (rounds 1-4)
+    const int query_env = knob::wait_query();
     double t_q = 0;
     for (long spin = 0; coll || spin < 2000000000L; ++spin) {
         if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == seq) return PRE3_OK;
@@ -360,7 +354,7 @@ int pre3_create(pre3_ctx **out, int device, int dtype, int max_landmarks, int ma
     c->device = device; c->dtype = dtype; c->esz = dtype == PRE3_F64 ? 8 : 4;
     c->capN = max_landmarks; c->capn = 13 + 6 * max_landmarks; c->capm = max_landmarks; c->caph = max_hyp;
     c->ld = round_up(c->capn, TILE); c->ldw = c->ld + NB;
-    { const char *e = getenv("PRE3_TAIL"); c->step_tail = e ? atoi(e) != 0 : false; }      // PRE3_OPT_STEP_TAIL: off by default (measured: DESIGN.md section 5d)
+    c->step_tail = knob::tail() != 0;               // PRE3_OPT_STEP_TAIL
     c->rcap = round_up(2 * c->capm, NB) + NB;       // (+ one panel: the rescued landmarks' rows follow the LI update's inside the persistent launch, pre3_cholp.hip)
     c->mask_words_cap = ceil_div(c->capm, 32);
     int rc = PRE3_OK;
@@ -458,7 +452,7 @@ int pre3_create(pre3_ctx **out, int device, int dtype, int max_landmarks, int ma
         if (rc == PRE3_OK && hipMemcpy(c->tiles, flat.data(), sizeof(int2) * flat.size(), hipMemcpyHostToDevice) != hipSuccess) { set_error("tile table upload failed"); rc = PRE3_E_HIP; }
     }
     if (dtype == PRE3_F32) {
-        { const char *e = getenv("PRE3_K9_B3"); c->k9_b3 = e ? atoi(e) != 0 : true; }
+        c->k9_b3 = knob::k9_b3() != 0;
         // k_downdate_b3: bf16 planes of W and the 128x128 tile list (4x4 super-tiles dealt to 8 lists, lists interleaved: block b runs
         // on XCD b % 8, so a super-tile's 8 column blocks of planes stay in one L2)
         A(dmalloc_bytes(&c->Wp, (size_t)(c->ld + 128) * c->rcap * 6));       // + one column block for the nu strip's planes
@@ -480,7 +474,7 @@ int pre3_create(pre3_ctx **out, int device, int dtype, int max_landmarks, int ma
         // (the buffers of the in-launch tail, PRE3_OPT_STEP_TAIL, are allocated when the option is switched on: tail_alloc -- at N = 2000 they are
         //  ~300 MB that the default path never touches)
         if (c->step_tail) A(tail_alloc(c));
-        { const char *e = getenv("PRE3_PEND_HI"); if (e && atoi(e) != 0 && c->rcap >= 2 * NB && c->rcap / NB <= CP_MAX_NRB + 1) { A(pend_alloc(c)); c->pend_opt = rc == PRE3_OK; } }      // PRE3_OPT_PEND_HI
+        if (knob::pend_hi() != 0 && c->rcap >= 2 * NB && c->rcap / NB <= CP_MAX_NRB + 1) { A(pend_alloc(c)); c->pend_opt = rc == PRE3_OK; }      // PRE3_OPT_PEND_HI
         if (rc == PRE3_OK) { cholp_context_count(c->device, +1); c->cholp_counted = true; }
         const int nt = c->ld / 128, ns = ceil_div(nt, 4);
         std::vector<std::vector<int2>> lists(8);
@@ -1083,7 +1077,7 @@ int pre3_set_scan(pre3_ctx *c, int K2, const double *descriptor_raw, const doubl
         // The frame's scan crosses PCIe from a pinned block of the context's own, enqueued on its stream: the call neither waits for the queued
         // work nor ends in a read-back.  The bounds the ranked route needs of the descriptors (k_rank_pack's test: finite, |x| <= 2^60, no
         // non-zero |x| < 2^-40) are checked here, on the way into that block.
-        static const int trace = getenv("PRE3_SCAN_TRACE") ? atoi(getenv("PRE3_SCAN_TRACE")) : 0;
+        const int trace = knob::scan_trace();
         const auto t0 = std::chrono::steady_clock::now();
         void *st_v = nullptr, *st_dev = nullptr; int k = 0;
         PRE3_TRY(stage_acquire(c, sizeof(double) * (size_t)K2 * (DESC_DIM + 4), &st_v, &st_dev, &k));
@@ -1220,7 +1214,6 @@ int pre3_comm_init(pre3_ctx *c, const void *id, int rank, int world)
 }
 
 // ---- test hook (pre3_test_hooks.h; inert without PRE3_TEST_HOOKS=1): a kernel that keeps the stream busy until the host releases it (or ~20 s have passed)
-static bool test_hooks_on() { const char *e = getenv("PRE3_TEST_HOOKS"); return e && atoi(e) == 1; }
 __global__ void k_test_stall(volatile int32_t *flag)
 {
     for (long spin = 0; spin < 6000000L; ++spin) {          // (~20 s: the kernel lets go by itself)
@@ -1230,7 +1223,7 @@ __global__ void k_test_stall(volatile int32_t *flag)
 }
 int pre3_test_stall(pre3_ctx *c, int release)
 {
-    PRE3_CHECK(test_hooks_on(), PRE3_E_STATE, "pre3_test_stall: test hooks are off (PRE3_TEST_HOOKS=1 enables them)");
+    PRE3_CHECK(knob::test_hooks(), PRE3_E_STATE, "pre3_test_stall: test hooks are off (PRE3_TEST_HOOKS=1 enables them)");
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "null context");
     PRE3_HIP(hipSetDevice(c->device));
     if (release) { __atomic_store_n(c->mail_host + 15, 1, __ATOMIC_RELEASE); return PRE3_OK; }
@@ -1572,7 +1565,7 @@ int pre3_match_shard_match(pre3_match_shard *s, double thresh, double *pairs_out
 int pre3_match_shard_destroy(pre3_match_shard *s) { if (s) match_shard_destroy(s); return PRE3_OK; }
 int pre3_match_shard_test_stall(pre3_match_shard *s, int release)
 {
-    PRE3_CHECK(test_hooks_on(), PRE3_E_STATE, "pre3_match_shard_test_stall: test hooks are off (PRE3_TEST_HOOKS=1 enables them)");
+    PRE3_CHECK(knob::test_hooks(), PRE3_E_STATE, "pre3_match_shard_test_stall: test hooks are off (PRE3_TEST_HOOKS=1 enables them)");
     return s ? match_shard_test_stall(s, release) : PRE3_E_ARG;
 }
 

@@ -2629,7 +2629,7 @@ constexpr int CP_WIN_MAX = 11;                     // plane blocks of W a strip 
 
 bool cholp_usable(const pre3_ctx *c, int nrb_max)
 {
-    static const int form = getenv("PRE3_CHOL_FORM") ? atoi(getenv("PRE3_CHOL_FORM")) : 1;
+    const int form = knob::chol_form();
     if (form == 0 || !c->chol_persist) return false;
     if (form != 2 && c->device >= 0 && c->device < 64 && g_cholp_live[c->device].load() > 2) return false;
     // crit and the rows wait for one another: blocks 0, 8, .. 8 nH must be resident together, each on a CU of its own (the strips only wait
@@ -2767,15 +2767,13 @@ int launch_cholp(pre3_ctx *c, int nrb, int nrb_max, int rows, int which_prior, c
     // Down-date consumers (P -= W_J' W_J behind the strips, update.m:37): as many groups as there are CUs left.  Every workgroup of the launch
     // declares the same LDS (more than half a CU's), so there is one per CU, and the grid never exceeds the CU count: all of them are resident
     // together whatever the dispatch order -- a consumer can never hold the CU a strip, a row or crit is waiting for.
-    static const int ov_env = getenv("PRE3_K9_OVERLAP") ? atoi(getenv("PRE3_K9_OVERLAP")) : 1;
     int n_dd = 0;
     // (with the consumers a launch fills the chip: it must be the only such launch in flight -- one live fp32 context on the device; with two,
     //  the launches run without consumers, 2 x 110 workgroups side by side as before)
-    static const int form = getenv("PRE3_CHOL_FORM") ? atoi(getenv("PRE3_CHOL_FORM")) : 1;
-    const bool alone = form == 2 || !(c->device >= 0 && c->device < 64) || g_cholp_live[c->device].load() <= 1;
-    if (ov_env && alone && c->k9_overlap && c->dd_groups != nullptr && c->dd_n_groups > 0) {
+    const bool alone = knob::chol_form() == 2 || !(c->device >= 0 && c->device < 64) || g_cholp_live[c->device].load() <= 1;
+    if (knob::k9_overlap() && alone && c->k9_overlap && c->dd_groups != nullptr && c->dd_n_groups > 0) {
         n_dd = std::min(c->dd_n_groups, c->num_cus - (1 + nH + n_strips));
-        static const int dd_max = getenv("PRE3_DD_MAX") ? atoi(getenv("PRE3_DD_MAX")) : -1;      // (tests: fewer groups in the launch than would fit -- the rest goes to k_downdate_b3)
+        const int dd_max = knob::dd_max();
         if (dd_max >= 0) n_dd = std::min(n_dd, dd_max);
         if (n_dd < 0 || std::max(1 + nH + n_strips + n_dd, stride * nH + 1) > c->num_cus) n_dd = 0;
     }
@@ -2799,8 +2797,7 @@ int launch_cholp(pre3_ctx *c, int nrb, int nrb_max, int rows, int which_prior, c
     }
     // the tail (rescue stage + HI update inside this launch): every group of P's tiles must be in the launch, the strips do the x-update, the row
     // count is the device's (the speculative launch of a step)
-    static const int xu_env0 = getenv("PRE3_CHOLP_XU") ? atoi(getenv("PRE3_CHOLP_XU")) : 1;
-    const bool tail = tail_req != nullptr && nrb < 0 && n_dd > 0 && n_dd == c->dd_n_groups && xu_env0 && which_prior == PRE3_X_K_KM1 && cholp_tail_usable(c, nrb_max);
+    const bool tail = tail_req != nullptr && nrb < 0 && n_dd > 0 && n_dd == c->dd_n_groups && knob::cholp_xu() && which_prior == PRE3_X_K_KM1 && cholp_tail_usable(c, nrb_max);
     if (tail) {
         const size_t strip_tail = ((size_t)(win + 1) * CP_WGRAN * 16 + (size_t)NB * CP_WS * sizeof(float) + 127) / 128 * 128 + sizeof(TailSmem);
         PRE3_CHECK(strip_tail <= CP_T_OFF && CP_TAIL_OFF + sizeof(TailSmem) <= CP_T_OFF, PRE3_E_ARG, "launch_cholp: the tail's LDS does not fit");
@@ -2820,32 +2817,24 @@ int launch_cholp(pre3_ctx *c, int nrb, int nrb_max, int rows, int which_prior, c
     a.cf = c->cholp_flags; a.base = c->cholp_epoch; a.status = c->stats + 6;
     a.n_dev = nrb < 0 ? c->stats + 4 : nullptr; a.nrb = nrb < 0 ? nrb_max : nrb; a.nrb_max = nrb_max; a.n_strips = n_strips;
     a.win = win; a.stride = stride;
-    static const int dd_mode = getenv("PRE3_DD_MODE") ? atoi(getenv("PRE3_DD_MODE")) : 17;     // bit 0: sc1 LDS-DMA of the planes; bit 1: an acquire per panel (experiment); bit 2: P warm-up; bit 4: write-through stores of P
-    a.dd_mode = dd_mode;
-    static const int poll_budget = getenv("PRE3_CHOLP_POLL") ? atoi(getenv("PRE3_CHOLP_POLL")) : 0;      // crit's wave 11: shader clocks per chain step spent polling (0: one poll per step, rounds 3-4)
-    a.poll_budget = poll_budget;
-    static const int poll_from = getenv("PRE3_CHOLP_POLL_FROM") ? atoi(getenv("PRE3_CHOLP_POLL_FROM")) : 3;
-    a.poll_from = poll_from;
-    static const int row_late = getenv("PRE3_ROW_LATE") ? atoi(getenv("PRE3_ROW_LATE")) : 0;      // measured (round 6): 5625 vs 5644 steps/s -- crit does not wait for the rows at present
-    a.row_late = row_late;
-    static const int crit_early = getenv("PRE3_CRIT_EARLY") ? atoi(getenv("PRE3_CRIT_EARLY")) : 1;
-    a.crit_early = crit_early;
-    static const int strip_rl = getenv("PRE3_STRIP_RL") ? atoi(getenv("PRE3_STRIP_RL")) : 1;
-    a.strip_rl = strip_rl;
+    a.dd_mode = knob::dd_mode();
+    a.poll_budget = knob::cholp_poll();
+    a.poll_from = knob::cholp_poll_from();
+    a.row_late = knob::row_late();
+    a.crit_early = knob::crit_early();
+    a.strip_rl = knob::strip_rl();
     // every group of P's tiles is in this launch and the strips finish x: the consumers also leave rows 3..6 behind for the gate (GateRide, pre3_geom.hip)
     a.jn_q = (!tail && n_dd > 0 && n_dd == c->dd_n_groups && c->jn_q != nullptr) ? c->jn_q : nullptr;
     c->out.jn_q_valid = a.jn_q != nullptr;
     // with the consumers in the launch the strips also finish the state: x_k_k = x_prior + W'(L^-1 nu) (the K9 launch that used to carry the
     // x-update as riders has nothing left to do at N = 500)
-    static const int xu_env = getenv("PRE3_CHOLP_XU") ? atoi(getenv("PRE3_CHOLP_XU")) : 1;
-    a.xu = (xu_env && n_dd > 0 && which_prior >= 0) ? 1 : 0;
+    a.xu = (knob::cholp_xu() && n_dd > 0 && which_prior >= 0) ? 1 : 0;
     a.n = c->n; a.x_prior = which_prior == PRE3_X_K_K ? c->x_kk : c->x_km1; a.x_out = c->x_kk; a.params = c->pred_params;
     a.P = (float *)c->P; a.dd = c->dd_groups; a.n_dd = n_dd; a.rows = nrb < 0 ? nrb_max * NB : (rows > 0 && rows <= nrb * NB ? rows : nrb * NB);
     CpTail t{};
     a.tail = tail ? 1 : 0;
     // without the tail: the strips still end with the rescue stage's projection when the step wants the gate to ride with the Jnorm pass (GateRide)
-    static const int proj_env = getenv("PRE3_CHOLP_PROJ") ? atoi(getenv("PRE3_CHOLP_PROJ")) : 1;
-    a.proj = (proj_env && !tail && c->req.want_gate_ride && a.jn_q != nullptr && a.xu && c->N > 0 && lds_strip <= CP_T_OFF) ? 1 : 0;
+    a.proj = (knob::cholp_proj() && !tail && c->req.want_gate_ride && a.jn_q != nullptr && a.xu && c->N > 0 && lds_strip <= CP_T_OFF) ? 1 : 0;
     if (a.proj) {
         t.N = c->N; t.lm_type = c->lm.type; t.lm_off = c->lm.off; t.has_h = c->lm.has_h; t.h = c->lm.h; t.Hc = c->lm.Hc; t.Hl = c->lm.Hl;
         t.cam = CamD{ c->cam.f, c->cam.Cx, c->cam.Cy, c->cam.k1, c->cam.k2, (double)c->cam.nRows, (double)c->cam.nCols };

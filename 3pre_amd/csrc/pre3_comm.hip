@@ -39,7 +39,7 @@ static const Rccl *rccl()
     // the copy already in the process first (a second RCCL beside the host program's would double every per-process resource)
     const char *names[] = { "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1" };
     void *h = nullptr;
-    const char *override_path = getenv("PRE3_RCCL_LIB");
+    const char *override_path = knob::rccl_lib();
     if (override_path && *override_path) h = dlopen(override_path, RTLD_NOW | RTLD_LOCAL);
     for (int pass = 0; pass < 2 && !h; ++pass)
         for (const char *nm : names) { h = dlopen(nm, RTLD_NOW | RTLD_LOCAL | (pass == 0 ? RTLD_NOLOAD : 0)); if (h) break; }

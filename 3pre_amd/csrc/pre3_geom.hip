@@ -1143,7 +1143,6 @@ __global__ __launch_bounds__(64) void k_collect_hi(int m, const int32_t *__restr
 }
 // The collection can ride in the gate's last workgroup (PRE3_HI_FUSE=1, round 1's form) or follow as its own launch (default): like the
 // RANSAC selection (pre3_api.hip, pre3_ransac), the in-launch form makes every workgroup pay a device-scope release and a ticket.
-static bool hi_fuse() { static const int e = getenv("PRE3_HI_FUSE") ? atoi(getenv("PRE3_HI_FUSE")) : 0; return e != 0; }
 static int launch_collect_hi(pre3_ctx *c, const HiArgs &ha)
 {
     hipLaunchKernelGGL(k_collect_hi, dim3(1), dim3(64), 0, c->stream, ha.m, ha.meas, c->lm.ic, c->lm.li, c->lm.hi, ha.hi_meas, ha.sel_rows, ha.stats, ha.mail, ha.seq);
@@ -1233,7 +1232,7 @@ int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection, si
     U7 uu; for (int i = 0; i < 7; ++i) uu.v[i] = u[i];
     int blocks = ceil_div(c->n, 256);
     ProjRide pr{};
-    static const int own_pose = getenv("PRE3_RIDE_POSE") ? atoi(getenv("PRE3_RIDE_POSE")) : 1;      // 0: the riders wait for block 0's pose (rounds 2-4)
+    const int own_pose = knob::ride_pose();
     if (with_projection && c->N > 0) {
         pr = make_proj_ride(c, PRE3_X_K_KM1, 1, 0, own_pose ? 0 : 1); pr.x_lm = c->x_kk;      // (one producer: block 0 -- or none: the riders compute the pose themselves)
         pr.own_pose = own_pose ? 1 : 0; pr.x_prev = c->x_kk; pr.u = uu;
@@ -1287,9 +1286,8 @@ int launch_jnorm(pre3_ctx *c, int)
     int blocks = ceil_div(c->n, 256);
     ProjRide pr{};
     GateRide<float> gr{};
-    static const int gate_env = getenv("PRE3_GATE_RIDE") ? atoi(getenv("PRE3_GATE_RIDE")) : 1;      // 0: the gate as a launch of its own behind this one (rounds 3-4)
     if (c->out.proj_with_jnorm && c->N > 0) {        // (no producer to wait for: x_k_k is complete)
-        if (gate_env && c->req.want_gate_ride && c->out.jn_q_valid && c->dtype == PRE3_F32) {
+        if (knob::gate_ride() && c->req.want_gate_ride && c->out.jn_q_valid && c->dtype == PRE3_F32) {
             // pre3_step behind a persistent launch whose consumers wrote all of P: projection AND chi2 gate ride here (GateRide)
             gr.n_blocks = ceil_div(c->N, 16); gr.N = c->N; gr.Q = c->jn_q; gr.chi2 = c->req.rescue_chi2; gr.project = c->out.proj_in_cholp ? 0 : 1;
             gr.lm_type = c->lm.type; gr.lm_off = c->lm.off; gr.x = c->x_kk; gr.cam = to_camd(c->cam);
@@ -1328,7 +1326,7 @@ int launch_project_innovation(pre3_ctx *c, int which, int clear_first, int mode,
     int32_t *clr = (int32_t *)((unsigned char *)c->inbox_dev + c->off_flags);
     const int n_clr = mode == 0 ? (int)(c->flags_bytes / sizeof(int32_t)) : 0;
     HiArgs ha{};
-    if (mode == 1 && collect) ha = HiArgs{ hi_fuse() ? 1 : 0, c->m, ++c->seq_collect, c->meas, c->hi_meas, c->sel_rows, c->stats, c->mail_dev, c->chol_arrive + 2 };
+    if (mode == 1 && collect) ha = HiArgs{ knob::hi_fuse() ? 1 : 0, c->m, ++c->seq_collect, c->meas, c->hi_meas, c->sel_rows, c->stats, c->mail_dev, c->chol_arrive + 2 };
     dim3 g(ceil_div(c->N * 16, 256) + mr.n_blocks), b(256);
     DISPATCH_T(c,
         hipLaunchKernelGGL(k_project_innovation<double>, g, b, 0, c->stream, c->N, c->lm.type, c->lm.off, x, to_camd(c->cam), clear_first,
@@ -1348,7 +1346,7 @@ int launch_innovation(pre3_ctx *c, int mode, double chi2, bool clear_flags, bool
     int32_t *clr = (int32_t *)((unsigned char *)c->inbox_dev + c->off_flags);
     const int n_clr = clear_flags ? (int)(c->flags_bytes / sizeof(int32_t)) : 0;
     HiArgs ha{};
-    if (mode == 1 && collect) ha = HiArgs{ hi_fuse() ? 1 : 0, c->m, ++c->seq_collect, c->meas, c->hi_meas, c->sel_rows, c->stats, c->mail_dev, c->chol_arrive + 2 };
+    if (mode == 1 && collect) ha = HiArgs{ knob::hi_fuse() ? 1 : 0, c->m, ++c->seq_collect, c->meas, c->hi_meas, c->sel_rows, c->stats, c->mail_dev, c->chol_arrive + 2 };
     dim3 g(ceil_div(c->N * 16, 256)), b(256);
     DISPATCH_T(c,
         hipLaunchKernelGGL(k_innovation<double>, g, b, 0, c->stream, c->N, c->lm.type, c->lm.off, (const double *)c->P, c->ld, c->lm.Hc,
@@ -1427,15 +1425,14 @@ int launch_ransac_select_impl(pre3_ctx *c, int n_draw, int k, int early_exit, in
 
 bool select_gather_usable(const pre3_ctx *c)
 {
-    static const int env = getenv("PRE3_SELECT_GATHER") ? atoi(getenv("PRE3_SELECT_GATHER")) : 1;
-    return env && c->m > 0 && ceil_div(c->m, 32) <= SG_MAXW;
+    return knob::select_gather() && c->m > 0 && ceil_div(c->m, 32) <= SG_MAXW;
 }
 
 int launch_select_gather(pre3_ctx *c, int n_draw, int k, int early_exit, int mask_words)
 {
     const int r_pad_max = round_up(2 * c->m, NB);
     const int seq = ++c->seq_select;
-    static const int lds_env = getenv("PRE3_SELECT_GATHER_LDS") ? atoi(getenv("PRE3_SELECT_GATHER_LDS")) : 1;
+    const int lds_env = knob::select_gather_lds();
     const size_t stage = (size_t)SGL_RB * c->ldw * (c->dtype == PRE3_F64 ? 8 : 4);
     const size_t stage1 = stage / SGL_RB;
     if (lds_env && stage > 55 * 1024 && stage1 <= 55 * 1024 && c->dtype == PRE3_F32) {

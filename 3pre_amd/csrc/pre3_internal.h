@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/pre3.h"
+#include "pre3_knobs.h"
 
 namespace pre3 {
 

@@ -421,8 +421,7 @@ static int apply_map(pre3_ctx *c, const std::vector<int32_t> &desc, int n_new, c
     const MapFinish fin{ n_new, c->x_alt, c->x_kk, N, d_types, d_off, c->lm.type, c->lm.off, c->capN, c->lm.has_h, c->lm.has_S, (int32_t *)c->inbox_dev, (int)(c->inbox_bytes / 4),
                          d_src, with_bank ? c->bank : nullptr, c->bank_alt,
                          c->req.book_from ? c->req.book_from : c->book, with_book ? c->book_alt : nullptr, c->book_vis, c->book_s };
-    static const int one_pass = getenv("PRE3_MAP_ONE_PASS") ? atoi(getenv("PRE3_MAP_ONE_PASS")) : 1;
-    if (one_pass) {
+    if (knob::map_one_pass()) {
         // one pass into the second buffer, which becomes P
         const int gx = ceil_div(c->ld, 1024), ny = c->ld / 8, fin_rows = std::min(64, ceil_div(ceil_div(fin_work, 256), gx));
         dim3 g1(gx, ny + fin_rows), b(256);

@@ -1213,8 +1213,7 @@ static int i8_prepare(I8Match &m, int ND, int K1, const T *L1, int K2, const T *
     size_t np = (size_t)m.K1p * m.ntn * 4;            // four partials (32-column chunks) per 128-column tile (row-scan form)
     PRE3_TRY(m.pb.alloc(sizeof(int) * np)); PRE3_TRY(m.ps.alloc(sizeof(int) * np)); PRE3_TRY(m.pa.alloc(sizeof(int) * np));
     PRE3_TRY(m.ob.alloc(sizeof(double) * K1)); PRE3_TRY(m.os.alloc(sizeof(double) * K1)); PRE3_TRY(m.oa.alloc(sizeof(int32_t) * K1));
-    static const int form = getenv("PRE3_MATCH_I8_FORM") ? atoi(getenv("PRE3_MATCH_I8_FORM")) : 1;     // 0: row-scan form (k_match_i8_mfma + reduce), A/B
-    m.frag = form == 1 && m.NDp == 128;
+    m.frag = knob::match_i8_form() == 1 && m.NDp == 128;
     launch_pack_i8<T>(ND, m.NDp, K1, m.K1p, (const T *)r1.p, center, (int8_t *)m.A.p, (int *)m.na.p, m.frag);
     launch_pack_i8<T>(ND, m.NDp, K2, m.K2p, (const T *)r2.p, center, (int8_t *)m.B.p, (int *)m.nb.p, m.frag);
     PRE3_HIP(hipGetLastError());
@@ -1259,13 +1258,8 @@ struct RankMatch {
     int nsl2 = 0;                                                         // ... of the LDS-staged form with 128 queries per workgroup (k_rank_tiled2); 0: that form does not apply
     I8Match m;                                                            // int8 operands + the outputs (ob, os, oa) of every route
 };
-static int float_form()
-{
-    const char *e = getenv("PRE3_MATCH_FLOAT_FORM");           // 0: exact VALU kernels only, 1: auto, 2: never the int8 route (A/B, tests); read per call
-    return e ? atoi(e) : 1;
-}
 template <typename T>
-static bool rank_applies(int ND, int K1, int K2) { return float_form() != 0 && ND <= 128 && (size_t)K1 * K2 >= (size_t)64 * 64 * 16; }
+static bool rank_applies(int ND, int K1, int K2) { return knob::match_float_form() != 0 && ND <= 128 && (size_t)K1 * K2 >= (size_t)64 * 64 * 16; }
 
 template <typename T>
 static int rank_prepare(RankMatch &r, int ND, int K1, const T *L1, int K2, const T *L2)
@@ -1306,7 +1300,7 @@ static int rank_prepare(RankMatch &r, int ND, int K1, const T *L1, int K2, const
     PRE3_HIP(hipGetLastError());
     int fl = 0;
     PRE3_HIP(hipMemcpy(&fl, r.fl.p, sizeof(int), hipMemcpyDeviceToHost));
-    r.route = (fl & 1) ? 0 : ((fl & 2) == 0 && float_form() != 2) ? 1 : 2;
+    r.route = (fl & 1) ? 0 : ((fl & 2) == 0 && knob::match_float_form() != 2) ? 1 : 2;
     return PRE3_OK;
 }
 
@@ -1315,9 +1309,7 @@ static int rank_run(RankMatch &r, int k2_offset, hipStream_t st, bool count = fa
 {
     if (r.route == 1) return i8_run(r.m, k2_offset, st);
     PRE3_CHECK(r.route == 2, PRE3_E_STATE, "float-class matcher: the data is outside the ranked path's bounds");
-    const char *fe = getenv("PRE3_MATCH_RANK_FORM");                      // 1 (default): tiled both ways, three launches; 0: one launch, database streamed per 16 queries
-    static const int form2_default = 0;                                      // (measured, 4096 x 4096 unit-norm doubles: form 2 52.2 us per match, form 1 43.5)
-    const int form = fe ? atoi(fe) : (form2_default ? 2 : 1);               // 2: 128 queries per workgroup, database staged through LDS (round 6); 1: k_rank_tiled; 0: k_match_rank
+    const int form = knob::match_rank_form();
     if (form == 2 && r.nsl2 > 0) {
         static std::atomic<int> attr_ok{ 0 };
         if (attr_ok.load() == 0) {
@@ -1541,8 +1533,7 @@ int ic_rank_set_scan(pre3_ctx *c, bool in_bounds)
 
 static bool ic_rank_usable(const pre3_ctx *c)
 {
-    const char *e = getenv("PRE3_IC_RANK");                    // 0: the exact VALU kernel (A/B, tests); read per call
-    if (e && atoi(e) == 0) return false;
+    if (knob::ic_rank() == 0) return false;
     const IcRank *ic = static_cast<const IcRank *>(c->ic_rank);
     return ic && ic->scan_ok && ic->packed && ic->K2 == c->scan_K2 && c->bank_ok && c->N <= ic->K1cap && rank_applies<double>(DESC_DIM, c->N, c->scan_K2);
 }
@@ -1682,8 +1673,7 @@ __global__ __launch_bounds__(ICG_NTH) void k_ic_gate_fused(IcGateF a)
 
 static bool ic_fused_usable(const pre3_ctx *c)
 {
-    const char *e = getenv("PRE3_IC_FUSED");                   // 0: the ranked / exact routes (A/B, tests); read per call
-    if (e && atoi(e) == 0) return false;
+    if (knob::ic_fused() == 0) return false;
     const int ntn = ceil_div(c->scan_K2, ICS_T);
     return c->scan_K2 > 0 && c->N <= ICG_MAXN && ntn <= ICS_MAXT && c->ic_pb != nullptr && c->ic_pcap >= (size_t)c->capN * ICS_MAXT
            && (size_t)c->N * c->scan_K2 <= ((size_t)1 << 20);
@@ -1694,9 +1684,8 @@ static bool ic_fused_usable(const pre3_ctx *c)
 // without a predicted landmark)
 IcMatchRide ic_match_ride(const pre3_ctx *c)
 {
-    static const int ride_env = getenv("PRE3_IC_RIDE") ? atoi(getenv("PRE3_IC_RIDE")) : 1;
     IcMatchRide r{};
-    if (!ride_env || !ic_fused_usable(c)) return r;
+    if (!knob::ic_ride() || !ic_fused_usable(c)) return r;
     r.ntn = ceil_div(c->scan_K2, ICS_T); r.N = c->N; r.K2 = c->scan_K2; r.n_blocks = r.ntn * ceil_div(c->N, ICS_T);
     r.bank = c->bank; r.scan = c->scan_desc; r.has_h = nullptr; r.pb = c->ic_pb; r.ps = c->ic_ps; r.pa = c->ic_pa;
     return r;

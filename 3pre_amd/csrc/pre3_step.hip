@@ -46,8 +46,7 @@ static int ransac_prepare(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, in
     c->masks = reinterpret_cast<uint32_t *>(c->support + round_up(n_draw, 4));
     c->scored_n_draw = n_draw; c->scored_k = k;         // the mask offset depends on n_draw: select / export / import must use the same
     int r = 2 * c->m, r_pad = round_up(r, NB);
-    static const int inline_g_env = getenv("PRE3_INLINE_G") ? atoi(getenv("PRE3_INLINE_G")) : 1;
-    const bool inline_g = inline_g_env != 0;
+    const bool inline_g = knob::inline_g() != 0;
     if (sliced) {
         // a rank's slice of a sharded round: H*P and H*P*H' only for the measurements its hypotheses draw (the scorer of hypothesis h
         // reads the 2k rows of its own landmarks and the entries of G among them, nothing else) -- the part of the round that
@@ -59,9 +58,8 @@ static int ransac_prepare(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, in
         return PRE3_OK;
     }
     if (need_pull) {
-        static const int ride_env = getenv("PRE3_HYP_RIDE") ? atoi(getenv("PRE3_HYP_RIDE")) : 1;      // 0: the pull as a launch of its own (rounds 2-4)
         const size_t n16 = (sizeof(int32_t) * n_draw * k + 15) / 16;
-        if (ride_env) {
+        if (knob::hyp_ride()) {
             const InboxRide ib{ (const int4 *)((const unsigned char *)c->inbox_host_dev + c->off_hyp), (int4 *)c->hyp, (int)n16, c->mail_dev, ++c->seq_inbox, 10, nullptr, 0 };
             c->inbox_pending = true;
             PRE3_TRY(launch_ell_HP_build(c, c->HP, nullptr, 0, &ib));
@@ -197,8 +195,7 @@ static int ransac_impl(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, doubl
     // in the scoring launch's last workgroup (PRE3_SELECT_FUSE=1, round 1's form), but measured at N=500 / 200 hypotheses that launch then
     // takes 21.2 us against 10.0 + 6.7 us for the two (tools/score_split.py): every workgroup pays a device-scope release (an L2 write-back)
     // and a ticket before it may finish, and the last one starts the selection behind an L2 invalidate.
-    static const int fuse_env = getenv("PRE3_SELECT_FUSE") ? atoi(getenv("PRE3_SELECT_FUSE")) : 0;
-    if (fuse_env) PRE3_TRY(launch_ransac_score_impl(c, k, threshold, 0, n_draw, round_up(2 * c->m, NB), c->support, c->masks, words, n_draw, early_exit));
+    if (knob::select_fuse()) PRE3_TRY(launch_ransac_score_impl(c, k, threshold, 0, n_draw, round_up(2 * c->m, NB), c->support, c->masks, words, n_draw, early_exit));
     else {
         PRE3_TRY(launch_ransac_score_impl(c, k, threshold, 0, n_draw, round_up(2 * c->m, NB), c->support, c->masks, words, 0, 0));
         // pre3_step: the selection rides in the LI gather's launch (k_select_gather), which pre3_update_li sends next
@@ -261,8 +258,7 @@ static int update_selected(pre3_ctx *c, int which_prior, int nsel, const int32_t
     if (reuse) { if (!gathered) PRE3_TRY(launch_gather_li(c, nsel, nsel, sel_dev, round_up(2 * c->m, NB))); }
     else if (r > 0) {
         // rows built on the fly inside the H*P launch (one launch instead of k_build_rows + k_ell_HP; PRE3_FUSE_ROWS=0: the two)
-        static const int fuse_rows = getenv("PRE3_FUSE_ROWS") ? atoi(getenv("PRE3_FUSE_ROWS")) : 1;
-        if (fuse_rows && round_up(r, NB) <= c->rcap) { PRE3_TRY(launch_ell_HP_build_sel(c, nsel, sel_dev, c->W)); hp_built = true; }
+        if (knob::fuse_rows() && round_up(r, NB) <= c->rcap) { PRE3_TRY(launch_ell_HP_build_sel(c, nsel, sel_dev, c->W)); hp_built = true; }
         else PRE3_TRY(launch_build_rows_impl(c, nsel, sel_dev, round_up(r, NB)));
     }
     PRE3_TRY(run_update(c, which_prior, r, false, nullptr, reuse, first_done && reuse, hp_built));
@@ -289,8 +285,7 @@ static int update_li_impl(pre3_ctx *c)
             else PRE3_TRY(launch_gather_li(c, -1, c->m, c->sel_rows, round_up(2 * c->m, NB)));
             gathered = true;
             // ... and so does the first panel of the factorisation (row count read on the device, grid sized for all measurements)
-            static const int spec_env = getenv("PRE3_CHOL_SPEC0") ? atoi(getenv("PRE3_CHOL_SPEC0")) : 1;
-            if (spec_env && round_up(2 * c->m, NB) <= c->rcap) {
+            if (knob::chol_spec0() && round_up(2 * c->m, NB) <= c->rcap) {
                 // fp32: the whole factorisation + solve is ONE launch that reads the row count on the device (pre3_cholp.hip)
                 if (cholp_usable(c, round_up(2 * c->m, NB) / NB)) {
                     // pre3_step: the rescue stage and the HI update ride in the same launch (mono_slam.m:184-187 as panel nrb of this factorisation)
@@ -388,8 +383,7 @@ int pre3::update_hi_impl(pre3_ctx *c)
                     c->carry.pend_rows = 2 * n_hi;
                     // (two panels of pending rows cost the next H*P launch ~19 us more, one panel ~5: sending the two-panel ones out at once -- PRE3_PEND_MAX_ROWS=64 --
                     //  measured 5922 against 5954 steps/s: the launch they then need costs as much)
-                    static const int pend_max = getenv("PRE3_PEND_MAX_ROWS") ? atoi(getenv("PRE3_PEND_MAX_ROWS")) : 2 * NB;
-                    if (c->carry.pend_rows > pend_max) PRE3_TRY(pend_flush(c));
+                    if (c->carry.pend_rows > knob::pend_max_rows()) PRE3_TRY(pend_flush(c));
                 }
                 if (c->req.leave_jn_to_predict) c->carry.jn_pending = true;
                 else PRE3_TRY(launch_jnorm(c, 0));              // (flushes the pending rows first: the pass reads P)
@@ -530,7 +524,7 @@ static int step_back(pre3_ctx *c, int m, int n_draw, int k, const int32_t *hyp, 
         PRE3_TRY(rc_r);
         ran = true;
     }
-    static const int ride_rescue = getenv("PRE3_RIDE_RESCUE") ? atoi(getenv("PRE3_RIDE_RESCUE")) : 1;      // 0: projection + gate as one launch of their own (A/B)
+    const int ride_rescue = knob::ride_rescue();
     c->req.ride_rescue_projection = ride_rescue != 0;               // the rescue's projection rides in the LI update's K9 launch
     {
         // ... or, with the whole rescue stage and the HI update, in the persistent launch itself (not on a booked context: the rescue's visibility
@@ -581,7 +575,7 @@ static int step_front(pre3_ctx *c, const double u[7], int m, const int32_t *meas
     // PRE3_OPT_PEND_HI (pend_keep): this call's own launches take a pending HI down-date along (prediction, H*P + S_i, the LI update's consumers); whatever
     // of it cannot -- and every launch made from in here that reads P some other way -- flushes it first (pend_flush in the launchers)
     EntryScope scope(c, Entry::step, c && c->pend_opt && c->dtype == PRE3_F32 && m >= k && m > 0 && c->N > 0); PRE3_TRY(scope.rc);
-    static const bool trace = getenv("PRE3_STEP_TRACE") != nullptr;     // host-side stage clock (debug): where the host spends a step
+    const bool trace = knob::step_trace();
     static double acc[8], t_prev_end = 0; static int nacc = 0;
     auto now = [] { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e6 + t.tv_nsec * 1e-3; };
     double t0 = trace ? now() : 0, t1 = 0, t5 = 0;
@@ -597,7 +591,7 @@ static int step_front(pre3_ctx *c, const double u[7], int m, const int32_t *meas
     // mono_slam.m:153 + search_IC_matches.m:31-32: prediction, with the projection of every landmark at x_k_km1 riding in the
     // same launch; then search_IC_matches.m:33-44 (S_i), which also clears the previous frame's inlier flags
     {
-        static const int ride_proj = getenv("PRE3_RIDE_PROJ") ? atoi(getenv("PRE3_RIDE_PROJ")) : 1;      // 0: the projection as its own launch (A/B)
+        const int ride_proj = knob::ride_proj();
         const int rc_p = launch_predict_impl(c, u, ride_proj != 0, (inbox_bytes + 15) / 16, ++c->seq_inbox);
         c->inbox_pending = rc_p == PRE3_OK;
         if (rc_p != PRE3_OK) { c->measurements_set = false; return rc_p; }
@@ -606,8 +600,7 @@ static int step_front(pre3_ctx *c, const double u[7], int m, const int32_t *meas
     c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
     c->projected = true;
     // S_i (which also clears last frame's inlier flags) rides in the H*P launch of the RANSAC stage when there is one
-    static const int ride_env = getenv("PRE3_RIDE_INNOV") ? atoi(getenv("PRE3_RIDE_INNOV")) : 1;
-    c->req.ride_innovation = ride_env && c->N > 0 && m >= k && m > 0;
+    c->req.ride_innovation = knob::ride_innov() && c->N > 0 && m >= k && m > 0;
     if (c->N && !c->req.ride_innovation) PRE3_TRY(launch_innovation(c, 0, 0.0, true));
     c->innovated = true;
     if (trace) t1 = now();

@@ -1843,7 +1843,6 @@ __device__ __forceinline__ void update_x_block(int blk, int n, int r, const T *_
     if (rg == 0 && i < n) x_out[i] = s;
 }
 
-static inline int k9_write_through() { static const int v = getenv("PRE3_K9_WT") ? atoi(getenv("PRE3_K9_WT")) : 1; return v; }
 struct XUpd { int n_tiles, n, r; const double *x_prior; double *x_out; double *params;
               const int32_t *gate;
               int nx, wt = 0; };        // (wt: P leaves as write-through stores, store_wt)  x-update workgroups in the launch (0: the state has been updated elsewhere -- the riders behind the tiles are all projection blocks)   // gate != nullptr (the speculative down-date behind k_hi_fused): run only if gate[8] == 1, with r = 2 * gate[5] rows
@@ -2312,8 +2311,6 @@ int launch_ell_HP(pre3_ctx *c, int r, void *dst, bool with_nu)
     return PRE3_OK;
 }
 
-static inline int hp_build_mb() { static const int v = getenv("PRE3_HP_MB") ? atoi(getenv("PRE3_HP_MB")) : 1; return v; }      // 0: one measurement per workgroup (k_ell_HP_build)
-
 // the same for a subset: row pair a = measurement sel[a] (sel == nullptr: a), a < nsel; the padding up to r_pad is zero rows
 int launch_ell_HP_build_sel(pre3_ctx *c, int nsel, const int32_t *sel_dev, void *dst)
 {
@@ -2327,7 +2324,7 @@ int launch_ell_HP_build_sel(pre3_ctx *c, int nsel, const int32_t *sel_dev, void 
         ir = InnovRide{ rows * gx, c->N, c->ld, (int)(c->flags_bytes / sizeof(int32_t)), c->lm.type, c->lm.off, c->lm.has_h, c->P, c->lm.Hc, c->lm.Hl,
                         c->lm.S, c->lm.has_S, (int32_t *)((unsigned char *)c->inbox_dev + c->off_flags) };
     }
-    if (hp_build_mb() > 0) {
+    if (knob::hp_mb() > 0) {
         constexpr int MBF = 4, MBD = 2;
         auto kd = k_ell_HP_build_mb<double, MBD>; auto kf = k_ell_HP_build_mb<float, MBF>;
         const int nyg = c->dtype == PRE3_F32 ? ceil_div(ny, MBF) : ceil_div(ny, MBD);
@@ -2367,12 +2364,11 @@ int launch_ell_HP_build(pre3_ctx *c, void *dst, const int32_t *need, int need_ta
     }
     // PRE3_OPT_PEND_HI: this launch (rows of ALL measurements at the predicted state, S_i riding) reads P - W~'W~; every other form runs behind the flush
     PendW pw = pend_args(c);
-    if (pw.rows > 0 && !(hp_build_mb() > 0 && c->dtype == PRE3_F32 && need == nullptr)) { PRE3_TRY(pend_flush(c)); pw = PendW{}; }
+    if (pw.rows > 0 && !(knob::hp_mb() > 0 && c->dtype == PRE3_F32 && need == nullptr)) { PRE3_TRY(pend_flush(c)); pw = PendW{}; }
     if (pw.rows > 0) { ir.pend_W = pw.W; ir.pend_ldw = pw.ldw; ir.pend_rows = pw.rows; }
-    if (hp_build_mb() > 0 && need == nullptr) {      // (a sharded round's slice -- need != nullptr -- skips most measurements: one per workgroup, k_ell_HP_build, returns at once for those)
+    if (knob::hp_mb() > 0 && need == nullptr) {      // (a sharded round's slice -- need != nullptr -- skips most measurements: one per workgroup, k_ell_HP_build, returns at once for those)
         constexpr int MBF = 4, MBD = 2;
-        static const int mbp = getenv("PRE3_PEND_MB") ? atoi(getenv("PRE3_PEND_MB")) : 4;      // measurements per workgroup of the pending form: 4 (17.1 -> 16.5 us with their landmark rows gathered two at a time); 8 halves the loads of W~ but leaves 156 workgroups for 256 CUs (18.7 us), 2 doubles them (21.5 us)
-        const int mbf = pw.rows > 0 ? (mbp == 8 ? 8 : 4) : MBF;
+        const int mbf = pw.rows > 0 ? (knob::pend_mb() == 8 ? 8 : 4) : MBF;
         auto kd = k_ell_HP_build_mb<double, MBD>; auto kf = pw.rows > 0 ? (mbf == 8 ? k_ell_HP_build_mb<float, 8, true> : k_ell_HP_build_mb<float, 4, true>) : k_ell_HP_build_mb<float, MBF, false>;
         const int nyg = c->dtype == PRE3_F32 ? ceil_div(ny, mbf) : ceil_div(ny, MBD);
         dim3 g(gx, nyg + (ir.n_blocks ? ir.n_blocks / gx : 0) + ib_rows), b(256);
@@ -2437,13 +2433,11 @@ static int launch_chol_solve(pre3_ctx *c, int r_pad, bool first_done = false, bo
     if (!first_done && (nrb >= 2 || predicted_prior) && cholp_usable(c, nrb)) return launch_cholp(c, nrb, nrb, r, which_prior);
     {
         const bool split = c->k9_b3 && c->dtype == PRE3_F32 && c->Wp != nullptr;
-        static const int pro_env = getenv("PRE3_CHOL_PRO_B3") ? atoi(getenv("PRE3_CHOL_PRO_B3")) : 1;
-        const bool pro_planes = split && pro_env && c->Sp != nullptr;       // pending updates on the bf16 MFMA as well
-        static const int early_env = getenv("PRE3_CHOL_EARLY") ? atoi(getenv("PRE3_CHOL_EARLY")) : 1;
-        const int rows_last = (early_env && r > 0 && r <= r_pad && r > r_pad - NB) ? r - (r_pad - NB) : 0;      // real rows of the last panel (0: unknown / switched off)
+        const bool pro_planes = split && knob::chol_pro_b3() && c->Sp != nullptr;       // pending updates on the bf16 MFMA as well
+        const int rows_last = (knob::chol_early() && r > 0 && r <= r_pad && r > r_pad - NB) ? r - (r_pad - NB) : 0;      // real rows of the last panel (0: unknown / switched off)
         // a trailing update with far more tiles than k_chol_step has slots (2 workgroups per CU: its 75 KB of LDS) goes out as a launch
         // of its own (no LDS, 8 workgroups per CU)
-        static const int trail_split = getenv("PRE3_CHOL_TRAIL_SPLIT") ? atoi(getenv("PRE3_CHOL_TRAIL_SPLIT")) : 4;
+        const int trail_split = knob::chol_trail_split();
         auto n_trail = [&](int J) { const int nK = J >= 1 ? nrb - J - 1 : 0; return nK * (nK + 1) / 2 + nK * nW; };      // tiles of panel J-1's update of the column blocks >= J+1
         auto own_trail_at = [&](int J) { return pro_planes && trail_split > 0 && n_trail(J) > trail_split * 2 * c->num_cus; };
         // Round 5: where the trailing update is a launch of its own it is bound by the read-modify-write of W's remaining rows (N = 2000: 4.8 GB per
@@ -2452,7 +2446,7 @@ static int launch_chol_solve(pre3_ctx *c, int r_pad, bool first_done = false, bo
         // a group: the whole group before it; the t-th: the t panels of its own group in front of it).  Every product is rounded and subtracted in
         // the order of the one-panel sweep: the same bits (PRE3_CHOL_TRAIL_P=1: that sweep).  The grouping ends with the first panel Jt of a group
         // from which on the update is small enough to ride in the panels' launches.
-        static const int trail_p = std::min(4, std::max(1, getenv("PRE3_CHOL_TRAIL_P") ? atoi(getenv("PRE3_CHOL_TRAIL_P")) : 4));
+        const int trail_p = std::min(4, std::max(1, knob::chol_trail_p()));
         int Jt = 0;
         if (trail_p > 1 && own_trail_at(1)) { Jt = trail_p; while (Jt < nrb && own_trail_at(Jt)) Jt += trail_p; }
         for (int J = first_done ? 1 : 0; J < nrb; ++J) {
@@ -2485,7 +2479,7 @@ static int launch_chol_solve(pre3_ctx *c, int r_pad, bool first_done = false, bo
             if (paired && J % trail_p == trail_p - 1 && J + 2 <= nrb - 1) {
                 // the group J-p+1 .. J on everything from column block J+2 on
                 const int nK2 = nrb - (J + 2), nT2 = nK2 * (nK2 + 1) / 2 + nK2 * nW;
-                static const int t128 = getenv("PRE3_CHOL_TRAIL_T128") ? atoi(getenv("PRE3_CHOL_TRAIL_T128")) : 2;      // W part in 128 x 128 super-tiles: 2 = operands staged through LDS, 1 = fragments straight from memory (0: 64 x 64 tiles)
+                const int t128 = knob::chol_trail_t128();
                 if (t128 == 2) {
                     static std::atomic<bool> attr{ false };
                     if (!attr.exchange(true)) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_chol_trail_b3l), hipFuncAttributeMaxDynamicSharedMemorySize, TL_NSLOT * TL_STAGE * 16);
@@ -2513,10 +2507,9 @@ int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior, int plan
     int r_pad = round_up(r, NB);
     // persistent grid: 2 workgroups per CU (or one per tile when there are fewer tiles); the tile counter is
     // monotonic across launches (each launch consumes grid + n_tiles tickets), reset long before it could wrap
-    static const int wgs_per_cu = getenv("PRE3_K9_WGS") ? atoi(getenv("PRE3_K9_WGS")) : 3;
-    const int gsz = std::min(c->n_tiles, wgs_per_cu * c->num_cus);
+    const int gsz = std::min(c->n_tiles, knob::k9_wgs() * c->num_cus);
     dim3 g(gsz), b(256);
-    static const int force = getenv("PRE3_K9_FORM") ? atoi(getenv("PRE3_K9_FORM")) : 0;     // 1: one-tile, 2: persistent (experiments)
+    const int force = knob::k9_form();
     // all tiles resident at once: 5 workgroups/CU in fp32 (16.9 KB of LDS each), 4 in fp64 (33.8 KB)
     const bool one_tile = force == 1 || (force == 0 && c->n_tiles <= 5 * c->num_cus);
     // fp32: three-way bf16 split on the bf16 matrix cores (k_split_w + k_downdate_b3); PRE3_K9_B3=0 keeps the f32-MFMA forms
@@ -2560,7 +2553,7 @@ int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior, int plan
         }
         c->out.dd_done = 0;
         XUpd xu{ n_tiles_launch, c->n, r, which_prior == PRE3_X_K_K ? c->x_kk : c->x_km1, c->x_kk, c->pred_params, nullptr, 0 };
-        xu.wt = k9_write_through();
+        xu.wt = knob::k9_wt();
         const bool x_done = c->out.x_done && which_prior >= 0;        // the factorisation's strips have computed x_k_k already
         c->out.x_done = false;
         const int nx = (which_prior >= 0 && !x_done) ? ceil_div(c->n, 64) : 0;
@@ -2581,7 +2574,7 @@ int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior, int plan
         }
     } else if (one_tile) {
         XUpd xu{ c->n_tiles, c->n, r, which_prior == PRE3_X_K_K ? c->x_kk : c->x_km1, c->x_kk, c->pred_params, nullptr, 0 };
-        xu.wt = k9_write_through();
+        xu.wt = knob::k9_wt();
         const int nx = which_prior >= 0 ? ceil_div(c->n, 64) : 0;
         xu.nx = nx;
         ProjRide pr{};
@@ -2591,7 +2584,7 @@ int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior, int plan
         }
         dim3 g1(c->n_tiles + nx + pr.n_blocks);
         // fp64 with few tiles per CU (configs[1]: 210 tiles on 256 CUs): two waves per wave tile, so that every SIMD has two waves to overlap
-        static const int nw8_env = getenv("PRE3_K9_F64_NW8") ? atoi(getenv("PRE3_K9_F64_NW8")) : 3;      // (measured at n = 1213, r = 320: 0: 24.3 us; 1 (16-row stages, 8 waves): 30.5; 2 (32-row stages): 24.8; 3 (32-row stages, 8 waves): 22.5)
+        const int nw8_env = knob::k9_f64_nw8();
         if (c->dtype == PRE3_F64 && nw8_env == 1 && c->n_tiles <= 2 * c->num_cus) {
             hipLaunchKernelGGL((k_downdate_1t<double, 16, 8>), g1, dim3(512), 0, c->stream, (double *)c->P, c->ld, (const double *)W, c->ldw, r_pad, (const int2 *)c->tiles_flat, c->num_cus, xu, pr);
         } else if (c->dtype == PRE3_F64 && nw8_env == 2 && c->n_tiles <= 2 * c->num_cus && r_pad % 32 == 0) {
@@ -2620,15 +2613,13 @@ int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior, int plan
 // (stats[8]) and takes its row count from the device.  seq: the mailbox sequence number the collection publishes.
 bool hi_fused_usable(const pre3_ctx *c)
 {
-    static const int env = getenv("PRE3_HI_FUSED") ? atoi(getenv("PRE3_HI_FUSED")) : 1;
-    return env != 0 && c->dtype == PRE3_F32 && c->k9_b3 && c->Wp != nullptr && c->Sp != nullptr && c->m > 0 && c->m <= 16384 && c->rcap >= NB && c->N > 0;
+    return knob::hi_fused() != 0 && c->dtype == PRE3_F32 && c->k9_b3 && c->Wp != nullptr && c->Sp != nullptr && c->m > 0 && c->m <= 16384 && c->rcap >= NB && c->N > 0;
 }
 
 // landmarks k_hi_fused updates with on its own: 64 (two panels) when the row capacity holds them (PRE3_HI_FUSED_TWO=0: one panel, A/B)
 int hi_fused_max(const pre3_ctx *c)
 {
-    static const int two_env = getenv("PRE3_HI_FUSED_TWO") ? atoi(getenv("PRE3_HI_FUSED_TWO")) : 1;
-    return two_env != 0 && c->rcap >= 2 * NB ? HF_MAXL2 : HF_MAXL;
+    return knob::hi_fused_two() != 0 && c->rcap >= 2 * NB ? HF_MAXL2 : HF_MAXL;
 }
 
 PendW pend_args(const pre3_ctx *c)
@@ -2644,7 +2635,7 @@ int pend_flush(pre3_ctx *c)
     const int rows = c->carry.pend_rows;
     c->carry.pend_rows = 0;
     XUpd xu{ c->n_tiles128, c->n, 0, c->x_kk, c->x_kk, c->pred_params, nullptr, 0 };
-    xu.wt = k9_write_through();
+    xu.wt = knob::k9_wt();
     ProjRide pr{};
     hipLaunchKernelGGL(k_downdate_b3, dim3(c->n_tiles128), dim3(256), 0, c->stream, (float *)c->P, c->ld, (const bf16x8_t *)c->Wp_pend, c->rcap / B3_BK, rows > NB ? 8 : 4,
                        (const float *)c->W_pend, c->ldw, (const int2 *)c->tiles128, xu, pr);
@@ -2664,13 +2655,11 @@ int launch_hi_fused(pre3_ctx *c, int32_t seq)
     a.P = (const float *)c->P; a.ld = c->ld; a.S = (float *)c->Smat; a.W = (float *)c->W; a.ldw = c->ldw;
     a.Wp = c->Wp; a.nst_total = c->rcap / B3_BK; a.Sp = c->Sp; a.sp_stride = c->rcap / NB; a.params = c->pred_params;
     a.max_l = hi_fused_max(c);
-    static const int deal_env = getenv("PRE3_HF_DEAL") ? atoi(getenv("PRE3_HF_DEAL")) : 1;      // 0: every workgroup builds all of S in the two-panel case too (round 5)
     // (the dealt S and the pending form's state update make workgroups of this launch wait for one another: only when all of them are resident together --
     //  one per CU: each declares more than half a CU's LDS)
     const bool co_resident = 1 + c->ldw / NB <= c->num_cus;
-    a.sx = deal_env && co_resident ? c->hf_sx : nullptr;
-    static const int deal_min = getenv("PRE3_HF_DEAL_MIN") ? atoi(getenv("PRE3_HF_DEAL_MIN")) : 18;      // measured, k_hi_fused at 4 .. 32 landmarks: dealt 14.4 14.7 15.7 16.3 17.0 17.5 19.1 us, every workgroup for itself 12.3 13.4 14.7 16.4 17.4 18.6 22.8
-    a.deal_min = deal_min;
+    a.sx = knob::hf_deal() && co_resident ? c->hf_sx : nullptr;
+    a.deal_min = knob::hf_deal_min();
     // PRE3_OPT_PEND_HI: W~ and its planes go to buffers of their own (the next LI update's strips overwrite W / Wp), the launch behind this one carries
     // the x-update only, and P - W~'W~ stays pending (pre3_update_hi learns the row count; pend_flush / launch_cholp end it)
     const bool pend = c->pend_opt && c->W_pend != nullptr && c->Wp_pend != nullptr && c->hf_xy != nullptr && co_resident;
@@ -2685,7 +2674,7 @@ int launch_hi_fused(pre3_ctx *c, int32_t seq)
     // the down-date of that update (one or two panels: four or eight k-stages, read on the device), the x-update riding along; every workgroup leaves at once unless stats[8] == 1
     const int nx = ceil_div(c->n, 64);
     XUpd xu{ c->n_tiles128, c->n, 0, c->x_kk, c->x_kk, c->pred_params, c->stats, nx };
-    xu.wt = k9_write_through();
+    xu.wt = knob::k9_wt();
     ProjRide pr{};
     hipLaunchKernelGGL(k_downdate_b3, dim3(c->n_tiles128 + nx), dim3(256), 0, c->stream, (float *)c->P, c->ld, (const bf16x8_t *)c->Wp, c->rcap / B3_BK, 4,
                        (const float *)c->W, c->ldw, (const int2 *)c->tiles128, xu, pr);
@@ -2765,8 +2754,7 @@ int launch_chol_first_spec(pre3_ctx *c, int nsel_max)
     const int nrb_max = round_up(2 * nsel_max, NB) / NB, nS_max = nrb_max - 1, nW = c->ldw / NB;
     if (nrb_max <= 0) return PRE3_OK;
     const bool split = c->k9_b3 && c->dtype == PRE3_F32 && c->Wp != nullptr;
-    static const int pro_env = getenv("PRE3_CHOL_PRO_B3") ? atoi(getenv("PRE3_CHOL_PRO_B3")) : 1;
-    const bool pro_planes = split && pro_env && c->Sp != nullptr;
+    const bool pro_planes = split && knob::chol_pro_b3() && c->Sp != nullptr;
     const int nP = 1 + nS_max + nW;
     c->chol_target += (unsigned)(nP - 1);
     DISPATCH_T(c,
