@@ -70,6 +70,15 @@ lib.pre3_sr_frame_sift_refined.argtypes = [_P, _P, _P]
 lib.pre3_sr_text_limits.argtypes = [_P, _P]
 lib.pre3_sr_text_parse.argtypes = [_I, _P, C.c_size_t, _P, C.c_size_t, _P]
 lib.pre3_sr_frame_load_text.argtypes = [_P, _I, _P, C.c_size_t, _P]
+lib.pre3_set_image.argtypes = [_P, _I, _I, _P]
+lib.pre3_get_image.argtypes = [_P, _I, _I, _P]
+lib.pre3_set_image_frame.argtypes = [_P, _P]
+lib.pre3_set_patches.argtypes = [_P, _I, _I, _P, _P, _P, _P]
+lib.pre3_get_patches.argtypes = [_P, _I, _I, _P, _P, _P, _P, _P]
+lib.pre3_patch_cut.argtypes = [_P, _I, _I, _P]
+lib.pre3_predict_patches.argtypes = [_P, _D, _P, _P]
+lib.pre3_patch_search.argtypes = [_P, _D, _D, _I, _P, _P, _P, _P, _P, _P]
+lib.pre3_patch_timing.argtypes = [_P, _P, _P]
 
 F64, F32 = 0, 1
 INVDEPTH, CARTESIAN = 0, 1
@@ -139,4 +148,6 @@ EXPORTS = [
     "pre3_set_process_noise", "pre3_get_process_noise", "pre3_vo_cov", "pre3_vo_pair_cov_seeded", "pre3_predict_pair_cov_seeded",
     "pre3_sift_plan_get", "pre3_sr_frame_sift", "pre3_sr_frame_gate", "pre3_sr_frame_sift_level", "pre3_sr_frame_sift_refined",
     "pre3_sr_text_limits", "pre3_sr_text_parse", "pre3_sr_frame_load_text",
+    "pre3_set_image", "pre3_get_image", "pre3_set_image_frame", "pre3_set_patches", "pre3_get_patches", "pre3_patch_cut", "pre3_predict_patches",
+    "pre3_patch_search", "pre3_patch_timing",
 ]

@@ -15,6 +15,7 @@
 #include "pre3_predictcv.h"
 #include <mutex>
 #include "pre3_cholp.h"
+#include "pre3_patch.h"
 
 namespace pre3 {
 
@@ -555,6 +556,7 @@ int pre3_destroy(pre3_ctx *c)
     free_rows(c);
     free_plane(c);
     free_policy(c);
+    free_patch(c);
     for (int k2 = 0; k2 < 2; ++k2) { if (c->map_stage[k2]) (void)hipHostFree(c->map_stage[k2]); if (c->map_stage_ev[k2]) (void)hipEventDestroy(c->map_stage_ev[k2]); }
     for (int k2 = 0; k2 < 2; ++k2) { if (c->up_stage[k2]) (void)hipHostFree(c->up_stage[k2]); if (c->up_stage_ev[k2]) (void)hipEventDestroy(c->up_stage_ev[k2]); }
     if (c->pinned_stats) (void)hipHostFree(c->pinned_stats);
@@ -653,6 +655,7 @@ int pre3_set_map(pre3_ctx *c, int N, const int32_t *lm_type)
     c->m = 0; c->meas_host.clear(); c->measurements_set = false; c->projected = false; c->innovated = false;
     c->x_valid[0] = c->x_valid[1] = false; c->p_which = -1;
     c->booked = false; c->book_s = 0;             // a new map has no book until pre3_set_book (or an empty map's first pre3_map_policy)
+    patch_drop_bank(c);                           // ... and no patches (pre3_patch.hip; nothing is queued when there is no bank)
     return PRE3_OK;
 }
 
@@ -1181,6 +1184,54 @@ int pre3_ic_search(pre3_ctx *c, double thresh, int strict_reference, int32_t *n_
     if (meas_idx_out) for (int j = 0; j < m; ++j) meas_idx_out[j] = meas[j];
     if (z_out) { const double *zz = (const double *)(blk.data() + 4 + 4 * capN); for (int j = 0; j < 2 * m; ++j) z_out[j] = zz[j]; }
     return install_measurements(c, (int)meas.size(), meas.data(), nullptr, nullptr, 0);
+}
+
+// ---- the patch branch of the IC search (search_IC_matches.m:45-51; pre3_patch.hip) ---------------
+int pre3_set_image(pre3_ctx *c, int nRows, int nCols, const uint8_t *im)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return patch_set_image(c, nRows, nCols, im);
+}
+int pre3_get_image(pre3_ctx *c, int nRows, int nCols, uint8_t *im)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return patch_get_image(c, nRows, nCols, im);
+}
+int pre3_set_image_frame(pre3_ctx *c, pre3_sr_frame *f)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return patch_set_image_frame(c, f);
+}
+int pre3_set_patches(pre3_ctx *c, int first, int count, const uint8_t *patch, const double *uv_init, const double *r_wc, const double *R_wc)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return patch_set_patches(c, first, count, patch, uv_init, r_wc, R_wc);
+}
+int pre3_get_patches(pre3_ctx *c, int first, int count, uint8_t *patch, double *uv_init, double *r_wc, double *R_wc, int32_t *has_patch)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return patch_get_patches(c, first, count, patch, uv_init, r_wc, R_wc, has_patch);
+}
+int pre3_patch_cut(pre3_ctx *c, int first, int count, const int32_t *uv)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return patch_cut(c, first, count, uv);
+}
+int pre3_predict_patches(pre3_ctx *c, double focal_over_d, double *patch_out, int32_t *status_out)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return patch_predict(c, focal_over_d, patch_out, status_out);
+}
+int pre3_patch_search(pre3_ctx *c, double focal_over_d, double corr_threshold, int strict_reference, int32_t *m_out, int32_t *meas_idx_out,
+                      double *z_out, double *corr_out, int32_t *ncand_out, int32_t *status_out)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return patch_search(c, focal_over_d, corr_threshold, strict_reference, m_out, meas_idx_out, z_out, corr_out, ncand_out, status_out);
+}
+int pre3_patch_timing(pre3_ctx *c, double *warp_ms_out, double *search_ms_out)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return patch_timing(c, warp_ms_out, search_ms_out);
 }
 
 // ---- RCCL communicator on the context (pre3_comm.hip) ------------------------------------------------

@@ -16,6 +16,7 @@
 #include "pre3_geomdev.h"
 #include "pre3_philox.h"
 #include "pre3_vopair.h"
+#include "pre3_patch.h"
 
 namespace pre3 {
 
@@ -448,6 +449,7 @@ static int apply_map(pre3_ctx *c, const std::vector<int32_t> &desc, int n_new, c
     PRE3_HIP(hipGetLastError());
     if (with_bank) std::swap(c->bank, c->bank_alt);
     if (with_book) std::swap(c->book, c->book_alt);
+    PRE3_TRY(patch_follow_map(c, N, d_src));       // the patch bank, when there is one: a launch of its own behind the congruence (pre3_patch.hip)
     c->N = N; c->n = n; c->lm_type_host = new_types;
     c->m = 0; c->meas_host.clear(); c->measurements_set = false; c->projected = false; c->innovated = false; c->hp_all_valid = false;
     c->li_from_host = c->hi_from_host = -1; c->li_kernel = c->hi_kernel = false;

@@ -463,6 +463,76 @@ class EkfFilter:
         return dict(meas_idx=meas[:self.m].copy(), z=z[:self.m].copy(), match_idx=pairs[:nm.value, :2].T.copy(),
                     accepted=pairs[:nm.value, 2].copy())
 
+    # ---- the patch branch of the IC search (search_IC_matches.m:45-51: predict_features_appearance.m + matching.m)
+    PATCH_STATUS = ("not_predicted", "no_patch", "zero_patch", "warp_outside", "no_candidate", "below_threshold", "matched", "warped")
+
+    def set_image(self, im):
+        """The frame the patch search reads: (nRows, nCols) uint8, the camera's shape.  Copied before the call returns, no wait."""
+        im = np.asarray(im)
+        assert im.ndim == 2 and im.dtype == np.uint8, "the image is a 2-D uint8 array"
+        imf = np.asfortranarray(im)                       # column-major, as MATLAB stores it
+        check(lib.pre3_set_image(self._ctx, int(im.shape[0]), int(im.shape[1]), imf.ctypes.data_as(C.c_void_p)))
+
+    def get_image(self, shape):
+        out = np.zeros(shape, np.uint8, order="F")
+        check(lib.pre3_get_image(self._ctx, int(shape[0]), int(shape[1]), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def set_image_frame(self, frame):
+        """set_image from a resident sr4000.SrFrame's filtered image plane: converted on the device, nothing read back, no wait."""
+        check(lib.pre3_set_image_frame(self._ctx, frame._h))
+
+    def set_patches(self, patch, uv_init, r_wc, R_wc, first=0):
+        """features_info(first+i).patch_when_initialized (count, 41, 41) uint8 indexed [i, row, column], uv_when_initialized (count, 2),
+        r_wc_when_initialized (count, 3), R_wc_when_initialized (count, 3, 3).  The bank follows the map like the descriptor bank."""
+        patch = np.asarray(patch)
+        assert patch.dtype == np.uint8 and patch.ndim == 3 and patch.shape[1:] == (41, 41), "patches are (count, 41, 41) uint8"
+        k = int(patch.shape[0])
+        pb = np.ascontiguousarray(patch.transpose(0, 2, 1))            # each patch column-major
+        uv, r = f64(np.asarray(uv_init, dtype=np.float64).reshape(k, 2)), f64(np.asarray(r_wc, dtype=np.float64).reshape(k, 3))
+        R = np.ascontiguousarray(np.asarray(R_wc, dtype=np.float64).reshape(k, 3, 3).transpose(0, 2, 1))
+        check(lib.pre3_set_patches(self._ctx, int(first), k, pb.ctypes.data_as(C.c_void_p), dptr(uv), dptr(r), dptr(R)))
+
+    def patches(self, first=0, count=None):
+        """The bank as dict(patch (count, 41, 41) uint8, uv_init, r_wc, R_wc (count, 3, 3), has_patch (count,) bool)."""
+        count = self.N - int(first) if count is None else int(count)
+        k = max(count, 1)
+        pb, uv, r, R, has = np.zeros((k, 41, 41), np.uint8), np.zeros((k, 2)), np.zeros((k, 3)), np.zeros((k, 3, 3)), np.zeros(k, np.int32)
+        check(lib.pre3_get_patches(self._ctx, int(first), count, pb.ctypes.data_as(C.c_void_p), dptr(uv), dptr(r), dptr(R), dptr(has)))
+        return dict(patch=pb[:count].transpose(0, 2, 1).copy(), uv_init=uv[:count].copy(), r_wc=r[:count].copy(),
+                    R_wc=R[:count].transpose(0, 2, 1).copy(), has_patch=has[:count].astype(bool))
+
+    def patch_cut(self, uv, first=0):
+        """add_feature_to_info_vector_my_version.m:33-41 on the device: 41 x 41 around the integer pixels uv (count, 2) = (column, row), 1-based,
+        out of the resident image; r_wc and q2r(q) from the resident x_k_k."""
+        uv = i32(np.asarray(uv).reshape(-1, 2))
+        check(lib.pre3_patch_cut(self._ctx, int(first), int(uv.shape[0]), dptr(uv)))
+
+    def predict_features_appearance(self, focal_over_d):
+        """predict_features_appearance.m behind a projection at x_k_km1: (patches (N, 13, 13) indexed [i, row, column], status (N,))."""
+        k = max(self.N, 1)
+        out, st = np.zeros((k, 13, 13)), np.zeros(k, np.int32)
+        check(lib.pre3_predict_patches(self._ctx, float(focal_over_d), dptr(out), dptr(st)))
+        return out[:self.N].transpose(0, 2, 1).copy(), st[:self.N].copy()
+
+    def search_ic_matches_patch(self, focal_over_d, corr_threshold=0.60, strict_reference=True):
+        """search_IC_matches.m:31-51 on the patch branch in one call; the accepted landmarks become the measurement list.
+        Returns meas_idx, z (m, 2), corr (N,), ncand (N,), status (N,: indices into PATCH_STATUS)."""
+        k = max(self.N, 1)
+        m = C.c_int32(0)
+        meas, z, corr, ncand, st = np.zeros(k, np.int32), np.zeros((k, 2)), np.zeros(k), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        check(lib.pre3_patch_search(self._ctx, float(focal_over_d), float(corr_threshold), int(bool(strict_reference)), C.byref(m), dptr(meas), dptr(z),
+                                    dptr(corr), dptr(ncand), dptr(st)))
+        self.m = int(m.value)
+        self.meas_idx = meas[:self.m].copy()
+        return meas[:self.m].copy(), z[:self.m].copy(), corr[:self.N].copy(), ncand[:self.N].copy(), st[:self.N].copy()
+
+    def patch_timing(self):
+        """(k_patch_warp ms, k_patch_search ms) of the last search_ic_matches_patch under kernel timing."""
+        a, b = C.c_double(0), C.c_double(0)
+        check(lib.pre3_patch_timing(self._ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     # ---- step stages
     def ekf_prediction(self, u):
         u = f64(u)

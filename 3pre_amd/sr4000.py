@@ -175,6 +175,10 @@ class SrFrame:
         check(lib.pre3_sr_frame_get(self._h, None, None, None, dptr(img), None, None, None))
         return img.astype(np.uint8)
 
+    def feed_image(self, filt):
+        """this frame's filtered image as the frame an ekf.EkfFilter's patch search reads (pre3_set_image_frame): on the device, no wait"""
+        filt.set_image_frame(self)
+
     def maxima(self):
         """(imax, cmax)"""
         imax, cmax = C.c_double(0), C.c_double(0)

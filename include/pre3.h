@@ -429,6 +429,66 @@ PRE3_API int pre3_set_scan(pre3_ctx *ctx, int K2, const double *descriptor_raw, 
 PRE3_API int pre3_ic_search(pre3_ctx *ctx, double thresh, int strict_reference, int32_t *n_matches_out, int32_t *m_out,
                             int32_t *meas_idx_out, double *z_out, int32_t *pairs_out);
 
+/* ---- the patch branch of the IC search: warped patches and NCC in the S-ellipse (search_IC_matches.m:45-51) -------------------
+ * FEATURE_EXTRACTOR == 'FAST': predict_features_appearance.m:34-53 + pred_patch_fc.m:27-85 warp every predicted landmark's stored 41 x 41 patch
+ * (add_feature_to_info_vector_my_version.m:29-41: half_patch_size_when_initialized = 20) to the predicted view as a 13 x 13 patch
+ * (half_patch_size_when_matching = 6), and mex_files/CorePar_Ver1/matching.m:39-146 takes the best Pearson correlation (corrcoef) of that patch with
+ * im(i-6:i+6, j-6:j+6) over the integer pixels (j, i) inside the 95 % ellipse of S_i (chi_095_2 = 5.9915, :36, :80).  Pixels are the reference's
+ * 1-based coordinates; the image and the patches are column-major bytes, as MATLAB stores uint8.  All patch arithmetic is fp64 in both context dtypes.
+ *   warp   pred_patch_fc.m:33-34: h outside the open band (6, nCols - 6) x (6, nRows - 6) gives the zero patch (:84), whose correlation with anything is
+ *          NaN.  :40, :43: H_Wk_p_f = [R 0; 0 1] [I r; 0 1] = [R, R r] (the uncommented lines), H_kpf_k = inv(H_Wk_p_f) H_Wk (:46).  :52-53: the normals
+ *          carry f/d = cam.F / cam.dx, which pre3_cam does not hold: it is the argument focal_over_d (the fork: 250.57731 / (4/176 * 0.001); Civera's
+ *          f / dx in pixels works as well).  :66: the patch centre is rotate_with_dist_fc_c2c1.m:41-50 of uv_when_initialized; :68-74: the 13 x 13 integer
+ *          grid around that sub-pixel centre goes back through rotate_with_dist_fc_c1c2.m:40-43 -- both over undistort_fm_my_version.m:56-81 (ten Newton
+ *          steps, :64-67) and distort_fm_my_version.m:52-61 --, is shifted by uv_when_initialized - 20 - 1 (:75-76) and read with interp2 (:81), linear;
+ *          a sample outside [1, 41] in either coordinate is NaN, and one NaN makes every correlation of the landmark NaN.
+ *   search matching.m:61-62: the box ceil(5 sqrt(S(1,1))) x ceil(5 sqrt(S(2,2))) around round(h) (only a bound: sqrt(5.9915) < 5 and S >= R = I);
+ *          :74-82: candidates in the order j (column, outer), i (row, inner), kept when nu' inv(S) nu < 5.9915 and j > 6 && j < nCols - 6 && i > 6 &&
+ *          i < nRows - 6; a flat image patch gives NaN, which max ignores; :121: accepted when maximum_correlation > corr_threshold (0.60 in the fork,
+ *          :31; 0.80 in the original, :29); ties go to the first maximum in candidate order.
+ *          strict_reference = 0: the original line :115 -- the maximum over all K candidates, z that candidate.
+ *          strict_reference = 1: what the fork runs, :118's correlation_matrix(2:end, 1) over corrcoef_partitioned.m:3-21.  With n = K + 1 < 100 the
+ *          first candidate is dropped from the maximum and z is the candidate BEFORE the best one in scan order (K <= 1: no match); with n >= 100 the
+ *          maximum is over candidates 1 .. 100 floor(n / 100) - 1 only and z is the best of those (the tail is lost).
+ *          last_visible (:124) and the MaxInnov print are not part of this. */
+#define PRE3_PATCH_NOT_PREDICTED 0     /* isempty(h): not searched */
+#define PRE3_PATCH_NO_PATCH 1          /* the landmark has no stored patch (none set or cut since it was added): not searched */
+#define PRE3_PATCH_ZERO 2              /* h in the border band: the zero patch, every correlation NaN */
+#define PRE3_PATCH_OUTSIDE 3           /* the warp left the stored patch: a NaN sample, every correlation NaN */
+#define PRE3_PATCH_NO_CANDIDATE 4      /* K == 0 */
+#define PRE3_PATCH_BELOW 5             /* searched; the maximum is not above the threshold (or NaN) */
+#define PRE3_PATCH_MATCHED 6
+#define PRE3_PATCH_WARPED 7            /* pre3_predict_patches only: the predicted patch is valid */
+/* The frame the search reads, nRows x nCols column-major bytes, resident until the next one.  The shape must be the camera's (PRE3_E_ARG; rows and
+ * columns 15 .. 1024).  Asynchronous like pre3_set_scan: copied into pinned memory of the context's and pulled on its stream. */
+PRE3_API int pre3_set_image(pre3_ctx *ctx, int nRows, int nCols, const uint8_t *im);
+PRE3_API int pre3_get_image(pre3_ctx *ctx, int nRows, int nCols, uint8_t *im_out);                  /* synchronises; PRE3_E_STATE without an image */
+/* (pre3_set_image_frame, below with pre3_set_scan_frame, takes the image from a resident SR4000 frame) */
+/* The per-landmark bank for landmarks first .. first+count-1: patch_when_initialized (1681 bytes each, 41 x 41 column-major), uv_when_initialized (2),
+ * r_wc_when_initialized (3), R_wc_when_initialized (9, column-major).  The bank follows the map through every pre3_map_* call and the policy calls,
+ * like the descriptor bank: deleted landmarks drop out, survivors keep their patch under their new index, a new landmark has no patch until one is
+ * set or cut and is not searched until then; pre3_set_map drops the bank.  The re-layout is one launch of its own behind the map call's, queued only
+ * when a bank exists.  Asynchronous.  pre3_get_patches: any output may be NULL; has_patch_out[count] 0 / 1; a landmark without one reads zeros. */
+PRE3_API int pre3_set_patches(pre3_ctx *ctx, int first, int count, const uint8_t *patch, const double *uv_init, const double *r_wc, const double *R_wc);
+PRE3_API int pre3_get_patches(pre3_ctx *ctx, int first, int count, uint8_t *patch_out, double *uv_init_out, double *r_wc_out, double *R_wc_out,
+                              int32_t *has_patch_out);
+/* add_feature_to_info_vector_my_version.m:33-41 on the device: 41 x 41 around the integer pixels uv[2 count] (u = column, v = row, 1-based) out of the
+ * resident image, r_wc and q2r(q) from the resident x_k_k.  A patch that leaves the image: PRE3_E_ARG before anything is queued.  Asynchronous. */
+PRE3_API int pre3_patch_cut(pre3_ctx *ctx, int first, int count, const int32_t *uv);
+/* predict_features_appearance.m alone, behind a projection at x_k_km1 (pre3_project): patch_out[169 N] (may be NULL; per landmark 13 x 13
+ * column-major; zeros unless the status is PRE3_PATCH_WARPED or PRE3_PATCH_OUTSIDE, whose samples outside the stored patch are NaN),
+ * status_out[N] (PRE3_PATCH_NOT_PREDICTED, _NO_PATCH, _ZERO, _OUTSIDE or _WARPED).  Synchronises. */
+PRE3_API int pre3_predict_patches(pre3_ctx *ctx, double focal_over_d, double *patch_out, int32_t *status_out);
+/* One call = search_IC_matches.m:31-51 on the patch branch: h, H, S at the prediction (pre3_ic_search's launch), k_patch_warp, k_patch_search, the
+ * compaction of the accepted into ascending landmark order; one host wait at the end; z / individually_compatible are installed where pre3_ic_search
+ * leaves them, so pre3_step_predicted[_seeded] and pre3_update_all follow.  Needs the predicted estimate in the covariance buffer, a camera and an
+ * image (PRE3_E_STATE).  N == 0: m = 0.  Outputs: *m_out, meas_idx_out[m], z_out[2 m], and per landmark corr_out[N] (maximum_correlation as the mode
+ * computes it; NaN where there is none), ncand_out[N] (K; 0 for a landmark that is not searched), status_out[N] (PRE3_PATCH_*); all but m_out optional. */
+PRE3_API int pre3_patch_search(pre3_ctx *ctx, double focal_over_d, double corr_threshold, int strict_reference, int32_t *m_out,
+                               int32_t *meas_idx_out, double *z_out, double *corr_out, int32_t *ncand_out, int32_t *status_out);
+/* measurement only: with pre3_kernel_timing on, the last pre3_patch_search bracketed k_patch_warp and k_patch_search with events; their times */
+PRE3_API int pre3_patch_timing(pre3_ctx *ctx, double *warp_ms_out, double *search_ms_out);
+
 /* ---- the VO front end's 4-point 3D-3D RANSAC (code_from_dr_ye/) ------------------------------------ */
 typedef struct pre3_vo_result {
     double rot[9];          /* final rotation, row-major (find_transform_matrix_dr_ye.m on the winner's inliers, vodometry_dr_ye.m:221) */
@@ -738,6 +798,10 @@ PRE3_API int pre3_heading_from_frame_seeded(pre3_ctx *ctx, pre3_sr_frame *f, con
  * of other than 128 entries, a handle on another device than the context.  PRE3_E_STATE: a handle without a loaded frame, or without a keypoint
  * result for the frame it holds (none yet, or a pre3_sr_frame_load after it). */
 PRE3_API int pre3_set_scan_frame(pre3_ctx *ctx, pre3_sr_frame *f, int which);
+/* pre3_set_image with the frame taken from the handle's filtered image plane (doubles holding 0 .. 255) instead of the host: one conversion launch on
+ * the context's stream behind an event on the handle's, released as above; nothing crosses PCIe, nothing is read back, the call does not synchronise.
+ * The frame's shape must be the camera's (PRE3_E_ARG); PRE3_E_STATE: a handle without a loaded frame. */
+PRE3_API int pre3_set_image_frame(pre3_ctx *ctx, pre3_sr_frame *f);
 
 /* ---- the prediction fed from a resident VO pair: u never leaves the device -----------------------------------------------------
  * fv.m:47 + Calculate_V_Omega_RANSAC_dr_ye.m:41-50 + predict_state_and_covariance.m:27-143 in one call: the VO front end between the keypoint records of

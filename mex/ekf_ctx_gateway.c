@@ -665,6 +665,48 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         }
         mxFree(meas); mxFree(pairs); mxFree(z); check(rc);
     }
+    else if (!strcmp(cmd, "set_image")) {         /* pre3_mex('set_image', im (uint8, nRows x nCols)): the frame search_IC_matches.m:48-51's patch branch reads; with no argument: the
+                                                     resident SR4000 frame's filtered image, converted on the device */
+        if (nin == 1) {
+            if (!g_sr) mexErrMsgTxt("pre3_mex('set_image'): without an image, call pre3_mex('sr_frame', ...) first");
+            check(pre3_set_image_frame(g_ctx, g_sr));
+        } else {
+            if (mxGetClassID(in[1]) != mxUINT8_CLASS) mexErrMsgTxt("pre3_mex('set_image', im): im must be uint8");
+            check(pre3_set_image(g_ctx, (int)mxGetM(in[1]), (int)mxGetN(in[1]), (const uint8_t *)mxGetData(in[1])));
+        }
+    }
+    else if (!strcmp(cmd, "set_patches")) {       /* pre3_mex('set_patches', patches (uint8, 41 x 41 x k: [features_info.patch_when_initialized]), uv (2 x k), r_wc (3 x k),
+                                                     R_wc (3 x 3 x k) [, first (0-based)]) */
+        int k = (int)mxGetN(in[2]);
+        if (nin < 5 || mxGetClassID(in[1]) != mxUINT8_CLASS || (int)mxGetNumberOfElements(in[1]) != 1681 * k || (int)mxGetNumberOfElements(in[3]) != 3 * k ||
+            (int)mxGetNumberOfElements(in[4]) != 9 * k || (int)mxGetM(in[2]) != 2)
+            mexErrMsgTxt("pre3_mex('set_patches', patches, uv, r_wc, R_wc [, first]): uint8 41 x 41 x k, 2 x k, 3 x k, 3 x 3 x k");
+        check(pre3_set_patches(g_ctx, nin > 5 ? (int)mxGetScalar(in[5]) : 0, k, (const uint8_t *)mxGetData(in[1]), mxGetPr(in[2]), mxGetPr(in[3]), mxGetPr(in[4])));
+    }
+    else if (!strcmp(cmd, "patch_cut")) {         /* pre3_mex('patch_cut', uv (2 x k integer pixels, 1-based) [, first (0-based)]): add_feature_to_info_vector_my_version.m:33-41 */
+        int k = (int)mxGetN(in[1]), i, rc;
+        int32_t *uv = (int32_t *)mxCalloc(2 * (k ? k : 1), sizeof(int32_t));
+        if ((int)mxGetM(in[1]) != 2) mexErrMsgTxt("pre3_mex('patch_cut', uv [, first]): uv is 2 x k");
+        for (i = 0; i < 2 * k; ++i) uv[i] = (int32_t)mxGetPr(in[1])[i];
+        rc = pre3_patch_cut(g_ctx, nin > 2 ? (int)mxGetScalar(in[2]) : 0, k, uv);
+        mxFree(uv); check(rc);
+    }
+    else if (!strcmp(cmd, "patch_search")) {      /* [meas_idx, z, corr, ncand, status] = pre3_mex('patch_search', focal_over_d (cam.F / cam.dx) [, corr_threshold = 0.60 [, strict = 1]]):
+                                                     search_IC_matches.m:31-51 on the patch branch (predict_features_appearance.m + matching.m) */
+        int N = pre3_get_map(g_ctx, NULL), i, rc; int32_t m = 0;
+        int32_t *meas = (int32_t *)mxCalloc(N ? N : 1, sizeof(int32_t)), *nc = (int32_t *)mxCalloc(N ? N : 1, sizeof(int32_t)), *st = (int32_t *)mxCalloc(N ? N : 1, sizeof(int32_t));
+        double *z = (double *)mxCalloc(2 * (N ? N : 1), sizeof(double)), *corr = (double *)mxCalloc(N ? N : 1, sizeof(double));
+        rc = pre3_patch_search(g_ctx, mxGetScalar(in[1]), nin > 2 ? mxGetScalar(in[2]) : 0.60, nin > 3 ? (int)mxGetScalar(in[3]) : 1, &m, meas, z, corr, nc, st);
+        if (rc == PRE3_OK) {
+            out[0] = mxCreateDoubleMatrix(1, m, mxREAL);
+            for (i = 0; i < m; ++i) mxGetPr(out[0])[i] = meas[i] + 1;                       /* 1-based landmark numbers */
+            if (nout > 1) { out[1] = mxCreateDoubleMatrix(2, m, mxREAL); memcpy(mxGetPr(out[1]), z, sizeof(double) * 2 * m); }
+            if (nout > 2) { out[2] = mxCreateDoubleMatrix(1, N, mxREAL); memcpy(mxGetPr(out[2]), corr, sizeof(double) * N); }
+            if (nout > 3) { out[3] = mxCreateDoubleMatrix(1, N, mxREAL); for (i = 0; i < N; ++i) mxGetPr(out[3])[i] = nc[i]; }
+            if (nout > 4) { out[4] = mxCreateDoubleMatrix(1, N, mxREAL); for (i = 0; i < N; ++i) mxGetPr(out[4])[i] = st[i]; }
+        }
+        mxFree(meas); mxFree(nc); mxFree(st); mxFree(z); mxFree(corr); check(rc);
+    }
     else if (!strcmp(cmd, "set_option")) {        /* pre3_mex('set_option', option, value): PRE3_OPT_DEFER_HI = 1, PRE3_OPT_K9_BF16X3 = 2, PRE3_OPT_CHOL_PERSIST = 3, PRE3_OPT_K9_OVERLAP = 5 (include/pre3.h) */
         check(pre3_set_option(g_ctx, (int)mxGetScalar(in[1]), (int)mxGetScalar(in[2])));
     }
