@@ -79,10 +79,21 @@ lib.pre3_patch_cut.argtypes = [_P, _I, _I, _P]
 lib.pre3_predict_patches.argtypes = [_P, _D, _P, _P]
 lib.pre3_patch_search.argtypes = [_P, _D, _D, _I, _P, _P, _P, _P, _P, _P]
 lib.pre3_patch_timing.argtypes = [_P, _P, _P]
+lib.pre3_fast_detect.argtypes = [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]
+lib.pre3_fast_timing.argtypes = [_P, _P]
+lib.pre3_init_feature_fast.argtypes = [_P, _P, _D, _I, _I, _I, _P, _I, _P]
+lib.pre3_init_feature_fast_seeded.argtypes = [_P, _P, _D, _I, _I, _I, _U, _U, _P]
+lib.pre3_init_features_fast_all.argtypes = [_P, _P, _D, _I, _I, _P, _P, _P, _P, _P]
 
 F64, F32 = 0, 1
 INVDEPTH, CARTESIAN = 0, 1
 X_K_K, X_K_KM1 = 0, 1
+FAST_MAX_CORNERS, FAST_MAX_ATTEMPTS = 8192, 10
+
+
+class FastInitResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("attempts", C.c_int32), ("uv", C.c_int32 * 2), ("landmark", C.c_int32), ("pad", C.c_int32), ("rho", C.c_double),
+                ("xyz", C.c_double * 3), ("centres", C.c_int32 * 20)]
 
 
 class Cam(C.Structure):
@@ -150,4 +161,5 @@ EXPORTS = [
     "pre3_sr_text_limits", "pre3_sr_text_parse", "pre3_sr_frame_load_text",
     "pre3_set_image", "pre3_get_image", "pre3_set_image_frame", "pre3_set_patches", "pre3_get_patches", "pre3_patch_cut", "pre3_predict_patches",
     "pre3_patch_search", "pre3_patch_timing",
+    "pre3_fast_detect", "pre3_fast_timing", "pre3_init_feature_fast", "pre3_init_feature_fast_seeded", "pre3_init_features_fast_all",
 ]

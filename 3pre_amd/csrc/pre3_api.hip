@@ -16,6 +16,7 @@
 #include <mutex>
 #include "pre3_cholp.h"
 #include "pre3_patch.h"
+#include "pre3_fast.h"
 
 namespace pre3 {
 
@@ -557,6 +558,7 @@ int pre3_destroy(pre3_ctx *c)
     free_plane(c);
     free_policy(c);
     free_patch(c);
+    free_fast(c);
     for (int k2 = 0; k2 < 2; ++k2) { if (c->map_stage[k2]) (void)hipHostFree(c->map_stage[k2]); if (c->map_stage_ev[k2]) (void)hipEventDestroy(c->map_stage_ev[k2]); }
     for (int k2 = 0; k2 < 2; ++k2) { if (c->up_stage[k2]) (void)hipHostFree(c->up_stage[k2]); if (c->up_stage_ev[k2]) (void)hipEventDestroy(c->up_stage_ev[k2]); }
     if (c->pinned_stats) (void)hipHostFree(c->pinned_stats);
@@ -1232,6 +1234,37 @@ int pre3_patch_timing(pre3_ctx *c, double *warp_ms_out, double *search_ms_out)
 {
     EntryScope scope(c); PRE3_TRY(scope.rc);
     return patch_timing(c, warp_ms_out, search_ms_out);
+}
+
+// ---- FAST-9 corners on the resident image (fast_corner_detect_9.m, fast_nonmax.m; pre3_fast.hip) ---------------
+int pre3_fast_detect(pre3_ctx *c, int r0, int c0, int rows, int cols, int threshold, int barrier, int nonmax, int32_t *K_out, int32_t *uv_out, int32_t *score_out)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return fast_detect(c, r0, c0, rows, cols, threshold, barrier, nonmax, K_out, uv_out, score_out);
+}
+int pre3_init_feature_fast(pre3_ctx *c, pre3_sr_frame *frame, double std_pxl, int strict_reference, int threshold, int barrier, const int32_t *centres, int attempts,
+                           pre3_fast_init_result *out)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    PRE3_CHECK(centres != nullptr, PRE3_E_ARG, "pre3_init_feature_fast: null centres");
+    return fast_init_feature(c, frame, std_pxl, strict_reference, threshold, barrier, centres, attempts, 0, 0, out);
+}
+int pre3_init_feature_fast_seeded(pre3_ctx *c, pre3_sr_frame *frame, double std_pxl, int strict_reference, int threshold, int barrier, uint64_t seed, uint64_t seq,
+                                  pre3_fast_init_result *out)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return fast_init_feature(c, frame, std_pxl, strict_reference, threshold, barrier, nullptr, PRE3_FAST_MAX_ATTEMPTS, seed, seq, out);
+}
+int pre3_init_features_fast_all(pre3_ctx *c, pre3_sr_frame *frame, double std_pxl, int threshold, int barrier, int32_t *K_out, int32_t *n_added_out, int32_t *uv_out,
+                                double *rho_out, int32_t *verdict_out)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return fast_init_all(c, frame, std_pxl, threshold, barrier, K_out, n_added_out, uv_out, rho_out, verdict_out);
+}
+int pre3_fast_timing(pre3_ctx *c, double *detect_ms_out)
+{
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    return fast_timing(c, detect_ms_out);
 }
 
 // ---- RCCL communicator on the context (pre3_comm.hip) ------------------------------------------------

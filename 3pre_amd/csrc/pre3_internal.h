@@ -124,7 +124,7 @@ struct Carried {
     bool select_pending = false; int sel_n_draw = 0, sel_k = 0, sel_early_exit = 0;   // W ransac_impl: the selection is still to be launched | R update_li_impl; install_measurements drops it
 };
 
-namespace pre3 { struct PatchState; }
+namespace pre3 { struct PatchState; struct FastState; }
 struct pre3_ctx {
     int device = 0, dtype = PRE3_F32;
     size_t esz = 4;
@@ -259,6 +259,8 @@ struct pre3_ctx {
     int32_t *pol_host = nullptr, *pol_host_dev = nullptr; size_t pol_host_bytes = 0;   // the result block in mapped pinned memory
     // the patch branch of the IC search (pre3_patch.hip), allocated on first use: the resident image, the patch bank, the warped patches
     pre3::PatchState *patch = nullptr;
+    // FAST-9 corners on the resident image (pre3_fast.hip), allocated on first use: the verdict map and the result block
+    pre3::FastState *fast = nullptr;
 };
 
 namespace pre3 {

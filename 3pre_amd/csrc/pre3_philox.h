@@ -2,7 +2,8 @@
 // Philox4x64-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11) with its public constants: one block is a pure
 // function of (counter[4], key[2]); no state lives anywhere.  numpy.random.Philox is the same generator (it advances the counter before its first
 // block): tests/test_draws_ref.py pins tests/draws_ref.py's restatement against it, tests/test_gpu_draws.py the kernels against the restatement.
-//   key     = [seed, stream]               stream 1: 1-point RANSAC, 2: VO 4-point RANSAC, 3: floor-plane RANSAC, 4: the candidates' weighted order
+//   key     = [seed, stream]               stream 1: 1-point RANSAC, 2: VO 4-point RANSAC, 3: floor-plane RANSAC, 4: the candidates' weighted order,
+//                                          5: initialize_a_feature's box centres (counter [attempt, 0, seq, 0])
 //   counter = [index, attempt, seq, 0]     index: the hypothesis; attempt: the redraw number (0 = first draw); seq: the caller's frame / step number
 // A bounded integer in [0, range) is the high 64 bits of word * range: no rejection, so value v is drawn with probability floor- or ceil-(2^64 / range)
 // / 2^64 -- a bias of at most range / 2^64 (below 2^-50 for every range of this library).  A uniform double is the word's top 53 bits times 2^-53.
@@ -21,7 +22,8 @@ namespace pre3 {
 
 constexpr uint64_t PHILOX_M0 = 0xD2E7470EE14C6C93ull, PHILOX_M1 = 0xCA5A826395121157ull;
 constexpr uint64_t PHILOX_W0 = 0x9E3779B97F4A7C15ull, PHILOX_W1 = 0xBB67AE8584CAA73Bull;
-enum { DRAW_STREAM_1P = 1, DRAW_STREAM_VO = 2, DRAW_STREAM_PLANE = 3, DRAW_STREAM_CAND = 4 };
+enum { DRAW_STREAM_1P = 1, DRAW_STREAM_VO = 2, DRAW_STREAM_PLANE = 3, DRAW_STREAM_CAND = 4,
+       DRAW_STREAM_FAST = 5 /* initialize_a_feature.m:64: counter [attempt, 0, seq, 0], words 0 and 1 -> the box centre's two uniforms */ };
 constexpr int VO_MAX_REDRAWS = 64;          // per position; ransac_dr_ye.m:28-46 loops for ever
 constexpr int PLANE_MAX_ATTEMPTS = 100;     // ransac.m:122 maxDataTrials
 

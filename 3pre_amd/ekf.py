@@ -50,6 +50,7 @@ class EkfFilter:
         check(lib.pre3_create(C.byref(self._ctx), int(device), self.dtype, int(max_landmarks or max(self.N, 1)), int(max_hyp)))
         c = _cam(cam)
         check(lib.pre3_set_cam(self._ctx, C.byref(c)))
+        self._image_shape = (int(c.nRows), int(c.nCols))     # the resident image has the camera's shape
         check(lib.pre3_set_map(self._ctx, self.N, dptr(lm_type)))
         self.n = int(lib.pre3_state_size(self._ctx))
         self.lm_type = lm_type
@@ -532,6 +533,86 @@ class EkfFilter:
         a, b = C.c_double(0), C.c_double(0)
         check(lib.pre3_patch_timing(self._ctx, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # ---- FAST-9 corners on the resident image (fast_corner_detect_9.m, fast_nonmax.m; DESIGN.md section 30: the published segment test, not the
+    # reference's learned tree)
+    def _fast_detect(self, threshold, barrier, nonmax, box):
+        if box is None:
+            box = (0, 0) + tuple(self._image_shape)
+        r0, c0, rows, cols = (int(v) for v in box)
+        K = C.c_int32(0)
+        uv, score = np.zeros((_lib.FAST_MAX_CORNERS, 2), np.int32), np.zeros(_lib.FAST_MAX_CORNERS, np.int32)
+        check(lib.pre3_fast_detect(self._ctx, r0, c0, rows, cols, int(threshold), int(barrier), int(nonmax), C.byref(K), dptr(uv), dptr(score)))
+        return uv[:K.value].copy(), score[:K.value].copy()
+
+    def fast_corner_detect_9(self, threshold, box=None, barrier=None):
+        """fast_corner_detect_9(im, threshold) on the resident image, or on box = (r0, c0, rows, cols) (0-based) of it taken as an image of its own:
+        (K, 2) int32 corners (x, y) = (column, row), 1-based and relative to the box, x outer / y inner.  With a barrier: (corners, scores)."""
+        uv, score = self._fast_detect(threshold, 0 if barrier is None else barrier, 0, box)
+        return uv if barrier is None else (uv, score)
+
+    def fast_nonmax(self, threshold, barrier, box=None):
+        """fast_nonmax(im, barrier, fast_corner_detect_9(im, threshold)): (maxima (K, 2) int32, scores (K,) int32)."""
+        return self._fast_detect(threshold, barrier, 1, box)
+
+    FAST_STATUS = ("initialised", "no_box", "no_depth_nan", "no_depth_near", "no_depth_conf")
+
+    def _fast_init_result(self, res):
+        ok = res.status == 0
+        if ok:
+            self._refresh_map()
+        tried = np.array(res.centres[:], np.int32).reshape(-1, 2)[:res.attempts].copy()
+        found = res.status != 1
+        return dict(status=int(res.status), attempts=int(res.attempts), uv=np.array(res.uv[:], np.int32) if found else None,
+                    rho=float(res.rho) if ok else None, xyz=np.array(res.xyz[:]) if ok else None, landmark=int(res.landmark) if ok else None, centres=tried)
+
+    def initialize_a_feature(self, frame, std_pxl, centres, strict_reference=True, threshold=10, barrier=20):
+        """initialize_a_feature.m:27-215 on the FAST branch, one call and one wait (pre3_init_feature_fast): up to 10 attempts over the box centres
+        `centres` (attempts, 2) = (row, column), 1-based; depth from the resident sr4000.SrFrame `frame`.  On status 0 ("initialised") the map has the
+        new inverse-depth landmark (rho = 1 / df) and the bank its 41 x 41 patch, as after add_features_inverse_depth(uv, std_pxl, rho) and
+        patch_cut(uv, first=N).  Returns dict(status (index into FAST_STATUS), attempts, uv (column, row), rho, xyz, landmark, centres tried)."""
+        ce = i32(np.asarray(centres).reshape(-1, 2))
+        res = _lib.FastInitResult()
+        check(lib.pre3_init_feature_fast(self._ctx, frame._h, float(std_pxl), int(bool(strict_reference)), int(threshold), int(barrier), dptr(ce), int(ce.shape[0]),
+                                         C.byref(res)))
+        return self._fast_init_result(res)
+
+    def initialize_a_feature_seeded(self, frame, std_pxl, seed, seq, strict_reference=True, threshold=10, barrier=20):
+        """initialize_a_feature with its rand(2, 1) per attempt (:64) drawn on the device: Philox key [seed, 5], counter [attempt, 0, seq, 0]."""
+        res = _lib.FastInitResult()
+        check(lib.pre3_init_feature_fast_seeded(self._ctx, frame._h, float(std_pxl), int(bool(strict_reference)), int(threshold), int(barrier), int(seed), int(seq),
+                                                C.byref(res)))
+        return self._fast_init_result(res)
+
+    def initialize_n_features_fast(self, frame, std_pxl, threshold=5, barrier=20):
+        """initialize_n_features_FAST.m:55-145 (pre3_init_features_fast_all): every maximum of the image inside the 20-pixel band through the depth
+        gate, the survivors added in scan order in one map call with one patch cut.  Returns dict(uv (K, 2) of all maxima, rho (K,), verdict (K,:
+        0 = added, else an index into FAST_STATUS), n_added)."""
+        K, n = C.c_int32(0), C.c_int32(0)
+        uv, rho, ver = np.zeros((_lib.FAST_MAX_CORNERS, 2), np.int32), np.zeros(_lib.FAST_MAX_CORNERS), np.zeros(_lib.FAST_MAX_CORNERS, np.int32)
+        check(lib.pre3_init_features_fast_all(self._ctx, frame._h, float(std_pxl), int(threshold), int(barrier), C.byref(K), C.byref(n), dptr(uv), dptr(rho), dptr(ver)))
+        if n.value:
+            self._refresh_map()
+        return dict(uv=uv[:K.value].copy(), rho=rho[:K.value].copy(), verdict=ver[:K.value].copy(), n_added=int(n.value))
+
+    def initialize_features_fast(self, frame, n, std_pxl, seed, seq0=0, max_calls=50, **kw):
+        """initialize_features.m:110-142: initialize_a_feature until n features are in or max_calls calls are spent -- the bound the reference declares
+        (max_attempts = 50, :106) and never applies.  Each new feature changes the next call's "is the box free" test, so this is a host loop with one
+        wait per call; call k draws from (seed, seq0 + k).  A depth refusal counts as a spent call.  Returns the list of the calls' results."""
+        out, added = [], 0
+        for k in range(int(max_calls)):
+            if added >= int(n):
+                break
+            r = self.initialize_a_feature_seeded(frame, std_pxl, seed, int(seq0) + k, **kw)
+            added += r["status"] == 0
+            out.append(r)
+        return out
+
+    def fast_timing(self):
+        """ms of the launches of the last detector / initialisation call under kernel timing."""
+        a = C.c_double(0)
+        check(lib.pre3_fast_timing(self._ctx, C.byref(a)))
+        return a.value
 
     # ---- step stages
     def ekf_prediction(self, u):

@@ -489,6 +489,26 @@ PRE3_API int pre3_patch_search(pre3_ctx *ctx, double focal_over_d, double corr_t
 /* measurement only: with pre3_kernel_timing on, the last pre3_patch_search bracketed k_patch_warp and k_patch_search with events; their times */
 PRE3_API int pre3_patch_timing(pre3_ctx *ctx, double *warp_ms_out, double *search_ms_out);
 
+/* ---- FAST-9 corners on the resident image (pre3_fast.hip) --------------------------------------------------------
+ * mex_files/Fast_Cr_Ver1/fast_corner_detect_9.m:53-3286 as initialize_a_feature.m:102 and initialize_n_features_FAST.m:69 call it, and
+ * fast-matlab-src/fast_nonmax.m:38-100 (:104, :81).  The device computes the PUBLISHED segment test (9 contiguous ring pixels all > centre + threshold
+ * or all < centre - threshold, strict as :61-63); the reference's file is a learned decision tree that answers differently on most ring states and
+ * on few pixels of a real image (DESIGN.md section 30 has the counts; the fixture tests/golden/fast_lab_crop.npz pins an image where they agree).
+ * There is no tree-exact mode. */
+#define PRE3_FAST_MAX_CORNERS 8192
+/* The rectangle rows [r0, r0 + rows) x columns [c0, c0 + cols) (0-based) of the resident image, taken as an image of its own the way imTemp2 is
+ * (initialize_a_feature.m:93-94): candidates are its pixels 4 .. size - 3 (1-based, fast_corner_detect_9.m:59-60) and the ring never leaves it.
+ * nonmax = 0: fast_corner_detect_9's list; nonmax = 1: fast_nonmax's (score = max of the two sums over the ring beyond centre +/- barrier, :70-75;
+ * kept when >= all eight neighbours' scores, :87-92: ties are kept on both sides and so is a score-0 corner among score-0 neighbours).
+ * K_out, uv_out[2 K] (column, row; 1-based, relative to the rectangle as the .m returns them; x outer, y inner as :59-60), score_out[K] (may be NULL;
+ * the score at `barrier`, also with nonmax = 0).  uv_out and score_out hold PRE3_FAST_MAX_CORNERS entries unless K is known.  Waits once.
+ * PRE3_E_STATE without an image.  PRE3_E_ARG before anything is queued: a rectangle that leaves the image, rows or cols < 7, a negative threshold
+ * or barrier.  More than PRE3_FAST_MAX_CORNERS corners: PRE3_E_NOMEM after the wait with *K_out = 0; the context stays usable. */
+PRE3_API int pre3_fast_detect(pre3_ctx *ctx, int r0, int c0, int rows, int cols, int threshold, int barrier, int nonmax,
+                              int32_t *K_out, int32_t *uv_out, int32_t *score_out);
+/* measurement only: with pre3_kernel_timing on, the last call of pre3_fast_detect or of the three pre3_init_feature*_fast* calls below bracketed its launches of pre3_fast.hip with events; their time */
+PRE3_API int pre3_fast_timing(pre3_ctx *ctx, double *detect_ms_out);
+
 /* ---- the VO front end's 4-point 3D-3D RANSAC (code_from_dr_ye/) ------------------------------------ */
 typedef struct pre3_vo_result {
     double rot[9];          /* final rotation, row-major (find_transform_matrix_dr_ye.m on the winner's inliers, vodometry_dr_ye.m:221) */
@@ -802,6 +822,51 @@ PRE3_API int pre3_set_scan_frame(pre3_ctx *ctx, pre3_sr_frame *f, int which);
  * the context's stream behind an event on the handle's, released as above; nothing crosses PCIe, nothing is read back, the call does not synchronise.
  * The frame's shape must be the camera's (PRE3_E_ARG); PRE3_E_STATE: a handle without a loaded frame. */
 PRE3_API int pre3_set_image_frame(pre3_ctx *ctx, pre3_sr_frame *f);
+
+/* ---- patch-feature initialisation from FAST corners --------------------------------------------------------------
+ * mex_files/Fast_Cr_Ver1/initialize_a_feature.m:27-215 on the FAST branch in one call, between steps: needs (x_k_k, p_k_k), the camera, the resident
+ * image and a loaded pre3_sr_frame of the image's shape on the context's device, whose filtered planes supply the depth.  One launch (k_fast_box)
+ * behind the existing projection at x_k_k (:48) runs up to `attempts` attempts; per attempt
+ *   :64-68    the box centre, (row, column) 1-based, with BoxLimX = [1 nCols], BoxLimY = [1 nRows] (the fork's 144 x 176 generalised):
+ *             row = round(u1 ((nRows - 1) - 42 - 60)) + 51, column = round(u2 ((nCols - 1) - 42 - 40)) + 41 -- from centres[2 a], centres[2 a + 1], or
+ *             (_seeded) from words 0 and 1 of the Philox block with key [seed, 5] and counter [a, 0, seq, 0] (pre3_philox.h);
+ *   :93-105   the 61 x 41 box as an image of its own: the segment test at `threshold`, fast_nonmax at `barrier` (-1: the reference's 10 and 20);
+ *   :164-174  "features in the box" over the landmarks with an h, strict inequalities.  strict_reference = 1: u (the column) against the ROW centre
+ *             +/- 30 and v against the COLUMN centre +/- 20, as written; 0: the axes matched;
+ *   :176-180  the first maximum in scan order of a box with a corner and no feature, shifted into the image (:152-157);
+ *   :188-194  gate 0 of pre3_sr_frame_keypoints at that pixel (x NaN, df < 0.4, conf <= 0.5 cmax); a refusal ends the call with no feature and
+ *             no further attempt.
+ * Waits once, on the result.  On PRE3_FAST_INITIALISED the call then queues, without a second wait, pre3_map_add_inverse_depth for the one feature
+ * (rho = 1 / df) and pre3_patch_cut for the new landmark: the context comes out exactly as if the caller had made those two calls with the returned
+ * uv and rho.  The h of the projection are dropped (:211-213): a following stage projects for itself.
+ * PRE3_E_ARG before anything is queued: a null frame or result, a frame of another shape or device, std_pxl, attempts outside 1 .. 10, an image
+ * smaller than 103 x 83, a centre outside the range that can be drawn.  PRE3_E_STATE likewise: no image, no x_k_k, an unloaded frame.  PRE3_E_NOMEM
+ * likewise: no room for one more landmark.  PRE3_E_NUMERIC after the wait, the map untouched: the corner's rho is not finite (a NaN y or z passes
+ * the depth gate, as in the reference). */
+#define PRE3_FAST_MAX_ATTEMPTS 10      /* initialize_a_feature.m:34 */
+#define PRE3_FAST_INITIALISED 0
+#define PRE3_FAST_NO_BOX 1             /* every attempt met a box without a corner or with a predicted feature (:176-183) */
+#define PRE3_FAST_NO_DEPTH_NAN 2       /* inittialize_depth_my_version.m:40 */
+#define PRE3_FAST_NO_DEPTH_NEAR 3      /* :74 df < 0.4 */
+#define PRE3_FAST_NO_DEPTH_CONF 4      /* :74 conf <= 0.5 cmax */
+typedef struct pre3_fast_init_result {
+    int32_t status, attempts;          /* PRE3_FAST_*; attempts used, 1-based */
+    int32_t uv[2];                     /* the corner (column, row), 1-based, in the image; zero for PRE3_FAST_NO_BOX */
+    int32_t landmark, pad;             /* the new landmark's index, -1 unless PRE3_FAST_INITIALISED */
+    double rho, xyz[3];                /* 1 / df and [-x, -y, z] of the pixel: pre3_sr_frame_keypoints' gate-0 outputs, bit for bit; zero when refused */
+    int32_t centres[2 * PRE3_FAST_MAX_ATTEMPTS];      /* the (row, column) centres tried; zero behind `attempts` */
+} pre3_fast_init_result;
+PRE3_API int pre3_init_feature_fast(pre3_ctx *ctx, pre3_sr_frame *frame, double std_pxl, int strict_reference, int threshold, int barrier,
+                                    const int32_t *centres /* 2 x attempts */, int attempts, pre3_fast_init_result *out);
+PRE3_API int pre3_init_feature_fast_seeded(pre3_ctx *ctx, pre3_sr_frame *frame, double std_pxl, int strict_reference, int threshold, int barrier,
+                                           uint64_t seed, uint64_t seq, pre3_fast_init_result *out);
+/* initialize_n_features_FAST.m:55-145: the maxima (threshold -1: 5, barrier -1: 20, :69-82) of the image inside the 20-pixel band (:62-64), every
+ * one through gate 0 (:118-127), the survivors added in scan order in ONE pre3_map_add_inverse_depth with ONE pre3_patch_cut, queued behind the
+ * call's one wait.  K_out maxima; uv_out[2 K] (column, row, 1-based, in the image), rho_out[K] (zero when refused), verdict_out[K]
+ * (PRE3_FAST_INITIALISED = kept, or PRE3_FAST_NO_DEPTH_*) -- each may be NULL, else holds PRE3_FAST_MAX_CORNERS entries; n_added_out survivors.
+ * Errors as above; more survivors than the context has room for, or more than PRE3_FAST_MAX_CORNERS maxima: PRE3_E_NOMEM, the map untouched. */
+PRE3_API int pre3_init_features_fast_all(pre3_ctx *ctx, pre3_sr_frame *frame, double std_pxl, int threshold, int barrier, int32_t *K_out,
+                                         int32_t *n_added_out, int32_t *uv_out, double *rho_out, int32_t *verdict_out);
 
 /* ---- the prediction fed from a resident VO pair: u never leaves the device -----------------------------------------------------
  * fv.m:47 + Calculate_V_Omega_RANSAC_dr_ye.m:41-50 + predict_state_and_covariance.m:27-143 in one call: the VO front end between the keypoint records of

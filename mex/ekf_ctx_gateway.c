@@ -44,6 +44,7 @@ static pre3_ctx *g_ctx = NULL;
 static pre3_sr_frame *g_sr = NULL;          /* the resident SR4000 frame of 'sr_frame' / 'sr_keypoints' */
 static pre3_sr_frame *g_sr_prev = NULL;     /* the frame 'sr_keep' put aside: prev of 'vo_pair' */
 static int g_sr_rows = 0, g_sr_cols = 0;
+static int g_cam_rows = 0, g_cam_cols = 0;  /* the camera's shape, which is the resident image's ('fast_detect' without a box) */
 static void at_exit(void) { if (g_ctx) { pre3_destroy(g_ctx); g_ctx = NULL; } }
 static void sr_at_exit(void) { if (g_sr) { pre3_sr_frame_destroy(g_sr); g_sr = NULL; } if (g_sr_prev) { pre3_sr_frame_destroy(g_sr_prev); g_sr_prev = NULL; } at_exit(); }
 static void check(int rc) { if (rc != PRE3_OK) mexErrMsgTxt(pre3_last_error()); }
@@ -63,6 +64,7 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         t = (int32_t *)mxMalloc(sizeof(int32_t) * (N ? N : 1));
         for (i = 0; i < N; ++i) t[i] = (int32_t)mxGetPr(in[2])[i];
         check(pre3_set_cam(g_ctx, &cam)); check(pre3_set_map(g_ctx, N, t)); mxFree(t);
+        g_cam_rows = (int)cam.nRows; g_cam_cols = (int)cam.nCols;
         return;
     }
     if (!strcmp(cmd, "sr_frame")) {          /* [x, y, z, img, imax, cmax] = pre3_mex('sr_frame', mode (0: read_xyz_sr4000 / read_image_sr4000, 1: read_sr4000_data_dr_ye),
@@ -706,6 +708,61 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
             if (nout > 4) { out[4] = mxCreateDoubleMatrix(1, N, mxREAL); for (i = 0; i < N; ++i) mxGetPr(out[4])[i] = st[i]; }
         }
         mxFree(meas); mxFree(nc); mxFree(st); mxFree(z); mxFree(corr); check(rc);
+    }
+    else if (!strcmp(cmd, "fast_detect")) {       /* [corners, scores] = pre3_mex('fast_detect', threshold [, barrier = 20 [, nonmax = 0 [, box = [r0 c0 rows cols] (0-based)]]]):
+                                                     fast_corner_detect_9.m (nonmax = 0) / fast_nonmax.m (nonmax = 1) on the resident image or a rectangle of it; corners
+                                                     K x 2 [x y], 1-based, relative to the rectangle.  The published segment test, not the reference's tree */
+        int32_t K = 0, *uv = (int32_t *)mxCalloc(2 * PRE3_FAST_MAX_CORNERS, sizeof(int32_t)), *sc = (int32_t *)mxCalloc(PRE3_FAST_MAX_CORNERS, sizeof(int32_t));
+        int box[4] = { 0, 0, 0, 0 }, i, rc;
+        if (nin < 2) mexErrMsgTxt("pre3_mex('fast_detect', threshold [, barrier, nonmax, box])");
+        if (nin > 4) { if (mxGetNumberOfElements(in[4]) != 4) mexErrMsgTxt("pre3_mex('fast_detect', ...): box is [r0 c0 rows cols]"); for (i = 0; i < 4; ++i) box[i] = (int)mxGetPr(in[4])[i]; }
+        else { box[2] = g_cam_rows; box[3] = g_cam_cols; }
+        rc = pre3_fast_detect(g_ctx, box[0], box[1], box[2], box[3], (int)mxGetScalar(in[1]), nin > 2 ? (int)mxGetScalar(in[2]) : 20, nin > 3 ? (int)mxGetScalar(in[3]) : 0, &K, uv, sc);
+        if (rc == PRE3_OK) {
+            out[0] = mxCreateDoubleMatrix(K, 2, mxREAL);
+            for (i = 0; i < K; ++i) { mxGetPr(out[0])[i] = uv[2 * i]; mxGetPr(out[0])[K + i] = uv[2 * i + 1]; }
+            if (nout > 1) { out[1] = mxCreateDoubleMatrix(K, 1, mxREAL); for (i = 0; i < K; ++i) mxGetPr(out[1])[i] = sc[i]; }
+        }
+        mxFree(uv); mxFree(sc); check(rc);
+    }
+    else if (!strcmp(cmd, "init_feature_fast")) { /* [uv, status, rho, xyz, centres] = pre3_mex('init_feature_fast', std_pxl, centres (2 x attempts: [row; column]) | [seed seq]
+                                                     [, strict = 1 [, threshold = 10 [, barrier = 20]]]): initialize_a_feature.m:27-215 on the FAST branch with the
+                                                     resident frame's depth; a 2 x 1 second argument is one centre, a 1 x 2 one is [seed seq].  uv is [] unless status is 0 */
+        pre3_fast_init_result r; int i, rc, strict = nin > 3 ? (int)mxGetScalar(in[3]) : 1, thr = nin > 4 ? (int)mxGetScalar(in[4]) : -1, bar = nin > 5 ? (int)mxGetScalar(in[5]) : -1;
+        if (nin < 3) mexErrMsgTxt("pre3_mex('init_feature_fast', std_pxl, centres | [seed seq] [, strict, threshold, barrier])");
+        if (!g_sr) mexErrMsgTxt("pre3_mex('init_feature_fast'): call pre3_mex('sr_frame', ...) first");
+        if (mxGetM(in[2]) == 1 && mxGetN(in[2]) == 2)
+            rc = pre3_init_feature_fast_seeded(g_ctx, g_sr, mxGetScalar(in[1]), strict, thr, bar, (uint64_t)mxGetPr(in[2])[0], (uint64_t)mxGetPr(in[2])[1], &r);
+        else {
+            int32_t ce[2 * PRE3_FAST_MAX_ATTEMPTS]; int na = (int)mxGetN(in[2]);
+            if (mxGetM(in[2]) != 2 || na < 1 || na > PRE3_FAST_MAX_ATTEMPTS) mexErrMsgTxt("pre3_mex('init_feature_fast', ...): centres is 2 x (1 .. 10)");
+            for (i = 0; i < 2 * na; ++i) ce[i] = (int32_t)mxGetPr(in[2])[i];
+            rc = pre3_init_feature_fast(g_ctx, g_sr, mxGetScalar(in[1]), strict, thr, bar, ce, na, &r);
+        }
+        check(rc);
+        out[0] = mxCreateDoubleMatrix(r.status == PRE3_FAST_INITIALISED ? 2 : 0, r.status == PRE3_FAST_INITIALISED ? 1 : 0, mxREAL);
+        if (r.status == PRE3_FAST_INITIALISED) { mxGetPr(out[0])[0] = r.uv[0]; mxGetPr(out[0])[1] = r.uv[1]; }
+        if (nout > 1) out[1] = mxCreateDoubleScalar(r.status);
+        if (nout > 2) out[2] = mxCreateDoubleScalar(r.rho);
+        if (nout > 3) { out[3] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[3]), r.xyz, sizeof(double) * 3); }
+        if (nout > 4) { out[4] = mxCreateDoubleMatrix(2, r.attempts, mxREAL); for (i = 0; i < 2 * r.attempts; ++i) mxGetPr(out[4])[i] = r.centres[i]; }
+    }
+    else if (!strcmp(cmd, "init_features_fast_all")) {   /* [uv, rho, verdict, n_added] = pre3_mex('init_features_fast_all', std_pxl [, threshold = 5 [, barrier = 20]]):
+                                                            initialize_n_features_FAST.m:55-145 -- uv 2 x K of every maximum, verdict 0 = added */
+        int32_t K = 0, n = 0, *uv = (int32_t *)mxCalloc(2 * PRE3_FAST_MAX_CORNERS, sizeof(int32_t)), *ver = (int32_t *)mxCalloc(PRE3_FAST_MAX_CORNERS, sizeof(int32_t));
+        double *rho = (double *)mxCalloc(PRE3_FAST_MAX_CORNERS, sizeof(double));
+        int i, rc;
+        if (nin < 2) mexErrMsgTxt("pre3_mex('init_features_fast_all', std_pxl [, threshold, barrier])");
+        if (!g_sr) mexErrMsgTxt("pre3_mex('init_features_fast_all'): call pre3_mex('sr_frame', ...) first");
+        rc = pre3_init_features_fast_all(g_ctx, g_sr, mxGetScalar(in[1]), nin > 2 ? (int)mxGetScalar(in[2]) : -1, nin > 3 ? (int)mxGetScalar(in[3]) : -1, &K, &n, uv, rho, ver);
+        if (rc == PRE3_OK) {
+            out[0] = mxCreateDoubleMatrix(2, K, mxREAL);
+            for (i = 0; i < 2 * K; ++i) mxGetPr(out[0])[i] = uv[i];
+            if (nout > 1) { out[1] = mxCreateDoubleMatrix(1, K, mxREAL); memcpy(mxGetPr(out[1]), rho, sizeof(double) * K); }
+            if (nout > 2) { out[2] = mxCreateDoubleMatrix(1, K, mxREAL); for (i = 0; i < K; ++i) mxGetPr(out[2])[i] = ver[i]; }
+            if (nout > 3) out[3] = mxCreateDoubleScalar(n);
+        }
+        mxFree(uv); mxFree(ver); mxFree(rho); check(rc);
     }
     else if (!strcmp(cmd, "set_option")) {        /* pre3_mex('set_option', option, value): PRE3_OPT_DEFER_HI = 1, PRE3_OPT_K9_BF16X3 = 2, PRE3_OPT_CHOL_PERSIST = 3, PRE3_OPT_K9_OVERLAP = 5 (include/pre3.h) */
         check(pre3_set_option(g_ctx, (int)mxGetScalar(in[1]), (int)mxGetScalar(in[2])));
