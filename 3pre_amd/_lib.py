@@ -84,6 +84,11 @@ lib.pre3_fast_timing.argtypes = [_P, _P]
 lib.pre3_init_feature_fast.argtypes = [_P, _P, _D, _I, _I, _I, _P, _I, _P]
 lib.pre3_init_feature_fast_seeded.argtypes = [_P, _P, _D, _I, _I, _I, _U, _U, _P]
 lib.pre3_init_features_fast_all.argtypes = [_P, _P, _D, _I, _I, _P, _P, _P, _P, _P]
+lib.pre3_icp.argtypes = [_I, _P, _I, _P, _I, _D, _P, _P, _P, _P, _P, _P]
+lib.pre3_icp_limits.argtypes = [_P]
+lib.pre3_icp_frames.argtypes = [_P, _P, _I, _D, _P, _P, _P, _P, _P, _P, _P]
+lib.pre3_icp_pair_seeded.argtypes = [_P, _P, _D, _U, _U, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]
+lib.pre3_icp_nn_bench.argtypes = [_I, _P, _I, _P, _I, _I, _P]
 
 F64, F32 = 0, 1
 INVDEPTH, CARTESIAN = 0, 1
@@ -162,4 +167,5 @@ EXPORTS = [
     "pre3_set_image", "pre3_get_image", "pre3_set_image_frame", "pre3_set_patches", "pre3_get_patches", "pre3_patch_cut", "pre3_predict_patches",
     "pre3_patch_search", "pre3_patch_timing",
     "pre3_fast_detect", "pre3_fast_timing", "pre3_init_feature_fast", "pre3_init_feature_fast_seeded", "pre3_init_features_fast_all",
+    "pre3_icp", "pre3_icp_limits", "pre3_icp_frames", "pre3_icp_pair_seeded", "pre3_icp_nn_bench",
 ]

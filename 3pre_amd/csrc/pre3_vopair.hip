@@ -23,6 +23,7 @@
 #include "pre3_vopair.h"
 #include "pre3_predictu.h"
 #include "pre3_vocov.h"
+#include "pre3_icp.h"
 
 namespace pre3 {
 
@@ -226,19 +227,27 @@ void vp_cov_out(const VpPair &p, double *cov_out, int32_t *cov_status_out)
     if (cov_out && cv->status == VC_VALID) memcpy(cov_out, cv->cov, sizeof cv->cov);
 }
 
-// pre3_vo_pair_seeded, and -- with_cov -- pre3_vo_pair_cov_seeded: the same launches, transfer and checks, k_vo_cov and its block besides
+// the dense ICP queued behind the pair's launches (pre3_icp_pair_seeded)
+struct IcpAttach { int stride; double res; IcpOutputs out; };
+void icp_not_run(const IcpAttach *icp) { if (icp && icp->out.res) icp->out.res->sta = ICP_NOT_RUN; }
+
+// pre3_vo_pair_seeded, and -- with_cov -- pre3_vo_pair_cov_seeded: the same launches, transfer and checks, k_vo_cov and its block besides;
+// icp != nullptr: pre3_icp_frames' launches behind them on the same stream, seeded from the pair's result block
 int vo_pair_impl(const char *who, bool with_cov, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out, double *match_out,
                  double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out, int32_t *state_out,
-                 int32_t *inlier_out, pre3_vo_result *res, double *cov_out, int32_t *cov_status_out)
+                 int32_t *inlier_out, pre3_vo_result *res, double *cov_out, int32_t *cov_status_out, const IcpAttach *icp = nullptr)
 {
     VpPair p;
     p.with_cov = with_cov;
     PRE3_TRY(sr_frame_pair_views(who, prev, cur, thresh, &p.v1, &p.v2, &p.k1, &p.k2));
+    if (icp) PRE3_TRY(icp_check_args(who, icp->stride, icp->res));
     PRE3_TRY(select_device(who, p.v2.device));
     if (pnum_out) *pnum_out = 0;
     if (cov_status_out) *cov_status_out = VC_NOT_COMPUTED;
-    if (vp_empty(p)) { vo_no_solution(res); return PRE3_OK; }      // siftmatch of an empty set: no match, nothing to queue
+    if (vp_empty(p)) { vo_no_solution(res); icp_not_run(icp); return PRE3_OK; }      // siftmatch of an empty set: no match, nothing to queue
     PRE3_TRY(vp_queue(prev, cur, thresh, seed, seq, &p));
+    IcpJob job;
+    if (icp) PRE3_TRY(icp_job_queue_frames(&job, p.v1, p.v2, icp->stride, icp->res, nullptr, nullptr, (const VoOut *)(p.d + p.o_out), icp->out, p.v2.stream));
     size_t need = p.o_match;                    // the prefix of the block the caller's outputs reach into
     if (match_out) need = p.o_p1;
     if (pset1_out) need = p.o_p2;
@@ -258,7 +267,7 @@ int vo_pair_impl(const char *who, bool with_cov, pre3_sr_frame *prev, pre3_sr_fr
     const int pnum = h.pnum, rst = h.rst;
     if (pnum_out) *pnum_out = pnum;
     if (match_out) memcpy(match_out, pin + p.o_match, sizeof(double) * 2 * (size_t)pnum);
-    if (pnum < 4) { vo_no_solution(res); return PRE3_OK; }
+    if (pnum < 4) { vo_no_solution(res); icp_not_run(icp); return PRE3_OK; }
     PRE3_TRY(vp_refuse_bad(h));
     if (with_cov) vp_cov_out(p, cov_out, cov_status_out);
     if (pset1_out) memcpy(pset1_out, pin + p.o_p1, sizeof(double) * 3 * (size_t)pnum);
@@ -270,6 +279,7 @@ int vo_pair_impl(const char *who, bool with_cov, pre3_sr_frame *prev, pre3_sr_fr
     if (state_out) memcpy(state_out, pin + p.o_state, sizeof(int32_t) * (size_t)rst);
     if (inlier_out) memcpy(inlier_out, pin + p.o_inl, sizeof(int32_t) * (size_t)pnum);
     if (res) vo_result(o, res);
+    if (icp) PRE3_TRY(icp_job_collect(&job, who, icp->out));
     return PRE3_OK;
 }
 
@@ -342,6 +352,17 @@ int pre3_vo_pair_cov_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thre
 {
     return vo_pair_impl("pre3_vo_pair_cov_seeded", true, prev, cur, thresh, seed, seq, pnum_out, match_out, pset1_out, pset2_out, draws_out, capped_out, cnum_out, state_out,
                         inlier_out, res, cov_out, cov_status_out);
+}
+
+// icp_with_init.m behind vodometry_dr_ye.m:139-236: pre3_vo_pair_seeded's launches, then the ICP's on the same stream, one host wait
+int pre3_icp_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int stride, double res, int32_t *pnum_out,
+                         double *match_out, double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out,
+                         int32_t *state_out, int32_t *inlier_out, pre3_vo_result *vo_res, pre3_icp_result *icp, double *corr_out, int32_t *corr_pix_out,
+                         double *data2_out, double *log_out)
+{
+    const IcpAttach at{ stride, res, IcpOutputs{ icp, corr_out, corr_pix_out, data2_out, log_out } };
+    return vo_pair_impl("pre3_icp_pair_seeded", false, prev, cur, thresh, seed, seq, pnum_out, match_out, pset1_out, pset2_out, draws_out, capped_out, cnum_out, state_out,
+                        inlier_out, vo_res, nullptr, nullptr, &at);
 }
 
 int pre3_predict_pair_seeded(pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out,

@@ -8,6 +8,7 @@
     Calculate_V_Omega_RANSAC_dr_ye.m:40-50 -> result["u"] = [T; R2q(R)], the argument of EkfFilter.ekf_prediction
     aux_code/cov_pose_shift_calc.m       -> cov_pose_shift_calc (the 7 x 7 covariance of [T; q] from the points' range and angle noise)
     aux_code/calc_cov_RANSAC_dr_ye.m:17-30 -> vo_cov, vo_pair_cov_seeded (the same from a pair's inliers, on the device behind the final fit)
+    TestScripts/icp_with_init.m:34-120   -> icp_with_init, icp_frames, icp_pair_seeded (dense ICP seeded with a pose)
 
 All compute runs in libpre3.so on the GPU; this module marshals numpy arrays and draws random numbers.
 """
@@ -229,6 +230,106 @@ def cov_pose_shift_calc(Ya, Yb, R, T, device=0):
     if r["status"] != 1:
         raise ValueError("cov_pose_shift_calc: status %d (0: fewer than four points, 2: singular fit or non-finite input)" % r["status"])
     return r["cov"]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("Rtot", C.c_double * 9), ("ttot", C.c_double * 3), ("u", C.c_double * 7),
+                ("error", C.c_double), ("sta", C.c_int32), ("p", C.c_int32), ("iters1", C.c_int32), ("iters2", C.c_int32),
+                ("n_model", C.c_int32), ("n_source", C.c_int32), ("pad", C.c_int32)]
+
+
+ICP_MAX_ITERATIONS = 62
+
+
+def icp_limits():
+    """dict(src_tile, chunk, pts_per_lane, iter_cap): the nearest-neighbour launch's source tile and model chunk, the source points a lane keeps in
+    registers, and the iteration cap (pre3_icp_limits)"""
+    out = np.zeros(4, np.int32)
+    check(lib.pre3_icp_limits(dptr(out)))
+    return dict(src_tile=int(out[0]), chunk=int(out[1]), pts_per_lane=int(out[2]), iter_cap=int(out[3]))
+
+
+def _icp_seed(Rinit, Tinit):
+    R = None if Rinit is None else np.ascontiguousarray(f64(Rinit).reshape(3, 3))
+    T = None if Tinit is None else f64(Tinit).reshape(3).copy()
+    return R, T
+
+
+def _icp_result(r, corr, data2, log, pix=None):
+    """the ICP's outputs as a dict; sta == 0 (not run): only sta"""
+    sta = int(r.sta)
+    if sta == 0:
+        return dict(sta=0)
+    p, n2, it = int(r.p), int(r.n_source), int(r.iters1) + int(r.iters2)
+    out = dict(R=np.array(r.R).reshape(3, 3), t=np.array(r.t), Rtot=np.array(r.Rtot).reshape(3, 3), ttot=np.array(r.ttot), u=np.array(r.u),
+               error=float(r.error), sta=sta, p=p, iters1=int(r.iters1), iters2=int(r.iters2), n_model=int(r.n_model), n_source=n2,
+               corr=corr[:p].copy(), data2=data2[:n2].T.copy(), log=log[:it].copy())
+    if pix is not None:
+        out["corr_pix"] = pix[:p].copy()
+    return out
+
+
+def icp_with_init(data1, data2, res, Rinit=None, Tinit=None, device=0):
+    """[R, t, corr, error, data2] = icp_with_init(data1, data2, res, Rinit, Tinit) (TestScripts/icp_with_init.m) on the device with the exact nearest
+    neighbour in place of dsearchn's triangulation.  data1 (3, n1) the model, data2 (3, n2) the source.  Returns dict(R, t -- the accumulated
+    registration of the seeded source --, Rtot = R Rinit, ttot = R Tinit + t, u = [ttot; R2q(Rtot)], corr (p, 3) = [model, source, D] 1-based,
+    p, error, data2 (3, n2) registered, sta (1 ended by the reference's rule, 2 an iteration found fewer than three pairs), iters1, iters2,
+    log (iterations, 3) = [phase, p, sum(D) / (p res)])."""
+    d1, d2 = np.ascontiguousarray(f64(data1).T), np.ascontiguousarray(f64(data2).T)
+    assert d1.ndim == 2 and d2.ndim == 2 and d1.shape[1] == 3 and d2.shape[1] == 3
+    n1, n2 = d1.shape[0], d2.shape[0]
+    R, T = _icp_seed(Rinit, Tinit)
+    r = IcpResult()
+    corr, out2, log = np.zeros((max(min(n1, n2), 1), 3)), np.zeros((max(n2, 1), 3)), np.zeros((ICP_MAX_ITERATIONS, 3))
+    check(lib.pre3_icp(int(device), dptr(d1), n1, dptr(d2), n2, float(res), dptr(R), dptr(T), C.byref(r), dptr(corr), dptr(out2), dptr(log)))
+    return _icp_result(r, corr, out2, log)
+
+
+def _icp_frame_buffers(cur, stride):
+    npix = cur.rows * cur.cols
+    ncand = -(-cur.rows // max(int(stride), 1)) * -(-cur.cols // max(int(stride), 1))
+    return np.zeros((ncand, 3)), np.zeros((ncand, 2), np.int32), np.zeros((ncand, 3)), np.zeros((ICP_MAX_ITERATIONS, 3)), npix
+
+
+def icp_frames(prev, cur, res, Rinit=None, Tinit=None, stride=1):
+    """icp_with_init between two resident frames (sr4000.SrFrame): the model every pixel of prev's filtered planes as [-x; -y; z] in column-major pixel
+    order, the source cur's pixels at rows and columns 0, stride, ...; pixels with a non-finite coordinate or z <= 0 dropped on the device.  The dict of
+    icp_with_init plus n_model, n_source (the kept counts) and corr_pix (p, 2): the 0-based column-major pixel of either side of every pair."""
+    R, T = _icp_seed(Rinit, Tinit)
+    corr, pix, out2, log, _ = _icp_frame_buffers(cur, stride)
+    r = IcpResult()
+    check(lib.pre3_icp_frames(prev._h, cur._h, int(stride), float(res), dptr(R), dptr(T), C.byref(r), dptr(corr), dptr(pix), dptr(out2), dptr(log)))
+    return _icp_result(r, corr, out2, log, pix)
+
+
+def icp_pair_seeded(prev, cur, seed, seq=0, thresh=1.5, stride=1, res=0.02):
+    """vo_pair_seeded with icp_frames queued behind it on the same stream, seeded on the device with the pair's rot, trans: one host wait.  Returns
+    (pair, icp): pair is vo_pair_seeded's dict, bit for bit; icp is icp_frames' dict, or dict(sta=0) when the pair did not end in sta == 1."""
+    n1 = max(int(getattr(prev, "n_kept", 0)), 1)
+    pnum, capped = C.c_int32(0), C.c_int32(0)
+    match = np.zeros((2, n1), order="F")
+    p1, p2 = np.zeros((n1, 3)), np.zeros((n1, 3))
+    draws, cnum, state, inl = np.zeros((700, 4), np.int32), np.zeros(700, np.int32), np.zeros(700, np.int32), np.zeros(n1, np.int32)
+    vres, r = VoResult(), IcpResult()
+    corr, pix, out2, log, _ = _icp_frame_buffers(cur, stride)
+    check(lib.pre3_icp_pair_seeded(prev._h, cur._h, float(thresh), int(seed), int(seq), int(stride), float(res), C.byref(pnum), dptr(match), dptr(p1),
+                                   dptr(p2), dptr(draws), C.byref(capped), dptr(cnum), dptr(state), dptr(inl), C.byref(vres), C.byref(r), dptr(corr),
+                                   dptr(pix), dptr(out2), dptr(log)))
+    pnum = int(pnum.value)
+    rst = vo_rst(pnum) if pnum >= 4 else 0
+    pair = _result(vres, cnum[:rst].copy(), state[:rst].copy(), inl[:pnum if rst else 0].copy())
+    pair["pset1"], pair["pset2"] = p1[:pnum if rst else 0].T.copy(), p2[:pnum if rst else 0].T.copy()
+    pair["draws"], pair["capped"] = draws[:rst].copy(), int(capped.value)
+    pair["match"], pair["pnum"], pair["rst"] = match[:, :pnum].copy(order="F"), pnum, rst
+    return pair, _icp_result(r, corr, out2, log, pix)
+
+
+def icp_nn_bench(data1, data2, reps=20, device=0):
+    """milliseconds of one nearest-neighbour launch on resident clouds (measurement only)"""
+    d1, d2 = np.ascontiguousarray(f64(data1).T), np.ascontiguousarray(f64(data2).T)
+    ms = C.c_double(0)
+    check(lib.pre3_icp_nn_bench(int(device), dptr(d1), d1.shape[0], dptr(d2), d2.shape[0], int(reps), C.byref(ms)))
+    return ms.value
 
 
 def vo_bench(pset1, pset2, draws, reps=20, device=0):

@@ -936,6 +936,59 @@ PRE3_API int pre3_vo_pair_cov_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, do
 PRE3_API int pre3_predict_pair_cov_seeded(pre3_ctx *ctx, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq,
                                           int32_t *pnum_out, pre3_vo_result *res_out, double *cov_out, int32_t *cov_status_out);
 
+/* ---- dense ICP between two point clouds: the refinement of the VO pair's pose ---------------------------------------------------
+ * TestScripts/icp_with_init.m:34-120 (Mian's ICP seeded with Rinit, Tinit; the icp(Ya, Yb) lines of TestScripts/ICP_RANSAC*.m and
+ * RANSAC_CALC_VER_test.m:77-78, which the reference leaves commented out): data1 the model, data2 the source, both 3 x n column-major; data2 <- Rinit data2
+ * + Tinit (:34-35); per iteration the exact nearest model point of every source point (dsearchn without its triangulation: d = dx dx + dy dy + dz dz
+ * summed in that order, D = sqrt(d), a tie to the lowest model index), D > 2 res dropped (:51), one pair per model index -- the smallest D, on equal D
+ * the highest source index: sortrows and the 2005 code's unique, which kept the LAST occurrence (:53-56) --, reg (:103-120: means, K = Sshifted
+ * Mshifted' / n, R1 = V U' with the det < 0 repair, t1 = mm - R1 ms), data2 <- R1 data2 + t1 in place, R <- R1 R, t <- R1 t + t1; the two loops of
+ * :47-68 and :74-99 literally (maxIter 30 and `n > maxIter` after the increment: at most 31 iterations each, 62 in all); error = min(e1, e2) (:100).
+ * One deliberate departure: length(corr) is max(p, 3) for a p x 3 array and the reference fails at p = 0; here an iteration that finds p < 3 pairs ends
+ * the run with sta = 2 and the transform accumulated so far.  All fp64 on the device, no contraction; 5 launches per iteration, all 62 iterations queued
+ * at once (a launch behind the end of the run returns at once), ONE host wait.  Results are bit-equal from run to run. */
+#define PRE3_ICP_MAX_ITERATIONS 62
+typedef struct pre3_icp_result {
+    double R[9], t[3];          /* the accumulated registration of the seeded source (row-major): registered = R (Rinit data2 + Tinit) + t */
+    double Rtot[9], ttot[3];    /* R Rinit, R Tinit + t: data1 ~ Rtot data2 + ttot */
+    double u[7];                /* [ttot; R2q(Rtot)] as pre3_vo_result's u (Calculate_V_Omega_RANSAC_dr_ye.m:40-50) */
+    double error;               /* :100 */
+    int32_t sta;                /* 0 not run (pre3_icp_pair_seeded: the pair did not end in sta == 1; nothing else is written), 1 ended by the reference's
+                                   rule, 2 an iteration found fewer than three pairs (or, in the *_frames forms, a cloud kept fewer than three points) */
+    int32_t p;                  /* rows of corr: the last iteration's pairs */
+    int32_t iters1, iters2;     /* iterations of :47-68 and of :74-99 (one that found p < 3 included) */
+    int32_t n_model, n_source;  /* points of either cloud (the *_frames forms: pixels kept) */
+    int32_t pad;
+} pre3_icp_result;
+/* Stateless, host in and host out.  Rinit[9] row-major, Tinit[3] (NULL: identity / zero).  Outputs, each may be NULL: out; corr_out[p][3] = (model,
+ * source, D) per row, indices 1-based, ascending in the model index (sized by the caller for min(n1, n2) rows); data2_out 3 x n2, the registered source;
+ * log_out[62][3] = (phase, p, sum(D) / (p res)) per iteration run, zero rows behind.  PRE3_E_ARG before anything is queued: n1 < 3, n2 < 3, res not
+ * positive and finite.  A non-finite coordinate is found on the device: PRE3_E_NUMERIC after the wait, no output written. */
+PRE3_API int pre3_icp(int device, const double *data1, int n1, const double *data2, int n2, double res, const double Rinit[9], const double Tinit[3],
+                      pre3_icp_result *out, double *corr_out, double *data2_out, double *log_out);
+/* out = { source points per workgroup of the nearest-neighbour launch, model points per workgroup (the chunk staged in LDS), source points per lane,
+ * the iteration cap } */
+PRE3_API int pre3_icp_limits(int32_t out[4]);
+/* pre3_icp on two resident frames: the model is every pixel of prev's filtered planes as [-x; -y; z] (ransac_dr_ye.m:17-18, the frame the VO pair's
+ * R, T live in) in column-major pixel order, the source cur's pixels at rows and columns 0, stride, 2 stride, ... in the same order.  A pixel with a
+ * non-finite coordinate or z <= 0 is dropped from either side by an order-preserving compaction on the device; no plane is read back.  out->n_model /
+ * n_source are the kept counts; corr's indices are positions in the kept lists, corr_pix_out[p][2] the 0-based column-major pixel indices (model,
+ * source) of the same rows; data2_out is sized for the candidate count ceil(rows / stride) ceil(cols / stride).  On cur's stream with prev lent to it.
+ * PRE3_E_ARG / PRE3_E_STATE before anything is queued, the handles unchanged: a null handle, prev == cur, different devices or sizes, nothing loaded,
+ * stride < 1, res not positive and finite. */
+PRE3_API int pre3_icp_frames(pre3_sr_frame *prev, pre3_sr_frame *cur, int stride, double res, const double Rinit[9], const double Tinit[3],
+                             pre3_icp_result *out, double *corr_out, int32_t *corr_pix_out, double *data2_out, double *log_out);
+/* vodometry_dr_ye.m:139-236 with icp_with_init.m behind it: pre3_vo_pair_seeded's launches, then pre3_icp_frames' on the same stream with Rinit, Tinit
+ * read from the pair's result block on the device.  A pair that does not end in sta == 1 (fewer than four matches included): the ICP launches return at
+ * once, icp->sta = 0 and no other ICP output is written.  One host wait.  The pair's outputs, refusals and errors are pre3_vo_pair_seeded's, bit for
+ * bit; the ICP's outputs are bit-equal to pre3_icp_frames fed res->rot, res->trans. */
+PRE3_API int pre3_icp_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int stride, double res,
+                                  int32_t *pnum_out, double *match_out, double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out,
+                                  int32_t *cnum_out, int32_t *state_out, int32_t *inlier_out, pre3_vo_result *vo_res, pre3_icp_result *icp,
+                                  double *corr_out, int32_t *corr_pix_out, double *data2_out, double *log_out);
+/* measurement only: the nearest-neighbour launch of one iteration on resident clouds, averaged over reps */
+PRE3_API int pre3_icp_nn_bench(int device, const double *data1, int n1, const double *data2, int n2, int reps, double *ms_per_launch_out);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them

@@ -31,6 +31,8 @@
  *   predict_state_and_covariance.m:98-102 (Pn)                          [Pn, source] = pre3_mex('process_noise' [, Pn])                                  % the Pn of every prediction; [] -> the constant
  *   aux_code/calc_cov_RANSAC_dr_ye.m:17-30                              [cov, status, n] = pre3_mex('vo_cov', op_pset1, op_pset2, rot, trans [, inliers])  % cached RANSAC_RESULT contents
  *   predict_state_and_covariance.m:115 on two resident frames           [T, q, sta, pnum, cov, cst] = pre3_mex('predict_pair_cov', seed, seq)            % 'predict_pair' with the pair's covariance as Pn
+ *   TestScripts/icp_with_init.m on two resident frames                  [R, t, corr, err, data2, sta] = pre3_mex('icp', res, Rinit, Tinit [, stride])      % the dense refinement of a pose; 'sr_keep' as for 'vo_pair'
+ *   TestScripts/ICP_RANSAC*.m ("visually bootstrapped ICP")             [T, q, R, sta, icp_sta, err] = pre3_mex('icp_pair', seed, seq, res [, stride, thresh])   % 'vo_pair' with the ICP behind it, one wait
  *
  * The context lives in a static guarded by mexAtExit + mexLock (the convention of the reference's Coder MEX,
  * corrcoef_partitioned_mex.c:25-57).  NOT compiled in the build container (no MATLAB / mex.h there).
@@ -205,6 +207,55 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
             m[0] = r.n_iterations; m[1] = r.n_support; m[2] = r.error_mean; m[3] = r.error_std; memcpy(m + 4, r.euler, sizeof r.euler); m[7] = pnum; m[8] = capped;
         }
         mxFree(mt);
+        return;
+    }
+    if (!strcmp(cmd, "icp") || !strcmp(cmd, "icp_pair")) {
+        /* [R, t, corr, err, data2, sta] = pre3_mex('icp', res, Rinit, Tinit [, stride = 1]): icp_with_init.m:34-120 between the frame 'sr_keep' put aside (the model: every
+           pixel as [-x; -y; z]) and the resident one (the source: rows and columns 1, 1 + stride, ...), seeded with Rinit 3 x 3, Tinit 3 x 1.  R, t the accumulated
+           registration of the seeded source, corr p x 3 = [model source D] (1-based positions in the kept pixel lists), data2 3 x n2 registered, sta 1 / 2.
+           [T, q, R, sta, icp_sta, err] = pre3_mex('icp_pair', seed, seq, res [, stride = 1, thresh = 1.5]): 'vo_pair' with that ICP queued behind it on the device, seeded
+           with the pair's own R, T; T, q, R are the refined total when icp_sta >= 1, else the pair's as 'vo_pair' returns them (icp_sta = 0: the pair's sta ~= 1). */
+        const int pair = !strcmp(cmd, "icp_pair");
+        pre3_icp_result ir; pre3_vo_result vr; int32_t pnum = 0; int i, k, stride; mwSize ncand; double Ri[9], *corr, *d2;
+        if (!g_sr || !g_sr_prev) mexErrMsgTxt("pre3_mex('icp' / 'icp_pair'): needs two frames -- 'sr_frame', 'sr_keep', then 'sr_frame' again");
+        if (pair ? (nin < 4 || nin > 6) : (nin < 4 || nin > 5)) mexErrMsgTxt("pre3_mex('icp', res, Rinit, Tinit [, stride]) or pre3_mex('icp_pair', seed, seq, res [, stride, thresh])");
+        stride = nin > 4 ? (int)mxGetScalar(in[4]) : 1;
+        if (stride < 1) mexErrMsgTxt("pre3_mex('icp' / 'icp_pair'): stride must be at least 1");
+        ncand = (mwSize)((g_sr_rows + stride - 1) / stride) * (mwSize)((g_sr_cols + stride - 1) / stride);
+        memset(&ir, 0, sizeof ir);
+        if (pair) {
+            check(pre3_icp_pair_seeded(g_sr_prev, g_sr, nin > 5 ? mxGetScalar(in[5]) : 1.5, (uint64_t)mxGetScalar(in[1]), (uint64_t)mxGetScalar(in[2]), stride, mxGetScalar(in[3]),
+                                       &pnum, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, &vr, &ir, NULL, NULL, NULL, NULL));
+            {
+                const int refined = ir.sta >= 1;
+                const double *u = refined ? ir.u : vr.u, *rot = refined ? ir.Rtot : vr.rot;
+                out[0] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[0]), u, sizeof(double) * 3);
+                if (nout > 1) { out[1] = mxCreateDoubleMatrix(4, 1, mxREAL); memcpy(mxGetPr(out[1]), u + 3, sizeof(double) * 4); }
+                if (nout > 2) {
+                    out[2] = mxCreateDoubleMatrix(3, 3, mxREAL);
+                    for (i = 0; i < 3; ++i) for (k = 0; k < 3; ++k) mxGetPr(out[2])[i + 3 * k] = (refined || vr.sta == 1) ? rot[3 * i + k] : (i == k ? 1.0 : 0.0);
+                }
+                if (nout > 3) out[3] = mxCreateDoubleScalar(vr.sta);
+                if (nout > 4) out[4] = mxCreateDoubleScalar(ir.sta);
+                if (nout > 5) out[5] = mxCreateDoubleScalar(refined ? ir.error : 0.0);
+            }
+            return;
+        }
+        if (mxGetNumberOfElements(in[2]) != 9 || mxGetNumberOfElements(in[3]) != 3) mexErrMsgTxt("pre3_mex('icp'): Rinit is 3 x 3, Tinit 3 x 1");
+        for (i = 0; i < 3; ++i) for (k = 0; k < 3; ++k) Ri[3 * i + k] = mxGetPr(in[2])[i + 3 * k];      /* column-major -> row-major */
+        corr = (double *)mxMalloc(sizeof(double) * 3 * ncand); d2 = (double *)mxMalloc(sizeof(double) * 3 * ncand);
+        check(pre3_icp_frames(g_sr_prev, g_sr, stride, mxGetScalar(in[1]), Ri, mxGetPr(in[3]), &ir, corr, NULL, d2, NULL));
+        out[0] = mxCreateDoubleMatrix(3, 3, mxREAL);
+        for (i = 0; i < 3; ++i) for (k = 0; k < 3; ++k) mxGetPr(out[0])[i + 3 * k] = ir.R[3 * i + k];
+        if (nout > 1) { out[1] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[1]), ir.t, sizeof ir.t); }
+        if (nout > 2) {
+            out[2] = mxCreateDoubleMatrix(ir.p, 3, mxREAL);
+            for (i = 0; i < ir.p; ++i) for (k = 0; k < 3; ++k) mxGetPr(out[2])[i + (size_t)ir.p * k] = corr[3 * i + k];
+        }
+        if (nout > 3) out[3] = mxCreateDoubleScalar(ir.error);
+        if (nout > 4) { out[4] = mxCreateDoubleMatrix(3, ir.n_source, mxREAL); memcpy(mxGetPr(out[4]), d2, sizeof(double) * 3 * (size_t)ir.n_source); }
+        if (nout > 5) out[5] = mxCreateDoubleScalar(ir.sta);
+        mxFree(corr); mxFree(d2);
         return;
     }
     if (!strcmp(cmd, "plane_frame")) {       /* [R, sta, B, n_inliers] = pre3_mex('plane_frame', seed, seq [, n_draw = 1001, box = [80 144 50 120], t = 0.02]): plane_fit_to_data.m:7-149 on
