@@ -117,7 +117,6 @@ int wait_mail(pre3_ctx *c, int slot, int32_t seq)
     // host for ever -- the wait has a wall-clock deadline (pre3_comm_set_timeout), and never ends in a bare hipStreamSynchronize.
     const bool coll = c->comm != nullptr;
     const double t0 = coll ? now_ms() : 0;
-    const int query_env = knob::wait_query();
     double t_q = 0;
     for (long spin = 0; coll || spin < 2000000000L; ++spin) {
         if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == seq) return PRE3_OK;
@@ -126,11 +125,9 @@ int wait_mail(pre3_ctx *c, int slot, int32_t seq)
             // to learn the state of the last launch the runtime appends a marker (a barrier packet with a completion signal) behind it, and the next
             // launch then starts ~6 us after its predecessor has ended -- the two "holes" of the step (behind k_cholp and behind the HI down-date: the
             // two places where the host polls a count) were these markers, not store drains.  So: only after 2 ms without the word.
-            if (!query_env) {
-                const double t = now_ms();
-                if (t_q == 0) { t_q = t; continue; }
-                if (t - t_q < 2.0) continue;
-            }
+            const double t = now_ms();
+            if (t_q == 0) { t_q = t; continue; }
+            if (t - t_q < 2.0) continue;
             if (hipStreamQuery(c->stream) == hipSuccess) break;
             if (coll && (spin & 0x3ffff) == 0x3ffff) {
                 PRE3_TRY(comm_poll_error(c->comm));     // a collective in front of the awaited kernel whose peer died

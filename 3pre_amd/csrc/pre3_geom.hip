@@ -110,9 +110,6 @@ __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in
             d_q2R_sola(q, R);
             for (int i = 0; i < 7; ++i) x_out[i] = pose[i];
             for (int i = 7; i < 13; ++i) x_out[i] = 0;
-            // (riders that wait for the pose -- PRE3_RIDE_POSE=0 -- get their signal right behind it: the rest of this lane's serial work, a few
-            //  hundred dependent fp64 operations, need not stand in front of the 500 projections)
-            if (pr.n_blocks && !pr.own_pose) { __threadfence(); __hip_atomic_fetch_add(pr.ctr, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
         }
         const double Qq1[16] = { w, -x, -y, -z,  x, w, z, -y,  y, -z, w, x,  z, y, -x, w };
         double Jn[16];
@@ -132,9 +129,9 @@ __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in
             for (int i = 0; i < 16; ++i) { params[i] = Qq1[i]; params[16 + i] = Jn[i]; }
         }
     }
-    // the projection riders read the landmarks from x_in (the prediction copies them unchanged) and only the POSE from x_out: block 0's
-    // signal is the only one they wait for (every block signalling cost each of them a device-scope release)
-    __syncthreads();                                               // (block 0's lane 0 has signalled the riders already, behind the pose)
+    // the projection riders read the landmarks from x_in (the prediction copies them unchanged) and compute the pose themselves (predict_pose):
+    // waiting for block 0's pose cost them its fence + counter and their own poll, about 1.5 us in front of the projections
+    __syncthreads();
     double cfix = 0; int cpos = -1;
     if (fuse_jn) {
         if (j >= 7 && j < n) { double w[4]; for (int i = 0; i < 4; ++i) w[i] = (double)(T)jn_row(sJu, i, v); for (int i = 0; i < 4; ++i) v[i] = w[i]; }
@@ -414,42 +411,16 @@ __global__ void k_project(int N, const int32_t *__restrict__ lm_type, const int3
 // mode 1 (rescue_hi_inliers.m:35-46): for ic && !li: d2 = nu' inv(H P H') nu < chi2 -> hi flag.
 // ------------------------------------------------------------------------------------------------
 
-// the HI collection (k_collect_hi's work) as the tail of the rescue launch: run by the first wave of the LAST workgroup
-struct HiArgs { int fuse, m, seq; const int32_t *meas; int32_t *hi_meas, *sel_rows, *stats, *mail; unsigned int *done; };
-__device__ __forceinline__ void collect_hi_body(int m, const int32_t *__restrict__ meas, const int32_t *__restrict__ lm_ic,
-                                                const int32_t *__restrict__ lm_li, const int32_t *lm_hi,
-                                                int32_t *__restrict__ hi_meas, int32_t *__restrict__ sel_rows, int32_t *__restrict__ stats,
-                                                int32_t *mail, int seq);
-
-__device__ __forceinline__ void hi_tail(const HiArgs &ha, const int32_t *__restrict__ ic, const int32_t *__restrict__ li, int32_t *hi)
-{
-    if (!ha.fuse) return;
-    __shared__ int s_last;
-    __syncthreads();                                   // this workgroup's hi flags are written
-    if (threadIdx.x == 0) {
-        __threadfence();
-        s_last = atomicAdd(ha.done, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (s_last && threadIdx.x < 64) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        if (threadIdx.x == 0) *ha.done = 0;
-        collect_hi_body(ha.m, ha.meas, ic, li, hi, ha.hi_meas, ha.sel_rows, ha.stats, ha.mail, ha.seq);
-    }
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void k_innovation(int N, const int32_t *__restrict__ lm_type, const int32_t *__restrict__ lm_off,
                                                     const T *__restrict__ P, int ld, const double *__restrict__ Hc, const double *__restrict__ Hl,
                                                     const int32_t *__restrict__ has_h, int mode, double chi2,
                                                     const double *__restrict__ h, const double *__restrict__ z,
                                                     const int32_t *__restrict__ ic, const int32_t *__restrict__ li, int32_t *__restrict__ hi,
-                                                    double *__restrict__ S, int32_t *__restrict__ has_S, int32_t *__restrict__ clear, int n_clear,
-                                                    HiArgs ha)
+                                                    double *__restrict__ S, int32_t *__restrict__ has_S, int32_t *__restrict__ clear, int n_clear)
 {
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n_clear; t += gridDim.x * blockDim.x) clear[t] = 0;
     innovation_body<T>(N, lm_type, lm_off, P, ld, Hc, Hl, has_h, mode, chi2, h, z, ic, li, hi, S, has_S, blockIdx.x * blockDim.x + threadIdx.x);
-    hi_tail(ha, ic, li, hi);
 }
 
 // k_project and k_innovation in ONE launch: the first of a landmark's 16 lanes projects it and writes h / H, the block
@@ -460,7 +431,7 @@ __global__ __launch_bounds__(256) void k_project_innovation(int N, const int32_t
                                                             double *Hc, double *Hl, int32_t *has_h, int mode, double chi2, double *h,
                                                             const double *__restrict__ z, const int32_t *__restrict__ ic,
                                                             const int32_t *__restrict__ li, int32_t *__restrict__ hi, double *__restrict__ S,
-                                                            int32_t *__restrict__ has_S, int32_t *__restrict__ clear, int n_clear, HiArgs ha,
+                                                            int32_t *__restrict__ has_S, int32_t *__restrict__ clear, int n_clear,
                                                             int32_t *__restrict__ clear2, int n_clear2, IcMatchRide mr)
 {
     // pre3_ic_search (round 5): the small-problem matcher's tiles are extra workgroups of this launch -- they read the descriptor bank and the scan,
@@ -480,7 +451,6 @@ __global__ __launch_bounds__(256) void k_project_innovation(int N, const int32_t
     __threadfence_block();
     __syncthreads();
     innovation_body<T>(N, lm_type, lm_off, P, ld, Hc, Hl, has_h, mode, chi2, h, z, ic, li, hi, S, has_S, blockIdx.x * blockDim.x + threadIdx.x);
-    hi_tail(ha, ic, li, hi);
 }
 
 // matching_sift_based.m:119-134
@@ -545,19 +515,6 @@ __device__ inline int wave_sum(int v)
     return v;
 }
 
-// Arguments of the selection stage when it rides at the end of the scoring launch (fuse != 0): the LAST workgroup to
-// finish (device-wide ticket) replays the reference's loop over all supports -- one kernel boundary less per step.
-struct SelArgs {
-    int fuse, n_draw, k, early_exit, seq;
-    int32_t *li_meas, *lm_li, *sel_rows, *stats, *mail;
-    unsigned int *done;
-};
-__device__ __forceinline__ void select_body(int n_draw, int k, int early_exit, int m, const int32_t *__restrict__ meas,
-                                            int32_t *support, const uint32_t *masks, int mask_words,
-                                            int32_t *__restrict__ li_meas, int32_t *__restrict__ lm_li,
-                                            int32_t *__restrict__ sel_rows, int32_t *__restrict__ stats,
-                                            int32_t *mail, int seq, int err_idx = -1);
-
 template <typename T, int K>
 __global__ __launch_bounds__(512) void k_ransac_score(int hyp_begin, const int32_t *__restrict__ hyp, int m,
                                                       const int32_t *__restrict__ meas, const int32_t *__restrict__ lm_type,
@@ -565,7 +522,7 @@ __global__ __launch_bounds__(512) void k_ransac_score(int hyp_begin, const int32
                                                       const T *__restrict__ HP, int ldw, const T *__restrict__ G, int ldg,
                                                       const double *__restrict__ row_nu, const double *__restrict__ z,
                                                       CamD cam, double threshold, int32_t *support,
-                                                      uint32_t *masks, int mask_words, SelArgs sel,
+                                                      uint32_t *masks, int mask_words,
                                                       const int32_t *__restrict__ row_col, const T *__restrict__ row_val)
 {
     constexpr int R = 2 * K;                // compile-time so that every small array stays in registers
@@ -754,21 +711,6 @@ __global__ __launch_bounds__(512) void k_ransac_score(int hyp_begin, const int32
     __syncthreads();
     if (tid == 0) { int sc = 0; for (int w2 = 0; w2 < (int)(blockDim.x >> 6); ++w2) sc += s_cnt[w2]; support[hidx] = sc; }
     for (int wd = tid; wd < mask_words; wd += blockDim.x) masks[(size_t)hidx * mask_words + wd] = s_mask[wd];
-    if (sel.fuse) {
-        __shared__ int s_last;
-        __syncthreads();                                   // this workgroup's support and mask are written
-        if (tid == 0) {
-            __threadfence();
-            s_last = atomicAdd(sel.done, 1u) == gridDim.x - 1;
-        }
-        __syncthreads();
-        if (s_last) {                                               // every thread enters (the stage's barriers are reached by all 512); 256 lanes work
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // see every other workgroup's results
-            if (tid == 0) *sel.done = 0;
-            select_body(sel.n_draw, sel.k, sel.early_exit, m, meas, support, masks, mask_words, sel.li_meas, sel.lm_li, sel.sel_rows,
-                        sel.stats, sel.mail, sel.seq);
-        }
-    }
 }
 
 // K6: sequential replay of ransac_hypotheses.m:40-80 over the supports (quirk Q1), winner's mask ->
@@ -844,7 +786,7 @@ __device__ __forceinline__ void select_body(int n_draw, int k, int early_exit, i
                                             int32_t *support, const uint32_t *masks, int mask_words,
                                             int32_t *__restrict__ li_meas, int32_t *__restrict__ lm_li,
                                             int32_t *__restrict__ sel_rows, int32_t *__restrict__ stats,
-                                            int32_t *mail, int seq, int err_idx)
+                                            int32_t *mail, int seq, int err_idx = -1)
 {
     __shared__ int s_wcnt[4], s_base;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -852,7 +794,7 @@ __device__ __forceinline__ void select_body(int n_draw, int k, int early_exit, i
     const SelBest sb = select_find_best(n_draw, k, early_exit, m, support);
     if (tid == 0) { stats[0] = sb.best; stats[1] = sb.iters; stats[2] = sb.n_hyp; stats[3] = sb.max_support; }
     const int best = sb.best, iters = sb.iters;
-    const bool act = tid < 256;                                            // the launch may have more waves (k_ransac_score: 8): they only keep the barriers
+    const bool act = tid < 256;                                            // a launch may have more waves: they only keep the barriers
     // (k_select_gather: the gather's workgroups replay select_find_best on this array while this store runs.  That is a benign race by an invariant
     //  both sides keep: only entries BEHIND the exit index `iters` are overwritten, the replay's result depends on the entries up to it alone --
     //  its exit test passes at the first index whose support suffices, and a -1 never passes it.  Trimming at or below `iters` would break it.)
@@ -1141,11 +1083,11 @@ __global__ __launch_bounds__(64) void k_collect_hi(int m, const int32_t *__restr
 {
     collect_hi_body(m, meas, lm_ic, lm_li, lm_hi, hi_meas, sel_rows, stats, mail, seq);
 }
-// The collection can ride in the gate's last workgroup (PRE3_HI_FUSE=1, round 1's form) or follow as its own launch (default): like the
-// RANSAC selection (pre3_api.hip, pre3_ransac), the in-launch form makes every workgroup pay a device-scope release and a ticket.
-static int launch_collect_hi(pre3_ctx *c, const HiArgs &ha)
+// A launch of its own, not the gate's last workgroup: like the RANSAC selection (pre3_step.hip, ransac_impl), an in-launch form would make
+// every workgroup of the gate pay a device-scope release and a ticket.
+static int launch_collect_hi(pre3_ctx *c)
 {
-    hipLaunchKernelGGL(k_collect_hi, dim3(1), dim3(64), 0, c->stream, ha.m, ha.meas, c->lm.ic, c->lm.li, c->lm.hi, ha.hi_meas, ha.sel_rows, ha.stats, ha.mail, ha.seq);
+    hipLaunchKernelGGL(k_collect_hi, dim3(1), dim3(64), 0, c->stream, c->m, c->meas, c->lm.ic, c->lm.li, c->lm.hi, c->hi_meas, c->sel_rows, c->stats, c->mail_dev, ++c->seq_collect);
     PRE3_HIP(hipGetLastError());
     return PRE3_OK;
 }
@@ -1232,10 +1174,9 @@ int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection, si
     U7 uu; for (int i = 0; i < 7; ++i) uu.v[i] = u[i];
     int blocks = ceil_div(c->n, 256);
     ProjRide pr{};
-    const int own_pose = knob::ride_pose();
     if (with_projection && c->N > 0) {
-        pr = make_proj_ride(c, PRE3_X_K_KM1, 1, 0, own_pose ? 0 : 1); pr.x_lm = c->x_kk;      // (one producer: block 0 -- or none: the riders compute the pose themselves)
-        pr.own_pose = own_pose ? 1 : 0; pr.x_prev = c->x_kk; pr.u = uu;
+        pr = make_proj_ride(c, PRE3_X_K_KM1, 1, 0, 0); pr.x_lm = c->x_kk;      // (no producer: the riders compute the pose themselves)
+        pr.own_pose = 1; pr.x_prev = c->x_kk; pr.u = uu;
     }
     InboxRide ib{ (const int4 *)c->inbox_host_dev, (int4 *)c->inbox_dev, (int)inbox_n16, c->mail_dev, inbox_seq };     // one more block when inbox_n16 > 0
     const int nb = blocks + pr.n_blocks + (inbox_n16 ? 1 : 0);
@@ -1325,18 +1266,16 @@ int launch_project_innovation(pre3_ctx *c, int which, int clear_first, int mode,
     const double *x = which == PRE3_X_K_K ? c->x_kk : c->x_km1;
     int32_t *clr = (int32_t *)((unsigned char *)c->inbox_dev + c->off_flags);
     const int n_clr = mode == 0 ? (int)(c->flags_bytes / sizeof(int32_t)) : 0;
-    HiArgs ha{};
-    if (mode == 1 && collect) ha = HiArgs{ knob::hi_fuse() ? 1 : 0, c->m, ++c->seq_collect, c->meas, c->hi_meas, c->sel_rows, c->stats, c->mail_dev, c->chol_arrive + 2 };
     dim3 g(ceil_div(c->N * 16, 256) + mr.n_blocks), b(256);
     DISPATCH_T(c,
         hipLaunchKernelGGL(k_project_innovation<double>, g, b, 0, c->stream, c->N, c->lm.type, c->lm.off, x, to_camd(c->cam), clear_first,
                            (const double *)c->P, c->ld, c->lm.Hc, c->lm.Hl, c->lm.has_h, mode, chi2, c->lm.h, c->lm.z, c->lm.ic, c->lm.li,
-                           c->lm.hi, c->lm.S, c->lm.has_S, clr, n_clr, ha, clear_ic ? c->lm.ic : nullptr, clear_ic ? c->N : 0, mr),
+                           c->lm.hi, c->lm.S, c->lm.has_S, clr, n_clr, clear_ic ? c->lm.ic : nullptr, clear_ic ? c->N : 0, mr),
         hipLaunchKernelGGL(k_project_innovation<float>, g, b, 0, c->stream, c->N, c->lm.type, c->lm.off, x, to_camd(c->cam), clear_first,
                            (const float *)c->P, c->ld, c->lm.Hc, c->lm.Hl, c->lm.has_h, mode, chi2, c->lm.h, c->lm.z, c->lm.ic, c->lm.li,
-                           c->lm.hi, c->lm.S, c->lm.has_S, clr, n_clr, ha, clear_ic ? c->lm.ic : nullptr, clear_ic ? c->N : 0, mr));
+                           c->lm.hi, c->lm.S, c->lm.has_S, clr, n_clr, clear_ic ? c->lm.ic : nullptr, clear_ic ? c->N : 0, mr));
     PRE3_HIP(hipGetLastError());
-    if (mode == 1 && collect && !ha.fuse) PRE3_TRY(launch_collect_hi(c, ha));
+    if (mode == 1 && collect) PRE3_TRY(launch_collect_hi(c));
     return PRE3_OK;
 }
 
@@ -1345,16 +1284,14 @@ int launch_innovation(pre3_ctx *c, int mode, double chi2, bool clear_flags, bool
     PRE3_TRY(pend_flush(c));                    // (reads P: a pending HI down-date goes first)
     int32_t *clr = (int32_t *)((unsigned char *)c->inbox_dev + c->off_flags);
     const int n_clr = clear_flags ? (int)(c->flags_bytes / sizeof(int32_t)) : 0;
-    HiArgs ha{};
-    if (mode == 1 && collect) ha = HiArgs{ knob::hi_fuse() ? 1 : 0, c->m, ++c->seq_collect, c->meas, c->hi_meas, c->sel_rows, c->stats, c->mail_dev, c->chol_arrive + 2 };
     dim3 g(ceil_div(c->N * 16, 256)), b(256);
     DISPATCH_T(c,
         hipLaunchKernelGGL(k_innovation<double>, g, b, 0, c->stream, c->N, c->lm.type, c->lm.off, (const double *)c->P, c->ld, c->lm.Hc,
-                           c->lm.Hl, c->lm.has_h, mode, chi2, c->lm.h, c->lm.z, c->lm.ic, c->lm.li, c->lm.hi, c->lm.S, c->lm.has_S, clr, n_clr, ha),
+                           c->lm.Hl, c->lm.has_h, mode, chi2, c->lm.h, c->lm.z, c->lm.ic, c->lm.li, c->lm.hi, c->lm.S, c->lm.has_S, clr, n_clr),
         hipLaunchKernelGGL(k_innovation<float>, g, b, 0, c->stream, c->N, c->lm.type, c->lm.off, (const float *)c->P, c->ld, c->lm.Hc,
-                           c->lm.Hl, c->lm.has_h, mode, chi2, c->lm.h, c->lm.z, c->lm.ic, c->lm.li, c->lm.hi, c->lm.S, c->lm.has_S, clr, n_clr, ha));
+                           c->lm.Hl, c->lm.has_h, mode, chi2, c->lm.h, c->lm.z, c->lm.ic, c->lm.li, c->lm.hi, c->lm.S, c->lm.has_S, clr, n_clr));
     PRE3_HIP(hipGetLastError());
-    if (mode == 1 && collect && !ha.fuse) PRE3_TRY(launch_collect_hi(c, ha));
+    if (mode == 1 && collect) PRE3_TRY(launch_collect_hi(c));
     return PRE3_OK;
 }
 
@@ -1384,10 +1321,10 @@ constexpr int SCORE_THREADS = 512;      // one measurement per lane up to m = 51
 
 template <typename T>
 static void launch_score_k(pre3_ctx *c, int k, int nb, size_t shm, int hyp_begin, double threshold, int ldg, int32_t *support_dev,
-                           uint32_t *mask_dev, int mask_words, const SelArgs &sel)
+                           uint32_t *mask_dev, int mask_words)
 {
 #define SCORE_ARGS hyp_begin, c->hyp, c->m, c->meas, c->lm.type, c->lm.off, c->x_km1, (const T *)c->HP, c->ldw, c->g_valid ? (const T *)c->G : (const T *)nullptr, ldg, \
-                   c->row_nu, c->lm.z, to_camd(c->cam), threshold, support_dev, mask_dev, mask_words, sel, c->row_col, (const T *)c->row_val
+                   c->row_nu, c->lm.z, to_camd(c->cam), threshold, support_dev, mask_dev, mask_words, c->row_col, (const T *)c->row_val
     switch (k) {
     case 1: hipLaunchKernelGGL((k_ransac_score<T, 1>), dim3(nb), dim3(SCORE_THREADS), shm, c->stream, SCORE_ARGS); break;
     case 2: hipLaunchKernelGGL((k_ransac_score<T, 2>), dim3(nb), dim3(SCORE_THREADS), shm, c->stream, SCORE_ARGS); break;
@@ -1397,20 +1334,15 @@ static void launch_score_k(pre3_ctx *c, int k, int nb, size_t shm, int hyp_begin
 #undef SCORE_ARGS
 }
 
-// select_n_draw > 0: the selection stage (k_ransac_select's work) runs in the last workgroup of this launch
 int launch_ransac_score_impl(pre3_ctx *c, int k, double threshold, int hyp_begin, int hyp_end, int ldg, int32_t *support_dev,
-                             uint32_t *mask_dev, int mask_words, int select_n_draw, int early_exit)
+                             uint32_t *mask_dev, int mask_words)
 {
     int nb = hyp_end - hyp_begin;
     if (nb <= 0) return PRE3_OK;
     size_t shm = sizeof(double) * c->m + sizeof(uint32_t) * mask_words + 16;
-    SelArgs sel{};
-    if (select_n_draw > 0) {
-        sel = SelArgs{ 1, select_n_draw, k, early_exit, ++c->seq_select, c->li_meas, c->lm.li, c->sel_rows, c->stats, c->mail_dev, c->chol_arrive + 1 };
-    }
     DISPATCH_T(c,
-        launch_score_k<double>(c, k, nb, shm, hyp_begin, threshold, ldg, support_dev, mask_dev, mask_words, sel),
-        launch_score_k<float>(c, k, nb, shm, hyp_begin, threshold, ldg, support_dev, mask_dev, mask_words, sel));
+        launch_score_k<double>(c, k, nb, shm, hyp_begin, threshold, ldg, support_dev, mask_dev, mask_words),
+        launch_score_k<float>(c, k, nb, shm, hyp_begin, threshold, ldg, support_dev, mask_dev, mask_words));
     PRE3_HIP(hipGetLastError());
     return PRE3_OK;
 }

@@ -150,7 +150,7 @@ struct pre3_ctx {
     bool k9_b3 = false;                           // fp32: K9 as three-way bf16 split on the bf16 matrix cores (PRE3_K9_B3=0 turns it off)
     void *Sp = nullptr;                           // fp32 path: bf16 planes of the factorisation's S blocks (pending updates), rcap/64 x rcap/64 x 24 KB
     void *tiles128 = nullptr; int n_tiles128 = 0; // int2[n_tiles128]: 128x128 upper-triangle tiles of k_downdate_b3, XCD-interleaved
-    unsigned int *chol_arrive = nullptr; unsigned int chol_target = 0;   // [0] panel arrivals, [1] scoring done, [2] rescue done, [3],[4] rider producers
+    unsigned int *chol_arrive = nullptr; unsigned int chol_target = 0;   // [0] panel arrivals, [1],[2] unused, [3],[4] rider producers
     unsigned int ride_target[2] = { 0, 0 };
     void *comm = nullptr; bool comm_owned = false;                 // RCCL communicator (pre3_comm.hip): pre3_comm_init / pre3_set_comm
     StepRequest req; LaunchOutcome out; Carried carry;             // the hand-offs of a call: see the three structs above
@@ -383,8 +383,7 @@ int launch_inbox_pull(pre3_ctx *c, const void *src_host_mapped, void *dst_dev, s
 int launch_slice_prepare(pre3_ctx *c, const void *src_host_mapped, size_t n16, int32_t seq, int n_zero, int k, int lo, int hi, int tag);
 int launch_window_gate(pre3_ctx *c, int M, const int32_t *pred_idx_dev, const int32_t *k1_dev, const double *zc_dev, int strict, int32_t *accept_dev);
 int launch_build_rows_impl(pre3_ctx *c, int nsel, const int32_t *sel_dev, int r_pad);
-int launch_ransac_score_impl(pre3_ctx *c, int k, double threshold, int hyp_begin, int hyp_end, int ldg, int32_t *support_dev, uint32_t *mask_dev, int mask_words,
-                             int select_n_draw = 0, int early_exit = 0);
+int launch_ransac_score_impl(pre3_ctx *c, int k, double threshold, int hyp_begin, int hyp_end, int ldg, int32_t *support_dev, uint32_t *mask_dev, int mask_words);
 int launch_ransac_select_impl(pre3_ctx *c, int n_draw, int k, int early_exit, int32_t *support_dev, const uint32_t *mask_dev, int mask_words, int err_idx = -1);
 
 // ---- marginal readers (pre3_map.hip): gathers of x and P at `which`, a pending HI down-date (PendW) and a pending rows/cols 3..6 pass (jn: Jn on the

@@ -21,15 +21,12 @@
     X(pend_hi,           "PRE3_PEND_HI",           0,  create,  "fp32 contexts, initial PRE3_OPT_PEND_HI: the HI update's down-date stays pending across the step boundary (DESIGN.md section 5e); needs 2 .. CP_MAX_NRB + 1 panels of row capacity") \
     /* ---- entry, waits, debug (pre3_api.hip, pre3_step.hip, pre3_comm.hip) */ \
     X(fuse_jn,           "PRE3_FUSE_JN",           1,  once,    "the rows/cols 3..6 <- Jn pass of a HI update completed at the start of a step rides in that step's prediction launch (0: k_jnorm_P as its own launch; same bits)") \
-    X(wait_query,        "PRE3_WAIT_QUERY",        0,  once,    "wait_mail: 1: hipStreamQuery from the first 1024 spins on (rounds 1-4); 0: only after 2 ms without the word -- the query's marker delays the next launch ~6 us") \
     X(scan_trace,        "PRE3_SCAN_TRACE",        0,  once,    "pre3_set_scan: host-side phase clock on stderr (event wait, copy + bounds check, positions, enqueue)") \
     X(step_trace,        "PRE3_STEP_TRACE",        0,  present, "host-side stage clock (debug): where the host spends a step, on stderr every 100 steps") \
     X(test_hooks,        "PRE3_TEST_HOOKS",        0,  is1,     "arms pre3_test_stall / pre3_match_shard_test_stall (tests of the communicator's deadline; not a performance switch)") \
     X(rccl_lib,          "PRE3_RCCL_LIB",          nullptr, text, "path of the RCCL library pre3_comm_* binds (default: librccl.so.1 as already loaded, else from the loader path, else /opt/rocm/lib)") \
     /* ---- the step's stage order (pre3_step.hip) */ \
     X(inline_g,          "PRE3_INLINE_G",          1,  once,    "RANSAC round: no H*P*H' launch (6.6 us in front of the scoring); the scorer and the LI gather compute their entries with k_ell_G's sum (0: k_ell_G / k_ell_G_hyp as launches; same bits)") \
-    X(hyp_ride,          "PRE3_HYP_RIDE",          1,  once,    "a caller's hypothesis table crosses PCIe as a rider of the H*P launch (frame leg 3.18 -> 3.22 k frames/s); 0: the pull as a 5-us launch of its own (rounds 2-4)") \
-    X(select_fuse,       "PRE3_SELECT_FUSE",       0,  once,    "1: the RANSAC selection rides in the scoring launch's last workgroup (round 1's form; N=500 / 200 hypotheses: 21.2 us against 10.0 + 6.7 us for the two launches, tools/score_split.py)") \
     X(fuse_rows,         "PRE3_FUSE_ROWS",         1,  once,    "updates of a subset: the ELL rows are built inside the H*P launch (0: k_build_rows + k_ell_HP; same bits)") \
     X(chol_spec0,        "PRE3_CHOL_SPEC0",        1,  once,    "LI update inside pre3_step: the factorisation (fp32: the whole persistent launch; else panel 0) is launched before the host has polled the row count (0: after)") \
     X(pend_max_rows,     "PRE3_PEND_MAX_ROWS",     128, once,   "pending HI rows above which the down-date goes out at once; 128 = 2 NB = never (two pending panels cost the next H*P launch ~19 us more, one ~5; 64 measured 5922 against 5954 steps/s)") \
@@ -37,8 +34,6 @@
     X(ride_proj,         "PRE3_RIDE_PROJ",         1,  once,    "the projection of every landmark rides in the prediction's launch (0: its own launch, A/B)") \
     X(ride_innov,        "PRE3_RIDE_INNOV",        1,  once,    "S_i (which also clears last frame's inlier flags) rides in the H*P launch of the RANSAC stage (0: its own launch)") \
     /* ---- prediction, projection, gate, selection (pre3_geom.hip) */ \
-    X(hi_fuse,           "PRE3_HI_FUSE",           0,  once,    "1: the HI collection rides in the gate's last workgroup (round 1's form: every workgroup pays a device-scope release and a ticket); 0: k_collect_hi follows as its own launch") \
-    X(ride_pose,         "PRE3_RIDE_POSE",         1,  once,    "the projection riders of the prediction compute the pose themselves (0: they wait for block 0's pose, rounds 2-4)") \
     X(gate_ride,         "PRE3_GATE_RIDE",         1,  once,    "the rescue's chi2 gate rides in the Jnorm pass's launch (0: a launch of its own behind it, rounds 3-4)") \
     X(select_gather,     "PRE3_SELECT_GATHER",     1,  once,    "pre3_step: the selection stage rides in the LI gather's launch (k_select_gather); 0: k_ransac_select + k_gather_li (same bits)") \
     X(select_gather_lds, "PRE3_SELECT_GATHER_LDS", 1,  once,    "k_select_gather in its LDS-staged form where the rows of H*P fit in 55 KB (0: the form gathering from global memory; same bits)") \
@@ -50,10 +45,9 @@
     X(chol_early,        "PRE3_CHOL_EARLY",        1,  once,    "per-panel factorisation: the last panel of an update whose row count is no multiple of 64 skips the chain steps behind its last real sub-panel (0: all of them; same bits)") \
     X(chol_trail_split,  "PRE3_CHOL_TRAIL_SPLIT",  4,  once,    "trailing updates with more than this x 2 x #CUs tiles go out as a launch of their own (no LDS, 8 workgroups per CU); 0: never") \
     X(chol_trail_p,      "PRE3_CHOL_TRAIL_P",      4,  once,    "panels per trailing sweep, clamped to 1 .. 4 (1: the one-panel sweep; same bits)") \
-    X(chol_trail_t128,   "PRE3_CHOL_TRAIL_T128",   2,  once,    "the sweep's W part in 128 x 128 super-tiles: 2 = operands staged through LDS, 1 = fragments straight from memory (0: 64 x 64 tiles)") \
+    X(chol_trail_t128,   "PRE3_CHOL_TRAIL_T128",   2,  once,    "the sweep's W part in 128 x 128 super-tiles with the operands staged through LDS (k_chol_trail_b3l); 0: 64 x 64 tiles (k_chol_trail_b3; same bits)") \
     X(k9_wgs,            "PRE3_K9_WGS",            3,  once,    "f32/f64 MFMA down-date, persistent form: workgroups per CU") \
     X(k9_form,           "PRE3_K9_FORM",           0,  once,    "f32/f64 MFMA down-date: force the one-tile (1) or the persistent (2) form (experiments)") \
-    X(k9_f64_nw8,        "PRE3_K9_F64_NW8",        3,  once,    "fp64 one-tile K9 with few tiles per CU (measured at n = 1213, r = 320: 0: 24.3 us; 1 (16-row stages, 8 waves): 30.5; 2 (32-row stages): 24.8; 3 (32-row stages, 8 waves): 22.5)") \
     X(hi_fused,          "PRE3_HI_FUSED",          1,  once,    "pre3_step: collection + HI update as k_hi_fused + a device-gated down-date; 0: k_collect_hi, host poll, four launches (same bits)") \
     X(hi_fused_two,      "PRE3_HI_FUSED_TWO",      1,  once,    "k_hi_fused takes up to 64 landmarks (two panels) when the row capacity holds them (0: one panel, A/B)") \
     X(hf_deal,           "PRE3_HF_DEAL",           1,  once,    "k_hi_fused's S dealt over the workgroups in the two-panel case (0: every workgroup builds all of S, round 5)") \
@@ -71,9 +65,7 @@
     X(strip_rl,          "PRE3_STRIP_RL",          1,  once,    "right-looking flag-driven strips") \
     X(cholp_proj,        "PRE3_CHOLP_PROJ",        1,  once,    "without the tail: the strips end with the rescue stage's projection when the step wants the gate to ride with the Jnorm pass (GateRide)") \
     /* ---- matcher, IC search, map management (pre3_match.hip, pre3_map.hip) */ \
-    X(match_i8_form,     "PRE3_MATCH_I8_FORM",     1,  once,    "integer-class matcher: 1 = query-per-lane kernel (k_match_i8_q), 0 = row-scan form (k_match_i8_mfma + reduce), A/B") \
     X(match_float_form,  "PRE3_MATCH_FLOAT_FORM",  1,  call,    "float / double matcher: 0: exact VALU kernels only, 1: auto (matrix-core paths chosen by the data), 2: never the int8 route (A/B, tests)") \
-    X(match_rank_form,   "PRE3_MATCH_RANK_FORM",   1,  call,    "ranked matcher: 1: k_rank_tiled, tiled both ways, three launches; 0: k_match_rank, one launch, database streamed per 16 queries; 2: 128 queries per workgroup, database staged through LDS (round 6; measured, 4096 x 4096 unit-norm doubles: form 2 52.2 us per match, form 1 43.5)") \
     X(ic_rank,           "PRE3_IC_RANK",           1,  call,    "pre3_ic_search: siftmatch on the matrix cores (bf16 rank + exact re-evaluation); 0: the exact VALU kernel (A/B, tests; same bits)") \
     X(ic_fused,          "PRE3_IC_FUSED",          1,  call,    "pre3_ic_search: the fused route (k_ic_match_small + k_ic_gate_fused); 0: the ranked / exact routes (A/B, tests)") \
     X(ic_ride,           "PRE3_IC_RIDE",           1,  once,    "the fused route's matcher rides in the projection + S_i launch in front of the gate (0: a launch of its own, which can skip the tiles without a predicted landmark)") \

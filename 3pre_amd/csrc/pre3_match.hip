@@ -10,7 +10,6 @@
 //   * uint8 / int8 classes: distances are integers; d2 = |a|^2 + |b|^2 - 2 a.b is evaluated exactly in
 //     int32 on the matrix cores (v_mfma_i32_32x32x32_i8; uint8 is re-centred by -128, which leaves a-b
 //     unchanged) with the best/second-best scan fused into the epilogue.
-#include <atomic>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -282,7 +281,7 @@ __global__ __launch_bounds__(256) void k_match_i8_mfma(int NDp, int K1, int K2, 
 // block's MFMAs, four register sets in rotation); operands are pre-packed in fragment order (k_pack_i8_v), so a fragment load is 1 KB
 // contiguous.  At the end the four lane groups of a query (interleaved database rows) and the 16 waves
 // are merged with the order-independent (best, second, first-arg) statistic through 3 KB of LDS.  4096 queries = 256 workgroups: one
-// per CU.  Measured at 4096 x 4096 x 128 (tools/match_ab.py): 11.4 us against 25.6 us for the row-scan form; of that 2.6 us is an empty
+// per CU.  Measured at 4096 x 4096 x 128: 11.4 us against 25.6 us for the row-scan form; of that 2.6 us is an empty
 // launch, ~3 us the scan's vector instructions, ~1 us the matrix pipe, the rest the stream of the database through L2 (every workgroup
 // reads all of it: K2 x 128 B at ~64 B/clk/CU) and the prologue's dependent loads.  (Tried: 32-query workgroups on the 32x32x32 MFMA with
 // the database split between workgroups + a ticket merge -- 15-20 us; norms in LDS -- no change; three blocks in flight -- this form.)
@@ -476,7 +475,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr double RK_E = 1.8e-4;
 constexpr float RK_PAD_NORM = 3.0e38f;
-constexpr int RK_WAVES = 16, RK_Q = 16, RK_CAP = 64;
+constexpr int RK_CAP = 64;                            // candidates per query (one per lane of the tail's wave)
 
 // One wave re-evaluates one query's candidates in the reference's arithmetic (siftmatch.c:97-116: bin 0..ND-1, subtract, multiply, add,
 // contraction off).  The accumulation is a chain over the bins, the loads are not: the wave fetches RK_CH candidate columns at a time into
@@ -603,140 +602,15 @@ __global__ __launch_bounds__(256) void k_rank_pack(int ND, int K, int Kp, const 
     if (fl) atomicOr(flags, fl);
 }
 
-template <typename T>
-__global__ __launch_bounds__(64 * RK_WAVES) void k_match_rank(int ND, int K1, int K2, int K2p, const v4i *__restrict__ Qh, const v4i *__restrict__ Ql,
-                                                                const v4i *__restrict__ Dh, const v4i *__restrict__ Dl, const float *__restrict__ nq,
-                                                                const float *__restrict__ nU, const float *__restrict__ nL, const T *__restrict__ L1,
-                                                                const T *__restrict__ L2, int k2_offset, double *__restrict__ obest,
-                                                                double *__restrict__ osecond, int32_t *__restrict__ oarg, int *__restrict__ stats)
-{
-#pragma clang fp contract(off)
-    __shared__ float mb[RK_WAVES * RK_Q], ms[RK_WAVES * RK_Q], thr_s[RK_Q];
-    __shared__ int cnt[RK_Q], cand[RK_Q][RK_CAP];
-    constexpr int RK_CH = 32 / sizeof(T), RK_LDT = 128 + 16 / sizeof(T);    // candidate columns per tail pass (1 KB each) and their LDS stride
-    __shared__ T qs[RK_Q][128], cols[RK_WAVES][RK_CH][RK_LDT];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, qi = lane & 15;
-    for (int i = tid; i < RK_Q * ND; i += 64 * RK_WAVES) {                  // the workgroup's queries as the caller gave them, for the tail
-        const int w = i / ND, b = i - w * ND, qq = blockIdx.x * RK_Q + w;
-        qs[w][b] = qq < K1 ? L1[(size_t)qq * ND + b] : (T)0;
-    }
-    const int nblk = K2p / 16;
-    struct Set { v4i h[4], l[4]; v4f n; };
-    v4i fqh[4], fql[4];
-    {
-        const v4i *qh = Qh + (size_t)blockIdx.x * 256 + lane, *ql = Ql + (size_t)blockIdx.x * 256 + lane;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) { fqh[s] = qh[64 * s]; fql[s] = ql[64 * s]; }
-    }
-    auto load = [&](int blk, Set &S, const float *__restrict__ norms) {
-        const v4i *dh = Dh + (size_t)blk * 256 + lane, *dl = Dl + (size_t)blk * 256 + lane;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) { S.h[s] = dh[64 * s]; S.l[s] = dl[64 * s]; }
-        S.n = *reinterpret_cast<const v4f *>(norms + blk * 16 + 4 * g);
-    };
-    // database block = A operand (accumulator rows 4 (lane >> 4) + e), query block = B operand (accumulator column lane & 15)
-    auto dots = [&](const Set &S) {
-        v4f acc = { 0.f, 0.f, 0.f, 0.f };
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, S.h[s]), __builtin_bit_cast(bf16x8, fqh[s]), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, S.h[s]), __builtin_bit_cast(bf16x8, fql[s]), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, S.l[s]), __builtin_bit_cast(bf16x8, fqh[s]), acc, 0, 0, 0);
-        }
-        return acc;
-    };
-    const int last = wave < nblk ? wave + (nblk - 1 - wave) / RK_WAVES * RK_WAVES : 0;
-    auto at = [&](int b) { return b < last ? b : last; };
-    Set A, B;
-    // ---- phase 1: the two smallest upper bounds per lane
-    float best = INFINITY, second = INFINITY;
-    if (wave < nblk) {
-        auto scan = [&](const Set &S) {
-            const v4f acc = dots(S);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float u = fmaf(-2.f, acc[e], S.n[e]);
-                second = __builtin_amdgcn_fmed3f(best, u, second);
-                best = fminf(best, u);
-            }
-        };
-        load(wave, A, nU);
-        for (int blk = wave; blk < nblk; blk += 2 * RK_WAVES) {
-            load(at(blk + RK_WAVES), B, nU);
-            scan(A);
-            if (blk + RK_WAVES >= nblk) break;
-            load(at(blk + 2 * RK_WAVES), A, nU);
-            scan(B);
-        }
-    }
-#pragma unroll
-    for (int o = 16; o <= 32; o <<= 1) {
-        const float ob = __shfl_xor(best, o, 64), os = __shfl_xor(second, o, 64);
-        second = fminf(fmaxf(best, ob), fminf(second, os));
-        best = fminf(best, ob);
-    }
-    if (g == 0) { mb[wave * RK_Q + lane] = best; ms[wave * RK_Q + lane] = second; }
-    __syncthreads();
-    if (tid < RK_Q) {
-        float b = mb[tid], s2 = ms[tid];
-#pragma unroll
-        for (int w = 1; w < RK_WAVES; ++w) {
-            const float ob = mb[w * RK_Q + tid], os = ms[w * RK_Q + tid];
-            s2 = fminf(fmaxf(b, ob), fminf(s2, os));
-            b = fminf(b, ob);
-        }
-        const int q = blockIdx.x * RK_Q + tid;
-        thr_s[tid] = s2 + (float)(2.0 * RK_E) * (q < K1 ? nq[q] : 0.f);       // lower bound <= upper bound of the second best, the query's norm moved across
-        cnt[tid] = 0;
-    }
-    __syncthreads();
-    // ---- phase 2: the candidates
-    if (wave < nblk) {
-        const float thr = thr_s[qi];
-        auto emit = [&](int blk, const Set &S) {
-            const v4f acc = dots(S);
-            float lw[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) lw[e] = fmaf(-2.f, acc[e], S.n[e]);
-            if (fminf(fminf(lw[0], lw[1]), fminf(lw[2], lw[3])) <= thr) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int idx = blk * 16 + 4 * g + e;
-                    if (lw[e] <= thr && idx < K2) {
-                        const int p = atomicAdd(&cnt[qi], 1);
-                        if (p < RK_CAP) cand[qi][p] = idx;
-                    }
-                }
-            }
-        };
-        load(wave, A, nL);
-        for (int blk = wave; blk < nblk; blk += 2 * RK_WAVES) {
-            load(at(blk + RK_WAVES), B, nL);
-            emit(blk, A);
-            if (blk + RK_WAVES >= nblk) break;
-            load(at(blk + 2 * RK_WAVES), A, nL);
-            emit(blk + RK_WAVES, B);
-        }
-    }
-    __syncthreads();
-    // ---- tail: wave w re-evaluates query w's candidates (rank_tail_wave)
-    const int q = blockIdx.x * RK_Q + wave;
-    if (q >= K1) return;
-    const int n = cnt[wave];
-    T eb, es; int ek;
-    rank_tail_wave<T>(ND, K2, n, cand[wave], qs[wave], &cols[wave][0][0], L2, lane, eb, es, ek, stats);
-    if (lane == 0) { obest[q] = (double)eb; osecond[q] = (double)es; oarg[q] = ek < 0 ? -1 : ek + k2_offset; if (stats) atomicAdd(stats + 1, n < RK_CAP ? n : RK_CAP); }
-}
-
-// ---- the same two phases tiled BOTH ways (the form used when there is enough work for it) -----------------------------------------
-// k_match_rank streams the whole database (K2 x 512 B of planes) into every 16-query workgroup, twice: at 4096 x 4096 that is 2 x 512 MB
-// through the L2 -> CU paths and sets its time (phase 1 23 us, phase 2 20 us).  Here a workgroup (8 waves) owns RT_NQB x 16 = 64 queries and
+// ---- the two phases, tiled BOTH ways ------------------------------------------------------------------------------------------------
+// Streaming the whole database (K2 x 512 B of planes) into every 16-query block, once per phase, would be 2 x 512 MB through the L2 -> CU
+// paths at 4096 x 4096 and would set the time.  Here a workgroup (8 waves) owns RT_NQB x 16 = 64 queries and
 // ONE slice of the database; every wave keeps the fragments of all 64 queries in registers (4 query blocks x 2 planes x 4 k-steps = 128 VGPRs)
 // and walks its share of the slice's blocks, so one 8 KB database fragment set feeds 4 x 12 = 48 MFMAs instead of 12 and the launch is bound by
 // the matrix pipe, not by operand delivery.  The price is that a query's database is spread over several workgroups:
-//   k_rank_bounds   phase 1 per (query group, slice): the two smallest upper bounds -> pb / ps [slice][query]; zeroes the candidate counters
-//   k_rank_emit     merges the slices' bounds into U2, phase 2 on its slice, candidates appended to per-query lists in global memory
-//   k_rank_tail     one wave per query: exact re-evaluation of the listed candidates (the tail of k_match_rank)
+//   k_rank_tiled<0> phase 1 per (query group, slice): the two smallest upper bounds -> pb / ps [slice][query]; zeroes the candidate counters
+//   k_rank_tiled<1> merges the slices' bounds into U2, phase 2 on its slice, candidates appended to per-query lists in global memory
+//   k_rank_tail     one wave per query: exact re-evaluation of the listed candidates (rank_tail_wave)
 // ---------------------------------------------------------------------------------------------------------------------------------
 constexpr int RT_NQB = 4, RT_WAVES = 8, RT_Q = 16 * RT_NQB;
 
@@ -776,7 +650,7 @@ __global__ __launch_bounds__(64 * RT_WAVES) void k_rank_tiled(int K1, int K2, in
         for (int s = 0; s < 4; ++s) { fqh[t][s] = qst[0][t * 256 + 64 * s + lane]; fql[t][s] = qst[1][t * 256 + 64 * s + lane]; }
     float thr[RT_NQB];
     if (PHASE == 1) {
-        // U2 of a query = second smallest upper bound over all slices; the query's own norm moved across (see k_match_rank)
+        // U2 of a query = second smallest upper bound over all slices; the query's own norm moved across (a lower bound <= the upper bound of the second best)
 #pragma unroll
         for (int t = 0; t < RT_NQB; ++t) {
             const int q = qg * RT_Q + 16 * t + qi;
@@ -869,167 +743,7 @@ __global__ __launch_bounds__(64 * RT_WAVES) void k_rank_tiled(int K1, int K2, in
     }
 }
 
-// ---- round 6: the same two phases with 128 queries per workgroup and the database slice staged through LDS --------------------------------------------
-// k_rank_tiled moves 2 MB of database planes into every one of its K1p / 64 query groups and 2 MB of query planes into every slice: 136 MB through the
-// L2 -> CU paths per phase at 4096 x 4096 (64 groups x 4 slices), which is what sets its time.  Here a workgroup owns TWO sets of four query blocks -- waves
-// 0-3 hold the fragments of queries 0..63 of the group, waves 4-7 those of 64..127 -- and every block of the slice is fetched ONCE (LDS-DMA, three-slot ring
-// of four blocks) and read from LDS by one wave of each half: 32 groups x 8 slices, 80 MB per phase.  Same MFMA chains per (query block, database block)
-// as k_rank_tiled: the same bounds, the same candidate sets.
-// *(measured, round 6)* 52.2 us per match against k_rank_tiled's 43.5 (unit-norm doubles), 47.3 against 40.0 (floats), with a three- or a four-slot ring alike:
-// the phases are NOT bound by operand delivery at this size -- both forms sit at three times their MFMA time, and the lock-step of eight waves per step
-// costs more than the halved traffic saves.  Kept as PRE3_MATCH_RANK_FORM=2 (bit-identical: tests/test_gpu_match_rank.py), not the default.
-constexpr int R2_Q = 128, R2_STEP = 4;                // queries per workgroup; database blocks per step (one per wave of a half)
-template <int PHASE>
-__global__ __launch_bounds__(64 * RT_WAVES) void k_rank_tiled2(int K1, int K2, int K2p, int nsl, const v4i *__restrict__ Qh, const v4i *__restrict__ Ql,
-                                                                 const v4i *__restrict__ Dh, const v4i *__restrict__ Dl, const float *__restrict__ nq,
-                                                                 const float *__restrict__ norms, float *__restrict__ pb, float *__restrict__ ps, int K1p,
-                                                                 int *__restrict__ gcnt, int *__restrict__ gcand)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char r2_smem[];
-    v4i *ring = reinterpret_cast<v4i *>(r2_smem);                            // [4 slots][plane 2][R2_STEP blocks][256] v4i = 4 x 32 KB
-    __shared__ float mb[RT_WAVES][RT_Q], ms[RT_WAVES][RT_Q];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, qi = lane & 15;
-    const int half = wave >> 2, wq = wave & 3;
-    const int qg = blockIdx.x, sl = blockIdx.y;
-    const int nblk = K2p / 16;
-    const int b0 = (int)((long long)nblk * sl / nsl), b1 = (int)((long long)nblk * (sl + 1) / nsl);
-    const int nstep = (b1 - b0 + R2_STEP - 1) / R2_STEP;
-    constexpr int SLOT = 2 * R2_STEP * 256;                                  // v4i per slot
-    // this thread's share of a step's 2048 granules: granule i = tid + 512 u (u < 4): plane i >> 10, the rest linear in the step's blocks
-    auto issue = [&](const int step, const int slot) {
-        const int blk0 = b0 + step * R2_STEP;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = tid + 512 * u, pl = i >> 10, w = i & 1023;
-            int blk = blk0 + (w >> 8);
-            blk = blk < b1 ? blk : b1 - 1;                                   // (a short last step re-reads the slice's last block: never used)
-            const v4i *src = (pl ? Dl : Dh) + (size_t)blk * 256 + (w & 255);
-            __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)(ring + slot * SLOT + (i & ~63)), 16, 0, 0);
-        }
-    };
-    // the 128 queries' fragments (64 KB) go through slots 2 and 3 into registers; slots 0 and 1 take the first two steps meanwhile
-    if (nstep > 0) issue(0, 0);
-    if (nstep > 1) issue(1, 1);
-    {
-        v4i *qst = ring + 2 * SLOT;
-        for (int i = tid; i < 2 * RT_NQB * 256; i += 64 * RT_WAVES) {
-            qst[i] = Qh[(size_t)qg * 2 * RT_NQB * 256 + i]; qst[2 * RT_NQB * 256 + i] = Ql[(size_t)qg * 2 * RT_NQB * 256 + i];
-        }
-    }
-    __syncthreads();
-    v4i fqh[RT_NQB][4], fql[RT_NQB][4];
-    {
-        const v4i *qst = ring + 2 * SLOT;
-#pragma unroll
-        for (int t = 0; t < RT_NQB; ++t)
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) {
-                fqh[t][s2] = qst[(half * RT_NQB + t) * 256 + 64 * s2 + lane];
-                fql[t][s2] = qst[2 * RT_NQB * 256 + (half * RT_NQB + t) * 256 + 64 * s2 + lane];
-            }
-    }
-    __syncthreads();                                                         // (slots 2 and 3 are free)
-    if (nstep > 2) issue(2, 2);
-    float thr[RT_NQB];
-    if (PHASE == 1) {
-#pragma unroll
-        for (int t = 0; t < RT_NQB; ++t) {
-            const int q = qg * R2_Q + half * RT_Q + 16 * t + qi;
-            float b = INFINITY, s2 = INFINITY;
-            for (int x = 0; x < nsl; ++x) {
-                const float ob = pb[(size_t)x * K1p + q], os = ps[(size_t)x * K1p + q];
-                s2 = fminf(fmaxf(b, ob), fminf(s2, os));
-                b = fminf(b, ob);
-            }
-            thr[t] = s2 + (float)(2.0 * RK_E) * (q < K1 ? nq[q] : 0.f);
-        }
-    } else if (sl == 0 && tid < R2_Q) gcnt[qg * R2_Q + tid] = 0;
-    float best[RT_NQB], second[RT_NQB];
-#pragma unroll
-    for (int t = 0; t < RT_NQB; ++t) best[t] = second[t] = INFINITY;
-    for (int step = 0; step < nstep; ++step) {
-        const int slot = step & 3;
-        // this step's granules have landed (the next two steps' four per thread each may still fly), everybody's: the slot of step - 1 is free for step + 3
-        if (step + 2 < nstep) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (step + 1 < nstep) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0xc07f);                                  // (raw barrier: __syncthreads() would wait for the next steps' granules too)
-        __builtin_amdgcn_s_barrier();
-        if (step + 3 < nstep) issue(step + 3, (step + 3) & 3);
-        const int blk = b0 + step * R2_STEP + wq;
-        if (blk < b1) {
-            RtSet S;
-            const v4i *sh = ring + slot * SLOT + wq * 256 + lane, *sl2 = sh + R2_STEP * 256;
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) { S.h[s2] = sh[64 * s2]; S.l[s2] = sl2[64 * s2]; }
-            S.n = *reinterpret_cast<const v4f *>(norms + blk * 16 + 4 * g);
-            v4f acc[RT_NQB];
-#pragma unroll
-            for (int t = 0; t < RT_NQB; ++t) acc[t] = v4f{ 0.f, 0.f, 0.f, 0.f };
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) {
-#pragma unroll
-                for (int t = 0; t < RT_NQB; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, S.h[s2]), __builtin_bit_cast(bf16x8, fqh[t][s2]), acc[t], 0, 0, 0);
-#pragma unroll
-                for (int t = 0; t < RT_NQB; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, S.h[s2]), __builtin_bit_cast(bf16x8, fql[t][s2]), acc[t], 0, 0, 0);
-#pragma unroll
-                for (int t = 0; t < RT_NQB; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, S.l[s2]), __builtin_bit_cast(bf16x8, fqh[t][s2]), acc[t], 0, 0, 0);
-            }
-#pragma unroll
-            for (int t = 0; t < RT_NQB; ++t) {
-                if (PHASE == 0) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float u = fmaf(-2.f, acc[t][e], S.n[e]);
-                        second[t] = __builtin_amdgcn_fmed3f(best[t], u, second[t]);
-                        best[t] = fminf(best[t], u);
-                    }
-                } else {
-                    float lw[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) lw[e] = fmaf(-2.f, acc[t][e], S.n[e]);
-                    if (fminf(fminf(lw[0], lw[1]), fminf(lw[2], lw[3])) <= thr[t]) {
-                        const int q = qg * R2_Q + half * RT_Q + 16 * t + qi;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const int idx = blk * 16 + 4 * g + e;
-                            if (lw[e] <= thr[t] && idx < K2 && q < K1) {
-                                const int p2 = atomicAdd(&gcnt[q], 1);
-                                if (p2 < RK_CAP) gcand[(size_t)q * RK_CAP + p2] = idx;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (PHASE == 0) {
-#pragma unroll
-        for (int t = 0; t < RT_NQB; ++t) {
-#pragma unroll
-            for (int o = 16; o <= 32; o <<= 1) {
-                const float ob = __shfl_xor(best[t], o, 64), os = __shfl_xor(second[t], o, 64);
-                second[t] = fminf(fmaxf(best[t], ob), fminf(second[t], os));
-                best[t] = fminf(best[t], ob);
-            }
-            if (g == 0) { mb[wave][16 * t + lane] = best[t]; ms[wave][16 * t + lane] = second[t]; }
-        }
-        __syncthreads();
-        if (tid < R2_Q) {
-            const int hf = tid >> 6, qq = tid & 63;
-            float b = mb[4 * hf][qq], s2 = ms[4 * hf][qq];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) {
-                const float ob = mb[4 * hf + w][qq], os = ms[4 * hf + w][qq];
-                s2 = fminf(fmaxf(b, ob), fminf(s2, os));
-                b = fminf(b, ob);
-            }
-            pb[(size_t)sl * K1p + qg * R2_Q + tid] = b; ps[(size_t)sl * K1p + qg * R2_Q + tid] = s2;
-        }
-    }
-}
-
-// one wave per query: the candidates of k_rank_tiled<1>, re-evaluated as the tail of k_match_rank does
+// one wave per query: the candidates of k_rank_tiled<1>, re-evaluated exactly (rank_tail_wave)
 template <typename T>
 __global__ __launch_bounds__(256) void k_rank_tail(int ND, int K1, int K2, const T *__restrict__ L1, const T *__restrict__ L2, const int *__restrict__ gcnt,
                                                     const int *__restrict__ gcand, int k2_offset, double *__restrict__ obest, double *__restrict__ osecond,
@@ -1213,7 +927,7 @@ static int i8_prepare(I8Match &m, int ND, int K1, const T *L1, int K2, const T *
     size_t np = (size_t)m.K1p * m.ntn * 4;            // four partials (32-column chunks) per 128-column tile (row-scan form)
     PRE3_TRY(m.pb.alloc(sizeof(int) * np)); PRE3_TRY(m.ps.alloc(sizeof(int) * np)); PRE3_TRY(m.pa.alloc(sizeof(int) * np));
     PRE3_TRY(m.ob.alloc(sizeof(double) * K1)); PRE3_TRY(m.os.alloc(sizeof(double) * K1)); PRE3_TRY(m.oa.alloc(sizeof(int32_t) * K1));
-    m.frag = knob::match_i8_form() == 1 && m.NDp == 128;
+    m.frag = m.NDp == 128;
     launch_pack_i8<T>(ND, m.NDp, K1, m.K1p, (const T *)r1.p, center, (int8_t *)m.A.p, (int *)m.na.p, m.frag);
     launch_pack_i8<T>(ND, m.NDp, K2, m.K2p, (const T *)r2.p, center, (int8_t *)m.B.p, (int *)m.nb.p, m.frag);
     PRE3_HIP(hipGetLastError());
@@ -1250,12 +964,11 @@ static int partial_i8(int ND, int K1, const T *L1, int K2, const T *L2, int cent
     return PRE3_OK;
 }
 
-// device-resident state of the float-class matcher (k_rank_pack / k_match_rank / the int8 route), reusable across calls
+// device-resident state of the float-class matcher (k_rank_pack / k_rank_tiled + k_rank_tail / the int8 route), reusable across calls
 struct RankMatch {
     int cls = 0, ND = 0, K1 = 0, K2 = 0, K1p = 0, K2p = 0, route = 0;     // route 0: exact kernels (data outside the bounds), 1: int8 MFMA, 2: bf16 rank + re-evaluation
     DevBuf L1, L2, qh, ql, dh, dl, nq, nqU, nqL, nU, nL, nd, fl, pb, ps, gcnt, gcand;
-    int nsl = 1;                                                          // database slices of the tiled form (k_rank_tiled)
-    int nsl2 = 0;                                                         // ... of the LDS-staged form with 128 queries per workgroup (k_rank_tiled2); 0: that form does not apply
+    int nsl = 1;                                                          // database slices (k_rank_tiled)
     I8Match m;                                                            // int8 operands + the outputs (ob, os, oa) of every route
 };
 template <typename T>
@@ -1284,10 +997,8 @@ static int rank_prepare(RankMatch &r, int ND, int K1, const T *L1, int K2, const
         }
         const int groups = r.K1p / RT_Q, nblk = r.K2p / 16;
         r.nsl = std::max(1, std::min(std::min(ceil_div(ncu, groups), nblk / RT_WAVES), 64));
-        // (k_rank_tiled2: K1p / 128 groups, at least four steps of four blocks per slice)
-        r.nsl2 = (r.K1p % R2_Q == 0 && nblk >= 4 * R2_STEP) ? std::max(1, std::min(std::min(ceil_div(ncu, r.K1p / R2_Q), nblk / (4 * R2_STEP)), 64)) : 0;
     }
-    PRE3_TRY(r.pb.alloc(sizeof(float) * (size_t)std::max(r.nsl, r.nsl2) * r.K1p)); PRE3_TRY(r.ps.alloc(sizeof(float) * (size_t)std::max(r.nsl, r.nsl2) * r.K1p));
+    PRE3_TRY(r.pb.alloc(sizeof(float) * (size_t)r.nsl * r.K1p)); PRE3_TRY(r.ps.alloc(sizeof(float) * (size_t)r.nsl * r.K1p));
     PRE3_TRY(r.gcnt.alloc(sizeof(int) * r.K1p)); PRE3_TRY(r.gcand.alloc(sizeof(int) * (size_t)r.K1p * RK_CAP));
     PRE3_TRY(m.A.alloc((size_t)m.K1p * 128)); PRE3_TRY(m.B.alloc((size_t)m.K2p * 128));
     PRE3_TRY(m.na.alloc(sizeof(int) * m.K1p)); PRE3_TRY(m.nb.alloc(sizeof(int) * m.K2p));
@@ -1309,40 +1020,13 @@ static int rank_run(RankMatch &r, int k2_offset, hipStream_t st, bool count = fa
 {
     if (r.route == 1) return i8_run(r.m, k2_offset, st);
     PRE3_CHECK(r.route == 2, PRE3_E_STATE, "float-class matcher: the data is outside the ranked path's bounds");
-    const int form = knob::match_rank_form();
-    if (form == 2 && r.nsl2 > 0) {
-        static std::atomic<int> attr_ok{ 0 };
-        if (attr_ok.load() == 0) {
-            const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(k_rank_tiled2<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void *>(k_rank_tiled2<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            attr_ok.store(e0 == hipSuccess && e1 == hipSuccess ? 1 : -1);
-        }
-        if (attr_ok.load() == 1) {
-            dim3 g(r.K1p / R2_Q, r.nsl2), b(64 * RT_WAVES);
-            hipLaunchKernelGGL((k_rank_tiled2<0>), g, b, 128 * 1024, st, r.K1, r.K2, r.K2p, r.nsl2, (const v4i *)r.qh.p, (const v4i *)r.ql.p, (const v4i *)r.dh.p, (const v4i *)r.dl.p,
-                               (const float *)r.nq.p, (const float *)r.nU.p, (float *)r.pb.p, (float *)r.ps.p, r.K1p, (int *)r.gcnt.p, (int *)r.gcand.p);
-            hipLaunchKernelGGL((k_rank_tiled2<1>), g, b, 128 * 1024, st, r.K1, r.K2, r.K2p, r.nsl2, (const v4i *)r.qh.p, (const v4i *)r.ql.p, (const v4i *)r.dh.p, (const v4i *)r.dl.p,
-                               (const float *)r.nq.p, (const float *)r.nL.p, (float *)r.pb.p, (float *)r.ps.p, r.K1p, (int *)r.gcnt.p, (int *)r.gcand.p);
-            hipLaunchKernelGGL((k_rank_tail<T>), dim3(ceil_div(r.K1, 4)), dim3(256), 0, st, r.ND, r.K1, r.K2, (const T *)r.L1.p, (const T *)r.L2.p, (const int *)r.gcnt.p,
-                               (const int *)r.gcand.p, k2_offset, (double *)r.m.ob.p, (double *)r.m.os.p, (int32_t *)r.m.oa.p, count ? (int *)r.fl.p + 2 : nullptr);
-            PRE3_HIP(hipGetLastError());
-            return PRE3_OK;
-        }
-    }
-    if (form != 0) {
-        dim3 g(r.K1p / RT_Q, r.nsl), b(64 * RT_WAVES);
-        hipLaunchKernelGGL((k_rank_tiled<0>), g, b, 0, st, r.K1, r.K2, r.K2p, r.nsl, (const v4i *)r.qh.p, (const v4i *)r.ql.p, (const v4i *)r.dh.p, (const v4i *)r.dl.p,
-                           (const float *)r.nq.p, (const float *)r.nU.p, (float *)r.pb.p, (float *)r.ps.p, r.K1p, (int *)r.gcnt.p, (int *)r.gcand.p);
-        hipLaunchKernelGGL((k_rank_tiled<1>), g, b, 0, st, r.K1, r.K2, r.K2p, r.nsl, (const v4i *)r.qh.p, (const v4i *)r.ql.p, (const v4i *)r.dh.p, (const v4i *)r.dl.p,
-                           (const float *)r.nq.p, (const float *)r.nL.p, (float *)r.pb.p, (float *)r.ps.p, r.K1p, (int *)r.gcnt.p, (int *)r.gcand.p);
-        hipLaunchKernelGGL((k_rank_tail<T>), dim3(ceil_div(r.K1, 4)), dim3(256), 0, st, r.ND, r.K1, r.K2, (const T *)r.L1.p, (const T *)r.L2.p, (const int *)r.gcnt.p,
-                           (const int *)r.gcand.p, k2_offset, (double *)r.m.ob.p, (double *)r.m.os.p, (int32_t *)r.m.oa.p, count ? (int *)r.fl.p + 2 : nullptr);
-        PRE3_HIP(hipGetLastError());
-        return PRE3_OK;
-    }
-    hipLaunchKernelGGL((k_match_rank<T>), dim3(r.K1p / RK_Q), dim3(64 * RK_WAVES), 0, st, r.ND, r.K1, r.K2, r.K2p, (const v4i *)r.qh.p, (const v4i *)r.ql.p,
-                       (const v4i *)r.dh.p, (const v4i *)r.dl.p, (const float *)r.nq.p, (const float *)r.nU.p, (const float *)r.nL.p, (const T *)r.L1.p,
-                       (const T *)r.L2.p, k2_offset, (double *)r.m.ob.p, (double *)r.m.os.p, (int32_t *)r.m.oa.p, count ? (int *)r.fl.p + 2 : nullptr);
+    dim3 g(r.K1p / RT_Q, r.nsl), b(64 * RT_WAVES);
+    hipLaunchKernelGGL((k_rank_tiled<0>), g, b, 0, st, r.K1, r.K2, r.K2p, r.nsl, (const v4i *)r.qh.p, (const v4i *)r.ql.p, (const v4i *)r.dh.p, (const v4i *)r.dl.p,
+                       (const float *)r.nq.p, (const float *)r.nU.p, (float *)r.pb.p, (float *)r.ps.p, r.K1p, (int *)r.gcnt.p, (int *)r.gcand.p);
+    hipLaunchKernelGGL((k_rank_tiled<1>), g, b, 0, st, r.K1, r.K2, r.K2p, r.nsl, (const v4i *)r.qh.p, (const v4i *)r.ql.p, (const v4i *)r.dh.p, (const v4i *)r.dl.p,
+                       (const float *)r.nq.p, (const float *)r.nL.p, (float *)r.pb.p, (float *)r.ps.p, r.K1p, (int *)r.gcnt.p, (int *)r.gcand.p);
+    hipLaunchKernelGGL((k_rank_tail<T>), dim3(ceil_div(r.K1, 4)), dim3(256), 0, st, r.ND, r.K1, r.K2, (const T *)r.L1.p, (const T *)r.L2.p, (const int *)r.gcnt.p,
+                       (const int *)r.gcand.p, k2_offset, (double *)r.m.ob.p, (double *)r.m.os.p, (int32_t *)r.m.oa.p, count ? (int *)r.fl.p + 2 : nullptr);
     PRE3_HIP(hipGetLastError());
     return PRE3_OK;
 }

@@ -59,14 +59,9 @@ static int ransac_prepare(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, in
     }
     if (need_pull) {
         const size_t n16 = (sizeof(int32_t) * n_draw * k + 15) / 16;
-        if (knob::hyp_ride()) {
-            const InboxRide ib{ (const int4 *)((const unsigned char *)c->inbox_host_dev + c->off_hyp), (int4 *)c->hyp, (int)n16, c->mail_dev, ++c->seq_inbox, 10, nullptr, 0 };
-            c->inbox_pending = true;
-            PRE3_TRY(launch_ell_HP_build(c, c->HP, nullptr, 0, &ib));
-        } else {
-            PRE3_TRY(launch_inbox_pull(c, (const unsigned char *)c->inbox_host_dev + c->off_hyp, c->hyp, n16, ++c->seq_inbox)); c->inbox_pending = true;
-            PRE3_TRY(launch_ell_HP_build(c, c->HP));
-        }
+        const InboxRide ib{ (const int4 *)((const unsigned char *)c->inbox_host_dev + c->off_hyp), (int4 *)c->hyp, (int)n16, c->mail_dev, ++c->seq_inbox, 10, nullptr, 0 };
+        c->inbox_pending = true;
+        PRE3_TRY(launch_ell_HP_build(c, c->HP, nullptr, 0, &ib));
     } else
     PRE3_TRY(launch_ell_HP_build(c, c->HP));
     // H*P*H' of all measured rows is no longer built (6.6 us of launch in front of the scoring, PRE3_INLINE_G=0 brings it back): the scorer
@@ -93,7 +88,7 @@ int pre3_ransac_score(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, double
     return PRE3_OK;
 }
 
-// after the selection stage has been enqueued (its own kernel, or the tail of the scoring launch)
+// after the selection stage has been enqueued
 static int ransac_results(pre3_ctx *c, int n_draw, int32_t *support, int32_t *li_mask, int32_t stats[4])
 {
     c->li_from_host = -1; c->li_kernel = true;
@@ -191,21 +186,17 @@ static int ransac_impl(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, doubl
     c->shard_round = false; c->carry.select_pending = false;
     PRE3_TRY(ransac_prepare(c, n_draw, k, hyp, 0, -1, false, 0, table_on_device));
     int words = ceil_div(c->m, 32);
-    // Scoring, then the selection stage (the reference's loop replayed on the supports) as a launch of its own.  The selection can also ride
-    // in the scoring launch's last workgroup (PRE3_SELECT_FUSE=1, round 1's form), but measured at N=500 / 200 hypotheses that launch then
-    // takes 21.2 us against 10.0 + 6.7 us for the two (tools/score_split.py): every workgroup pays a device-scope release (an L2 write-back)
-    // and a ticket before it may finish, and the last one starts the selection behind an L2 invalidate.
-    if (knob::select_fuse()) PRE3_TRY(launch_ransac_score_impl(c, k, threshold, 0, n_draw, round_up(2 * c->m, NB), c->support, c->masks, words, n_draw, early_exit));
-    else {
-        PRE3_TRY(launch_ransac_score_impl(c, k, threshold, 0, n_draw, round_up(2 * c->m, NB), c->support, c->masks, words, 0, 0));
-        // pre3_step: the selection rides in the LI gather's launch (k_select_gather), which pre3_update_li sends next
-        if (c->req.defer_select && !support && !li_mask && !stats && select_gather_usable(c)) {
-            c->carry.select_pending = true; c->carry.sel_n_draw = n_draw; c->carry.sel_k = k; c->carry.sel_early_exit = early_exit;
-            c->li_from_host = -1; c->li_kernel = true;
-            return PRE3_OK;
-        }
-        PRE3_TRY(launch_ransac_select_impl(c, n_draw, k, early_exit, c->support, c->masks, words));
+    // Scoring, then the selection stage (the reference's loop replayed on the supports) as a launch of its own, never in the scoring launch's
+    // last workgroup: every workgroup would pay a device-scope release (an L2 write-back) and a ticket before it may finish, and the last one
+    // would start the selection behind an L2 invalidate (measured: DESIGN.md section 4a).
+    PRE3_TRY(launch_ransac_score_impl(c, k, threshold, 0, n_draw, round_up(2 * c->m, NB), c->support, c->masks, words));
+    // pre3_step: the selection rides in the LI gather's launch (k_select_gather), which pre3_update_li sends next
+    if (c->req.defer_select && !support && !li_mask && !stats && select_gather_usable(c)) {
+        c->carry.select_pending = true; c->carry.sel_n_draw = n_draw; c->carry.sel_k = k; c->carry.sel_early_exit = early_exit;
+        c->li_from_host = -1; c->li_kernel = true;
+        return PRE3_OK;
     }
+    PRE3_TRY(launch_ransac_select_impl(c, n_draw, k, early_exit, c->support, c->masks, words));
     return ransac_results(c, n_draw, support, li_mask, stats);
 }
 int pre3_ransac(pre3_ctx *c, int n_draw, int k, const int32_t *hyp, double threshold, int early_exit, int32_t *support, int32_t *li_mask,

@@ -706,84 +706,18 @@ __global__ __launch_bounds__(256) void k_chol_trail_b3(float *__restrict__ S, in
     chol_trail_b3_tile(S, lds, W, ldw, J, isW, rb, K, c0, Wp, nst_total, Sp, sp_stride, J2);
 }
 
-// The same sweep with the W part in 128 x 128 super-tiles (round 5): a wave owns a 64 x 64 tile -- four 32 x 32 accumulators that share two A and
+// The same sweep with the W part in 128 x 128 super-tiles: a wave owns a 64 x 64 tile -- four 32 x 32 accumulators that share two A and
 // two B fragment sets per k-step, i.e. half the operand bytes per MFMA of the 32 x 32-per-wave form, whose launches were bound by the rate at
 // which a CU takes operand fragments (twice the matrix-pipe time at N = 2000), not by the read-modify-write of W any more once four panels
 // share a pass.  Every 32 x 32 tile sees the products of the one-panel sweep in its order: the same bits.  S tiles (a tenth of the work) keep
-// the 64 x 64 form.  No LDS, no barrier.  (measured, N = 2000: the eight sweeps 759 -> 696 us; what is left is the fragments' latency at two waves
-// per SIMD -- requesting a k-step ahead by hand spilled (741 us), parking the tile's own values in LDS did not raise the occupancy: the compiler
-// hoists every load the register budget allows.  k_chol_trail_b3l below stages the operands through LDS instead: 635 us.)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_chol_trail_b3w(float *__restrict__ S, int lds, float *__restrict__ W, int ldw, int J, int K0, int nrb, int nW,
-                                                        const void *__restrict__ Wp, int nst_total, const void *__restrict__ Sp, int sp_stride, int J2)
-{
-    const int nK = nrb - K0, nSt = nK * (nK + 1) / 2;
-    if ((int)blockIdx.x < nSt) {
-        bool isW; int rb, K, c0;
-        chol_trail_decode(blockIdx.x, K0, nrb, nW, isW, rb, K, c0);
-        chol_trail_b3_tile(S, lds, W, ldw, J, false, rb, K, 0, Wp, nst_total, Sp, sp_stride, J2);
-        return;
-    }
-    typedef int frag_t __attribute__((ext_vector_type(4)));
-    const int t = blockIdx.x - nSt, nWp = (nW + 1) >> 1;
-    const int kp = t / nWp, wp = t - kp * nWp;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int K = K0 + 2 * kp + (wave >> 1), cb = 2 * wp + (wave & 1), c0 = cb * NB;
-    if (K >= nrb || cb >= nW) return;
-    const int lrow = 4 * (lane >> 5), lcol = lane & 31;
-    float *Cbase = W + (size_t)(K * NB) * ldw + c0 + lcol;
-    float cvv[2][2][16];
-#pragma unroll
-    for (int fa = 0; fa < 2; ++fa)
-#pragma unroll
-        for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) cvv[fa][fb][e] = Cbase[(size_t)(32 * fa + (e & 3) + 8 * (e >> 2) + lrow) * ldw + 32 * fb];
-    for (int Jp = J; Jp <= (J2 >= 0 ? J2 : J); ++Jp) {
-        const frag_t *Ap = static_cast<const frag_t *>(Sp) + ((size_t)K * sp_stride + Jp) * B3_SGRAN + lane;
-        const frag_t *Bp = static_cast<const frag_t *>(Wp) + ((size_t)(c0 >> 7) * nst_total + 4 * Jp) * B3_GRAN + (2 * ((c0 >> 6) & 1)) * 64 + lane;
-        f32x16_t acc[2][2];
-#pragma unroll
-        for (int fa = 0; fa < 2; ++fa)
-#pragma unroll
-            for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[fa][fb][e] = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            frag_t fA[2][3], fB[2][3];
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) { fA[h][pl] = Ap[q * 384 + pl * 128 + h * 64]; fB[h][pl] = Bp[q * B3_GRAN + pl * 256 + h * 64]; }
-            // (plane pairs outside, the four tiles inside: four independent accumulators between two products of the same tile)
-#define TW_MMA(px, py) \
-            _Pragma("unroll") for (int fa = 0; fa < 2; ++fa) \
-                _Pragma("unroll") for (int fb = 0; fb < 2; ++fb) \
-                    acc[fa][fb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fA[fa][px]), __builtin_bit_cast(bf16x8_t, fB[fb][py]), acc[fa][fb], 0, 0, 0)
-            TW_MMA(0, 0); TW_MMA(0, 1); TW_MMA(1, 0); TW_MMA(1, 1); TW_MMA(0, 2); TW_MMA(2, 0);
-#undef TW_MMA
-        }
-#pragma unroll
-        for (int fa = 0; fa < 2; ++fa)
-#pragma unroll
-            for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) cvv[fa][fb][e] = cvv[fa][fb][e] - acc[fa][fb][e];
-    }
-#pragma unroll
-    for (int fa = 0; fa < 2; ++fa)
-#pragma unroll
-        for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) Cbase[(size_t)(32 * fa + (e & 3) + 8 * (e >> 2) + lrow) * ldw + 32 * fb] = cvv[fa][fb][e];
-}
-
-// The super-tile sweep with the operands staged through LDS (k_downdate_b3's form): per k-step the workgroup's four operand sub-blocks -- the
+// the 64 x 64 form.
+// The operands are staged through LDS (k_downdate_b3's form): per k-step the workgroup's four operand sub-blocks -- the
 // S planes of its two row blocks, the W planes of its 128 columns: 24 KB -- come in ONCE by LDS-DMA (six 1-KB requests per wave, no registers
 // held while they travel), three stages deep, and every wave takes its twelve fragments from LDS.  A quarter of the 32 x 32-per-wave form's
-// operand traffic, and the fragments' latency is the pipeline's, not the wave's.  Same products per 32 x 32 tile in the same order.
-// (measured, N = 2000: the eight sweeps of an update 759 us with 64 x 64 tiles -> 696 us (k_chol_trail_b3w) -> 635 us; step 3.99 -> 3.81 ms.  Two
-// workgroups per CU and two stages of lookahead still leave the start of a workgroup -- its tile of W from HBM -- and part of the DMA latency exposed.)
+// operand traffic, and the fragments' latency is the pipeline's, not the wave's.
+// (measured, N = 2000: the eight sweeps of an update 759 us with 64 x 64 tiles -> 696 us with super-tiles whose fragments came straight from
+// memory -> 635 us; step 3.99 -> 3.81 ms.  Two workgroups per CU and two stages of lookahead still leave the start of a workgroup -- its tile of
+// W from HBM -- and part of the DMA latency exposed.)
 constexpr int TL_STAGE = 1536, TL_NSLOT = 3;                // granules per stage: A0 384 | A1 384 | B 768
 __global__ __launch_bounds__(256) void k_chol_trail_b3l(float *__restrict__ S, int lds, float *__restrict__ W, int ldw, int J, int K0, int nrb, int nW,
                                                         const void *__restrict__ Wp, int nst_total, const void *__restrict__ Sp, int sp_stride, int J2)
@@ -2479,16 +2413,12 @@ static int launch_chol_solve(pre3_ctx *c, int r_pad, bool first_done = false, bo
             if (paired && J % trail_p == trail_p - 1 && J + 2 <= nrb - 1) {
                 // the group J-p+1 .. J on everything from column block J+2 on
                 const int nK2 = nrb - (J + 2), nT2 = nK2 * (nK2 + 1) / 2 + nK2 * nW;
-                const int t128 = knob::chol_trail_t128();
-                if (t128 == 2) {
+                if (knob::chol_trail_t128()) {
                     static std::atomic<bool> attr{ false };
                     if (!attr.exchange(true)) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_chol_trail_b3l), hipFuncAttributeMaxDynamicSharedMemorySize, TL_NSLOT * TL_STAGE * 16);
                     hipLaunchKernelGGL(k_chol_trail_b3l, dim3(nK2 * (nK2 + 1) / 2 + ((nK2 + 1) / 2) * ((nW + 1) / 2)), dim3(256), TL_NSLOT * TL_STAGE * 16, c->stream, (float *)c->Smat, r_pad,
                                        (float *)c->W, c->ldw, J - trail_p + 1, J + 2, nrb, nW, c->Wp, c->rcap / B3_BK, c->Sp, c->rcap / NB, J);
-                } else if (t128)
-                    hipLaunchKernelGGL(k_chol_trail_b3w, dim3(nK2 * (nK2 + 1) / 2 + ((nK2 + 1) / 2) * ((nW + 1) / 2)), dim3(256), 0, c->stream, (float *)c->Smat, r_pad, (float *)c->W,
-                                       c->ldw, J - trail_p + 1, J + 2, nrb, nW, c->Wp, c->rcap / B3_BK, c->Sp, c->rcap / NB, J);
-                else
+                } else
                 hipLaunchKernelGGL(k_chol_trail_b3, dim3(nT2), dim3(256), 0, c->stream, (float *)c->Smat, r_pad, (float *)c->W, c->ldw, J - trail_p + 1, J + 2, nrb, nW,
                                    c->Wp, c->rcap / B3_BK, c->Sp, c->rcap / NB, J);
             }
@@ -2583,13 +2513,9 @@ int launch_downdate(pre3_ctx *c, int r, const void *W, int which_prior, int plan
             c->out.rescue_projected = true;
         }
         dim3 g1(c->n_tiles + nx + pr.n_blocks);
-        // fp64 with few tiles per CU (configs[1]: 210 tiles on 256 CUs): two waves per wave tile, so that every SIMD has two waves to overlap
-        const int nw8_env = knob::k9_f64_nw8();
-        if (c->dtype == PRE3_F64 && nw8_env == 1 && c->n_tiles <= 2 * c->num_cus) {
-            hipLaunchKernelGGL((k_downdate_1t<double, 16, 8>), g1, dim3(512), 0, c->stream, (double *)c->P, c->ld, (const double *)W, c->ldw, r_pad, (const int2 *)c->tiles_flat, c->num_cus, xu, pr);
-        } else if (c->dtype == PRE3_F64 && nw8_env == 2 && c->n_tiles <= 2 * c->num_cus && r_pad % 32 == 0) {
-            hipLaunchKernelGGL((k_downdate_1t<double, 32, 4>), g1, dim3(256), 0, c->stream, (double *)c->P, c->ld, (const double *)W, c->ldw, r_pad, (const int2 *)c->tiles_flat, c->num_cus, xu, pr);
-        } else if (c->dtype == PRE3_F64 && nw8_env == 3 && c->n_tiles <= 2 * c->num_cus && r_pad % 32 == 0) {
+        // fp64 with few tiles per CU (configs[1]: 210 tiles on 256 CUs): 32-row stages and two waves per wave tile, so that every SIMD has two
+        // waves to overlap (measured: DESIGN.md section 6b)
+        if (c->dtype == PRE3_F64 && c->n_tiles <= 2 * c->num_cus && r_pad % 32 == 0) {
             hipLaunchKernelGGL((k_downdate_1t<double, 32, 8>), g1, dim3(512), 0, c->stream, (double *)c->P, c->ld, (const double *)W, c->ldw, r_pad, (const int2 *)c->tiles_flat, c->num_cus, xu, pr);
         } else
         DISPATCH_T(c,

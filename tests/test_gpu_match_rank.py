@@ -1,4 +1,4 @@
-"""The float / double classes of siftmatch on the matrix cores (pre3_match.hip: k_rank_pack, k_match_rank): a bf16 distance GEMM ranks the
+"""The float / double classes of siftmatch on the matrix cores (pre3_match.hip: k_rank_pack, k_rank_tiled, k_rank_tail): a bf16 distance GEMM ranks the
 database, the candidates inside the guard band are re-evaluated in the reference's own arithmetic (sift/siftmatch.c:97-116).  Everything
 here must be BIT-identical to the oracle / to the exact VALU kernels, including scores, ties and the second-best value."""
 import ctypes as C
@@ -11,9 +11,11 @@ pytestmark = pytest.mark.gpu
 
 
 class _Form:
-    """PRE3_MATCH_FLOAT_FORM (or another switch the library reads per call) for the duration of a block (0: exact kernels only, 2: never the int8 route)"""
-    def __init__(self, v, name="PRE3_MATCH_FLOAT_FORM"):
-        self.v, self.name = v, name
+    """PRE3_MATCH_FLOAT_FORM for the duration of a block (0: exact kernels only, 2: never the int8 route)"""
+    name = "PRE3_MATCH_FLOAT_FORM"
+
+    def __init__(self, v):
+        self.v = v
 
     def __enter__(self):
         self.old = os.environ.get(self.name)
@@ -177,29 +179,28 @@ def test_full_size_double_class(pre3):
 
 
 @pytest.mark.parametrize("dt", [np.float64, np.float32])
-def test_one_launch_and_tiled_forms_agree(pre3, orc, dt):
-    """PRE3_MATCH_RANK_FORM: the tiled form (three launches, default) and the one-launch form rank with differently packed planes and
-    different reduction trees -- the exact re-evaluation makes both land on the oracle's bits"""
+def test_tiled_form_lands_on_the_oracle_s_bits(pre3, orc, dt):
+    """the ranked route (k_rank_tiled: three launches) on a problem that is no multiple of its tiles, with near matches and an exact duplicate:
+    the exact re-evaluation lands on the oracle's bits"""
     rng = np.random.default_rng(6)
     L1 = (rng.standard_normal((128, 333)) * 7).astype(dt)
     L2 = (rng.standard_normal((128, 901)) * 7).astype(dt)
     L2[:, 100:300] = L1[:, :200] + (0.05 * rng.standard_normal((128, 200))).astype(dt)
     L2[:, 900] = L2[:, 100]
     mr, dr = orc.siftmatch(L1, L2, 1.4)
-    for form in (1, 0, 2):                     # (2, round 6: 128 queries per workgroup, the database slice staged through LDS -- measured slower, kept as an option)
-        with _Form(form, "PRE3_MATCH_RANK_FORM"):
-            m, d = pre3.siftmatch(L1, L2, 1.4, return_scores=True)
-        assert np.array_equal(m, mr) and np.array_equal(d, dr), form
+    m, d = pre3.siftmatch(L1, L2, 1.4, return_scores=True)
+    assert np.array_equal(m, mr) and np.array_equal(d, dr)
 
 
-def test_lds_staged_rank_form_at_full_size_is_bit_identical(pre3):
-    """4096 x 4096 x 128 unit-norm doubles (BASELINE configs[3]'s float class): PRE3_MATCH_RANK_FORM=2 against the default form"""
+def test_full_size_unit_norm_doubles_ranked_route_is_bit_identical(pre3):
+    """4096 x 4096 x 128 unit-norm doubles (BASELINE configs[3]'s float class): (best, second, arg) of the ranked route == the exact kernels for
+    every query, and the planted pair is found"""
     rng = np.random.default_rng(11)
     L1 = rng.random((128, 4096)); L1 /= np.linalg.norm(L1, axis=0)
     L2 = rng.random((128, 4096)); L2 /= np.linalg.norm(L2, axis=0)
     L2[:, 7] = L1[:, 1234]
-    res = []
-    for form in (1, 2):
-        with _Form(form, "PRE3_MATCH_RANK_FORM"):
-            res.append(pre3.siftmatch(L1, L2, 1.5, return_scores=True))
-    assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])
+    info, got = _route(pre3, L1, L2)
+    assert info[0] == 2
+    ref = _exact_partial(pre3, L1, L2)
+    assert all(np.array_equal(g, r) for g, r in zip(got, ref))
+    assert got[2][1234] == 7 and got[0][1234] == 0.0

@@ -14,7 +14,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 #  it agrees with them to rounding, not to the bit: test_the_step_tail_agrees_with_the_launch_per_stage_form)
 VARIANTS = [
     {},
-    {"PRE3_SELECT_FUSE": "1", "PRE3_HI_FUSE": "1"},
     {"PRE3_RIDE_INNOV": "0", "PRE3_RIDE_PROJ": "0", "PRE3_RIDE_RESCUE": "0"},
     {"PRE3_CHOL_SPEC0": "0"},
     {"PRE3_FUSE_JN": "0", "PRE3_FUSE_ROWS": "0"},           # the Jnorm pass / the row build as launches of their own
@@ -27,7 +26,6 @@ VARIANTS = [
     {"PRE3_MAP_ONE_PASS": "0"},                             # map management's congruence as two gather passes (T = A P, P = T A') instead of one                        # k_select_gather reading H*P from global memory instead of staging its rows in LDS                            # the selection stage and the LI gather as two launches instead of k_select_gather
     {"PRE3_CHOL_EARLY": "0"},                               # the padded last panel runs all ten chain steps (the skipped ones change nothing)
     {"PRE3_CHOLP_PROJ": "0"},                               # the rescue stage's projection in the gate's blocks instead of on the persistent launch's strips behind their x-update
-    {"PRE3_RIDE_POSE": "0"},                                # the prediction's projection riders wait for block 0 to publish the predicted pose instead of computing it themselves
     {"PRE3_HF_DEAL": "0"},                                  # k_hi_fused: every workgroup builds all of S = H P H' + I instead of dealing its rows out from 18 rescued landmarks on (round 6)
     {"PRE3_HP_MB": "0"},                                    # H*P of the measured rows one measurement per workgroup (k_ell_HP_build) instead of four sharing the pose rows' loads (round 6)
     {"PRE3_GATE_RIDE": "0"},                                # the rescue stage's chi2 gate as a launch of its own behind the Jnorm pass instead of riding in it (round 5: GateRide recomputes the

@@ -1,6 +1,6 @@
 #!/bin/bash
 # build 3pre_amd/lib/libpre3_<tag>.so with extra -D flags on ONE source file (same-box A/B of kernel variants):
-#   tools/build_variant_file.sh pre3_match nomfma -DI8Q_EXP=1 ; PRE3_LIB=3pre_amd/lib/libpre3_nomfma.so python tools/match_ab.py child
+#   tools/build_variant_file.sh pre3_match nomfma -DI8Q_EXP=1 ; PRE3_LIB=3pre_amd/lib/libpre3_nomfma.so python tools/bench_match.py
 set -e
 src=$1; tag=$2; shift; shift
 cd 3pre_amd/csrc

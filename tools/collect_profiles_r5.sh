@@ -22,7 +22,6 @@ for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GR
   t=$(echo $set | tr ' ' '_' | cut -c1-40)
   K9_ROWS=554 timeout -k 10 180 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $R/gpurun_out/${tag}_pmc_k9s/$t -o p -- python3 $R/tools/k9ab.py > $R/gpurun_out/${tag}_pmc_k9s_$t.log 2>&1 || echo "failed: k9 $set"
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${tag}_match -o m -- python3 $R/tools/match_ab.py child > $R/gpurun_out/${tag}_match.log 2>&1 || echo "failed: match"
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${tag}_matchf -o mf -- python3 $R/tools/match_float.py > $R/gpurun_out/${tag}_matchf.log 2>&1 || echo "failed: matchf"
 cd $R
 PRE3_LIB=3pre_amd/lib/libpre3_probe.so timeout -k 10 200 python3 tools/probe_tail.py 30 > gpurun_out/${tag}_probe_tail.txt 2>&1 || echo "failed: probe_tail"

@@ -192,26 +192,12 @@ if by:
         fh.write("\n".join(lines) + "\n")
     print("\n".join(lines[-14:]))
 
-# ---- the matcher (k_match_i8_q)
-try:
-    shutil.copy(find("%s_match" % tag, "m_kernel_stats.csv"), os.path.join(P, "%s_match_kernel_stats.csv" % tag))
-    rows = [r for r in csv.DictReader(open(find("%s_match" % tag, "m_kernel_trace.csv"))) if "k_match_i8_q" in r["Kernel_Name"]]
-    gkey = "Grid_Size" if "Grid_Size" in rows[0] else "Grid_Size_X"
-    gmax = max(int(r[gkey]) for r in rows)                          # the 4096 x 4096 launches (the ragged shapes of the same script have smaller grids)
-    big = sorted((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if int(r[gkey]) == gmax)
-    big = big[:max(1, int(0.9 * len(big)))]                         # drop the slowest tenth (first launches)
-    with open(os.path.join(P, "%s_match_kernel_stats.csv" % tag), "a") as fh:
-        fh.write("# k_match_i8_q at 4096 x 4096 x 128 uint8 (the %d largest launches of tools/match_ab.py child): mean %.2f us, min %.2f us\n" % (len(big), sum(big) / len(big), min(big)))
-    print("matcher 4096^2 launches: mean %.2f us" % (sum(big) / len(big)))
-except FileNotFoundError as e:
-    print("no matcher trace:", e)
-
-# ---- the float / double classes on the matrix cores (k_rank_pack, k_match_rank; tools/match_float.py)
+# ---- the float / double classes on the matrix cores (k_rank_pack, k_rank_tiled, k_rank_tail; tools/match_float.py)
 try:
     shutil.copy(find("%s_matchf" % tag, "mf_kernel_stats.csv"), os.path.join(P, "%s_match_float_kernel_stats.csv" % tag))
     by = {}
     for r in csv.DictReader(open(find("%s_matchf" % tag, "mf_kernel_trace.csv"))):
-        for k_ in ("k_match_rank<double>", "k_match_rank<float>", "k_match_i8_q", "k_match_exact_tiled<double>", "k_match_exact_tiled<float>"):
+        for k_ in ("k_rank_tiled<0>", "k_rank_tiled<1>", "k_rank_tail<double>", "k_rank_tail<float>", "k_match_i8_q", "k_match_exact_tiled<double>", "k_match_exact_tiled<float>"):
             if k_ in r["Kernel_Name"]:
                 by.setdefault(k_, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     with open(os.path.join(P, "%s_match_float_kernel_stats.csv" % tag), "a") as fh:

@@ -1,5 +1,6 @@
-"""k_ransac_score at the headline size (N=500, 400 measurements, 200 hypotheses) with and without the selection stage in its last workgroup:
-run under rocprofv3 --kernel-trace and compare the durations (the un-fused form also shows k_ransac_select's own time)."""
+"""k_ransac_score and k_ransac_select at the headline size (N=500, 400 measurements, 200 hypotheses), through pre3_ransac and through the
+score / select entry points: run under rocprofv3 --kernel-trace and read the two kernels' durations (the form with the selection in the
+scoring launch's last workgroup, which this script once compared them with, is removed: DESIGN.md section 4a)."""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -11,7 +12,7 @@ f.set_x_p_k_k(seq["x0"], seq["P0"])
 s = seq["steps"][0]
 f.ekf_prediction(s["u"]); f.search_IC_matches(); f.set_measurements(s["meas_idx"], s["z"])
 for _ in range(30):
-    f.ransac_hypotheses(s["hyp"], threshold=1.0, early_exit=False)          # fused: scoring + selection in one launch
+    f.ransac_hypotheses(s["hyp"], threshold=1.0, early_exit=False)          # scoring + selection through pre3_ransac
 for _ in range(30):
     f.ransac_score_shard(s["hyp"], 1.0, 0, H)                                # scoring only (full range)
     f.ransac_select(H, 3, False)                                             # selection as its own launch
