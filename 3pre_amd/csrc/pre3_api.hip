@@ -1619,6 +1619,35 @@ int pre3_bench_downdate(pre3_ctx *c, int r, int reps, double *ms_per_launch_out)
     return PRE3_OK;
 }
 
+// ---- test hook (pre3_test_hooks.h; inert without PRE3_TEST_HOOKS=1): P <- P - launches * W'W for the caller's W (r x n, row-major, host), through
+// launch_downdate alone -- no rows, no factorisation, no x-update rider.  The second and later launches find the bf16 planes split, as in pre3_bench_downdate.
+int pre3_test_downdate(pre3_ctx *c, int r, const double *W, int launches)
+{
+    PRE3_CHECK(knob::test_hooks(), PRE3_E_STATE, "pre3_test_downdate: test hooks are off (PRE3_TEST_HOOKS=1 enables them)");
+    PRE3_CHECK(c != nullptr && W != nullptr, PRE3_E_ARG, "pre3_test_downdate: null pointer");
+    PRE3_CHECK(r >= 1 && round_up(r, NB) <= c->rcap && launches >= 1, PRE3_E_ARG, "pre3_test_downdate: bad r/launches");
+    PRE3_CHECK(c->n > 0, PRE3_E_STATE, "pre3_test_downdate: no map/state set");
+    for (size_t i = 0; i < (size_t)r * c->n; ++i) PRE3_CHECK(c->dtype == PRE3_F64 ? std::isfinite(W[i]) : std::isfinite((float)W[i]), PRE3_E_ARG, "pre3_test_downdate: W has a non-finite entry");
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    const int r_pad = round_up(r, NB), n = c->n, ldw = c->ldw;
+    // rows 0 .. r-1 in the context's dtype at row stride ldw; columns n .. ldw-1 and rows r .. r_pad-1 are the zeros launch_downdate relies on
+    std::vector<unsigned char> img((size_t)r_pad * ldw * c->esz, 0);
+    for (int i = 0; i < r; ++i)
+        for (int j = 0; j < n; ++j) {
+            if (c->dtype == PRE3_F64) reinterpret_cast<double *>(img.data())[(size_t)i * ldw + j] = W[(size_t)i * n + j];
+            else reinterpret_cast<float *>(img.data())[(size_t)i * ldw + j] = (float)W[(size_t)i * n + j];
+        }
+    PRE3_TRY(stream_drain(c, __func__));
+    PRE3_HIP(hipMemcpy(c->W, img.data(), img.size(), hipMemcpyHostToDevice));
+    c->hp_all_valid = false; c->g_valid = false;                   // (H*P of the measured rows belongs to the P before this call)
+    bool was = c->kt.enabled; c->kt.enabled = false;
+    int rc = launch_downdate(c, r, c->W);
+    for (int i = 1; i < launches && rc == PRE3_OK; ++i) rc = launch_downdate(c, r, c->W, -1, r_pad);
+    c->kt.enabled = was;
+    PRE3_TRY(rc);
+    return stream_drain(c, __func__);
+}
+
 // ---- device-resident database shard of the sharded matcher (uint8 class; DESIGN.md "multi-GPU", C2)
 int pre3_match_shard_create_cls(pre3_match_shard **out, int device, int cls, int ND, int K1, const void *L1, int K2_local, const void *L2_local, int k2_offset)
 {

@@ -1,5 +1,5 @@
-/* pre3_test_hooks.h -- NOT part of the public interface (include/pre3.h): two hooks for tests/test_gpu_comm.py, exported from libpre3.so but inert
- * unless the environment has PRE3_TEST_HOOKS=1 (they return PRE3_E_STATE otherwise).
+/* pre3_test_hooks.h -- NOT part of the public interface (include/pre3.h): two hooks for tests/test_gpu_comm.py and one for
+ * tests/test_gpu_k9_alone.py, exported from libpre3.so but inert unless the environment has PRE3_TEST_HOOKS=1 (they return PRE3_E_STATE otherwise).
  *
  * pre3_test_stall(ctx, 0) / pre3_match_shard_test_stall(s, 0): park a one-thread kernel on the context's / the shard's stream that spins until it is
  * released (..., 1) -- it also lets go by itself after ~20 s -- so that a test can stand in for a peer that stalls inside a collective.
@@ -7,7 +7,13 @@
  *
  * Reserved mailbox words: word 15 of the context's pinned mailbox (pre3_ctx::mail_host; words 0..9 carry the step's counts and sequence numbers, 16..19 the
  * staging blocks') and word 3 of the shard's result-block mailbox (words 0..2: the match's sequence number, count and missing-slice word) belong to these
- * hooks and to nothing else. */
+ * hooks and to nothing else.
+ *
+ * pre3_test_downdate(ctx, r, W, launches): the down-date P <- P - W'W (K9) on the caller's W and on nothing else, `launches` times in a row.  W is r x n,
+ * row-major, host memory; it is converted to the context's dtype and written to rows 0 .. r-1 of the update workspace (row stride ldw; columns n .. ldw-1
+ * and rows r .. round_up(r, 64)-1 zeroed), then launch_downdate runs without the x-update rider -- the first launch splits the bf16 planes, the later ones
+ * find them, as in pre3_bench_downdate -- and the stream is drained.  P is read back with pre3_get_state.  PRE3_E_ARG (nothing touched) for r < 1,
+ * round_up(r, 64) above the context's row capacity, launches < 1, a null pointer or a non-finite entry of W. */
 #pragma once
 #include "../../include/pre3.h"
 #ifdef __cplusplus
@@ -15,6 +21,7 @@ extern "C" {
 #endif
 PRE3_API int pre3_test_stall(pre3_ctx *ctx, int release);
 PRE3_API int pre3_match_shard_test_stall(pre3_match_shard *s, int release);
+PRE3_API int pre3_test_downdate(pre3_ctx *ctx, int r, const double *W, int launches);
 #ifdef __cplusplus
 }
 #endif

@@ -2068,7 +2068,7 @@ __device__ __forceinline__ void b3_tile(float *__restrict__ P, int ld, const bf1
     // largest terms first; six of the nine partial products
 #define B3_MFMAS(FA, FB) do { B3_MMA(FA, 0, FB, 0); B3_MMA(FA, 0, FB, 1); B3_MMA(FA, 1, FB, 0); B3_MMA(FA, 1, FB, 1); B3_MMA(FA, 0, FB, 2); B3_MMA(FA, 2, FB, 0); } while (0)
     // one stage: FA/FB hold stage s, GA/GB receive stage s+1 (ping-pong over two unrolled stages: no register copies).
-    // LEFT: stages that may still be in flight once stage s+1 has landed; DMA: whether stage s+3 exists.  nst is a multiple of 4.
+    // LEFT: stages that may still be in flight once stage s+1 has landed; DMA: whether stage s+3 exists.  nst is even and >= 4 (launch_downdate).
 #define B3_STAGE(s_, FA, FB, GA, GB, LEFT, DMA) do { \
         const int nxt_ = buf == 2 ? 0 : buf + 1; \
         b3_wait<TM, LEFT>(wave);                                             /* stage s+1 has landed (this wave's granules) */ \

@@ -792,6 +792,13 @@ class EkfFilter:
         """test hook: 0 parks a kernel on the context's stream until test_stall(1) (a peer that stalls inside a collective)"""
         check(lib.pre3_test_stall(self._ctx, int(release)))
 
+    def test_downdate(self, W, launches=1):
+        """test hook (PRE3_TEST_HOOKS=1): P <- P - launches * W'W through the down-date launch alone; W is r x n.  Read P with get_p_k_k()."""
+        W = f64(W)
+        if W.ndim != 2 or W.shape[1] != self.n:
+            raise ValueError("test_downdate: W must be r x %d" % self.n)
+        check(lib.pre3_test_downdate(self._ctx, int(W.shape[0]), dptr(W), int(launches)))
+
     def ransac_export(self, n_draw, support_ptr, mask_ptr):
         check(lib.pre3_ransac_export(self._ctx, int(n_draw), C.c_void_p(support_ptr), C.c_void_p(mask_ptr)))
 
