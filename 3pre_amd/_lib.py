@@ -90,6 +90,7 @@ lib.pre3_icp_frames.argtypes = [_P, _P, _I, _D, _P, _P, _P, _P, _P, _P, _P]
 lib.pre3_icp_pair_seeded.argtypes = [_P, _P, _D, _U, _U, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]
 lib.pre3_icp_nn_bench.argtypes = [_I, _P, _I, _P, _I, _I, _P]
 lib.pre3_test_downdate.argtypes = [_P, _I, _P, _I]            # csrc/pre3_test_hooks.h, not include/pre3.h: not in EXPORTS
+lib.pre3_test_factor_solve.argtypes = [_P, _I, _P, _P, _P, _I, _I, _P, _P]      # (the same)
 
 F64, F32 = 0, 1
 INVDEPTH, CARTESIAN = 0, 1

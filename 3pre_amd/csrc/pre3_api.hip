@@ -1648,6 +1648,58 @@ int pre3_test_downdate(pre3_ctx *c, int r, const double *W, int launches)
     return stream_drain(c, __func__);
 }
 
+// ---- test hook (pre3_test_hooks.h; inert without PRE3_TEST_HOOKS=1): S = L L', L W = [B | nu] for the caller's S (r x r), B (r x n) and nu (r), through
+// launch_chol_solve alone (mode 0: P is not touched) or followed by launch_downdate on the planes the factorisation wrote, as in run_update (mode 1).
+// L_out (r x r, the lower triangle; zeros above) and W_out (round_up(r, 64) x (n + 1), the nu column last) may each be null.
+int pre3_test_factor_solve(pre3_ctx *c, int r, const double *S, const double *B, const double *nu, int mode, int predicted_prior, double *L_out, double *W_out)
+{
+    PRE3_CHECK(knob::test_hooks(), PRE3_E_STATE, "pre3_test_factor_solve: test hooks are off (PRE3_TEST_HOOKS=1 enables them)");
+    PRE3_CHECK(c != nullptr && S != nullptr && B != nullptr && nu != nullptr, PRE3_E_ARG, "pre3_test_factor_solve: null pointer");
+    PRE3_CHECK(r >= 1 && round_up(r, NB) <= c->rcap && (mode == 0 || mode == 1), PRE3_E_ARG, "pre3_test_factor_solve: bad r/mode");
+    PRE3_CHECK(c->n > 0, PRE3_E_STATE, "pre3_test_factor_solve: no map/state set");
+    const bool f64 = c->dtype == PRE3_F64;
+    auto finite = [&](const double *a, size_t cnt) { for (size_t i = 0; i < cnt; ++i) if (!(f64 ? std::isfinite(a[i]) : std::isfinite((float)a[i]))) return false; return true; };
+    PRE3_CHECK(finite(S, (size_t)r * r) && finite(B, (size_t)r * c->n) && finite(nu, (size_t)r), PRE3_E_ARG, "pre3_test_factor_solve: S, B or nu has a non-finite entry");
+    EntryScope scope(c); PRE3_TRY(scope.rc);
+    const int r_pad = round_up(r, NB), n = c->n, ldw = c->ldw;
+    // S at stride r_pad, both triangles, with k_ell_G's padding (identity on the padded diagonal); [B | nu] at stride ldw, nu in column ld, zeros elsewhere
+    std::vector<unsigned char> simg((size_t)r_pad * r_pad * c->esz, 0), wimg((size_t)r_pad * ldw * c->esz, 0);
+    auto put = [&](std::vector<unsigned char> &img, size_t at, double v) { if (f64) reinterpret_cast<double *>(img.data())[at] = v; else reinterpret_cast<float *>(img.data())[at] = (float)v; };
+    auto get = [&](const std::vector<unsigned char> &img, size_t at) { return f64 ? reinterpret_cast<const double *>(img.data())[at] : (double)reinterpret_cast<const float *>(img.data())[at]; };
+    for (int i = 0; i < r_pad; ++i) {
+        if (i >= r) { put(simg, (size_t)i * r_pad + i, 1.0); continue; }
+        for (int j = 0; j < r; ++j) put(simg, (size_t)i * r_pad + j, S[(size_t)i * r + j]);
+        for (int j = 0; j < n; ++j) put(wimg, (size_t)i * ldw + j, B[(size_t)i * n + j]);
+        put(wimg, (size_t)i * ldw + c->ld, nu[i]);
+    }
+    PRE3_TRY(stream_drain(c, __func__));
+    PRE3_HIP(hipMemcpy(c->Smat, simg.data(), simg.size(), hipMemcpyHostToDevice));
+    PRE3_HIP(hipMemcpy(c->W, wimg.data(), wimg.size(), hipMemcpyHostToDevice));
+    c->hp_all_valid = false; c->g_valid = false;                   // (H*P and H*P*H' of the measured rows are not what W and Smat hold now)
+    const bool kt_was = c->kt.enabled, ov_was = c->k9_overlap;
+    c->kt.enabled = false;
+    if (mode == 0) c->k9_overlap = false;                          // no down-date consumers in the persistent launch: P stays as it is
+    int rc = chol_solve_for_test(c, r_pad, predicted_prior != 0, r);
+    c->k9_overlap = ov_was;
+    if (rc == PRE3_OK && mode == 1) rc = launch_downdate(c, r, c->W, -1);
+    c->kt.enabled = kt_was;
+    PRE3_TRY(rc);
+    PRE3_TRY(fetch_stats(c));                                      // drains; PRE3_E_NUMERIC if a pivot was not positive
+    if (L_out != nullptr) {
+        PRE3_HIP(hipMemcpy(simg.data(), c->Smat, simg.size(), hipMemcpyDeviceToHost));
+        for (int i = 0; i < r; ++i)
+            for (int j = 0; j < r; ++j) L_out[(size_t)i * r + j] = j <= i ? get(simg, (size_t)i * r_pad + j) : 0.0;
+    }
+    if (W_out != nullptr) {
+        PRE3_HIP(hipMemcpy(wimg.data(), c->W, wimg.size(), hipMemcpyDeviceToHost));
+        for (int i = 0; i < r_pad; ++i) {
+            for (int j = 0; j < n; ++j) W_out[(size_t)i * (n + 1) + j] = get(wimg, (size_t)i * ldw + j);
+            W_out[(size_t)i * (n + 1) + n] = get(wimg, (size_t)i * ldw + c->ld);
+        }
+    }
+    return PRE3_OK;
+}
+
 // ---- device-resident database shard of the sharded matcher (uint8 class; DESIGN.md "multi-GPU", C2)
 int pre3_match_shard_create_cls(pre3_match_shard **out, int device, int cls, int ND, int K1, const void *L1, int K2_local, const void *L2_local, int k2_offset)
 {

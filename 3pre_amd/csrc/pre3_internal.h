@@ -470,6 +470,7 @@ int run_update(pre3_ctx *c, int which_prior, int r, bool dense_R, void *Kt_out_d
                bool hp_built = false /* rows and W = H*P are in place (launch_ell_HP_build_sel), S is not */);
 int launch_ell_HP_build_sel(pre3_ctx *c, int nsel, const int32_t *sel_dev /* nullable: the first nsel measurements */, void *dst);
 int launch_chol_first_spec(pre3_ctx *c, int nsel_max);
+int chol_solve_for_test(pre3_ctx *c, int r_pad, bool predicted_prior, int r);      /* pre3_test_factor_solve's way to the (static) launch_chol_solve: S and [B | nu] are in place */
 struct InboxRide;
 int launch_ell_HP_build(pre3_ctx *c, void *dst, const int32_t *need = nullptr, int need_tag = 0 /* sharded RANSAC: only the measurements with need[s] == need_tag */,
                         const InboxRide *ib = nullptr /* a pull from the pinned inbox that rides in the launch */);

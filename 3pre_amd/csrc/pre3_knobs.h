@@ -23,7 +23,7 @@
     X(fuse_jn,           "PRE3_FUSE_JN",           1,  once,    "the rows/cols 3..6 <- Jn pass of a HI update completed at the start of a step rides in that step's prediction launch (0: k_jnorm_P as its own launch; same bits)") \
     X(scan_trace,        "PRE3_SCAN_TRACE",        0,  once,    "pre3_set_scan: host-side phase clock on stderr (event wait, copy + bounds check, positions, enqueue)") \
     X(step_trace,        "PRE3_STEP_TRACE",        0,  present, "host-side stage clock (debug): where the host spends a step, on stderr every 100 steps") \
-    X(test_hooks,        "PRE3_TEST_HOOKS",        0,  is1,     "arms pre3_test_stall / pre3_match_shard_test_stall (tests of the communicator's deadline) and pre3_test_downdate (K9 alone on the caller's W); not a performance switch") \
+    X(test_hooks,        "PRE3_TEST_HOOKS",        0,  is1,     "arms pre3_test_stall / pre3_match_shard_test_stall (tests of the communicator's deadline) pre3_test_downdate (K9 alone on the caller's W) and pre3_test_factor_solve (factorisation and solve alone on the caller's S, B, nu); not a performance switch") \
     X(rccl_lib,          "PRE3_RCCL_LIB",          nullptr, text, "path of the RCCL library pre3_comm_* binds (default: librccl.so.1 as already loaded, else from the loader path, else /opt/rocm/lib)") \
     /* ---- the step's stage order (pre3_step.hip) */ \
     X(inline_g,          "PRE3_INLINE_G",          1,  once,    "RANSAC round: no H*P*H' launch (6.6 us in front of the scoring); the scorer and the LI gather compute their entries with k_ell_G's sum (0: k_ell_G / k_ell_G_hyp as launches; same bits)") \

@@ -2429,6 +2429,9 @@ static int launch_chol_solve(pre3_ctx *c, int r_pad, bool first_done = false, bo
     }
 }
 
+// pre3_test_factor_solve (pre3_test_hooks.h): the factorisation and solve exactly as run_update asks for them, without the x-update
+int chol_solve_for_test(pre3_ctx *c, int r_pad, bool predicted_prior, int r) { return launch_chol_solve(c, r_pad, false, predicted_prior, r, -1); }
+
 // the step asks for the rescue's projection as a rider (req) and no launch of this call has taken it yet (out)
 static bool rescue_ride_open(const pre3_ctx *c) { return c->req.ride_rescue_projection && !c->out.rescue_projected && !c->out.proj_with_jnorm && c->N > 0; }
 

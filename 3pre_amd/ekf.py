@@ -799,6 +799,18 @@ class EkfFilter:
             raise ValueError("test_downdate: W must be r x %d" % self.n)
         check(lib.pre3_test_downdate(self._ctx, int(W.shape[0]), dptr(W), int(launches)))
 
+    def test_factor_solve(self, S, B, nu, mode=0, predicted_prior=False):
+        """test hook (PRE3_TEST_HOOKS=1): S = L L', L W = [B | nu] through the factorisation's launches alone (mode 0: P untouched) or with the
+        down-date behind them as in an update (mode 1: read P with get_p_k_k()).  S is r x r, B r x n, nu r.  Returns (L, W): L r x r, lower triangle;
+        W round_up(r, 64) x (n + 1), the nu column last."""
+        S, B, nu = f64(S), f64(B), f64(nu)
+        r = S.shape[0]
+        if S.ndim != 2 or S.shape != (r, r) or B.shape != (r, self.n) or nu.shape != (r,):
+            raise ValueError("test_factor_solve: S must be r x r, B r x %d, nu r" % self.n)
+        L, W = np.zeros((r, r)), np.zeros(((r + 63) // 64 * 64, self.n + 1))
+        check(lib.pre3_test_factor_solve(self._ctx, int(r), dptr(S), dptr(B), dptr(nu), int(mode), int(bool(predicted_prior)), dptr(L), dptr(W)))
+        return L, W
+
     def ransac_export(self, n_draw, support_ptr, mask_ptr):
         check(lib.pre3_ransac_export(self._ctx, int(n_draw), C.c_void_p(support_ptr), C.c_void_p(mask_ptr)))
 
