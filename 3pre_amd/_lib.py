@@ -70,6 +70,10 @@ lib.pre3_sr_frame_sift_refined.argtypes = [_P, _P, _P]
 lib.pre3_sr_text_limits.argtypes = [_P, _P]
 lib.pre3_sr_text_parse.argtypes = [_I, _P, C.c_size_t, _P, C.c_size_t, _P]
 lib.pre3_sr_frame_load_text.argtypes = [_P, _I, _P, C.c_size_t, _P]
+lib.pre3_sr_frame_set_compensation.argtypes = [_P, _I, _D]
+lib.pre3_sr_frame_get_compensation.argtypes = [_P, _P, _P]
+lib.pre3_sr_frame_bad_pixels.argtypes = [_P, _P, _P]
+lib.pre3_sr_medfilt3.argtypes = [_I, _I, _I, _P, _I, _P]
 lib.pre3_set_image.argtypes = [_P, _I, _I, _P]
 lib.pre3_get_image.argtypes = [_P, _I, _I, _P]
 lib.pre3_set_image_frame.argtypes = [_P, _P]
@@ -166,6 +170,7 @@ EXPORTS = [
     "pre3_set_process_noise", "pre3_get_process_noise", "pre3_vo_cov", "pre3_vo_pair_cov_seeded", "pre3_predict_pair_cov_seeded",
     "pre3_sift_plan_get", "pre3_sr_frame_sift", "pre3_sr_frame_gate", "pre3_sr_frame_sift_level", "pre3_sr_frame_sift_refined",
     "pre3_sr_text_limits", "pre3_sr_text_parse", "pre3_sr_frame_load_text",
+    "pre3_sr_frame_set_compensation", "pre3_sr_frame_get_compensation", "pre3_sr_frame_bad_pixels", "pre3_sr_medfilt3",
     "pre3_set_image", "pre3_get_image", "pre3_set_image_frame", "pre3_set_patches", "pre3_get_patches", "pre3_patch_cut", "pre3_predict_patches",
     "pre3_patch_search", "pre3_patch_timing",
     "pre3_fast_detect", "pre3_fast_timing", "pre3_init_feature_fast", "pre3_init_feature_fast_seeded", "pre3_init_features_fast_all",

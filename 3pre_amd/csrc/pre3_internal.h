@@ -423,6 +423,7 @@ struct SrFrameView {
     int device, rows, cols, mode, has_conf;
     const double *x, *y, *z, *img, *conf, *maxima;
     hipStream_t stream;
+    int comp_form;                  // the compensation the frame was conditioned with (0 none, 1 bad pixels, 2 the image's median): x .. img hold its result
 };
 int sr_frame_view(pre3_sr_frame *f, SrFrameView *v);      /* PRE3_E_STATE before the first load */
 // the handle's last keypoint result (pre3_sr_frame_keypoints), which stays in its keypoint block: the kept frames [n_kept][ldf] and descriptors

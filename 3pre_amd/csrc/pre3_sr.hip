@@ -3,11 +3,13 @@
 //   code_from_dr_ye/read_sr4000_data_dr_ye.m:8,11-21,42,70,88-90                       (mode 1: sigma = 1, replicated border)
 //   SIFT_extract_save.m:71-88 over inittialize_depth_my_version.m:16,40-45,74-92       (gate 0: the depth gate, XYZ_DATA, rho)
 //   code_from_dr_ye/confidence_filtering.m:1-13                                        (gate 1)
+//   aux_code/compensate_badpixel_soonhac.m:5-14, code_from_dr_ye/read_image_sr4000_dr_ye.m:21-24   (the compensation in front of the Gaussian, section 32)
 // Three launches, all fp64, on the handle's own stream:
-//   k_sr_maxima     one workgroup: imax (the largest unsaturated amplitude) and cmax (max(confidence_map(:)), NaNs skipped) -- xor butterfly per wave,
-//                   the waves combined through LDS.
+//   k_sr_maxima     one workgroup: imax (the largest unsaturated amplitude), cmax (max(confidence_map(:)), NaNs skipped) and, under form 1, the number
+//                   of pixels with conf < cutoff -- xor butterfly per wave, the waves combined through LDS.
 //   k_sr_condition  16 x 16 tiles with a one-pixel halo in LDS: the filtered x, y, z and the filtered uint8 image.  Halo pixels recompute the
-//                   normalisation from the raw amplitude; the image exists only filtered.
+//                   normalisation from the raw amplitude; the image exists only filtered.  The compensated instantiations stage a two-pixel halo and
+//                   fill the same tiles with the compensated values first.
 //   k_sr_keypoints  a workgroup owns 256 consecutive keypoints; its base offset is the predicate of every earlier keypoint re-evaluated by itself
 //                   (ballot + popcount), ranks inside it are a ballot prefix per wave plus the wave sums through LDS; then one wave per kept keypoint
 //                   copies its frame entries and descriptor to slot `rank`.
@@ -25,6 +27,8 @@ namespace {
 
 constexpr int ST = 16;              // tile edge of k_sr_condition
 constexpr int SH = ST + 2;          // ... with its halo
+constexpr int SW = ST + 4;          // ... with the two-pixel halo of the compensated forms: a Gaussian tap one pixel outside the tile needs the 3 x 3 around it
+constexpr int MF = 256;             // threads of k_sr_medfilt3
 constexpr int MB = 1024;            // threads of k_sr_maxima's one workgroup
 constexpr int KB = 256;             // keypoints (and threads) per workgroup of k_sr_keypoints
 constexpr int KW = KB / 64;
@@ -33,48 +37,113 @@ static_assert(PRE3_SR_MAX_KEYPOINTS % KB == 0 && PRE3_SR_MAX_KEYPOINTS / KB == 3
 struct SrWeights { double w[9]; };
 
 __global__ __launch_bounds__(MB) void k_sr_maxima(int npix, const double *__restrict__ amp, const double *__restrict__ conf /* null: none */,
-                                                  double *__restrict__ out /* imax, cmax */)
+                                                  int count_bad, double cutoff, double *__restrict__ out /* imax, cmax, n_bad */)
 {
     __shared__ double s_a[MB / 64], s_c[MB / 64];
+    __shared__ int s_n[MB / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double a = 0.0, c = NAN;
+    int n = 0;                                               // pixels with conf < cutoff (form 1 only): at most npix <= 2^26
     for (int i = tid; i < npix; i += MB) {
         const double v = amp[i];
         if (v <= SR_SATURATED && v > a) a = v;               // read_image_sr4000.m:12-17: saturated pixels count as 0
-        if (conf != nullptr) c = sr_nanmax(c, conf[i]);
+        if (conf != nullptr) { const double cv = conf[i]; c = sr_nanmax(c, cv); n += (count_bad != 0 && sr_is_bad(true, cv, cutoff)) ? 1 : 0; }
     }
     for (int o = 32; o > 0; o >>= 1) {
         const double a2 = __shfl_xor(a, o, 64), c2 = __shfl_xor(c, o, 64);
         a = a2 > a ? a2 : a;
         c = sr_nanmax(c, c2);
+        n += __shfl_xor(n, o, 64);
     }
-    if (lane == 0) { s_a[wave] = a; s_c[wave] = c; }
+    if (lane == 0) { s_a[wave] = a; s_c[wave] = c; s_n[wave] = n; }
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < MB / 64; ++w) { a = s_a[w] > a ? s_a[w] : a; c = sr_nanmax(c, s_c[w]); }
-        out[0] = a; out[1] = c;
+        for (int w = 1; w < MB / 64; ++w) { a = s_a[w] > a ? s_a[w] : a; c = sr_nanmax(c, s_c[w]); n += s_n[w]; }
+        out[0] = a; out[1] = c; out[2] = (double)n;
     }
 }
 
+// the 3 x 3 median around (lr, lc) of a staged SW x SW tile [lc * SW + lr]; 1 <= lr, lc <= SW - 2
+__device__ inline double tile_median9(const double *s, int lr, int lc)
+{
+    double p[9];
+#pragma unroll
+    for (int dj = 0; dj < 3; ++dj)
+#pragma unroll
+        for (int di = 0; di < 3; ++di) p[3 * dj + di] = s[(lc + dj - 1) * SW + lr + di - 1];
+    return sr_median9(p);
+}
+
+// COMP: the compensation in front of the Gaussian.  SR_COMP_NONE is the launch as it was before there was one.
+//   SR_COMP_BADPIXEL      x, y, z, U and the confidence staged with a TWO-pixel halo (SW x SW), every pixel outside the image read at the clamped
+//                         coordinates -- one step out, that is medfilt2's 'symmetric' mirror; two steps out, the value is never read.  Then the
+//                         SH x SH tile the nine-tap sums read: at a pixel inside the image bad ? median9 of the staged window : the staged pixel;
+//                         outside it 0.0 (mode 0) or the same expression at the clamped coordinates (mode 1).
+//   SR_COMP_IMAGE_MEDIAN  only U is staged SW x SW, with 0.0 outside the image (medfilt2's default padding); its SH x SH tile is the median at every
+//                         pixel, outside the image as above; x, y, z go straight into their SH x SH tiles as in SR_COMP_NONE.
+// Index arithmetic: SH-tile (lr, lc) is the pixel (r0 + lr - 1, c0 + lc - 1); clamped into the image it lies in [r0 - 1, r0 + ST] x [c0 - 1, c0 + ST]
+// still (the tile holds at least one image row and column), i.e. at SW-tile (cr - r0 + 2, cc - c0 + 2) in [1, SW - 2]: its window stays in [0, SW - 1].
+template <int COMP>
 __global__ __launch_bounds__(ST * ST) void k_sr_condition(int rows, int cols, int mode, SrWeights W, const double *__restrict__ raw,
-                                                          const double *__restrict__ maxima, double *__restrict__ filt)
+                                                          const double *__restrict__ maxima, double *__restrict__ filt, int has_conf, double cutoff)
 {
     __shared__ double s_p[4][SH * SH];                       // x, y, z, uint8 image; [lc * SH + lr]
     const size_t npix = (size_t)rows * cols;
     const double *Z = raw, *X = raw + npix, *Y = raw + 2 * npix, *A = raw + 3 * npix;
     const int tid = threadIdx.x, r0 = blockIdx.x * ST, c0 = blockIdx.y * ST;
     const double imax = maxima[0];
-    for (int i = tid; i < SH * SH; i += ST * ST) {
-        const int lr = i % SH, lc = i / SH;
-        int gr = r0 + lr - 1, gc = c0 + lc - 1;
-        const bool inside = gr >= 0 && gr < rows && gc >= 0 && gc < cols;
-        double x = 0.0, y = 0.0, z = 0.0, u = 0.0;           // mode 0: imfilter(.., 'same') pads with zeros (the uint8 image too)
-        if (inside || mode == 1) {                           // mode 1: 'replicate' reads the nearest edge pixel
+    if constexpr (COMP == SR_COMP_NONE) {
+        for (int i = tid; i < SH * SH; i += ST * ST) {
+            const int lr = i % SH, lc = i / SH;
+            int gr = r0 + lr - 1, gc = c0 + lc - 1;
+            const bool inside = gr >= 0 && gr < rows && gc >= 0 && gc < cols;
+            double x = 0.0, y = 0.0, z = 0.0, u = 0.0;           // mode 0: imfilter(.., 'same') pads with zeros (the uint8 image too)
+            if (inside || mode == 1) {                           // mode 1: 'replicate' reads the nearest edge pixel
+                gr = min(max(gr, 0), rows - 1); gc = min(max(gc, 0), cols - 1);
+                const size_t g = (size_t)gc * rows + gr;
+                x = X[g]; y = Y[g]; z = Z[g]; u = sr_norm_pixel(A[g], imax);
+            }
+            s_p[0][i] = x; s_p[1][i] = y; s_p[2][i] = z; s_p[3][i] = u;
+        }
+    } else {
+        constexpr int NW = COMP == SR_COMP_BADPIXEL ? 5 : 1;     // staged with the two-pixel halo: x, y, z, U, confidence -- or U alone
+        __shared__ double s_w[NW][SW * SW];                      // [lc * SW + lr]
+        const double *Cf = raw + 4 * npix;
+        for (int i = tid; i < SW * SW; i += ST * ST) {
+            const int lr = i % SW, lc = i / SW;
+            int gr = r0 + lr - 2, gc = c0 + lc - 2;
+            const bool inside = gr >= 0 && gr < rows && gc >= 0 && gc < cols;
             gr = min(max(gr, 0), rows - 1); gc = min(max(gc, 0), cols - 1);
             const size_t g = (size_t)gc * rows + gr;
-            x = X[g]; y = Y[g]; z = Z[g]; u = sr_norm_pixel(A[g], imax);
+            if constexpr (COMP == SR_COMP_BADPIXEL) {
+                s_w[0][i] = X[g]; s_w[1][i] = Y[g]; s_w[2][i] = Z[g]; s_w[3][i] = sr_norm_pixel(A[g], imax);
+                s_w[4][i] = has_conf ? Cf[g] : 0.0;
+            } else {
+                s_w[0][i] = inside ? sr_norm_pixel(A[g], imax) : 0.0;
+            }
         }
-        s_p[0][i] = x; s_p[1][i] = y; s_p[2][i] = z; s_p[3][i] = u;
+        __syncthreads();
+        for (int i = tid; i < SH * SH; i += ST * ST) {
+            const int lr = i % SH, lc = i / SH;
+            const int gr = r0 + lr - 1, gc = c0 + lc - 1;
+            const bool inside = gr >= 0 && gr < rows && gc >= 0 && gc < cols;
+            double x = 0.0, y = 0.0, z = 0.0, u = 0.0;           // mode 0: a tap outside the image is a literal 0.0, compensation or not
+            if (inside || mode == 1) {                           // mode 1: the compensated edge pixel
+                const int cr = min(max(gr, 0), rows - 1), cc = min(max(gc, 0), cols - 1);
+                const int wr = cr - r0 + 2, wc = cc - c0 + 2, j = wc * SW + wr;
+                if constexpr (COMP == SR_COMP_BADPIXEL) {
+                    const bool bad = sr_is_bad(has_conf != 0, s_w[4][j], cutoff);
+                    x = bad ? tile_median9(s_w[0], wr, wc) : s_w[0][j];
+                    y = bad ? tile_median9(s_w[1], wr, wc) : s_w[1][j];
+                    z = bad ? tile_median9(s_w[2], wr, wc) : s_w[2][j];
+                    u = bad ? tile_median9(s_w[3], wr, wc) : s_w[3][j];
+                } else {
+                    const size_t g = (size_t)cc * rows + cr;
+                    x = X[g]; y = Y[g]; z = Z[g]; u = tile_median9(s_w[0], wr, wc);
+                }
+            }
+            s_p[0][i] = x; s_p[1][i] = y; s_p[2][i] = z; s_p[3][i] = u;
+        }
     }
     __syncthreads();
     const int tr = tid % ST, tc = tid / ST, r = r0 + tr, c = c0 + tc;
@@ -162,6 +231,14 @@ __global__ __launch_bounds__(KB) void k_sr_keypoints(KpArgs a)
     }
 }
 
+// medfilt2(A, [3 3]) on a whole plane, one pixel per thread straight from global memory (pre3_sr_medfilt3): the window and the network are pre3_sr.h's
+__global__ __launch_bounds__(MF) void k_sr_medfilt3(int rows, int cols, int padding, const double *__restrict__ A, double *__restrict__ out)
+{
+    const size_t g = (size_t)blockIdx.x * MF + threadIdx.x;
+    if (g >= (size_t)rows * cols) return;
+    out[g] = sr_medfilt_pixel(A, rows, cols, (int)(g % rows), (int)(g / rows), padding);
+}
+
 // Device memory of the handle, zeroed ON THE HANDLE'S STREAM: the stream does not synchronise with the null stream (hipStreamNonBlocking), so a
 // hipMemset there -- asynchronous to the host -- could land behind the first transfer queued into the block.
 static int sr_dmalloc(pre3_sr_frame *f, void **p, size_t bytes)
@@ -209,15 +286,20 @@ int sr_frame_kp_reserve(pre3_sr_frame *f, size_t total)
 int sr_condition_run(pre3_sr_frame *f, int mode, bool has_conf)
 {
     const size_t npix = (size_t)f->rows * f->cols;
+    const int form = f->comp_form;                            // the setting as it stands when the load is queued (pre3_sr_frame_set_compensation)
+    const double cutoff = f->comp_cutoff;
     hipLaunchKernelGGL(k_sr_maxima, dim3(1), dim3(MB), 0, f->stream, (int)npix, (const double *)(f->raw + 3 * npix),
-                       has_conf ? (const double *)(f->raw + 4 * npix) : (const double *)nullptr, f->maxima);
+                       has_conf ? (const double *)(f->raw + 4 * npix) : (const double *)nullptr, form == SR_COMP_BADPIXEL ? 1 : 0, cutoff, f->maxima);
     PRE3_HIP(hipGetLastError());
     SrWeights W;
     sr_gauss3(mode == 0 ? 2.0 : 1.0, W.w);
-    hipLaunchKernelGGL(k_sr_condition, dim3(ceil_div(f->rows, ST), ceil_div(f->cols, ST)), dim3(ST * ST), 0, f->stream, f->rows, f->cols, mode, W,
-                       (const double *)f->raw, (const double *)f->maxima, f->filt);
+    const dim3 grid(ceil_div(f->rows, ST), ceil_div(f->cols, ST));
+    auto *kern = form == SR_COMP_BADPIXEL ? k_sr_condition<SR_COMP_BADPIXEL>
+                                          : (form == SR_COMP_IMAGE_MEDIAN ? k_sr_condition<SR_COMP_IMAGE_MEDIAN> : k_sr_condition<SR_COMP_NONE>);
+    hipLaunchKernelGGL(kern, grid, dim3(ST * ST), 0, f->stream, f->rows, f->cols, mode, W, (const double *)f->raw, (const double *)f->maxima, f->filt,
+                       has_conf ? 1 : 0, cutoff);
     PRE3_HIP(hipGetLastError());
-    f->mode = mode; f->has_conf = has_conf ? 1 : 0; f->loaded = 1;
+    f->mode = mode; f->has_conf = has_conf ? 1 : 0; f->loaded = 1; f->frame_form = form;
     return PRE3_OK;
 }
 
@@ -251,7 +333,7 @@ int sr_frame_view(pre3_sr_frame *f, SrFrameView *v)
     v->device = f->device; v->rows = f->rows; v->cols = f->cols; v->mode = f->mode; v->has_conf = f->has_conf;
     v->x = f->filt; v->y = f->filt + npix; v->z = f->filt + 2 * npix; v->img = f->filt + 3 * npix;
     v->conf = f->has_conf ? f->raw + 4 * npix : nullptr;
-    v->maxima = f->maxima; v->stream = f->stream;
+    v->maxima = f->maxima; v->stream = f->stream; v->comp_form = f->frame_form;
     return PRE3_OK;
 }
 
@@ -367,7 +449,7 @@ static int sr_create_buffers(pre3_sr_frame *f)
     PRE3_HIP(hipEventCreateWithFlags(&f->pair_ev, hipEventDisableTiming));
     PRE3_TRY(sr_dmalloc(f, (void **)&f->raw, sizeof(double) * 5 * npix));
     PRE3_TRY(sr_dmalloc(f, (void **)&f->filt, sizeof(double) * 4 * npix));
-    PRE3_TRY(sr_dmalloc(f, (void **)&f->maxima, sizeof(double) * 2));
+    PRE3_TRY(sr_dmalloc(f, (void **)&f->maxima, sizeof(double) * 4));     // imax, cmax, n_bad (and a spare)
     PRE3_HIP(hipHostMalloc((void **)&f->pinned_n, 64, hipHostMallocDefault));
     return sr_grow_stage(f, sizeof(double) * 5 * npix);
 }
@@ -422,6 +504,56 @@ int pre3_sr_frame_get(pre3_sr_frame *f, double *x, double *y, double *z, double 
     PRE3_HIP(hipStreamSynchronize(f->stream));
     if (imax) *imax = mx[0];
     if (cmax) *cmax = mx[1];
+    return PRE3_OK;
+}
+
+int pre3_sr_frame_set_compensation(pre3_sr_frame *f, int form, double cutoff)
+{
+    PRE3_CHECK(f != nullptr, PRE3_E_ARG, "pre3_sr_frame_set_compensation: null handle");
+    PRE3_CHECK(form >= SR_COMP_NONE && form <= SR_COMP_IMAGE_MEDIAN, PRE3_E_ARG,
+               "pre3_sr_frame_set_compensation: form %d is neither 0 (none), 1 (bad pixels) nor 2 (the image's median)", form);
+    PRE3_CHECK(form != SR_COMP_BADPIXEL || std::isfinite(cutoff), PRE3_E_ARG, "pre3_sr_frame_set_compensation: the cut-off of form 1 must be finite");
+    f->comp_form = form; f->comp_cutoff = cutoff;
+    return PRE3_OK;
+}
+
+int pre3_sr_frame_get_compensation(pre3_sr_frame *f, int32_t *form, double *cutoff)
+{
+    PRE3_CHECK(f != nullptr, PRE3_E_ARG, "pre3_sr_frame_get_compensation: null handle");
+    if (form) *form = f->comp_form;
+    if (cutoff) *cutoff = f->comp_cutoff;
+    return PRE3_OK;
+}
+
+int pre3_sr_frame_bad_pixels(pre3_sr_frame *f, int32_t *form_of_frame, int32_t *n_bad)
+{
+    PRE3_CHECK(f != nullptr, PRE3_E_ARG, "pre3_sr_frame_bad_pixels: null handle");
+    PRE3_CHECK(f->loaded, PRE3_E_STATE, "pre3_sr_frame_bad_pixels: no frame has been loaded");
+    PRE3_TRY(select_device("pre3_sr_frame_bad_pixels", f->device));
+    double n = 0.0;
+    PRE3_HIP(hipMemcpyAsync(&n, f->maxima + 2, sizeof n, hipMemcpyDeviceToHost, f->stream));
+    PRE3_HIP(hipStreamSynchronize(f->stream));
+    if (form_of_frame) *form_of_frame = f->frame_form;
+    if (n_bad) *n_bad = (int32_t)n;
+    return PRE3_OK;
+}
+
+int pre3_sr_medfilt3(int device, int rows, int cols, const double *A, int padding, double *out)
+{
+    const char *who = "pre3_sr_medfilt3";
+    PRE3_CHECK(A != nullptr && out != nullptr, PRE3_E_ARG, "%s: null argument", who);
+    PRE3_CHECK(padding == SR_PAD_ZEROS || padding == SR_PAD_SYMMETRIC, PRE3_E_ARG, "%s: padding %d is neither 0 (zeros) nor 1 (symmetric)", who, padding);
+    PRE3_CHECK(rows >= 1 && cols >= 1 && (long long)rows * cols <= PRE3_SR_MEDFILT_MAX_PIXELS, PRE3_E_ARG, "%s: a %d x %d plane", who, rows, cols);
+    PRE3_TRY(select_device(who, device));
+    const size_t npix = (size_t)rows * cols, nb = sizeof(double) * npix;
+    Scratch d;
+    PRE3_TRY(d.alloc(2 * nb));
+    double *dA = d.as<double>(), *dO = dA + npix;
+    PRE3_HIP(hipMemcpy(dA, A, nb, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_sr_medfilt3, dim3((unsigned)((npix + MF - 1) / MF)), dim3(MF), 0, nullptr, rows, cols, padding, (const double *)dA, dO);
+    PRE3_HIP(hipGetLastError());
+    PRE3_HIP(hipStreamSynchronize(nullptr));
+    PRE3_HIP(hipMemcpy(out, dO, nb, hipMemcpyDeviceToHost));
     return PRE3_OK;
 }
 

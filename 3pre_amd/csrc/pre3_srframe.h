@@ -10,10 +10,13 @@ void sift_work_free(SiftWork *w);                            // pre3_sift.hip
 struct pre3_sr_frame {
     int device = 0, rows = 0, cols = 0;
     int loaded = 0, mode = 0, has_conf = 0;
+    // the compensation: the setting the next load takes, and the form the resident frame was conditioned with
+    int comp_form = 0, frame_form = 0;
+    double comp_cutoff = 1.0;
     hipStream_t stream = nullptr;
     double *raw = nullptr;          // [5][npix]: z, x, y, amplitude, confidence -- as uploaded
     double *filt = nullptr;         // [4][npix]: x, y, z, image
-    double *maxima = nullptr;       // imax, cmax
+    double *maxima = nullptr;       // imax, cmax, n_bad (pixels with conf < cutoff, counted under form 1 only)
     void *stage = nullptr;          // pinned: the five planes of a load, or the keypoints of a call
     size_t stage_bytes = 0;
     void *kp = nullptr;             // device: the keypoint stage's input and output block

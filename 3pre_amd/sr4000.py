@@ -16,6 +16,10 @@ readers and keypoint filters over the C ABI.
 
     read_xyz_sr4000.m:2-3,25-42 (load of d1_%04d.dat)        -> loadtxt_device, SrFrame.load_text, parse="device" (the text parsed on the device, section 26)
 
+    aux_code/compensate_badpixel_soonhac.m:5-14              -> SrFrame.set_compensation(COMP_BADPIXEL, cutoff), compensate_badpixel_soonhac (section 32)
+    code_from_dr_ye/read_image_sr4000_dr_ye.m:21-24          -> SrFrame.set_compensation(COMP_IMAGE_MEDIAN), read_image_sr4000_dr_ye
+    medfilt2(A, [3 3]) / medfilt2(A, [3 3], 'symmetric')     -> medfilt2
+
 All compute runs in libpre3.so on the GPU; this module reads the file's bytes -- parsed on the host (numpy.loadtxt, the default) or handed to the device
 as they are (parse="device") -- and marshals numpy arrays.
 """
@@ -30,6 +34,8 @@ MAX_KEYPOINTS = 8192                      # PRE3_SR_MAX_KEYPOINTS
 MODE_XYZ, MODE_DR_YE = 0, 1               # read_xyz_sr4000.m / read_image_sr4000.m; read_sr4000_data_dr_ye.m
 GATE_DEPTH, GATE_CONFIDENCE = 0, 1        # inittialize_depth_my_version.m:40,74; confidence_filtering.m:8
 SIFT_LEVELS, SIFT_MAX_TAPS = 6, 32        # PRE3_SIFT_LEVELS, PRE3_SIFT_MAX_TAPS
+COMP_NONE, COMP_BADPIXEL, COMP_IMAGE_MEDIAN = 0, 1, 2      # PRE3_SR_COMP_*: nothing; compensate_badpixel_soonhac.m; read_image_sr4000_dr_ye.m:21-24
+PADDING = {"zeros": 0, "symmetric": 1}    # medfilt2's default, and its 'symmetric'
 
 
 def gauss3(sigma):
@@ -37,6 +43,32 @@ def gauss3(sigma):
     w = np.zeros(9)
     check(lib.pre3_sr_gauss3(float(sigma), dptr(w)))
     return w.reshape(3, 3).T.copy()
+
+
+def medfilt2(A, padding="zeros", device=0):
+    """medfilt2(A, [3 3]) (padding="zeros", MATLAB's default) or medfilt2(A, [3 3], 'symmetric') on the device (pre3_sr_medfilt3): the fifth smallest of
+    each 3 x 3 window; a NaN in the window makes the pixel NaN.  Returns doubles of A's shape (uint8 values stay uint8 values: a median selects)."""
+    if padding not in PADDING:
+        raise ValueError("padding must be 'zeros' or 'symmetric', not %r" % (padding,))
+    A = np.asfortranarray(f64(A))
+    if A.ndim != 2:
+        raise Pre3Error(-1, "medfilt2: A must be a matrix")
+    out = np.zeros(A.shape, order="F")
+    check(lib.pre3_sr_medfilt3(int(device), A.shape[0], A.shape[1], dptr(A), PADDING[padding], dptr(out)))
+    return out
+
+
+def compensate_badpixel_soonhac(img, x, y, z, c, confidence_cut_off, device=0):
+    """[img, x, y, z, c] = compensate_badpixel_soonhac(img, x, y, z, c, confidence_cut_off) (aux_code/compensate_badpixel_soonhac.m:5-14): four symmetric
+    medians on the device, taken on the planes as given, selected where c < confidence_cut_off.  img keeps its dtype."""
+    e_index = f64(c) < float(confidence_cut_off)
+    out = []
+    for p in (img, x, y, z):
+        p = np.array(p)
+        q = p.copy()
+        q[e_index] = medfilt2(p, "symmetric", device)[e_index].astype(p.dtype)
+        out.append(q)
+    return out[0], out[1], out[2], out[3], c
 
 
 def sift_plan(rows, cols):
@@ -139,6 +171,27 @@ class SrFrame:
         if a.shape != (self.rows, self.cols):
             raise Pre3Error(-1, "SrFrame.load: %s is %s, the handle holds %d x %d frames" % (name, a.shape, self.rows, self.cols))
         return a
+
+    def set_compensation(self, form, cutoff=1.0):
+        """the compensation of every load() / load_text() that follows (pre3_sr_frame_set_compensation; the resident frame stays as it is): COMP_NONE,
+        COMP_BADPIXEL (x, y, z and the image replaced by their 3 x 3 symmetric median where conf < cutoff) or COMP_IMAGE_MEDIAN (the uint8 image
+        median-filtered with zero padding), in front of the mode's Gaussian"""
+        check(lib.pre3_sr_frame_set_compensation(self._h, int(form), float(cutoff)))
+        return self
+
+    @property
+    def compensation(self):
+        """(form, cutoff): the setting the next load takes"""
+        form, cutoff = C.c_int32(0), C.c_double(0)
+        check(lib.pre3_sr_frame_get_compensation(self._h, C.byref(form), C.byref(cutoff)))
+        return form.value, cutoff.value
+
+    def bad_pixels(self):
+        """(form_of_frame, n_bad): the form the resident frame was conditioned with and how many of its pixels were compensated (0 unless the form is
+        COMP_BADPIXEL and the frame has a confidence map); waits"""
+        form, n = C.c_int32(0), C.c_int32(0)
+        check(lib.pre3_sr_frame_bad_pixels(self._h, C.byref(form), C.byref(n)))
+        return form.value, n.value
 
     def load(self, planes, mode=MODE_XYZ):
         """planes: dict(z, x, y, amp, conf or None) as load_dat returns it; mode 0: sigma = 2, zero padding; 1: sigma = 1, replicate"""
@@ -291,39 +344,57 @@ def _load_into(f, path, mode, parse):
     return d
 
 
-def _conditioned(path, mode, device, parse="host"):
+def _compensated(f, compensation):
+    """a handle this module created, with the caller's compensation=(form, cutoff) set on it (None: the default, none)"""
+    if compensation is not None:
+        try:
+            f.set_compensation(*compensation)
+        except Exception:
+            f.close()
+            raise
+    return f
+
+
+def _conditioned(path, mode, device, parse="host", compensation=None):
     if _check_parse(parse):                                   # a d1_%04d.dat frame (the handle's size is fixed before the text is seen)
-        f = SrFrame(ROWS, COLS, device)
+        f = _compensated(SrFrame(ROWS, COLS, device), compensation)
         try:
             return _load_into(f, path, mode, parse), f
         except Exception:
             f.close()
             raise
     d = load_dat(path)
-    f = SrFrame(d["z"].shape[0], d["z"].shape[1], device).load(d, mode)
+    f = _compensated(SrFrame(d["z"].shape[0], d["z"].shape[1], device), compensation).load(d, mode)
     return d, f
 
 
-def read_xyz_sr4000(path, with_timestamp=False, device=0, parse="host"):
+def read_xyz_sr4000(path, with_timestamp=False, device=0, parse="host", compensation=None):
     """[x, y, z, confidence_map (, timestamp)] = read_xyz_sr4000(...) on the file `path`; confidence_map is None for a frame without one.
-    parse="device": the text is parsed on the device (a 144 x 176 frame)."""
-    d, f = _conditioned(path, MODE_XYZ, device, parse)
+    parse="device": the text is parsed on the device (a 144 x 176 frame).  compensation=(form, cutoff): SrFrame.set_compensation on the frame."""
+    d, f = _conditioned(path, MODE_XYZ, device, parse, compensation)
     with f:
         out = f.planes()
     return out + (d["timestamp"],) if with_timestamp else out
 
 
-def read_image_sr4000(path, device=0, parse="host"):
+def read_image_sr4000(path, device=0, parse="host", compensation=None):
     """im = read_image_sr4000(...) on the file `path`: uint8"""
-    d, f = _conditioned(path, MODE_XYZ, device, parse)
+    d, f = _conditioned(path, MODE_XYZ, device, parse, compensation)
     with f:
         return f.image()
 
 
-def read_sr4000_data_dr_ye(path, with_timestamp=False, device=0, parse="host"):
+def read_image_sr4000_dr_ye(path, device=0, parse="host"):
+    """img = read_image_sr4000_dr_ye(...) on the file `path` (code_from_dr_ye/read_image_sr4000_dr_ye.m): read_image_sr4000 with the uint8 image
+    median-filtered (:21-24, zero padding) in front of the Gaussian -- mode 0 under COMP_IMAGE_MEDIAN"""
+    return read_image_sr4000(path, device, parse, compensation=(COMP_IMAGE_MEDIAN, 1.0))
+
+
+def read_sr4000_data_dr_ye(path, with_timestamp=False, device=0, parse="host", compensation=None):
     """[x, y, z, confidence_map, img1 (, timestamp)] = read_sr4000_data_dr_ye(path).  Deviation: a frame without confidence rows gets the same
-    normalised image as one with them (the reference leaves it un-normalised, :34-59)."""
-    d, f = _conditioned(path, MODE_DR_YE, device, parse)
+    normalised image as one with them (the reference leaves it un-normalised, :34-59).  compensation=(COMP_BADPIXEL, 1.0) switches on the call its
+    author left commented out at :44."""
+    d, f = _conditioned(path, MODE_DR_YE, device, parse, compensation)
     with f:
         out = f.planes() + (f.image(),)
     return out + (d["timestamp"],) if with_timestamp else out
@@ -440,20 +511,31 @@ def initialize_features_frames(filt, step, dat_prev, dat_cur, sift_prev, sift_cu
     return out
 
 
-def _two_frames(d1, d2, device, frames):
+def _own_pair(shape1, shape2, device, compensation):
+    """two handles of this module's own, the caller's compensation set on both"""
+    f1 = _compensated(SrFrame(shape1[0], shape1[1], device), compensation)
+    try:
+        return f1, _compensated(SrFrame(shape2[0], shape2[1], device), compensation)
+    except Exception:
+        f1.close()
+        raise
+
+
+def _two_frames(d1, d2, device, frames, compensation=None):
     own = frames is None
-    f1, f2 = (SrFrame(d1["z"].shape[0], d1["z"].shape[1], device), SrFrame(d2["z"].shape[0], d2["z"].shape[1], device)) if own else frames
+    f1, f2 = _own_pair(d1["z"].shape, d2["z"].shape, device, compensation) if own else frames
     return own, f1, f2
 
 
-def _two_frames_for(dat1, dat2, device, frames, parse):
-    """(own, f1, f2, d1, d2): the pair of handles and, for the host parse, the two files' planes (None for the device parse: _load_into reads them)"""
+def _two_frames_for(dat1, dat2, device, frames, parse, compensation=None):
+    """(own, f1, f2, d1, d2): the pair of handles and, for the host parse, the two files' planes (None for the device parse: _load_into reads them).
+    compensation=(form, cutoff) is set on the handles made here; a caller's frames= keep what the caller set on them."""
     if _check_parse(parse):
         own = frames is None
-        f1, f2 = (SrFrame(ROWS, COLS, device), SrFrame(ROWS, COLS, device)) if own else frames
+        f1, f2 = _own_pair((ROWS, COLS), (ROWS, COLS), device, compensation) if own else frames
         return own, f1, f2, None, None
     d1, d2 = load_dat(dat1), load_dat(dat2)
-    return _two_frames(d1, d2, device, frames) + (d1, d2)
+    return _two_frames(d1, d2, device, frames, compensation) + (d1, d2)
 
 
 def _load_pair_member(f, path, d, mode, parse):
@@ -463,12 +545,13 @@ def _load_pair_member(f, path, d, mode, parse):
     return d
 
 
-def vodometry_frames(dat1, dat2, seed, seq=0, thresh=1.5, device=0, frames=None, parse="host"):
+def vodometry_frames(dat1, dat2, seed, seq=0, thresh=1.5, device=0, frames=None, parse="host", compensation=None):
     """vodometry_dr_ye with the SIFT sets made on the device: each file is conditioned in mode 1, SrFrame.sift runs on its filtered image, gate 1 (gate 0
     on a frame without confidence rows) drops keypoints, then vo.vo_pair_seeded.  The gated set is 1-based, as vodometry_dr_ye.m:73-74,120-122 make
-    it before confidence_filtering.  parse="device": the two texts are parsed on the device too (SrFrame.load_text)."""
+    it before confidence_filtering.  parse="device": the two texts are parsed on the device too (SrFrame.load_text).  compensation=(form, cutoff):
+    SrFrame.set_compensation on the two frames made here (a caller's frames= keep their own setting)."""
     from . import vo
-    own, f1, f2, d1, d2 = _two_frames_for(dat1, dat2, device, frames, parse)
+    own, f1, f2, d1, d2 = _two_frames_for(dat1, dat2, device, frames, parse, compensation)
     try:
         kept = []
         for f, path, d in ((f1, dat1, d1), (f2, dat2, d2)):
@@ -483,10 +566,11 @@ def vodometry_frames(dat1, dat2, seed, seq=0, thresh=1.5, device=0, frames=None,
     return out
 
 
-def initialize_features_scans(filt, step, dat_prev, dat_cur, seed, seq=0, thresh=1.5, mode=MODE_XYZ, device=0, frames=None, parse="host", **policy):
+def initialize_features_scans(filt, step, dat_prev, dat_cur, seed, seq=0, thresh=1.5, mode=MODE_XYZ, device=0, frames=None, parse="host", compensation=None,
+                              **policy):
     """initialize_features_frames with the SIFT sets made on the device (SrFrame.sift on each conditioned scan, then the depth gate); cand_idx indexes the
-    previous scan's raw set.  parse="device": the two texts are parsed on the device too."""
-    own, f1, f2, d1, d2 = _two_frames_for(dat_prev, dat_cur, device, frames, parse)
+    previous scan's raw set.  parse="device": the two texts are parsed on the device too.  compensation=(form, cutoff): as in vodometry_frames."""
+    own, f1, f2, d1, d2 = _two_frames_for(dat_prev, dat_cur, device, frames, parse, compensation)
     try:
         kept = []
         for f, path, d in ((f1, dat_prev, d1), (f2, dat_cur, d2)):

@@ -643,6 +643,37 @@ PRE3_API int pre3_sr_frame_load(pre3_sr_frame *f, int mode, const double *z, con
  * conf != NULL on a frame loaded without one: PRE3_E_ARG. */
 PRE3_API int pre3_sr_frame_get(pre3_sr_frame *f, double *x, double *y, double *z, double *img, double *conf,
                                double *imax, double *cmax);
+/* ---- Low-confidence pixels compensated by a 3 x 3 median in front of the Gaussian -------------------------------------------
+ * A setting on the handle, not a mode: it applies to every pre3_sr_frame_load / pre3_sr_frame_load_text queued after it and does not recondition the
+ * frame that is resident.  Conditioning stays at two launches.  P a plane as loaded, U the normalised uint8 image, bad = conf < cutoff (strictly; a NaN
+ * confidence is not bad; on a frame loaded without a confidence map nothing is bad):
+ *   form 0  PRE3_SR_COMP_NONE          nothing: the default, bit for bit the library without this section.
+ *   form 1  PRE3_SR_COMP_BADPIXEL      aux_code/compensate_badpixel_soonhac.m:5-14 as code_from_dr_ye/read_sr4000_data_dr_ye.m:44 (commented out
+ *           there, between the uint8 normalisation :42 and the Gaussian :70,88-90) and read_xyz_sr4000_dr_ye.m:36-39 (cut-off 1) call it: for x, y, z
+ *           and U alike comp = bad ? medfilt2(P, [3 3], 'symmetric') : P, every median taken on the plane as loaded; the mode's Gaussian reads comp.
+ *   form 2  PRE3_SR_COMP_IMAGE_MEDIAN  code_from_dr_ye/read_image_sr4000_dr_ye.m:21-24: U' = medfilt2(U, [3 3]) (zero padding) at every pixel, the
+ *           Gaussian reads U'; x, y, z are untouched.  With mode 0 this is that file exactly.
+ * A Gaussian tap outside the image reads 0.0 in mode 0 and the compensated edge pixel in mode 1.  The median is the fifth smallest of the nine window
+ * values; a NaN in the window makes it NaN (our rule: medfilt2 documents none).  raw planes, the confidence map, imax, cmax, both keypoint gates'
+ * confidence term and pre3_sr_frame_get's conf are the same in every form.
+ * Deviations: form 1 with mode 0 is our composition of the step with read_xyz_sr4000.m's filter (the reference pairs it with sigma = 1 only);
+ * read_xyz_sr4000_dr_ye.m's own pairing (sigma = 1 with zero padding) is neither mode and is not reachable. */
+#define PRE3_SR_COMP_NONE 0
+#define PRE3_SR_COMP_BADPIXEL 1
+#define PRE3_SR_COMP_IMAGE_MEDIAN 2
+#define PRE3_SR_MEDFILT_MAX_PIXELS (1 << 26)   /* rows * cols of pre3_sr_medfilt3, the cap of pre3_sr_frame_create */
+/* the setting for the loads that follow.  PRE3_E_ARG, the setting unchanged: a null handle, a form outside 0 .. 2, a non-finite cutoff with form 1.
+ * Host only: launches nothing, waits for nothing. */
+PRE3_API int pre3_sr_frame_set_compensation(pre3_sr_frame *f, int form, double cutoff);
+PRE3_API int pre3_sr_frame_get_compensation(pre3_sr_frame *f, int32_t *form, double *cutoff);
+/* the form the RESIDENT frame was conditioned with and the number of pixels compensate_badpixel_soonhac.m:6 replaced in it: n_bad is 0 under forms 0
+ * and 2 and on a frame without a confidence map.  Synchronises.  PRE3_E_STATE before the first load; a refused pre3_sr_frame_load_text leaves both as
+ * they were, with the previous frame. */
+PRE3_API int pre3_sr_frame_bad_pixels(pre3_sr_frame *f, int32_t *form_of_frame, int32_t *n_bad);
+/* medfilt2(A, [3 3]) (padding 0: zeros, MATLAB's default) or medfilt2(A, [3 3], 'symmetric') (padding 1) of a rows x cols column-major plane of
+ * doubles -- they may hold uint8 values: the median is a selection.  Stateless, on the library's per-device scratch; synchronises.  Any size from
+ * 1 x 1 to PRE3_SR_MEDFILT_MAX_PIXELS pixels.  PRE3_E_ARG: a null pointer, a padding other than 0 or 1, a non-positive size or one above the cap. */
+PRE3_API int pre3_sr_medfilt3(int device, int rows, int cols, const double *A, int padding, double *out);
 /* ---- The .dat text of a frame parsed on the device (read_xyz_sr4000.m:2-3,25-42: load() of d1_%04d.dat).
  * Grammar -- what MATLAB's load and numpy.loadtxt both accept for these files, nothing more: space, tab and \r separate; a row ends at \n or at the
  * end of the text; a line without a token is skipped; a token is [+-]?digits[.digits*]?([eE][+-]?digits)?, [+-]?.digits with the same exponent,

@@ -46,6 +46,8 @@ static pre3_ctx *g_ctx = NULL;
 static pre3_sr_frame *g_sr = NULL;          /* the resident SR4000 frame of 'sr_frame' / 'sr_keypoints' */
 static pre3_sr_frame *g_sr_prev = NULL;     /* the frame 'sr_keep' put aside: prev of 'vo_pair' */
 static int g_sr_rows = 0, g_sr_cols = 0;
+static int g_sr_comp_form = PRE3_SR_COMP_NONE;   /* 'sr_compensation': the setting of every frame loaded from now on, whichever handle takes it */
+static double g_sr_comp_cutoff = 1.0;
 static int g_cam_rows = 0, g_cam_cols = 0;  /* the camera's shape, which is the resident image's ('fast_detect' without a box) */
 static void at_exit(void) { if (g_ctx) { pre3_destroy(g_ctx); g_ctx = NULL; } }
 static void sr_at_exit(void) { if (g_sr) { pre3_sr_frame_destroy(g_sr); g_sr = NULL; } if (g_sr_prev) { pre3_sr_frame_destroy(g_sr_prev); g_sr_prev = NULL; } at_exit(); }
@@ -81,6 +83,7 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
             if (g_sr_prev) { pre3_sr_frame_destroy(g_sr_prev); g_sr_prev = NULL; }
         }
         if (!g_sr) { check(pre3_sr_frame_create(&g_sr, 0, rows, cols)); g_sr_rows = rows; g_sr_cols = cols; mexAtExit(sr_at_exit); if (!mexIsLocked()) mexLock(); }
+        check(pre3_sr_frame_set_compensation(g_sr, g_sr_comp_form, g_sr_comp_cutoff));
         check(pre3_sr_frame_load(g_sr, (int)mxGetScalar(in[1]), mxGetPr(in[2]), mxGetPr(in[3]), mxGetPr(in[4]), mxGetPr(in[5]), mxIsEmpty(in[6]) ? NULL : mxGetPr(in[6])));
         for (i = 0; i < 4; ++i) out[i] = mxCreateDoubleMatrix(rows, cols, mxREAL);
         check(pre3_sr_frame_get(g_sr, mxGetPr(out[0]), mxGetPr(out[1]), mxGetPr(out[2]), mxGetPr(out[3]), NULL, &imax, &cmax));
@@ -102,6 +105,7 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
             if (g_sr_prev) { pre3_sr_frame_destroy(g_sr_prev); g_sr_prev = NULL; }
         }
         if (!g_sr) { check(pre3_sr_frame_create(&g_sr, 0, rows, cols)); g_sr_rows = rows; g_sr_cols = cols; mexAtExit(sr_at_exit); if (!mexIsLocked()) mexLock(); }
+        check(pre3_sr_frame_set_compensation(g_sr, g_sr_comp_form, g_sr_comp_cutoff));
         n = mxGetNumberOfElements(in[2]);
         if (is_char) {                       /* MATLAB's char is 16 bits wide */
             const unsigned short *c = (const unsigned short *)mxGetData(in[2]);
@@ -117,6 +121,46 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         v[7] = ti.bad_row; v[8] = ti.bad_col; v[9] = (double)ti.bad_offset; v[10] = ti.timestamp;
         out[0] = mxCreateStructMatrix(1, 1, 11, fn);
         for (i = 0; i < 11; ++i) mxSetField(out[0], 0, fn[i], mxCreateDoubleScalar(v[i]));
+        (void)nout;
+        return;
+    }
+    if (!strcmp(cmd, "sr_compensation")) {   /* [form, cutoff] = pre3_mex('sr_compensation', h, form, cutoff): the compensation in front of the Gaussian for every 'sr_frame' /
+                                                 'sr_frame_text' from now on (pre3_sr_frame_set_compensation) -- form 0: none, 1: aux_code/compensate_badpixel_soonhac.m:5-14 (x, y, z
+                                                 and the image replaced by their 3 x 3 symmetric median where conf < cutoff), 2: read_image_sr4000_dr_ye.m:21-24 (medfilt2 of the uint8
+                                                 image).  h = 0: the setting is the gateway's, because 'sr_keep' swaps the two handles; the resident frames stay as they are.
+                                                 With h alone: returns the setting */
+        if (nin != 2 && nin != 4) mexErrMsgTxt("pre3_mex('sr_compensation', h [, form, cutoff]): one or three arguments");
+        if ((int)mxGetScalar(in[1]) != 0) mexErrMsgTxt("pre3_mex('sr_compensation'): h must be 0 (the setting belongs to the gateway, not to one of its two frames)");
+        if (nin == 4) {
+            const int form = (int)mxGetScalar(in[2]); const double cutoff = mxGetScalar(in[3]);
+            if (form < PRE3_SR_COMP_NONE || form > PRE3_SR_COMP_IMAGE_MEDIAN || (double)form != mxGetScalar(in[2])) mexErrMsgTxt("pre3_mex('sr_compensation'): form must be 0, 1 or 2");
+            if (form == PRE3_SR_COMP_BADPIXEL && !(cutoff - cutoff == 0.0)) mexErrMsgTxt("pre3_mex('sr_compensation'): the cut-off of form 1 must be finite");
+            if (g_sr) check(pre3_sr_frame_set_compensation(g_sr, form, cutoff));
+            if (g_sr_prev) check(pre3_sr_frame_set_compensation(g_sr_prev, form, cutoff));
+            g_sr_comp_form = form; g_sr_comp_cutoff = cutoff;
+        }
+        out[0] = mxCreateDoubleScalar((double)g_sr_comp_form);
+        if (nout > 1) out[1] = mxCreateDoubleScalar(g_sr_comp_cutoff);
+        return;
+    }
+    if (!strcmp(cmd, "sr_bad_pixels")) {     /* [n_bad, form_of_frame] = pre3_mex('sr_bad_pixels', h): how many pixels of the frame were compensated and the form it was conditioned
+                                                 with (pre3_sr_frame_bad_pixels).  h = 0: the resident frame, 1: the frame 'sr_keep' put aside */
+        int32_t form = 0, n_bad = 0; int h;
+        if (nin != 2) mexErrMsgTxt("pre3_mex('sr_bad_pixels', h): one argument");
+        h = (int)mxGetScalar(in[1]);
+        if (h != 0 && h != 1) mexErrMsgTxt("pre3_mex('sr_bad_pixels'): h must be 0 (the resident frame) or 1 (the frame 'sr_keep' put aside)");
+        if (!(h ? g_sr_prev : g_sr)) mexErrMsgTxt("pre3_mex('sr_bad_pixels'): there is no such frame yet");
+        check(pre3_sr_frame_bad_pixels(h ? g_sr_prev : g_sr, &form, &n_bad));
+        out[0] = mxCreateDoubleScalar((double)n_bad);
+        if (nout > 1) out[1] = mxCreateDoubleScalar((double)form);
+        return;
+    }
+    if (!strcmp(cmd, "medfilt3")) {          /* B = pre3_mex('medfilt3', A, padding): medfilt2(A, [3 3]) (padding 0, zeros: MATLAB's default) or medfilt2(A, [3 3], 'symmetric')
+                                                 (padding 1) of a double matrix on the device (pre3_sr_medfilt3); a NaN in a window makes that pixel NaN */
+        if (nin != 3) mexErrMsgTxt("pre3_mex('medfilt3', A, padding): two arguments");
+        if (!mxIsDouble(in[1]) || mxIsComplex(in[1]) || mxGetNumberOfDimensions(in[1]) != 2 || mxIsEmpty(in[1])) mexErrMsgTxt("pre3_mex('medfilt3'): A must be a real, non-empty double matrix");
+        out[0] = mxCreateDoubleMatrix(mxGetM(in[1]), mxGetN(in[1]), mxREAL);
+        check(pre3_sr_medfilt3(0, (int)mxGetM(in[1]), (int)mxGetN(in[1]), mxGetPr(in[1]), (int)mxGetScalar(in[2]), mxGetPr(out[0])));
         (void)nout;
         return;
     }
