@@ -2,6 +2,7 @@
 // marshalling, the stateless drop-ins, matcher forwards and timers.  The stage order of a filter step is in pre3_step.hip.
 #include <time.h>
 #include <algorithm>
+#include <atomic>
 #include <immintrin.h>
 #include <cmath>
 #include <cstdarg>
@@ -28,22 +29,39 @@ void set_error(const char *fmt, ...)
     va_end(ap);
 }
 
-template <typename T> static int dmalloc(T **p, size_t count)
+// ---- the seam of pre3_own.h over HIP: the only allocations of the library besides the ScratchPool's (pre3_match.hip).  g_live: device blocks, device
+// bytes, pinned blocks, pinned bytes that are live (pre3_test_live_blocks)
+static std::atomic<int64_t> g_live[4];
+static void live_count(int kind, int sign, size_t bytes)
 {
-    void *q = nullptr;
-    if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) { set_error("hipMalloc of %zu bytes failed", sizeof(T) * count); return PRE3_E_NOMEM; }
-    // defined contents: a recycled allocation must not leak a previous context's data into fields the reference leaves empty
-    // (a measured landmark that is not predicted has h = [] there; its h/H were whatever the allocator returned here)
-    if (hipMemset(q, 0, sizeof(T) * (count ? count : 1)) != hipSuccess) { (void)hipFree(q); set_error("hipMemset failed"); return PRE3_E_HIP; }
-    *p = (T *)q;
+    g_live[2 * kind].fetch_add(sign, std::memory_order_relaxed);
+    g_live[2 * kind + 1].fetch_add(sign * (int64_t)bytes, std::memory_order_relaxed);
+}
+int own_dev_alloc(void **p, size_t bytes)
+{
+    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; set_error("hipMalloc of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
+    live_count(0, +1, bytes);
     return PRE3_OK;
 }
-int dmalloc_bytes(void **p, size_t bytes)
+void own_dev_free(void *p, size_t bytes) { (void)hipFree(p); live_count(0, -1, bytes); }
+static_assert(PIN_DEFAULT == hipHostMallocDefault && PIN_PORTABLE == hipHostMallocPortable && PIN_MAPPED == hipHostMallocMapped, "pre3_own.h's flags are HIP's");
+int own_pin_alloc(void **p, size_t bytes, unsigned flags)
 {
-    if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) { set_error("hipMalloc of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
-    if (hipMemset(*p, 0, bytes ? bytes : 16) != hipSuccess) { (void)hipFree(*p); *p = nullptr; set_error("hipMemset failed"); return PRE3_E_HIP; }
+    if (hipHostMalloc(p, bytes, flags) != hipSuccess) { *p = nullptr; set_error("hipHostMalloc of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
+    live_count(1, +1, bytes);
     return PRE3_OK;
 }
+void own_pin_free(void *p, size_t bytes) { (void)hipHostFree(p); live_count(1, -1, bytes); }
+int own_dev_zero(void *p, size_t bytes, void *stream)
+{
+    const hipError_t e = stream ? hipMemsetAsync(p, 0, bytes, (hipStream_t)stream) : hipMemset(p, 0, bytes);
+    if (e != hipSuccess) { set_error("hipMemset failed: %s", hipGetErrorString(e)); return PRE3_E_HIP; }
+    return PRE3_OK;
+}
+
+// a block on the context's fixed list with defined contents: a recycled allocation must not leak a previous context's data into fields the reference
+// leaves empty (a measured landmark that is not predicted has h = [] there; its h/H were whatever the allocator returned here)
+template <typename T> static int dmalloc(pre3_ctx *c, T **p, size_t count) { return c->mem.fixed.dev(p, sizeof(T) * (count ? count : 1), Zero::sync()); }
 
 static int complete_deferred_hi(pre3_ctx *c)
 {
@@ -241,6 +259,7 @@ int stage_wait(pre3_ctx *c, int k)
     }
     return PRE3_OK;
 }
+static int ring_wait(void *ctx, int slot) { return stage_wait(static_cast<pre3_ctx *>(ctx), slot); }
 static StageDone stage_done(pre3_ctx *c, int k) { return StageDone{ c->chol_arrive + 8 + k, c->mail_dev + 16 + k, ++c->stage_seq[k] }; }
 
 // bytes of a pinned (device-mapped) host block -> device memory, read over PCIe by the device itself on the context's stream: no DMA engine,
@@ -319,9 +338,9 @@ static int pend_alloc(pre3_ctx *c)
     PRE3_CHECK(c->dtype == PRE3_F32 && c->Wp != nullptr && c->rcap >= 2 * NB, PRE3_E_STATE, "PRE3_OPT_PEND_HI: fp32 contexts with the persistent factorisation only");
     int rc = PRE3_OK;
     auto A = [&](int r) { if (rc == PRE3_OK) rc = r; };
-    if (!c->W_pend) { void *f = nullptr; A(dmalloc_bytes(&f, (size_t)2 * NB * c->ldw * sizeof(float))); c->W_pend = (float *)f; }
-    if (!c->Wp_pend) A(dmalloc_bytes(&c->Wp_pend, (size_t)ceil_div(c->ldw, 128) * (c->rcap / 16) * (3 * 4 * 64) * 16));
-    if (!c->hf_xy) { void *f = nullptr; A(dmalloc_bytes(&f, sizeof(unsigned) * 256)); c->hf_xy = (unsigned *)f; }
+    if (!c->W_pend) A(dmalloc_bytes(c, &c->W_pend, (size_t)2 * NB * c->ldw * sizeof(float)));
+    if (!c->Wp_pend) A(dmalloc_bytes(c, &c->Wp_pend, (size_t)ceil_div(c->ldw, 128) * (c->rcap / 16) * (3 * 4 * 64) * 16));
+    if (!c->hf_xy) A(dmalloc_bytes(c, &c->hf_xy, sizeof(unsigned) * 256));
     return rc;
 }
 
@@ -331,10 +350,10 @@ static int tail_alloc(pre3_ctx *c)
     PRE3_CHECK(c->dtype == PRE3_F32 && c->Wp != nullptr, PRE3_E_STATE, "PRE3_OPT_STEP_TAIL: fp32 contexts with the persistent factorisation only");
     int rc = PRE3_OK;
     auto A = [&](int r) { if (rc == PRE3_OK) rc = r; };
-    if (!c->tail_yp) A(dmalloc_bytes(&c->tail_yp, (size_t)(c->capN + 1) * 2 * 3 * c->rcap * 2));
-    if (!c->tail_hb) { void *f = nullptr; A(dmalloc_bytes(&f, (size_t)c->capN * 2 * 16 * sizeof(float))); c->tail_hb = (float *)f; }
-    if (!c->tail_hib) { void *f = nullptr; A(dmalloc_bytes(&f, sizeof(int32_t) * (64 + 64 * 16))); c->tail_hib = (int32_t *)f; }
-    if (!c->tail_wt) { void *f = nullptr; A(dmalloc_bytes(&f, (size_t)c->ldw * c->rcap * sizeof(float))); c->tail_wt = (float *)f; }
+    if (!c->tail_yp) A(dmalloc_bytes(c, &c->tail_yp, (size_t)(c->capN + 1) * 2 * 3 * c->rcap * 2));
+    if (!c->tail_hb) A(dmalloc_bytes(c, &c->tail_hb, (size_t)c->capN * 2 * 16 * sizeof(float)));
+    if (!c->tail_hib) A(dmalloc_bytes(c, &c->tail_hib, sizeof(int32_t) * (64 + 64 * 16)));
+    if (!c->tail_wt) A(dmalloc_bytes(c, &c->tail_wt, (size_t)c->ldw * c->rcap * sizeof(float)));
     return rc;
 }
 
@@ -359,12 +378,14 @@ int pre3_create(pre3_ctx **out, int device, int dtype, int max_landmarks, int ma
     int rc = PRE3_OK;
     auto A = [&](int r) { if (rc == PRE3_OK) rc = r; };
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete c; return PRE3_E_HIP; }
-    A(dmalloc(&c->x_kk, c->capn)); A(dmalloc(&c->x_km1, c->capn));
-    A(dmalloc_bytes(&c->P, (size_t)c->ld * c->ld * c->esz));
-    A(dmalloc(&c->lm.type, c->capN)); A(dmalloc(&c->lm.off, c->capN));
-    A(dmalloc(&c->lm.h, 2 * (size_t)c->capN)); A(dmalloc(&c->lm.has_h, c->capN));
-    A(dmalloc(&c->lm.Hc, 14 * (size_t)c->capN)); A(dmalloc(&c->lm.Hl, 12 * (size_t)c->capN));
-    A(dmalloc(&c->lm.S, 4 * (size_t)c->capN)); A(dmalloc(&c->lm.has_S, c->capN));
+    for (StageRing *r : { &c->mem.up_ring, &c->mem.map_ring }) { r->flags = PIN_MAPPED; r->wait = ring_wait; r->wait_ctx = c; }
+    c->mem.map_ring.base = 2;
+    A(dmalloc(c, &c->x_kk, c->capn)); A(dmalloc(c, &c->x_km1, c->capn));
+    A(dmalloc_bytes(c, &c->P, (size_t)c->ld * c->ld * c->esz));
+    A(dmalloc(c, &c->lm.type, c->capN)); A(dmalloc(c, &c->lm.off, c->capN));
+    A(dmalloc(c, &c->lm.h, 2 * (size_t)c->capN)); A(dmalloc(c, &c->lm.has_h, c->capN));
+    A(dmalloc(c, &c->lm.Hc, 14 * (size_t)c->capN)); A(dmalloc(c, &c->lm.Hl, 12 * (size_t)c->capN));
+    A(dmalloc(c, &c->lm.S, 4 * (size_t)c->capN)); A(dmalloc(c, &c->lm.has_S, c->capN));
     {
         // inbox: [meas | ic | hyp | z] is what the one H2D copy of a step ships (kept under 16 KB at N=500: larger copies
         // leave the runtime's shader path for the SDMA path, +20 us); the inlier flags [li | hi | li_meas | hi_meas] follow
@@ -378,8 +399,8 @@ int pre3_create(pre3_ctx **out, int device, int dtype, int max_landmarks, int ma
         const size_t off_lim = off_hi + sizeof(int32_t) * c->capN, off_him = off_lim + sizeof(int32_t) * c->capm;
         c->flags_bytes = sizeof(int32_t) * (2 * (size_t)c->capN + 2 * (size_t)c->capm);
         c->inbox_bytes = c->off_flags + c->flags_bytes;
-        A(dmalloc_bytes(&c->inbox_dev, c->inbox_bytes));
-        if (rc == PRE3_OK && hipHostMalloc((void **)&c->inbox_host, c->inbox_bytes, hipHostMallocMapped) != hipSuccess) { set_error("hipHostMalloc failed"); rc = PRE3_E_NOMEM; }
+        A(dmalloc_bytes(c, &c->inbox_dev, c->inbox_bytes));
+        if (rc == PRE3_OK) A(c->mem.fixed.pin(&c->inbox_host, c->inbox_bytes, PIN_MAPPED));
         if (rc == PRE3_OK && hipHostGetDevicePointer((void **)&c->inbox_host_dev, c->inbox_host, 0) != hipSuccess) { set_error("hipHostGetDevicePointer failed"); rc = PRE3_E_HIP; }
         if (rc == PRE3_OK) {
             memset(c->inbox_host, 0, c->inbox_bytes);
@@ -389,20 +410,20 @@ int pre3_create(pre3_ctx **out, int device, int dtype, int max_landmarks, int ma
             c->hyp = (int32_t *)(d + c->off_hyp); c->lm.z = (double *)(d + c->off_z);
         }
     }
-    A(dmalloc(&c->row_col, (size_t)c->rcap * ELLW)); A(dmalloc_bytes(&c->row_val, (size_t)c->rcap * ELLW * c->esz));
-    A(dmalloc(&c->row_nu, c->rcap));
-    A(dmalloc_bytes(&c->HP, (size_t)c->rcap * c->ldw * c->esz));
-    A(dmalloc_bytes(&c->W, (size_t)c->rcap * c->ldw * c->esz));
-    A(dmalloc_bytes(&c->G, (size_t)c->rcap * c->rcap * c->esz));
-    A(dmalloc_bytes(&c->Smat, (size_t)c->rcap * c->rcap * c->esz));
-    A(dmalloc(&c->sel_rows, c->rcap)); A(dmalloc(&c->need, c->capm));
+    A(dmalloc(c, &c->row_col, (size_t)c->rcap * ELLW)); A(dmalloc_bytes(c, &c->row_val, (size_t)c->rcap * ELLW * c->esz));
+    A(dmalloc(c, &c->row_nu, c->rcap));
+    A(dmalloc_bytes(c, &c->HP, (size_t)c->rcap * c->ldw * c->esz));
+    A(dmalloc_bytes(c, &c->W, (size_t)c->rcap * c->ldw * c->esz));
+    A(dmalloc_bytes(c, &c->G, (size_t)c->rcap * c->rcap * c->esz));
+    A(dmalloc_bytes(c, &c->Smat, (size_t)c->rcap * c->rcap * c->esz));
+    A(dmalloc(c, &c->sel_rows, c->rcap)); A(dmalloc(c, &c->need, c->capm));
     if (rc == PRE3_OK) (void)hipMemset(c->need, 0, sizeof(int32_t) * c->capm);
     // supports and inlier masks in ONE allocation, the masks right behind the n_draw supports of the current round (ransac_prepare sets
     // c->masks): a sharded round all-reduces both with a single collective over one contiguous range
-    A(dmalloc(&c->support, (size_t)c->caph + 4 + (size_t)c->caph * c->mask_words_cap));
+    A(dmalloc(c, &c->support, (size_t)c->caph + 4 + (size_t)c->caph * c->mask_words_cap));
     if (rc == PRE3_OK) c->masks = reinterpret_cast<uint32_t *>(c->support + c->caph + 4);
-    A(dmalloc(&c->stats, 16));
-    A(dmalloc(&c->pred_params, 192));
+    A(dmalloc(c, &c->stats, 16));
+    A(dmalloc(c, &c->pred_params, 192));
     {
         // K9 tile schedule: upper-triangle 64x64 tiles in 4x4 super-tile order, so that the tiles in flight at
         // any moment (tickets are handed out in this order) share W panels in L2 / Infinity Cache.
@@ -440,36 +461,36 @@ int pre3_create(pre3_ctx **out, int device, int dtype, int max_landmarks, int ma
             while ((int)inter.size() < total)
                 for (int x = 0; x < 8 && (int)inter.size() < total; ++x)
                     if (pos[x] < lists[x].size()) inter.push_back(lists[x][pos[x]++]);
-            A(dmalloc_bytes(&c->tiles_flat, sizeof(int2) * (inter.size() ? inter.size() : 1)));
+            A(dmalloc_bytes(c, &c->tiles_flat, sizeof(int2) * (inter.size() ? inter.size() : 1)));
             if (rc == PRE3_OK && hipMemcpy(c->tiles_flat, inter.data(), sizeof(int2) * inter.size(), hipMemcpyHostToDevice) != hipSuccess) { set_error("tile table upload failed"); rc = PRE3_E_HIP; }
         }
-        A(dmalloc(&c->tile_ctr, 8)); A(dmalloc(&c->tile_cnt, 8)); A(dmalloc(&c->chol_arrive, 16));      // ([8..11]: arrival counters of the staging pulls)
+        A(dmalloc(c, &c->tile_ctr, 8)); A(dmalloc(c, &c->tile_cnt, 8)); A(dmalloc(c, &c->chol_arrive, 16));      // ([8..11]: arrival counters of the staging pulls)
         if (rc == PRE3_OK) (void)hipMemset(c->chol_arrive, 0, sizeof(unsigned int) * 16);
         if (rc == PRE3_OK) { (void)hipMemset(c->tile_ctr, 0, sizeof(unsigned int) * 8); (void)hipMemcpy(c->tile_cnt, cnts, sizeof(cnts), hipMemcpyHostToDevice); }
         { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0) c->num_cus = pr.multiProcessorCount; }
-        A(dmalloc_bytes(&c->tiles, sizeof(int2) * flat.size()));
+        A(dmalloc_bytes(c, &c->tiles, sizeof(int2) * flat.size()));
         if (rc == PRE3_OK && hipMemcpy(c->tiles, flat.data(), sizeof(int2) * flat.size(), hipMemcpyHostToDevice) != hipSuccess) { set_error("tile table upload failed"); rc = PRE3_E_HIP; }
     }
     if (dtype == PRE3_F32) {
         c->k9_b3 = knob::k9_b3() != 0;
         // k_downdate_b3: bf16 planes of W and the 128x128 tile list (4x4 super-tiles dealt to 8 lists, lists interleaved: block b runs
         // on XCD b % 8, so a super-tile's 8 column blocks of planes stay in one L2)
-        A(dmalloc_bytes(&c->Wp, (size_t)(c->ld + 128) * c->rcap * 6));       // + one column block for the nu strip's planes
-        A(dmalloc_bytes(&c->Sp, (size_t)(c->rcap / NB) * (c->rcap / NB) * 1536 * 16));
+        A(dmalloc_bytes(c, &c->Wp, (size_t)(c->ld + 128) * c->rcap * 6));       // + one column block for the nu strip's planes
+        A(dmalloc_bytes(c, &c->Sp, (size_t)(c->rcap / NB) * (c->rcap / NB) * 1536 * 16));
         // persistent factorisation (pre3_cholp.hip): flag words (zero: every launch brings its own epoch), one plane block per row for the hand-over to crit
-        { void *f = nullptr; A(dmalloc_bytes(&f, cholp_flag_bytes(c->ldw / 32))); c->cholp_flags = (unsigned int *)f; }
+        A(dmalloc_bytes(c, &c->cholp_flags, cholp_flag_bytes(c->ldw / 32)));
         {   // the down-date consumers' schedule (pre3_cholp.hip)
             std::vector<int32_t> rec; std::vector<int2> t64;
             dd_build_groups(c->ld / 64, rec, t64, c->dd_tile_off);
             c->dd_n_groups = (int)c->dd_tile_off.size() - 1;
-            { void *f = nullptr; A(dmalloc_bytes(&f, sizeof(int32_t) * rec.size())); c->dd_groups = (int32_t *)f; }
-            A(dmalloc_bytes(&c->dd_tiles, sizeof(int2) * t64.size()));
+            A(dmalloc_bytes(c, &c->dd_groups, sizeof(int32_t) * rec.size()));
+            A(dmalloc_bytes(c, &c->dd_tiles, sizeof(int2) * t64.size()));
             if (rc == PRE3_OK && (hipMemcpy(c->dd_groups, rec.data(), sizeof(int32_t) * rec.size(), hipMemcpyHostToDevice) != hipSuccess ||
                                   hipMemcpy(c->dd_tiles, t64.data(), sizeof(int2) * t64.size(), hipMemcpyHostToDevice) != hipSuccess)) { set_error("consumer table upload failed"); rc = PRE3_E_HIP; }
         }
-        A(dmalloc_bytes(&c->cholp_tp, (size_t)(c->rcap / NB) * 1536 * 16));
-        { void *f = nullptr; A(dmalloc_bytes(&f, sizeof(float) * 4 * (size_t)c->ld)); c->jn_q = (float *)f; }
-        { void *f = nullptr; A(dmalloc_bytes(&f, sizeof(unsigned long long) * (2 * NB) * (2 * NB))); c->hf_sx = (unsigned long long *)f; }      // rows 3..6 of P before the Jnorm pass (GateRide, pre3_geom.hip)
+        A(dmalloc_bytes(c, &c->cholp_tp, (size_t)(c->rcap / NB) * 1536 * 16));
+        A(dmalloc_bytes(c, &c->jn_q, sizeof(float) * 4 * (size_t)c->ld));
+        A(dmalloc_bytes(c, &c->hf_sx, sizeof(unsigned long long) * (2 * NB) * (2 * NB)));      // rows 3..6 of P before the Jnorm pass (GateRide, pre3_geom.hip)
         // (the buffers of the in-launch tail, PRE3_OPT_STEP_TAIL, are allocated when the option is switched on: tail_alloc -- at N = 2000 they are
         //  ~300 MB that the default path never touches)
         if (c->step_tail) A(tail_alloc(c));
@@ -515,11 +536,11 @@ int pre3_create(pre3_ctx **out, int device, int dtype, int max_landmarks, int ma
         inter = big;
         inter.insert(inter.end(), small.begin(), small.end());
         c->n_tiles128 = (int)inter.size();
-        A(dmalloc_bytes(&c->tiles128, sizeof(int2) * inter.size()));
+        A(dmalloc_bytes(c, &c->tiles128, sizeof(int2) * inter.size()));
         if (rc == PRE3_OK && hipMemcpy(c->tiles128, inter.data(), sizeof(int2) * inter.size(), hipMemcpyHostToDevice) != hipSuccess) { set_error("tile table upload failed"); rc = PRE3_E_HIP; }
     }
-    if (rc == PRE3_OK && hipHostMalloc((void **)&c->pinned_stats, sizeof(int32_t) * 16) != hipSuccess) { set_error("hipHostMalloc failed"); rc = PRE3_E_NOMEM; }
-    if (rc == PRE3_OK && hipHostMalloc((void **)&c->mail_host, sizeof(int32_t) * 32, hipHostMallocMapped) != hipSuccess) { set_error("hipHostMalloc failed"); rc = PRE3_E_NOMEM; }
+    if (rc == PRE3_OK) A(c->mem.fixed.pin(&c->pinned_stats, sizeof(int32_t) * 16, PIN_DEFAULT));
+    if (rc == PRE3_OK) A(c->mem.fixed.pin(&c->mail_host, sizeof(int32_t) * 32, PIN_MAPPED));
     if (rc == PRE3_OK) {
         memset(c->mail_host, 0, sizeof(int32_t) * 32);      // (words 16..19: the staging blocks' "pulled" sequence numbers, stage_wait)
         if (hipHostGetDevicePointer((void **)&c->mail_dev, c->mail_host, 0) != hipSuccess) { set_error("hipHostGetDevicePointer failed"); rc = PRE3_E_HIP; }
@@ -546,22 +567,9 @@ int pre3_destroy(pre3_ctx *c)
     ic_rank_free(c);
     if (c->comm && c->comm_owned) (void)pre3_comm_destroy((pre3_comm *)c->comm);
     c->comm = nullptr;
-    void *bufs[] = { c->x_kk, c->x_km1, c->P, c->lm.type, c->lm.off, c->lm.h, c->lm.has_h, c->lm.Hc, c->lm.Hl, c->lm.S, c->lm.has_S,
-                     c->inbox_dev, c->row_col, c->row_val, c->row_nu, c->HP, c->W, c->G, c->Smat, c->Rdense,
-                     c->sel_rows, c->support, c->stats, c->pred_params, c->tiles, c->tile_ctr, c->tile_cnt, c->tiles_flat, c->P_alt, c->x_alt, c->map_col, c->map_val, c->map_desc, c->map_src0, c->map_conv, c->map_feat, c->map_flags, c->bank, c->bank_alt, c->scan_desc, c->scan_pos, c->ic_pred, c->ic_counts, c->ic_arg, c->ic_newk2, c->ic_best, c->ic_second, c->bank_src, c->chol_arrive, c->ic_pb, c->ic_ps, c->ic_pa, c->Wp, c->Sp, c->tiles128, c->need, c->cholp_flags, c->cholp_tp, c->dd_groups, c->dd_tiles, c->tail_yp, c->tail_hb, c->tail_hib, c->tail_wt, c->jn_q, c->W_pend, c->Wp_pend, c->hf_xy, c->hf_sx };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    free_readers(c);
-    free_rows(c);
-    free_plane(c);
-    free_policy(c);
+    c->mem = CtxMemory();                 // every device and pinned block of the context (the typed pointers dangle from here on)
     free_patch(c);
     free_fast(c);
-    for (int k2 = 0; k2 < 2; ++k2) { if (c->map_stage[k2]) (void)hipHostFree(c->map_stage[k2]); if (c->map_stage_ev[k2]) (void)hipEventDestroy(c->map_stage_ev[k2]); }
-    for (int k2 = 0; k2 < 2; ++k2) { if (c->up_stage[k2]) (void)hipHostFree(c->up_stage[k2]); if (c->up_stage_ev[k2]) (void)hipEventDestroy(c->up_stage_ev[k2]); }
-    if (c->pinned_stats) (void)hipHostFree(c->pinned_stats);
-    if (c->inbox_host) (void)hipHostFree(c->inbox_host);
-    if (c->mail_host) (void)hipHostFree(c->mail_host);
-    if (c->ic_result_host) (void)hipHostFree(c->ic_result_host);
     for (hipEvent_t e : c->kt.ev) (void)hipEventDestroy(e);
     if (c->t0) (void)hipEventDestroy(c->t0);
     if (c->t1) (void)hipEventDestroy(c->t1);
@@ -875,13 +883,13 @@ int pre3_window_gate(pre3_ctx *c, int M, const int32_t *k1, const double *zc, in
     for (int q = 0; q < M; ++q) PRE3_CHECK(k1[q] >= 0 && k1[q] < (int)pred.size(), PRE3_E_ARG, "pre3_window_gate: k1[%d]=%d out of range", q, k1[q]);
     std::vector<int32_t> acc(M ? M : 1, 0);
     if (M) {
-        // temporaries are released on every exit path (an early PRE3_TRY / PRE3_HIP return used to leak them)
-        struct Tmp { void *p[4] = { nullptr, nullptr, nullptr, nullptr }; ~Tmp() { for (void *q : p) if (q) (void)hipFree(q); } } tmp;
+        // temporaries, released on every exit path
+        BlockList tmp;
         int32_t *d_pred = nullptr, *d_k1 = nullptr, *d_acc = nullptr; double *d_zc = nullptr;
-        PRE3_TRY(dmalloc(&d_pred, pred.size())); tmp.p[0] = d_pred;
-        PRE3_TRY(dmalloc(&d_k1, M)); tmp.p[1] = d_k1;
-        PRE3_TRY(dmalloc(&d_acc, M)); tmp.p[2] = d_acc;
-        PRE3_TRY(dmalloc(&d_zc, 2 * (size_t)M)); tmp.p[3] = d_zc;
+        PRE3_TRY(tmp.dev(&d_pred, sizeof(int32_t) * pred.size(), Zero::sync()));
+        PRE3_TRY(tmp.dev(&d_k1, sizeof(int32_t) * M, Zero::sync()));
+        PRE3_TRY(tmp.dev(&d_acc, sizeof(int32_t) * M, Zero::sync()));
+        PRE3_TRY(tmp.dev(&d_zc, sizeof(double) * 2 * (size_t)M, Zero::sync()));
         PRE3_HIP(hipMemcpy(d_pred, pred.data(), sizeof(int32_t) * pred.size(), hipMemcpyHostToDevice));
         PRE3_HIP(hipMemcpy(d_k1, k1, sizeof(int32_t) * M, hipMemcpyHostToDevice));
         PRE3_HIP(hipMemcpy(d_zc, zc, sizeof(double) * 2 * M, hipMemcpyHostToDevice));
@@ -903,18 +911,22 @@ int pre3_window_gate(pre3_ctx *c, int M, const int32_t *k1, const double *zc, in
 // ---- IC search on the device ---------------------------------------------------------
 static int ensure_ic_buffers(pre3_ctx *c)
 {
-    if (c->bank) return PRE3_OK;
+    if (c->ic_ready) return PRE3_OK;
     const size_t N = (size_t)c->capN;
-    PRE3_TRY(dmalloc(&c->bank, N * DESC_DIM)); PRE3_TRY(dmalloc(&c->bank_alt, N * DESC_DIM));
+    Group g(c->mem.fixed, c->ic_ready);       // complete, or gone with its pointers null: a call after a failed one starts over
+    auto D = [&](auto **p, size_t count) { return g.dev(p, sizeof(**p) * count, Zero::sync()); };      // (dmalloc's zeroing)
+    PRE3_TRY(D(&c->bank, N * DESC_DIM)); PRE3_TRY(D(&c->bank_alt, N * DESC_DIM));
     // result block, fetched with ONE copy: [counts(4) | meas(capN) | pairs(3 capN) | z(2 capN doubles)]
-    PRE3_TRY(dmalloc(&c->ic_pred, N)); PRE3_TRY(dmalloc(&c->ic_counts, 4 + 4 * N + 4 * N + 4)); PRE3_TRY(dmalloc(&c->ic_arg, N));
-    c->ic_pairs = c->ic_counts + 4 + N;
+    PRE3_TRY(D(&c->ic_pred, N)); PRE3_TRY(D(&c->ic_counts, 4 + 4 * N + 4 * N + 4)); PRE3_TRY(D(&c->ic_arg, N));
+    c->ic_pairs = c->ic_counts + 4 + N; g.alias(&c->ic_pairs);
     PRE3_HIP(hipMemset(c->ic_counts, 0, sizeof(int32_t) * (4 + 8 * N)));
-    PRE3_TRY(dmalloc(&c->ic_newk2, N)); PRE3_TRY(dmalloc(&c->ic_best, N)); PRE3_TRY(dmalloc(&c->ic_second, N)); PRE3_TRY(dmalloc(&c->bank_src, N));
+    PRE3_TRY(D(&c->ic_newk2, N)); PRE3_TRY(D(&c->ic_best, N)); PRE3_TRY(D(&c->ic_second, N)); PRE3_TRY(D(&c->bank_src, N));
     PRE3_HIP(hipMemset(c->bank, 0, sizeof(double) * N * DESC_DIM));
     const size_t blk_bytes = (sizeof(int32_t) * (4 + 4 * N) + sizeof(double) * 2 * N + 15) & ~(size_t)15;
-    PRE3_HIP(hipHostMalloc(&c->ic_result_host, blk_bytes, hipHostMallocMapped));
+    PRE3_TRY(g.pin(&c->ic_result_host, blk_bytes, PIN_MAPPED));
+    g.alias(&c->ic_result_host_dev);
     PRE3_HIP(hipHostGetDevicePointer(&c->ic_result_host_dev, c->ic_result_host, 0));
+    g.commit();
     return PRE3_OK;
 }
 
@@ -965,28 +977,13 @@ bool pre3::desc_copy_checked(double *dst, const double *src, size_t count) { ret
 // context's stream and calls stage_release.
 int pre3::stage_acquire(pre3_ctx *c, size_t bytes, void **host, void **dev, int *slot)
 {
-    if (c->up_stage_bytes < bytes) {
-        for (int k = 0; k < 2; ++k) {
-            if (c->up_stage_used[k]) PRE3_TRY(stage_wait(c, k));
-            if (c->up_stage[k]) (void)hipHostFree(c->up_stage[k]);
-            c->up_stage[k] = nullptr; c->up_stage_used[k] = false;
-        }
-        c->up_stage_bytes = 0;
-        const size_t cap = (bytes + 65535) & ~(size_t)65535;
-        for (int k = 0; k < 2; ++k) {
-            PRE3_HIP(hipHostMalloc(&c->up_stage[k], cap, hipHostMallocMapped));
-        }
-        c->up_stage_bytes = cap;
-    }
-    const int k = c->up_stage_next; c->up_stage_next ^= 1;
-    if (c->up_stage_used[k]) PRE3_TRY(stage_wait(c, k));
-    *host = c->up_stage[k]; *slot = k;
-    PRE3_HIP(hipHostGetDevicePointer(dev, c->up_stage[k], 0));
+    PRE3_TRY(c->mem.up_ring.acquire(bytes, (bytes + 65535) & ~(size_t)65535, host, slot));
+    PRE3_HIP(hipHostGetDevicePointer(dev, *host, 0));
     return PRE3_OK;
 }
 int pre3::stage_release(pre3_ctx *c, int slot)        // (the pull launched with stage_done(c, slot) announces itself)
 {
-    c->up_stage_used[slot] = true;
+    c->mem.up_ring.release(slot);
     return PRE3_OK;
 }
 
@@ -1052,18 +1049,17 @@ static int scan_reserve(pre3_ctx *c, int K2, bool *grew)
     if (grew) *grew = false;
     if (K2 > c->scan_cap) {
         PRE3_TRY(stream_drain(c, __func__));             // (the buffers being replaced may still be read by queued kernels)
-        if (c->scan_desc) (void)hipFree(c->scan_desc);
-        if (c->scan_pos) (void)hipFree(c->scan_pos);
-        if (c->ic_pb) (void)hipFree(c->ic_pb);
-        if (c->ic_ps) (void)hipFree(c->ic_ps);
-        if (c->ic_pa) (void)hipFree(c->ic_pa);
+        CtxMemory &m = c->mem;
+        for (DevBlock *b : { &m.scan_desc, &m.scan_pos, &m.ic_pb, &m.ic_ps, &m.ic_pa }) b->release();      // all five first: the peak does not rise
         c->scan_desc = c->scan_pos = nullptr; c->ic_pb = c->ic_ps = nullptr; c->ic_pa = nullptr; c->scan_cap = 0; c->ic_pcap = 0;
         const int cap = round_up(K2, 256);
-        PRE3_TRY(dmalloc(&c->scan_desc, (size_t)cap * DESC_DIM)); PRE3_TRY(dmalloc(&c->scan_pos, (size_t)cap * 4));
         const size_t np = std::max((size_t)(cap / 64) * c->capN, (size_t)64 * c->capN);     // [scan_cap/64][capN] for the 64-wide tiles; the fused route: [capN][64 column tiles of 32]
-        c->ic_pcap = np;
-        PRE3_TRY(dmalloc(&c->ic_pb, np)); PRE3_TRY(dmalloc(&c->ic_ps, np)); PRE3_TRY(dmalloc(&c->ic_pa, np));
-        c->scan_cap = cap;
+        const size_t b_desc = sizeof(double) * cap * DESC_DIM, b_pos = sizeof(double) * cap * 4, b_d = sizeof(double) * np, b_i = sizeof(int32_t) * np;
+        PRE3_TRY(m.scan_desc.reserve(b_desc, b_desc, Zero::sync())); PRE3_TRY(m.scan_pos.reserve(b_pos, b_pos, Zero::sync()));
+        PRE3_TRY(m.ic_pb.reserve(b_d, b_d, Zero::sync())); PRE3_TRY(m.ic_ps.reserve(b_d, b_d, Zero::sync())); PRE3_TRY(m.ic_pa.reserve(b_i, b_i, Zero::sync()));
+        c->scan_desc = m.scan_desc.as<double>(); c->scan_pos = m.scan_pos.as<double>();
+        c->ic_pb = m.ic_pb.as<double>(); c->ic_ps = m.ic_ps.as<double>(); c->ic_pa = m.ic_pa.as<int32_t>();
+        c->ic_pcap = np; c->scan_cap = cap;
         if (grew) *grew = true;
     }
     return PRE3_OK;
@@ -1386,12 +1382,12 @@ int pre3_update_ell(int device, int dtype, int n, int r, const double *x, const 
         }
         if (hipMemcpy(c->row_nu, nu.data(), sizeof(double) * r_pad, hipMemcpyHostToDevice) != hipSuccess) { rc = PRE3_E_HIP; break; }
         if (R) {
-            if ((rc = dmalloc_bytes(&c->Rdense, (size_t)r * r * c->esz)) != PRE3_OK) break;
+            if ((rc = dmalloc_bytes(c, &c->Rdense, (size_t)r * r * c->esz)) != PRE3_OK) break;
             if (dtype == PRE3_F64) { if (hipMemcpy(c->Rdense, R, sizeof(double) * r * r, hipMemcpyHostToDevice) != hipSuccess) { rc = PRE3_E_HIP; break; } }
             else { std::vector<float> rf(R, R + (size_t)r * r); if (hipMemcpy(c->Rdense, rf.data(), sizeof(float) * rf.size(), hipMemcpyHostToDevice) != hipSuccess) { rc = PRE3_E_HIP; break; } }
         }
         void *Kt = nullptr;
-        if (K_out) { if ((rc = dmalloc_bytes(&Kt, (size_t)r_pad * c->ldw * c->esz)) != PRE3_OK) break; }
+        if (K_out) { if ((rc = dmalloc_bytes(c, &Kt, (size_t)r_pad * c->ldw * c->esz)) != PRE3_OK) break; }
         rc = run_update(c, PRE3_X_K_KM1, r, R != nullptr, Kt);
         if (rc == PRE3_OK) { c->x_valid[PRE3_X_K_K] = true; c->p_which = PRE3_X_K_K; rc = pre3_get_state(c, PRE3_X_K_K, n, x_out, P_out); }
         if (rc == PRE3_OK && K_out) {
@@ -1404,7 +1400,6 @@ int pre3_update_ell(int device, int dtype, int n, int r, const double *x, const 
                 else for (size_t i = 0; i < kf.size(); ++i) K_out[i] = kf[i];
             }
         }
-        if (Kt) (void)hipFree(Kt);
     } while (0);
     pre3_destroy(c);
     return rc;
@@ -1616,6 +1611,15 @@ int pre3_bench_downdate(pre3_ctx *c, int r, int reps, double *ms_per_launch_out)
     float ms = 0; PRE3_HIP(hipEventElapsedTime(&ms, c->t0, c->t1));
     if (ms_per_launch_out) *ms_per_launch_out = ms / reps;
     c->kt.enabled = was;
+    return PRE3_OK;
+}
+
+// ---- test hook (pre3_test_hooks.h; inert without PRE3_TEST_HOOKS=1): what the seam of pre3_own.h has allocated and not freed
+int pre3_test_live_blocks(int64_t out[4])
+{
+    PRE3_CHECK(knob::test_hooks(), PRE3_E_STATE, "pre3_test_live_blocks: test hooks are off (PRE3_TEST_HOOKS=1 enables them)");
+    PRE3_CHECK(out != nullptr, PRE3_E_ARG, "pre3_test_live_blocks: null pointer");
+    for (int k = 0; k < 4; ++k) out[k] = g_live[k].load(std::memory_order_relaxed);
     return PRE3_OK;
 }
 

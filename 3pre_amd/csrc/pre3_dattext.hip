@@ -156,20 +156,20 @@ __global__ __launch_bounds__(PB) void k_dat_parse(const char *__restrict__ text,
 // the power-of-five table: computed once on the host, uploaded once per device
 std::mutex g_table_mu;
 std::vector<uint64_t> g_table_host;
-uint64_t *g_table_dev[64] = {};
+DevBlock g_table_dev[64];
 
 int table_on_device(int device, const uint64_t **out)
 {
     std::lock_guard<std::mutex> lk(g_table_mu);
     PRE3_CHECK(device >= 0 && device < 64, PRE3_E_ARG, "the .dat text parse keeps a table for devices 0 .. 63, not %d", device);
-    if (g_table_dev[device] == nullptr) {
+    DevBlock &t = g_table_dev[device];
+    if (t.p == nullptr) {
         if (g_table_host.empty()) { g_table_host.resize(2 * (size_t)DAT_TABLE_ROWS); dat_build_table(g_table_host.data()); }
-        uint64_t *p = nullptr;
-        PRE3_HIP(hipMalloc((void **)&p, sizeof(uint64_t) * g_table_host.size()));
-        PRE3_HIP(hipMemcpy(p, g_table_host.data(), sizeof(uint64_t) * g_table_host.size(), hipMemcpyHostToDevice));
-        g_table_dev[device] = p;
+        const size_t bytes = sizeof(uint64_t) * g_table_host.size();
+        PRE3_TRY(t.reserve(bytes, bytes, Zero::none()));
+        if (hipMemcpy(t.p, g_table_host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { t.release(); set_error("the .dat text parse: table upload failed"); return PRE3_E_HIP; }
     }
-    *out = g_table_dev[device];
+    *out = t.as<uint64_t>();
     return PRE3_OK;
 }
 

@@ -24,6 +24,7 @@ struct FastState {
     uint16_t *map = nullptr; size_t map_px = 0;  // per pixel of the rectangle, column-major: bit 15 = listed, bits 0..14 = score
     double *blk = nullptr, *blk_host = nullptr;
     hipEvent_t ev[2] = { nullptr, nullptr }; bool ev_valid = false;    // pre3_kernel_timing: the bracket of the last call's launches
+    struct { BlockList fixed; DevBlock map; } mem;   // the owners: blk and blk_host sit on `fixed`, the map grows with the rectangle
 };
 constexpr size_t FAST_BLK_DOUBLES = FAST_RES + (size_t)PRE3_FAST_MAX_CORNERS;
 constexpr size_t FAST_O_STRIPS = 4, FAST_O_UV = FAST_O_STRIPS + FAST_MAX_STRIPS, FAST_O_SCORE = FAST_O_UV + 2 * (size_t)PRE3_FAST_MAX_CORNERS,

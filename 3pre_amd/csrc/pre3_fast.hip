@@ -246,9 +246,6 @@ void free_fast(pre3_ctx *c)
 {
     FastState *f = c->fast;
     if (!f) return;
-    if (f->map) (void)hipFree(f->map);
-    if (f->blk) (void)hipFree(f->blk);
-    if (f->blk_host) (void)hipHostFree(f->blk_host);
     for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
     delete f;
     c->fast = nullptr;
@@ -261,17 +258,18 @@ static int ensure_fast(pre3_ctx *c, const char *who, size_t px)
     if (!c->fast) {
         FastState *f = new (std::nothrow) FastState;
         PRE3_CHECK(f != nullptr, PRE3_E_NOMEM, "%s: out of host memory", who);
+        // the state is the group: the context takes it complete, or it goes with what it allocated
+        int rc = f->mem.fixed.dev(&f->blk, FAST_BLK_BYTES, Zero::none());
+        if (rc == PRE3_OK) rc = f->mem.fixed.pin(&f->blk_host, FAST_BLK_BYTES, PIN_DEFAULT);
+        if (rc != PRE3_OK) { delete f; return rc; }
         c->fast = f;
-        const bool ok = hipMalloc((void **)&f->blk, FAST_BLK_BYTES) == hipSuccess && hipHostMalloc((void **)&f->blk_host, FAST_BLK_BYTES, hipHostMallocDefault) == hipSuccess;
-        if (!ok) { free_fast(c); set_error("%s: device allocation failed", who); return PRE3_E_NOMEM; }
     }
     FastState *f = c->fast;
     if (f->map_px < px) {
         PRE3_TRY(stream_drain(c, who));
-        if (f->map) (void)hipFree(f->map);
         f->map = nullptr; f->map_px = 0;
-        PRE3_HIP(hipMalloc((void **)&f->map, sizeof(uint16_t) * px));
-        f->map_px = px;
+        PRE3_TRY(f->mem.map.reserve(sizeof(uint16_t) * px, sizeof(uint16_t) * px, Zero::none()));
+        f->map = f->mem.map.as<uint16_t>(); f->map_px = px;
     }
     return PRE3_OK;
 }

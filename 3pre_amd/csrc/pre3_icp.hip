@@ -374,19 +374,13 @@ __global__ void k_icp_final(IcpHead *h)
 
 // ---- host side
 std::mutex g_pin_mu;
-void *g_pin = nullptr; size_t g_pin_bytes = 0;          // the library's pinned block of ICP results, grown on demand, held by one run at a time
+PinBlock g_pin;                                         // the library's pinned block of ICP results, grown on demand, held by one run at a time
 
 int pin_reserve(IcpJob *job, size_t bytes)
 {
     job->pin_lock = std::unique_lock<std::mutex>(g_pin_mu);
-    if (g_pin_bytes < bytes) {
-        if (g_pin) (void)hipHostFree(g_pin);
-        g_pin = nullptr; g_pin_bytes = 0;
-        const size_t cap = (bytes + bytes / 4 + 65535) & ~(size_t)65535;
-        PRE3_HIP(hipHostMalloc(&g_pin, cap, hipHostMallocPortable));      // (one block for every device's runs)
-        g_pin_bytes = cap;
-    }
-    job->pin = (char *)g_pin;
+    PRE3_TRY(g_pin.reserve(bytes, (bytes + bytes / 4 + 65535) & ~(size_t)65535, PIN_PORTABLE));      // (one block for every device's runs)
+    job->pin = g_pin.as<char>();
     return PRE3_OK;
 }
 

@@ -9,6 +9,7 @@
 
 #include "../../include/pre3.h"
 #include "pre3_knobs.h"
+#include "pre3_own.h"
 
 namespace pre3 {
 
@@ -125,6 +126,16 @@ struct Carried {
 };
 
 namespace pre3 { struct PatchState; struct FastState; }
+// Every device and pinned block of a context (pre3_own.h).  `fixed`: what lives as long as the context and never grows -- the
+// typed pointers of pre3_ctx point into it.  The rest grows on demand.  pre3_destroy releases all of it by assigning an empty one.
+struct CtxMemory {
+    pre3::BlockList fixed;
+    pre3::StageRing up_ring, map_ring;                          // pinned staging of uploads (mailbox words 16, 17) and of map management (18, 19)
+    pre3::DevBlock scan_desc, scan_pos, ic_pb, ic_ps, ic_pa;    // scan_reserve
+    pre3::DevBlock mset_dev; pre3::PinBlock mset_host;          // read_marginal: the index-set block and its pinned image, grown with k
+    pre3::DevBlock plane_buf;                                   // pre3_heading_from_scan's work block
+    pre3::DevBlock pol_dev; pre3::PinBlock pol_host;            // the map policy's scratch and its mapped result block
+};
 struct pre3_ctx {
     int device = 0, dtype = PRE3_F32;
     size_t esz = 4;
@@ -198,17 +209,14 @@ struct pre3_ctx {
     // map management (allocated on first use)
     void *P_alt = nullptr; double *x_alt = nullptr; int32_t *map_col = nullptr; void *map_val = nullptr; int32_t *map_desc = nullptr; int32_t *map_src0 = nullptr; double *map_conv = nullptr;
     double *map_feat = nullptr; int32_t *map_flags = nullptr;
-    void *map_stage[2] = { nullptr, nullptr }; hipEvent_t map_stage_ev[2] = { nullptr, nullptr }; bool map_stage_used[2] = { false, false };
-    int map_stage_next = 0; size_t map_stage_bytes = 0;   // pinned staging blocks of the map operations (pre3_map.hip)
+    bool map_ready = false;                       // ensure_map_buffers' group is complete
     std::vector<int32_t> lm_type_host;
     // IC search (matching_sift_based.m): landmark descriptor bank [capN][128], the current scan's SIFT set, match scratch
-    double *bank = nullptr, *bank_alt = nullptr; bool bank_set = false;
+    double *bank = nullptr, *bank_alt = nullptr; bool bank_set = false; bool ic_ready = false;      // ic_ready: ensure_ic_buffers' group is complete
     double *scan_desc = nullptr, *scan_pos = nullptr; int scan_K2 = 0, scan_cap = 0;
-    // pinned staging of host arrays on their way to the device (the per-frame scan, descriptors of new landmarks): two blocks used alternately,
-    // an event each; the caller's data is copied (and bounds-checked) into a block, the device pulls it over PCIe on the context's stream --
+    // pinned staging of host arrays on their way to the device (the per-frame scan, descriptors of new landmarks): mem.up_ring's two blocks, used
+    // alternately; the caller's data is copied (and bounds-checked) into a block, the device pulls it over PCIe on the context's stream --
     // no synchronisation, no read-back (pre3_api.hip: stage_acquire / stage_release)
-    void *up_stage[2] = { nullptr, nullptr }; hipEvent_t up_stage_ev[2] = { nullptr, nullptr }; bool up_stage_used[2] = { false, false };
-    int up_stage_next = 0; size_t up_stage_bytes = 0;
     int32_t stage_seq[4] = { 0, 0, 0, 0 };          // sequence number of the last pull of staging block k (0, 1: uploads; 2, 3: map management)
     void *ic_result_host = nullptr, *ic_result_host_dev = nullptr; int32_t seq_ic = 0;    // the IC search's result block in mapped pinned memory: written by the device, announced through mailbox word 12
     int32_t *ic_pred = nullptr, *ic_counts = nullptr, *ic_arg = nullptr, *ic_pairs = nullptr, *ic_newk2 = nullptr; double *ic_best = nullptr, *ic_second = nullptr;
@@ -243,24 +251,23 @@ struct pre3_ctx {
     bool step_tail = false;                       // PRE3_OPT_STEP_TAIL (default: the environment's PRE3_TAIL, else off)
     // marginal readers (pre3_get_landmarks / pre3_get_marginal, pre3_map.hip), allocated on first use: device results and their pinned host image;
     // the landmark block is sized by the map capacity, the index-set block grows with k
-    double *lmr_dev = nullptr, *lmr_host = nullptr;
-    void *mset_dev = nullptr, *mset_host = nullptr; size_t mset_bytes = 0;
+    double *lmr_dev = nullptr, *lmr_host = nullptr; bool lmr_ready = false;
     // pre3_update_rows / pre3_heading_update (pre3_rows.hip), allocated on first use: the rows block and H*P (RMAX x ld, fp64)
-    pre3::RowsBlock *rows_blk = nullptr; double *rows_hp = nullptr;
+    pre3::RowsBlock *rows_blk = nullptr; double *rows_hp = nullptr; bool rows_ready = false;
     int rows_form = 0;                            // PRE3_OPT_ROWS_FORM: 1 the single-sweep form, 0 run_update
     // pre3_heading_from_scan (pre3_plane.hip), allocated on first use: [points | draws | scores | result] and the block the heading rows read
-    void *plane_buf = nullptr; size_t plane_bytes = 0; pre3::HeadingSrc *plane_src = nullptr;
+    pre3::HeadingSrc *plane_src = nullptr;
     // features_info bookkeeping and the map policy (pre3_set_book / pre3_map_policy, pre3_map.hip).  A booked context carries
     // [capN][4] int32 (times_predicted, times_measured, init_frame, last_visible) through every map call; book_vis[i] = has_h || visible at x_k_k
     // after the LI update, recorded where the reference's rescue projects (pre3_step / pre3_step_predicted / pre3_rescue), cleared by every map call
     bool booked = false; int book_s = 0;          // book_s: init_frame / last_visible of landmarks a map call adds (the last policy call's step - 1)
-    int32_t *book = nullptr, *book_alt = nullptr, *book_vis = nullptr;
-    void *pol_dev = nullptr; size_t pol_dev_bytes = 0;                     // policy scratch: candidates, per-landmark flags and projections, blocked[K]
-    int32_t *pol_host = nullptr, *pol_host_dev = nullptr; size_t pol_host_bytes = 0;   // the result block in mapped pinned memory
+    int32_t *book = nullptr, *book_alt = nullptr, *book_vis = nullptr; bool book_ready = false;
+    int32_t *pol_host = nullptr, *pol_host_dev = nullptr;                  // the policy's result block (mem.pol_host) and its device address
     // the patch branch of the IC search (pre3_patch.hip), allocated on first use: the resident image, the patch bank, the warped patches
     pre3::PatchState *patch = nullptr;
     // FAST-9 corners on the resident image (pre3_fast.hip), allocated on first use: the verdict map and the result block
     pre3::FastState *fast = nullptr;
+    CtxMemory mem;
 };
 
 namespace pre3 {
@@ -289,7 +296,7 @@ struct EntryScope {
 };
 int flush_unless_kept(pre3_ctx *c);      /* a pending rows/cols 3..6 pass, then a pending HI down-date, out unless this call keeps them */
 void drop_carried(pre3_ctx *c);          /* the deferred work of a state that is being replaced is dropped, not run */
-int dmalloc_bytes(void **p, size_t bytes);
+template <typename T> int dmalloc_bytes(pre3_ctx *c, T **p, size_t bytes) { return c->mem.fixed.dev(p, bytes ? bytes : 16, Zero::sync()); }      /* a zeroed block on the context's fixed list (at least 16 bytes) */
 int wait_mail(pre3_ctx *c, int slot, int32_t seq);      /* poll the pinned mailbox until the kernel launched with `seq` has published in word `slot` */
 int stats_words(pre3_ctx *c);            /* the device's error words, once a copy of them into pinned_stats has completed */
 const char *numeric_word_message(int32_t word);      /* what a non-zero numeric error word (stats[6]) says: the factorisation's, or a refused VO pair's (pre3_predictu.h) */
@@ -390,16 +397,12 @@ int launch_ransac_select_impl(pre3_ctx *c, int n_draw, int k, int early_exit, in
 // device, null: none) applied by the reading launch itself; results into the caller's host arrays (any may be null).  Arguments checked by the caller.
 int read_landmarks(pre3_ctx *c, int which, int first, int count, double *xyz, double *cov_xyz, double *cov_native, double *linearity);
 int read_marginal(pre3_ctx *c, int which, int k, const int32_t *idx, const double *jn, double *x_out, double *P_out);
-void free_readers(pre3_ctx *c);
 
 // ---- small-rank update on the resident x_k_k / p_k_k (pre3_rows.hip): rows from the host block, or (rows == null) the heading rows built on the device
 // from x_k_k(4:7) behind the gate of hd.  Two launches, P swept once.  rows_applied: the gate word into host memory, on the stream (caller drains).
 int launch_rows_update(pre3_ctx *c, const RowsBlock *rows, const RowsHeading *hd);
 int rows_applied(pre3_ctx *c, int32_t *applied_host);
-void free_rows(pre3_ctx *c);
 
-// ---- the floor-plane fit behind pre3_heading_from_scan (pre3_plane.hip)
-void free_plane(pre3_ctx *c);
 int stage_acquire(pre3_ctx *c, size_t bytes, void **host, void **dev, int *slot);      /* pre3_api.hip: a pinned staging block of the context ... */
 int stage_release(pre3_ctx *c, int slot);                                              /* ... handed to the pull queued with launch_pull(.., slot) */
 
@@ -459,7 +462,6 @@ bool desc_copy_checked(double *dst, const double *src, size_t count);
 
 // ---- map policy (pre3_map.hip): the rescue-visibility rider of a booked context (one small launch at the post-LI x_k_k), buffers
 int launch_book_vis(pre3_ctx *c);
-void free_policy(pre3_ctx *c);
 
 int run_hypothesis_support(int n, const double *xi, const pre3_cam &cam, int n_id, const int32_t *i1, const int32_t *i2, const int32_t *i3,
                            const double *z_id, int n_euc, const int32_t *i4, const double *z_euc, double threshold, int32_t *out_host /* [1 + n_id + n_euc] */);

@@ -356,24 +356,23 @@ __global__ void k_map_add_noise(int n_feat, int first_off, const double *__restr
 
 static int ensure_map_buffers(pre3_ctx *c)
 {
-    if (c->P_alt) return PRE3_OK;
-    auto bytes = [&](void **p, size_t b) { return hipMalloc(p, b ? b : 16) == hipSuccess; };
-    bool ok = bytes(&c->P_alt, (size_t)c->ld * c->ld * c->esz) && bytes((void **)&c->x_alt, sizeof(double) * c->capn) &&
-              bytes((void **)&c->map_col, sizeof(int32_t) * (size_t)c->capn * MAPW) && bytes(&c->map_val, c->esz * (size_t)c->capn * MAPW) &&
-              bytes((void **)&c->map_desc, sizeof(int32_t) * (3 * (size_t)c->capn + 3 * (size_t)c->capN + 16) + sizeof(double) * 3 * (size_t)c->capN + 16) &&
-              bytes((void **)&c->map_feat, sizeof(double) * (size_t)c->capN * (FEATW > CONVW ? FEATW : CONVW)) &&
-              bytes((void **)&c->map_flags, sizeof(int32_t) * c->capN) && bytes((void **)&c->map_src0, sizeof(int32_t) * (size_t)c->ld) &&
-              bytes((void **)&c->map_conv, sizeof(double) * (size_t)c->capN * CONVW);
-    if (!ok) { set_error("map management: device allocation failed"); return PRE3_E_NOMEM; }
-    // two pinned staging blocks ([desc | types | off | src | uvd, rho]: ONE upload per call), used alternately: a block is written again only
-    // after the call before last has been consumed (its event), so a call does not end in a stream synchronisation
-    c->map_stage_bytes = (sizeof(int32_t) * (3 * (size_t)c->capn + 3 * (size_t)c->capN + 16) + sizeof(double) * 3 * (size_t)c->capN + 15) & ~(size_t)15;
-    for (int k = 0; k < 2; ++k) {
-        if (hipHostMalloc(&c->map_stage[k], c->map_stage_bytes, hipHostMallocMapped) != hipSuccess || hipEventCreateWithFlags(&c->map_stage_ev[k], hipEventDisableTiming) != hipSuccess) {
-            set_error("map management: pinned staging allocation failed"); return PRE3_E_NOMEM;
-        }
-    }
+    if (c->map_ready) return PRE3_OK;
+    Group g(c->mem.fixed, c->map_ready);      // complete, or gone with its pointers null: a call after a failed one starts over
+    auto bytes = [&](auto **p, size_t b) { return g.dev(p, b ? b : 16, Zero::none()); };      // (none is zeroed: P_alt at N = 2000 is 580 MB)
+    PRE3_TRY(bytes(&c->P_alt, (size_t)c->ld * c->ld * c->esz)); PRE3_TRY(bytes(&c->x_alt, sizeof(double) * c->capn));
+    PRE3_TRY(bytes(&c->map_col, sizeof(int32_t) * (size_t)c->capn * MAPW)); PRE3_TRY(bytes(&c->map_val, c->esz * (size_t)c->capn * MAPW));
+    PRE3_TRY(bytes(&c->map_desc, sizeof(int32_t) * (3 * (size_t)c->capn + 3 * (size_t)c->capN + 16) + sizeof(double) * 3 * (size_t)c->capN + 16));
+    PRE3_TRY(bytes(&c->map_feat, sizeof(double) * (size_t)c->capN * (FEATW > CONVW ? FEATW : CONVW)));
+    PRE3_TRY(bytes(&c->map_flags, sizeof(int32_t) * c->capN)); PRE3_TRY(bytes(&c->map_src0, sizeof(int32_t) * (size_t)c->ld));
+    PRE3_TRY(bytes(&c->map_conv, sizeof(double) * (size_t)c->capN * CONVW));
+    g.commit();
     return PRE3_OK;
+}
+// the map ring's one capacity ([desc | types | off | src | uvd, rho]: ONE upload per call).  Its two blocks are used alternately: a block is written
+// again only after the call before last has been consumed, so a call does not end in a stream synchronisation
+static size_t map_stage_bytes(const pre3_ctx *c)
+{
+    return (sizeof(int32_t) * (3 * (size_t)c->capn + 3 * (size_t)c->capN + 16) + sizeof(double) * 3 * (size_t)c->capN + 15) & ~(size_t)15;
 }
 
 // apply the state map described by desc (3 ints per new row), then install the new landmark table.  uvd_rho: 3 n_feat doubles ([u v] per new
@@ -390,9 +389,10 @@ static int apply_map(pre3_ctx *c, const std::vector<int32_t> &desc, int n_new, c
     for (int i = 0; i < N; ++i) { off[i] = n; n += new_types[i] == PRE3_INVDEPTH ? 6 : 3; }
     PRE3_CHECK(n == n_new, PRE3_E_STATE, "map management: internal size mismatch (%d vs %d)", n, n_new);
     // ---- stage: [desc 3 n_new | types N | off N | src N | pad to 8 bytes | uvd 2 n_feat, rho n_feat]
-    const int k = c->map_stage_next; c->map_stage_next ^= 1;
-    if (c->map_stage_used[k]) PRE3_TRY(stage_wait(c, 2 + k));
-    int32_t *st = static_cast<int32_t *>(c->map_stage[k]);
+    StageRing &ring = c->mem.map_ring;
+    void *st_v = nullptr; int k = 0;
+    PRE3_TRY(ring.acquire(map_stage_bytes(c), map_stage_bytes(c), &st_v, &k));
+    int32_t *st = static_cast<int32_t *>(st_v);
     const size_t o_types = desc.size(), o_off = o_types + (size_t)N, o_src = o_off + (size_t)N, o_end = (o_src + (size_t)N + 1) & ~(size_t)1;
     memcpy(st, desc.data(), sizeof(int32_t) * desc.size());
     if (N) { memcpy(st + o_types, new_types.data(), sizeof(int32_t) * N); memcpy(st + o_off, off.data(), sizeof(int32_t) * N); memcpy(st + o_src, lm_src.data(), sizeof(int32_t) * N); }
@@ -402,9 +402,9 @@ static int apply_map(pre3_ctx *c, const std::vector<int32_t> &desc, int n_new, c
         memcpy(sd, uvd, sizeof(double) * 2 * n_feat); memcpy(sd + 2 * n_feat, rho0, sizeof(double) * n_feat);
         bytes += sizeof(double) * 3 * (size_t)n_feat;
     }
-    PRE3_CHECK(bytes <= c->map_stage_bytes, PRE3_E_ARG, "map management: staging block too small");
-    PRE3_TRY(launch_pull(c, st, c->map_desc, bytes, 2 + k));        // (read over PCIe by the device: no DMA-engine copy; announces itself: no event)
-    c->map_stage_used[k] = true;
+    PRE3_CHECK(bytes <= ring.cap, PRE3_E_ARG, "map management: staging block too small");
+    PRE3_TRY(launch_pull(c, st, c->map_desc, bytes, ring.base + k));        // (read over PCIe by the device: no DMA-engine copy; announces itself: no event)
+    ring.release(k);
     const int32_t *d_types = c->map_desc + o_types, *d_off = c->map_desc + o_off, *d_src = c->map_desc + o_src;
     if (n_feat > 0) {
         const double *d_uvd = reinterpret_cast<const double *>(c->map_desc + o_end);
@@ -600,10 +600,11 @@ __global__ __launch_bounds__(256) void k_read_marginal(int k, const int32_t *__r
 int read_landmarks(pre3_ctx *c, int which, int first, int count, double *xyz, double *cov_xyz, double *cov_native, double *linearity)
 {
     if (count <= 0 || (!xyz && !cov_xyz && !cov_native && !linearity)) return PRE3_OK;
-    if (c->lmr_dev == nullptr) {
+    if (!c->lmr_ready) {
         const size_t bytes = sizeof(double) * LMR_W * (size_t)std::max(c->capN, 1);
-        if (hipMalloc((void **)&c->lmr_dev, bytes) != hipSuccess) { c->lmr_dev = nullptr; set_error("pre3_get_landmarks: device allocation failed"); return PRE3_E_NOMEM; }
-        if (hipHostMalloc((void **)&c->lmr_host, bytes, 0) != hipSuccess) { c->lmr_host = nullptr; (void)hipFree(c->lmr_dev); c->lmr_dev = nullptr; set_error("pre3_get_landmarks: pinned allocation failed"); return PRE3_E_NOMEM; }
+        Group g(c->mem.fixed, c->lmr_ready);
+        PRE3_TRY(g.dev(&c->lmr_dev, bytes, Zero::none())); PRE3_TRY(g.pin(&c->lmr_host, bytes, PIN_DEFAULT));
+        g.commit();
     }
     const PendW pw = pend_args(c);
     const double *x = which == PRE3_X_K_K ? c->x_kk : c->x_km1;
@@ -629,15 +630,9 @@ int read_marginal(pre3_ctx *c, int which, int k, const int32_t *idx, const doubl
     if (k <= 0 || (!x_out && !P_out)) return PRE3_OK;
     const size_t o_x = ((size_t)k * sizeof(int32_t) + 15) & ~(size_t)15, o_P = o_x + sizeof(double) * (size_t)k;
     const size_t bytes = o_P + sizeof(double) * (size_t)k * (size_t)k;
-    if (bytes > c->mset_bytes) {                     // (grows with k; the call before this one has drained the stream)
-        if (c->mset_dev) (void)hipFree(c->mset_dev);
-        if (c->mset_host) (void)hipHostFree(c->mset_host);
-        c->mset_dev = c->mset_host = nullptr; c->mset_bytes = 0;
-        if (hipMalloc(&c->mset_dev, bytes) != hipSuccess) { c->mset_dev = nullptr; set_error("pre3_get_marginal: device allocation of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
-        if (hipHostMalloc(&c->mset_host, bytes, 0) != hipSuccess) { c->mset_host = nullptr; (void)hipFree(c->mset_dev); c->mset_dev = nullptr; set_error("pre3_get_marginal: pinned allocation of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
-        c->mset_bytes = bytes;
-    }
-    unsigned char *hb = static_cast<unsigned char *>(c->mset_host), *db = static_cast<unsigned char *>(c->mset_dev);
+    // (both grow with k; the call before this one has drained the stream)
+    PRE3_TRY(c->mem.mset_dev.reserve(bytes, bytes, Zero::none())); PRE3_TRY(c->mem.mset_host.reserve(bytes, bytes, PIN_DEFAULT));
+    unsigned char *hb = c->mem.mset_host.as<unsigned char>(), *db = c->mem.mset_dev.as<unsigned char>();
     memcpy(hb, idx, sizeof(int32_t) * (size_t)k);
     PRE3_HIP(hipMemcpyAsync(db, hb, sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, c->stream));
     const PendW pw = pend_args(c);
@@ -655,15 +650,6 @@ int read_marginal(pre3_ctx *c, int which, int k, const int32_t *idx, const doubl
     if (x_out) memcpy(x_out, hb + o_x, sizeof(double) * (size_t)k);
     if (P_out) memcpy(P_out, hb + o_P, sizeof(double) * (size_t)k * (size_t)k);
     return PRE3_OK;
-}
-
-void free_readers(pre3_ctx *c)
-{
-    if (c->lmr_dev) (void)hipFree(c->lmr_dev);
-    if (c->lmr_host) (void)hipHostFree(c->lmr_host);
-    if (c->mset_dev) (void)hipFree(c->mset_dev);
-    if (c->mset_host) (void)hipHostFree(c->mset_host);
-    c->lmr_dev = c->lmr_host = nullptr; c->mset_dev = c->mset_host = nullptr; c->mset_bytes = 0;
 }
 
 
@@ -878,11 +864,11 @@ int launch_book_vis(pre3_ctx *c)
 
 static int ensure_book(pre3_ctx *c)
 {
-    if (c->book) return PRE3_OK;
+    if (c->book_ready) return PRE3_OK;
     const size_t b4 = sizeof(int32_t) * 4 * (size_t)c->capN, b1 = sizeof(int32_t) * (size_t)c->capN;
-    if (hipMalloc((void **)&c->book, b4) != hipSuccess || hipMalloc((void **)&c->book_alt, b4) != hipSuccess || hipMalloc((void **)&c->book_vis, b1) != hipSuccess) {
-        free_policy(c); set_error("features_info book: device allocation failed"); return PRE3_E_NOMEM;
-    }
+    Group g(c->mem.fixed, c->book_ready);
+    PRE3_TRY(g.dev(&c->book, b4, Zero::none())); PRE3_TRY(g.dev(&c->book_alt, b4, Zero::none())); PRE3_TRY(g.dev(&c->book_vis, b1, Zero::none()));
+    g.commit();
     return PRE3_OK;
 }
 
@@ -896,15 +882,6 @@ static int start_book(pre3_ctx *c)
         c->booked = true;
     }
     return PRE3_OK;
-}
-
-void free_policy(pre3_ctx *c)
-{
-    void *d[] = { c->book, c->book_alt, c->book_vis, c->pol_dev };
-    for (void *p : d) if (p) (void)hipFree(p);
-    if (c->pol_host) (void)hipHostFree(c->pol_host);
-    c->book = c->book_alt = c->book_vis = nullptr; c->pol_dev = nullptr; c->pol_host = c->pol_host_dev = nullptr;
-    c->pol_dev_bytes = c->pol_host_bytes = 0; c->booked = false;
 }
 
 }  // namespace pre3
@@ -1136,22 +1113,20 @@ static int map_policy_impl(const char *who, pre3_ctx *c, int step, int min_featu
     const size_t fo_match = sizeof(VoPairHeader), fo_flags = fo_match + sizeof(double) * 2 * Kc, fo_part = (fo_flags + sizeof(int32_t) * Kc + 15) & ~(size_t)15;
     char *f_dev = nullptr, *f_pin = nullptr;
     if (fcq) PRE3_TRY(sr_frame_pair_work(fc->cur, fo_part + vp_match_part_bytes(K, fc->k2.n_kept), fo_part, (void **)&f_dev, (void **)&f_pin));
-    if (dev_bytes > c->pol_dev_bytes) {
-        if (c->pol_dev) (void)hipFree(c->pol_dev);
-        c->pol_dev = nullptr; c->pol_dev_bytes = 0;
-        PRE3_CHECK(hipMalloc(&c->pol_dev, dev_bytes) == hipSuccess, PRE3_E_NOMEM, "%s: device allocation of %zu bytes failed", who, dev_bytes);
-        c->pol_dev_bytes = dev_bytes;
-    }
-    if (host_bytes > c->pol_host_bytes) {
-        if (c->pol_host) (void)hipHostFree(c->pol_host);
-        c->pol_host = c->pol_host_dev = nullptr; c->pol_host_bytes = 0;
-        PRE3_CHECK(hipHostMalloc((void **)&c->pol_host, host_bytes, hipHostMallocMapped) == hipSuccess, PRE3_E_NOMEM, "%s: pinned allocation failed", who);
-        PRE3_HIP(hipHostGetDevicePointer((void **)&c->pol_host_dev, c->pol_host, 0));
-        c->pol_host_bytes = host_bytes;
+    PRE3_TRY(c->mem.pol_dev.reserve(dev_bytes, dev_bytes, Zero::none()));
+    bool new_host = false;
+    const int rc_host = c->mem.pol_host.reserve(host_bytes, host_bytes, PIN_MAPPED, &new_host);
+    if (rc_host != PRE3_OK || new_host) {               // (the typed pointers follow the block, a failed one too)
+        c->pol_host = c->mem.pol_host.as<int32_t>(); c->pol_host_dev = nullptr;
+        PRE3_TRY(rc_host);
+        if (hipHostGetDevicePointer((void **)&c->pol_host_dev, c->pol_host, 0) != hipSuccess) {
+            c->mem.pol_host.release(); c->pol_host = c->pol_host_dev = nullptr;
+            set_error("%s: the result block has no device address", who); return PRE3_E_HIP;
+        }
     }
     double *h_cand = reinterpret_cast<double *>(c->pol_host + res_words);
     for (int k = 0; k < K && !fc; ++k) { h_cand[2 * k] = cand_uv[2 * k]; h_cand[2 * k + 1] = cand_uv[2 * k + 1]; h_cand[2 * K + k] = rho[k]; }
-    double *d_cand = static_cast<double *>(c->pol_dev), *d_puv = d_cand + 3 * Kc, *d_raw = d_puv + 2 * cap, *d_keys = d_raw + 3 * Ks;
+    double *d_cand = c->mem.pol_dev.as<double>(), *d_puv = d_cand + 3 * Kc, *d_raw = d_puv + 2 * cap, *d_keys = d_raw + 3 * Ks;
     int32_t *d_del = reinterpret_cast<int32_t *>(d_keys + Ks), *d_mh = d_del + cap, *d_pvis = d_mh + cap, *d_nbook = d_pvis + cap, *d_blocked = d_nbook + 4 * cap;
     int32_t *d_order2 = fcq ? d_blocked + Kc : nullptr, *d_acc_row = fcq ? d_order2 + Kc : nullptr;
     const int32_t *d_kreal = nullptr;

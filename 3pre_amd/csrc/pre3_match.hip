@@ -1495,9 +1495,19 @@ struct MatchShard {
     DevBuf raw; int raw_stride = 0;                           // [best | second | arg] of the slice, the distance kernel's outputs live here (+ the MISSING word behind arg)
     bool missing_set = false, test_fail = false;                // (test_fail: pre3_match_shard_test_stall(s, 2) makes the next match's distance kernels "fail")
     DevBuf gathered; int gathered_world = 0;
-    double *res_host = nullptr, *res_host_dev = nullptr;      // [1 + 3 K1] + one int32 sequence word behind it
+    PinBlock res_blk; double *res_host = nullptr, *res_host_dev = nullptr;      // mapped: [1 + 3 K1] + one int32 sequence word behind it
     int32_t seq = 0;
-    ~MatchShard() { if (st) (void)hipStreamDestroy(st); if (res_host) (void)hipHostFree(res_host); }
+    ~MatchShard() { if (st) (void)hipStreamDestroy(st); }
+    int result_block(size_t nres)                             // the stream and the result block, on first use
+    {
+        if (!st) PRE3_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        if (res_host) return PRE3_OK;
+        PRE3_TRY(res_blk.reserve(sizeof(double) * nres + 64, sizeof(double) * nres + 64, PIN_MAPPED));
+        memset(res_blk.p, 0, sizeof(double) * nres + 64);
+        if (hipHostGetDevicePointer((void **)&res_host_dev, res_blk.p, 0) != hipSuccess) { res_blk.release(); set_error("match shard: the result block has no device address"); return PRE3_E_HIP; }
+        res_host = res_blk.as<double>();
+        return PRE3_OK;
+    }
 };
 
 __global__ void k_shard_pack(int K1, const double *__restrict__ b, const double *__restrict__ s2, const int32_t *__restrict__ a, double *__restrict__ out)
@@ -1667,12 +1677,7 @@ int match_shard_match(void *h, double thresh, double *pairs_out, double *score_o
     I8Match &o = sh->out();
     const int K1 = o.K1;
     const size_t nres = 1 + 3 * (size_t)K1;
-    if (!sh->st) PRE3_HIP(hipStreamCreateWithFlags(&sh->st, hipStreamNonBlocking));
-    if (!sh->res_host) {
-        PRE3_HIP(hipHostMalloc((void **)&sh->res_host, sizeof(double) * nres + 64, hipHostMallocMapped));
-        memset(sh->res_host, 0, sizeof(double) * nres + 64);
-        PRE3_HIP(hipHostGetDevicePointer((void **)&sh->res_host_dev, sh->res_host, 0));
-    }
+    PRE3_TRY(sh->result_block(nres));
     int rank = 0, world = 1;
     if (sh->comm) comm_rank_world(sh->comm, &rank, &world);
     const size_t nraw = 3 * (size_t)sh->raw_stride;
@@ -1745,12 +1750,7 @@ int match_shard_test_stall(void *h, int release)
     if (release == 2) { sh->test_fail = true; return PRE3_OK; }
     PRE3_HIP(hipSetDevice(sh->device));
     const size_t nres = 1 + 3 * (size_t)sh->out().K1;
-    if (!sh->st) PRE3_HIP(hipStreamCreateWithFlags(&sh->st, hipStreamNonBlocking));
-    if (!sh->res_host) {
-        PRE3_HIP(hipHostMalloc((void **)&sh->res_host, sizeof(double) * nres + 64, hipHostMallocMapped));
-        memset(sh->res_host, 0, sizeof(double) * nres + 64);
-        PRE3_HIP(hipHostGetDevicePointer((void **)&sh->res_host_dev, sh->res_host, 0));
-    }
+    PRE3_TRY(sh->result_block(nres));
     int32_t *mail_host = reinterpret_cast<int32_t *>(sh->res_host + nres), *mail_dev = reinterpret_cast<int32_t *>(sh->res_host_dev + nres);
     if (release) { __atomic_store_n(mail_host + 3, 1, __ATOMIC_RELEASE); return PRE3_OK; }
     __atomic_store_n(mail_host + 3, 0, __ATOMIC_RELEASE);

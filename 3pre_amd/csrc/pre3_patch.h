@@ -21,6 +21,7 @@ struct PatchState {
     double *warp = nullptr; int32_t *wstatus = nullptr;  // [capN][169], [capN]
     void *blk = nullptr, *blk_host = nullptr; size_t blk_bytes = 0;   // the search's result block and its pinned image
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr }; bool ev_valid = false;   // pre3_kernel_timing: brackets of k_patch_warp / k_patch_search
+    struct { BlockList fixed; DevBlock img; } mem;   // the owners: everything above but img sits on `fixed`; img is replaced when the camera's shape changes
 };
 
 int patch_set_image(pre3_ctx *c, int nRows, int nCols, const uint8_t *im);

@@ -387,15 +387,19 @@ static int ensure_patch(pre3_ctx *c)
     const size_t N = (size_t)(c->capN > 0 ? c->capN : 1);
     p->up_bytes = up16(N * (PATCH_BYTES + 14 * sizeof(double))) + 16;
     p->blk_bytes = up16(blk_size((int)N));
-    bool ok = hipMalloc((void **)&p->pb, N * PATCH_BYTES) == hipSuccess && hipMalloc((void **)&p->pb_alt, N * PATCH_BYTES) == hipSuccess &&
-              hipMalloc((void **)&p->meta, sizeof(double) * N * PATCH_META) == hipSuccess && hipMalloc((void **)&p->meta_alt, sizeof(double) * N * PATCH_META) == hipSuccess &&
-              hipMalloc((void **)&p->up, p->up_bytes) == hipSuccess && hipMalloc((void **)&p->warp, sizeof(double) * N * PATCH_PIX) == hipSuccess &&
-              hipMalloc((void **)&p->wstatus, sizeof(int32_t) * N) == hipSuccess && hipMalloc(&p->blk, p->blk_bytes) == hipSuccess &&
-              hipHostMalloc(&p->blk_host, p->blk_bytes, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipMemset(p->meta, 0, sizeof(double) * N * PATCH_META) == hipSuccess && hipMemset(p->meta_alt, 0, sizeof(double) * N * PATCH_META) == hipSuccess &&
-         hipMemset(p->pb, 0, N * PATCH_BYTES) == hipSuccess && hipMemset(p->pb_alt, 0, N * PATCH_BYTES) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    // the state is the group: the context takes it complete, or it goes with everything it allocated
+    BlockList &m = p->mem.fixed;
+    const Zero z = Zero::sync(), nz = Zero::none();
+    int rc = PRE3_OK;
+    auto A = [&](int r) { if (rc == PRE3_OK) rc = r; };
+    A(m.dev(&p->pb, N * PATCH_BYTES, z)); A(m.dev(&p->pb_alt, N * PATCH_BYTES, z));
+    A(m.dev(&p->meta, sizeof(double) * N * PATCH_META, z)); A(m.dev(&p->meta_alt, sizeof(double) * N * PATCH_META, z));
+    A(m.dev(&p->up, p->up_bytes, nz)); A(m.dev(&p->warp, sizeof(double) * N * PATCH_PIX, nz));
+    A(m.dev(&p->wstatus, sizeof(int32_t) * N, nz)); A(m.dev(&p->blk, p->blk_bytes, nz));
+    A(m.pin(&p->blk_host, p->blk_bytes, PIN_DEFAULT));
+    if (rc == PRE3_OK && hipDeviceSynchronize() != hipSuccess) { set_error("patch search: device allocation failed"); rc = PRE3_E_NOMEM; }
+    if (rc != PRE3_OK) { delete p; return rc; }
     c->patch = p;
-    if (!ok) { free_patch(c); set_error("patch search: device allocation failed"); return PRE3_E_NOMEM; }
     return PRE3_OK;
 }
 
@@ -403,9 +407,6 @@ void free_patch(pre3_ctx *c)
 {
     PatchState *p = c->patch;
     if (!p) return;
-    void *d[] = { p->img, p->pb, p->pb_alt, p->meta, p->meta_alt, p->up, p->warp, p->wstatus, p->blk };
-    for (void *q : d) if (q) (void)hipFree(q);
-    if (p->blk_host) (void)hipHostFree(p->blk_host);
     for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
     delete p;
     c->patch = nullptr;
@@ -430,10 +431,11 @@ static int image_reserve(pre3_ctx *c, const char *who, int nRows, int nCols)
     PatchState *p = c->patch;
     if (p->rows != nRows || p->cols != nCols || p->img == nullptr) {
         PRE3_TRY(stream_drain(c, who));
-        if (p->img) (void)hipFree(p->img);
+        p->mem.img.release();                 // (replaced for every new shape, a smaller one too)
         p->img = nullptr; p->img_set = false; p->rows = p->cols = 0;
-        PRE3_HIP(hipMalloc((void **)&p->img, up16((size_t)nRows * nCols)));
-        p->rows = nRows; p->cols = nCols;
+        const size_t bytes = up16((size_t)nRows * nCols);
+        PRE3_TRY(p->mem.img.reserve(bytes, bytes, Zero::none()));
+        p->img = p->mem.img.as<uint8_t>(); p->rows = nRows; p->cols = nCols;
     }
     return PRE3_OK;
 }

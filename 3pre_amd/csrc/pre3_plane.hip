@@ -488,58 +488,25 @@ static int plane_read_back(const PlaneJob &j, const char *buf, int32_t *count_ou
 }
 
 // pinned staging of the stateless entry point: one block per process, grown on demand, held for the length of a call
-struct PlaneStage {
-    void *p = nullptr; size_t cap = 0; std::mutex mu;
-    ~PlaneStage() { if (p) (void)hipHostFree(p); }
-};
-static PlaneStage g_stage;
-
-static int stage_reserve(size_t bytes)      // (the caller holds g_stage.mu)
-{
-    if (g_stage.cap >= bytes) return PRE3_OK;
-    if (g_stage.p) (void)hipHostFree(g_stage.p);
-    g_stage.p = nullptr; g_stage.cap = 0;
-    const size_t cap = (bytes + 65535) & ~(size_t)65535;
-    PRE3_HIP(hipHostMalloc(&g_stage.p, cap, hipHostMallocDefault));
-    g_stage.cap = cap;
-    return PRE3_OK;
-}
+static PinBlock g_stage; static std::mutex g_stage_mu;      // (whoever touches g_stage holds g_stage_mu)
 
 struct StreamIdle {             // a work block fed from a handle's stream goes back to its pool only once that stream is idle, on every way out
     hipStream_t st;
     ~StreamIdle() { if (st) (void)hipStreamSynchronize(st); }
 };
 
-// a block of the context: zeroed on the context's stream, which does not synchronise with the null stream
-static int plane_dmalloc(pre3_ctx *c, void **p, size_t bytes)
-{
-    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; set_error("hipMalloc of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
-    PRE3_HIP(hipMemsetAsync(*p, 0, bytes, c->stream));
-    return PRE3_OK;
-}
-
-// the context's work block [points | draws | scores | result | mask | flag], grown on demand, and the block the heading rows read
+// the context's work block [points | draws | scores | result | mask | flag], grown on demand, and the block the heading rows read: both zeroed on the
+// context's stream, which does not synchronise with the null stream
 static int plane_reserve(pre3_ctx *c, const char *who, size_t bytes)
 {
-    if (c->plane_bytes < bytes) {
-        if (c->plane_buf) { PRE3_TRY(stream_drain(c, who)); (void)hipFree(c->plane_buf); }
-        c->plane_buf = nullptr; c->plane_bytes = 0;
-        const size_t cap = bytes + bytes / 4;
-        PRE3_TRY(plane_dmalloc(c, &c->plane_buf, cap));
-        c->plane_bytes = cap;
-    }
-    if (c->plane_src == nullptr) { void *p = nullptr; PRE3_TRY(plane_dmalloc(c, &p, sizeof(HeadingSrc))); c->plane_src = (HeadingSrc *)p; }
+    DevBlock &buf = c->mem.plane_buf;
+    if (buf.p && buf.bytes < bytes) PRE3_TRY(stream_drain(c, who));
+    PRE3_TRY(buf.reserve(bytes, bytes + bytes / 4, Zero::on_stream(c->stream)));
+    if (c->plane_src == nullptr) PRE3_TRY(c->mem.fixed.dev(&c->plane_src, sizeof(HeadingSrc), Zero::on_stream(c->stream)));
     return PRE3_OK;
 }
 
 }  // namespace
-
-void free_plane(pre3_ctx *c)
-{
-    if (c->plane_buf) (void)hipFree(c->plane_buf);
-    if (c->plane_src) (void)hipFree(c->plane_src);
-    c->plane_buf = nullptr; c->plane_bytes = 0; c->plane_src = nullptr;
-}
 
 }  // namespace pre3
 
@@ -563,9 +530,9 @@ static int plane_fit_impl(const char *who, PlaneSource s, const int32_t *box, do
     const PlaneUpload up = plane_upload(j, s, draws);
     PlaneOut o;
     {
-        std::lock_guard<std::mutex> lk(g_stage.mu);
+        std::lock_guard<std::mutex> lk(g_stage_mu);
         if (up.bytes) {
-            PRE3_TRY(stage_reserve(up.stage_bytes));
+            PRE3_TRY(g_stage.reserve(up.stage_bytes, (up.stage_bytes + 65535) & ~(size_t)65535, PIN_DEFAULT));
             plane_stage_fill(j, s, draws, up, g_stage.p);
             PRE3_HIP(hipMemcpyAsync(d.as<char>() + up.off, g_stage.p, up.bytes, hipMemcpyHostToDevice, st));
         }
@@ -627,8 +594,9 @@ int pre3_plane_bench(int device, int rows, int cols, const double *x_sr, const d
     PRE3_TRY(select_device(who, device));
     Scratch d;
     PRE3_TRY(d.alloc(j.bytes_total));
-    void *st = nullptr;
-    PRE3_HIP(hipHostMalloc(&st, j.bytes_in, hipHostMallocDefault));
+    PinBlock stb;
+    PRE3_TRY(stb.reserve(j.bytes_in, j.bytes_in, PIN_DEFAULT));
+    void *const st = stb.p;
     plane_pack(j, s, draws, st);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = PRE3_OK;
@@ -645,7 +613,6 @@ int pre3_plane_bench(int device, int rows, int cols, const double *x_sr, const d
     (void)hipDeviceSynchronize();
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipHostFree(st);
     PRE3_TRY(rc);
     *ms_per_call = ms / reps;
     return PRE3_OK;
@@ -659,8 +626,8 @@ static int heading_wait(pre3_ctx *c, const char *who, const PlaneJob &j, int32_t
     PlaneOut o;
     PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
     PRE3_TRY(rows_applied(c, &applied));
-    PRE3_HIP(hipMemcpyAsync(&o, (char *)c->plane_buf + j.off_out, sizeof o, hipMemcpyDeviceToHost, c->stream));
-    if (draws_out) PRE3_HIP(hipMemcpyAsync(draws_out, (char *)c->plane_buf + j.off_draws, sizeof(int32_t) * 3 * (size_t)j.n_draw, hipMemcpyDeviceToHost, c->stream));
+    PRE3_HIP(hipMemcpyAsync(&o, c->mem.plane_buf.as<char>() + j.off_out, sizeof o, hipMemcpyDeviceToHost, c->stream));
+    if (draws_out) PRE3_HIP(hipMemcpyAsync(draws_out, c->mem.plane_buf.as<char>() + j.off_draws, sizeof(int32_t) * 3 * (size_t)j.n_draw, hipMemcpyDeviceToHost, c->stream));
     PRE3_TRY(stream_drain(c, who));
     if (res_out) plane_result(o, res_out);
     if (o.sta == 5 && draws_out) memset(draws_out, 0, sizeof(int32_t) * 3 * (size_t)j.n_draw);      // (no draw was made: the region holds an earlier call's)
@@ -694,11 +661,11 @@ static int heading_impl(const char *who, pre3_ctx *c, PlaneSource s, const int32
         void *st = nullptr, *st_dev = nullptr; int slot = 0;
         PRE3_TRY(stage_acquire(c, up.stage_bytes, &st, &st_dev, &slot));
         plane_stage_fill(j, s, draws, up, st);
-        PRE3_TRY(launch_pull(c, st, (char *)c->plane_buf + up.off, up.bytes, slot));
+        PRE3_TRY(launch_pull(c, st, c->mem.plane_buf.as<char>() + up.off, up.bytes, slot));
         PRE3_TRY(stage_release(c, slot));
     }
     if (s.resident) PRE3_TRY(sr_frame_lend(s.frame, c->stream));
-    PRE3_TRY(plane_launch(j, (char *)c->plane_buf, t, transpose ? 1 : 0, false, c->plane_src, c->stream, sd, s.crop()));
+    PRE3_TRY(plane_launch(j, c->mem.plane_buf.as<char>(), t, transpose ? 1 : 0, false, c->plane_src, c->stream, sd, s.crop()));
     if (s.resident) PRE3_TRY(sr_frame_reclaim(s.frame, c->stream));
     RowsHeading hd{};
     hd.on = 1; hd.strict = strict_reference ? 1 : 0; hd.src = c->plane_src;

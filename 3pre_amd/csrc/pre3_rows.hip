@@ -248,12 +248,10 @@ __global__ __launch_bounds__(RB) void k_rows_sweep(T *__restrict__ P, int ld, in
 
 int launch_rows_update(pre3_ctx *c, const RowsBlock *rows, const RowsHeading *hd)
 {
-    if (c->rows_blk == nullptr) {
-        void *p = nullptr;
-        if (hipMalloc(&p, sizeof(RowsBlock)) != hipSuccess) { set_error("hipMalloc of %zu bytes failed", sizeof(RowsBlock)); return PRE3_E_NOMEM; }
-        c->rows_blk = (RowsBlock *)p;
-        if (hipMalloc(&p, sizeof(double) * RMAX * (size_t)c->ld) != hipSuccess) { set_error("hipMalloc of the H*P rows failed"); return PRE3_E_NOMEM; }
-        c->rows_hp = (double *)p;
+    if (!c->rows_ready) {
+        Group g(c->mem.fixed, c->rows_ready);
+        PRE3_TRY(g.dev(&c->rows_blk, sizeof(RowsBlock), Zero::none())); PRE3_TRY(g.dev(&c->rows_hp, sizeof(double) * RMAX * (size_t)c->ld, Zero::none()));
+        g.commit();
     }
     const int r = rows ? rows->r : 3;
     PRE3_CHECK(r >= 1 && r <= RMAX, PRE3_E_ARG, "launch_rows_update: %d rows", r);
@@ -278,16 +276,9 @@ int launch_rows_update(pre3_ctx *c, const RowsBlock *rows, const RowsHeading *hd
 
 int rows_applied(pre3_ctx *c, int32_t *applied_host)
 {
-    PRE3_CHECK(c->rows_blk != nullptr, PRE3_E_STATE, "no small-rank update has run");
+    PRE3_CHECK(c->rows_ready, PRE3_E_STATE, "no small-rank update has run");
     PRE3_HIP(hipMemcpyAsync(applied_host, &c->rows_blk->applied, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     return PRE3_OK;
-}
-
-void free_rows(pre3_ctx *c)
-{
-    if (c->rows_blk) (void)hipFree(c->rows_blk);
-    if (c->rows_hp) (void)hipFree(c->rows_hp);
-    c->rows_blk = nullptr; c->rows_hp = nullptr;
 }
 
 }  // namespace pre3

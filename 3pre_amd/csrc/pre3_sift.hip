@@ -38,6 +38,7 @@ struct SiftConsts { double sigma0, pow2[SIFT_NDOG], thresh, r; };
 struct SiftWork {
     SiftPlan plan;
     SiftOctaves oc;
+    DevBlock dev_blk; PinBlock pin_blk;                      // the owners of dev and pin
     char *dev = nullptr;
     SiftLevelPlan *d_lev = nullptr;                          // [2][SIFT_NLEV]
     double *d_img = nullptr, *d_tmp0 = nullptr, *d_tmp1 = nullptr;
@@ -50,9 +51,6 @@ struct SiftWork {
 
 void sift_work_free(SiftWork *w)
 {
-    if (w == nullptr) return;
-    if (w->dev) (void)hipFree(w->dev);
-    if (w->pin) (void)hipHostFree(w->pin);
     delete w;
 }
 
@@ -285,13 +283,12 @@ int sift_work_get(pre3_sr_frame *f, const SiftPlan &plan)
     }
     const size_t o_cand = take(8 * 4 * (size_t)CAND_CAP), o_pth = take(8 * (size_t)SIFT_MAX_PEAKS * CAND_CAP), o_npk = take(4 * (size_t)CAND_CAP);
     const size_t o_okp = take(8 * 5 * (size_t)KP_CAP), o_frm0 = take(8 * 4 * (size_t)KP_CAP), o_words = take(4 * N_WORDS);
-    if (hipMalloc((void **)&w->dev, off) != hipSuccess) { delete w; set_error("pre3_sr_frame_sift: hipMalloc of %zu bytes failed", off); return PRE3_E_NOMEM; }
     const size_t pin_bytes = 1024 + 8 * (size_t)(4 + 128) * KP_CAP + 8 * 4 * (size_t)KP_CAP;
-    if (hipHostMalloc((void **)&w->pin, pin_bytes, hipHostMallocDefault) != hipSuccess) {
-        sift_work_free(w); set_error("pre3_sr_frame_sift: hipHostMalloc of %zu bytes failed", pin_bytes); return PRE3_E_NOMEM;
-    }
+    int rc = w->dev_blk.reserve(off, off, Zero::on_stream(f->stream));
+    if (rc == PRE3_OK) rc = w->pin_blk.reserve(pin_bytes, pin_bytes, PIN_DEFAULT);
+    if (rc != PRE3_OK) { delete w; return rc; }
+    w->dev = w->dev_blk.as<char>(); w->pin = w->pin_blk.as<char>();
     f->sift = w;
-    PRE3_HIP(hipMemsetAsync(w->dev, 0, off, f->stream));
     w->d_lev = (SiftLevelPlan *)(w->dev + o_lev); w->d_img = (double *)(w->dev + o_img);
     w->d_tmp0 = (double *)(w->dev + o_t0); w->d_tmp1 = (double *)(w->dev + o_t1);
     w->oc.O = plan.O;

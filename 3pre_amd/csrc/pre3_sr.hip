@@ -239,26 +239,17 @@ __global__ __launch_bounds__(MF) void k_sr_medfilt3(int rows, int cols, int padd
     out[g] = sr_medfilt_pixel(A, rows, cols, (int)(g % rows), (int)(g / rows), padding);
 }
 
-// Device memory of the handle, zeroed ON THE HANDLE'S STREAM: the stream does not synchronise with the null stream (hipStreamNonBlocking), so a
+// Device memory of the handle is zeroed ON THE HANDLE'S STREAM: the stream does not synchronise with the null stream (hipStreamNonBlocking), so a
 // hipMemset there -- asynchronous to the host -- could land behind the first transfer queued into the block.
-static int sr_dmalloc(pre3_sr_frame *f, void **p, size_t bytes)
-{
-    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; set_error("hipMalloc of %zu bytes failed", bytes); return PRE3_E_NOMEM; }
-    PRE3_HIP(hipMemsetAsync(*p, 0, bytes, f->stream));
-    return PRE3_OK;
-}
+static Zero sr_zero(pre3_sr_frame *f) { return Zero::on_stream(f->stream); }
 
 }  // namespace
 
 int sr_grow_stage(pre3_sr_frame *f, size_t bytes)
 {
-    if (f->stage_bytes >= bytes) return PRE3_OK;
-    if (f->stage) (void)hipHostFree(f->stage);
-    f->stage = nullptr; f->stage_bytes = 0;
-    const size_t cap = (bytes + 65535) & ~(size_t)65535;
-    PRE3_HIP(hipHostMalloc(&f->stage, cap, hipHostMallocDefault));
-    f->stage_bytes = cap;
-    return PRE3_OK;
+    const int rc = f->mem.stage.reserve(bytes, (bytes + 65535) & ~(size_t)65535, PIN_DEFAULT);
+    f->stage = f->mem.stage.p;
+    return rc;
 }
 
 KpLayout kp_layout(int K, int ldf, int ND)
@@ -273,12 +264,9 @@ KpLayout kp_layout(int K, int ldf, int ND)
 
 int sr_frame_kp_reserve(pre3_sr_frame *f, size_t total)
 {
-    if (f->kp_bytes >= total) return PRE3_OK;
-    if (f->kp) (void)hipFree(f->kp);
-    f->kp = nullptr; f->kp_bytes = 0;
-    PRE3_TRY(sr_dmalloc(f, &f->kp, total + total / 4));
-    f->kp_bytes = total + total / 4;
-    return PRE3_OK;
+    const int rc = f->mem.kp.reserve(total, total + total / 4, sr_zero(f));
+    f->kp = f->mem.kp.p;
+    return rc;
 }
 
 // the device half of a load, behind whatever put the planes into `raw` (the staged transfer of pre3_sr_frame_load, the text parse of
@@ -307,13 +295,10 @@ int sr_condition_run(pre3_sr_frame *f, int mode, bool has_conf)
 // the parse writes -- it and `raw` swap once a text is accepted.  The caller has waited for the stream.
 int sr_frame_text_work(pre3_sr_frame *f, size_t work_bytes, size_t spare_bytes)
 {
-    if (f->text_dev_bytes < work_bytes) {
-        if (f->text_dev) (void)hipFree(f->text_dev);
-        f->text_dev = nullptr; f->text_dev_bytes = 0;
-        PRE3_TRY(sr_dmalloc(f, &f->text_dev, work_bytes + work_bytes / 4));
-        f->text_dev_bytes = work_bytes + work_bytes / 4;
-    }
-    if (f->spare == nullptr) PRE3_TRY(sr_dmalloc(f, (void **)&f->spare, spare_bytes));
+    const int rc = f->mem.text_dev.reserve(work_bytes, work_bytes + work_bytes / 4, sr_zero(f));
+    f->text_dev = f->mem.text_dev.p;
+    PRE3_TRY(rc);
+    if (f->spare == nullptr) PRE3_TRY(f->mem.fixed.dev(&f->spare, spare_bytes, sr_zero(f)));
     return PRE3_OK;
 }
 
@@ -356,24 +341,13 @@ int sr_frame_keypoint_view(pre3_sr_frame *f, SrKeypointView *v)
 }
 
 // dev_bytes of device memory and pin_bytes of pinned host memory owned by the handle, grown on demand; a new device block is zeroed on the handle's stream
-// (sr_dmalloc's rule).  The caller has made sure that nothing queued still uses the old blocks.
+// (sr_zero's rule).  The caller has made sure that nothing queued still uses the old blocks.
 int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, void **dev, void **pin)
 {
     PRE3_CHECK(f != nullptr, PRE3_E_ARG, "sr_frame_pair_work: null handle");
-    if (f->pair_dev_bytes < dev_bytes) {
-        if (f->pair_dev) (void)hipFree(f->pair_dev);
-        f->pair_dev = nullptr; f->pair_dev_bytes = 0;
-        PRE3_TRY(sr_dmalloc(f, &f->pair_dev, dev_bytes + dev_bytes / 4));
-        f->pair_dev_bytes = dev_bytes + dev_bytes / 4;
-    }
-    if (f->pair_pin_bytes < pin_bytes) {
-        if (f->pair_pin) (void)hipHostFree(f->pair_pin);
-        f->pair_pin = nullptr; f->pair_pin_bytes = 0;
-        const size_t cap = (pin_bytes + pin_bytes / 4 + 65535) & ~(size_t)65535;
-        PRE3_HIP(hipHostMalloc(&f->pair_pin, cap, hipHostMallocDefault));
-        f->pair_pin_bytes = cap;
-    }
-    *dev = f->pair_dev; *pin = f->pair_pin;
+    PRE3_TRY(f->mem.pair_dev.reserve(dev_bytes, dev_bytes + dev_bytes / 4, sr_zero(f)));
+    PRE3_TRY(f->mem.pair_pin.reserve(pin_bytes, (pin_bytes + pin_bytes / 4 + 65535) & ~(size_t)65535, PIN_DEFAULT));
+    *dev = f->mem.pair_dev.p; *pin = f->mem.pair_pin.p;
     return PRE3_OK;
 }
 
@@ -426,16 +400,7 @@ int pre3_sr_frame_destroy(pre3_sr_frame *f)
     if (f == nullptr) return PRE3_OK;
     (void)hipSetDevice(f->device);
     if (f->stream) { (void)hipStreamSynchronize(f->stream); (void)hipStreamDestroy(f->stream); }
-    if (f->raw) (void)hipFree(f->raw);
-    if (f->filt) (void)hipFree(f->filt);
-    if (f->maxima) (void)hipFree(f->maxima);
-    if (f->kp) (void)hipFree(f->kp);
-    if (f->stage) (void)hipHostFree(f->stage);
-    if (f->pinned_n) (void)hipHostFree(f->pinned_n);
-    if (f->pair_dev) (void)hipFree(f->pair_dev);
-    if (f->text_dev) (void)hipFree(f->text_dev);
-    if (f->spare) (void)hipFree(f->spare);
-    if (f->pair_pin) (void)hipHostFree(f->pair_pin);
+    f->mem = {};
     if (f->pair_ev) (void)hipEventDestroy(f->pair_ev);
     if (f->sift) sift_work_free(f->sift);
     delete f;
@@ -447,10 +412,10 @@ static int sr_create_buffers(pre3_sr_frame *f)
     const size_t npix = (size_t)f->rows * f->cols;
     PRE3_HIP(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
     PRE3_HIP(hipEventCreateWithFlags(&f->pair_ev, hipEventDisableTiming));
-    PRE3_TRY(sr_dmalloc(f, (void **)&f->raw, sizeof(double) * 5 * npix));
-    PRE3_TRY(sr_dmalloc(f, (void **)&f->filt, sizeof(double) * 4 * npix));
-    PRE3_TRY(sr_dmalloc(f, (void **)&f->maxima, sizeof(double) * 4));     // imax, cmax, n_bad (and a spare)
-    PRE3_HIP(hipHostMalloc((void **)&f->pinned_n, 64, hipHostMallocDefault));
+    PRE3_TRY(f->mem.fixed.dev(&f->raw, sizeof(double) * 5 * npix, sr_zero(f)));
+    PRE3_TRY(f->mem.fixed.dev(&f->filt, sizeof(double) * 4 * npix, sr_zero(f)));
+    PRE3_TRY(f->mem.fixed.dev(&f->maxima, sizeof(double) * 4, sr_zero(f)));     // imax, cmax, n_bad (and a spare)
+    PRE3_TRY(f->mem.fixed.pin(&f->pinned_n, 64, PIN_DEFAULT));
     return sr_grow_stage(f, sizeof(double) * 5 * npix);
 }
 

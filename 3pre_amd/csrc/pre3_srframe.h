@@ -17,10 +17,8 @@ struct pre3_sr_frame {
     double *raw = nullptr;          // [5][npix]: z, x, y, amplitude, confidence -- as uploaded
     double *filt = nullptr;         // [4][npix]: x, y, z, image
     double *maxima = nullptr;       // imax, cmax, n_bad (pixels with conf < cutoff, counted under form 1 only)
-    void *stage = nullptr;          // pinned: the five planes of a load, or the keypoints of a call
-    size_t stage_bytes = 0;
-    void *kp = nullptr;             // device: the keypoint stage's input and output block
-    size_t kp_bytes = 0;
+    void *stage = nullptr;          // pinned (mem.stage): the five planes of a load, or the keypoints of a call
+    void *kp = nullptr;             // device (mem.kp): the keypoint stage's input and output block
     int32_t *pinned_n = nullptr;    // n_kept
     // the last keypoint call's result, still in `kp` (sr_frame_keypoint_view): kp_valid 0 = none yet, or stale after a load
     int kp_valid = 0, kp_K = 0, kp_ldf = 0, kp_ND = 0, kp_gate = 0, kp_n = 0;
@@ -29,17 +27,16 @@ struct pre3_sr_frame {
     bool kp_raw_ok = true;                  // its descriptors passed the ranked IC route's bounds on their way through `stage`
     size_t kp_o_frm = 0, kp_o_des = 0;      // offsets of frm_out / des_out inside kp
     size_t kp_o_xyz = 0, kp_o_rho = 0, kp_o_idx = 0;      // ... of xyz_out / rho_out (written by gate 0 only) and keep_idx
-    // the pair stage's work block and its pinned image (pre3_vopair.hip), allocated on its first use
-    void *pair_dev = nullptr, *pair_pin = nullptr;
-    size_t pair_dev_bytes = 0, pair_pin_bytes = 0;
     hipEvent_t pair_ev = nullptr;   // carries the hand-offs to and from a consumer's stream (sr_frame_lend, sr_frame_reclaim)
     // the SIFT extractor's plan, scale space and lists (pre3_sift.hip), allocated on its first use
     pre3::SiftWork *sift = nullptr;
     // the text stage (pre3_dattext.hip), allocated on its first use: [text | chunk records | token offsets | status], and the plane block the parse
     // writes, which swaps with `raw` when a text is accepted
     void *text_dev = nullptr;
-    size_t text_dev_bytes = 0;
     double *spare = nullptr;
+    // the owners (pre3_own.h): raw, filt, maxima, pinned_n and spare sit on `fixed`; the others grow on demand, each zeroed on the handle's stream when
+    // it is new.  pair_dev / pair_pin: the pair stage's work block and its pinned image (pre3_vopair.hip), allocated on its first use
+    struct { pre3::BlockList fixed; pre3::PinBlock stage, pair_pin; pre3::DevBlock kp, pair_dev, text_dev; } mem;
 };
 
 namespace pre3 {

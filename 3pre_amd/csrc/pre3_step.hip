@@ -454,7 +454,7 @@ int pre3_update_rows(pre3_ctx *c, int r, int width, const int32_t *nnz, const in
     else { hf.assign(hv.begin(), hv.end()); PRE3_HIP(hipMemcpyAsync(c->row_val, hf.data(), sizeof(float) * hf.size(), hipMemcpyHostToDevice, c->stream)); }
     PRE3_HIP(hipMemcpyAsync(c->row_nu, nu.data(), sizeof(double) * r_pad, hipMemcpyHostToDevice, c->stream));
     if (R) {
-        if (c->Rdense == nullptr) PRE3_TRY(dmalloc_bytes(&c->Rdense, (size_t)c->rcap * c->rcap * c->esz));
+        if (c->Rdense == nullptr) PRE3_TRY(dmalloc_bytes(c, &c->Rdense, (size_t)c->rcap * c->rcap * c->esz));
         if (c->dtype == PRE3_F64) PRE3_HIP(hipMemcpyAsync(c->Rdense, R, sizeof(double) * r * r, hipMemcpyHostToDevice, c->stream));
         else { rf.assign(R, R + (size_t)r * r); PRE3_HIP(hipMemcpyAsync(c->Rdense, rf.data(), sizeof(float) * rf.size(), hipMemcpyHostToDevice, c->stream)); }
     }

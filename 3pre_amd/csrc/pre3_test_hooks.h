@@ -25,7 +25,10 @@
  *           pre3_get_state.
  * The stream is drained; PRE3_E_NUMERIC if a pivot was not positive.  L_out (nullable): r x r, the lower triangle of L, zeros above.  W_out (nullable):
  * r_pad x (n + 1), L^-1 B with L^-1 nu as the last column, the padded rows included.  PRE3_E_ARG (nothing touched) for r < 1, r_pad above the context's
- * row capacity, a mode other than 0 / 1, a null input pointer or a non-finite entry after conversion. */
+ * row capacity, a mode other than 0 / 1, a null input pointer or a non-finite entry after conversion.
+ *
+ * pre3_test_live_blocks(out): the device blocks, device bytes, pinned blocks and pinned bytes of the whole process that are live right now, counted
+ * where pre3_own.h's seam allocates and frees (the ScratchPool of the stateless entry points is not in it). */
 #pragma once
 #include "../../include/pre3.h"
 #ifdef __cplusplus
@@ -35,6 +38,7 @@ PRE3_API int pre3_test_stall(pre3_ctx *ctx, int release);
 PRE3_API int pre3_match_shard_test_stall(pre3_match_shard *s, int release);
 PRE3_API int pre3_test_downdate(pre3_ctx *ctx, int r, const double *W, int launches);
 PRE3_API int pre3_test_factor_solve(pre3_ctx *ctx, int r, const double *S, const double *B, const double *nu, int mode, int predicted_prior, double *L_out, double *W_out);
+PRE3_API int pre3_test_live_blocks(int64_t out[4]);
 #ifdef __cplusplus
 }
 #endif

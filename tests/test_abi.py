@@ -25,14 +25,14 @@ def test_library_exports_every_declared_symbol(pre3):
 
 
 def test_the_test_hooks_are_not_part_of_the_public_header(pre3):
-    """pre3_test_stall / pre3_match_shard_test_stall (tests/test_gpu_comm.py), pre3_test_downdate (tests/test_gpu_k9_alone.py) and
-    pre3_test_factor_solve (tests/test_gpu_chol_alone.py) are declared in
+    """pre3_test_stall / pre3_match_shard_test_stall (tests/test_gpu_comm.py), pre3_test_downdate (tests/test_gpu_k9_alone.py),
+    pre3_test_factor_solve (tests/test_gpu_chol_alone.py) and pre3_test_live_blocks (tests/test_gpu_regrow.py) are declared in
     3pre_amd/csrc/pre3_test_hooks.h, exported, inert without PRE3_TEST_HOOKS=1, and not declared in include/pre3.h"""
     txt = open(os.path.join(ROOT, "include", "pre3.h")).read()
     assert "test_stall" not in txt and "test_downdate" not in txt and "test_factor_solve" not in txt and "pre3_test_" not in txt
     hooks = open(os.path.join(ROOT, "3pre_amd", "csrc", "pre3_test_hooks.h")).read()
     lib = C.CDLL(pre3.LIB_PATH)
-    for name in ("pre3_test_stall", "pre3_match_shard_test_stall", "pre3_test_downdate", "pre3_test_factor_solve"):
+    for name in ("pre3_test_stall", "pre3_match_shard_test_stall", "pre3_test_downdate", "pre3_test_factor_solve", "pre3_test_live_blocks"):
         assert hasattr(lib, name) and re.search(r"PRE3_API\s+int\s+%s\s*\(" % name, hooks), name
         assert name not in pre3._lib.EXPORTS
 
