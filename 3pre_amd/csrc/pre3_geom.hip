@@ -21,6 +21,8 @@
 #include "pre3_predictu.h"
 #include "pre3_predictcv.h"
 #include "pre3_vocov.h"
+#include "pre3_icp.h"
+#include "pre3_predicticp.h"
 #include <type_traits>
 
 namespace pre3 {
@@ -76,6 +78,32 @@ __device__ __forceinline__ const double *predict_pn_src(const PnPair &s)
 {
     return vc_predict_takes(s.out->sta, s.hdr->pnum, s.hdr->bad, s.out->dist_ok, s.cov->status) ? s.cov->cov : s.behind;
 }
+// Behind a dense ICP that refined the pair's pose (US = PredictUIcp, NS = PnIcp; pre3_predict_icp_pair_seeded): u and Pn under
+// predict_icp_select (pre3_predicticp.h), evaluated from words the pair's and the ICP's launches wrote in front of this one.  Block 0 reports what was
+// taken.  predict_pn_src gives the block that is copied -- in mode PRE3_NOISE_ICP_FLOOR the context's own noise, on which predict_pn_add's block (the
+// ICP's covariance) is then added entry by entry, one fp64 addition each.
+__device__ __forceinline__ int predict_icp_rule(const PredictIcpSrc &s, double *u_out, int *ut, int *nt)
+{
+    return predict_icp_select(s.out->sta, s.hdr->pnum, s.hdr->bad, s.out->dist_ok, s.out->u, s.ctl->status, s.u_icp, *s.error, s.max_error, s.noise,
+                              s.cov_pair->status, s.cov_icp->status, u_out, ut, nt);
+}
+__device__ __forceinline__ const U7 &predict_u(const PredictUIcp &s, U7 &ud)
+{
+    int ut, nt;
+    const int refusal = predict_icp_rule(s.s, ud.v, &ut, &nt);
+    if (blockIdx.x == 0) {
+        if (refusal != PU_OK) atomicCAS(s.err, 0, pu_error_word(refusal));
+        s.taken[0] = ut; s.taken[1] = nt;
+    }
+    return ud;
+}
+__device__ __forceinline__ int predict_pn_taken(const PnIcp &s) { U7 ud; int ut, nt; (void)predict_icp_rule(s.s, ud.v, &ut, &nt); return nt; }
+__device__ __forceinline__ const double *predict_pn_src(const PnIcp &s)
+{
+    const int nt = predict_pn_taken(s);
+    return nt == PI_NOISE_PAIR ? s.s.cov_pair->cov : nt == PI_NOISE_ICP ? s.s.cov_icp->cov : s.behind;
+}
+__device__ __forceinline__ const double *predict_pn_add(const PnIcp &s) { return predict_pn_taken(s) == PI_NOISE_ICP_FLOOR ? s.s.cov_icp->cov : nullptr; }
 template <typename T, typename US = U7, typename NS = PnConst>
 __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in, double *x_out, T *__restrict__ P, int n, int ld, US u,
                                                  double *__restrict__ params, int n_pred_blocks, ProjRide pr, InboxRide ib, int fuse_jn, PendW pw = PendW{}, NS ns = NS{})
@@ -132,6 +160,13 @@ __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in
     // the projection riders read the landmarks from x_in (the prediction copies them unchanged) and compute the pose themselves (predict_pose):
     // waiting for block 0's pose cost them its fence + counter and their own poll, about 1.5 us in front of the projections
     __syncthreads();
+    if constexpr (std::is_same<NS, PnIcp>::value) {
+        if (blockIdx.x == 0) {                                     // PRE3_NOISE_ICP_FLOOR: Pn = cov_icp + the context's noise, which sPn holds by now
+            const double *add = predict_pn_add(ns);
+            if (add != nullptr && threadIdx.x >= 64 && threadIdx.x < 64 + 49) sPn[threadIdx.x - 64] = add[threadIdx.x - 64] + sPn[threadIdx.x - 64];
+            __syncthreads();
+        }
+    }
     double cfix = 0; int cpos = -1;
     if (fuse_jn) {
         if (j >= 7 && j < n) { double w[4]; for (int i = 0; i < 4; ++i) w[i] = (double)(T)jn_row(sJu, i, v); for (int i = 0; i < 4; ++i) v[i] = w[i]; }
@@ -1183,6 +1218,18 @@ int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection, si
     const int fuse_jn = c->carry.jn_pending ? 1 : 0;          // the pending update.m:42-46 pass of the update in front (run_update left it to this launch)
     if (c->pn_set) predict_launch(c, nb, uu, own, blocks, pr, ib, fuse_jn);
     else predict_launch(c, nb, uu, PnConst{}, blocks, pr, ib, fuse_jn);
+    PRE3_HIP(hipGetLastError());
+    c->carry.jn_pending = false;
+    return PRE3_OK;
+}
+
+// launch_predict_impl's device form with the ICP's tags: no riders, no inbox pull; the context's block, or the constant, stands behind and under the rule
+int launch_predict_icp(pre3_ctx *c, const PredictUIcp &u_icp)
+{
+    const int blocks = ceil_div(c->n, 256);
+    const int fuse_jn = c->carry.jn_pending ? 1 : 0;
+    const PnIcp ns{ u_icp.s, c->pn_set ? c->pred_params + PRED_PN_OFF : nullptr };
+    predict_launch(c, blocks, u_icp, ns, blocks, ProjRide{}, InboxRide{}, fuse_jn);
     PRE3_HIP(hipGetLastError());
     c->carry.jn_pending = false;
     return PRE3_OK;

@@ -18,6 +18,15 @@ struct VoCov;
 struct PnConst {};
 struct PnBlock { const double *pn; };
 struct PnPair { const VoCov *cov; const VoOut *out; const VoPairHeader *hdr; const double *behind; };
+// k_predict's increment and process noise where a dense ICP refined the pair's pose in front of the launch (pre3_predict_icp_pair_seeded; DESIGN.md
+// section 34): the pair's blocks as above, the ICP run's state block, u, error and covariance block where its launches left them, and the caller's gate
+// and noise mode.  PredictUIcp (US) takes u under predict_icp_select (pre3_predicticp.h) and block 0 reports what was taken in taken[0..1]; PnIcp (NS)
+// takes Pn under the same rule with `behind` -- the context's block, or null: the constant -- behind it, and under it in mode PRE3_NOISE_ICP_FLOOR.
+struct IcpCtl;
+struct PredictIcpSrc { const VoOut *out; const VoPairHeader *hdr; const VoCov *cov_pair; const IcpCtl *ctl; const double *u_icp, *error; const VoCov *cov_icp;
+                       double max_error; int noise; };
+struct PredictUIcp { PredictIcpSrc s; int32_t *err; int32_t *taken; };
+struct PnIcp { PredictIcpSrc s; const double *behind; };
 
 // ------------------------------------------------------------------------------------------------
 // device math (fp64)

@@ -89,9 +89,10 @@ PRE3_ICP_HD double icp_error(const IcpCtl *c) { return c->e1 < c->e2 ? c->e1 : c
 #include "pre3_internal.h"
 #include <mutex>
 namespace pre3 {
-struct VoOut;
+struct VoOut; struct VoCov;
 // what a call hands out (each may be null): corr [p][3] = (model, source, D), 1-based; corr_pix [p][2] pixel indices (frames only); data2 3 x n2; log [62][3]
-struct IcpOutputs { pre3_icp_result *res; double *corr; int32_t *corr_pix; double *data2; double *log; };
+// cov [49], cov_status: the closed-form covariance of u behind the run (IcpJob::with_cov; pre3_icpcov.h)
+struct IcpOutputs { pre3_icp_result *res; double *corr; int32_t *corr_pix; double *data2; double *log; double *cov = nullptr; int32_t *cov_status = nullptr; };
 // one run in flight: its device block, the lock on the library's pinned result block, and what the host needs to decode it after the wait
 struct IcpJob {
     Scratch dev;
@@ -101,10 +102,27 @@ struct IcpJob {
     bool queued = false, waited = false, frames = false;
     int cap1 = 0, cap2 = 0;
     size_t o_corr_m = 0, o_corr_s = 0, o_corr_d = 0, o_src = 0, o_mpix = 0, o_spix = 0, pin_bytes = 0;
+    // set by the caller before the run is queued (frames forms): k_icp_cov_part / k_icp_cov_fin behind k_icp_final, their VoCov block and partials at the
+    // end of the device block, the VoCov block transferred behind the front of the pinned one
+    bool with_cov = false;
+    size_t o_cov = 0, o_part = 0, o_pin_cov = 0;
+    const double *cov_x = nullptr, *cov_y = nullptr, *cov_z = nullptr;      // the source frame's filtered planes, read through spix
+    int cov_npix = 0;
+    // set by the caller before the run is queued: the device block comes from an owner that outlives the run (block(owner, bytes, &d)) instead of `dev`,
+    // and the head is built by a launch instead of uploaded from the pinned block -- nothing of a run that no host waits for hangs on this object or on
+    // the library's pinned block.  pin_back: the results are still transferred (the caller waits and collects); otherwise the pinned block is not touched
+    int (*block)(void *owner, size_t bytes, char **out) = nullptr;
+    void *owner = nullptr;
+    bool pin_back = true;
+    char *d = nullptr;              // the device block in use, either way
     IcpJob() = default;
     IcpJob(const IcpJob &) = delete;
-    ~IcpJob() { if (queued && !waited) (void)hipStreamSynchronize(st); }      // an error path: nothing queued may outlive the block
+    ~IcpJob() { if (queued && !waited && pin_back) (void)hipStreamSynchronize(st); }      // an error path: nothing queued may outlive the blocks it holds
+    size_t o_taken = 0, o_pin_taken = 0;        // with `block`: two int32 a launch behind the run reports in (pre3_predict_icp_pair_seeded's taken_out)
 };
+// where a run's launches leave what a launch behind them reads (IcpJob::with_cov for cov, IcpJob::block for taken)
+struct IcpDevView { const IcpCtl *ctl; const double *u, *error; const VoCov *cov; int32_t *taken; };
+void icp_job_dev_view(const IcpJob *job, IcpDevView *v);
 // the model is every pixel of v1's filtered planes as [-x; -y; z], the source v2's pixels at rows and columns 0, stride, ...; Rinit / Tinit from the host,
 // or (vo_dev != nullptr) from a VO pair's result block on the device, in which case a pair that did not end in sta == 1 leaves the run at ICP_NOT_RUN.
 // Everything is queued on st, the transfer of the results included; the caller waits for st, then calls icp_job_collect.

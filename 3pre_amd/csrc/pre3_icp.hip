@@ -22,6 +22,7 @@
 #include "pre3_internal.h"
 #include "pre3_vodev.h"
 #include "pre3_icp.h"
+#include "pre3_icpcov.h"
 #include "pre3_srframe.h"
 
 namespace pre3 {
@@ -60,6 +61,14 @@ __global__ void k_icp_seed(IcpHead *h, const VoOut *__restrict__ vo)
     if (vo->sta != 1) { h->ctl.done = 1; h->ctl.status = ICP_NOT_RUN; return; }
     for (int i = 0; i < 9; ++i) h->Rinit[i] = vo->rot[i];
     for (int i = 0; i < 3; ++i) h->Tinit[i] = vo->trans[i];
+}
+
+// head_image's fields (the host's image of a run that starts at n1 = n2 = 0 with the identity seed) written into a head the stream has zeroed
+__global__ void k_icp_head(IcpHead *h, double res)
+{
+    if (threadIdx.x != 0) return;
+    icp_ctl_start(&h->ctl, 0, 0, res);
+    for (int i = 0; i < 9; ++i) { h->R[i] = (i % 4 == 0) ? 1.0 : 0.0; h->Rinit[i] = h->R[i]; }
 }
 
 // the two clouds from two resident frames: blockIdx.x == 0 every pixel of prev, 1 cur's pixels at rows and columns 0, stride, ...; a pixel with a
@@ -404,8 +413,11 @@ int icp_layout(IcpJob *job, int cap1, int cap2, IcpWork *w, size_t *o_model)
     const size_t o_bi = o; o += up16(sizeof(int32_t) * (size_t)cap2);
     const size_t o_min = o; o += up16(sizeof(unsigned long long) * (size_t)cap1);
     const size_t o_own = o; o += up16(sizeof(int32_t) * (size_t)cap1);
-    PRE3_TRY(job->dev.alloc(o));
-    char *d = job->dev.as<char>();
+    if (job->with_cov) { job->o_cov = o; o += up16(sizeof(VoCov)); job->o_part = o; o += up16(ic_part_bytes(cap1 < cap2 ? cap1 : cap2)); }
+    if (job->block != nullptr) { job->o_taken = o; o += 16; }
+    if (job->block != nullptr) PRE3_TRY(job->block(job->owner, o, &job->d));
+    else { PRE3_TRY(job->dev.alloc(o)); job->d = job->dev.as<char>(); }
+    char *d = job->d;
     w->h = (IcpHead *)d; w->cap1 = cap1; w->cap2 = cap2;
     w->corr_m = (int32_t *)(d + job->o_corr_m); w->corr_s = (int32_t *)(d + job->o_corr_s); w->corr_d = (double *)(d + job->o_corr_d);
     w->sx = (double *)(d + job->o_src); w->sy = w->sx + cap2; w->sz = w->sy + cap2;
@@ -440,11 +452,22 @@ int icp_queue_run(IcpJob *job, const IcpWork &w, const IcpOutputs &want, hipStre
     }
     hipLaunchKernelGGL(k_icp_final, dim3(1), dim3(64), 0, st, w.h);
     PRE3_HIP(hipGetLastError());
+    char *d = job->d;
+    if (job->with_cov) {            // the covariance of u over the final pairs: the state block, u, the pairs and both clouds are read where they lie
+        IcCovArgs a{};
+        a.ctl = &w.h->ctl; a.u_dev = w.h->u; a.cap = cap1 < cap2 ? cap1 : cap2; a.cap1 = cap1; a.cap2 = cap2; a.npix = job->cov_npix;
+        a.corr_m = w.corr_m; a.corr_s = w.corr_s; a.mx = w.mx; a.my = w.my; a.mz = w.mz;
+        a.sx = job->cov_x; a.sy = job->cov_y; a.sz = job->cov_z; a.spix = w.spix;
+        PRE3_TRY(launch_icp_cov(a, (IcPart *)(d + job->o_part), (VoCov *)(d + job->o_cov), st));
+    }
     size_t need = up16(sizeof(IcpHead));            // the prefix of the block the caller's outputs reach into
     if (want.corr || want.corr_pix) need = job->o_src;
     if (want.data2) need = job->o_mpix;
     if (want.corr_pix) need = job->pin_bytes;
-    PRE3_HIP(hipMemcpyAsync(job->pin, job->dev.p, need, hipMemcpyDeviceToHost, st));
+    if (job->pin_back) {
+        PRE3_HIP(hipMemcpyAsync(job->pin, d, need, hipMemcpyDeviceToHost, st));
+        if (job->with_cov) PRE3_HIP(hipMemcpyAsync(job->pin + job->o_pin_cov, d + job->o_cov, sizeof(VoCov), hipMemcpyDeviceToHost, st));
+    }
     job->st = st; job->queued = true;
     return PRE3_OK;
 }
@@ -465,19 +488,37 @@ int icp_job_queue_frames(IcpJob *job, const SrFrameView &v1, const SrFrameView &
     IcpWork w{};
     size_t o_model = 0;
     PRE3_TRY(icp_layout(job, cap1, cap2, &w, &o_model));
-    PRE3_TRY(pin_reserve(job, job->pin_bytes));
+    job->o_pin_cov = job->pin_bytes;
+    job->o_pin_taken = job->o_pin_cov + (job->with_cov ? up16(sizeof(VoCov)) : 0);
+    if (job->pin_back) PRE3_TRY(pin_reserve(job, job->o_pin_taken + (job->block != nullptr ? 16 : 0)));
     job->frames = true;
-    head_image((IcpHead *)job->pin, 0, 0, res, Rinit, Tinit);
-    PRE3_HIP(hipMemcpyAsync(w.h, job->pin, sizeof(IcpHead), hipMemcpyHostToDevice, st));
+    job->cov_x = v2.x; job->cov_y = v2.y; job->cov_z = v2.z; job->cov_npix = v2.rows * v2.cols;
+    if (job->block != nullptr) {        // head_image's bytes without the pinned block: nothing the host holds has to outlive the call
+        PRE3_CHECK(Rinit == nullptr && Tinit == nullptr, PRE3_E_STATE, "icp_job_queue_frames: a run in an owner's block is seeded on the device");
+        PRE3_HIP(hipMemsetAsync(w.h, 0, sizeof(IcpHead), st));
+        hipLaunchKernelGGL(k_icp_head, dim3(1), dim3(64), 0, st, w.h, res);
+    } else {
+        head_image((IcpHead *)job->pin, 0, 0, res, Rinit, Tinit);
+        PRE3_HIP(hipMemcpyAsync(w.h, job->pin, sizeof(IcpHead), hipMemcpyHostToDevice, st));
+    }
     if (vo_dev) hipLaunchKernelGGL(k_icp_seed, dim3(1), dim3(64), 0, st, w.h, vo_dev);
     hipLaunchKernelGGL(k_icp_pack, dim3(2), dim3(REG_NTH), 0, st, w, v1.rows, v1.cols, stride, v1.x, v1.y, v1.z, v2.x, v2.y, v2.z);
     return icp_queue_run(job, w, want, st);
+}
+
+void icp_job_dev_view(const IcpJob *job, IcpDevView *v)
+{
+    const IcpHead *h = (const IcpHead *)job->d;
+    v->ctl = &h->ctl; v->u = h->u; v->error = &h->error;
+    v->cov = job->with_cov ? (const VoCov *)(job->d + job->o_cov) : nullptr;
+    v->taken = job->block != nullptr ? (int32_t *)(job->d + job->o_taken) : nullptr;
 }
 
 // after the wait: the front of the block, checked, into the caller's arrays
 int icp_job_collect(IcpJob *job, const char *who, const IcpOutputs &o)
 {
     job->waited = true;
+    if (o.cov_status) *o.cov_status = VC_NOT_COMPUTED;
     const IcpHead *h = (const IcpHead *)job->pin;
     const IcpCtl &c = h->ctl;
     if (c.status == ICP_NOT_RUN && c.done) { if (o.res) o.res->sta = ICP_NOT_RUN; return PRE3_OK; }
@@ -506,6 +547,12 @@ int icp_job_collect(IcpJob *job, const char *who, const IcpOutputs &o)
         for (int j = 0; j < n2; ++j) { o.data2[3 * j] = s[j]; o.data2[3 * j + 1] = s[cap2 + j]; o.data2[3 * j + 2] = s[2 * (size_t)cap2 + j]; }
     }
     if (o.log) memcpy(o.log, h->log, sizeof h->log);
+    if (job->with_cov) {
+        const VoCov *cv = (const VoCov *)(job->pin + job->o_pin_cov);
+        PRE3_CHECK(cv->status >= VC_NOT_COMPUTED && cv->status <= VC_UNUSABLE, PRE3_E_HIP, "%s: the device reports covariance status %d", who, cv->status);
+        if (o.cov_status) *o.cov_status = cv->status;
+        if (o.cov && cv->status == VC_VALID) memcpy(o.cov, cv->cov, sizeof cv->cov);
+    }
     return PRE3_OK;
 }
 

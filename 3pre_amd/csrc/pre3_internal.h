@@ -374,10 +374,12 @@ struct IcMatchRide;
 int launch_project_innovation(pre3_ctx *c, int which, int clear_first, int mode, double chi2, bool collect = true, bool clear_ic = false, const IcMatchRide *ride = nullptr);
 int launch_update_x(pre3_ctx *c, int which_prior, int r);
 int launch_jnorm(pre3_ctx *c, int which);
-struct PredictUDev; struct PnPair;
+struct PredictUDev; struct PnPair; struct PredictUIcp;
 int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection = false, size_t inbox_n16 = 0, int32_t inbox_seq = 0,
                         const PredictUDev *u_dev = nullptr /* the increment from a VO pair's device result block (pre3_geomdev.h); u unused */,
                         const PnPair *pn_pair = nullptr /* with u_dev: the pair's covariance as Pn under the status rule (pre3_vocov.h); its `behind` is filled here */);
+// the prediction behind a VO pair and the dense ICP that refined it: u and Pn under predict_icp_select (pre3_predicticp.h)
+int launch_predict_icp(pre3_ctx *c, const PredictUIcp &u_icp);
 // the camera-only prediction (pre3_predict_cv; pre3_predictcv.h): one launch, no riders, pred_params untouched
 int launch_predict_cv(pre3_ctx *c, int type, double dt, double sigma_a, double sigma_alpha);
 constexpr int PRED_PN_OFF = 128;         /* pred_params[128 .. 176]: the context's process noise block (pre3_set_process_noise) */
@@ -440,6 +442,7 @@ struct SrKeypointView { int K, ldf, ND, gate, n_kept; const double *frm, *des; c
                         int K_in; const double *frm_in, *des_in; bool raw_in_bounds; };
 int sr_frame_keypoint_view(pre3_sr_frame *f, SrKeypointView *v);
 int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, void **dev, void **pin);      /* pre3_vopair.hip's work blocks */
+int sr_frame_icp_work(pre3_sr_frame *f, size_t dev_bytes, void **dev);      /* the device block of an ICP run a prediction reads without a host wait */
 // the hand-off between the handle's stream and a consumer's, on the handle's own event.  lend: `consumer` waits for everything
 // queued on the handle's stream so far (a load, the conditioning launches).  reclaim: the handle's stream waits for everything queued on `consumer` so
 // far, so that a load or a keypoint call that follows cannot overwrite blocks the consumer's launches still read.

@@ -351,6 +351,15 @@ int sr_frame_pair_work(pre3_sr_frame *f, size_t dev_bytes, size_t pin_bytes, voi
     return PRE3_OK;
 }
 
+// the same rule for the ICP run of pre3_predict_icp_pair_seeded: owned by the handle, so that it outlives the prediction's read in the no-wait form
+int sr_frame_icp_work(pre3_sr_frame *f, size_t dev_bytes, void **dev)
+{
+    PRE3_CHECK(f != nullptr, PRE3_E_ARG, "sr_frame_icp_work: null handle");
+    PRE3_TRY(f->mem.icp_dev.reserve(dev_bytes, dev_bytes + dev_bytes / 4, sr_zero(f)));
+    *dev = f->mem.icp_dev.p;
+    return PRE3_OK;
+}
+
 int sr_frame_lend(pre3_sr_frame *f, hipStream_t consumer)
 {
     PRE3_CHECK(f != nullptr, PRE3_E_ARG, "sr_frame_lend: null handle");

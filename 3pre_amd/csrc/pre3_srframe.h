@@ -36,7 +36,8 @@ struct pre3_sr_frame {
     double *spare = nullptr;
     // the owners (pre3_own.h): raw, filt, maxima, pinned_n and spare sit on `fixed`; the others grow on demand, each zeroed on the handle's stream when
     // it is new.  pair_dev / pair_pin: the pair stage's work block and its pinned image (pre3_vopair.hip), allocated on its first use
-    struct { pre3::BlockList fixed; pre3::PinBlock stage, pair_pin; pre3::DevBlock kp, pair_dev, text_dev; } mem;
+    // icp_dev: the device block of the ICP run pre3_predict_icp_pair_seeded queues on this handle (cur); the prediction reads it behind the call's return
+    struct { pre3::BlockList fixed; pre3::PinBlock stage, pair_pin; pre3::DevBlock kp, pair_dev, text_dev, icp_dev; } mem;
 };
 
 namespace pre3 {

@@ -24,6 +24,7 @@
 #include "pre3_predictu.h"
 #include "pre3_vocov.h"
 #include "pre3_icp.h"
+#include "pre3_predicticp.h"
 
 namespace pre3 {
 
@@ -228,8 +229,12 @@ void vp_cov_out(const VpPair &p, double *cov_out, int32_t *cov_status_out)
 }
 
 // the dense ICP queued behind the pair's launches (pre3_icp_pair_seeded)
-struct IcpAttach { int stride; double res; IcpOutputs out; };
-void icp_not_run(const IcpAttach *icp) { if (icp && icp->out.res) icp->out.res->sta = ICP_NOT_RUN; }
+struct IcpAttach { int stride; double res; IcpOutputs out; bool with_cov = false; };      // with_cov: pre3_icp_pair_cov_seeded
+void icp_not_run(const IcpAttach *icp)
+{
+    if (icp && icp->out.res) icp->out.res->sta = ICP_NOT_RUN;
+    if (icp && icp->out.cov_status) *icp->out.cov_status = VC_NOT_COMPUTED;
+}
 
 // pre3_vo_pair_seeded, and -- with_cov -- pre3_vo_pair_cov_seeded: the same launches, transfer and checks, k_vo_cov and its block besides;
 // icp != nullptr: pre3_icp_frames' launches behind them on the same stream, seeded from the pair's result block
@@ -244,9 +249,11 @@ int vo_pair_impl(const char *who, bool with_cov, pre3_sr_frame *prev, pre3_sr_fr
     PRE3_TRY(select_device(who, p.v2.device));
     if (pnum_out) *pnum_out = 0;
     if (cov_status_out) *cov_status_out = VC_NOT_COMPUTED;
+    if (icp && icp->out.cov_status) *icp->out.cov_status = VC_NOT_COMPUTED;
     if (vp_empty(p)) { vo_no_solution(res); icp_not_run(icp); return PRE3_OK; }      // siftmatch of an empty set: no match, nothing to queue
     PRE3_TRY(vp_queue(prev, cur, thresh, seed, seq, &p));
     IcpJob job;
+    job.with_cov = icp != nullptr && icp->with_cov;
     if (icp) PRE3_TRY(icp_job_queue_frames(&job, p.v1, p.v2, icp->stride, icp->res, nullptr, nullptr, (const VoOut *)(p.d + p.o_out), icp->out, p.v2.stream));
     size_t need = p.o_match;                    // the prefix of the block the caller's outputs reach into
     if (match_out) need = p.o_p1;
@@ -333,6 +340,75 @@ int predict_pair_impl(const char *who, bool with_cov, pre3_ctx *c, pre3_sr_frame
     if (res_out) vo_result(o, res_out);
     return PRE3_OK;
 }
+
+// the ICP run's device block from cur's handle (pre3_own.h: one owner, which outlives the prediction's read when no host waits)
+int icp_block_of_frame(void *owner, size_t bytes, char **out) { return sr_frame_icp_work((pre3_sr_frame *)owner, bytes, (void **)out); }
+
+// predict_pair_impl with the dense ICP and both covariances between the pair and the prediction (pre3_predict_icp_pair_seeded):
+// pre3_icp_pair_cov_seeded's launches on cur's stream, then k_predict on the context's with u and Pn taken on the device under predict_icp_select
+int predict_icp_pair_impl(const char *who, pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int stride, double res,
+                          double max_error, int noise, int32_t *pnum_out, pre3_vo_result *res_out, pre3_icp_result *icp_out, double *cov_out,
+                          int32_t *cov_status_out, int32_t *taken_out)
+{
+    static const double u_identity[7] = { 0, 0, 0, 1, 0, 0, 0 };
+    VpPair p;
+    p.with_cov = true;
+    PRE3_CHECK(c != nullptr, PRE3_E_ARG, "%s: null context", who);
+    PRE3_TRY(sr_frame_pair_views(who, prev, cur, thresh, &p.v1, &p.v2, &p.k1, &p.k2));
+    PRE3_TRY(icp_check_args(who, stride, res));
+    PRE3_CHECK(pi_max_error_ok(max_error), PRE3_E_ARG, "%s: max_error must be positive (+inf: no gate)", who);
+    PRE3_CHECK(noise >= PRE3_NOISE_CONTEXT && noise <= PRE3_NOISE_ICP_FLOOR, PRE3_E_ARG, "%s: noise is %d, not one of PRE3_NOISE_*", who, noise);
+    PRE3_CHECK(p.v2.device == c->device, PRE3_E_ARG, "%s: the frames are on device %d, the context on device %d", who, p.v2.device, c->device);
+    PRE3_CHECK(c->x_valid[PRE3_X_K_K] && c->p_which == PRE3_X_K_K, PRE3_E_STATE, "%s: needs (x_k_k, p_k_k) on the device", who);
+    EntryScope scope(c); PRE3_TRY(scope.rc);            // as pre3_predict's
+    const bool wait = pnum_out != nullptr || res_out != nullptr || icp_out != nullptr || cov_out != nullptr || cov_status_out != nullptr || taken_out != nullptr;
+    if (pnum_out) *pnum_out = 0;
+    if (cov_status_out) cov_status_out[0] = cov_status_out[1] = VC_NOT_COMPUTED;
+    if (taken_out) { taken_out[0] = PI_U_IDENTITY; taken_out[1] = PI_NOISE_CONTEXT; }
+    if (vp_empty(p)) {                                  // no pair launches, no ICP: the ordinary prediction with the identity increment
+        PRE3_TRY(launch_predict_impl(c, u_identity));
+        c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
+        vo_no_solution(res_out);
+        if (icp_out) icp_out->sta = ICP_NOT_RUN;
+        return PRE3_OK;
+    }
+    PRE3_TRY(vp_queue(prev, cur, thresh, seed, seq, &p));
+    const hipStream_t st = p.v2.stream;
+    IcpJob job;
+    job.with_cov = true; job.block = icp_block_of_frame; job.owner = cur; job.pin_back = wait;
+    const IcpOutputs io{ icp_out, nullptr, nullptr, nullptr, nullptr, cov_out ? cov_out + 49 : nullptr, cov_status_out ? cov_status_out + 1 : nullptr };
+    PRE3_TRY(icp_job_queue_frames(&job, p.v1, p.v2, stride, res, nullptr, nullptr, (const VoOut *)(p.d + p.o_out), io, st));
+    PRE3_TRY(sr_frame_reclaim(prev, st));               // prev is read by the pair's and the ICP's launches only
+    PRE3_TRY(sr_frame_lend(cur, c->stream));            // the prediction reads cur's work blocks behind the ICP's last launch
+    IcpDevView iv;
+    icp_job_dev_view(&job, &iv);
+    const PredictUIcp ui{ PredictIcpSrc{ (const VoOut *)(p.d + p.o_out), (const VoPairHeader *)p.d, (const VoCov *)(p.d + p.o_cov), iv.ctl, iv.u, iv.error, iv.cov,
+                                         max_error, noise }, c->stats + 6, iv.taken };
+    PRE3_TRY(launch_predict_icp(c, ui));
+    c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
+    if (wait) PRE3_HIP(hipMemcpyAsync(c->pinned_stats, c->stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, c->stream));
+    PRE3_TRY(sr_frame_reclaim(cur, c->stream));         // the next call's launches into these blocks, a load or a keypoint call on cur stay behind the reads
+    if (!wait) return PRE3_OK;
+
+    // one wait, on cur's stream, which now stands behind the prediction as well
+    PRE3_HIP(hipMemcpyAsync(p.pin, p.d, p.o_match, hipMemcpyDeviceToHost, st));
+    PRE3_HIP(hipMemcpyAsync(job.pin + job.o_pin_taken, iv.taken, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st));
+    PRE3_TRY(stream_drain_on(st, c->comm, who));
+    job.waited = true;
+    if (pu_word_refusal(c->pinned_stats[6]) != PU_OK) (void)hipMemsetAsync(c->stats + 6, 0, sizeof(int32_t), c->stream);      // reported by this call's return code
+    VoPairHeader h; VoOut o;
+    PRE3_TRY(vp_header(p, &h, &o));
+    if (pnum_out) *pnum_out = h.pnum;
+    if (h.pnum < 4) { vo_no_solution(res_out); if (icp_out) icp_out->sta = ICP_NOT_RUN; return PRE3_OK; }
+    PRE3_TRY(vp_refuse_bad(h));
+    PRE3_TRY(vp_refuse_near(o));
+    vp_cov_out(p, cov_out, cov_status_out);
+    if (res_out) vo_result(o, res_out);
+    PRE3_TRY(icp_job_collect(&job, who, io));
+    const int32_t *tk = (const int32_t *)(job.pin + job.o_pin_taken);
+    if (taken_out) { taken_out[0] = tk[0]; taken_out[1] = tk[1]; }
+    return PRE3_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -363,6 +439,27 @@ int pre3_icp_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh,
     const IcpAttach at{ stride, res, IcpOutputs{ icp, corr_out, corr_pix_out, data2_out, log_out } };
     return vo_pair_impl("pre3_icp_pair_seeded", false, prev, cur, thresh, seed, seq, pnum_out, match_out, pset1_out, pset2_out, draws_out, capped_out, cnum_out, state_out,
                         inlier_out, vo_res, nullptr, nullptr, &at);
+}
+
+// both covariances behind pre3_icp_pair_seeded: k_vo_cov behind the pair's final fit, k_icp_cov_part / k_icp_cov_fin behind k_icp_final
+int pre3_icp_pair_cov_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int stride, double res, int32_t *pnum_out,
+                             double *match_out, double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out,
+                             int32_t *state_out, int32_t *inlier_out, pre3_vo_result *vo_res, pre3_icp_result *icp, double *corr_out, int32_t *corr_pix_out,
+                             double *data2_out, double *log_out, double *cov_pair_out, int32_t *cov_pair_status_out, double *cov_icp_out,
+                             int32_t *cov_icp_status_out)
+{
+    const IcpAttach at{ stride, res, IcpOutputs{ icp, corr_out, corr_pix_out, data2_out, log_out, cov_icp_out, cov_icp_status_out }, true };
+    return vo_pair_impl("pre3_icp_pair_cov_seeded", true, prev, cur, thresh, seed, seq, pnum_out, match_out, pset1_out, pset2_out, draws_out, capped_out, cnum_out,
+                        state_out, inlier_out, vo_res, cov_pair_out, cov_pair_status_out, &at);
+}
+
+// the prediction fed from the ICP-refined pair, u and Pn chosen on the device
+int pre3_predict_icp_pair_seeded(pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int stride, double res,
+                                 double max_error, int noise, int32_t *pnum_out, pre3_vo_result *vo_res_out, pre3_icp_result *icp_out, double *cov_out,
+                                 int32_t *cov_status_out, int32_t *taken_out)
+{
+    return predict_icp_pair_impl("pre3_predict_icp_pair_seeded", c, prev, cur, thresh, seed, seq, stride, res, max_error, noise, pnum_out, vo_res_out, icp_out,
+                                 cov_out, cov_status_out, taken_out);
 }
 
 int pre3_predict_pair_seeded(pre3_ctx *c, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out,

@@ -677,6 +677,42 @@ class EkfFilter:
         out["cov"] = cov if out["cov_status"] == 1 else None
         return out
 
+    def ekf_prediction_icp_pair_seeded(self, prev, cur, seed, seq=0, thresh=1.5, stride=1, res=0.02, max_error=float("inf"), noise=0, wait=True):
+        """ekf_prediction_pair_seeded with the dense ICP between the pair and the prediction: vo.icp_pair_cov_seeded's launches,
+        then the prediction with u and Pn taken on the device.  u: the ICP's when the pair's is taken (sta == 1), the ICP ended with sta == 1, its u is
+        finite and its error <= max_error; else the pair's; the identity when the pair is not taken.  noise: 0 this filter's own (set_process_noise, or
+        the constant), 1 the pair's covariance as ekf_prediction_pair_cov_seeded takes it, 2 the ICP's closed-form covariance when the ICP's u is taken
+        and its status is 1 (else as 1), 3 as 2 with this filter's own noise added to it entry by entry.  Mode 2 is optimistic -- it propagates sensor
+        noise only --, mode 3 lets set_process_noise act as a floor.  The filter's noise setting is unchanged afterwards.
+        wait=True: one host wait; the dict of ekf_prediction_pair_seeded plus cov_status / cov (the pair's), icp (dict(sta=0) when it did not run, else
+        R, t, Rtot, ttot, u, error, sta, p, iters1, iters2, n_model, n_source, cov_status, cov) and taken = (which u: 0 identity, 1 pair, 2 ICP; which
+        noise: 0 .. 3).  wait=False: returns None at once, nothing is synchronised."""
+        from . import vo
+        args = (self._ctx, prev._h, cur._h, float(thresh), int(seed), int(seq), int(stride), float(res), float(max_error), int(noise))
+        if not wait:
+            check(lib.pre3_predict_icp_pair_seeded(*args, None, None, None, None, None, None))
+            return None
+        pnum, res_, r = C.c_int32(0), vo.VoResult(), vo.IcpResult()
+        cov, status, taken = np.zeros((2, 7, 7)), np.zeros(2, np.int32), np.zeros(2, np.int32)
+        check(lib.pre3_predict_icp_pair_seeded(*args, C.byref(pnum), C.byref(res_), C.byref(r), dptr(cov), dptr(status), dptr(taken)))
+        pnum = int(pnum.value)
+        out = vo._result(res_, None, None, None)
+        for k in ("cnum", "state", "inliers"):
+            del out[k]
+        out["pnum"], out["rst"] = pnum, (vo.vo_rst(pnum) if pnum >= 4 else 0)
+        out["cov_status"] = int(status[0])
+        out["cov"] = cov[0].copy() if out["cov_status"] == 1 else None
+        if int(r.sta) == 0:
+            icp = dict(sta=0)
+        else:
+            icp = dict(R=np.array(r.R).reshape(3, 3), t=np.array(r.t), Rtot=np.array(r.Rtot).reshape(3, 3), ttot=np.array(r.ttot), u=np.array(r.u),
+                       error=float(r.error), sta=int(r.sta), p=int(r.p), iters1=int(r.iters1), iters2=int(r.iters2), n_model=int(r.n_model),
+                       n_source=int(r.n_source))
+        icp["cov_status"] = int(status[1])
+        icp["cov"] = cov[1].copy() if icp["cov_status"] == 1 else None
+        out["icp"], out["taken"] = icp, (int(taken[0]), int(taken[1]))
+        return out
+
     def set_process_noise(self, Pn=None):
         """predict_state_and_covariance.m:98-102: the 7 x 7 process noise Pn of every prediction this filter makes from now on (ekf_prediction, step*,
         ekf_prediction_pair_seeded); None returns to the reference's constant.  Must be finite, exactly symmetric and without a negative diagonal

@@ -478,6 +478,18 @@ def ekf_prediction_frames_cov(filt, step, frames, seed, seq=0, thresh=1.5, wait=
     return _prediction_frames(filt, step, frames, seed, seq, thresh, wait, "pair")
 
 
+def ekf_prediction_frames_icp(filt, step, frames, seed, seq=0, thresh=1.5, stride=1, res=0.02, max_error=float("inf"), noise=0, wait=True):
+    """ekf_prediction_frames with the dense ICP refining the pair's pose on the same two resident frames in front of the prediction
+    (EkfFilter.ekf_prediction_icp_pair_seeded): the ICP's u when it ended by the reference's rule within max_error, with the
+    process noise `noise` names (0 the filter's own, 1 the pair's covariance, 2 the ICP's closed-form covariance, 3 that plus the filter's own).  The
+    identity frames are predicted with the filter's own noise."""
+    pair = fv_pair(step)
+    if pair is None:
+        filt.ekf_prediction([0, 0, 0, 1, 0, 0, 0])
+        return None
+    return filt.ekf_prediction_icp_pair_seeded(frames[pair[0]], frames[pair[1]], seed, seq, thresh, stride, res, max_error, noise, wait)
+
+
 def _prediction_frames(filt, step, frames, seed, seq, thresh, wait, noise):
     pair = fv_pair(step)
     if pair is None:

@@ -324,6 +324,69 @@ def icp_pair_seeded(prev, cur, seed, seq=0, thresh=1.5, stride=1, res=0.02):
     return pair, _icp_result(r, corr, out2, log, pix)
 
 
+def icp_cov_limits():
+    """dict(pairs_per_workgroup, partials_per_thread): the pairs one workgroup of the partial-sum launch owns, and the partials a thread of the finishing
+    workgroup adds at the largest supported p (pre3_icp_cov_limits); max_pairs = 256 x pairs_per_workgroup x partials_per_thread"""
+    out = np.zeros(2, np.int32)
+    check(lib.pre3_icp_cov_limits(dptr(out)))
+    return dict(pairs_per_workgroup=int(out[0]), partials_per_thread=int(out[1]), max_pairs=256 * int(out[0]) * int(out[1]))
+
+
+def icp_cov(data1, data2, corr, u, device=0):
+    """The closed-form covariance of the ICP's u = [T; q] over its final pairs, stateless: data1 (3, n1) the model, data2 (3, n2)
+    the ORIGINAL source (as icp_with_init took it), corr (p, 2) or icp_with_init's (p, 3): 1-based (model, source) rows, u the run's u.
+    Returns dict(cov (7, 7) or None, status, n): status 0 not computed (p < 4), 1 valid, 2 unusable.  It propagates sensor noise only and is
+    optimistic as a process noise."""
+    d1, d2 = np.ascontiguousarray(f64(data1).T), np.ascontiguousarray(f64(data2).T)
+    assert d1.ndim == 2 and d2.ndim == 2 and d1.shape[1] == 3 and d2.shape[1] == 3
+    c = np.asarray(corr)
+    c = np.ascontiguousarray(c.reshape(-1, c.shape[-1] if c.ndim == 2 else 2)[:, :2].astype(np.int32))
+    u = f64(u).reshape(7)
+    cov, status, n = np.zeros((7, 7)), C.c_int32(0), C.c_int32(0)
+    check(lib.pre3_icp_cov(int(device), dptr(d1), d1.shape[0], dptr(d2), d2.shape[0], dptr(c), c.shape[0], dptr(u), dptr(cov), C.byref(status), C.byref(n)))
+    st = int(status.value)
+    return dict(cov=cov if st == 1 else None, status=st, n=int(n.value))
+
+
+def icp_cov_bench(data1, data2, corr, u, reps=50, device=0):
+    """milliseconds of icp_cov's two launches on resident operands (measurement only)"""
+    d1, d2 = np.ascontiguousarray(f64(data1).T), np.ascontiguousarray(f64(data2).T)
+    c = np.ascontiguousarray(np.asarray(corr)[:, :2].astype(np.int32))
+    u = f64(u).reshape(7)
+    ms = C.c_double(0)
+    check(lib.pre3_icp_cov_bench(int(device), dptr(d1), d1.shape[0], dptr(d2), d2.shape[0], dptr(c), c.shape[0], dptr(u), int(reps), C.byref(ms)))
+    return ms.value
+
+
+def icp_pair_cov_seeded(prev, cur, seed, seq=0, thresh=1.5, stride=1, res=0.02):
+    """icp_pair_seeded with both covariances behind it on the device, still one host wait.  Returns (pair, icp): the dicts of
+    icp_pair_seeded, bit for bit; pair has vo_pair_cov_seeded's cov_status and cov besides, icp has cov_status (0 not computed: the ICP did not end in
+    sta == 1, or p < 4; 1 valid; 2 unusable) and cov -- the (7, 7) covariance of icp["u"] on status 1, else None."""
+    n1 = max(int(getattr(prev, "n_kept", 0)), 1)
+    pnum, capped = C.c_int32(0), C.c_int32(0)
+    match = np.zeros((2, n1), order="F")
+    p1, p2 = np.zeros((n1, 3)), np.zeros((n1, 3))
+    draws, cnum, state, inl = np.zeros((700, 4), np.int32), np.zeros(700, np.int32), np.zeros(700, np.int32), np.zeros(n1, np.int32)
+    vres, r = VoResult(), IcpResult()
+    corr, pix, out2, log, _ = _icp_frame_buffers(cur, stride)
+    cov_p, st_p, cov_i, st_i = np.zeros((7, 7)), C.c_int32(0), np.zeros((7, 7)), C.c_int32(0)
+    check(lib.pre3_icp_pair_cov_seeded(prev._h, cur._h, float(thresh), int(seed), int(seq), int(stride), float(res), C.byref(pnum), dptr(match), dptr(p1),
+                                       dptr(p2), dptr(draws), C.byref(capped), dptr(cnum), dptr(state), dptr(inl), C.byref(vres), C.byref(r), dptr(corr),
+                                       dptr(pix), dptr(out2), dptr(log), dptr(cov_p), C.byref(st_p), dptr(cov_i), C.byref(st_i)))
+    pnum = int(pnum.value)
+    rst = vo_rst(pnum) if pnum >= 4 else 0
+    pair = _result(vres, cnum[:rst].copy(), state[:rst].copy(), inl[:pnum if rst else 0].copy())
+    pair["pset1"], pair["pset2"] = p1[:pnum if rst else 0].T.copy(), p2[:pnum if rst else 0].T.copy()
+    pair["draws"], pair["capped"] = draws[:rst].copy(), int(capped.value)
+    pair["match"], pair["pnum"], pair["rst"] = match[:, :pnum].copy(order="F"), pnum, rst
+    pair["cov_status"] = int(st_p.value)
+    pair["cov"] = cov_p if pair["cov_status"] == 1 else None
+    icp = _icp_result(r, corr, out2, log, pix)
+    icp["cov_status"] = int(st_i.value)
+    icp["cov"] = cov_i if icp["cov_status"] == 1 else None
+    return pair, icp
+
+
 def icp_nn_bench(data1, data2, reps=20, device=0):
     """milliseconds of one nearest-neighbour launch on resident clouds (measurement only)"""
     d1, d2 = np.ascontiguousarray(f64(data1).T), np.ascontiguousarray(f64(data2).T)

@@ -1020,6 +1020,65 @@ PRE3_API int pre3_icp_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, doubl
 /* measurement only: the nearest-neighbour launch of one iteration on resident clouds, averaged over reps */
 PRE3_API int pre3_icp_nn_bench(int device, const double *data1, int n1, const double *data2, int n2, int reps, double *ms_per_launch_out);
 
+/* ---- the closed-form covariance of the ICP's increment over its final correspondences -------------------------------------------
+ * aux_code/d2E_*_4cov.m, dE_*_4cov.m and Calc_derivatives_for_covariance.m (the derivatives of the rigid fit's energy) with
+ * aux_code/cov_pose_shift_calc.m:24-40 (the SR4000's per-point range and angle noise), evaluated over the pairs TestScripts/icp_with_init.m:76-89 ends
+ * with: pre3_vo_cov's cov = H^-1 M H^-1 (pre3_vocov.h), with f_p = data1(:, corr(k, 1)) the model point and f_n = data2(:, corr(k, 2)) the ORIGINAL
+ * source point -- data2 as pre3_icp took it, before Rinit / Tinit and before any registration step -- and r = T + R(q) f_n - f_p, u = [T; q] = the run's
+ * u (data1 ~ Rtot data2 + ttot).  Stateless, host in and host out: data1 3 x n1, data2 3 x n2 (column-major), corr[p][2] int32 1-based (model, source)
+ * rows, u[7].  Two launches: one partial sum per 256 pairs, then one workgroup that adds the partials in a tree whose shape depends on p alone, factors H
+ * and solves; all fp64, no floating-point atomics, bit-equal from run to run.  *status_out: 0 not computed (p < 4), 1 valid, 2 unusable (a non-finite
+ * coordinate in a pair, a Cholesky pivot of H at or below 7 eps times its diagonal entry, a non-finite result).  cov_out[49] (row-major, symmetric) is
+ * written on status 1 only; *n_out (may be NULL) the pairs summed.  PRE3_E_ARG before anything is queued: a null cloud, list, u or status_out, an empty
+ * cloud, p < 0 or beyond 256 x 256 x limits[1] pairs, an index outside its cloud.  Synchronises.
+ * The estimate propagates sensor noise only: on two independent samplings of one surface it gives a sigma_T of millimetres while the registration itself
+ * ends centimetres from the true pose, so as a process noise it is optimistic. */
+PRE3_API int pre3_icp_cov(int device, const double *data1, int n1, const double *data2, int n2, const int32_t *corr, int p, const double u[7],
+                          double *cov_out, int32_t *status_out, int32_t *n_out);
+/* out = { pairs per workgroup of the partial-sum launch, partials a thread of the finishing workgroup adds at the largest supported p } */
+PRE3_API int pre3_icp_cov_limits(int32_t out[2]);
+/* measurement only: pre3_icp_cov's two launches on resident operands (p >= 4), back to back between two events, averaged over reps */
+PRE3_API int pre3_icp_cov_bench(int device, const double *data1, int n1, const double *data2, int n2, const int32_t *corr, int p, const double u[7],
+                                int reps, double *ms_per_pair_of_launches_out);
+/* pre3_icp_pair_seeded with both covariances behind it, still one host wait: k_vo_cov behind the pair's final fit (pre3_vo_pair_cov_seeded's), and the two
+ * launches of pre3_icp_cov behind the ICP's last launch, reading the final pairs, the model, u and -- through the kept-pixel list -- cur's filtered planes
+ * as [-x; -y; z] where they lie.  Every output shared with pre3_icp_pair_seeded is bit-equal to that call's, as are its refusals and errors; cov_pair_out
+ * and *cov_pair_status_out are pre3_vo_pair_cov_seeded's.  *cov_icp_status_out: 0 not computed (the ICP did not end in sta == 1, or p < 4), 1, 2 as
+ * pre3_icp_cov's; cov_icp_out[49] is written on status 1 only and is then bit-equal to pre3_icp_cov fed the two clouds gathered through corr_pix_out, this
+ * call's pairs and icp->u.  Each of the four may be NULL. */
+PRE3_API int pre3_icp_pair_cov_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int stride, double res,
+                                      int32_t *pnum_out, double *match_out, double *pset1_out, double *pset2_out, int32_t *draws_out,
+                                      int32_t *capped_out, int32_t *cnum_out, int32_t *state_out, int32_t *inlier_out, pre3_vo_result *vo_res,
+                                      pre3_icp_result *icp, double *corr_out, int32_t *corr_pix_out, double *data2_out, double *log_out,
+                                      double *cov_pair_out, int32_t *cov_pair_status_out, double *cov_icp_out, int32_t *cov_icp_status_out);
+
+/* The prediction fed from the ICP-refined pair on the device (fv.m:47 + Calculate_V_Omega_RANSAC_dr_ye.m:41-50 + predict_state_and_covariance.m:27-143,
+ * :115 with TestScripts/icp_with_init.m's refinement in between -- the RANSAC_CALC_VER_test.m:77-78 the reference leaves commented out): the launches of
+ * pre3_icp_pair_cov_seeded on cur's stream, then k_predict on the context's with u and Pn chosen on the device; neither u nor a covariance crosses PCIe.
+ *   u:  the pair not taken (pre3_predict_pair_seeded's rule: pnum < 4, a refused pair, sta != 1): the identity increment, refusals reported exactly as
+ *       pre3_predict_pair_seeded reports them.  The pair taken: the ICP's u when icp sta == 1, every entry of it is finite and icp error <= max_error
+ *       (+inf: no gate); otherwise the pair's own u.
+ *   Pn: `noise` is one of */
+#define PRE3_NOISE_CONTEXT 0    /* the context's own noise: pre3_set_process_noise's, or the constant */
+#define PRE3_NOISE_PAIR 1       /* the pair's RANSAC covariance under pre3_predict_pair_cov_seeded's rule, else the context's */
+#define PRE3_NOISE_ICP 2        /* the ICP's covariance when the ICP's u is taken and its status is 1; else as PRE3_NOISE_PAIR */
+#define PRE3_NOISE_ICP_FLOOR 3  /* as PRE3_NOISE_ICP, but Pn = cov_icp + the context's noise, one fp64 addition per entry */
+/* PRE3_NOISE_ICP is the published closed-form estimator and is optimistic: it propagates sensor noise only (see pre3_icp_cov).  PRE3_NOISE_ICP_FLOOR lets
+ * pre3_set_process_noise act as a floor under it.
+ * taken_out[2] = { which u: 0 identity, 1 the pair's, 2 the ICP's; which noise: a PRE3_NOISE_* value }.  cov_out[2][49] / cov_status_out[2]: the pair's
+ * and the ICP's covariance and status as pre3_icp_pair_cov_seeded hands them out (cov written on status 1 only).  With every output NULL nothing is
+ * synchronised; otherwise the call waits once.  Afterwards the context (x_k_km1, P, the prediction's parameters, pending rows, flags) is bit-identical
+ * to the chain pre3_icp_pair_cov_seeded -> the rule above on the host -> pre3_set_process_noise(the taken Pn) when one is taken -> pre3_predict(the
+ * taken u) -> the previous setting restored (as for pre3_predict_pair_seeded, the identity's zeros are +0), and the context's noise setting is unchanged.
+ * (One combination has no such chain: PRE3_NOISE_ICP_FLOOR on a context that runs on the constant, whose quaternion block is symmetric only to the last
+ * place as the launch builds it, so pre3_set_process_noise would refuse the sum; the prediction adds the two blocks entry by entry all the same.)
+ * PRE3_E_ARG / PRE3_E_STATE before anything is queued, the context and both handles unchanged: everything pre3_predict_pair_seeded and
+ * pre3_icp_pair_seeded refuse there, max_error NaN or <= 0, noise outside 0 .. 3.  The ICP's device block belongs to cur's handle and outlives the
+ * prediction's read.  Calls that share a handle or the context must be serialised by the caller. */
+PRE3_API int pre3_predict_icp_pair_seeded(pre3_ctx *ctx, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int stride,
+                                          double res, double max_error, int noise, int32_t *pnum_out, pre3_vo_result *vo_res_out,
+                                          pre3_icp_result *icp_out, double *cov_out, int32_t *cov_status_out, int32_t *taken_out);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them

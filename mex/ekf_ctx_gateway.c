@@ -630,6 +630,52 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         if (nout > 4) { out[4] = mxCreateDoubleMatrix(7, 7, mxREAL); memcpy(mxGetPr(out[4]), cov, sizeof cov); }
         if (nout > 5) out[5] = mxCreateDoubleScalar(cst);
     }
+    else if (!strcmp(cmd, "icp_cov")) {           /* [cov, status, n] = pre3_mex('icp_cov', data1, data2, corr, T, q): the closed-form covariance of the ICP's [T; q] over its final
+                                                     pairs -- data1 3 x n1 the model, data2 3 x n2 the source AS icp_with_init TOOK IT (before Rinit, Tinit), corr p x 2 or p x 3 as
+                                                     icp_with_init returns it (1-based model, source), T 3 x 1 and q 4 x 1 of the run's u (data1 ~ R(q) data2 + T).  cov 7 x 7
+                                                     (zeros unless status == 1); status 0 fewer than four pairs, 1 valid, 2 unusable (pre3_icp_cov, on device 0).  Sensor noise
+                                                     only: optimistic as a process noise */
+        double u[7]; int32_t status = 0, n = 0, *cr; int i, rc; mwSize p, n1, n2;
+        if (nin != 6) mexErrMsgTxt("pre3_mex('icp_cov', data1, data2, corr, T, q): five arguments");
+        n1 = mxGetN(in[1]); n2 = mxGetN(in[2]); p = mxGetM(in[3]);
+        if (!mxIsDouble(in[1]) || !mxIsDouble(in[2]) || !mxIsDouble(in[3]) || !mxIsDouble(in[4]) || !mxIsDouble(in[5]) || mxGetM(in[1]) != 3 || mxGetM(in[2]) != 3
+            || (p > 0 && mxGetN(in[3]) != 2 && mxGetN(in[3]) != 3) || mxGetNumberOfElements(in[4]) != 3 || mxGetNumberOfElements(in[5]) != 4)
+            mexErrMsgTxt("pre3_mex('icp_cov'): data1 3 x n1, data2 3 x n2, corr p x 2 or p x 3, T 3 x 1, q 4 x 1 (all double)");
+        memcpy(u, mxGetPr(in[4]), sizeof(double) * 3); memcpy(u + 3, mxGetPr(in[5]), sizeof(double) * 4);
+        cr = (int32_t *)mxMalloc(sizeof(int32_t) * 2 * (p ? p : 1));
+        for (i = 0; i < (int)p; ++i) { cr[2 * i] = (int32_t)mxGetPr(in[3])[i]; cr[2 * i + 1] = (int32_t)mxGetPr(in[3])[i + p]; }      /* column-major p x k -> rows */
+        out[0] = mxCreateDoubleMatrix(7, 7, mxREAL);
+        rc = pre3_icp_cov(0, mxGetPr(in[1]), (int)n1, mxGetPr(in[2]), (int)n2, cr, (int)p, u, mxGetPr(out[0]), &status, &n);
+        mxFree(cr);
+        check(rc);
+        if (nout > 1) out[1] = mxCreateDoubleScalar(status);
+        if (nout > 2) out[2] = mxCreateDoubleScalar(n);
+    }
+    else if (!strcmp(cmd, "predict_icp_pair")) {  /* [T, q, sta, icp_sta, taken, cov_pair, cov_icp, cov_status] = pre3_mex('predict_icp_pair', seed, seq, res [, stride = 1, max_error = inf,
+                                                     noise = 0, thresh = 1.5]): 'predict_pair' with the dense ICP of 'icp_pair' between the pair and the prediction -- the ICP's [T; q]
+                                                     when the pair's is taken, icp_sta == 1, it is finite and its error <= max_error; noise 0 the context's own, 1 the pair's covariance,
+                                                     2 the ICP's closed-form covariance, 3 that plus the context's own (PRE3_NOISE_*).  T, q: the increment taken (taken(1): 0 identity,
+                                                     1 the pair's, 2 the ICP's; taken(2): the noise taken).  Without output arguments nothing is waited for (pre3_predict_icp_pair_seeded) */
+        pre3_vo_result r; pre3_icp_result ir; int32_t pnum = 0, cst[2] = { 0, 0 }, tk[2] = { 0, 0 }; double cov[98]; const double *u; int i;
+        static const double u_id[7] = { 0, 0, 0, 1, 0, 0, 0 };
+        if (nin < 4 || nin > 8) mexErrMsgTxt("pre3_mex('predict_icp_pair', seed, seq, res [, stride, max_error, noise, thresh]): three to seven arguments");
+        if (!g_sr || !g_sr_prev) mexErrMsgTxt("pre3_mex('predict_icp_pair'): needs two frames -- 'sr_frame' + 'sr_keypoints', 'sr_keep', then 'sr_frame' + 'sr_keypoints' again");
+        for (i = 0; i < 98; ++i) cov[i] = 0;
+        memset(&ir, 0, sizeof ir); memset(&r, 0, sizeof r);
+        check(pre3_predict_icp_pair_seeded(g_ctx, g_sr_prev, g_sr, nin > 7 ? mxGetScalar(in[7]) : 1.5, (uint64_t)mxGetScalar(in[1]), (uint64_t)mxGetScalar(in[2]),
+                                           nin > 4 ? (int)mxGetScalar(in[4]) : 1, mxGetScalar(in[3]), nin > 5 ? mxGetScalar(in[5]) : mxGetInf(),
+                                           nin > 6 ? (int)mxGetScalar(in[6]) : PRE3_NOISE_CONTEXT, nout > 0 ? &pnum : NULL, nout > 0 ? &r : NULL, nout > 0 ? &ir : NULL,
+                                           nout > 0 ? cov : NULL, nout > 0 ? cst : NULL, nout > 0 ? tk : NULL));
+        u = tk[0] == 2 ? ir.u : tk[0] == 1 ? r.u : u_id;
+        if (nout > 0) { out[0] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[0]), u, sizeof(double) * 3); }
+        if (nout > 1) { out[1] = mxCreateDoubleMatrix(4, 1, mxREAL); memcpy(mxGetPr(out[1]), u + 3, sizeof(double) * 4); }
+        if (nout > 2) out[2] = mxCreateDoubleScalar(r.sta);
+        if (nout > 3) out[3] = mxCreateDoubleScalar(ir.sta);
+        if (nout > 4) { out[4] = mxCreateDoubleMatrix(1, 2, mxREAL); mxGetPr(out[4])[0] = tk[0]; mxGetPr(out[4])[1] = tk[1]; }
+        if (nout > 5) { out[5] = mxCreateDoubleMatrix(7, 7, mxREAL); memcpy(mxGetPr(out[5]), cov, sizeof(double) * 49); }
+        if (nout > 6) { out[6] = mxCreateDoubleMatrix(7, 7, mxREAL); memcpy(mxGetPr(out[6]), cov + 49, sizeof(double) * 49); }
+        if (nout > 7) { out[7] = mxCreateDoubleMatrix(1, 2, mxREAL); mxGetPr(out[7])[0] = cst[0]; mxGetPr(out[7])[1] = cst[1]; }
+    }
     else if (!strcmp(cmd, "map_delete")) {        /* pre3_mex('map_delete', idx (0-based, ascending))   delete_features.m:54-74 */
         int k = (int)mxGetNumberOfElements(in[1]), i, rc; int32_t *d = (int32_t *)mxMalloc(sizeof(int32_t) * (k ? k : 1));
         for (i = 0; i < k; ++i) d[i] = (int32_t)mxGetPr(in[1])[i];
