@@ -14,25 +14,7 @@ namespace pre3 {
 // device helpers
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 
-// undistort_fm_my_version.m:56-81 (ten Newton steps, :64-67)
-__device__ inline void d_undistort10(const CamD &cam, double ud, double vd, double *u, double *v)
-{
-    const double xd = (ud - cam.Cx) / cam.f, yd = (vd - cam.Cy) / cam.f;
-    const double rd = sqrt(xd * xd + yd * yd);
-    const double rd2 = rd * rd;
-    double ru = rd / (1 + cam.k1 * rd2 + cam.k2 * (rd2 * rd2));
-#pragma unroll 1
-    for (int k = 0; k < 10; ++k) {
-        const double r2 = ru * ru;
-        const double f1 = ru + cam.k1 * (r2 * ru) + cam.k2 * (r2 * r2 * ru) - rd;
-        const double f1p = 1 + 3 * cam.k1 * r2 + 5 * cam.k2 * (r2 * r2);
-        ru = ru - f1 / f1p;
-    }
-    const double r2 = ru * ru;
-    const double D = 1 + cam.k1 * r2 + cam.k2 * (r2 * r2);
-    *u = cam.f * xd / D + cam.Cx;
-    *v = cam.f * yd / D + cam.Cy;
-}
+// (d_undistort10, undistort_fm_my_version.m's ten Newton steps: pre3_geomdev.h, shared with pre3_pnp.hip)
 // distort_fm_my_version.m:52-61
 __device__ inline void d_distort(const CamD &cam, double u, double v, double *ud, double *vd)
 {

@@ -3,7 +3,7 @@
 // function of (counter[4], key[2]); no state lives anywhere.  numpy.random.Philox is the same generator (it advances the counter before its first
 // block): tests/test_draws_ref.py pins tests/draws_ref.py's restatement against it, tests/test_gpu_draws.py the kernels against the restatement.
 //   key     = [seed, stream]               stream 1: 1-point RANSAC, 2: VO 4-point RANSAC, 3: floor-plane RANSAC, 4: the candidates' weighted order,
-//                                          5: initialize_a_feature's box centres (counter [attempt, 0, seq, 0])
+//                                          5: initialize_a_feature's box centres (counter [attempt, 0, seq, 0]), 6: the EPnP RANSAC's samples
 //   counter = [index, attempt, seq, 0]     index: the hypothesis; attempt: the redraw number (0 = first draw); seq: the caller's frame / step number
 // A bounded integer in [0, range) is the high 64 bits of word * range: no rejection, so value v is drawn with probability floor- or ceil-(2^64 / range)
 // / 2^64 -- a bias of at most range / 2^64 (below 2^-50 for every range of this library).  A uniform double is the word's top 53 bits times 2^-53.
@@ -23,7 +23,8 @@ namespace pre3 {
 constexpr uint64_t PHILOX_M0 = 0xD2E7470EE14C6C93ull, PHILOX_M1 = 0xCA5A826395121157ull;
 constexpr uint64_t PHILOX_W0 = 0x9E3779B97F4A7C15ull, PHILOX_W1 = 0xBB67AE8584CAA73Bull;
 enum { DRAW_STREAM_1P = 1, DRAW_STREAM_VO = 2, DRAW_STREAM_PLANE = 3, DRAW_STREAM_CAND = 4,
-       DRAW_STREAM_FAST = 5 /* initialize_a_feature.m:64: counter [attempt, 0, seq, 0], words 0 and 1 -> the box centre's two uniforms */ };
+       DRAW_STREAM_FAST = 5 /* initialize_a_feature.m:64: counter [attempt, 0, seq, 0], words 0 and 1 -> the box centre's two uniforms */,
+       DRAW_STREAM_PNP = 6 /* the EPnP RANSAC's six-point samples: counter [hypothesis, block 0 or 1, seq, 0] */ };
 constexpr int VO_MAX_REDRAWS = 64;          // per position; ransac_dr_ye.m:28-46 loops for ever
 constexpr int PLANE_MAX_ATTEMPTS = 100;     // ransac.m:122 maxDataTrials
 
@@ -71,6 +72,26 @@ PRE3_HD void draw_three_distinct(int m, const PhiloxBlock &b, int32_t out[3])
     if (i2 >= lo) ++i2;
     if (i2 >= hi) ++i2;
     out[0] = i0; out[1] = i1; out[2] = i2;
+}
+
+// ---- the EPnP RANSAC's table (pre3_pnp.hip): six distinct of n (n >= 6) for hypothesis h -- ranks in [0,n), [0,n-1), ..., [0,n-5),
+// each later one shifted past the earlier picks in ascending order: draw_three_distinct's rule continued.  Ranks 0..3 are words 0..3 of
+// block(h, 0, seq), ranks 4 and 5 words 0 and 1 of block(h, 1, seq).  No redraws; every index a compile-time one (no per-lane array in memory).
+PRE3_HD void draw_rule_pnp(uint64_t seed, uint64_t seq, int n, int h, int32_t out[6])
+{
+    const PhiloxBlock b0 = draw_block(seed, DRAW_STREAM_PNP, (uint64_t)h, 0, seq), b1 = draw_block(seed, DRAW_STREAM_PNP, (uint64_t)h, 1, seq);
+    int32_t sorted[6] = { 0, 0, 0, 0, 0, 0 };
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        int r = draw_bounded(j < 4 ? b0.w[j & 3] : b1.w[j & 3], n - j);
+#pragma unroll
+        for (int s = 0; s < j; ++s) if (r >= sorted[s]) ++r;
+        out[j] = r;
+        sorted[j] = r;
+#pragma unroll
+        for (int s = j; s > 0; --s)
+            if (sorted[s - 1] > sorted[s]) { const int32_t t = sorted[s]; sorted[s] = sorted[s - 1]; sorted[s - 1] = t; }
+    }
 }
 
 // ---- select_random_match.m:40-51: k positions of hypothesis h in the individually compatible list of m (k = 3 when m > 3, else 1; m == 0: zero)

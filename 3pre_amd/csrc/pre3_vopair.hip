@@ -15,6 +15,8 @@
 // pre3_vo_ransac_frames_seeded fed the same match list with n_hyp = rst.
 // pre3_predict_pair_seeded queues the same eight launches through the same host path (vp_queue) and puts the prediction behind
 // them on the context's stream: k_predict reads u from the VoOut block k_vp_final wrote, so the increment never reaches the host.
+// pre3_vo_pair_pnp_seeded queues two more launches behind the eight (launch_pnp_pair, pre3_pnp.hip): the EPnP refit over the pair's
+// inliers, prev's range points against cur's pixels; its pixels and result ride in the same transfer.
 #include <cmath>
 
 #include "pre3_internal.h"
@@ -25,6 +27,7 @@
 #include "pre3_vocov.h"
 #include "pre3_icp.h"
 #include "pre3_predicticp.h"
+#include "pre3_pnp.h"
 
 namespace pre3 {
 
@@ -154,6 +157,8 @@ struct VpPair {
     SrFrameView v1, v2; SrKeypointView k1, k2;
     size_t o_out, o_match, o_p1, o_p2, o_draws, o_cnum, o_state, o_inl, o_end;
     bool with_cov = false; size_t o_cov = 0;        // the *_cov_* entry points: a VoCov block behind the result block, k_vo_cov behind k_vp_final
+    // pre3_vo_pair_pnp_seeded: cur's pixels of the matches and the EPnP result behind the inlier flags, inside the transfer
+    const pre3_cam *pnp_cam = nullptr; int pnp_undistort = 0; size_t o_pix = 0, o_pnp = 0;
     char *d = nullptr, *pin = nullptr;              // cur's device work block and its pinned image
 };
 bool vp_empty(const VpPair &p) { return p.k1.n_kept == 0 || p.k2.n_kept == 0; }
@@ -169,10 +174,13 @@ int vp_queue(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t se
     const size_t o_p1 = o_match + up16(sizeof(double) * 2 * (size_t)n1);
     const size_t o_p2 = o_p1 + up16(sizeof(double) * 3 * (size_t)n1), o_draws = o_p2 + up16(sizeof(double) * 3 * (size_t)n1);
     const size_t o_cnum = o_draws + up16(sizeof(int32_t) * 4 * VO_RST_CAP), o_state = o_cnum + up16(sizeof(int32_t) * VO_RST_CAP);
-    const size_t o_inl = o_state + up16(sizeof(int32_t) * VO_RST_CAP), o_end = o_inl + up16(sizeof(int32_t) * (size_t)n1);
-    const size_t o_part = o_end, o_masks = o_part + vp_match_part_bytes(n1, n2), total = o_masks + sizeof(unsigned long long) * (size_t)VO_RST_CAP * wcap;
+    const bool pnp = q->pnp_cam != nullptr;
+    const size_t o_inl = o_state + up16(sizeof(int32_t) * VO_RST_CAP), o_pix = o_inl + up16(sizeof(int32_t) * (size_t)n1);
+    const size_t o_pnp = pnp ? o_pix + up16(sizeof(double) * 2 * (size_t)n1) : o_pix, o_end = pnp ? o_pnp + up16(sizeof(pre3_pnp_result)) : o_pix;
+    const size_t o_part = o_end, o_masks = o_part + vp_match_part_bytes(n1, n2), o_list = up16(o_masks + sizeof(unsigned long long) * (size_t)VO_RST_CAP * wcap);
+    const size_t total = pnp ? o_list + sizeof(int32_t) * ((size_t)n1 + 4) : o_masks + sizeof(unsigned long long) * (size_t)VO_RST_CAP * wcap;
     q->o_out = o_out; q->o_match = o_match; q->o_p1 = o_p1; q->o_p2 = o_p2; q->o_draws = o_draws; q->o_cnum = o_cnum; q->o_state = o_state;
-    q->o_inl = o_inl; q->o_end = o_end; q->o_cov = o_cov;
+    q->o_inl = o_inl; q->o_end = o_end; q->o_cov = o_cov; q->o_pix = o_pix; q->o_pnp = o_pnp;
     char *d = nullptr;
     PRE3_TRY(sr_frame_pair_work(cur, total, o_end, (void **)&d, (void **)&q->pin));
     q->d = d;
@@ -197,6 +205,8 @@ int vp_queue(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t se
     PRE3_HIP(hipGetLastError());
     // (the memset above left status = 0 in the block; pset1, pset2 and inl hold n1 positions, which bounds the launch whatever the header says)
     if (q->with_cov) PRE3_TRY(launch_vo_cov_pair(hdr, out, n1, p1, p2, inl, (VoCov *)(d + o_cov), st));
+    if (pnp) PRE3_TRY(launch_pnp_pair(hdr, out, n1, p1, match, k2.frm, k2.ldf, n2, inl, q->pnp_cam, q->pnp_undistort, (double *)(d + o_pix), (int32_t *)(d + o_list),
+                                      (pre3_pnp_result *)(d + o_pnp), st));
     return PRE3_OK;
 }
 
@@ -229,6 +239,13 @@ void vp_cov_out(const VpPair &p, double *cov_out, int32_t *cov_status_out)
 }
 
 // the dense ICP queued behind the pair's launches (pre3_icp_pair_seeded)
+// the EPnP refit queued behind the pair's launches (pre3_vo_pair_pnp_seeded)
+struct PnpAttach { const pre3_cam *cam; int undistort; double *pix2_out; pre3_pnp_result *res; };
+void pnp_not_computed(pre3_pnp_result *r)
+{
+    memset(r, 0, sizeof *r);
+    r->R[0] = r->R[4] = r->R[8] = 1.0; r->u[3] = 1.0; r->err[0] = r->err[1] = r->err[2] = NAN; r->sta = 0;
+}
 struct IcpAttach { int stride; double res; IcpOutputs out; bool with_cov = false; };      // with_cov: pre3_icp_pair_cov_seeded
 void icp_not_run(const IcpAttach *icp)
 {
@@ -240,16 +257,22 @@ void icp_not_run(const IcpAttach *icp)
 // icp != nullptr: pre3_icp_frames' launches behind them on the same stream, seeded from the pair's result block
 int vo_pair_impl(const char *who, bool with_cov, pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, int32_t *pnum_out, double *match_out,
                  double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out, int32_t *cnum_out, int32_t *state_out,
-                 int32_t *inlier_out, pre3_vo_result *res, double *cov_out, int32_t *cov_status_out, const IcpAttach *icp = nullptr)
+                 int32_t *inlier_out, pre3_vo_result *res, double *cov_out, int32_t *cov_status_out, const IcpAttach *icp = nullptr, const PnpAttach *pnp = nullptr)
 {
     VpPair p;
     p.with_cov = with_cov;
+    if (pnp) {
+        PRE3_CHECK(pnp->cam != nullptr && pnp->res != nullptr, PRE3_E_ARG, "%s: a null camera or EPnP result", who);
+        PRE3_CHECK(pnp->cam->f > 0, PRE3_E_ARG, "%s: the focal length must be positive", who);
+        p.pnp_cam = pnp->cam; p.pnp_undistort = pnp->undistort;
+    }
     PRE3_TRY(sr_frame_pair_views(who, prev, cur, thresh, &p.v1, &p.v2, &p.k1, &p.k2));
     if (icp) PRE3_TRY(icp_check_args(who, icp->stride, icp->res));
     PRE3_TRY(select_device(who, p.v2.device));
     if (pnum_out) *pnum_out = 0;
     if (cov_status_out) *cov_status_out = VC_NOT_COMPUTED;
     if (icp && icp->out.cov_status) *icp->out.cov_status = VC_NOT_COMPUTED;
+    if (pnp) pnp_not_computed(pnp->res);                                   // what every early way out leaves: sta = 0, the identity increment
     if (vp_empty(p)) { vo_no_solution(res); icp_not_run(icp); return PRE3_OK; }      // siftmatch of an empty set: no match, nothing to queue
     PRE3_TRY(vp_queue(prev, cur, thresh, seed, seq, &p));
     IcpJob job;
@@ -262,7 +285,8 @@ int vo_pair_impl(const char *who, bool with_cov, pre3_sr_frame *prev, pre3_sr_fr
     if (draws_out) need = p.o_cnum;
     if (cnum_out) need = p.o_state;
     if (state_out) need = p.o_inl;
-    if (inlier_out) need = p.o_end;
+    if (inlier_out) need = p.o_pix;
+    if (pnp) need = p.o_end;
     const hipStream_t st = p.v2.stream;
     char *pin = p.pin;
     PRE3_HIP(hipMemcpyAsync(pin, p.d, need, hipMemcpyDeviceToHost, st));
@@ -286,6 +310,11 @@ int vo_pair_impl(const char *who, bool with_cov, pre3_sr_frame *prev, pre3_sr_fr
     if (state_out) memcpy(state_out, pin + p.o_state, sizeof(int32_t) * (size_t)rst);
     if (inlier_out) memcpy(inlier_out, pin + p.o_inl, sizeof(int32_t) * (size_t)pnum);
     if (res) vo_result(o, res);
+    if (pnp) {
+        if (pnp->pix2_out) memcpy(pnp->pix2_out, pin + p.o_pix, sizeof(double) * 2 * (size_t)pnum);
+        memcpy(pnp->res, pin + p.o_pnp, sizeof *pnp->res);
+        pnp->res->n_support = o.n_support;
+    }
     if (icp) PRE3_TRY(icp_job_collect(&job, who, icp->out));
     return PRE3_OK;
 }
@@ -419,6 +448,18 @@ int pre3_vo_pair_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, 
 {
     return vo_pair_impl("pre3_vo_pair_seeded", false, prev, cur, thresh, seed, seq, pnum_out, match_out, pset1_out, pset2_out, draws_out, capped_out, cnum_out, state_out,
                         inlier_out, res, nullptr, nullptr);
+}
+
+// RANSAC_CALC_VER2.m:191 in place: pre3_vo_pair_seeded's launches, then the EPnP refit over the pair's inliers -- prev's range
+// points against cur's PIXELS -- on the same stream; still one host wait
+int pre3_vo_pair_pnp_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, const pre3_cam *cam, int undistort,
+                            int32_t *pnum_out, double *match_out, double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out,
+                            int32_t *cnum_out, int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res, double *pix2_out, pre3_pnp_result *pnp)
+{
+    const PnpAttach a{ cam, undistort, pix2_out, pnp };
+    PRE3_CHECK(pnp != nullptr, PRE3_E_ARG, "pre3_vo_pair_pnp_seeded: null EPnP result");
+    return vo_pair_impl("pre3_vo_pair_pnp_seeded", false, prev, cur, thresh, seed, seq, pnum_out, match_out, pset1_out, pset2_out, draws_out, capped_out, cnum_out,
+                        state_out, inlier_out, res, nullptr, nullptr, nullptr, &a);
 }
 
 // calc_cov_RANSAC_dr_ye.m:17-30 behind vodometry_dr_ye.m: pre3_vo_pair_seeded with k_vo_cov behind k_vp_final, still one host wait

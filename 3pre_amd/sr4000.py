@@ -557,7 +557,14 @@ def _load_pair_member(f, path, d, mode, parse):
     return d
 
 
-def vodometry_frames(dat1, dat2, seed, seq=0, thresh=1.5, device=0, frames=None, parse="host", compensation=None):
+def vodometry_frames_pnp(dat1, dat2, seed, cam, seq=0, thresh=1.5, undistort=True, device=0, frames=None, parse="host", compensation=None):
+    """vodometry_frames with RANSAC_CALC_VER2.m:191 behind it (vo.vo_pair_pnp_seeded): out["pnp"] is the pose of the pair's
+    inliers from prev's range points and cur's pixels alone -- no depth of the current frame.  cam = [f, Cx, Cy, k1, k2, nRows, nCols]; the pixels
+    go through undistort_fm_my_version.m first unless undistort=False."""
+    return vodometry_frames(dat1, dat2, seed, seq, thresh, device, frames, parse, compensation, _pnp=(cam, undistort))
+
+
+def vodometry_frames(dat1, dat2, seed, seq=0, thresh=1.5, device=0, frames=None, parse="host", compensation=None, _pnp=None):
     """vodometry_dr_ye with the SIFT sets made on the device: each file is conditioned in mode 1, SrFrame.sift runs on its filtered image, gate 1 (gate 0
     on a frame without confidence rows) drops keypoints, then vo.vo_pair_seeded.  The gated set is 1-based, as vodometry_dr_ye.m:73-74,120-122 make
     it before confidence_filtering.  parse="device": the two texts are parsed on the device too (SrFrame.load_text).  compensation=(form, cutoff):
@@ -570,7 +577,7 @@ def vodometry_frames(dat1, dat2, seed, seq=0, thresh=1.5, device=0, frames=None,
             d = _load_pair_member(f, path, d, MODE_DR_YE, parse)
             f.sift(want_arrays=False)
             kept.append(f.gate(GATE_CONFIDENCE if d["conf"] is not None else GATE_DEPTH)["keep_idx"])
-        out = vo.vo_pair_seeded(f1, f2, seed, seq, thresh)
+        out = vo.vo_pair_seeded(f1, f2, seed, seq, thresh) if _pnp is None else vo.vo_pair_pnp_seeded(f1, f2, seed, _pnp[0], seq, thresh, _pnp[1])
     finally:
         if own:
             f1.close(); f2.close()

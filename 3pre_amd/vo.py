@@ -387,6 +387,101 @@ def icp_pair_cov_seeded(prev, cur, seed, seq=0, thresh=1.5, stride=1, res=0.02):
     return pair, icp
 
 
+# ---- the camera pose from 3-D / 2-D correspondences: EPnP and its RANSAC ------------------------------------------------------
+class PnpResult(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("T", C.c_double * 3), ("u", C.c_double * 7), ("err", C.c_double * 3),
+                ("best", C.c_int32), ("sta", C.c_int32), ("n", C.c_int32), ("n_support", C.c_int32)]
+
+
+def _pnp_dict(r):
+    return dict(R=np.array(r.R).reshape(3, 3), T=np.array(r.T), u=np.array(r.u), err=np.array(r.err), best=int(r.best), sta=int(r.sta), n=int(r.n),
+                n_support=int(r.n_support))
+
+
+def _pnp_args(Xw, U, cam):
+    from ._lib import Cam
+    xw, uv = f64(Xw), f64(U)
+    assert xw.ndim == 2 and xw.shape[1] == 3 and uv.shape == (xw.shape[0], 2), "Xw is (n, 3) and U (n, 2): one correspondence a row"
+    return xw, uv, Cam(*[float(v) for v in np.asarray(cam, np.float64).ravel()[:7]])
+
+
+def pnp_limits():
+    """dict(max_n, max_hyp) (pre3_pnp_limits)"""
+    out = np.zeros(2, np.int32)
+    check(lib.pre3_pnp_limits(dptr(out)))
+    return dict(max_n=int(out[0]), max_hyp=int(out[1]))
+
+
+def efficient_pnp(Xw, U, cam, undistort=False, device=0):
+    """aux_code/EPnP_matlab/EPnP/efficient_pnp.m for kernel dimensions 1 to 3 on the device: Xw (n, 3) points, U (n, 2) pixels, cam = [f, Cx, Cy, k1,
+    k2, nRows, nCols].  Returns R, T, Xc, best_solution in the reference's order (Xc = (R Xw' + T)', best_solution 1-based), plus the result dict:
+    R, T, u (the VO pair's convention, what predict takes), err[3], best (0-based), sta (1 ok; 2 the best of three where the reference would go on
+    to dimension 4, which is not built; -1 a non-finite intermediate), n.  undistort=True passes every pixel through undistort_fm_my_version.m's
+    ten Newton steps first: the form to use on real frames."""
+    xw, uv, c = _pnp_args(Xw, U, cam)
+    r = PnpResult()
+    check(lib.pre3_epnp(int(device), C.byref(c), int(bool(undistort)), xw.shape[0], dptr(xw), dptr(uv), C.byref(r)))
+    d = _pnp_dict(r)
+    return d["R"], d["T"], xw @ d["R"].T + d["T"], d["best"] + 1, d
+
+
+def _pnp_ransac_out(n, n_hyp, want_hyp):
+    return (np.zeros(n_hyp, np.int32), np.zeros(n_hyp, np.int32), np.zeros(n, np.int32), (PnpResult * n_hyp)() if want_hyp else None, PnpResult())
+
+
+def _pnp_ransac_dict(sup, sta, inl, hyp, r, draws):
+    d = _pnp_dict(r)
+    d.update(support=sup, state=sta, inliers=inl, draws=draws, hyp=None if hyp is None else [_pnp_dict(h) for h in hyp])
+    return d
+
+
+def pnp_ransac(Xw, U, cam, draws, thr_px, undistort=False, hyp_results=False, device=0):
+    """Six-point EPnP hypotheses from the table draws (n_hyp, 6), all scored over the n correspondences (an inlier: reprojection distance < thr_px and
+    camera-frame z > 0), the winner by (largest support, smallest inlier distance sum, lowest index), and the EPnP refit over its inliers.  Returns
+    the refit's dict (sta = 0 when the support is below six) with support, state, inliers (0/1 flags of the winner), draws and, on request, hyp."""
+    xw, uv, c = _pnp_args(Xw, U, cam)
+    dr = i32(draws).reshape(-1, 6)
+    sup, sta, inl, hyp, r = _pnp_ransac_out(xw.shape[0], dr.shape[0], hyp_results)
+    check(lib.pre3_pnp_ransac(int(device), C.byref(c), int(bool(undistort)), xw.shape[0], dptr(xw), dptr(uv), dr.shape[0], dptr(dr), float(thr_px), dptr(sup),
+                              dptr(sta), dptr(inl), None if hyp is None else C.byref(hyp), C.byref(r)))
+    return _pnp_ransac_dict(sup, sta, inl, hyp, r, dr)
+
+
+def pnp_ransac_seeded(Xw, U, cam, n_hyp, thr_px, seed, seq=0, undistort=False, hyp_results=False, device=0):
+    """pnp_ransac with the table drawn on the device (Philox stream 6, six distinct of n per hypothesis); bit-identical to pnp_ransac fed result["draws"]"""
+    xw, uv, c = _pnp_args(Xw, U, cam)
+    dr = np.zeros((max(int(n_hyp), 0), 6), np.int32)
+    sup, sta, inl, hyp, r = _pnp_ransac_out(xw.shape[0], dr.shape[0], hyp_results)
+    check(lib.pre3_pnp_ransac_seeded(int(device), C.byref(c), int(bool(undistort)), xw.shape[0], dptr(xw), dptr(uv), int(n_hyp), int(seed), int(seq), float(thr_px),
+                                     dptr(dr), dptr(sup), dptr(sta), dptr(inl), None if hyp is None else C.byref(hyp), C.byref(r)))
+    return _pnp_ransac_dict(sup, sta, inl, hyp, r, dr)
+
+
+def vo_pair_pnp_seeded(prev, cur, seed, cam, seq=0, thresh=1.5, undistort=False):
+    """vo_pair_seeded with RANSAC_CALC_VER2.m:191 behind it on the device: the EPnP of efficient_pnp over the pair's inliers --
+    prev's range points (pset1) against cur's PIXELS, no depth of cur -- still one host wait.  The dict of vo_pair_seeded, bit for bit, plus pix2
+    (2, pnum): cur's pixel of every match, and pnp: the result dict of efficient_pnp (u in the pair's convention, comparable with the pair's own u;
+    sta = 0 and the identity when the pair's sta != 1 or it has fewer than six inliers).  On real frames pass undistort=True."""
+    from ._lib import Cam
+    c = Cam(*[float(v) for v in np.asarray(cam, np.float64).ravel()[:7]])
+    n1 = max(int(getattr(prev, "n_kept", 0)), 1)
+    pix, r = np.zeros((n1, 2)), PnpResult()
+    fn = lambda a, b, th, sd, sq, *rest: lib.pre3_vo_pair_pnp_seeded(a, b, th, sd, sq, C.byref(c), int(bool(undistort)), *rest)      # noqa: E731
+    out = _pair_call(fn, prev, cur, seed, seq, thresh, dptr(pix), C.byref(r))
+    out["pix2"] = pix[:out["pnum"] if out["rst"] else 0].T.copy()
+    out["pnp"] = _pnp_dict(r)
+    return out
+
+
+def pnp_bench(Xw, U, cam, n_hyp, thr_px, seed=1, seq=0, undistort=False, reps=20, device=0):
+    """milliseconds of pnp_ransac_seeded's four launches on resident operands (measurement only)"""
+    xw, uv, c = _pnp_args(Xw, U, cam)
+    ms = C.c_double(0)
+    check(lib.pre3_pnp_bench(int(device), C.byref(c), int(bool(undistort)), xw.shape[0], dptr(xw), dptr(uv), int(n_hyp), int(seed), int(seq), float(thr_px), int(reps),
+                             C.byref(ms)))
+    return ms.value
+
+
 def icp_nn_bench(data1, data2, reps=20, device=0):
     """milliseconds of one nearest-neighbour launch on resident clouds (measurement only)"""
     d1, d2 = np.ascontiguousarray(f64(data1).T), np.ascontiguousarray(f64(data2).T)

@@ -1079,6 +1079,63 @@ PRE3_API int pre3_predict_icp_pair_seeded(pre3_ctx *ctx, pre3_sr_frame *prev, pr
                                           double res, double max_error, int noise, int32_t *pnum_out, pre3_vo_result *vo_res_out,
                                           pre3_icp_result *icp_out, double *cov_out, int32_t *cov_status_out, int32_t *taken_out);
 
+/* ---- the camera pose from 3-D / 2-D correspondences: EPnP, its RANSAC ------------------------------------------------------------
+ * aux_code/EPnP_matlab/EPnP/efficient_pnp.m:34-175 (Moreno-Noguer, Lepetit, Fua, ICCV 2007) for kernel dimensions 1, 2 and 3 -- the solver
+ * mex_files/RANSAC_CALCULATION/RANSAC_CALC_VER2.m:187-191 leaves commented out: the pose of 3-D points of one frame against the PIXELS of another, with
+ * no use of the second frame's depth.  Control points Cw = [e1; e2; e3; 0] (define_control_points.m: not centred on the data), M of
+ * compute_M_ver2.m:32-52 from A = [f 0 Cx; 0 f Cy; 0 0 1], the kernel vectors of kernel_noise.m:19-22 by a cyclic Jacobi eigensolver, scale and
+ * sign by compute_norm_sign_scaling_factor.m:26-61 (the whole Xc negated if any z < 0), getrotT (:179-205; R = -R, the whole matrix, if det R < 0),
+ * the mean pixel distance of :210-226 (no test on depth); dimension 3 is entered only if min(err) > 20 px after the first two (:98); the answer is
+ * [min_err, best] = min(err), the first index on ties (:171).  eig leaves a vector's sign open and the z < 0 rule makes a mixed-sign answer depend on
+ * it, so each kernel vector's entry of largest magnitude is made positive first.  Dimension 4 (:129-169) is NOT built -- its result depends on the basis
+ * null() happens to return: where the reference would enter it (min(err) > 20 after dimension 3) the answer is the best of the three with sta = 2.
+ * All fp64; every sum over the points is a tree whose shape depends on the count alone: bit-equal from run to run. */
+typedef struct pre3_pnp_result {
+    double R[9], T[3];      /* row-major; Xc = R Xw + T (efficient_pnp.m:171-174) */
+    double u[7];            /* the pair's convention: [-R'T; R2q(R')] -- pset1 ~ rot pset2 + trans, what pre3_predict takes; the identity unless sta is 1 or 2 */
+    double err[3];          /* err(1..3); NaN where a dimension was not computed */
+    int32_t best;           /* 0-based dimension of the answer */
+    int32_t sta;            /* 1 ok; 2 best of three, the reference would go on to dimension 4; -1 a non-finite intermediate; 0 not computed */
+    int32_t n;              /* correspondences the answer was computed from */
+    int32_t n_support;      /* RANSAC forms: the winner's support; else n */
+} pre3_pnp_result;
+/* Stateless, host in and host out, synchronises.  Xw[3 x n], U[2 x n] column-major (one correspondence a column).  undistort = 0 uses the pixels as they
+ * are (the commented-out line's cam.K); undistort = 1 passes every pixel through undistort_fm_my_version.m:56-81's ten Newton steps first -- the form to
+ * use on real frames: the SR4000's k1 = -0.84656 moves a corner pixel by more than ten pixels.  PRE3_E_ARG: n < 6 or beyond pre3_pnp_limits, a null pointer,
+ * cam->f <= 0.  A non-finite coordinate gives sta = -1. */
+PRE3_API int pre3_epnp(int device, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, pre3_pnp_result *res);
+/* n_hyp in [1, limits[1]] six-point hypotheses, all evaluated (no early exit: the reference has no PnP RANSAC and its count rule is not borrowed).
+ * draws[n_hyp][6]: 0-based indices, distinct within a row (else PRE3_E_ARG).  Every hypothesis is solved as pre3_epnp solves six correspondences and all n
+ * are scored under its answer: an inlier has a reprojection distance < thr_px and a camera-frame z > 0.  support_out[n_hyp], state_out[n_hyp] (the
+ * hypothesis' sta; a non-finite pose: support 0, state -1), hyp_res_out[n_hyp] (may be NULL; n_support = the hypothesis' support).  The winner: the largest
+ * support, then the smallest sum of inlier distances, then the lowest index (RANSAC_CALC_VER2.m:165-172's rule); inlier_out[n] its 0/1 flags.  res: the
+ * EPnP refit over the winner's inliers, read on the device; support below 6: sta = 0, n_support as found.  Stateless, host in and host out, synchronises: the two uploads, three launches, one copy back.
+ * With sta 0 or -1 (here and in pre3_epnp) R is the identity, T zero and u the identity increment.
+ * PRE3_E_ARG besides pre3_epnp's: n_hyp out of range, thr_px not positive and finite, a null table. */
+PRE3_API int pre3_pnp_ransac(int device, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, int n_hyp, const int32_t *draws,
+                             double thr_px, int32_t *support_out, int32_t *state_out, int32_t *inlier_out, pre3_pnp_result *hyp_res_out, pre3_pnp_result *res);
+/* the same with the table drawn on the device in front (one more launch): six distinct of n per hypothesis on Philox stream 6, counter
+ * [hypothesis, block, seq, 0] -- ranks in [0,n), [0,n-1), ..., each shifted past the earlier picks (DESIGN.md section 18's rule for three, continued).
+ * draws_out[n_hyp][6] may be NULL.  Bit-identical to pre3_pnp_ransac fed that table. */
+PRE3_API int pre3_pnp_ransac_seeded(int device, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, int n_hyp, uint64_t seed,
+                                    uint64_t seq, double thr_px, int32_t *draws_out, int32_t *support_out, int32_t *state_out, int32_t *inlier_out,
+                                    pre3_pnp_result *hyp_res_out, pre3_pnp_result *res);
+/* RANSAC_CALC_VER2.m:191 in place: pre3_vo_pair_seeded's launches, and behind them on the same stream the EPnP of pre3_epnp over the pair's inliers,
+ * read on the device through the pair's inlier flags -- Xw = pset1, prev's range points [-x; -y; z]; U = entries 0 and 1 of cur's kept keypoint frame at
+ * match(2, i), the uv pre3_map_policy_frames_seeded hands the map -- so the pose uses no depth of cur.  Still ONE host wait.  Every output shared with
+ * pre3_vo_pair_seeded is bit-equal to that call's, as are its refusals and errors; pix2_out[2 x pnum] (may be NULL) the pixels of all matches; pnp is
+ * bit-equal to pre3_epnp on pset1_out and pix2_out gathered at the inliers, with n_support the pair's, and pnp->u is in the pair's convention (comparable
+ * with res->u).  The pair's sta != 1, fewer than four matches or fewer than six inliers: pnp->sta = 0, R and u the identity.  PRE3_E_ARG besides the
+ * pair's: a null cam or pnp, cam->f <= 0. */
+PRE3_API int pre3_vo_pair_pnp_seeded(pre3_sr_frame *prev, pre3_sr_frame *cur, double thresh, uint64_t seed, uint64_t seq, const pre3_cam *cam, int undistort,
+                                     int32_t *pnum_out, double *match_out, double *pset1_out, double *pset2_out, int32_t *draws_out, int32_t *capped_out,
+                                     int32_t *cnum_out, int32_t *state_out, int32_t *inlier_out, pre3_vo_result *res, double *pix2_out, pre3_pnp_result *pnp);
+/* out = { the largest n, the largest n_hyp } */
+PRE3_API int pre3_pnp_limits(int32_t out[2]);
+/* measurement only: pre3_pnp_ransac_seeded's four launches on resident operands, back to back between two events, averaged over reps */
+PRE3_API int pre3_pnp_bench(int device, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, int n_hyp, uint64_t seed, uint64_t seq,
+                            double thr_px, int reps, double *ms_per_ransac_out);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them

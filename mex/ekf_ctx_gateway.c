@@ -651,6 +651,73 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         if (nout > 1) out[1] = mxCreateDoubleScalar(status);
         if (nout > 2) out[2] = mxCreateDoubleScalar(n);
     }
+    else if (!strcmp(cmd, "epnp") || !strcmp(cmd, "pnp_ransac")) {
+        /* [R, T, Xc, best_solution, sta, err, u] = pre3_mex('epnp', Xw, U, cam_struct [, undistort = 0]): aux_code/EPnP_matlab/EPnP/efficient_pnp.m for kernel
+           dimensions 1 to 3, in its order of outputs -- Xw 3 x n points, U 2 x n pixels (one correspondence a column), Xc = R Xw + T (3 x n), best_solution
+           1-based; sta 1 ok, 2 the best of three where the reference would go on to dimension 4 (not built), -1 a non-finite intermediate; u 7 x 1 the pose in
+           the VO pair's convention.  undistort = 1: every pixel through undistort_fm_my_version.m first (pre3_epnp, on device 0).
+           [R, T, inliers, support, sta, err, u] = pre3_mex('pnp_ransac', Xw, U, cam_struct, n_hyp, thr_px, seed, seq [, undistort = 0]): up to 700 six-point
+           hypotheses drawn on the device, all scored (reprojection distance < thr_px, depth > 0), the refit over the winner's inliers (n x 1 flags);
+           sta 0: fewer than six inliers (pre3_pnp_ransac_seeded) */
+        pre3_cam cam; pre3_pnp_result r; int i, k, ransac = !strcmp(cmd, "pnp_ransac"), und; mwSize n; int32_t *inl = NULL;
+        const char *fn[7] = { "f", "Cx", "Cy", "k1", "k2", "nRows", "nCols" }; double *cf = &cam.f;
+        if (ransac ? (nin < 8 || nin > 9) : (nin < 4 || nin > 5))
+            mexErrMsgTxt("pre3_mex('epnp', Xw, U, cam [, undistort]) or pre3_mex('pnp_ransac', Xw, U, cam, n_hyp, thr_px, seed, seq [, undistort])");
+        n = mxGetN(in[1]);
+        if (!mxIsDouble(in[1]) || !mxIsDouble(in[2]) || mxGetM(in[1]) != 3 || mxGetM(in[2]) != 2 || mxGetN(in[2]) != n || !mxIsStruct(in[3]))
+            mexErrMsgTxt("pre3_mex('epnp' / 'pnp_ransac'): Xw 3 x n, U 2 x n (double), cam a struct");
+        for (i = 0; i < 7; ++i) { mxArray *v = mxGetField(in[3], 0, fn[i]); if (!v) mexErrMsgTxt("pre3_mex: cam field missing"); cf[i] = mxGetScalar(v); }
+        memset(&r, 0, sizeof r);
+        if (ransac) {
+            und = nin > 8 ? (int)mxGetScalar(in[8]) : 0;
+            inl = (int32_t *)mxCalloc(n ? n : 1, sizeof(int32_t));
+            check(pre3_pnp_ransac_seeded(0, &cam, und, (int)n, mxGetPr(in[1]), mxGetPr(in[2]), (int)mxGetScalar(in[4]), (uint64_t)mxGetScalar(in[6]),
+                                         (uint64_t)mxGetScalar(in[7]), mxGetScalar(in[5]), NULL, NULL, NULL, inl, NULL, &r));
+        } else {
+            und = nin > 4 ? (int)mxGetScalar(in[4]) : 0;
+            check(pre3_epnp(0, &cam, und, (int)n, mxGetPr(in[1]), mxGetPr(in[2]), &r));
+        }
+        out[0] = mxCreateDoubleMatrix(3, 3, mxREAL);
+        for (i = 0; i < 3; ++i) for (k = 0; k < 3; ++k) mxGetPr(out[0])[i + 3 * k] = r.R[3 * i + k];      /* row-major -> column-major */
+        if (nout > 1) { out[1] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[1]), r.T, sizeof r.T); }
+        if (nout > 2) {
+            if (ransac) { out[2] = mxCreateDoubleMatrix(n, 1, mxREAL); for (i = 0; i < (int)n; ++i) mxGetPr(out[2])[i] = inl[i]; }
+            else {
+                const double *xw = mxGetPr(in[1]); double *xc;
+                out[2] = mxCreateDoubleMatrix(3, n, mxREAL); xc = mxGetPr(out[2]);
+                for (i = 0; i < (int)n; ++i) for (k = 0; k < 3; ++k) xc[3 * i + k] = r.R[3 * k] * xw[3 * i] + r.R[3 * k + 1] * xw[3 * i + 1] + r.R[3 * k + 2] * xw[3 * i + 2] + r.T[k];
+            }
+        }
+        if (inl) mxFree(inl);
+        if (nout > 3) out[3] = mxCreateDoubleScalar(ransac ? r.n_support : r.best + 1);
+        if (nout > 4) out[4] = mxCreateDoubleScalar(r.sta);
+        if (nout > 5) { out[5] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[5]), r.err, sizeof r.err); }
+        if (nout > 6) { out[6] = mxCreateDoubleMatrix(7, 1, mxREAL); memcpy(mxGetPr(out[6]), r.u, sizeof r.u); }
+    }
+    else if (!strcmp(cmd, "vo_pair_pnp")) {       /* [T, q, sta, pnp_sta, R, Tc, err, pnum, T3, q3] = pre3_mex('vo_pair_pnp', seed, seq, cam_struct [, undistort = 1, thresh = 1.5]):
+                                                     RANSAC_CALC_VER2.m:191 in place between the kept frame and the current one -- the VO pair's launches, then
+                                                     efficient_pnp over the pair's inliers, prev's range points against cur's PIXELS.  T, q: the EPnP pose in the pair's
+                                                     convention (the identity unless pnp_sta is 1 or 2); sta the pair's; R, Tc with Xc = R Xw + Tc; T3, q3 the pair's
+                                                     own 3-D / 3-D increment (pre3_vo_pair_pnp_seeded) */
+        pre3_cam cam; pre3_pnp_result r; pre3_vo_result v; int32_t pnum = 0; int i, k;
+        const char *fn[7] = { "f", "Cx", "Cy", "k1", "k2", "nRows", "nCols" }; double *cf = &cam.f;
+        if (nin < 4 || nin > 6 || !mxIsStruct(in[3])) mexErrMsgTxt("pre3_mex('vo_pair_pnp', seed, seq, cam [, undistort, thresh]): three to five arguments, cam a struct");
+        if (!g_sr || !g_sr_prev) mexErrMsgTxt("pre3_mex('vo_pair_pnp'): needs two frames -- 'sr_frame' + 'sr_keypoints', 'sr_keep', then 'sr_frame' + 'sr_keypoints' again");
+        for (i = 0; i < 7; ++i) { mxArray *f = mxGetField(in[3], 0, fn[i]); if (!f) mexErrMsgTxt("pre3_mex: cam field missing"); cf[i] = mxGetScalar(f); }
+        memset(&r, 0, sizeof r); memset(&v, 0, sizeof v);
+        check(pre3_vo_pair_pnp_seeded(g_sr_prev, g_sr, nin > 5 ? mxGetScalar(in[5]) : 1.5, (uint64_t)mxGetScalar(in[1]), (uint64_t)mxGetScalar(in[2]), &cam,
+                                      nin > 4 ? (int)mxGetScalar(in[4]) : 1, &pnum, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, &v, NULL, &r));
+        out[0] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[0]), r.u, sizeof(double) * 3);
+        if (nout > 1) { out[1] = mxCreateDoubleMatrix(4, 1, mxREAL); memcpy(mxGetPr(out[1]), r.u + 3, sizeof(double) * 4); }
+        if (nout > 2) out[2] = mxCreateDoubleScalar(v.sta);
+        if (nout > 3) out[3] = mxCreateDoubleScalar(r.sta);
+        if (nout > 4) { out[4] = mxCreateDoubleMatrix(3, 3, mxREAL); for (i = 0; i < 3; ++i) for (k = 0; k < 3; ++k) mxGetPr(out[4])[i + 3 * k] = r.R[3 * i + k]; }
+        if (nout > 5) { out[5] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[5]), r.T, sizeof r.T); }
+        if (nout > 6) { out[6] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[6]), r.err, sizeof r.err); }
+        if (nout > 7) out[7] = mxCreateDoubleScalar(pnum);
+        if (nout > 8) { out[8] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[8]), v.u, sizeof(double) * 3); }
+        if (nout > 9) { out[9] = mxCreateDoubleMatrix(4, 1, mxREAL); memcpy(mxGetPr(out[9]), v.u + 3, sizeof(double) * 4); }
+    }
     else if (!strcmp(cmd, "predict_icp_pair")) {  /* [T, q, sta, icp_sta, taken, cov_pair, cov_icp, cov_status] = pre3_mex('predict_icp_pair', seed, seq, res [, stride = 1, max_error = inf,
                                                      noise = 0, thresh = 1.5]): 'predict_pair' with the dense ICP of 'icp_pair' between the pair and the prediction -- the ICP's [T; q]
                                                      when the pair's is taken, icp_sta == 1, it is finite and its error <= max_error; noise 0 the context's own, 1 the pair's covariance,
