@@ -424,6 +424,7 @@ int pre3_create(pre3_ctx **out, int device, int dtype, int max_landmarks, int ma
     if (rc == PRE3_OK) c->masks = reinterpret_cast<uint32_t *>(c->support + c->caph + 4);
     A(dmalloc(c, &c->stats, 16));
     A(dmalloc(c, &c->pred_params, 192));
+    A(reloc_alloc(c));
     {
         // K9 tile schedule: upper-triangle 64x64 tiles in 4x4 super-tile order, so that the tiles in flight at
         // any moment (tickets are handed out in this order) share W panels in L2 / Infinity Cache.
@@ -800,11 +801,7 @@ int pre3_set_process_noise(pre3_ctx *c, const double *Pn)
 {
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "pre3_set_process_noise: null context");
     if (Pn == nullptr) { c->pn_set = false; return PRE3_OK; }
-    for (int i = 0; i < 49; ++i) PRE3_CHECK(std::isfinite(Pn[i]), PRE3_E_ARG, "pre3_set_process_noise: Pn[%d] is not finite", i);
-    for (int i = 0; i < 7; ++i) {
-        PRE3_CHECK(Pn[8 * i] >= 0, PRE3_E_ARG, "pre3_set_process_noise: the diagonal entry %d is negative", i);
-        for (int j = 0; j < i; ++j) PRE3_CHECK(Pn[7 * i + j] == Pn[7 * j + i], PRE3_E_ARG, "pre3_set_process_noise: Pn(%d,%d) != Pn(%d,%d)", i, j, j, i);
-    }
+    PRE3_TRY(process_noise_check("pre3_set_process_noise", Pn));
     PRE3_HIP(hipSetDevice(c->device));
     PRE3_TRY(launch_set_pn(c, Pn));
     memcpy(c->pn_host, Pn, sizeof c->pn_host);
@@ -971,6 +968,16 @@ static bool copy_desc_checked(double *__restrict__ dst, const double *__restrict
 }
 
 }  // extern "C"
+// a process noise's three checks (pre3_set_process_noise, pre3_relocalise_seeded): finite, no negative diagonal entry, exactly symmetric
+int pre3::process_noise_check(const char *who, const double *Pn)
+{
+    for (int i = 0; i < 49; ++i) PRE3_CHECK(std::isfinite(Pn[i]), PRE3_E_ARG, "%s: Pn[%d] is not finite", who, i);
+    for (int i = 0; i < 7; ++i) {
+        PRE3_CHECK(Pn[8 * i] >= 0, PRE3_E_ARG, "%s: the diagonal entry %d is negative", who, i);
+        for (int j = 0; j < i; ++j) PRE3_CHECK(Pn[7 * i + j] == Pn[7 * j + i], PRE3_E_ARG, "%s: Pn(%d,%d) != Pn(%d,%d)", who, i, j, j, i);
+    }
+    return PRE3_OK;
+}
 bool pre3::desc_copy_checked(double *dst, const double *src, size_t count) { return copy_desc_checked(dst, src, count); }
 // A pinned block of the context for `bytes` of host data on their way to the device: two blocks, used alternately, grown on demand; a block is
 // written again only after the pull of its previous contents has run (its sequence number in the mailbox: stage_wait).  The caller fills *host, enqueues the pull from *dev on the
@@ -1053,7 +1060,8 @@ static int scan_reserve(pre3_ctx *c, int K2, bool *grew)
         for (DevBlock *b : { &m.scan_desc, &m.scan_pos, &m.ic_pb, &m.ic_ps, &m.ic_pa }) b->release();      // all five first: the peak does not rise
         c->scan_desc = c->scan_pos = nullptr; c->ic_pb = c->ic_ps = nullptr; c->ic_pa = nullptr; c->scan_cap = 0; c->ic_pcap = 0;
         const int cap = round_up(K2, 256);
-        const size_t np = std::max((size_t)(cap / 64) * c->capN, (size_t)64 * c->capN);     // [scan_cap/64][capN] for the 64-wide tiles; the fused route: [capN][64 column tiles of 32]
+        // [scan_cap/64][capN] for the 64-wide tiles; the fused route: [capN][64 column tiles of 32]; pre3_relocalise_seeded: [scan_cap/32][capN], whatever K2
+        const size_t np = std::max((size_t)(cap / ICS_T) * c->capN, (size_t)64 * c->capN);
         const size_t b_desc = sizeof(double) * cap * DESC_DIM, b_pos = sizeof(double) * cap * 4, b_d = sizeof(double) * np, b_i = sizeof(int32_t) * np;
         PRE3_TRY(m.scan_desc.reserve(b_desc, b_desc, Zero::sync())); PRE3_TRY(m.scan_pos.reserve(b_pos, b_pos, Zero::sync()));
         PRE3_TRY(m.ic_pb.reserve(b_d, b_d, Zero::sync())); PRE3_TRY(m.ic_ps.reserve(b_d, b_d, Zero::sync())); PRE3_TRY(m.ic_pa.reserve(b_i, b_i, Zero::sync()));
@@ -1069,7 +1077,11 @@ int pre3_set_scan(pre3_ctx *c, int K2, const double *descriptor_raw, const doubl
 {
     EntryScope scope(c); PRE3_TRY(scope.rc);
     PRE3_CHECK(K2 >= 0 && (K2 == 0 || (descriptor_raw && scale_orient_pos_raw)), PRE3_E_ARG, "pre3_set_scan: bad arguments");
-    PRE3_TRY(scan_reserve(c, K2, nullptr));
+    bool grew = false;
+    PRE3_TRY(scan_reserve(c, K2, &grew));
+    // (as pre3_set_scan_frame: the new buffers are zeroed on the null stream, which the context's stream does not wait for -- the pull below writes the
+    //  scan, and pre3_relocalise_seeded's matcher the partial arrays, right behind this call)
+    if (grew) PRE3_HIP(hipStreamSynchronize(0));
     bool in_bounds = true;
     if (K2) {
         // The frame's scan crosses PCIe from a pinned block of the context's own, enqueued on its stream: the call neither waits for the queued

@@ -23,6 +23,7 @@
 #include "pre3_vocov.h"
 #include "pre3_icp.h"
 #include "pre3_predicticp.h"
+#include "pre3_reloc.h"
 #include <type_traits>
 
 namespace pre3 {
@@ -104,6 +105,19 @@ __device__ __forceinline__ const double *predict_pn_src(const PnIcp &s)
     return nt == PI_NOISE_PAIR ? s.s.cov_pair->cov : nt == PI_NOISE_ICP ? s.s.cov_icp->cov : s.behind;
 }
 __device__ __forceinline__ const double *predict_pn_add(const PnIcp &s) { return predict_pn_taken(s) == PI_NOISE_ICP_FLOOR ? s.s.cov_icp->cov : nullptr; }
+// Behind an EPnP RANSAC of the whole map against the scan (US = PredictUReloc, NS = PnReloc; pre3_relocalise_seeded): u under
+// reloc_select (pre3_reloc.h) from the refit's result block, which the launch in front of this one wrote, and x_in[0:7].  Block 0 reports the increment
+// and whether the pose was taken.
+__device__ __forceinline__ const U7 &predict_u(const PredictUReloc &s, U7 &ud)
+{
+    const int taken = reloc_select(s.x, s.res->sta, s.res->n_support, s.min_support, s.res->u, ud.v);
+    if (blockIdx.x == 0) {
+        for (int i = 0; i < 7; ++i) s.u_out[i] = ud.v[i];
+        s.taken_out[0] = taken;
+    }
+    return ud;
+}
+__device__ __forceinline__ const double *predict_pn_src(const PnReloc &s) { return reloc_takes(s.res->sta, s.res->n_support, s.min_support) ? s.pn : s.behind; }
 template <typename T, typename US = U7, typename NS = PnConst>
 __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in, double *x_out, T *__restrict__ P, int n, int ld, US u,
                                                  double *__restrict__ params, int n_pred_blocks, ProjRide pr, InboxRide ib, int fuse_jn, PendW pw = PendW{}, NS ns = NS{})
@@ -1230,6 +1244,18 @@ int launch_predict_icp(pre3_ctx *c, const PredictUIcp &u_icp)
     const int fuse_jn = c->carry.jn_pending ? 1 : 0;
     const PnIcp ns{ u_icp.s, c->pn_set ? c->pred_params + PRED_PN_OFF : nullptr };
     predict_launch(c, blocks, u_icp, ns, blocks, ProjRide{}, InboxRide{}, fuse_jn);
+    PRE3_HIP(hipGetLastError());
+    c->carry.jn_pending = false;
+    return PRE3_OK;
+}
+
+// launch_predict_impl's device form with the relocalisation's tags: no riders, no inbox pull; the context's block, or the constant, stands behind
+int launch_predict_reloc(pre3_ctx *c, const PredictUReloc &u_reloc, const double *pn_reloc_dev)
+{
+    const int blocks = ceil_div(c->n, 256);
+    const int fuse_jn = c->carry.jn_pending ? 1 : 0;
+    const PnReloc ns{ u_reloc.res, u_reloc.min_support, pn_reloc_dev, c->pn_set ? c->pred_params + PRED_PN_OFF : nullptr };
+    predict_launch(c, blocks, u_reloc, ns, blocks, ProjRide{}, InboxRide{}, fuse_jn);
     PRE3_HIP(hipGetLastError());
     c->carry.jn_pending = false;
     return PRE3_OK;

@@ -27,6 +27,11 @@ struct PredictIcpSrc { const VoOut *out; const VoPairHeader *hdr; const VoCov *c
                        double max_error; int noise; };
 struct PredictUIcp { PredictIcpSrc s; int32_t *err; int32_t *taken; };
 struct PnIcp { PredictIcpSrc s; const double *behind; };
+// k_predict's increment and process noise where an EPnP RANSAC over map and scan ran in front of the launch (pre3_relocalise_seeded; DESIGN.md section
+// 36): the refit's result block, the support the pose needs, and the prediction's own x_in for the rule of pre3_reloc.h.  PredictUReloc (US): block 0
+// leaves the increment and whether the pose was taken in u_out[0..6] / taken_out[0]; PnReloc (NS): the caller's wide noise when taken, else `behind`.
+struct PredictUReloc { const pre3_pnp_result *res; const double *x; int32_t min_support; double *u_out; int32_t *taken_out; };
+struct PnReloc { const pre3_pnp_result *res; int32_t min_support; const double *pn; const double *behind; };
 
 // ------------------------------------------------------------------------------------------------
 // device math (fp64)
@@ -60,6 +65,16 @@ __device__ __forceinline__ double jn_row(const double *J, int i, const double v[
     return fma(J[i * 4 + 3], v[3], fma(J[i * 4 + 2], v[2], fma(J[i * 4 + 1], v[1], J[i * 4] * v[0])));
 }
 
+// The point alone (inversedepth2cartesian.m), and the direction m it was made with: ONE text for id_to_cartesian below and for the correspondences of
+// pre3_relocalise_seeded (pre3_reloc.hip), whose Xw must be the reader's xyz bit for bit.
+__device__ __forceinline__ void id_point(const double *x, int o, double p[3], double mi[3])
+{
+    const double rho = x[o + 5], theta = x[o + 3], phi = x[o + 4];
+    const double cphi = cos(phi);
+    mi[0] = cphi * sin(theta); mi[1] = -sin(phi); mi[2] = cphi * cos(theta);
+    p[0] = x[o] + (1 / rho) * mi[0]; p[1] = x[o + 1] + (1 / rho) * mi[1]; p[2] = x[o + 2] + (1 / rho) * mi[2];
+}
+__device__ __forceinline__ void id_point(const double *x, int o, double p[3]) { double mi[3]; id_point(x, o, p, mi); }
 // inversedepth_2_cartesian.m:41-65 for the inverse-depth landmark at offset o of x, with P(rho, rho) = p_rho_rho: the point p
 // (inversedepth2cartesian.m), the linearity index 4 std_d cos(alpha) / d_c2p (camera position x(1:3)) and the 3 x 6 Jacobian
 // J = [I3, dm_dtheta / rho, dm_dphi / rho, -m / rho^2] (row-major).  One arithmetic for k_map_convert_flags and the landmark reader
@@ -68,9 +83,8 @@ __device__ __forceinline__ void id_to_cartesian(const double *x, int o, double p
 {
     const double std_rho = sqrt(p_rho_rho);
     const double rho = x[o + 5], std_d = std_rho / (rho * rho), theta = x[o + 3], phi = x[o + 4];
-    const double cphi = cos(phi);
-    const double mi[3] = { cphi * sin(theta), -sin(phi), cphi * cos(theta) };
-    p[0] = x[o] + (1 / rho) * mi[0]; p[1] = x[o + 1] + (1 / rho) * mi[1]; p[2] = x[o + 2] + (1 / rho) * mi[2];
+    double mi[3];
+    id_point(x, o, p, mi);
     const double a[3] = { p[0] - x[o], p[1] - x[o + 1], p[2] - x[o + 2] }, c2[3] = { p[0] - x[0], p[1] - x[1], p[2] - x[2] };
     const double d_c2p = sqrt(c2[0] * c2[0] + c2[1] * c2[1] + c2[2] * c2[2]);
     const double cos_alpha = (a[0] * c2[0] + a[1] * c2[1] + a[2] * c2[2]) / (sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) * d_c2p);

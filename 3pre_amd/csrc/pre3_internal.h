@@ -252,6 +252,9 @@ struct pre3_ctx {
     // marginal readers (pre3_get_landmarks / pre3_get_marginal, pre3_map.hip), allocated on first use: device results and their pinned host image;
     // the landmark block is sized by the map capacity, the index-set block grows with k
     double *lmr_dev = nullptr, *lmr_host = nullptr; bool lmr_ready = false;
+    // pre3_relocalise_seeded (pre3_reloc.hip), allocated by pre3_create: the work block [Xw | U | masks | what goes back | the RANSAC's tables] for
+    // min(capN, RELOC_MAX_N) landmarks and the pinned image of the part that goes back
+    char *reloc_dev = nullptr, *reloc_host = nullptr; int reloc_cap = 0;
     // pre3_update_rows / pre3_heading_update (pre3_rows.hip), allocated on first use: the rows block and H*P (RMAX x ld, fp64)
     pre3::RowsBlock *rows_blk = nullptr; double *rows_hp = nullptr; bool rows_ready = false;
     int rows_form = 0;                            // PRE3_OPT_ROWS_FORM: 1 the single-sweep form, 0 run_update
@@ -380,10 +383,16 @@ int launch_predict_impl(pre3_ctx *c, const double u[7], bool with_projection = f
                         const PnPair *pn_pair = nullptr /* with u_dev: the pair's covariance as Pn under the status rule (pre3_vocov.h); its `behind` is filled here */);
 // the prediction behind a VO pair and the dense ICP that refined it: u and Pn under predict_icp_select (pre3_predicticp.h)
 int launch_predict_icp(pre3_ctx *c, const PredictUIcp &u_icp);
+// the prediction behind an EPnP RANSAC of the map against the scan: u and Pn under reloc_select (pre3_reloc.h)
+struct PredictUReloc;
+int launch_predict_reloc(pre3_ctx *c, const PredictUReloc &u_reloc, const double *pn_reloc_dev);
+// pre3_relocalise_seeded's device block and the pinned image of what it returns, sized by the map capacity (pre3_reloc.hip; pre3_create)
+int reloc_alloc(pre3_ctx *c);
 // the camera-only prediction (pre3_predict_cv; pre3_predictcv.h): one launch, no riders, pred_params untouched
 int launch_predict_cv(pre3_ctx *c, int type, double dt, double sigma_a, double sigma_alpha);
 constexpr int PRED_PN_OFF = 128;         /* pred_params[128 .. 176]: the context's process noise block (pre3_set_process_noise) */
 int launch_set_pn(pre3_ctx *c, const double *Pn);
+int process_noise_check(const char *who, const double *Pn);      /* finite, no negative diagonal entry, exactly symmetric: else PRE3_E_ARG */
 int launch_get_pn_const(pre3_ctx *c, double *dst_dev);      /* d_process_noise's 49 doubles into device memory, on the context's stream */
 struct VoOut; struct VoPairHeader; struct VoCov;
 int launch_vo_cov_pair(const VoPairHeader *hdr, const VoOut *out, int cap, const double *pset1, const double *pset2, const int32_t *inl, VoCov *cov, hipStream_t st);

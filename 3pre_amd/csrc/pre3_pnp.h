@@ -332,5 +332,15 @@ struct VoOut; struct VoPairHeader;
 // list holds n1 + 4 words (the count in front).
 int launch_pnp_pair(const VoPairHeader *hdr, const VoOut *out, int n1, const double *pset1, const double *match, const double *frm2, int ldf2, int K2,
                     const int32_t *inl, const pre3_cam *cam, int undistort, double *pix2, int32_t *list, pre3_pnp_result *res, hipStream_t st);
+// pre3_pnp_ransac_seeded's four launches on st, no wait, over resident correspondences whose count an earlier launch on st left in *n_dev
+// (pre3_relocalise_seeded): Xw[3 x n_cap], U[2 x n_cap], of which the first min(*n_dev, n_cap) are read.  The grid, masks
+// (n_hyp x ceil(n_cap / 64) words) and every array are sized by n_cap; the draws are draw_rule_pnp(seed, seq, *n_dev, h).  *n_dev < 6: the draw writes
+// zeros, no hypothesis is solved, ctl = { winner -1, support 0 } and res->sta = 0.  ctl: PNP_CTL_WORDS words, the winner and its support first.
+constexpr int PNP_CTL_WORDS = 4;
+struct PnpRansacDev {
+    const double *Xw, *U; int n_cap; const int32_t *n_dev; int n_hyp; double thr_px;
+    unsigned long long *masks; int32_t *draws, *support, *state; double *dsum; int32_t *ctl, *idx, *flag; pre3_pnp_result *res, *hyp;
+};
+int launch_pnp_ransac_dev(const PnpRansacDev &r, const pre3_cam *cam, int undistort, uint64_t seed, uint64_t seq, hipStream_t st);
 }  // namespace pre3
 #endif

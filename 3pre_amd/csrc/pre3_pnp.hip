@@ -33,6 +33,15 @@ static_assert(sizeof(pre3_pnp_result) == 22 * 8 + 4 * 4, "pre3_pnp_result is 22 
 struct PnpSrc { const double *Xw, *U; int n_all; CamD cam; int undistort; };
 // what k_pnp_select leaves for the refit
 struct PnpCtl { int32_t winner, support, pad[2]; };
+// how many of the arrays' positions hold a correspondence: the launch's own count (PnpNHost: every caller but one), or a device word an earlier launch
+// left, clamped to the launch's count (PnpNDev: pre3_relocalise_seeded, whose count is the matcher's).  Below six under PnpNDev the draw writes zeros,
+// no hypothesis is solved and the selection leaves winner = -1, support = 0; nothing indexes beyond the count.
+struct PnpNHost {};
+struct PnpNDev { const int32_t *n; };
+__device__ __forceinline__ int pnp_n(const PnpNHost &, int n) { return n; }
+__device__ __forceinline__ int pnp_n(const PnpNDev &c, int n) { const int v = *c.n; return v < n ? (v < 0 ? 0 : v) : n; }
+template <typename CN> constexpr bool pnp_n_dev = false;
+template <> constexpr bool pnp_n_dev<PnpNDev> = true;
 // a problem's answer, the same in every thread
 struct PnpAns { double R[9], T[3], err[3]; int32_t best, sta; };
 
@@ -264,13 +273,28 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_solve(PnpSrc s, const int32
 }
 
 // hypothesis h = blockIdx.x over draws[6 h .. 6 h + 5], then every correspondence scored under its answer; masks: `words` 64-bit words a hypothesis
-__global__ __launch_bounds__(64) void k_pnp_hyp(PnpSrc s, const int32_t *__restrict__ draws, double thr_px, int words, unsigned long long *__restrict__ masks,
+template <typename CN>
+__global__ __launch_bounds__(64) void k_pnp_hyp(PnpSrc s_in, const int32_t *__restrict__ draws, double thr_px, int words, unsigned long long *__restrict__ masks,
                                                 int32_t *__restrict__ support, int32_t *__restrict__ state, double *__restrict__ dsum,
-                                                pre3_pnp_result *__restrict__ hyp_res)
+                                                pre3_pnp_result *__restrict__ hyp_res, CN cn)
 {
     __shared__ PnpLds<64> L;
     const int h = blockIdx.x, lane = threadIdx.x;
+    PnpSrc s = s_in;
     PnpAns ans;
+    if constexpr (pnp_n_dev<CN>) {
+        s.n_all = pnp_n(cn, s.n_all);
+        if (s.n_all < PNP_MIN_N) {                                      // (one word for every lane) nothing to sample: empty masks, support 0, state 0
+            for (int w = lane; w < words; w += 64) masks[(size_t)h * words + w] = 0ull;
+            if (lane == 0) {
+                for (int i = 0; i < 9; ++i) ans.R[i] = i % 4 == 0 ? 1.0 : 0.0;
+                ans.T[0] = ans.T[1] = ans.T[2] = 0; ans.err[0] = ans.err[1] = ans.err[2] = NAN; ans.best = 0; ans.sta = PNP_NOT_COMPUTED;
+                support[h] = 0; state[h] = PNP_NOT_COMPUTED; dsum[h] = 0.0;
+                pnp_store(ans, 0, 0, hyp_res + h);
+            }
+            return;
+        }
+    }
     pnp_body<64, true>(s, draws + 6 * (size_t)h, 6, L, ans);
     const bool ok = ans.sta == PNP_OK || ans.sta == PNP_BEST_OF_THREE;
     double P[12];
@@ -300,13 +324,22 @@ __global__ __launch_bounds__(64) void k_pnp_hyp(PnpSrc s, const int32_t *__restr
 }
 
 constexpr int SEL_T = 256;
-__global__ __launch_bounds__(SEL_T) void k_pnp_select(int n_hyp, int n, int words, const int32_t *__restrict__ support, const double *__restrict__ dsum,
+template <typename CN>
+__global__ __launch_bounds__(SEL_T) void k_pnp_select(int n_hyp, int n_in, int words, const int32_t *__restrict__ support, const double *__restrict__ dsum,
                                                       const unsigned long long *__restrict__ masks, PnpCtl *__restrict__ ctl, int32_t *__restrict__ inl_idx,
-                                                      int32_t *__restrict__ inl_flag)
+                                                      int32_t *__restrict__ inl_flag, CN cn)
 {
     __shared__ int s_s[SEL_T / 64], s_i[SEL_T / 64], s_cnt[SEL_T], s_win;
     __shared__ double s_d[SEL_T / 64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = pnp_n(cn, n_in);
+    if constexpr (pnp_n_dev<CN>) {
+        if (n < PNP_MIN_N) {                                            // (one word for every thread) no hypothesis ran
+            if (tid < n) inl_flag[tid] = 0;
+            if (tid == 0) { ctl->winner = -1; ctl->support = 0; }
+            return;
+        }
+    }
     int bs = -1, bi = 0x7fffffff;
     double bd = 0;
     for (int h = tid; h < n_hyp; h += SEL_T) {
@@ -353,11 +386,20 @@ __global__ __launch_bounds__(SEL_T) void k_pnp_select(int n_hyp, int n, int word
     }
 }
 
-__global__ __launch_bounds__(64) void k_pnp_draw(uint64_t seed, uint64_t seq, int n_hyp, int n, int32_t *__restrict__ draws)
+template <typename CN>
+__global__ __launch_bounds__(64) void k_pnp_draw(uint64_t seed, uint64_t seq, int n_hyp, int n_in, int32_t *__restrict__ draws, CN cn)
 {
     const int h = blockIdx.x * 64 + threadIdx.x;
     if (h >= n_hyp) return;
+    const int n = pnp_n(cn, n_in);
     int32_t r[6];
+    if constexpr (pnp_n_dev<CN>) {
+        if (n < PNP_MIN_N) {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) draws[6 * (size_t)h + j] = 0;
+            return;
+        }
+    }
     draw_rule_pnp(seed, seq, n, h, r);
 #pragma unroll
     for (int j = 0; j < 6; ++j) draws[6 * (size_t)h + j] = r[j];
@@ -445,11 +487,11 @@ int pnp_ransac_fill(PnpRansac *r, const pre3_cam *cam, int undistort, int n, con
 int pnp_ransac_launch(const PnpRansac &r, bool draw, uint64_t seed, uint64_t seq, hipStream_t st)
 {
     unsigned long long *masks = r.at<unsigned long long>(r.o_mask);
-    if (draw) hipLaunchKernelGGL(k_pnp_draw, dim3(ceil_div(r.n_hyp, 64)), dim3(64), 0, st, seed, seq, r.n_hyp, r.n, r.at<int32_t>(r.o_draws));
-    hipLaunchKernelGGL(k_pnp_hyp, dim3(r.n_hyp), dim3(64), 0, st, r.src, (const int32_t *)r.at<int32_t>(r.o_draws), r.thr, r.words, masks, r.at<int32_t>(r.o_sup),
-                       r.at<int32_t>(r.o_sta), r.at<double>(r.o_dsum), r.at<pre3_pnp_result>(r.o_hyp));
-    hipLaunchKernelGGL(k_pnp_select, dim3(1), dim3(SEL_T), 0, st, r.n_hyp, r.n, r.words, (const int32_t *)r.at<int32_t>(r.o_sup), (const double *)r.at<double>(r.o_dsum),
-                       (const unsigned long long *)masks, r.at<PnpCtl>(r.o_ctl), r.at<int32_t>(r.o_idx), r.at<int32_t>(r.o_flag));
+    if (draw) hipLaunchKernelGGL(k_pnp_draw<PnpNHost>, dim3(ceil_div(r.n_hyp, 64)), dim3(64), 0, st, seed, seq, r.n_hyp, r.n, r.at<int32_t>(r.o_draws), PnpNHost{});
+    hipLaunchKernelGGL(k_pnp_hyp<PnpNHost>, dim3(r.n_hyp), dim3(64), 0, st, r.src, (const int32_t *)r.at<int32_t>(r.o_draws), r.thr, r.words, masks, r.at<int32_t>(r.o_sup),
+                       r.at<int32_t>(r.o_sta), r.at<double>(r.o_dsum), r.at<pre3_pnp_result>(r.o_hyp), PnpNHost{});
+    hipLaunchKernelGGL(k_pnp_select<PnpNHost>, dim3(1), dim3(SEL_T), 0, st, r.n_hyp, r.n, r.words, (const int32_t *)r.at<int32_t>(r.o_sup), (const double *)r.at<double>(r.o_dsum),
+                       (const unsigned long long *)masks, r.at<PnpCtl>(r.o_ctl), r.at<int32_t>(r.o_idx), r.at<int32_t>(r.o_flag), PnpNHost{});
     hipLaunchKernelGGL(k_pnp_solve<true>, dim3(1), dim3(PNP_THREADS), 0, st, r.src, (const int32_t *)r.at<int32_t>(r.o_idx), (const PnpCtl *)r.at<PnpCtl>(r.o_ctl), 0,
                        r.at<pre3_pnp_result>(r.o_res));
     PRE3_HIP(hipGetLastError());
@@ -495,6 +537,23 @@ int launch_pnp_pair(const VoPairHeader *hdr, const VoOut *out, int n1, const dou
     const PnpSrc s = pnp_src(cam, undistort, n1, pset1, pix2);
     hipLaunchKernelGGL(k_pnp_pair_prep, dim3(1), dim3(PREP_T), 0, st, hdr, out, n1, match, frm2, ldf2, K2, inl, pix2, ctl, idx);
     hipLaunchKernelGGL(k_pnp_solve<true>, dim3(1), dim3(PNP_THREADS), 0, st, s, (const int32_t *)idx, (const PnpCtl *)ctl, 0, res);
+    PRE3_HIP(hipGetLastError());
+    return PRE3_OK;
+}
+
+// pnp_ransac_launch's four launches with the count read on the device (pre3_pnp.h: PnpRansacDev): grid, masks and words sized by r.n_cap
+int launch_pnp_ransac_dev(const PnpRansacDev &r, const pre3_cam *cam, int undistort, uint64_t seed, uint64_t seq, hipStream_t st)
+{
+    static_assert(sizeof(PnpCtl) == sizeof(int32_t) * PNP_CTL_WORDS, "PnpRansacDev::ctl is a PnpCtl");
+    const PnpSrc s = pnp_src(cam, undistort, r.n_cap, r.Xw, r.U);
+    const PnpNDev cn{ r.n_dev };
+    const int words = ceil_div(r.n_cap, 64);
+    PnpCtl *ctl = (PnpCtl *)r.ctl;
+    hipLaunchKernelGGL(k_pnp_draw<PnpNDev>, dim3(ceil_div(r.n_hyp, 64)), dim3(64), 0, st, seed, seq, r.n_hyp, r.n_cap, r.draws, cn);
+    hipLaunchKernelGGL(k_pnp_hyp<PnpNDev>, dim3(r.n_hyp), dim3(64), 0, st, s, (const int32_t *)r.draws, r.thr_px, words, r.masks, r.support, r.state, r.dsum, r.hyp, cn);
+    hipLaunchKernelGGL(k_pnp_select<PnpNDev>, dim3(1), dim3(SEL_T), 0, st, r.n_hyp, r.n_cap, words, (const int32_t *)r.support, (const double *)r.dsum,
+                       (const unsigned long long *)r.masks, ctl, r.idx, r.flag, cn);
+    hipLaunchKernelGGL(k_pnp_solve<true>, dim3(1), dim3(PNP_THREADS), 0, st, s, (const int32_t *)r.idx, (const PnpCtl *)ctl, 0, r.res);
     PRE3_HIP(hipGetLastError());
     return PRE3_OK;
 }

@@ -713,6 +713,33 @@ class EkfFilter:
         out["icp"], out["taken"] = icp, (int(taken[0]), int(taken[1]))
         return out
 
+    RELOC_PN = np.diag([0.05 ** 2] * 3 + [0.02 ** 2] * 4)      # relocalise_seeded's default noise: 5 cm and 0.02 per quaternion entry, one sigma
+
+    def relocalise_seeded(self, seed, seq=0, thresh=1.5, n_hyp=200, thr_px=2.0, undistort=True, min_support=12, Pn=None, wait=True):
+        """Relocalise a lost filter (the project's own, the reference has none): replaces ekf_prediction on the frame on which the
+        caller has judged the filter lost.  siftmatch of the whole map's descriptors against the loaded scan with no window gate, the camera pose by a
+        seeded EPnP RANSAC (vo.pnp_ransac_seeded's launches) from the matched landmarks' 3-D points at x_k_k and the scan's pixels, then the prediction
+        onto that pose with the wide noise Pn ((7, 7) over [dX; dq]; default RELOC_PN), so that P stays a consistent covariance; matching_sift_based and
+        step* follow as after any prediction.  The pose is taken iff the refit ended with sta == 1 over at least min_support inliers; otherwise the
+        identity motion is predicted under this filter's own noise.  Everything stays on the device; the filter's noise setting is unchanged.
+        wait=True: one host wait; returns dict(pnp (vo.efficient_pnp's result dict of the refit), u (the increment applied), n_matches, n_corr, winner
+        (-1: no hypothesis ran), taken, match_idx (2, n_matches) 0-based (k1, k2), inliers (n_corr,) 0/1 flags of the winner over the correspondences).
+        wait=False: returns None at once, nothing is synchronised.  Pre3Error -4: no descriptors, no scan, or the covariance buffer holds the
+        prediction; -1: fewer than 6 landmarks, n_hyp outside 1 .. 700, thresh or thr_px not positive and finite, min_support < 6, a bad Pn."""
+        from . import vo
+        Pn = f64(self.RELOC_PN if Pn is None else Pn)
+        assert Pn.shape == (7, 7), "Pn is 7 x 7 over [dX(3); dq(4)]"
+        args = (self._ctx, float(thresh), int(n_hyp), int(seed), int(seq), float(thr_px), int(bool(undistort)), int(min_support), dptr(Pn))
+        if not wait:
+            check(lib.pre3_relocalise_seeded(*args, None, None, None))
+            return None
+        N = max(self.N, 1)
+        res, pairs, inl = vo.RelocResult(), np.zeros((N, 2), np.int32), np.zeros(N, np.int32)
+        check(lib.pre3_relocalise_seeded(*args, C.byref(res), dptr(pairs), dptr(inl)))
+        nm, nc = int(res.n_matches), int(res.n_corr)
+        return dict(pnp=vo._pnp_dict(res.pnp), u=np.array(res.u), n_matches=nm, n_corr=nc, winner=int(res.winner), taken=int(res.taken),
+                    match_idx=pairs[:nm].T.copy(), inliers=inl[:nc].copy())
+
     def set_process_noise(self, Pn=None):
         """predict_state_and_covariance.m:98-102: the 7 x 7 process noise Pn of every prediction this filter makes from now on (ekf_prediction, step*,
         ekf_prediction_pair_seeded); None returns to the reference's constant.  Must be finite, exactly symmetric and without a negative diagonal

@@ -393,6 +393,11 @@ class PnpResult(C.Structure):
                 ("best", C.c_int32), ("sta", C.c_int32), ("n", C.c_int32), ("n_support", C.c_int32)]
 
 
+class RelocResult(C.Structure):
+    """pre3_reloc_result (include/pre3.h): EkfFilter.relocalise_seeded's result block"""
+    _fields_ = [("pnp", PnpResult), ("u", C.c_double * 7), ("n_matches", C.c_int32), ("n_corr", C.c_int32), ("winner", C.c_int32), ("taken", C.c_int32)]
+
+
 def _pnp_dict(r):
     return dict(R=np.array(r.R).reshape(3, 3), T=np.array(r.T), u=np.array(r.u), err=np.array(r.err), best=int(r.best), sta=int(r.sta), n=int(r.n),
                 n_support=int(r.n_support))

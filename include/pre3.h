@@ -1136,6 +1136,43 @@ PRE3_API int pre3_pnp_limits(int32_t out[2]);
 PRE3_API int pre3_pnp_bench(int device, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, int n_hyp, uint64_t seed, uint64_t seq,
                             double thr_px, int reps, double *ms_per_ransac_out);
 
+/* ---- relocalising a lost filter: the EPnP pose of the whole map against the scan as this frame's prediction --------------------
+ * The project's own follow-up of sections 9 and 35: the reference has no relocalisation.  The call REPLACES the prediction of the frame on which the
+ * caller has judged the filter lost (that judgement is not made here).  On the context's stream, no host wait between the stages:
+ *   1. siftmatch(bank(128 x N), Descriptor_RAW(128 x K2), thresh) over ALL N landmarks -- the double class, the ratio test in float, the first index on
+ *      ties: the match list of pre3_siftmatch_f64 on pre3_get_descriptors and the scan.  No window gate, no descriptor refresh; h, H, S, z, the flags
+ *      and the bank are not touched.
+ *   2. per match (k1, k2), in ascending k1: Xw = the landmark's point at x_k_k, bit-equal to pre3_get_landmarks' xyz (both landmark types), and
+ *      U = entries 0 and 1 of the scan's SCALE_ORIENT_POS_RAW at k2 -- what pre3_ic_search installs as z.  A match whose point is not finite (an
+ *      inverse depth of 0) is left out, order kept; two landmarks may match one keypoint, both stay.
+ *   3. pre3_pnp_ransac_seeded's four launches over those n_corr correspondences, the count read on the device: draws draw_rule_pnp(seed, seq, n_corr, h).
+ *      n_corr < 6: no hypothesis is solved, winner = -1, pnp.sta = 0.
+ *   4. the prediction, with u and Pn chosen on the device: the pose is taken iff pnp.sta == 1 and pnp.n_support >= min_support.  Taken: with
+ *      [r*; q*] = pnp.u = [-R'T; R2q(R')] and [r; q] = x_k_k[0:7], dX = R(q)'(r* - r), dq = conj(q) (x) q* / |q|^2, negated if its scalar part is
+ *      negative (q stays in the hemisphere the cross-covariances of P were built in), and Pn = Pn_reloc, a wide noise of the caller's so that P stays a
+ *      consistent covariance.  Not taken: u = [0 0 0 1 0 0 0] and the context's own noise (pre3_set_process_noise's, or the constant).
+ * The ordinary step (pre3_ic_search, pre3_step*) follows as after any prediction.  A deferred HI update is completed first, P follows pre3_predict, and
+ * the context's noise setting is unchanged afterwards.  Bit-equal to the chain pre3_get_landmarks, pre3_siftmatch_f64, a gather of the finite matches,
+ * pre3_pnp_ransac_seeded, pre3_set_process_noise(Pn_reloc) when taken, pre3_predict(u), the noise setting restored.  Nothing crosses PCIe but the result
+ * block; ONE host wait, none when res_out, pairs_out and inlier_out are all NULL.  No allocation: the work block is sized at pre3_create.
+ * pairs_out: the first 2 * n_matches entries are written; inlier_out: the winner's 0/1 flags over the n_corr correspondences.
+ * PRE3_E_STATE (nothing queued, the context unchanged): no descriptor bank, no scan (or an empty one), the covariance buffer does not hold (x_k_k, p_k_k).
+ * PRE3_E_ARG (the same): N < 6 or beyond pre3_reloc_limits, n_hyp outside 1 .. 700, thr_px or thresh not positive and finite, min_support < 6,
+ * Pn_reloc null or refused by pre3_set_process_noise's checks (finite, no negative diagonal entry, exactly symmetric), no camera set. */
+typedef struct pre3_reloc_result {
+    pre3_pnp_result pnp;     /* the refit over the winner's inliers, as pre3_pnp_ransac_seeded's res */
+    double u[7];             /* the increment the prediction applied (identity when not taken) */
+    int32_t n_matches;       /* matches of siftmatch(bank, scan) */
+    int32_t n_corr;          /* of those, correspondences with a finite 3-D point: the PnP's n */
+    int32_t winner;          /* winning hypothesis, -1 if none ran */
+    int32_t taken;           /* 1: pose taken; 0: identity u and the context's own noise */
+} pre3_reloc_result;
+PRE3_API int pre3_relocalise_seeded(pre3_ctx *ctx, double thresh, int n_hyp, uint64_t seed, uint64_t seq, double thr_px, int undistort, int min_support,
+                                    const double *Pn_reloc /* [49] */, pre3_reloc_result *res_out,
+                                    int32_t *pairs_out /* [2 * N] (k1, k2) 0-based, may be NULL */, int32_t *inlier_out /* [N] over the correspondences, may be NULL */);
+/* out = { the largest N, the largest n_hyp } the call takes */
+PRE3_API int pre3_reloc_limits(int32_t out[2]);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them

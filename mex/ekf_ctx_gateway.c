@@ -861,6 +861,35 @@ void mexFunction(int nout, mxArray *out[], int nin, const mxArray *in[])
         if (!g_sr) mexErrMsgTxt("pre3_mex('set_scan_frame'): call pre3_mex('sr_frame', ...) and pre3_mex('sr_keypoints', ...) first");
         check(pre3_set_scan_frame(g_ctx, g_sr, nin > 1 ? (int)mxGetScalar(in[1]) : 0));
     }
+    else if (!strcmp(cmd, "relocalise")) {        /* [T, q, taken, sta, n_support, match_idx, inliers, R, Tc] = pre3_mex('relocalise', seed, seq, Pn [, n_hyp = 200, thr_px = 2,
+                                                     min_support = 12, undistort = 1, thresh = 1.5]): the library's own, the reference has none -- IN PLACE OF 'predict' on a frame
+                                                     on which the caller has judged the filter lost: siftmatch of the whole map against the scan with no gate, the EPnP RANSAC of
+                                                     'pnp_ransac' over the matched landmarks' 3-D points and the scan's pixels, then the prediction onto that pose under the wide
+                                                     7 x 7 noise Pn; 'ic_search' and 'step_predicted' follow as usual.  T, q: the increment applied (the identity unless taken);
+                                                     sta, n_support: the refit's; match_idx 2 x M, 1-based; inliers: 0/1 over the correspondences; R, Tc with Xc = R Xw + Tc.
+                                                     Without output arguments nothing is waited for (pre3_relocalise_seeded) */
+        pre3_reloc_result r; int N = pre3_get_map(g_ctx, NULL), i, k, rc;
+        int32_t *pairs, *inl;
+        if (nin < 4 || nin > 9) mexErrMsgTxt("pre3_mex('relocalise', seed, seq, Pn [, n_hyp, thr_px, min_support, undistort, thresh]): three to eight arguments");
+        if (!mxIsDouble(in[3]) || mxIsComplex(in[3]) || mxGetM(in[3]) != 7 || mxGetN(in[3]) != 7) mexErrMsgTxt("pre3_mex('relocalise', seed, seq, Pn): Pn is a real 7 x 7 double matrix");
+        memset(&r, 0, sizeof r);
+        pairs = (int32_t *)mxCalloc(2 * (N ? N : 1), sizeof(int32_t)); inl = (int32_t *)mxCalloc(N ? N : 1, sizeof(int32_t));
+        rc = pre3_relocalise_seeded(g_ctx, nin > 8 ? mxGetScalar(in[8]) : 1.5, nin > 4 ? (int)mxGetScalar(in[4]) : 200, (uint64_t)mxGetScalar(in[1]), (uint64_t)mxGetScalar(in[2]),
+                                    nin > 5 ? mxGetScalar(in[5]) : 2.0, nin > 7 ? (int)mxGetScalar(in[7]) : 1, nin > 6 ? (int)mxGetScalar(in[6]) : 12,
+                                    mxGetPr(in[3]) /* (symmetric: row-major == column-major) */, nout > 0 ? &r : NULL, nout > 5 ? pairs : NULL, nout > 6 ? inl : NULL);
+        if (rc == PRE3_OK) {
+            if (nout > 0) { out[0] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[0]), r.u, sizeof(double) * 3); }
+            if (nout > 1) { out[1] = mxCreateDoubleMatrix(4, 1, mxREAL); memcpy(mxGetPr(out[1]), r.u + 3, sizeof(double) * 4); }
+            if (nout > 2) out[2] = mxCreateDoubleScalar(r.taken);
+            if (nout > 3) out[3] = mxCreateDoubleScalar(r.pnp.sta);
+            if (nout > 4) out[4] = mxCreateDoubleScalar(r.pnp.n_support);
+            if (nout > 5) { out[5] = mxCreateDoubleMatrix(2, r.n_matches, mxREAL); for (i = 0; i < 2 * r.n_matches; ++i) mxGetPr(out[5])[i] = pairs[i] + 1; }
+            if (nout > 6) { out[6] = mxCreateDoubleMatrix(1, r.n_corr, mxREAL); for (i = 0; i < r.n_corr; ++i) mxGetPr(out[6])[i] = inl[i]; }
+            if (nout > 7) { out[7] = mxCreateDoubleMatrix(3, 3, mxREAL); for (i = 0; i < 3; ++i) for (k = 0; k < 3; ++k) mxGetPr(out[7])[i + 3 * k] = r.pnp.R[3 * i + k]; }
+            if (nout > 8) { out[8] = mxCreateDoubleMatrix(3, 1, mxREAL); memcpy(mxGetPr(out[8]), r.pnp.T, sizeof(double) * 3); }
+        }
+        mxFree(pairs); mxFree(inl); check(rc);
+    }
     else if (!strcmp(cmd, "ic_search")) {         /* [meas_idx, z, match_idx] = pre3_mex('ic_search', 1.5, strict)   matching_sift_based.m:104-149 */
         int N = pre3_get_map(g_ctx, NULL), i, rc; int32_t nm = 0, m = 0;
         int32_t *meas = (int32_t *)mxCalloc(N ? N : 1, sizeof(int32_t)), *pairs = (int32_t *)mxCalloc(3 * (N ? N : 1), sizeof(int32_t));
