@@ -106,6 +106,9 @@ lib.pre3_vo_pair_pnp_seeded.argtypes = [_P, _P, _D, _U, _U, _P, _I, _P, _P, _P, 
 lib.pre3_pnp_bench.argtypes = [_I, _P, _I, _I, _P, _P, _I, _U, _U, _D, _I, _P]
 lib.pre3_relocalise_seeded.argtypes = [_P, _D, _I, _U, _U, _D, _I, _I, _P, _P, _P, _P]
 lib.pre3_reloc_limits.argtypes = [_P]
+lib.pre3_pnp_refine.argtypes = [_I, _P, _I, _I, _P, _P, _P, _P, _I, _D, _P]
+lib.pre3_pnp_ransac_refined_seeded.argtypes = [_I, _P, _I, _I, _P, _P, _I, _U, _U, _D, _P, _P, _P, _P, _P, _P, _I, _D, _P]
+lib.pre3_relocalise_refined_seeded.argtypes = [_P, _D, _I, _U, _U, _D, _I, _I, _I, _D, _I, _P, _P, _P, _P]
 lib.pre3_test_downdate.argtypes = [_P, _I, _P, _I]            # csrc/pre3_test_hooks.h, not include/pre3.h: not in EXPORTS
 lib.pre3_test_factor_solve.argtypes = [_P, _I, _P, _P, _P, _I, _I, _P, _P]      # (the same)
 
@@ -191,4 +194,5 @@ EXPORTS = [
     "pre3_icp_cov", "pre3_icp_cov_limits", "pre3_icp_cov_bench", "pre3_icp_pair_cov_seeded", "pre3_predict_icp_pair_seeded",
     "pre3_epnp", "pre3_pnp_ransac", "pre3_pnp_ransac_seeded", "pre3_pnp_limits", "pre3_pnp_bench", "pre3_vo_pair_pnp_seeded",
     "pre3_relocalise_seeded", "pre3_reloc_limits",
+    "pre3_pnp_refine", "pre3_pnp_ransac_refined_seeded", "pre3_relocalise_refined_seeded",
 ]

@@ -118,6 +118,44 @@ __device__ __forceinline__ const U7 &predict_u(const PredictUReloc &s, U7 &ud)
     return ud;
 }
 __device__ __forceinline__ const double *predict_pn_src(const PnReloc &s) { return reloc_takes(s.res->sta, s.res->n_support, s.min_support) ? s.pn : s.behind; }
+// The same behind k_pnp_refine (US = PredictURelocRef, NS = PnRelocRef; pre3_relocalise_refined_seeded): the refinement's u when its
+// sta is 1, and the noise under reloc_noise_rule.  predict_pn_src gives the block that is copied first -- the caller's, which the pose's covariance then
+// replaces (PRE3_RELOC_NOISE_POSE) or is added to (_POSE_FLOOR) in predict_pn_pose below.
+__device__ __forceinline__ const U7 &predict_u(const PredictURelocRef &s, U7 &ud)
+{
+    const double *pu = s.ref->sta == 1 ? s.ref->u : s.b.res->u;
+    const int taken = reloc_select(s.b.x, s.b.res->sta, s.b.res->n_support, s.b.min_support, pu, ud.v);
+    if (blockIdx.x == 0) {
+        for (int i = 0; i < 7; ++i) s.b.u_out[i] = ud.v[i];
+        s.b.taken_out[0] = taken;
+    }
+    return ud;
+}
+__device__ __forceinline__ int predict_pn_rule(const PnRelocRef &s)
+{
+    return reloc_noise_rule(reloc_takes(s.b.res->sta, s.b.res->n_support, s.b.min_support), s.noise, s.ref->sta);
+}
+__device__ __forceinline__ const double *predict_pn_src(const PnRelocRef &s) { return predict_pn_rule(s) == RELOC_NOISE_OWN ? s.b.behind : s.b.pn; }
+// block 0, every thread, behind the barrier that follows the load of Pn: sPn <- reloc_noise_from_pose(x, ref.cov) [+ sPn], one entry a lane of the second
+// wave and a barrier between the stages; then the noise the prediction uses and its source go out
+__device__ __forceinline__ void predict_pn_pose(const PnRelocRef &s, double *sPn)
+{
+    __shared__ double rJd[49], rT[49], rM[49];
+    const int rule = predict_pn_rule(s), t = (int)threadIdx.x - 64;
+    const bool lane = t >= 0 && t < 49;
+    if (rule == RELOC_NOISE_POSE || rule == RELOC_NOISE_POSE_FLOOR) {       // (words earlier launches wrote: the block takes the branch as one)
+        if (t == 0) reloc_noise_jd(s.x, rJd);
+        __syncthreads();
+        if (lane) rT[t] = reloc_noise_left(rJd, s.ref->cov, t);
+        __syncthreads();
+        if (lane) rM[t] = reloc_noise_right(rT, rJd, t);
+        __syncthreads();
+        if (lane) { const double p = reloc_noise_sym(rM, t); sPn[t] = rule == RELOC_NOISE_POSE_FLOOR ? reloc_noise_floor(p, sPn[t]) : p; }
+        __syncthreads();
+    }
+    if (lane) s.pn_out[t] = sPn[t];
+    if (t == 0) s.noise_out[0] = rule;
+}
 template <typename T, typename US = U7, typename NS = PnConst>
 __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in, double *x_out, T *__restrict__ P, int n, int ld, US u,
                                                  double *__restrict__ params, int n_pred_blocks, ProjRide pr, InboxRide ib, int fuse_jn, PendW pw = PendW{}, NS ns = NS{})
@@ -180,6 +218,9 @@ __global__ __launch_bounds__(256) void k_predict(const double *__restrict__ x_in
             if (add != nullptr && threadIdx.x >= 64 && threadIdx.x < 64 + 49) sPn[threadIdx.x - 64] = add[threadIdx.x - 64] + sPn[threadIdx.x - 64];
             __syncthreads();
         }
+    }
+    if constexpr (std::is_same<NS, PnRelocRef>::value) {
+        if (blockIdx.x == 0) predict_pn_pose(ns, sPn);             // the refinement's covariance as Pn, or on the caller's floor, which sPn holds by now
     }
     double cfix = 0; int cpos = -1;
     if (fuse_jn) {
@@ -1256,6 +1297,20 @@ int launch_predict_reloc(pre3_ctx *c, const PredictUReloc &u_reloc, const double
     const int fuse_jn = c->carry.jn_pending ? 1 : 0;
     const PnReloc ns{ u_reloc.res, u_reloc.min_support, pn_reloc_dev, c->pn_set ? c->pred_params + PRED_PN_OFF : nullptr };
     predict_launch(c, blocks, u_reloc, ns, blocks, ProjRide{}, InboxRide{}, fuse_jn);
+    PRE3_HIP(hipGetLastError());
+    c->carry.jn_pending = false;
+    return PRE3_OK;
+}
+
+// the same behind k_pnp_refine: the refinement's u and the noise of the caller's mode (pre3_relocalise_refined_seeded)
+int launch_predict_reloc_refined(pre3_ctx *c, const PredictUReloc &u_reloc, const double *pn_reloc_dev, const pre3_pnp_refine_result *ref, int noise, double *pn_out,
+                                 int32_t *noise_out)
+{
+    const int blocks = ceil_div(c->n, 256);
+    const int fuse_jn = c->carry.jn_pending ? 1 : 0;
+    const PredictURelocRef us{ u_reloc, ref };
+    const PnRelocRef ns{ PnReloc{ u_reloc.res, u_reloc.min_support, pn_reloc_dev, c->pn_set ? c->pred_params + PRED_PN_OFF : nullptr }, ref, u_reloc.x, noise, pn_out, noise_out };
+    predict_launch(c, blocks, us, ns, blocks, ProjRide{}, InboxRide{}, fuse_jn);
     PRE3_HIP(hipGetLastError());
     c->carry.jn_pending = false;
     return PRE3_OK;

@@ -32,6 +32,12 @@ struct PnIcp { PredictIcpSrc s; const double *behind; };
 // leaves the increment and whether the pose was taken in u_out[0..6] / taken_out[0]; PnReloc (NS): the caller's wide noise when taken, else `behind`.
 struct PredictUReloc { const pre3_pnp_result *res; const double *x; int32_t min_support; double *u_out; int32_t *taken_out; };
 struct PnReloc { const pre3_pnp_result *res; int32_t min_support; const double *pn; const double *behind; };
+// The same where k_pnp_refine ran between the refit and this launch (pre3_relocalise_refined_seeded).  PredictURelocRef (US): the
+// taking rule is PredictUReloc's on the refit, u comes from the refinement's result when its sta is 1.  PnRelocRef (NS): reloc_noise_rule (pre3_reloc.h)
+// over the caller's mode -- the caller's block, the refinement's covariance carried to the increment at x (reloc_noise_from_pose's items, dealt over 49
+// lanes of block 0), or their sum --, `behind` when the pose is not taken; block 0 leaves the noise it used and its source in pn_out[49] / noise_out[0].
+struct PredictURelocRef { PredictUReloc b; const pre3_pnp_refine_result *ref; };
+struct PnRelocRef { PnReloc b; const pre3_pnp_refine_result *ref; const double *x; int32_t noise; double *pn_out; int32_t *noise_out; };
 
 // ------------------------------------------------------------------------------------------------
 // device math (fp64)

@@ -386,6 +386,9 @@ int launch_predict_icp(pre3_ctx *c, const PredictUIcp &u_icp);
 // the prediction behind an EPnP RANSAC of the map against the scan: u and Pn under reloc_select (pre3_reloc.h)
 struct PredictUReloc;
 int launch_predict_reloc(pre3_ctx *c, const PredictUReloc &u_reloc, const double *pn_reloc_dev);
+// the same behind k_pnp_refine (pre3_relocalise_refined_seeded): noise is PRE3_RELOC_NOISE_*, pn_out[49] / noise_out[0] what was used
+int launch_predict_reloc_refined(pre3_ctx *c, const PredictUReloc &u_reloc, const double *pn_reloc_dev, const pre3_pnp_refine_result *ref, int noise, double *pn_out,
+                                 int32_t *noise_out);
 // pre3_relocalise_seeded's device block and the pinned image of what it returns, sized by the map capacity (pre3_reloc.hip; pre3_create)
 int reloc_alloc(pre3_ctx *c);
 // the camera-only prediction (pre3_predict_cv; pre3_predictcv.h): one launch, no riders, pred_params untouched

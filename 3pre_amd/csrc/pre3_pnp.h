@@ -342,5 +342,7 @@ struct PnpRansacDev {
     unsigned long long *masks; int32_t *draws, *support, *state; double *dsum; int32_t *ctl, *idx, *flag; pre3_pnp_result *res, *hyp;
 };
 int launch_pnp_ransac_dev(const PnpRansacDev &r, const pre3_cam *cam, int undistort, uint64_t seed, uint64_t seq, hipStream_t st);
+// k_pnp_refine (pre3_pnpref.h) behind those launches on st, no wait: Gauss-Newton over the winner's list from the refit's result block
+int launch_pnp_refine_dev(const PnpRansacDev &r, const pre3_cam *cam, int undistort, int n_iter, double sigma_px, pre3_pnp_refine_result *ref, hipStream_t st);
 }  // namespace pre3
 #endif

@@ -6,6 +6,8 @@
 // k_pnp_select  one workgroup: the winner (largest support, smallest inlier distance sum, lowest index) and its inlier list in ascending order.
 // k_pnp_draw    one lane per hypothesis: six distinct of n (pre3_philox.h, stream 6).
 // k_pnp_pair_prep  one workgroup behind a VO pair's launches (pre3_vo_pair_pnp_seeded): cur's pixels of the matches, the pair's inliers as a list.
+// k_pnp_refine  one workgroup of 256 threads: Gauss-Newton on the reprojection error from a result block's pose, and the pose's covariance (pre3_pnpref.h;
+//               DESIGN.md section 37).
 // One body (pnp_body), templated on the thread count and on whether the points come through an index list.  Every sum over the points: thread t adds
 // points t, t + NT, ... in ascending order, the lanes of a wave meet in the xor butterfly, the waves in wave order through LDS -- a tree whose shape
 // depends on the count alone.  No floating-point atomics: equal bits from run to run.  The 12 x 12, its eigenvectors and the 6 x 7 system live in
@@ -20,6 +22,7 @@
 #include "pre3_geomdev.h"
 #include "pre3_philox.h"
 #include "pre3_pnp.h"
+#include "pre3_pnpref.h"
 #include "pre3_vodev.h"
 #include "pre3_vopair.h"
 
@@ -439,6 +442,100 @@ __global__ __launch_bounds__(PREP_T) void k_pnp_pair_prep(const VoPairHeader *__
     for (int i = i0; i < i1; ++i) if (inl[i] != 0) list[o++] = i;       // o <= i < n1
 }
 
+// ---- the refinement (pre3_pnpref.h) ------------------------------------------------------------------------------------------
+// One pass over the points at the pose (R, T): the 28 sums in every thread, and whether every depth is positive.  The pixels are undistorted again in
+// every pass (sixteen points a thread at the relocaliser's 4096): no scratch array.
+template <bool IDX>
+__device__ __forceinline__ bool pnpref_pass(const PnpSrc &s, const int32_t *idx, int n, const double R[9], const double T[3], double *red, double (&acc)[PNPREF_SUMS])
+{
+    bool front = true;
+#pragma unroll
+    for (int i = 0; i < PNPREF_SUMS; ++i) acc[i] = 0;
+#pragma unroll 1
+    for (int k = threadIdx.x; k < n; k += PNP_THREADS) {
+        double xw[3], u, v;
+        pnp_point<IDX>(s, idx, k, xw, &u, &v, true);
+        const double z = pnpref_point(R, T, s.cam.f, s.cam.Cx, s.cam.Cy, xw, u, v, acc);
+        front = front && z > 0;
+    }
+    pnp_reduce<PNPREF_SUMS, PNP_THREADS>(acc, red);
+    return __syncthreads_and(front ? 1 : 0) != 0;
+}
+
+// The starting pose comes from a result block in device memory (the refit's, or the one pre3_pnp_refine uploads); idx, ctl and n_host as k_pnp_solve.
+// Every thread holds the same sums behind pnp_reduce, so every thread solves and updates for itself (as pnp_dim's scalars) and every branch on them is
+// taken by the workgroup as one.  Exactly n_iter steps.  Thread 0 writes the result; cost[k] goes out as the loop finds it (an index chosen at run time
+// would put a local array into scratch).
+template <bool IDX>
+__global__ __launch_bounds__(PNP_THREADS) void k_pnp_refine(PnpSrc s, const int32_t *__restrict__ idx, const PnpCtl *__restrict__ ctl, int n_host,
+                                                            const pre3_pnp_result *__restrict__ start, int n_iter, double sigma_px,
+                                                            pre3_pnp_refine_result *__restrict__ out)
+{
+    __shared__ double red[(PNP_THREADS / 64) * PNPREF_SUMS];
+    const int tid = threadIdx.x;
+    int n = n_host;
+    if (ctl != nullptr) n = ctl->support;
+    if (n > s.n_all) n = s.n_all;
+    if (n < 0) n = 0;
+    const int sta_in = start->sta;
+    double R0[9], T0[3], R[9], T[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = R0[i] = start->R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) T[i] = T0[i] = start->T[i];
+    if (tid == 0) {
+        for (int i = 0; i <= PNPREF_MAX_ITER; ++i) out->cost[i] = NAN;
+        for (int i = 0; i < 36; ++i) out->cov6[i] = NAN;
+        for (int i = 0; i < 49; ++i) out->cov[i] = NAN;
+        for (int i = 0; i < 9; ++i) out->R[i] = R0[i];
+        for (int i = 0; i < 3; ++i) out->T[i] = T0[i];
+        for (int i = 0; i < 7; ++i) out->u[i] = start->u[i];
+        out->sigma2 = NAN; out->sta = PNPREF_NOT_COMPUTED; out->n = n; out->n_iter = n_iter; out->pad = 0;
+    }
+    if (!(sta_in == PNP_OK || sta_in == PNP_BEST_OF_THREE) || n < PNP_MIN_N) return;        // (the same words for every thread)
+    double acc[PNPREF_SUMS], cost_first = 0;
+    bool fin = true;
+#pragma unroll 1
+    for (int k = 0; k < n_iter; ++k) {
+        (void)pnpref_pass<IDX>(s, idx, n, R, T, red, acc);
+        if (k == 0) cost_first = acc[27];
+        if (tid == 0) out->cost[k] = acc[27];
+        fin = fin && pnp_finite(acc, PNPREF_SUMS);
+        fin = pnpref_step(acc, R, T) && fin;
+        fin = fin && pnp_finite(R, 9) && pnp_finite(T, 3);
+    }
+    bool front = pnpref_pass<IDX>(s, idx, n, R, T, red, acc);
+    if (n_iter == 0) cost_first = acc[27];
+    if (tid == 0) out->cost[n_iter] = acc[27];
+    fin = fin && pnp_finite(acc, PNPREF_SUMS);
+    const bool taken = pnpref_takes(n_iter, fin, front, cost_first, acc[27]);
+    if (!taken && n_iter >= 1) {                                        // the input pose is kept: the covariance is evaluated there
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = R0[i];
+        T[0] = T0[0]; T[1] = T0[1]; T[2] = T0[2];
+        front = pnpref_pass<IDX>(s, idx, n, R, T, red, acc);
+    }
+    if (tid != 0) return;
+    double u[7], cov6[36], cov7[49];
+    const double s2 = pnpref_sigma2(sigma_px, acc[27], n);
+    pnp_pair_u(R, T, u);
+    bool ok = front && pnp_finite(acc, PNPREF_SUMS) && isfinite(s2) && pnp_finite(u, 7);
+    ok = ok && pnpref_cov6(acc, s2, cov6);
+    ok = ok && pnpref_cov7(R, u, cov6, cov7);
+    if (!ok) {                                                          // no covariance: the input's pose
+        pnp_pair_u(R0, T0, u);
+        for (int i = 0; i < 7; ++i) out->u[i] = u[i];
+        out->sta = PNPREF_NO_COV;
+        return;
+    }
+    for (int i = 0; i < 9; ++i) out->R[i] = R[i];
+    for (int i = 0; i < 3; ++i) out->T[i] = T[i];
+    for (int i = 0; i < 7; ++i) out->u[i] = u[i];
+    for (int i = 0; i < 36; ++i) out->cov6[i] = cov6[i];
+    for (int i = 0; i < 49; ++i) out->cov[i] = cov7[i];
+    out->sigma2 = s2; out->sta = taken ? PNPREF_TAKEN : PNPREF_KEPT;
+}
+
 // ---- the host side ---------------------------------------------------------------------------------------------------------------------------------
 int pnp_check(const char *who, const pre3_cam *cam, int n, const double *Xw, const double *U, const void *res)
 {
@@ -456,15 +553,17 @@ PnpSrc pnp_src(const pre3_cam *cam, int undistort, int n, const double *Xw_dev, 
     return s;
 }
 
-// the RANSAC's block: [Xw | U | masks | out], out = [draws | support | state | dsum | ctl | list | flags | res | hypothesis results] comes back in one copy
+// the RANSAC's block: [Xw | U | masks | out], out = [draws | support | state | dsum | ctl | list | flags | res | ref | hypothesis results] comes back in one
+// copy; ref, the refinement's result, is there in the refined form alone
 struct PnpRansac {
     Scratch blk; PnpSrc src; int n, n_hyp, words; double thr;
-    size_t o_mask, o_out, o_draws, o_sup, o_sta, o_dsum, o_ctl, o_idx, o_flag, o_res, o_hyp, total;
+    size_t o_mask, o_out, o_draws, o_sup, o_sta, o_dsum, o_ctl, o_idx, o_flag, o_res, o_ref, o_hyp, total;
     char *d;
     template <typename T> T *at(size_t o) const { return (T *)(d + o); }
 };
 
-int pnp_ransac_fill(PnpRansac *r, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, int n_hyp, const int32_t *draws, double thr)
+int pnp_ransac_fill(PnpRansac *r, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, int n_hyp, const int32_t *draws, double thr,
+                    bool refined = false)
 {
     r->n = n; r->n_hyp = n_hyp; r->words = ceil_div(n, 64); r->thr = thr;
     const size_t o_xw = 0, o_u = o_xw + up16(sizeof(double) * 3 * (size_t)n), o_mask = o_u + up16(sizeof(double) * 2 * (size_t)n);
@@ -473,7 +572,7 @@ int pnp_ransac_fill(PnpRansac *r, const pre3_cam *cam, int undistort, int n, con
     r->o_draws = r->o_out; r->o_sup = r->o_draws + up16(sizeof(int32_t) * 6 * (size_t)n_hyp); r->o_sta = r->o_sup + up16(sizeof(int32_t) * (size_t)n_hyp);
     r->o_dsum = r->o_sta + up16(sizeof(int32_t) * (size_t)n_hyp); r->o_ctl = r->o_dsum + up16(sizeof(double) * (size_t)n_hyp);
     r->o_idx = r->o_ctl + up16(sizeof(PnpCtl)); r->o_flag = r->o_idx + up16(sizeof(int32_t) * (size_t)n); r->o_res = r->o_flag + up16(sizeof(int32_t) * (size_t)n);
-    r->o_hyp = r->o_res + up16(sizeof(pre3_pnp_result)); r->total = r->o_hyp + up16(sizeof(pre3_pnp_result) * (size_t)n_hyp);
+    r->o_ref = r->o_res + up16(sizeof(pre3_pnp_result)); r->o_hyp = r->o_ref + (refined ? up16(sizeof(pre3_pnp_refine_result)) : 0); r->total = r->o_hyp + up16(sizeof(pre3_pnp_result) * (size_t)n_hyp);
     PRE3_TRY(r->blk.alloc(r->total));
     r->d = r->blk.as<char>();
     PRE3_HIP(hipMemcpy(r->d + o_xw, Xw, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
@@ -506,14 +605,32 @@ int pnp_ransac_args(const char *who, const pre3_cam *cam, int n, const double *X
     return PRE3_OK;
 }
 
+// k_pnp_refine over the winner's list, from the refit's result block: behind pnp_ransac_launch on st, no wait
+int pnp_refine_launch(const PnpRansac &r, int n_iter, double sigma_px, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_pnp_refine<true>, dim3(1), dim3(PNP_THREADS), 0, st, r.src, (const int32_t *)r.at<int32_t>(r.o_idx), (const PnpCtl *)r.at<PnpCtl>(r.o_ctl), 0,
+                       (const pre3_pnp_result *)r.at<pre3_pnp_result>(r.o_res), n_iter, sigma_px, r.at<pre3_pnp_refine_result>(r.o_ref));
+    PRE3_HIP(hipGetLastError());
+    return PRE3_OK;
+}
+
+int pnp_refine_args(const char *who, int n_iter, double sigma_px)
+{
+    PRE3_CHECK(n_iter >= 0 && n_iter <= PNPREF_MAX_ITER, PRE3_E_ARG, "%s: %d iterations, 0 .. %d are run", who, n_iter, PNPREF_MAX_ITER);
+    PRE3_CHECK(std::isfinite(sigma_px) && sigma_px >= 0, PRE3_E_ARG, "%s: sigma_px must be finite and not negative", who);
+    return PRE3_OK;
+}
+
+// ref != nullptr: the refined form (n_iter, sigma_px), one more launch in front of the one wait
 int pnp_ransac_run(const char *who, int device, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, int n_hyp, const int32_t *draws,
                    bool seeded, uint64_t seed, uint64_t seq, double thr_px, int32_t *draws_out, int32_t *support_out, int32_t *state_out, int32_t *inlier_out,
-                   pre3_pnp_result *hyp_res_out, pre3_pnp_result *res)
+                   pre3_pnp_result *hyp_res_out, pre3_pnp_result *res, int n_iter = 0, double sigma_px = 0, pre3_pnp_refine_result *ref = nullptr)
 {
     PRE3_TRY(select_device(who, device));
     PnpRansac r;
-    PRE3_TRY(pnp_ransac_fill(&r, cam, undistort, n, Xw, U, n_hyp, seeded ? nullptr : draws, thr_px));
+    PRE3_TRY(pnp_ransac_fill(&r, cam, undistort, n, Xw, U, n_hyp, seeded ? nullptr : draws, thr_px, ref != nullptr));
     PRE3_TRY(pnp_ransac_launch(r, seeded, seed, seq, 0));
+    if (ref != nullptr) PRE3_TRY(pnp_refine_launch(r, n_iter, sigma_px, 0));
     const size_t bytes = (hyp_res_out != nullptr ? r.total : r.o_hyp) - r.o_out;
     std::vector<char> out(bytes);
     PRE3_HIP(hipMemcpy(out.data(), r.d + r.o_out, bytes, hipMemcpyDeviceToHost));              // the one wait
@@ -524,10 +641,21 @@ int pnp_ransac_run(const char *who, int device, const pre3_cam *cam, int undisto
     if (inlier_out) memcpy(inlier_out, o + r.o_flag, sizeof(int32_t) * (size_t)n);
     if (hyp_res_out) memcpy(hyp_res_out, o + r.o_hyp, sizeof(pre3_pnp_result) * (size_t)n_hyp);
     memcpy(res, o + r.o_res, sizeof *res);
+    if (ref) memcpy(ref, o + r.o_ref, sizeof *ref);
     return PRE3_OK;
 }
 
 }  // namespace
+
+// k_pnp_refine behind launch_pnp_ransac_dev on st, no wait: over the same list and count, from the refit's result block
+int launch_pnp_refine_dev(const PnpRansacDev &r, const pre3_cam *cam, int undistort, int n_iter, double sigma_px, pre3_pnp_refine_result *ref, hipStream_t st)
+{
+    const PnpSrc s = pnp_src(cam, undistort, r.n_cap, r.Xw, r.U);
+    hipLaunchKernelGGL(k_pnp_refine<true>, dim3(1), dim3(PNP_THREADS), 0, st, s, (const int32_t *)r.idx, (const PnpCtl *)r.ctl, 0, (const pre3_pnp_result *)r.res, n_iter,
+                       sigma_px, ref);
+    PRE3_HIP(hipGetLastError());
+    return PRE3_OK;
+}
 
 int launch_pnp_pair(const VoPairHeader *hdr, const VoOut *out, int n1, const double *pset1, const double *match, const double *frm2, int ldf2, int K2,
                     const int32_t *inl, const pre3_cam *cam, int undistort, double *pix2, int32_t *list, pre3_pnp_result *res, hipStream_t st)
@@ -611,6 +739,46 @@ int pre3_pnp_ransac_seeded(int device, const pre3_cam *cam, int undistort, int n
     const char *who = "pre3_pnp_ransac_seeded";
     PRE3_TRY(pnp_ransac_args(who, cam, n, Xw, U, n_hyp, thr_px, res));
     return pnp_ransac_run(who, device, cam, undistort, n, Xw, U, n_hyp, nullptr, true, seed, seq, thr_px, draws_out, support_out, state_out, inlier_out, hyp_res_out, res);
+}
+
+int pre3_pnp_refine(int device, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, const double *R0, const double *T0, int n_iter,
+                    double sigma_px, pre3_pnp_refine_result *res)
+{
+    const char *who = "pre3_pnp_refine";
+    PRE3_TRY(pnp_check(who, cam, n, Xw, U, res));
+    PRE3_CHECK(R0 != nullptr && T0 != nullptr, PRE3_E_ARG, "%s: a null starting pose", who);
+    PRE3_TRY(pnp_refine_args(who, n_iter, sigma_px));
+    PRE3_TRY(select_device(who, device));
+    const size_t o_u = up16(sizeof(double) * 3 * (size_t)n), o_start = o_u + up16(sizeof(double) * 2 * (size_t)n), o_res = o_start + up16(sizeof(pre3_pnp_result));
+    Scratch blk;
+    PRE3_TRY(blk.alloc(o_res + sizeof(pre3_pnp_refine_result)));
+    char *d = blk.as<char>();
+    pre3_pnp_result start;
+    memset(&start, 0, sizeof start);
+    memcpy(start.R, R0, sizeof start.R); memcpy(start.T, T0, sizeof start.T);
+    pnp_pair_u(start.R, start.T, start.u);                              // (the kernel forms u of the pose it ends on itself: these seven are never returned)
+    start.err[0] = start.err[1] = start.err[2] = NAN; start.sta = PNP_OK; start.n = n; start.n_support = n;
+    PRE3_HIP(hipMemcpy(d, Xw, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
+    PRE3_HIP(hipMemcpy(d + o_u, U, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice));
+    PRE3_HIP(hipMemcpy(d + o_start, &start, sizeof start, hipMemcpyHostToDevice));
+    const PnpSrc s = pnp_src(cam, undistort, n, (const double *)d, (const double *)(d + o_u));
+    hipLaunchKernelGGL(k_pnp_refine<false>, dim3(1), dim3(PNP_THREADS), 0, 0, s, (const int32_t *)nullptr, (const PnpCtl *)nullptr, n,
+                       (const pre3_pnp_result *)(d + o_start), n_iter, sigma_px, (pre3_pnp_refine_result *)(d + o_res));
+    PRE3_HIP(hipGetLastError());
+    PRE3_HIP(hipMemcpy(res, d + o_res, sizeof *res, hipMemcpyDeviceToHost));
+    return PRE3_OK;
+}
+
+int pre3_pnp_ransac_refined_seeded(int device, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, int n_hyp, uint64_t seed, uint64_t seq,
+                                   double thr_px, int32_t *draws_out, int32_t *support_out, int32_t *state_out, int32_t *inlier_out, pre3_pnp_result *hyp_res_out,
+                                   pre3_pnp_result *res, int n_iter, double sigma_px, pre3_pnp_refine_result *ref)
+{
+    const char *who = "pre3_pnp_ransac_refined_seeded";
+    PRE3_TRY(pnp_ransac_args(who, cam, n, Xw, U, n_hyp, thr_px, res));
+    PRE3_CHECK(ref != nullptr, PRE3_E_ARG, "%s: a null refinement result", who);
+    PRE3_TRY(pnp_refine_args(who, n_iter, sigma_px));
+    return pnp_ransac_run(who, device, cam, undistort, n, Xw, U, n_hyp, nullptr, true, seed, seq, thr_px, draws_out, support_out, state_out, inlier_out, hyp_res_out, res,
+                          n_iter, sigma_px, ref);
 }
 
 int pre3_pnp_bench(int device, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, int n_hyp, uint64_t seed, uint64_t seq, double thr_px,

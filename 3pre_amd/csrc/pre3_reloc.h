@@ -61,4 +61,75 @@ PRE3_RELOC_HD int reloc_select(const double x[7], int32_t sta, int32_t n_support
     return 1;
 }
 
+// ---- the refined form's process noise (pre3_relocalise_refined_seeded) ------------------------------------------------------
+// The covariance of the pose's u = [r*; q*] (cov7, pre3_pnpref.h) carried through reloc_select to the covariance of the increment the prediction takes:
+//   Pn = Jd cov7 Jd',  Jd = blkdiag(R(q)', L(conj q) / |q|^2) at x_k_k's q,  (M + M') / 2
+// The hemisphere flip negates Jd's lower block and leaves Pn alone.  The work is cut into items of one entry each, which k_predict deals over 49 lanes of
+// block 0 with barriers between the stages and the host walks in order; no product is fused into a sum, so both give the same bits.
+#if defined(__clang__)
+#define PRE3_RELOC_NOCONTRACT _Pragma("clang fp contract(off)")
+#else
+#define PRE3_RELOC_NOCONTRACT
+#endif
+enum { RELOC_NOISE_CALLER = 0, RELOC_NOISE_POSE = 1, RELOC_NOISE_POSE_FLOOR = 2, RELOC_NOISE_OWN = -1 };       // OWN: the context's own noise (the pose not taken)
+
+PRE3_RELOC_HD void reloc_noise_jd(const double x[7], double Jd[49])
+{
+    PRE3_RELOC_NOCONTRACT
+    double R[9];
+    {                                                                  // reloc_q2R's expressions, restated under this function's no-contraction rule
+        const double qa = x[3], qb = x[4], qc = x[5], qd = x[6];
+        const double aa = qa * qa, ab = 2 * qa * qb, ac = 2 * qa * qc, ad = 2 * qa * qd;
+        const double bb = qb * qb, bc = 2 * qb * qc, bd = 2 * qb * qd, cc = qc * qc, cd = 2 * qc * qd, dd = qd * qd;
+        R[0] = aa + bb - cc - dd; R[1] = bc - ad;           R[2] = bd + ac;
+        R[3] = bc + ad;           R[4] = aa - bb + cc - dd; R[5] = cd - ab;
+        R[6] = bd - ac;           R[7] = cd + ab;           R[8] = aa - bb - cc + dd;
+    }
+    for (int i = 0; i < 49; ++i) Jd[i] = 0.0;
+    for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 3; ++k) Jd[7 * i + k] = R[3 * k + i];
+    const double a = x[3], b = -x[4], c = -x[5], d = -x[6];            // conj(q)
+    const double n2 = x[3] * x[3] + x[4] * x[4] + x[5] * x[5] + x[6] * x[6];
+    const double Lq[16] = { a, -b, -c, -d,  b, a, -d, c,  c, d, a, -b,  d, -c, b, a };
+    for (int i = 0; i < 4; ++i)
+        for (int k = 0; k < 4; ++k) Jd[7 * (3 + i) + 3 + k] = Lq[4 * i + k] / n2;
+}
+// entry t = 7 i + k of Jd C, of (Jd C) Jd', and of the symmetrised result
+PRE3_RELOC_HD double reloc_noise_left(const double *Jd, const double *C, int t)
+{
+    PRE3_RELOC_NOCONTRACT
+    const int i = t / 7, k = t % 7;
+    double s = 0.0;
+    for (int q = 0; q < 7; ++q) s = s + Jd[7 * i + q] * C[7 * q + k];
+    return s;
+}
+PRE3_RELOC_HD double reloc_noise_right(const double *T1, const double *Jd, int t)
+{
+    PRE3_RELOC_NOCONTRACT
+    const int i = t / 7, k = t % 7;
+    double s = 0.0;
+    for (int q = 0; q < 7; ++q) s = s + T1[7 * i + q] * Jd[7 * k + q];
+    return s;
+}
+PRE3_RELOC_HD double reloc_noise_sym(const double *M, int t) { PRE3_RELOC_NOCONTRACT return (M[t] + M[7 * (t % 7) + t / 7]) / 2; }
+// PRE3_RELOC_NOISE_POSE_FLOOR: the caller's block added entry by entry, one fp64 addition each
+PRE3_RELOC_HD double reloc_noise_floor(double pose, double caller) { PRE3_RELOC_NOCONTRACT return pose + caller; }
+
+PRE3_RELOC_HD void reloc_noise_from_pose(const double x[7], const double cov7[49], double Pn[49])
+{
+    double Jd[49], T1[49], M[49];
+    reloc_noise_jd(x, Jd);
+    for (int t = 0; t < 49; ++t) T1[t] = reloc_noise_left(Jd, cov7, t);
+    for (int t = 0; t < 49; ++t) M[t] = reloc_noise_right(T1, Jd, t);
+    for (int t = 0; t < 49; ++t) Pn[t] = reloc_noise_sym(M, t);
+}
+
+// which noise the refined form's prediction uses: the pose's covariance needs the pose taken and a refinement that left one (ref_sta 1 or 2)
+PRE3_RELOC_HD int reloc_noise_rule(bool taken, int32_t noise, int32_t ref_sta)
+{
+    if (!taken) return RELOC_NOISE_OWN;
+    if (noise == RELOC_NOISE_CALLER || !(ref_sta == 1 || ref_sta == 2)) return RELOC_NOISE_CALLER;
+    return noise == RELOC_NOISE_POSE ? RELOC_NOISE_POSE : RELOC_NOISE_POSE_FLOOR;
+}
+
 }  // namespace pre3

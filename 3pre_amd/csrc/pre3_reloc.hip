@@ -8,6 +8,8 @@
 //                   scan's pixel, the matches with a finite point compacted once more into Xw / U; the two counts left in device words
 //   k_pnp_draw, k_pnp_hyp, k_pnp_select, k_pnp_solve (pre3_pnp.hip) with the count read on the device
 //   k_predict       US = PredictUReloc, NS = PnReloc (pre3_geom.hip): u and Pn under reloc_select (pre3_reloc.h)
+// pre3_relocalise_refined_seeded queues the same with k_pnp_refine (pre3_pnp.hip) between the refit and the prediction, whose tags
+// are then PredictURelocRef / PnRelocRef: the refinement's u and, by the caller's mode, its covariance as the prediction's noise.
 // k_reloc_corr is bound by its dependent loads (partials -> scan position; type -> offset -> state) and the sincos of an inverse-depth point, not by
 // HBM or the vector pipes: a few hundred landmarks, one pass of 512.
 #include <cmath>
@@ -29,9 +31,12 @@ constexpr int RC_T = 512, RC_NW = RC_T / 64;
 // what goes back to the host sits in front of the block's second half, in this order: header, ctl, res, pairs, flags
 struct RelocHdr { int32_t n_matches, n_corr, taken, pad; double u[7], pad2; };
 struct Pn49 { double v[49]; };
+// the refined form's own block at the end of the work block: what k_pnp_refine and its prediction leave, back in a second transfer in front of the one wait
+struct RelocRefBlk { pre3_pnp_refine_result ref; double Pn[49]; int32_t noise_taken, pad; };
+static_assert(sizeof(pre3_reloc_refined_result) == sizeof(pre3_reloc_result) + sizeof(RelocRefBlk), "pre3_reloc_refined_result is the base and the refined form's block");
 
 struct RelocLayout {
-    size_t o_xw, o_u, o_mask, o_hdr, o_ctl, o_res, o_pairs, o_flag, o_back_end, o_pn, o_draws, o_sup, o_sta, o_dsum, o_idx, o_hyp, total;
+    size_t o_xw, o_u, o_mask, o_hdr, o_ctl, o_res, o_pairs, o_flag, o_back_end, o_pn, o_draws, o_sup, o_sta, o_dsum, o_idx, o_hyp, o_ref, total;
     explicit RelocLayout(int cap)
     {
         const size_t n = (size_t)cap, H = PNP_MAX_HYP;
@@ -41,7 +46,8 @@ struct RelocLayout {
         o_flag = o_pairs + up16(sizeof(int32_t) * 2 * n); o_back_end = o_flag + up16(sizeof(int32_t) * n);
         o_pn = o_back_end; o_draws = o_pn + up16(sizeof(double) * 49); o_sup = o_draws + up16(sizeof(int32_t) * 6 * H); o_sta = o_sup + up16(sizeof(int32_t) * H);
         o_dsum = o_sta + up16(sizeof(int32_t) * H); o_idx = o_dsum + up16(sizeof(double) * H); o_hyp = o_idx + up16(sizeof(int32_t) * n);
-        total = o_hyp + up16(sizeof(pre3_pnp_result) * H);
+        o_ref = o_hyp + up16(sizeof(pre3_pnp_result) * H);
+        total = o_ref + up16(sizeof(RelocRefBlk));
     }
 };
 
@@ -117,28 +123,19 @@ int reloc_alloc(pre3_ctx *c)
     const int cap = c->capN < RELOC_MAX_N ? c->capN : RELOC_MAX_N;
     const RelocLayout L(cap);
     PRE3_TRY(c->mem.fixed.dev(&c->reloc_dev, L.total, Zero::sync()));
-    PRE3_TRY(c->mem.fixed.pin(&c->reloc_host, L.o_back_end - L.o_hdr, PIN_DEFAULT));
+    PRE3_TRY(c->mem.fixed.pin(&c->reloc_host, up16(L.o_back_end - L.o_hdr) + sizeof(RelocRefBlk), PIN_DEFAULT));
     c->reloc_cap = cap;
     return PRE3_OK;
 }
 
-}  // namespace pre3
+namespace {
 
-using namespace pre3;
+// the refined form's arguments; null: pre3_relocalise_seeded as it stands
+struct RelocRefine { int n_iter; double sigma_px; int noise; };
 
-extern "C" {
-
-int pre3_reloc_limits(int32_t out[2])
+int relocalise_run(const char *who, pre3_ctx *c, double thresh, int n_hyp, uint64_t seed, uint64_t seq, double thr_px, int undistort, int min_support,
+                   const RelocRefine *rf, const double *Pn_reloc, pre3_reloc_result *res_out, RelocRefBlk *ref_out, int32_t *pairs_out, int32_t *inlier_out)
 {
-    PRE3_CHECK(out != nullptr, PRE3_E_ARG, "pre3_reloc_limits: null output");
-    out[0] = RELOC_MAX_N; out[1] = PNP_MAX_HYP;
-    return PRE3_OK;
-}
-
-int pre3_relocalise_seeded(pre3_ctx *c, double thresh, int n_hyp, uint64_t seed, uint64_t seq, double thr_px, int undistort, int min_support,
-                           const double *Pn_reloc, pre3_reloc_result *res_out, int32_t *pairs_out, int32_t *inlier_out)
-{
-    const char *who = "pre3_relocalise_seeded";
     PRE3_CHECK(c != nullptr, PRE3_E_ARG, "%s: null context", who);
     // every refusal comes before the scope: a refused call queues nothing and leaves deferred and pending work where it was
     PRE3_CHECK(c->N >= PNP_MIN_N, PRE3_E_ARG, "%s: a map of %d landmarks, EPnP needs %d", who, c->N, PNP_MIN_N);
@@ -150,6 +147,11 @@ int pre3_relocalise_seeded(pre3_ctx *c, double thresh, int n_hyp, uint64_t seed,
     PRE3_CHECK(std::isfinite(thr_px) && thr_px > 0, PRE3_E_ARG, "%s: thr_px must be positive and finite", who);
     PRE3_CHECK(std::isfinite(thresh) && thresh > 0, PRE3_E_ARG, "%s: thresh must be positive and finite", who);
     PRE3_CHECK(min_support >= RELOC_MIN_SUPPORT, PRE3_E_ARG, "%s: min_support is %d, a pose needs at least %d inliers", who, min_support, RELOC_MIN_SUPPORT);
+    if (rf != nullptr) {
+        PRE3_CHECK(rf->n_iter >= 0 && rf->n_iter <= PRE3_PNP_REFINE_MAX_ITER, PRE3_E_ARG, "%s: %d iterations, 0 .. %d are run", who, rf->n_iter, PRE3_PNP_REFINE_MAX_ITER);
+        PRE3_CHECK(std::isfinite(rf->sigma_px) && rf->sigma_px >= 0, PRE3_E_ARG, "%s: sigma_px must be finite and not negative", who);
+        PRE3_CHECK(rf->noise >= PRE3_RELOC_NOISE_CALLER && rf->noise <= PRE3_RELOC_NOISE_POSE_FLOOR, PRE3_E_ARG, "%s: noise mode %d, 0 .. 2 exist", who, rf->noise);
+    }
     PRE3_CHECK(Pn_reloc != nullptr, PRE3_E_ARG, "%s: null Pn_reloc", who);
     PRE3_TRY(process_noise_check(who, Pn_reloc));
     PRE3_CHECK(c->have_cam && c->cam.f > 0, PRE3_E_ARG, "%s: camera not set", who);
@@ -185,13 +187,21 @@ int pre3_relocalise_seeded(pre3_ctx *c, double thresh, int n_hyp, uint64_t seed,
     PRE3_TRY(launch_pnp_ransac_dev(r, &c->cam, undistort, seed, seq, c->stream));
 
     const PredictUReloc ur{ res, c->x_kk, min_support, hdr->u, &hdr->taken };
-    PRE3_TRY(launch_predict_reloc(c, ur, a.pn_out));
+    RelocRefBlk *rb = (RelocRefBlk *)(d + L.o_ref);
+    if (rf != nullptr) {
+        PRE3_TRY(launch_pnp_refine_dev(r, &c->cam, undistort, rf->n_iter, rf->sigma_px, &rb->ref, c->stream));
+        PRE3_TRY(launch_predict_reloc_refined(c, ur, a.pn_out, &rb->ref, rf->noise, rb->Pn, &rb->noise_taken));
+    } else {
+        PRE3_TRY(launch_predict_reloc(c, ur, a.pn_out));
+    }
     c->x_valid[PRE3_X_K_KM1] = true; c->p_which = PRE3_X_K_KM1; c->hp_all_valid = false;
-    if (res_out == nullptr && pairs_out == nullptr && inlier_out == nullptr) return PRE3_OK;       // nothing is synchronised
+    if (res_out == nullptr && ref_out == nullptr && pairs_out == nullptr && inlier_out == nullptr) return PRE3_OK;       // nothing is synchronised
 
-    // the one wait: header, ctl and refit, and the two lists when they are asked for, in one transfer
+    // the one wait: header, ctl and refit, and the two lists when they are asked for, in one transfer (the refined form's block in a second one)
     const size_t back = (pairs_out != nullptr || inlier_out != nullptr ? L.o_flag + sizeof(int32_t) * (size_t)N : L.o_pairs) - L.o_hdr;
     PRE3_HIP(hipMemcpyAsync(c->reloc_host, d + L.o_hdr, back, hipMemcpyDeviceToHost, c->stream));
+    char *ref_host = c->reloc_host + up16(L.o_back_end - L.o_hdr);
+    if (rf != nullptr) PRE3_HIP(hipMemcpyAsync(ref_host, rb, sizeof(RelocRefBlk), hipMemcpyDeviceToHost, c->stream));
     PRE3_TRY(stream_drain(c, who));
     auto at = [&](size_t o) { return (const char *)c->reloc_host + (o - L.o_hdr); };
     RelocHdr hh;
@@ -205,9 +215,40 @@ int pre3_relocalise_seeded(pre3_ctx *c, double thresh, int n_hyp, uint64_t seed,
         memcpy(res_out->u, hh.u, sizeof res_out->u);
         res_out->n_matches = hh.n_matches; res_out->n_corr = hh.n_corr; res_out->winner = ctl[0]; res_out->taken = hh.taken;
     }
+    if (ref_out && rf != nullptr) memcpy(ref_out, ref_host, sizeof *ref_out);
     if (pairs_out) memcpy(pairs_out, at(L.o_pairs), sizeof(int32_t) * 2 * (size_t)hh.n_matches);
     if (inlier_out) memcpy(inlier_out, at(L.o_flag), sizeof(int32_t) * (size_t)hh.n_corr);
     return PRE3_OK;
+}
+
+}  // namespace
+
+}  // namespace pre3
+
+using namespace pre3;
+
+extern "C" {
+
+int pre3_reloc_limits(int32_t out[2])
+{
+    PRE3_CHECK(out != nullptr, PRE3_E_ARG, "pre3_reloc_limits: null output");
+    out[0] = RELOC_MAX_N; out[1] = PNP_MAX_HYP;
+    return PRE3_OK;
+}
+
+int pre3_relocalise_seeded(pre3_ctx *c, double thresh, int n_hyp, uint64_t seed, uint64_t seq, double thr_px, int undistort, int min_support,
+                           const double *Pn_reloc, pre3_reloc_result *res_out, int32_t *pairs_out, int32_t *inlier_out)
+{
+    return relocalise_run("pre3_relocalise_seeded", c, thresh, n_hyp, seed, seq, thr_px, undistort, min_support, nullptr, Pn_reloc, res_out, nullptr, pairs_out, inlier_out);
+}
+
+int pre3_relocalise_refined_seeded(pre3_ctx *c, double thresh, int n_hyp, uint64_t seed, uint64_t seq, double thr_px, int undistort, int min_support, int n_iter,
+                                   double sigma_px, int noise, const double *Pn_reloc, pre3_reloc_refined_result *res_out, int32_t *pairs_out, int32_t *inlier_out)
+{
+    const RelocRefine rf{ n_iter, sigma_px, noise };
+    // (the refined result is the base and, behind it, the block the launches leave: relocalise_run's static_assert)
+    return relocalise_run("pre3_relocalise_refined_seeded", c, thresh, n_hyp, seed, seq, thr_px, undistort, min_support, &rf, Pn_reloc,
+                          res_out != nullptr ? &res_out->base : nullptr, res_out != nullptr ? (RelocRefBlk *)&res_out->ref : nullptr, pairs_out, inlier_out);
 }
 
 }  // extern "C"

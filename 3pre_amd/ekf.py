@@ -740,6 +740,38 @@ class EkfFilter:
         return dict(pnp=vo._pnp_dict(res.pnp), u=np.array(res.u), n_matches=nm, n_corr=nc, winner=int(res.winner), taken=int(res.taken),
                     match_idx=pairs[:nm].T.copy(), inliers=inl[:nc].copy())
 
+    RELOC_NOISE = {"caller": 0, "pose": 1, "pose_floor": 2}
+
+    def relocalise_refined_seeded(self, seed, seq=0, thresh=1.5, n_hyp=200, thr_px=2.0, undistort=True, min_support=12, n_iter=5, sigma_px=0.0, noise="pose",
+                                  Pn=None, wait=True):
+        """relocalise_seeded with the pose refined by Gauss-Newton on the reprojection error between the refit and the prediction (DESIGN.md section 37;
+        vo.pnp_refine over the winner's inliers, n_iter steps), and the prediction's noise from the refined pose's own covariance.  Whether the pose is
+        taken is relocalise_seeded's rule on the EPnP refit; u comes from the refinement when it took its pose (ref.sta == 1), else from the refit.
+        noise: "caller" -- Pn, as relocalise_seeded; "pose" -- the refinement's covariance carried to the increment (Pn where the refinement left none);
+        "pose_floor" -- the same plus Pn entry by entry.  The covariance treats the map points as exact (pixel noise only: sigma_px, or the a-posteriori
+        estimate when 0) and is optimistic on a real map: "pose_floor" is the form to use there.
+        wait=True: relocalise_seeded's dict plus ref (vo.pnp_refine's dict), Pn (7, 7) the noise the prediction used and noise_taken ("caller", "pose",
+        "pose_floor", or "own": the pose not taken).  wait=False: None at once.  Pre3Error as relocalise_seeded, and -1 for n_iter outside 0 .. 10, a
+        negative or non-finite sigma_px."""
+        from . import vo
+        Pn = f64(self.RELOC_PN if Pn is None else Pn)
+        assert Pn.shape == (7, 7), "Pn is 7 x 7 over [dX(3); dq(4)]"
+        mode = self.RELOC_NOISE[noise] if isinstance(noise, str) else int(noise)
+        args = (self._ctx, float(thresh), int(n_hyp), int(seed), int(seq), float(thr_px), int(bool(undistort)), int(min_support), int(n_iter), float(sigma_px),
+                mode, dptr(Pn))
+        if not wait:
+            check(lib.pre3_relocalise_refined_seeded(*args, None, None, None))
+            return None
+        N = max(self.N, 1)
+        res, pairs, inl = vo.RelocRefinedResult(), np.zeros((N, 2), np.int32), np.zeros(N, np.int32)
+        check(lib.pre3_relocalise_refined_seeded(*args, C.byref(res), dptr(pairs), dptr(inl)))
+        b = res.base
+        nm, nc = int(b.n_matches), int(b.n_corr)
+        names = {v: k for k, v in self.RELOC_NOISE.items()}
+        return dict(pnp=vo._pnp_dict(b.pnp), u=np.array(b.u), n_matches=nm, n_corr=nc, winner=int(b.winner), taken=int(b.taken),
+                    match_idx=pairs[:nm].T.copy(), inliers=inl[:nc].copy(), ref=vo._pnp_refine_dict(res.ref), Pn=np.array(res.Pn).reshape(7, 7),
+                    noise_taken=names.get(int(res.noise_taken), "own"))
+
     def set_process_noise(self, Pn=None):
         """predict_state_and_covariance.m:98-102: the 7 x 7 process noise Pn of every prediction this filter makes from now on (ekf_prediction, step*,
         ekf_prediction_pair_seeded); None returns to the reference's constant.  Must be finite, exactly symmetric and without a negative diagonal

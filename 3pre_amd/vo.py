@@ -462,6 +462,53 @@ def pnp_ransac_seeded(Xw, U, cam, n_hyp, thr_px, seed, seq=0, undistort=False, h
     return _pnp_ransac_dict(sup, sta, inl, hyp, r, dr)
 
 
+# ---- the pose refined by Gauss-Newton on the reprojection error, with its covariance -------------------------------------------
+class PnpRefineResult(C.Structure):
+    """pre3_pnp_refine_result (include/pre3.h)"""
+    _fields_ = [("R", C.c_double * 9), ("T", C.c_double * 3), ("u", C.c_double * 7), ("cost", C.c_double * 11), ("cov6", C.c_double * 36), ("cov", C.c_double * 49),
+                ("sigma2", C.c_double), ("sta", C.c_int32), ("n", C.c_int32), ("n_iter", C.c_int32), ("pad", C.c_int32)]
+
+
+class RelocRefinedResult(C.Structure):
+    """pre3_reloc_refined_result (include/pre3.h): EkfFilter.relocalise_refined_seeded's result block"""
+    _fields_ = [("base", RelocResult), ("ref", PnpRefineResult), ("Pn", C.c_double * 49), ("noise_taken", C.c_int32), ("pad", C.c_int32)]
+
+
+def _pnp_refine_dict(r):
+    return dict(R=np.array(r.R).reshape(3, 3), T=np.array(r.T), u=np.array(r.u), cost=np.array(r.cost), cov6=np.array(r.cov6).reshape(6, 6),
+                cov=np.array(r.cov).reshape(7, 7), sigma2=float(r.sigma2), sta=int(r.sta), n=int(r.n), n_iter=int(r.n_iter))
+
+
+def pnp_refine(Xw, U, cam, R0, T0, n_iter=5, sigma_px=0.0, undistort=False, device=0):
+    """Gauss-Newton on the reprojection error from the pose (R0, T0) (Xc = R Xw + T): exactly n_iter (0 .. 10) plain steps over the six pose parameters,
+    the refined pose taken iff everything stayed finite, every point is in front of it and the cost fell; otherwise the input pose is kept.  Returns
+    dict(R, T, u, cost (11,; r'r in px^2 before each step and after the last, NaN beyond n_iter), cov6 (6, 6) over (tau, omega), cov (7, 7) of u,
+    sigma2, sta (1 refined pose taken; 2 input pose kept; -1 no covariance: R, T, u the input's, the covariances NaN), n, n_iter).  The covariance is
+    sigma2 (J'J)^-1 with sigma2 = sigma_px^2, or cost / (2 n - 6) when sigma_px == 0.  It treats the 3-D points as exact -- pixel noise only -- and is
+    optimistic for landmarks of a map."""
+    xw, uv, c = _pnp_args(Xw, U, cam)
+    r0, t0 = f64(R0).reshape(3, 3), f64(T0).reshape(3)
+    r = PnpRefineResult()
+    check(lib.pre3_pnp_refine(int(device), C.byref(c), int(bool(undistort)), xw.shape[0], dptr(xw), dptr(uv), dptr(r0), dptr(t0), int(n_iter), float(sigma_px),
+                              C.byref(r)))
+    return _pnp_refine_dict(r)
+
+
+def pnp_ransac_refined_seeded(Xw, U, cam, n_hyp, thr_px, seed, seq=0, undistort=False, hyp_results=False, n_iter=5, sigma_px=0.0, device=0):
+    """pnp_ransac_seeded with pnp_refine behind it on the device, over the winner's inliers from the refit's pose, still one host wait: the dict of
+    pnp_ransac_seeded (bit-equal) plus ref, pnp_refine's dict (sta = 0 when the refit's sta is not 1 or 2)"""
+    xw, uv, c = _pnp_args(Xw, U, cam)
+    dr = np.zeros((max(int(n_hyp), 0), 6), np.int32)
+    sup, sta, inl, hyp, r = _pnp_ransac_out(xw.shape[0], dr.shape[0], hyp_results)
+    ref = PnpRefineResult()
+    check(lib.pre3_pnp_ransac_refined_seeded(int(device), C.byref(c), int(bool(undistort)), xw.shape[0], dptr(xw), dptr(uv), int(n_hyp), int(seed), int(seq),
+                                             float(thr_px), dptr(dr), dptr(sup), dptr(sta), dptr(inl), None if hyp is None else C.byref(hyp), C.byref(r),
+                                             int(n_iter), float(sigma_px), C.byref(ref)))
+    d = _pnp_ransac_dict(sup, sta, inl, hyp, r, dr)
+    d["ref"] = _pnp_refine_dict(ref)
+    return d
+
+
 def vo_pair_pnp_seeded(prev, cur, seed, cam, seq=0, thresh=1.5, undistort=False):
     """vo_pair_seeded with RANSAC_CALC_VER2.m:191 behind it on the device: the EPnP of efficient_pnp over the pair's inliers --
     prev's range points (pset1) against cur's PIXELS, no depth of cur -- still one host wait.  The dict of vo_pair_seeded, bit for bit, plus pix2

@@ -1173,6 +1173,64 @@ PRE3_API int pre3_relocalise_seeded(pre3_ctx *ctx, double thresh, int n_hyp, uin
 /* out = { the largest N, the largest n_hyp } the call takes */
 PRE3_API int pre3_reloc_limits(int32_t out[2]);
 
+/* ---- the PnP pose refined by Gauss-Newton, its covariance, and relocalising under it ---------------------------------------------
+ * The project's own follow-up of sections 35 and 36.  EPnP minimises a linearised quantity, not the reprojection error it is scored by; the reference
+ * puts a Gauss-Newton stage behind the same solver (aux_code/EPnP_matlab/EPnP/efficient_pnp_gauss.m:191-225) and keeps its result "if Gauss Newton
+ * improves results" -- over the betas against control-point distances, another quantity and without a covariance; only its taking rule is followed.
+ * Here: Gauss-Newton on the reprojection error over the six pose parameters, d = (tau, omega) on the camera side (R <- E R, T <- E T + tau,
+ * E = exp([omega]x)), exactly n_iter plain steps over a fixed point set, no damping and no early exit; cost[k] = r'r (px^2, undistorted pixels when
+ * undistort = 1) before step k and cost[n_iter] after the last.  The refined pose is taken iff n_iter >= 1, every intermediate is finite, every point has
+ * z > 0 at the refined pose and cost[n_iter] < cost[0]; otherwise the input pose is kept.  cov6 = sigma2 (J'J)^-1 at the pose the call ends on, in
+ * (tau, omega); sigma2 = sigma_px^2, or cost / (2 n - 6) when sigma_px == 0.  cov = Jm cov6 Jm' is the covariance of u (rank 6; null vector [0; q*]).
+ * THE COVARIANCE TREATS THE 3-D POINTS AS EXACT: it carries pixel noise only, neither the landmarks' own uncertainty nor their correlation with the
+ * pose.  Like pre3_icp_cov's it is optimistic; on a real map use PRE3_RELOC_NOISE_POSE_FLOOR.
+ * All fp64, every sum over the points the fixed tree of pre3_epnp: bit-equal from run to run. */
+#define PRE3_PNP_REFINE_MAX_ITER 10
+typedef struct pre3_pnp_refine_result {
+    double R[9], T[3];      /* the pose the call ends on: refined (sta 1) or the input's (every other sta) */
+    double u[7];            /* its [-R'T; R2q(R')]; with sta 0 or -1 the input's */
+    double cost[11];        /* r'r before step k, after the last at [n_iter]; NaN beyond n_iter (all NaN with sta 0) */
+    double cov6[36];        /* row-major, (tau, omega); NaN with sta 0 or -1 */
+    double cov[49];         /* row-major, of u; NaN with sta 0 or -1 */
+    double sigma2;          /* the s^2 the covariances carry; NaN with sta 0 or -1 */
+    int32_t sta;            /* 1 refined pose taken, covariance valid; 2 input pose kept, covariance valid; -1 no covariance (a pivot of J'J at or below
+                               7 eps times its diagonal entry, a non-finite coordinate or result, a depth <= 0 at the pose the call ends on); 0 not computed
+                               (the pose fed in has sta outside {1, 2}, or fewer than six points) */
+    int32_t n;              /* points the sums ran over */
+    int32_t n_iter;
+    int32_t pad;
+} pre3_pnp_refine_result;
+/* Stateless, host in and host out, one launch, synchronises.  Xw, U, undistort as pre3_epnp; R0[9] row-major, T0[3]: the starting pose.
+ * PRE3_E_ARG: pre3_epnp's refusals, n_iter outside 0 .. 10, sigma_px negative or not finite, a null R0 or T0. */
+PRE3_API int pre3_pnp_refine(int device, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, const double *R0, const double *T0,
+                             int n_iter, double sigma_px, pre3_pnp_refine_result *res);
+/* pre3_pnp_ransac_seeded's four launches, then the refinement over the winner's inlier list from the refit's result block, both read on the device.
+ * Still ONE host wait.  Every output shared with pre3_pnp_ransac_seeded is bit-equal to that call's; ref is bit-equal to pre3_pnp_refine on the
+ * correspondences gathered at inlier_out, started from res->R, res->T (res->sta outside {1, 2}: ref->sta = 0). */
+PRE3_API int pre3_pnp_ransac_refined_seeded(int device, const pre3_cam *cam, int undistort, int n, const double *Xw, const double *U, int n_hyp, uint64_t seed,
+                                            uint64_t seq, double thr_px, int32_t *draws_out, int32_t *support_out, int32_t *state_out, int32_t *inlier_out,
+                                            pre3_pnp_result *hyp_res_out, pre3_pnp_result *res, int n_iter, double sigma_px, pre3_pnp_refine_result *ref);
+/* pre3_relocalise_seeded with the refinement between the refit and the prediction (one more launch, still one wait, none with every output NULL).
+ * Whether the pose is taken: pre3_relocalise_seeded's rule on the EPnP refit, unchanged.  u: from ref.u when ref.sta == 1, else from pnp.u.  The noise
+ * of a taken pose: */
+#define PRE3_RELOC_NOISE_CALLER 0      /* Pn_reloc, as pre3_relocalise_seeded */
+#define PRE3_RELOC_NOISE_POSE 1        /* Jd ref.cov Jd', Jd = blkdiag(R(q)', L(conj q) / |q|^2) at x_k_k's q -- ref.cov carried through the rule that makes
+                                          the increment of u -- when ref.sta is 1 or 2; else Pn_reloc */
+#define PRE3_RELOC_NOISE_POSE_FLOOR 2  /* the same plus Pn_reloc entry by entry, one fp64 addition each: the caller's block is a floor */
+/* Not taken: the identity u and the context's own noise.  Afterwards the context is bit-identical to the chain pre3_get_landmarks, pre3_siftmatch_f64,
+ * the gather, pre3_pnp_ransac_refined_seeded, the two rules on the host, pre3_set_process_noise(Pn) when taken, pre3_predict(u), the setting restored.
+ * Refusals: pre3_relocalise_seeded's, and PRE3_E_ARG for n_iter outside 0 .. 10, sigma_px negative or not finite, noise outside 0 .. 2. */
+typedef struct pre3_reloc_refined_result {
+    pre3_reloc_result base;          /* as pre3_relocalise_seeded's, u the increment this call applied */
+    pre3_pnp_refine_result ref;
+    double Pn[49];                   /* the process noise the prediction used */
+    int32_t noise_taken;             /* its source: PRE3_RELOC_NOISE_CALLER, _POSE or _POSE_FLOOR; -1 the context's own (the pose not taken) */
+    int32_t pad;
+} pre3_reloc_refined_result;
+PRE3_API int pre3_relocalise_refined_seeded(pre3_ctx *ctx, double thresh, int n_hyp, uint64_t seed, uint64_t seq, double thr_px, int undistort, int min_support,
+                                            int n_iter, double sigma_px, int noise, const double *Pn_reloc /* [49] */, pre3_reloc_refined_result *res_out,
+                                            int32_t *pairs_out /* [2 * N], may be NULL */, int32_t *inlier_out /* [N], may be NULL */);
+
 /* ---- a10: sift/siftmatch.c:83-132,139-250 ------------------------------------------------------- */
 /* L1: ND x K1, L2: ND x K2, one descriptor per column (column-major, as mxGetData returns them).
  * pairs_out[2*K1] receives 1-based (k1,k2) doubles in increasing k1 exactly as the MEX writes them
